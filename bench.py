@@ -51,7 +51,33 @@ def parse():
     ap.add_argument("--stress", type=int, default=50000, help="clusters of the stress sub-record (0 = skip)")
     ap.add_argument("--no-host-api", action="store_true", help="skip the value_host_api pass")
     ap.add_argument("--verify", action="store_true", help="multi-rank runs: after the timed region, check the assembled map bit for bit against a single-rank pass of rank 0 over a 64^3 sub-grid (any backend), and report per-rank pass / gather / exchange ms")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last timed step computed to DIR/*.npy (rank 0): "
+                    "test_result.npy = rows of the [grid^3, 8] float32 test() result (all of them up to %d rows, else a fixed seeded sample "
+                    "of that many), query_index.npy = their row indices in the grid (float64)" % DUMP_MAX_ROWS)
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+# --dump-outputs: at most this many result rows (32 B each) + their float64 indices = 40 MiB
+DUMP_MAX_ROWS = 1 << 20
+
+
+def dump_outputs(out_dir, result):
+    """Write the [n, 8] float32 result of the last timed step (a torch tensor) to out_dir: every row when n <= DUMP_MAX_ROWS,
+    else a sorted sample of DUMP_MAX_ROWS rows drawn with a fixed seed, so that two runs with the same arguments dump the same rows."""
+    import numpy as np
+    import torch
+    n = result.shape[0]
+    if n <= DUMP_MAX_ROWS:
+        idx = np.arange(n, dtype=np.int64)
+    else:
+        idx = np.sort(np.random.default_rng(0).choice(n, DUMP_MAX_ROWS, replace=False))
+    rows = result[torch.from_numpy(idx).to(result.device)].cpu().numpy().astype(np.float32, copy=False)
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "test_result.npy"), rows)
+    np.save(os.path.join(out_dir, "query_index.npy"), idx.astype(np.float64))
 
 
 def self_launch(args):
@@ -246,6 +272,8 @@ def main():
         per_rank = [[float(v) for v in e.cpu()] for e in evs]
     else:
         per_rank = [[evals_rank, k4_ms / max(1, args.steps), float(host_replays)]]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, full if world > 1 else res)
 
     # ---- --verify (any backend, outside the timed region): per-rank phase times of one extra step, and the assembled map
     # against a single-rank pass of rank 0 over a 64^3 sub-grid, bit for bit
