@@ -124,6 +124,18 @@ def lib():
     L.gpis_ongpis_set_lazy_inverse.argtypes = [vp, C.c_int]
     L.gpis3_prepare_test.argtypes = [vp]
     L.gpis3_set_lazy_inverse.argtypes = [vp, C.c_int]
+    if hasattr(L, "gpis_mesh_create"):
+        L.gpis_mesh_create.restype = vp
+        L.gpis_mesh_create.argtypes = []
+        L.gpis_mesh_destroy.argtypes = [vp]
+        L.gpis_mesh_set_chunk.argtypes = [vp, C.c_int]
+        L.gpis_mesh_from_grid.argtypes = [vp, vp, C.c_int, ip, fp, fp, C.c_float, vp]
+        L.gpis3_extract_mesh.argtypes = [vp, vp, ip, fp, fp, C.c_float, vp]
+        L.gpis2_extract_contour.argtypes = [vp, vp, ip, fp, fp, C.c_float, vp]
+        L.gpis_mesh_counts.argtypes = [vp, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
+        L.gpis_mesh_get.argtypes = [vp, fp, ip, fp]
+        L.gpis_mesh_get_grid.argtypes = [vp, fp]
+        L.gpis_mesh_device.argtypes = [vp, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
     _lib = L
     return L
 
@@ -351,6 +363,22 @@ class GPisMap3:
         """Cross-check switch: keep the training side (factor, re-tiled factor) of every model after its inverse exists."""
         _check(self.L.gpis3_set_keep_factors(self.h, int(on)), "gpis3_set_keep_factors")
 
+    def extract_mesh(self, origin, step, shape, level=None, max_var=None, mesh=None):
+        """The map's level surface on the device (gpis3_extract_mesh): test() on the lattice origin + i * step of
+        shape (nx, ny, nz), marching tetrahedra at `level` (None: -fbias, the level of the map's surface points), test() on the
+        vertices.  Returns (verts [V,3] f32, faces [F,3] i32, rec [V,8] f32); cross(v1 - v0, v2 - v0) points to f >= level.
+        max_var drops every face with a vertex whose var_f (rec[:, 4]) is above it and the vertices no face uses.
+        mesh: a Mesh to hold the device result (reused across calls; default: one kept by this map)."""
+        m = mesh if mesh is not None else self._own_mesh()
+        m._extract(self.L.gpis3_extract_mesh, self.h, 3, origin, step, shape, level, "gpis3_extract_mesh")
+        v, f, r = m.get()
+        return _filter_var(v, f, r, 4, max_var)
+
+    def _own_mesh(self):
+        if getattr(self, "_mesh", None) is None:
+            self._mesh = Mesh()
+        return self._mesh
+
 
 class GPisMap:
     """Mirror of the reference's mexGPisMap command set ('update', 'test', 'reset') on the HIP path."""
@@ -391,6 +419,10 @@ class GPisMap:
         _check(rc, "gpis2_test")
         return res
 
+    def test_device(self, d_x_ptr, n, d_res_ptr, stream=0):
+        _check(self.L.gpis2_test_device(self.h, C.c_void_p(d_x_ptr), n, C.c_void_p(d_res_ptr), C.c_void_p(stream)),
+               "gpis2_test_device")
+
     def nodes(self):
         n = self.L.gpis2_get_nodes(self.h, None, 0)
         out = np.zeros((n, 7), dtype=np.float32)
@@ -409,6 +441,112 @@ class GPisMap:
 
     def set_pipeline(self, on=True):
         _check(self.L.gpis2_set_pipeline(self.h, 1 if on else 0), "gpis2_set_pipeline")
+
+    def extract_contour(self, origin, step, shape, level=None, max_var=None, mesh=None):
+        """The map's level contour on the device (gpis2_extract_contour), shape (nx, ny).  Returns (verts [V,2] f32,
+        segs [S,2] i32, rec [V,6] f32); the right-hand normal (dy, -dx) of a segment points to f >= level.  max_var: the
+        demo's filter on var_f (rec[:, 3])."""
+        if mesh is None:
+            if getattr(self, "_mesh", None) is None:
+                self._mesh = Mesh()
+            mesh = self._mesh
+        mesh._extract(self.L.gpis2_extract_contour, self.h, 2, origin, step, shape, level, "gpis2_extract_contour")
+        v, f, r = mesh.get()
+        return _filter_var(v, f, r, 3, max_var)
+
+
+def _filter_var(verts, prims, rec, slot, max_var):
+    """Drop every primitive with a vertex whose variance (rec[:, slot]) is above max_var, then the vertices no primitive uses
+    (order kept, primitives renumbered)."""
+    if max_var is None:
+        return verts, prims, rec
+    keep = np.all(rec[prims, slot] <= np.float32(max_var), axis=1) if prims.size else np.zeros(0, bool)
+    prims = prims[keep]
+    used = np.zeros(verts.shape[0], bool)
+    used[prims.ravel()] = True
+    remap = np.cumsum(used, dtype=np.int64) - 1
+    return verts[used], remap[prims].astype(np.int32), rec[used]
+
+
+class Mesh:
+    """Result holder of the surface extraction (gpis_mesh_*): device buffers reused across calls.  Kernel level:
+    from_grid() on any device-resident value grid."""
+
+    def __init__(self):
+        self.L = lib()
+        if self.L.gpis_device_count() < 1:
+            raise GpisError("no HIP device: gpismap_amd has no CPU fallback")
+        self.h = C.c_void_p(self.L.gpis_mesh_create())
+        if not self.h:
+            raise GpisError("gpis_mesh_create failed")
+        self.dim = 0
+        self.shape = None
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.gpis_mesh_destroy(self.h)
+            self.h = None
+
+    __del__ = close
+
+    def set_chunk(self, points):
+        """Lattice points per test() pass of a map-level extraction (0 = default 2^22; results do not depend on it)."""
+        _check(self.L.gpis_mesh_set_chunk(self.h, int(points)), "gpis_mesh_set_chunk")
+
+    @staticmethod
+    def _lattice_args(dim, origin, step, shape):
+        n = np.ascontiguousarray(shape, dtype=np.int32).ravel()
+        o = np.ascontiguousarray(origin, dtype=np.float32).ravel()
+        s = np.ascontiguousarray(step if np.ndim(step) else [step] * dim, dtype=np.float32).ravel()
+        if n.size != dim or o.size != dim or s.size != dim:
+            raise GpisError("lattice arguments must have %d entries" % dim)
+        return n, o, s
+
+    def _extract(self, fn, map_h, dim, origin, step, shape, level, what):
+        n, o, s = self._lattice_args(dim, origin, step, shape)
+        lv = float("nan") if level is None else float(level)
+        _check(fn(map_h, self.h, _p(n, C.c_int), _p(o), _p(s), lv, None), what)
+        self.dim, self.shape = dim, tuple(int(v) for v in n)
+
+    def from_grid(self, d_val_ptr, shape, origin, step, level, stream=0):
+        """Kernel level (gpis_mesh_from_grid): d_val_ptr = device address of prod(shape) float32 values, x fastest."""
+        dim = len(shape)
+        n, o, s = self._lattice_args(dim, origin, step, shape)
+        _check(self.L.gpis_mesh_from_grid(self.h, C.c_void_p(d_val_ptr), dim, _p(n, C.c_int), _p(o), _p(s), float(level),
+                                          C.c_void_p(stream)), "gpis_mesh_from_grid")
+        self.dim, self.shape = dim, tuple(int(v) for v in n)
+
+    def counts(self):
+        nv, npr = C.c_longlong(0), C.c_longlong(0)
+        _check(self.L.gpis_mesh_counts(self.h, C.byref(nv), C.byref(npr)), "gpis_mesh_counts")
+        return int(nv.value), int(npr.value)
+
+    def get(self, records=None):
+        """(verts [V,dim], prims [P,dim], rec [V,2(1+dim)] or None): host copies of the last result."""
+        nv, npr = self.counts()
+        d = max(self.dim, 2)
+        v = np.zeros((nv, d), dtype=np.float32)
+        p = np.zeros((npr, d), dtype=np.int32)
+        want = self.has_records() if records is None else records
+        r = np.zeros((nv, 2 * (1 + d)), dtype=np.float32) if want else None
+        _check(self.L.gpis_mesh_get(self.h, _p(v), _p(p, C.c_int), _p(r) if r is not None else None), "gpis_mesh_get")
+        return v, p, r
+
+    def has_records(self):
+        dv = C.c_void_p(0)
+        _check(self.L.gpis_mesh_device(self.h, None, None, C.byref(dv)), "gpis_mesh_device")
+        return bool(dv.value)
+
+    def grid(self):
+        """The value grid (f) of the last map-level extraction, shape[::-1] (x fastest)."""
+        out = np.zeros(int(np.prod(self.shape)), dtype=np.float32)
+        _check(self.L.gpis_mesh_get_grid(self.h, _p(out)), "gpis_mesh_get_grid")
+        return out.reshape(self.shape[::-1])
+
+    def device_ptrs(self):
+        a, b, c = C.c_void_p(0), C.c_void_p(0), C.c_void_p(0)
+        _check(self.L.gpis_mesh_device(self.h, C.byref(a), C.byref(b), C.byref(c)), "gpis_mesh_device")
+        return a.value or 0, b.value or 0, c.value or 0
 
 
 class ObsGP:

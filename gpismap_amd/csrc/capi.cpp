@@ -1,4 +1,5 @@
 // C-ABI (include/gpismap_amd.h) over the C++ classes.  Nothing throws across it.
+#include <cmath>
 #include <cstring>
 #include <new>
 #include <vector>
@@ -6,6 +7,7 @@
 #include "../../include/GPisMap3.h"
 #include "../../include/gpismap_amd.h"
 #include "map_query.h"
+#include "mesh.h"
 #include "obsgp.h"
 #include "ongpis.h"
 
@@ -42,6 +44,8 @@ int gpis3_impl_apply_frame(GPisMap3* g, const void* buf, long long bytes);
 int gpis2_impl_device(GPisMap* m);
 int gpis2_impl_sync(GPisMap* m);
 void gpis2_impl_set_pipeline(GPisMap* m, int on);
+int gpis3_impl_extract(GPisMap3* g, MeshExtractor& me, const int* n3, const float* origin3, const float* step3, float level, void* stream);
+int gpis2_impl_extract(GPisMap* g, MeshExtractor& me, const int* n2, const float* origin2, const float* step2, float level, void* stream);
 
 namespace gpis { int selftest_ranged_arith(unsigned long long seed, int blocks, int per_thread, int mode, unsigned long long* mismatches); }
 extern "C" {
@@ -383,6 +387,95 @@ int gpis_ongpis_last_ms(void* s, float* t, float* e) {
     DeviceScope dev_scope_(h->device);
     if (t) *t = h->st.last_train_ms;
     if (e) *e = h->st.last_eval_ms;
+    return GPIS_OK;
+}
+
+// ---- surface extraction ---------------------------------------------------------------------------------------
+void* gpis_mesh_create(void) {
+    if (gpis_device_count() < 1) { fprintf(stderr, "[gpismap_amd] no HIP device\n"); return nullptr; }
+    MeshExtractor* me = new (std::nothrow) MeshExtractor();
+    if (me && !me->own) { delete me; return nullptr; }
+    return me;
+}
+void gpis_mesh_destroy(void* mesh) { delete (MeshExtractor*)mesh; }
+int gpis_mesh_set_chunk(void* mesh, int points) {
+    if (!mesh || points < 0) return GPIS_ERR_ARG;
+    ((MeshExtractor*)mesh)->chunk = points ? points : (1 << 22);
+    return GPIS_OK;
+}
+// (the result is dropped only once the arguments passed: an argument error leaves the previous one readable)
+static int mesh_args(void* mesh, int dim, const int* n, const float* origin, const float* step) {
+    if (!mesh) return GPIS_ERR_ARG;
+    long long np = 0;
+    return mesh_check_lattice(dim, n, origin, step, &np);
+}
+int gpis_mesh_from_grid(void* mesh, const float* d_val, int dim, const int* n, const float* origin, const float* step, float level,
+                        void* stream) {
+    if (int rc = mesh_args(mesh, dim, n, origin, step)) return rc;
+    if (!d_val || !std::isfinite(level)) return GPIS_ERR_ARG;
+    MeshExtractor& me = *(MeshExtractor*)mesh;
+    DeviceScope ds(me.device);
+    me.clear_result();
+    try {
+        const int rc = me.from_grid(d_val, dim, n, origin, step, level, stream ? (hipStream_t)stream : me.own);
+        if (rc != GPIS_OK) me.clear_result();
+        return rc;
+    } catch (...) { me.clear_result(); return GPIS_ERR_STATE; }
+}
+int gpis3_extract_mesh(void* m, void* mesh, const int* n3, const float* origin3, const float* step3, float level, void* stream) {
+    if (!m) return GPIS_ERR_ARG;
+    if (int rc = mesh_args(mesh, 3, n3, origin3, step3)) return rc;
+    if (std::isinf(level)) return GPIS_ERR_ARG;
+    MeshExtractor& me = *(MeshExtractor*)mesh;
+    me.clear_result();
+    const int rc = gpis3_impl_extract((GPisMap3*)m, me, n3, origin3, step3, level, stream);
+    if (rc != GPIS_OK) me.clear_result();
+    return rc;
+}
+int gpis2_extract_contour(void* m, void* mesh, const int* n2, const float* origin2, const float* step2, float level, void* stream) {
+    if (!m) return GPIS_ERR_ARG;
+    if (int rc = mesh_args(mesh, 2, n2, origin2, step2)) return rc;
+    if (std::isinf(level)) return GPIS_ERR_ARG;
+    MeshExtractor& me = *(MeshExtractor*)mesh;
+    me.clear_result();
+    const int rc = gpis2_impl_extract((GPisMap*)m, me, n2, origin2, step2, level, stream);
+    if (rc != GPIS_OK) me.clear_result();
+    return rc;
+}
+int gpis_mesh_counts(void* mesh, long long* nvert, long long* nprim) {
+    if (!mesh) return GPIS_ERR_ARG;
+    const MeshExtractor& me = *(MeshExtractor*)mesh;
+    if (nvert) *nvert = me.nvert;
+    if (nprim) *nprim = me.nprim;
+    return GPIS_OK;
+}
+int gpis_mesh_get(void* mesh, float* verts, int* prims, float* vrec) {
+    if (!mesh) return GPIS_ERR_ARG;
+    MeshExtractor& me = *(MeshExtractor*)mesh;
+    if (vrec && me.nvert > 0 && !me.rec_valid) return GPIS_ERR_STATE;
+    DeviceScope ds(me.device);
+    const size_t d = (size_t)me.dim;
+    if (verts && me.nvert > 0) GPIS_HIP(hipMemcpyAsync(verts, me.d_verts, sizeof(float) * d * me.nvert, hipMemcpyDeviceToHost, me.own));
+    if (prims && me.nprim > 0) GPIS_HIP(hipMemcpyAsync(prims, me.d_prims, sizeof(int) * d * me.nprim, hipMemcpyDeviceToHost, me.own));
+    if (vrec && me.nvert > 0) GPIS_HIP(hipMemcpyAsync(vrec, me.d_vrec, sizeof(float) * 2 * (1 + d) * me.nvert, hipMemcpyDeviceToHost, me.own));
+    GPIS_HIP(hipStreamSynchronize(me.own));
+    return GPIS_OK;
+}
+int gpis_mesh_get_grid(void* mesh, float* vals) {
+    if (!mesh || !vals) return GPIS_ERR_ARG;
+    MeshExtractor& me = *(MeshExtractor*)mesh;
+    if (!me.grid_valid) return GPIS_ERR_STATE;
+    DeviceScope ds(me.device);
+    GPIS_HIP(hipMemcpyAsync(vals, me.d_val, sizeof(float) * me.ngrid, hipMemcpyDeviceToHost, me.own));
+    GPIS_HIP(hipStreamSynchronize(me.own));
+    return GPIS_OK;
+}
+int gpis_mesh_device(void* mesh, const float** d_verts, const int** d_prims, const float** d_vrec) {
+    if (!mesh) return GPIS_ERR_ARG;
+    const MeshExtractor& me = *(MeshExtractor*)mesh;
+    if (d_verts) *d_verts = me.d_verts;
+    if (d_prims) *d_prims = me.d_prims;
+    if (d_vrec) *d_vrec = me.rec_valid ? me.d_vrec : nullptr;
     return GPIS_OK;
 }
 

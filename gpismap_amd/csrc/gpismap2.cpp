@@ -11,6 +11,7 @@
 #include "../../include/GPisMap.h"
 #include "flat_tree.h"
 #include "map_query.h"
+#include "mesh.h"
 #include "obsgp.h"
 #include "ongpis.h"
 
@@ -642,6 +643,22 @@ void gpis2_impl_stats(GPisMap* g, double* out, int n) {
                     (double)m.store.last_train_ms, 0.0};
     for (int i = 0; i < n && i < 12; ++i) out[i] = v[i];
 }
+
+// Contour extraction (gpis2_extract_contour): testDevice's checks and join, then the lattice and the vertices through the map's MapQuery.
+int gpis2_impl_extract(GPisMap* g, MeshExtractor& me, const int* n2, const float* origin2, const float* step2, float level, void* hip_stream) try {
+    GPisMap::Impl& m = *g->impl();
+    DeviceScope dev_scope_(m.device);
+    m.fail_rc = 0;
+    if (!m.ok) return GPIS_ERR_HIP;
+    if (!m.has_tree) return GPIS_ERR_STATE;
+    if (std::isnan(level)) level = -m.setting.fbias;
+    if (int rc = me.bind(m.device)) return rc;
+    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : m.stream;
+    (void)m.join_training();
+    const int rc = me.from_map(m.mq, m.store, 2, n2, origin2, step2, level, s);
+    if (rc != GPIS_OK) { m.fail_rc = rc; fprintf(stderr, "[gpismap_amd] gpis2_extract_contour: device path failed (%d)\n", rc); }
+    return rc;
+} catch (const std::exception& e) { nothrow_report("gpis2_extract_contour", e.what()); return GPIS_ERR_STATE; } catch (...) { nothrow_report("gpis2_extract_contour", "unknown exception"); return GPIS_ERR_STATE; }
 
 int gpis2_impl_fail(GPisMap* g) { return g->impl()->fail_rc; }
 int gpis2_impl_device(GPisMap* g) { return g->impl()->device; }

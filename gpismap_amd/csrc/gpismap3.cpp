@@ -24,6 +24,7 @@
 #include "flat_tree.h"
 #include "host_pool.h"
 #include "map_query.h"
+#include "mesh.h"
 #include "obsgp.h"
 #include "ongpis.h"
 
@@ -1939,6 +1940,25 @@ bool GPisMap3::loadMap_one(const char* path) try {
     m.build_cluster_table();
     return m.upd_rc == 0;
 } catch (const std::exception& e) { nothrow_report("GPisMap3::loadMap", e.what()); return false; } catch (...) { nothrow_report("GPisMap3::loadMap", "unknown exception"); return false; }
+
+// Surface extraction (gpis3_extract_mesh): testDevice's checks and joins, then the lattice and the vertices through the map's own
+// MapQuery.  A map over several devices extracts on its lead device, which holds the whole map (as testDevice answers there).
+int gpis3_impl_extract(GPisMap3* g, MeshExtractor& me, const int* n3, const float* origin3, const float* step3, float level, void* hip_stream) try {
+    GPisMap3::Impl& m = *g->impl();
+    DeviceScope dev_scope_(m.device);
+    m.fail_rc = 0;
+    if (!m.ok) return GPIS_ERR_HIP;
+    if (!m.has_tree) return GPIS_ERR_STATE;          // nothing to answer with (testDevice refuses the same map)
+    if (m.table_pending) { fprintf(stderr, "[gpismap_amd] gpis3_extract_mesh: sharded update not finished (gpis3_shard_finish)\n"); return GPIS_ERR_STATE; }
+    if (std::isnan(level)) level = -m.setting.fbias;  // the level the map stores its surface points at
+    if (int rc = me.bind(m.device)) return rc;
+    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : m.stream;
+    m.finish_training();
+    const int rc = me.from_map(m.mq, m.store, 3, n3, origin3, step3, level, s);
+    if (rc != GPIS_OK) { m.fail_rc = rc; fprintf(stderr, "[gpismap_amd] gpis3_extract_mesh: device path failed (%d)\n", rc); }
+    if (rc == GPIS_ERR_STATE) m.build_cluster_table();   // (models dropped by the inverse pass: their cells have no GP any more)
+    return rc;
+} catch (const std::exception& e) { nothrow_report("gpis3_extract_mesh", e.what()); return GPIS_ERR_STATE; } catch (...) { nothrow_report("gpis3_extract_mesh", "unknown exception"); return GPIS_ERR_STATE; }
 
 // accessors used by the C-ABI (capi.cpp)
 int gpis3_impl_fail(GPisMap3* g) { return g->impl()->fail_rc; }

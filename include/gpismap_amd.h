@@ -252,6 +252,45 @@ int   gpis_ongpis_set_cu_reserve(void* s, int n);
 int   gpis_selftest_ranged_arith(unsigned long long seed, int blocks, int per_thread, int mode, unsigned long long* mismatches2);
 int   gpis_ongpis_last_ms(void* s, float* train_ms, float* eval_ms);
 
+/* ---- surface extraction: the map's zero-level surface on the device (DESIGN.md "Surface extraction") ------------------
+ * The map's test() on a lattice of nx x ny (x nz) points (index p = (k ny + j) nx + i, x fastest; coordinates
+ * origin + (float)i * step per axis, float32, no FMA), f = slot 0 of each zero-prefilled record; marching tetrahedra on the
+ * Freudenthal split of every cell (6 tetrahedra per cube, 2 triangles per square) at `level` (inside iff f < level; NaN =
+ * -fbias of the map's parameters, the level its surface points are stored at); then the map's test() on the vertices.
+ * One vertex per crossed lattice edge, numbered in edge order; triangles (3-D) are wound so that cross(v1 - v0, v2 - v0)
+ * points to f >= level and start at their smallest index, segments (2-D) have the right-hand normal (dy, -dx) pointing
+ * there; primitives come by cell, then simplex.  Every position comes from an exclusive scan: the same bits on every run.
+ * A mesh object is a result holder whose device buffers (about 13 B per lattice point plus the output) are reused across
+ * calls; every extraction returns with its work finished.  Arguments: a size < 2 on any axis, a non-finite origin, a
+ * non-positive or non-finite step, null pointers -> GPIS_ERR_ARG, the previous result untouched.  More than 2^28 lattice
+ * points -> GPIS_ERR_LIMIT before anything is allocated; 2^31 or more vertices or primitives -> GPIS_ERR_LIMIT before the
+ * output is allocated.  Any other failure (the test() path's status propagates: GPIS_ERR_STATE on an expired K4 ring wait,
+ * ...) leaves no result (counts 0).  An empty surface is a result: 0 vertices, 0 primitives. */
+void* gpis_mesh_create(void);                              /* on the current device; NULL without one */
+void  gpis_mesh_destroy(void* mesh);
+/* lattice points per test() pass of a map-level extraction (test hook: the results do not depend on it); 0 = 2^22 */
+int   gpis_mesh_set_chunk(void* mesh, int points);
+/* kernel level: any device-resident value grid d_val[prod(n)] (x fastest) of the mesh's device, no map involved; dim 2 or 3,
+ * level finite.  No vertex records (gpis_mesh_get's vrec must be NULL afterwards).  hip_stream NULL: the mesh's own stream. */
+int   gpis_mesh_from_grid(void* mesh, const float* d_val, int dim, const int* n, const float* origin, const float* step,
+                          float level, void* hip_stream);
+/* map level: vertices [V][3], triangles [F][3], vertex records [V][8] (the map's test() record of every vertex: f, the
+ * gradient -- the surface normal -- and the variances).  Behaves like gpis3_test_device: GPIS_ERR_STATE while a sharded update
+ * is unfinished or when the map holds no tree, joins a pipelined training; a map over several devices extracts on its lead
+ * device (same result as a one-device map).  hip_stream NULL: the map's stream. */
+int   gpis3_extract_mesh(void* map, void* mesh, const int* n3, const float* origin3, const float* step3, float level,
+                         void* hip_stream);
+/* 2-D map: vertices [V][2], segments [S][2], vertex records [V][6] */
+int   gpis2_extract_contour(void* map, void* mesh, const int* n2, const float* origin2, const float* step2, float level,
+                            void* hip_stream);
+int   gpis_mesh_counts(void* mesh, long long* nvert, long long* nprim);
+/* host copies of the last result (any pointer may be NULL); vrec non-NULL after gpis_mesh_from_grid -> GPIS_ERR_STATE */
+int   gpis_mesh_get(void* mesh, float* verts, int* prims, float* vrec);
+/* the value grid (f, prod(n) floats) of the last map-level extraction; GPIS_ERR_STATE after gpis_mesh_from_grid */
+int   gpis_mesh_get_grid(void* mesh, float* vals);
+/* device pointers of the last result, valid until the next extraction or gpis_mesh_destroy (*d_vrec = NULL without records) */
+int   gpis_mesh_device(void* mesh, const float** d_verts, const int** d_prims, const float** d_vrec);
+
 #ifdef __cplusplus
 }
 #endif
