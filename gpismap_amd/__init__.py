@@ -27,6 +27,12 @@ class gpis_cam(C.Structure):
                 ("width", C.c_int), ("height", C.c_int)]
 
 
+class gpis_render_opts(C.Structure):
+    _fields_ = [("tnear", C.c_float), ("tfar", C.c_float), ("min_step", C.c_float), ("max_step", C.c_float),
+                ("far_step", C.c_float), ("level", C.c_float), ("max_var", C.c_float), ("refine", C.c_int),
+                ("max_steps", C.c_int)]
+
+
 def _p(a, t=C.c_float):
     return a.ctypes.data_as(C.POINTER(t))
 
@@ -136,6 +142,17 @@ def lib():
         L.gpis_mesh_get.argtypes = [vp, fp, ip, fp]
         L.gpis_mesh_get_grid.argtypes = [vp, fp]
         L.gpis_mesh_device.argtypes = [vp, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
+    if hasattr(L, "gpis_render_create"):
+        L.gpis_render_default_opts.argtypes = [C.c_int, C.POINTER(gpis_render_opts)]
+        L.gpis_render_create.restype = vp
+        L.gpis_render_create.argtypes = []
+        L.gpis_render_destroy.argtypes = [vp]
+        L.gpis_render_set_chunk.argtypes = [vp, C.c_int]
+        L.gpis3_render_depth.argtypes = [vp, vp, C.POINTER(gpis_cam), fp, C.POINTER(gpis_render_opts), vp]
+        L.gpis2_render_scan.argtypes = [vp, vp, fp, C.c_int, fp, C.POINTER(gpis_render_opts), vp]
+        L.gpis_render_get.argtypes = [vp, fp, fp, C.POINTER(C.c_ubyte)]
+        L.gpis_render_device.argtypes = [vp, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
+        L.gpis_render_info.argtypes = [vp, dp, C.c_int]
     _lib = L
     return L
 
@@ -379,6 +396,27 @@ class GPisMap3:
             self._mesh = Mesh()
         return self._mesh
 
+    def render_depth(self, pose, cam6=None, renderer=None, **opts):
+        """What the depth camera would see from `pose` (gpis3_render_depth): rays marched through the map's test() on the device.
+        Returns (depth [W*H] f32, rec [W*H, 8] f32, status [W*H] u8) in update()'s column-major layout (k = col * H + row), so
+        update(depth, pose) takes the depth.  No hit: depth NaN, record NaN.  Status 0 hit, 1 left the interval, 2 step limit.
+        cam6: (fx, fy, cx, cy, width, height), None = the map's camera.  opts: the gpis_render_opts fields (tnear, tfar,
+        min_step, max_step, far_step, level, max_var, refine, max_steps).  renderer: a Renderer to hold the device result
+        (default: one kept by this map)."""
+        pose = np.ascontiguousarray(pose, dtype=np.float32).ravel()
+        if pose.size != 12:
+            raise GpisError("pose must have 12 elements")
+        r = renderer if renderer is not None else self._own_renderer()
+        o = render_opts(3, **opts)
+        cam = C.byref(_cam(cam6)) if cam6 is not None else None
+        _check(self.L.gpis3_render_depth(self.h, r.h, cam, _p(pose), C.byref(o), None), "gpis3_render_depth")
+        return r.get()
+
+    def _own_renderer(self):
+        if getattr(self, "_renderer", None) is None:
+            self._renderer = Renderer()
+        return self._renderer
+
 
 class GPisMap:
     """Mirror of the reference's mexGPisMap command set ('update', 'test', 'reset') on the HIP path."""
@@ -453,6 +491,22 @@ class GPisMap:
         mesh._extract(self.L.gpis2_extract_contour, self.h, 2, origin, step, shape, level, "gpis2_extract_contour")
         v, f, r = mesh.get()
         return _filter_var(v, f, r, 3, max_var)
+
+    def render_scan(self, thetas, pose6, renderer=None, **opts):
+        """What the laser would see from `pose6` (gpis2_render_scan) along the beams `thetas`.  Returns (range [n] f32,
+        rec [n, 6] f32, status [n] u8); no hit: range NaN, record NaN.  opts: as GPisMap3.render_depth."""
+        thetas = np.ascontiguousarray(thetas, dtype=np.float32).ravel()
+        pose6 = np.ascontiguousarray(pose6, dtype=np.float32).ravel()
+        if pose6.size != 6:
+            raise GpisError("pose6 must have 6 elements")
+        if renderer is None:
+            if getattr(self, "_renderer", None) is None:
+                self._renderer = Renderer()
+            renderer = self._renderer
+        o = render_opts(2, **opts)
+        _check(self.L.gpis2_render_scan(self.h, renderer.h, _p(thetas), thetas.size, _p(pose6), C.byref(o), None),
+               "gpis2_render_scan")
+        return renderer.get()
 
 
 def _filter_var(verts, prims, rec, slot, max_var):
@@ -546,6 +600,70 @@ class Mesh:
     def device_ptrs(self):
         a, b, c = C.c_void_p(0), C.c_void_p(0), C.c_void_p(0)
         _check(self.L.gpis_mesh_device(self.h, C.byref(a), C.byref(b), C.byref(c)), "gpis_mesh_device")
+        return a.value or 0, b.value or 0, c.value or 0
+
+
+def render_opts(dim, **opts):
+    """gpis_render_opts of the library's defaults for `dim` (gpis_render_default_opts) with the given fields replaced."""
+    o = gpis_render_opts()
+    _check(lib().gpis_render_default_opts(int(dim), C.byref(o)), "gpis_render_default_opts")
+    names = {f[0] for f in gpis_render_opts._fields_}
+    for k, v in opts.items():
+        if k not in names:
+            raise GpisError("unknown render option %r" % k)
+        setattr(o, k, v)
+    return o
+
+
+class Renderer:
+    """Result holder of the renderer (gpis_render_*): device buffers reused across calls."""
+
+    INFO_KEYS = ("rays", "dim", "passes", "march_passes", "samples", "evals", "k4_ms", "hits",
+                 "box_lo_x", "box_lo_y", "box_lo_z", "box_hi_x", "box_hi_y", "box_hi_z", "valid", "mq_ms")
+
+    def __init__(self):
+        self.L = lib()
+        if self.L.gpis_device_count() < 1:
+            raise GpisError("no HIP device: gpismap_amd has no CPU fallback")
+        self.h = C.c_void_p(self.L.gpis_render_create())
+        if not self.h:
+            raise GpisError("gpis_render_create failed")
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.gpis_render_destroy(self.h)
+            self.h = None
+
+    __del__ = close
+
+    def set_chunk(self, rays):
+        """Rays per test() call within a pass (0 = default 2^22; results do not depend on it)."""
+        _check(self.L.gpis_render_set_chunk(self.h, int(rays)), "gpis_render_set_chunk")
+
+    def info(self):
+        out = np.zeros(len(self.INFO_KEYS), dtype=np.float64)
+        _check(self.L.gpis_render_info(self.h, _p(out, C.c_double), out.size), "gpis_render_info")
+        return dict(zip(self.INFO_KEYS, out.tolist()))
+
+    def box(self):
+        """(lo [3], hi [3]) float32: the clip box of the last render (the cluster cells' box grown by the search half-width)."""
+        i = self.info()
+        return (np.array([i["box_lo_x"], i["box_lo_y"], i["box_lo_z"]], np.float32),
+                np.array([i["box_hi_x"], i["box_hi_y"], i["box_hi_z"]], np.float32))
+
+    def get(self):
+        """(depth [n], rec [n, 2(1+dim)], status [n] u8): host copies of the last result."""
+        i = self.info()
+        n, d = int(i["rays"]), int(i["dim"])
+        depth = np.zeros(n, dtype=np.float32)
+        rec = np.zeros((n, 2 * (1 + d)), dtype=np.float32)
+        status = np.zeros(n, dtype=np.uint8)
+        _check(self.L.gpis_render_get(self.h, _p(depth), _p(rec), _p(status, C.c_ubyte)), "gpis_render_get")
+        return depth, rec, status
+
+    def device_ptrs(self):
+        a, b, c = C.c_void_p(0), C.c_void_p(0), C.c_void_p(0)
+        _check(self.L.gpis_render_device(self.h, C.byref(a), C.byref(b), C.byref(c)), "gpis_render_device")
         return a.value or 0, b.value or 0, c.value or 0
 
 

@@ -8,6 +8,7 @@
 #include "../../include/gpismap_amd.h"
 #include "map_query.h"
 #include "mesh.h"
+#include "render.h"
 #include "obsgp.h"
 #include "ongpis.h"
 
@@ -46,6 +47,8 @@ int gpis2_impl_sync(GPisMap* m);
 void gpis2_impl_set_pipeline(GPisMap* m, int on);
 int gpis3_impl_extract(GPisMap3* g, MeshExtractor& me, const int* n3, const float* origin3, const float* step3, float level, void* stream);
 int gpis2_impl_extract(GPisMap* g, MeshExtractor& me, const int* n2, const float* origin2, const float* step2, float level, void* stream);
+int gpis3_impl_render(GPisMap3* g, Renderer& r, const float* cam4, const int* wh, const float* pose12, RenderOpts o, void* stream);
+int gpis2_impl_render(GPisMap* g, Renderer& r, const float* thetas, int n, const float* pose6, RenderOpts o, void* stream);
 
 namespace gpis { int selftest_ranged_arith(unsigned long long seed, int blocks, int per_thread, int mode, unsigned long long* mismatches); }
 extern "C" {
@@ -476,6 +479,106 @@ int gpis_mesh_device(void* mesh, const float** d_verts, const int** d_prims, con
     if (d_verts) *d_verts = me.d_verts;
     if (d_prims) *d_prims = me.d_prims;
     if (d_vrec) *d_vrec = me.rec_valid ? me.d_vrec : nullptr;
+    return GPIS_OK;
+}
+
+// ---- rendering ---------------------------------------------------------------------------------------------------------
+static RenderOpts render_opts(const gpis_render_opts* o) {
+    RenderOpts r;
+    r.tnear = o->tnear; r.tfar = o->tfar; r.min_step = o->min_step; r.max_step = o->max_step; r.far_step = o->far_step;
+    r.level = o->level; r.max_var = o->max_var; r.refine = o->refine; r.max_steps = o->max_steps;
+    return r;
+}
+int gpis_render_default_opts(int dim, gpis_render_opts* o) {
+    if (!o || (dim != 2 && dim != 3)) return GPIS_ERR_ARG;
+    const float nan = std::nanf("");
+    if (dim == 3) { o->tnear = 0.4f; o->tfar = 4.0f; o->min_step = 1e-3f; o->max_step = 0.01f; o->max_steps = 512; }
+    else { o->tnear = 0.2f; o->tfar = 30.0f; o->min_step = 0.01f; o->max_step = 0.1f; o->max_steps = 1024; }
+    o->far_step = nan; o->level = nan; o->max_var = INFINITY; o->refine = 8;
+    return GPIS_OK;
+}
+void* gpis_render_create(void) {
+    if (gpis_device_count() < 1) { fprintf(stderr, "[gpismap_amd] no HIP device\n"); return nullptr; }
+    Renderer* r = new (std::nothrow) Renderer();
+    if (r && !r->own) { delete r; return nullptr; }
+    return r;
+}
+void gpis_render_destroy(void* render) { delete (Renderer*)render; }
+int gpis_render_set_chunk(void* render, int rays) {
+    if (!render || rays < 0) return GPIS_ERR_ARG;
+    ((Renderer*)render)->chunk = rays ? rays : (1 << 22);
+    return GPIS_OK;
+}
+// the checks that need no map: an argument error leaves the previous result readable
+static int render_args(void* render, int dim, const float* pose, const gpis_render_opts* opts, RenderOpts* o) {
+    if (!render || !pose) return GPIS_ERR_ARG;
+    gpis_render_opts d;
+    if (!opts) { (void)gpis_render_default_opts(dim, &d); opts = &d; }
+    *o = render_opts(opts);
+    const int np = dim == 3 ? 12 : 6;
+    for (int k = 0; k < np; ++k) if (!std::isfinite(pose[k])) return GPIS_ERR_ARG;
+    if (std::isinf(o->level) || (!std::isnan(o->far_step) && !(std::isfinite(o->far_step) && o->far_step > 0.f))) return GPIS_ERR_ARG;
+    RenderOpts c = *o;
+    c.level = 0.f; c.far_step = 1.f;          // (resolved against the map by the entry)
+    return render_check_opts(c);
+}
+int gpis3_render_depth(void* m, void* render, const gpis_cam* cam, const float* pose12, const gpis_render_opts* opts, void* stream) {
+    if (!m) return GPIS_ERR_ARG;
+    RenderOpts o;
+    if (int rc = render_args(render, 3, pose12, opts, &o)) return rc;
+    float c4[4];
+    int wh[2];
+    if (cam) {
+        c4[0] = cam->fx; c4[1] = cam->fy; c4[2] = cam->cx; c4[3] = cam->cy; wh[0] = cam->width; wh[1] = cam->height;
+        RayGeom g{};
+        g.dim = 3; g.fx = c4[0]; g.fy = c4[1]; g.cx = c4[2]; g.cy = c4[3]; g.width = wh[0]; g.height = wh[1];
+        for (int k = 0; k < 3; ++k) g.t[k] = pose12[k];
+        for (int k = 0; k < 9; ++k) g.R[k] = pose12[3 + k];
+        if (int rc = render_check_geom(g, (long long)wh[0] * wh[1])) return rc;
+    }
+    Renderer& r = *(Renderer*)render;
+    const int rc = gpis3_impl_render((GPisMap3*)m, r, cam ? c4 : nullptr, cam ? wh : nullptr, pose12, o, stream);
+    if (rc != GPIS_OK && rc != GPIS_ERR_ARG && rc != GPIS_ERR_LIMIT) r.clear_result();
+    return rc;
+}
+int gpis2_render_scan(void* m, void* render, const float* thetas, int n, const float* pose6, const gpis_render_opts* opts, void* stream) {
+    if (!m || !thetas || n < 1) return GPIS_ERR_ARG;
+    RenderOpts o;
+    if (int rc = render_args(render, 2, pose6, opts, &o)) return rc;
+    for (int k = 0; k < n; ++k) if (!std::isfinite(thetas[k])) return GPIS_ERR_ARG;
+    if ((long long)n > Renderer::kMaxRays) return GPIS_ERR_LIMIT;
+    Renderer& r = *(Renderer*)render;
+    const int rc = gpis2_impl_render((GPisMap*)m, r, thetas, n, pose6, o, stream);
+    if (rc != GPIS_OK && rc != GPIS_ERR_ARG && rc != GPIS_ERR_LIMIT) r.clear_result();
+    return rc;
+}
+int gpis_render_get(void* render, float* depth, float* rec, unsigned char* status) {
+    if (!render) return GPIS_ERR_ARG;
+    Renderer& r = *(Renderer*)render;
+    if (!r.valid) return GPIS_ERR_STATE;
+    DeviceScope ds(r.device);
+    const size_t n = (size_t)r.nrays, nc = 2 * (1 + (size_t)r.dim);
+    if (depth) GPIS_HIP(hipMemcpyAsync(depth, r.d_depth, sizeof(float) * n, hipMemcpyDeviceToHost, r.own));
+    if (rec) GPIS_HIP(hipMemcpyAsync(rec, r.d_rec, sizeof(float) * nc * n, hipMemcpyDeviceToHost, r.own));
+    if (status) GPIS_HIP(hipMemcpyAsync(status, r.d_status, n, hipMemcpyDeviceToHost, r.own));
+    GPIS_HIP(hipStreamSynchronize(r.own));
+    return GPIS_OK;
+}
+int gpis_render_device(void* render, const float** d_depth, const float** d_rec, const unsigned char** d_status) {
+    if (!render) return GPIS_ERR_ARG;
+    const Renderer& r = *(Renderer*)render;
+    if (d_depth) *d_depth = r.valid ? r.d_depth : nullptr;
+    if (d_rec) *d_rec = r.valid ? r.d_rec : nullptr;
+    if (d_status) *d_status = r.valid ? r.d_status : nullptr;
+    return GPIS_OK;
+}
+int gpis_render_info(void* render, double* out, int n) {
+    if (!render || !out || n < 0) return GPIS_ERR_ARG;
+    const Renderer& r = *(Renderer*)render;
+    const double v[16] = {(double)r.nrays, (double)r.dim, (double)r.passes, (double)r.march_passes, (double)r.samples,
+                          (double)r.evals, r.k4_ms, (double)r.hits, (double)r.box_lo[0], (double)r.box_lo[1], (double)r.box_lo[2],
+                          (double)r.box_hi[0], (double)r.box_hi[1], (double)r.box_hi[2], r.valid ? 1.0 : 0.0, r.mq_ms};
+    for (int i = 0; i < n && i < 16; ++i) out[i] = v[i];
     return GPIS_OK;
 }
 

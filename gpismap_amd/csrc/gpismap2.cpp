@@ -12,6 +12,7 @@
 #include "flat_tree.h"
 #include "map_query.h"
 #include "mesh.h"
+#include "render.h"
 #include "obsgp.h"
 #include "ongpis.h"
 
@@ -659,6 +660,37 @@ int gpis2_impl_extract(GPisMap* g, MeshExtractor& me, const int* n2, const float
     if (rc != GPIS_OK) { m.fail_rc = rc; fprintf(stderr, "[gpismap_amd] gpis2_extract_contour: device path failed (%d)\n", rc); }
     return rc;
 } catch (const std::exception& e) { nothrow_report("gpis2_extract_contour", e.what()); return GPIS_ERR_STATE; } catch (...) { nothrow_report("gpis2_extract_contour", "unknown exception"); return GPIS_ERR_STATE; }
+
+// Scan rendering (gpis2_render_scan): testDevice's checks and join, then the march through the map's MapQuery.  The beams'
+// cos / sin in double on the host (polar2Cart); the sensor offset of the map's parameters.
+int gpis2_impl_render(GPisMap* g, Renderer& r, const float* thetas, int n, const float* pose6, RenderOpts o, void* hip_stream) try {
+    GPisMap::Impl& m = *g->impl();
+    DeviceScope dev_scope_(m.device);
+    m.fail_rc = 0;
+    if (!m.ok) return GPIS_ERR_HIP;
+    if (!m.has_tree) return GPIS_ERR_STATE;
+    RayGeom geo{};
+    geo.dim = 2;
+    geo.t[0] = pose6[0]; geo.t[1] = pose6[1];
+    for (int i = 0; i < 4; ++i) geo.R[i] = pose6[2 + i];
+    geo.off[0] = m.setting.sensor_offset[0]; geo.off[1] = m.setting.sensor_offset[1];
+    if (std::isnan(o.level)) o.level = -m.setting.fbias;
+    if (std::isnan(o.far_step)) o.far_step = 0.9f * m.mq.search_half();
+    if (int rc = render_check_geom(geo, n)) return rc;
+    if (int rc = render_check_opts(o)) return rc;
+    std::vector<double> cs((size_t)2 * n);
+    for (int k = 0; k < n; ++k) {
+        if (!std::isfinite(thetas[k])) return GPIS_ERR_ARG;
+        cs[2 * (size_t)k] = std::cos((double)thetas[k]);
+        cs[2 * (size_t)k + 1] = std::sin((double)thetas[k]);
+    }
+    if (int rc = r.bind(m.device)) return rc;
+    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : m.stream;
+    (void)m.join_training();
+    const int rc = r.render(m.mq, m.store, geo, cs.data(), n, o, s);
+    if (rc != GPIS_OK) { m.fail_rc = rc; fprintf(stderr, "[gpismap_amd] gpis2_render_scan: device path failed (%d)\n", rc); }
+    return rc;
+} catch (const std::exception& e) { nothrow_report("gpis2_render_scan", e.what()); return GPIS_ERR_STATE; } catch (...) { nothrow_report("gpis2_render_scan", "unknown exception"); return GPIS_ERR_STATE; }
 
 int gpis2_impl_fail(GPisMap* g) { return g->impl()->fail_rc; }
 int gpis2_impl_device(GPisMap* g) { return g->impl()->device; }

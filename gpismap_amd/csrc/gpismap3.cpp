@@ -25,6 +25,7 @@
 #include "host_pool.h"
 #include "map_query.h"
 #include "mesh.h"
+#include "render.h"
 #include "obsgp.h"
 #include "ongpis.h"
 
@@ -1959,6 +1960,36 @@ int gpis3_impl_extract(GPisMap3* g, MeshExtractor& me, const int* n3, const floa
     if (rc == GPIS_ERR_STATE) m.build_cluster_table();   // (models dropped by the inverse pass: their cells have no GP any more)
     return rc;
 } catch (const std::exception& e) { nothrow_report("gpis3_extract_mesh", e.what()); return GPIS_ERR_STATE; } catch (...) { nothrow_report("gpis3_extract_mesh", "unknown exception"); return GPIS_ERR_STATE; }
+
+// Depth rendering (gpis3_render_depth): testDevice's checks and joins, then the march through the map's own MapQuery on the lead
+// device.  cam4 (fx, fy, cx, cy) and wh (width, height) NULL: the map's camera; o.level NaN: -fbias; o.far_step NaN: 0.9 x the search half-width.
+int gpis3_impl_render(GPisMap3* g, Renderer& r, const float* cam4, const int* wh, const float* pose12, RenderOpts o, void* hip_stream) try {
+    GPisMap3::Impl& m = *g->impl();
+    DeviceScope dev_scope_(m.device);
+    m.fail_rc = 0;
+    if (!m.ok) return GPIS_ERR_HIP;
+    if (!m.has_tree) return GPIS_ERR_STATE;
+    if (m.table_pending) { fprintf(stderr, "[gpismap_amd] gpis3_render_depth: sharded update not finished (gpis3_shard_finish)\n"); return GPIS_ERR_STATE; }
+    RayGeom geo{};
+    geo.dim = 3;
+    geo.fx = cam4 ? cam4[0] : m.cam.fx; geo.fy = cam4 ? cam4[1] : m.cam.fy;
+    geo.cx = cam4 ? cam4[2] : m.cam.cx; geo.cy = cam4 ? cam4[3] : m.cam.cy;
+    geo.width = cam4 ? wh[0] : m.cam.width; geo.height = cam4 ? wh[1] : m.cam.height;
+    for (int i = 0; i < 3; ++i) geo.t[i] = pose12[i];
+    for (int i = 0; i < 9; ++i) geo.R[i] = pose12[3 + i];
+    if (std::isnan(o.level)) o.level = -m.setting.fbias;
+    if (std::isnan(o.far_step)) o.far_step = 0.9f * m.mq.search_half();
+    const long long n = (long long)geo.width * geo.height;
+    if (int rc = render_check_geom(geo, n)) return rc;
+    if (int rc = render_check_opts(o)) return rc;
+    if (int rc = r.bind(m.device)) return rc;
+    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : m.stream;
+    m.finish_training();
+    const int rc = r.render(m.mq, m.store, geo, nullptr, n, o, s);
+    if (rc != GPIS_OK) { m.fail_rc = rc; fprintf(stderr, "[gpismap_amd] gpis3_render_depth: device path failed (%d)\n", rc); }
+    if (rc == GPIS_ERR_STATE) m.build_cluster_table();   // (models dropped by the inverse pass: their cells have no GP any more)
+    return rc;
+} catch (const std::exception& e) { nothrow_report("gpis3_render_depth", e.what()); return GPIS_ERR_STATE; } catch (...) { nothrow_report("gpis3_render_depth", "unknown exception"); return GPIS_ERR_STATE; }
 
 // accessors used by the C-ABI (capi.cpp)
 int gpis3_impl_fail(GPisMap3* g) { return g->impl()->fail_rc; }

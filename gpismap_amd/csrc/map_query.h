@@ -49,6 +49,14 @@ public:
     // test(): x device [n][dim] interleaved, res device [n][2(1+dim)]; only the entries the
     // reference writes are touched.
     int run(OnGPISStore& store, const float* d_x, int n, float* d_res, hipStream_t s);
+    // run() in two halves for callers that query the same models many times in a row (the renderer's march passes): prepare()
+    // does run()'s per-call host work once (lazy inverses, model sync, the per-class LDS sizing); run_prepared() is every
+    // pass after it and must not be separated from prepare() by a change of the models.  run() = prepare() + run_prepared().
+    int prepare(OnGPISStore& store, hipStream_t s);
+    int run_prepared(OnGPISStore& store, const float* d_x, int n, float* d_res, hipStream_t s);
+    // box of all cluster cells of the table (lo[0..2], hi[0..2]); false when the table is empty
+    bool cluster_box(float* lo, float* hi) const;
+    float search_half() const { return search_half_; }
     int num_clusters() const { return ncl_; }
     // statistics of the last run
     long long last_evals = 0, last_flops = 0, last_touched = 0;
@@ -65,6 +73,7 @@ private:
     float search_half_, var_thre_, prior_var_;
     int ncl_ = 0;
     ClusterTableView tv_{};
+    float box_lo_[3] = {0.f, 0.f, 0.f}, box_hi_[3] = {0.f, 0.f, 0.f};
     void* d_tab_ = nullptr; size_t cap_tab_ = 0;
     int* d_grid_ = nullptr; size_t cap_grid_ = 0;
     // per-chunk scratch

@@ -429,6 +429,10 @@ int MapQuery::set_clusters(const std::vector<ClusterEntry>& cl, const std::vecto
         }
         grid[cell] = i;
         tab[i] = make_float4(e.c[0], e.c[1], e.c[2], 0.f);
+        for (int d = 0; d < 3; ++d) {
+            box_lo_[d] = i ? std::min(box_lo_[d], e.lo[d]) : e.lo[d];
+            box_hi_[d] = i ? std::max(box_hi_[d], e.hi[d]) : e.hi[d];
+        }
         tab[(size_t)ncl_ + i] = make_float4(e.lo[0], e.lo[1], e.lo[2], 0.f);
         tab[(size_t)2 * ncl_ + i] = make_float4(e.hi[0], e.hi[1], e.hi[2], 0.f);
         mdl[i] = e.model;
@@ -619,6 +623,12 @@ int MapQuery::run_chunk(OnGPISStore& store, const float* d_x, int n, float* d_re
 int MapQuery::run(OnGPISStore& store, const float* d_x, int n, float* d_res, hipStream_t s) {
     last_evals = 0; last_eval_ms = 0.f; last_flops = 0; last_launches = 0;
     if (n <= 0) return GPIS_OK;
+    int rc = prepare(store, s);
+    if (rc) return rc;
+    return run_prepared(store, d_x, n, d_res, s);
+}
+
+int MapQuery::prepare(OnGPISStore& store, hipStream_t s) {
     int rc = store.ensure_inverses(s);     // (lazy inverse: the models retrained since the last prediction get their X now)
     if (rc) return rc;
     rc = store.sync_models(s);
@@ -633,6 +643,19 @@ int MapQuery::run(OnGPISStore& store, const float* d_x, int n, float* d_res, hip
         h_maxN_[c] = std::max(h_maxN_[c], m->N);
         h_maxLd_[c] = std::max(h_maxLd_[c], m->ld);
     }
+    return GPIS_OK;
+}
+
+bool MapQuery::cluster_box(float* lo, float* hi) const {
+    if (ncl_ == 0) return false;
+    for (int d = 0; d < 3; ++d) { lo[d] = box_lo_[d]; hi[d] = box_hi_[d]; }
+    return true;
+}
+
+int MapQuery::run_prepared(OnGPISStore& store, const float* d_x, int n, float* d_res, hipStream_t s) {
+    last_evals = 0; last_eval_ms = 0.f; last_flops = 0; last_launches = 0;
+    if (n <= 0) return GPIS_OK;
+    int rc = GPIS_OK;
     const int nc = 2 * (1 + dim_);
     if (ncl_ == 0) {  // no cluster anywhere: only the prior variance is written
         hipLaunchKernelGGL(prior_only_kernel, dim3((n + 255) / 256), dim3(256), 0, s, n, nc, 1 + dim_, prior_var_, d_res);

@@ -291,6 +291,63 @@ int   gpis_mesh_get_grid(void* mesh, float* vals);
 /* device pointers of the last result, valid until the next extraction or gpis_mesh_destroy (*d_vrec = NULL without records) */
 int   gpis_mesh_device(void* mesh, const float** d_verts, const int** d_prims, const float** d_vrec);
 
+/* ---- rendering: depth images and laser scans from the map on the device --------------------------------
+ * The inverse of update(): what the sensor would see from a pose.  Every ray is marched through the map's test(); every march
+ * step is one test() pass over the rays still active, and nothing but one count per pass leaves the device.
+ * 3-D rays: pixel (col, row) is ray k = col * height + row (update()'s column-major depth layout); u = ((float)col - cx) / fx,
+ * v = ((float)row - cy) / fy; the ray parameter is the depth z; the world point is R[i] (u z) + R[3+i] (v z) + R[6+i] z + t[i]
+ * evaluated left to right in float32 without FMA (update()'s expression, pose12 = [t(3), R(9)]); an arc-length step s is the
+ * z step s / sqrt(u^2 + v^2 + 1).  2-D rays: beam theta has c = cos((double)theta), s = sin((double)theta) (host double, as
+ * update()); local point ((float)(r c) + off0, (float)(r s) + off1) with the map's sensor offset, world R local + t
+ * (pose6 = [t(2), R(4)]); the parameter is the range r and steps are metres.
+ * Clip: [tnear, tfar] intersected with the box of all cluster cells of the map, grown by test()'s search half-width (slab test,
+ * IEEE division); an empty interval is a miss (status 1) without any test().  Samples are test() records pre-filled with
+ * f = NaN and zeros elsewhere: NaN = no cluster within the search box.  g = f - level.  Step: f NaN -> far_step (no point of that
+ * segment lies in a cluster cell); otherwise clamp(|g|, min_step, max_step).  f is NOT a distance bound: max_step is what limits
+ * tunnelling.  Hit: consecutive samples going from outside (g >= 0 or NaN) to inside (g < 0), both with var_f <= max_var
+ * (otherwise the march goes on).  Refinement: `refine` bisection rounds on [z_prev, z] (midpoint lo + (hi - lo) * 0.5; NaN counts
+ * as outside), then the secant point of the final bracket clamped into it (the top when g(lo) is NaN); one last test() gives the
+ * output record there.  Status per ray: 0 hit, 1 left the clipped interval, 2 max_steps samples taken.  Rays without a hit
+ * have depth NaN and an all-NaN record.  The active rays are compacted after every pass by an exclusive scan that keeps their
+ * order: the same call gives the same bits every time, for any chunk size and either update mode.
+ * Errors: a bad camera (size < 1, fx or fy zero or non-finite), a non-finite pose or beam angle, tnear < 0, tnear >= tfar,
+ * non-positive or non-finite steps, min_step > max_step, refine outside [0, 64], max_steps < 1, an infinite level or a NaN max_var
+ * -> GPIS_ERR_ARG, the previous result untouched; more than 2^26 rays -> GPIS_ERR_LIMIT before anything is allocated, the
+ * previous result untouched.  Any other failure (no tree or an unfinished sharded update: GPIS_ERR_STATE; the test() path's
+ * status) leaves no result.  A render object holds grow-only device buffers (about 150 B per ray) reused across calls; every
+ * render returns with its work finished.  A map over several devices renders on its lead device. */
+typedef struct gpis_render_opts {
+    float tnear, tfar;          /* ray interval: depth (3-D) / range (2-D) */
+    float min_step, max_step;   /* clamp of |g| as the arc-length step */
+    float far_step;             /* step after a sample with f NaN; NaN = 0.9 x the map's search half-width */
+    float level;                /* NaN = -fbias (the level of the map's surface points) */
+    float max_var;              /* +inf: no variance test */
+    int refine;                 /* bisection rounds */
+    int max_steps;              /* samples per ray */
+} gpis_render_opts;
+/* defaults.  3-D: tnear 0.4, tfar 4 (update()'s valid range), min_step 1e-3, max_step 0.01, max_steps 512;
+ * 2-D: tnear 0.2, tfar 30 (update()'s valid range), min_step 0.01, max_step 0.1, max_steps 1024; both: far_step NaN,
+ * level NaN, max_var +inf, refine 8 */
+int   gpis_render_default_opts(int dim, gpis_render_opts* opts);
+void* gpis_render_create(void);                            /* on the current device; NULL without one */
+void  gpis_render_destroy(void* render);
+/* rays per test() call within a pass (test hook: the results do not depend on it); 0 = 2^22 */
+int   gpis_render_set_chunk(void* render, int rays);
+/* depth [W*H], record [W*H][8], status [W*H].  cam NULL: the map's camera; opts NULL: the defaults; hip_stream NULL: the map's */
+int   gpis3_render_depth(void* map, void* render, const gpis_cam* cam, const float* pose12, const gpis_render_opts* opts,
+                         void* hip_stream);
+/* range [n], record [n][6], status [n] */
+int   gpis2_render_scan(void* map, void* render, const float* thetas, int n, const float* pose6, const gpis_render_opts* opts,
+                        void* hip_stream);
+/* host copies of the last result (any pointer may be NULL); GPIS_ERR_STATE without one */
+int   gpis_render_get(void* render, float* depth, float* rec, unsigned char* status);
+/* device pointers of the last result (NULL without one), valid until the next render or gpis_render_destroy */
+int   gpis_render_device(void* render, const float** d_depth, const float** d_rec, const unsigned char** d_status);
+/* out[0..n): rays, dim, test() passes (march + refinement + output), march passes, samples (rays over all passes), K4
+ * evaluations, ms inside K4 (only while the map's profiling is on), hits, clip box lo[3], hi[3] (NaN for an empty map),
+ * 1 if a result is held, ms of host wall time inside the test() passes (each ends synchronised) */
+int   gpis_render_info(void* render, double* out, int n);
+
 #ifdef __cplusplus
 }
 #endif
