@@ -33,6 +33,12 @@ class gpis_render_opts(C.Structure):
                 ("max_steps", C.c_int)]
 
 
+class gpis_track_opts(C.Structure):
+    _fields_ = [("max_residual", C.c_double), ("huber", C.c_double), ("max_var", C.c_double), ("damping", C.c_double),
+                ("eps_t", C.c_double), ("eps_r", C.c_double), ("level", C.c_float), ("stride", C.c_int),
+                ("max_iters", C.c_int), ("min_inliers", C.c_int)]
+
+
 def _p(a, t=C.c_float):
     return a.ctypes.data_as(C.POINTER(t))
 
@@ -153,6 +159,16 @@ def lib():
         L.gpis_render_get.argtypes = [vp, fp, fp, C.POINTER(C.c_ubyte)]
         L.gpis_render_device.argtypes = [vp, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
         L.gpis_render_info.argtypes = [vp, dp, C.c_int]
+    if hasattr(L, "gpis_track_create"):
+        L.gpis_track_default_opts.argtypes = [C.c_int, C.POINTER(gpis_track_opts)]
+        L.gpis_track_create.restype = vp
+        L.gpis_track_create.argtypes = []
+        L.gpis_track_destroy.argtypes = [vp]
+        L.gpis_track_set_chunk.argtypes = [vp, C.c_int]
+        L.gpis3_track_depth.argtypes = [vp, vp, C.POINTER(gpis_cam), fp, fp, C.POINTER(gpis_track_opts), fp, vp]
+        L.gpis2_track_scan.argtypes = [vp, vp, fp, fp, C.c_int, fp, C.POINTER(gpis_track_opts), fp, vp]
+        L.gpis_track_get.argtypes = [vp, dp, dp, fp]
+        L.gpis_track_info.argtypes = [vp, dp, C.c_int]
     _lib = L
     return L
 
@@ -222,6 +238,7 @@ class GPisMap3:
         if self.L.gpis_device_count() < 1:
             raise GpisError("no HIP device: gpismap_amd has no CPU fallback")
         cam = C.byref(_cam(cam6)) if cam6 is not None else None
+        self._wh = (640, 480) if cam6 is None else (int(cam6[4]), int(cam6[5]))    # (the reference's default camera)
         if devices is None:
             self.h = C.c_void_p(self.L.gpis3_create(cam))
         else:
@@ -245,6 +262,7 @@ class GPisMap3:
 
     def set_camera(self, cam6):
         _check(self.L.gpis3_set_camera(self.h, C.byref(_cam(cam6))), "gpis3_set_camera")
+        self._wh = (int(cam6[4]), int(cam6[5]))
 
     def update(self, depth, pose):
         depth = np.ascontiguousarray(depth, dtype=np.float32)
@@ -417,6 +435,32 @@ class GPisMap3:
             self._renderer = Renderer()
         return self._renderer
 
+    def track_depth(self, depth, pose0, cam6=None, tracker=None, **opts):
+        """The camera pose from which the map explains `depth` best (gpis3_track_depth): damped Gauss-Newton on SE(3) from pose0,
+        one test() pass over the frame's points per iteration, the normal equations reduced on the device.  depth: [W*H] in
+        update()'s column-major layout; pose0: 12 floats [t(3), R(9)].  Returns (pose [12] f32, info): info is Tracker.info()
+        plus H [6, 6], b [6] (xi = (v, omega)) at the returned pose and "resid" [W*H] (r of the inliers, NaN elsewhere).
+        Non-convergence is info["status"] (0 converged, 1 max_iters, 2 too few inliers, 3 degenerate), not an exception.
+        cam6: (fx, fy, cx, cy, width, height), None = the map's camera.  opts: the gpis_track_opts fields."""
+        depth = np.ascontiguousarray(depth, dtype=np.float32).ravel()
+        pose0 = np.ascontiguousarray(pose0, dtype=np.float32).ravel()
+        if pose0.size != 12:
+            raise GpisError("pose must have 12 elements")
+        w, h = (int(cam6[4]), int(cam6[5])) if cam6 is not None else self._wh
+        if depth.size != w * h:
+            raise GpisError("depth must have width * height = %d elements" % (w * h))
+        t = tracker if tracker is not None else self._own_tracker()
+        o = track_opts(3, **opts)
+        cam = C.byref(_cam(cam6)) if cam6 is not None else None
+        out = np.zeros(12, dtype=np.float32)
+        _check(self.L.gpis3_track_depth(self.h, t.h, cam, _p(depth), _p(pose0), C.byref(o), _p(out), None), "gpis3_track_depth")
+        return out, t.result()
+
+    def _own_tracker(self):
+        if getattr(self, "_tracker", None) is None:
+            self._tracker = Tracker()
+        return self._tracker
+
 
 class GPisMap:
     """Mirror of the reference's mexGPisMap command set ('update', 'test', 'reset') on the HIP path."""
@@ -507,6 +551,25 @@ class GPisMap:
         _check(self.L.gpis2_render_scan(self.h, renderer.h, _p(thetas), thetas.size, _p(pose6), C.byref(o), None),
                "gpis2_render_scan")
         return renderer.get()
+
+    def track_scan(self, thetas, ranges, pose0, tracker=None, **opts):
+        """The laser pose from which the map explains the scan best (gpis2_track_scan): damped Gauss-Newton on SE(2) from
+        pose0 (6 floats [t(2), R(4)]).  Returns (pose [6] f32, info) with H [3, 3], b [3] (xi = (vx, vy, omega)) and
+        "resid" [n]; opts and statuses as GPisMap3.track_depth."""
+        thetas = np.ascontiguousarray(thetas, dtype=np.float32).ravel()
+        ranges = np.ascontiguousarray(ranges, dtype=np.float32).ravel()
+        pose0 = np.ascontiguousarray(pose0, dtype=np.float32).ravel()
+        if pose0.size != 6 or thetas.size != ranges.size:
+            raise GpisError("bad 2-D track arguments")
+        if tracker is None:
+            if getattr(self, "_tracker", None) is None:
+                self._tracker = Tracker()
+            tracker = self._tracker
+        o = track_opts(2, **opts)
+        out = np.zeros(6, dtype=np.float32)
+        _check(self.L.gpis2_track_scan(self.h, tracker.h, _p(thetas), _p(ranges), thetas.size, _p(pose0), C.byref(o), _p(out),
+                                       None), "gpis2_track_scan")
+        return out, tracker.result()
 
 
 def _filter_var(verts, prims, rec, slot, max_var):
@@ -665,6 +728,69 @@ class Renderer:
         a, b, c = C.c_void_p(0), C.c_void_p(0), C.c_void_p(0)
         _check(self.L.gpis_render_device(self.h, C.byref(a), C.byref(b), C.byref(c)), "gpis_render_device")
         return a.value or 0, b.value or 0, c.value or 0
+
+
+def track_opts(dim, **opts):
+    """gpis_track_opts of the library's defaults for `dim` (gpis_track_default_opts) with the given fields replaced."""
+    o = gpis_track_opts()
+    _check(lib().gpis_track_default_opts(int(dim), C.byref(o)), "gpis_track_default_opts")
+    names = {f[0] for f in gpis_track_opts._fields_}
+    for k, v in opts.items():
+        if k not in names:
+            raise GpisError("unknown track option %r" % k)
+        setattr(o, k, v)
+    return o
+
+
+class Tracker:
+    """Result holder of the tracker (gpis_track_*): device buffers reused across calls."""
+
+    INFO_KEYS = ("status", "iterations", "passes", "points", "inliers", "cost0", "cost", "pass_ms", "k4_ms", "valid", "dim",
+                 "pixels", "evals")
+    INT_KEYS = ("status", "iterations", "passes", "points", "inliers", "valid", "dim", "pixels", "evals")
+
+    def __init__(self):
+        self.L = lib()
+        if self.L.gpis_device_count() < 1:
+            raise GpisError("no HIP device: gpismap_amd has no CPU fallback")
+        self.h = C.c_void_p(self.L.gpis_track_create())
+        if not self.h:
+            raise GpisError("gpis_track_create failed")
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.gpis_track_destroy(self.h)
+            self.h = None
+
+    __del__ = close
+
+    def set_chunk(self, points):
+        """Points per test() call within a pass (0 = default 2^22; results do not depend on it)."""
+        _check(self.L.gpis_track_set_chunk(self.h, int(points)), "gpis_track_set_chunk")
+
+    def info(self):
+        out = np.zeros(len(self.INFO_KEYS), dtype=np.float64)
+        _check(self.L.gpis_track_info(self.h, _p(out, C.c_double), out.size), "gpis_track_info")
+        d = dict(zip(self.INFO_KEYS, out.tolist()))
+        for k in self.INT_KEYS:
+            d[k] = int(d[k])
+        return d
+
+    def get(self):
+        """(H [n, n] f64, b [n] f64, resid [pixels] f32) of the last call (n = 6 / 3)."""
+        i = self.info()
+        n = 6 if i["dim"] == 3 else 3
+        H = np.zeros((n, n), dtype=np.float64)
+        b = np.zeros(n, dtype=np.float64)
+        resid = np.zeros(i["pixels"], dtype=np.float32)
+        _check(self.L.gpis_track_get(self.h, _p(H, C.c_double), _p(b, C.c_double), _p(resid)), "gpis_track_get")
+        return H, b, resid
+
+    def result(self):
+        """info() with "H", "b" and "resid" of the last call."""
+        d = self.info()
+        d["H"], d["b"], d["resid"] = self.get()
+        return d
 
 
 class ObsGP:

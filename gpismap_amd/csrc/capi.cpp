@@ -9,6 +9,7 @@
 #include "map_query.h"
 #include "mesh.h"
 #include "render.h"
+#include "track.h"
 #include "obsgp.h"
 #include "ongpis.h"
 
@@ -49,6 +50,10 @@ int gpis3_impl_extract(GPisMap3* g, MeshExtractor& me, const int* n3, const floa
 int gpis2_impl_extract(GPisMap* g, MeshExtractor& me, const int* n2, const float* origin2, const float* step2, float level, void* stream);
 int gpis3_impl_render(GPisMap3* g, Renderer& r, const float* cam4, const int* wh, const float* pose12, RenderOpts o, void* stream);
 int gpis2_impl_render(GPisMap* g, Renderer& r, const float* thetas, int n, const float* pose6, RenderOpts o, void* stream);
+int gpis3_impl_track(GPisMap3* g, Tracker& t, const float* cam4, const int* wh, const float* depth, const float* pose12, TrackOpts o,
+                     float* pose12_out, void* stream);
+int gpis2_impl_track(GPisMap* g, Tracker& t, const float* thetas, const float* ranges, int n, const float* pose6, TrackOpts o,
+                     float* pose6_out, void* stream);
 
 namespace gpis { int selftest_ranged_arith(unsigned long long seed, int blocks, int per_thread, int mode, unsigned long long* mismatches); }
 extern "C" {
@@ -579,6 +584,100 @@ int gpis_render_info(void* render, double* out, int n) {
                           (double)r.evals, r.k4_ms, (double)r.hits, (double)r.box_lo[0], (double)r.box_lo[1], (double)r.box_lo[2],
                           (double)r.box_hi[0], (double)r.box_hi[1], (double)r.box_hi[2], r.valid ? 1.0 : 0.0, r.mq_ms};
     for (int i = 0; i < n && i < 16; ++i) out[i] = v[i];
+    return GPIS_OK;
+}
+
+// ---- tracking ----------------------------------------------------------------------------------------------------------
+static TrackOpts track_opts(const gpis_track_opts* o) {
+    TrackOpts t;
+    t.max_residual = o->max_residual; t.huber = o->huber; t.max_var = o->max_var; t.damping = o->damping;
+    t.eps_t = o->eps_t; t.eps_r = o->eps_r; t.level = o->level; t.stride = o->stride; t.max_iters = o->max_iters;
+    t.min_inliers = o->min_inliers;
+    return t;
+}
+int gpis_track_default_opts(int dim, gpis_track_opts* o) {
+    if (!o || (dim != 2 && dim != 3)) return GPIS_ERR_ARG;
+    if (dim == 3) { o->max_residual = 0.05; o->huber = 0.01; o->min_inliers = 100; }
+    else { o->max_residual = 0.5; o->huber = 0.1; o->min_inliers = 20; }
+    o->max_var = INFINITY; o->damping = 1e-4; o->eps_t = 1e-5; o->eps_r = 1e-5; o->level = std::nanf("");
+    o->stride = 2; o->max_iters = 20;
+    return GPIS_OK;
+}
+void* gpis_track_create(void) {
+    if (gpis_device_count() < 1) { fprintf(stderr, "[gpismap_amd] no HIP device\n"); return nullptr; }
+    Tracker* t = new (std::nothrow) Tracker();
+    if (t && !t->own) { delete t; return nullptr; }
+    return t;
+}
+void gpis_track_destroy(void* tracker) { delete (Tracker*)tracker; }
+int gpis_track_set_chunk(void* tracker, int points) {
+    if (!tracker || points < 0) return GPIS_ERR_ARG;
+    ((Tracker*)tracker)->chunk = points ? points : (1 << 22);
+    return GPIS_OK;
+}
+// the checks that need no map: an argument error leaves the previous result readable
+static int track_args(void* tracker, int dim, const float* pose, const gpis_track_opts* opts, TrackOpts* o) {
+    if (!tracker || !pose) return GPIS_ERR_ARG;
+    gpis_track_opts d;
+    if (!opts) { (void)gpis_track_default_opts(dim, &d); opts = &d; }
+    *o = track_opts(opts);
+    const int np = dim == 3 ? 12 : 6;
+    for (int k = 0; k < np; ++k) if (!std::isfinite(pose[k])) return GPIS_ERR_ARG;
+    if (std::isinf(o->level)) return GPIS_ERR_ARG;
+    TrackOpts c = *o;
+    c.level = 0.f;                              // (resolved against the map by the entry)
+    return track_check_opts(c);
+}
+int gpis3_track_depth(void* m, void* tracker, const gpis_cam* cam, const float* depth, const float* pose12_init,
+                      const gpis_track_opts* opts, float* pose12_out, void* stream) {
+    if (!m || !depth) return GPIS_ERR_ARG;
+    TrackOpts o;
+    if (int rc = track_args(tracker, 3, pose12_init, opts, &o)) return rc;
+    float c4[4];
+    int wh[2];
+    if (cam) {
+        c4[0] = cam->fx; c4[1] = cam->fy; c4[2] = cam->cx; c4[3] = cam->cy; wh[0] = cam->width; wh[1] = cam->height;
+        TrackGeom g{};
+        g.dim = 3; g.fx = c4[0]; g.fy = c4[1]; g.cx = c4[2]; g.cy = c4[3]; g.width = wh[0]; g.height = wh[1];
+        if (int rc = track_check_geom(g, (long long)wh[0] * wh[1])) return rc;
+    }
+    Tracker& t = *(Tracker*)tracker;
+    const int rc = gpis3_impl_track((GPisMap3*)m, t, cam ? c4 : nullptr, cam ? wh : nullptr, depth, pose12_init, o, pose12_out, stream);
+    if (rc != GPIS_OK && rc != GPIS_ERR_ARG && rc != GPIS_ERR_LIMIT) t.clear_result();
+    return rc;
+}
+int gpis2_track_scan(void* m, void* tracker, const float* thetas, const float* ranges, int n, const float* pose6_init,
+                     const gpis_track_opts* opts, float* pose6_out, void* stream) {
+    if (!m || !thetas || !ranges || n < 1) return GPIS_ERR_ARG;
+    TrackOpts o;
+    if (int rc = track_args(tracker, 2, pose6_init, opts, &o)) return rc;
+    for (int k = 0; k < n; ++k) if (!std::isfinite(thetas[k])) return GPIS_ERR_ARG;
+    if ((long long)n > Tracker::kMaxPoints) return GPIS_ERR_LIMIT;
+    Tracker& t = *(Tracker*)tracker;
+    const int rc = gpis2_impl_track((GPisMap*)m, t, thetas, ranges, n, pose6_init, o, pose6_out, stream);
+    if (rc != GPIS_OK && rc != GPIS_ERR_ARG && rc != GPIS_ERR_LIMIT) t.clear_result();
+    return rc;
+}
+int gpis_track_get(void* tracker, double* H, double* b, float* resid) {
+    if (!tracker) return GPIS_ERR_ARG;
+    Tracker& t = *(Tracker*)tracker;
+    if (!t.valid) return GPIS_ERR_STATE;
+    const int nj = t.dim == 3 ? 6 : 3;
+    if (H) for (int k = 0; k < nj * nj; ++k) H[k] = t.H[k];
+    if (b) for (int k = 0; k < nj; ++k) b[k] = t.b[k];
+    if (resid) {
+        DeviceScope ds(t.device);
+        GPIS_HIP(hipMemcpyAsync(resid, t.d_resid, sizeof(float) * (size_t)t.pixels, hipMemcpyDeviceToHost, t.own));
+        GPIS_HIP(hipStreamSynchronize(t.own));
+    }
+    return GPIS_OK;
+}
+int gpis_track_info(void* tracker, double* out, int n) {
+    if (!tracker || !out || n < 0) return GPIS_ERR_ARG;
+    const Tracker& t = *(Tracker*)tracker;
+    const double v[13] = {(double)t.status, (double)t.iterations, (double)t.passes, (double)t.points, t.inliers, t.cost0, t.cost,
+                          t.pass_ms, t.k4_ms, t.valid ? 1.0 : 0.0, (double)t.dim, (double)t.pixels, (double)t.evals};
+    for (int i = 0; i < n && i < 13; ++i) out[i] = v[i];
     return GPIS_OK;
 }
 

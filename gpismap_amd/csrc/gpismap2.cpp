@@ -13,6 +13,7 @@
 #include "map_query.h"
 #include "mesh.h"
 #include "render.h"
+#include "track.h"
 #include "obsgp.h"
 #include "ongpis.h"
 
@@ -691,6 +692,37 @@ int gpis2_impl_render(GPisMap* g, Renderer& r, const float* thetas, int n, const
     if (rc != GPIS_OK) { m.fail_rc = rc; fprintf(stderr, "[gpismap_amd] gpis2_render_scan: device path failed (%d)\n", rc); }
     return rc;
 } catch (const std::exception& e) { nothrow_report("gpis2_render_scan", e.what()); return GPIS_ERR_STATE; } catch (...) { nothrow_report("gpis2_render_scan", "unknown exception"); return GPIS_ERR_STATE; }
+
+// Scan tracking (gpis2_track_scan): testDevice's checks and join, then the iterations through the map's MapQuery.  The beams'
+// cos / sin in double on the host (polar2Cart); the sensor offset of the map's parameters.  A map without a tree: status 2.
+int gpis2_impl_track(GPisMap* g, Tracker& t, const float* thetas, const float* ranges, int n, const float* pose6, TrackOpts o,
+                     float* pose6_out, void* hip_stream) try {
+    GPisMap::Impl& m = *g->impl();
+    DeviceScope dev_scope_(m.device);
+    m.fail_rc = 0;
+    if (!m.ok) return GPIS_ERR_HIP;
+    TrackGeom geo{};
+    geo.dim = 2;
+    geo.off[0] = m.setting.sensor_offset[0]; geo.off[1] = m.setting.sensor_offset[1];
+    if (std::isnan(o.level)) o.level = -m.setting.fbias;
+    if (int rc = track_check_geom(geo, n)) return rc;
+    if (int rc = track_check_opts(o)) return rc;
+    std::vector<double> cs((size_t)2 * n);
+    for (int k = 0; k < n; ++k) {
+        if (!std::isfinite(thetas[k])) return GPIS_ERR_ARG;
+        cs[2 * (size_t)k] = std::cos((double)thetas[k]);
+        cs[2 * (size_t)k + 1] = std::sin((double)thetas[k]);
+    }
+    if (int rc = t.bind(m.device)) return rc;
+    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : m.stream;
+    if (m.has_tree) (void)m.join_training();
+    double p0[6];
+    for (int k = 0; k < 6; ++k) p0[k] = pose6[k];
+    const int rc = t.track(m.mq, m.store, m.has_tree, geo, ranges, cs.data(), n, p0, o, s);
+    if (rc != GPIS_OK) { m.fail_rc = rc; fprintf(stderr, "[gpismap_amd] gpis2_track_scan: device path failed (%d)\n", rc); }
+    if (rc == GPIS_OK && pose6_out) for (int k = 0; k < 6; ++k) pose6_out[k] = (float)t.pose[k];
+    return rc;
+} catch (const std::exception& e) { nothrow_report("gpis2_track_scan", e.what()); return GPIS_ERR_STATE; } catch (...) { nothrow_report("gpis2_track_scan", "unknown exception"); return GPIS_ERR_STATE; }
 
 int gpis2_impl_fail(GPisMap* g) { return g->impl()->fail_rc; }
 int gpis2_impl_device(GPisMap* g) { return g->impl()->device; }

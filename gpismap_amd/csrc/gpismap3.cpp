@@ -26,6 +26,7 @@
 #include "map_query.h"
 #include "mesh.h"
 #include "render.h"
+#include "track.h"
 #include "obsgp.h"
 #include "ongpis.h"
 
@@ -1990,6 +1991,37 @@ int gpis3_impl_render(GPisMap3* g, Renderer& r, const float* cam4, const int* wh
     if (rc == GPIS_ERR_STATE) m.build_cluster_table();   // (models dropped by the inverse pass: their cells have no GP any more)
     return rc;
 } catch (const std::exception& e) { nothrow_report("gpis3_render_depth", e.what()); return GPIS_ERR_STATE; } catch (...) { nothrow_report("gpis3_render_depth", "unknown exception"); return GPIS_ERR_STATE; }
+
+// Depth tracking (gpis3_track_depth): testDevice's checks and joins, then the iterations through the map's own MapQuery on the
+// lead device.  cam4 (fx, fy, cx, cy) and wh (width, height) NULL: the map's camera; o.level NaN: -fbias.  A map without a tree
+// is no error: every record keeps f = NaN (status 2).
+int gpis3_impl_track(GPisMap3* g, Tracker& t, const float* cam4, const int* wh, const float* depth, const float* pose12, TrackOpts o,
+                     float* pose12_out, void* hip_stream) try {
+    GPisMap3::Impl& m = *g->impl();
+    DeviceScope dev_scope_(m.device);
+    m.fail_rc = 0;
+    if (!m.ok) return GPIS_ERR_HIP;
+    if (m.table_pending) { fprintf(stderr, "[gpismap_amd] gpis3_track_depth: sharded update not finished (gpis3_shard_finish)\n"); return GPIS_ERR_STATE; }
+    TrackGeom geo{};
+    geo.dim = 3;
+    geo.fx = cam4 ? cam4[0] : m.cam.fx; geo.fy = cam4 ? cam4[1] : m.cam.fy;
+    geo.cx = cam4 ? cam4[2] : m.cam.cx; geo.cy = cam4 ? cam4[3] : m.cam.cy;
+    geo.width = cam4 ? wh[0] : m.cam.width; geo.height = cam4 ? wh[1] : m.cam.height;
+    if (std::isnan(o.level)) o.level = -m.setting.fbias;
+    const long long n = (long long)geo.width * geo.height;
+    if (int rc = track_check_geom(geo, n)) return rc;
+    if (int rc = track_check_opts(o)) return rc;
+    if (int rc = t.bind(m.device)) return rc;
+    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : m.stream;
+    if (m.has_tree) m.finish_training();
+    double p0[12];
+    for (int k = 0; k < 12; ++k) p0[k] = pose12[k];
+    const int rc = t.track(m.mq, m.store, m.has_tree, geo, depth, nullptr, n, p0, o, s);
+    if (rc != GPIS_OK) { m.fail_rc = rc; fprintf(stderr, "[gpismap_amd] gpis3_track_depth: device path failed (%d)\n", rc); }
+    if (rc == GPIS_ERR_STATE) m.build_cluster_table();   // (models dropped by the inverse pass: their cells have no GP any more)
+    if (rc == GPIS_OK && pose12_out) for (int k = 0; k < 12; ++k) pose12_out[k] = (float)t.pose[k];
+    return rc;
+} catch (const std::exception& e) { nothrow_report("gpis3_track_depth", e.what()); return GPIS_ERR_STATE; } catch (...) { nothrow_report("gpis3_track_depth", "unknown exception"); return GPIS_ERR_STATE; }
 
 // accessors used by the C-ABI (capi.cpp)
 int gpis3_impl_fail(GPisMap3* g) { return g->impl()->fail_rc; }

@@ -81,6 +81,12 @@ private:
              hipStream_t s);
 };
 
+// The renderer's deterministic compaction, shared with the tracker (track.hip): out[0 .. count) = the entries e < n of `in` (the
+// identity when in is null) whose flag[e] is set, in order; one exclusive scan over at most kCompactBlocks contiguous segments
+// (no atomics).  d_part: kCompactBlocks + 1 device ints; h_cnt: one page-locked int.  Synchronises `s`.
+constexpr int kCompactBlocks = 1024;
+int compact_flags(const uint8_t* flag, const int* in, long long n, int* out, int* d_part, int* h_cnt, hipStream_t s, long long* count);
+
 // Argument checks shared by the C-ABI entries: GPIS_OK, GPIS_ERR_ARG, or GPIS_ERR_LIMIT (more than kMaxRays rays).
 int render_check_opts(const RenderOpts& o);
 int render_check_geom(const RayGeom& g, long long n);

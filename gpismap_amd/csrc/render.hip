@@ -18,7 +18,7 @@ namespace {
 
 constexpr int kBlock = 256;
 constexpr int kGridCap = 2048;
-constexpr int kScanBlocks = 1024;     // compaction segments (one thread each in the top scan)
+constexpr int kScanBlocks = kCompactBlocks;   // compaction segments (one thread each in the top scan)
 constexpr uint8_t kRunning = 255;     // status of a ray still marching
 
 inline int grid_for(long long n) { return (int)std::max(1ll, std::min((long long)kGridCap, (n + kBlock - 1) / kBlock)); }
@@ -321,16 +321,19 @@ int Renderer::ensure(long long n, int dm) {
     return GPIS_OK;
 }
 
-// out[0 .. count) = the entries e < n of `in` (the identity when in is null) whose flag is set, in order
 int Renderer::compact(const int* in, long long n, int* out, hipStream_t s, long long* count) {
+    return compact_flags(d_flag, in, n, out, d_part, h_cnt, s, count);
+}
+
+int compact_flags(const uint8_t* flag, const int* in, long long n, int* out, int* d_part, int* h_cnt, hipStream_t s, long long* count) {
     *count = 0;
     if (n <= 0) return GPIS_OK;
     const long long per = (n + kScanBlocks - 1) / kScanBlocks;
     const int seg = (int)std::max((long long)kBlock, (per + kBlock - 1) / kBlock * kBlock);
     const int nb = (int)((n + seg - 1) / seg);
-    hipLaunchKernelGGL(render_count_kernel, dim3(nb), dim3(kBlock), 0, s, d_flag, (int)n, seg, d_part);
+    hipLaunchKernelGGL(render_count_kernel, dim3(nb), dim3(kBlock), 0, s, flag, (int)n, seg, d_part);
     hipLaunchKernelGGL(render_top_kernel, dim3(1), dim3(1024), 0, s, d_part, nb);
-    hipLaunchKernelGGL(render_scatter_kernel, dim3(nb), dim3(kBlock), 0, s, in, d_flag, (int)n, seg, d_part, out);
+    hipLaunchKernelGGL(render_scatter_kernel, dim3(nb), dim3(kBlock), 0, s, in, flag, (int)n, seg, d_part, out);
     GPIS_HIP(hipGetLastError());
     GPIS_HIP(hipMemcpyAsync(h_cnt, d_part + nb, sizeof(int), hipMemcpyDeviceToHost, s));
     GPIS_HIP(hipStreamSynchronize(s));       // (the one synchronisation a march pass adds to test()'s own)

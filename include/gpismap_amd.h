@@ -348,6 +348,67 @@ int   gpis_render_device(void* render, const float** d_depth, const float** d_re
  * 1 if a result is held, ms of host wall time inside the test() passes (each ends synchronised) */
 int   gpis_render_info(void* render, double* out, int n);
 
+/* ---- tracking: depth-camera and laser poses against the map on the device -----------------------------
+ * The inverse question of rendering: from which pose does the sensor see this frame?  Damped Gauss-Newton on SE(3) (3-D) /
+ * SE(2) (2-D); every iteration is one test() pass over the frame's points, whose residual and Jacobian terms are reduced to the
+ * normal equations on the device; only the sums (29 / 11 doubles) leave it, and the host solves the 6x6 / 3x3 system.
+ * 3-D points: update()'s sampling with obs_skip = stride: pixels (col, row) = (n stride, m stride), n < W / stride,
+ * m < H / stride, column-major (k = col * H + row ascending), used iff 0.4 < (double)z < 4; u = ((float)col - cx) / fx,
+ * v = ((float)row - cy) / fy, local point (u z, v z, z), world R[i] x + R[3+i] y + R[6+i] z + t[i] left to right in float32
+ * without FMA, R and t the current double pose cast to float (pose12 = [t(3), R(9)] column-major): the point update() would
+ * insert with that pose.  2-D points: beams with 0.2 < (double)r < 30 in input order, local ((float)(r c) + off0,
+ * (float)(r s) + off1) with c, s = cos, sin((double)theta) on the host and the map's sensor offset, world R local + t
+ * (pose6 = [t(2), R(4)]).  Records: test() pre-filled with f = NaN, zeros elsewhere.  r = f - level (float32); a point is an
+ * inlier iff f and the gradient are finite, var_f <= max_var and |r| <= max_residual; Huber weight w = 1 if |r| <= huber, else huber / |r|.
+ * Jacobian (double, from the float values; rotation about the sensor centre): 3-D J = [g ; (p - t) x g], xi = (v, omega);
+ * 2-D J = [gx, gy, (px - tx) gy - (py - ty) gx]; p the float world point queried, t the float translation, g the gradient.
+ * Sums over the inliers in double: the upper triangle of H = sum w J J^T, b = sum w J r, sum w r^2, the inlier count, reduced
+ * by a fixed halving tree (segments of 256 points, then the segment partials): the same bits for every chunk size, launch
+ * shape, update mode and device count.  Step: (H + damping diag(H)) delta = -b by Cholesky; R <- Exp(omega) R, t <- t + v
+ * (Rodrigues in double; 2-D a rotation by omega).  Status: 0 converged (|v| < eps_t and |omega| < eps_r after a step),
+ * 1 max_iters steps taken, 2 fewer than min_inliers inliers (the last good pose is returned), 3 a non-positive Cholesky pivot
+ * (the pose is not moved).  The reported H, b, cost, inliers and residual image belong to the returned pose: after the last
+ * step one more pass runs there (passes = iterations + 1; + 2 when status 2 follows a step).  max_iters = 0 evaluates the
+ * given pose only.  A map without points is no error: status 2.
+ * Errors: a bad camera (size < 1, fx or fy zero or non-finite), a non-finite pose or beam angle, n < 1, stride < 1,
+ * max_iters < 0, min_inliers < 0, a negative or NaN max_residual / max_var / damping / eps, an infinite damping, huber <= 0 or
+ * non-finite, an infinite level -> GPIS_ERR_ARG, the previous result untouched; more than 2^26 pixels / beams ->
+ * GPIS_ERR_LIMIT before anything is allocated, the previous result untouched.  Any other failure (an unfinished sharded
+ * update: GPIS_ERR_STATE; the test() path's status) leaves no result.  A tracker holds grow-only device buffers (about 60 B per
+ * point, 8 B per pixel) reused across calls; every call returns with its work finished.  A map over several devices tracks
+ * on its lead device. */
+typedef struct gpis_track_opts {
+    double max_residual;        /* inlier: |r| <= max_residual */
+    double huber;               /* Huber threshold */
+    double max_var;             /* inlier: var_f <= max_var (+inf: no variance test) */
+    double damping;             /* lambda of (H + lambda diag(H)) */
+    double eps_t, eps_r;        /* convergence: |v| < eps_t (m) and |omega| < eps_r (rad) */
+    float level;                /* NaN = -fbias (the level of the map's surface points) */
+    int stride;                 /* 3-D pixel stride (update()'s obs_skip); ignored in 2-D */
+    int max_iters;              /* Gauss-Newton steps at most (0: evaluate the given pose) */
+    int min_inliers;            /* fewer inliers: status 2 */
+} gpis_track_opts;
+/* defaults.  3-D: stride 2, max_residual 0.05, huber 0.01, min_inliers 100; 2-D: max_residual 0.5, huber 0.1, min_inliers 20;
+ * both: max_var +inf, damping 1e-4, eps_t 1e-5, eps_r 1e-5, max_iters 20, level NaN */
+int   gpis_track_default_opts(int dim, gpis_track_opts* opts);
+void* gpis_track_create(void);                             /* on the current device; NULL without one */
+void  gpis_track_destroy(void* tracker);
+/* points per test() call within a pass (test hook: the results do not depend on it); 0 = 2^22 */
+int   gpis_track_set_chunk(void* tracker, int points);
+/* depth [W*H] column-major as update(); cam NULL: the map's camera; opts NULL: the defaults; pose12_out (may be NULL): the
+ * returned pose; hip_stream NULL: the map's */
+int   gpis3_track_depth(void* map, void* tracker, const gpis_cam* cam, const float* depth, const float* pose12_init,
+                        const gpis_track_opts* opts, float* pose12_out, void* hip_stream);
+/* thetas, ranges [n] as update() */
+int   gpis2_track_scan(void* map, void* tracker, const float* thetas, const float* ranges, int n, const float* pose6_init,
+                       const gpis_track_opts* opts, float* pose6_out, void* hip_stream);
+/* host copies of the last result (any pointer may be NULL): H [n x n] row-major and b [n] (n = 6 / 3) at the returned pose,
+ * the residual per pixel / beam (r of the inliers, NaN elsewhere); GPIS_ERR_STATE without one */
+int   gpis_track_get(void* tracker, double* H, double* b, float* resid);
+/* out[0..n): status, iterations, passes, points used, inliers, initial cost, final cost, ms of host wall time in the passes,
+ * ms inside K4 (only while the map's profiling is on), 1 if a result is held, dim, pixels / beams, K4 evaluations */
+int   gpis_track_info(void* tracker, double* out, int n);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,396 @@
+"""Tracking on the GPU (csrc/track.hip, gpis3_track_depth / gpis2_track_scan / gpis_track_*): the device call against the numpy
+reference (tests/track_ref.py) driven by the same map's host test(), bit for bit; the reference driven by the CPU oracle; pose
+recovery on the synthetic map, on held-out bigbird frames and on gazebo scans; determinism across runs, chunkings, update
+modes and a two-shard map; the error paths, the empty map, the evaluate-only call and an ill-conditioned plane."""
+import ctypes as C
+import math
+
+import numpy as np
+import pytest
+
+import oracle_lib
+import replay
+import track_ref
+
+pytestmark = pytest.mark.gpu
+F32 = np.float32
+U32 = np.uint32
+LEVEL = -0.2                      # -fbias of both maps
+OFF2 = (0.08, 0.0)                # the 2-D map's default sensor offset
+SYN_CAM = (284.0, 284.0, 155.0, 112.0, 320, 240)
+
+
+def _bits_equal(a, b):
+    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
+    return a.shape == b.shape and np.array_equal(a.view(U32 if a.dtype == F32 else np.uint64),
+                                                 b.view(U32 if b.dtype == F32 else np.uint64))
+
+
+def _same(x, y):
+    """Two (pose, info) results with the same bits."""
+    (p, a), (q, b) = x, y
+    return (_bits_equal(p, q) and all(a[k] == b[k] for k in ("status", "iterations", "passes", "points", "inliers"))
+            and _bits_equal(np.float64([a["cost0"], a["cost"]]), np.float64([b["cost0"], b["cost"]]))
+            and _bits_equal(a["H"], b["H"]) and _bits_equal(a["b"], b["b"]) and _bits_equal(a["resid"], b["resid"]))
+
+
+def _check_bits(out, ref, what):
+    pose, info = out
+    print("%s: status %d, %d iterations, %d passes, %d points, %d inliers, cost %.4e -> %.4e"
+          % (what, info["status"], info["iterations"], info["passes"], info["points"], info["inliers"], info["cost0"], info["cost"]))
+    assert (info["status"], info["iterations"], info["passes"], info["points"]) == \
+        (ref["status"], ref["iterations"], ref["passes"], ref["points"]), what
+    assert info["inliers"] == ref["inliers"], what
+    assert _bits_equal(pose, ref["pose"]), (what, pose, ref["pose"])
+    assert _bits_equal(np.float64([info["cost0"], info["cost"]]), np.float64([ref["cost0"], ref["cost"]])), what
+    assert _bits_equal(info["H"], ref["H"]) and _bits_equal(info["b"], ref["b"]), what
+    assert _bits_equal(info["resid"], ref["resid"]), what
+
+
+# ---- maps and poses -------------------------------------------------------------------------------------------------------
+def _synthetic_map(frames=5, **kw):
+    import gpismap_amd
+    gm = gpismap_amd.GPisMap3(**kw)
+    for fr in range(frames):
+        gm.update(replay.synthetic_depth(fr), replay.IDENTITY_POSE)
+    return gm
+
+
+def _bigbird_map(ids=range(5), devices=None, pipeline=True):
+    import gpismap_amd
+    frames = replay.load_bigbird()
+    ids = list(ids)
+    gm = gpismap_amd.GPisMap3(frames[ids[0]]["cam"], devices=devices)
+    if not pipeline:
+        gm.set_pipeline(False)
+    for i in ids:
+        gm.set_camera(frames[i]["cam"])
+        gm.update(frames[i]["depth"], frames[i]["pose"])
+    return gm, frames
+
+
+def _gazebo_map(ids=None, pipeline=True):
+    import gpismap_amd
+    gm = gpismap_amd.GPisMap()
+    if not pipeline:
+        gm.set_pipeline(False)
+    frames = replay.load_gazebo()
+    for i in (range(len(frames)) if ids is None else ids):
+        gm.update(frames[i]["thetas"], frames[i]["ranges"], frames[i]["pose"])
+    return gm, frames
+
+
+def _rot(axis, ang):
+    a = np.asarray(axis, np.float64)
+    a = a / np.linalg.norm(a)
+    K = np.array([[0, -a[2], a[1]], [a[2], 0, -a[0]], [-a[1], a[0], 0]])
+    return np.eye(3) + math.sin(ang) * K + (1 - math.cos(ang)) * K @ K
+
+
+def _R3(P):
+    return np.asarray(P[3:], np.float64).reshape(3, 3).T
+
+
+def _perturb3(P, dt, deg, axis=(0.4, -1.0, 0.7), tdir=(1.0, -0.8, 0.9)):
+    """P moved by dt metres along tdir and turned by deg degrees about axis (about the sensor centre)."""
+    d = np.asarray(tdir, np.float64)
+    t = np.asarray(P[:3], np.float64) + dt * d / np.linalg.norm(d)
+    R = _rot(axis, math.radians(deg)) @ _R3(P)
+    return np.concatenate([t, R.T.ravel()]).astype(F32)
+
+
+def _err3(P, Q):
+    c = (np.trace(_R3(P).T @ _R3(Q)) - 1) / 2
+    return (float(np.linalg.norm(np.asarray(P[:3], np.float64) - np.asarray(Q[:3], np.float64))),
+            math.degrees(math.acos(min(1.0, max(-1.0, c)))))
+
+
+def _perturb2(P, dt, deg, tdir=(1.0, -0.9)):
+    d = np.asarray(tdir, np.float64)
+    t = np.asarray(P[:2], np.float64) + dt * d / np.linalg.norm(d)
+    th = math.atan2(float(P[3]), float(P[2])) + math.radians(deg)
+    c, s = math.cos(th), math.sin(th)
+    return np.array([t[0], t[1], c, s, -s, c], F32)
+
+
+def _err2(P, Q):
+    dth = math.atan2(float(P[3]), float(P[2])) - math.atan2(float(Q[3]), float(Q[2]))
+    dth = (dth + math.pi) % (2 * math.pi) - math.pi
+    return float(np.hypot(float(P[0]) - float(Q[0]), float(P[1]) - float(Q[1]))), abs(math.degrees(dth))
+
+
+def _quarter(frame, k=4):
+    """A bigbird frame at 1/k resolution: every k-th pixel of every k-th column, the camera scaled to match."""
+    cam = frame["cam"]
+    W, H = int(cam[4]), int(cam[5])
+    d = frame["depth"].reshape(W, H)[::k, ::k]
+    return np.ascontiguousarray(d).ravel(), (cam[0] / k, cam[1] / k, cam[2] / k, cam[3] / k, d.shape[0], d.shape[1])
+
+
+def _ref3(test_fn, depth, cam, pose0, **kw):
+    return track_ref.track_depth(test_fn, depth, cam, pose0, track_ref.Opts(3, level=LEVEL, **kw))
+
+
+def _ref2(test_fn, thetas, ranges, pose0, **kw):
+    return track_ref.track_scan(test_fn, thetas, ranges, pose0, OFF2, track_ref.Opts(2, level=LEVEL, **kw))
+
+
+SYN_TRUE = _perturb3(replay.IDENTITY_POSE, 0.015, 1.0, axis=(1.0, 2.0, -1.0), tdir=(0.6, -1.0, 0.5))
+
+
+# ---- bits -----------------------------------------------------------------------------------------------------------------
+def test_bits_synthetic_320x240():
+    gm = _synthetic_map()
+    depth, _, st = gm.render_depth(SYN_TRUE, cam6=SYN_CAM)
+    assert np.count_nonzero(st == 0) > 0.5 * st.size
+    start = _perturb3(SYN_TRUE, 0.02, 2.0)
+    out = gm.track_depth(depth, start, cam6=SYN_CAM)
+    _check_bits(out, _ref3(lambda x, res: gm.test(x, res), depth, SYN_CAM, start), "synthetic 320x240")
+    assert out[1]["points"] > 15000
+
+
+def test_bits_bigbird_quarter_frames():
+    gm, frames = _bigbird_map()
+    for i in (0, 2, 4):
+        depth, cam = _quarter(frames[i])
+        start = _perturb3(frames[i]["pose"], 0.01, 1.0)
+        out = gm.track_depth(depth, start, cam6=cam)
+        assert out[1]["inliers"] > 100
+        _check_bits(out, _ref3(lambda x, res: gm.test(x, res), depth, cam, start), "bigbird frame %d at 1/4" % i)
+
+
+def test_bits_gazebo_scans():
+    gm, frames = _gazebo_map()
+    for i in (0, len(frames) // 2, len(frames) - 1):
+        fr = frames[i]
+        start = _perturb2(fr["pose"], 0.05, 1.0)
+        out = gm.track_scan(fr["thetas"], fr["ranges"], start)
+        assert out[1]["inliers"] > 20
+        _check_bits(out, _ref2(lambda x, res: gm.test(x, res), fr["thetas"], fr["ranges"], start), "gazebo scan %d" % i)
+
+
+def test_oracle_cross_check_64x48():
+    """bigbird frame 0 at 1/10: the reference driven by the CPU oracle (tiled mode, the kernels' arithmetic) gives the GPU call."""
+    gm, frames = _bigbird_map(ids=[0])
+    om = oracle_lib.OracleMap3(frames[0]["cam"])
+    om.update(frames[0]["depth"], frames[0]["pose"])
+    depth, cam = _quarter(frames[0], 10)
+    start = _perturb3(frames[0]["pose"], 0.01, 1.0)
+    out = gm.track_depth(depth, start, cam6=cam, stride=1, min_inliers=20)
+
+    def ofn(x, res):
+        assert om.L.orc3_test(om.h, x.ctypes.data_as(C.POINTER(C.c_float)), 3, x.shape[0], res.ctypes.data_as(C.POINTER(C.c_float)))
+        return res
+    assert out[1]["inliers"] > 20
+    _check_bits(out, _ref3(ofn, depth, cam, start, stride=1, min_inliers=20), "oracle 64x48")
+
+
+# ---- recovery -------------------------------------------------------------------------------------------------------------
+# Bounds from the first run on an MI355X with a 1.5x margin (DESIGN.md §7d has the measured values).  The synthetic wall is
+# tracked with the rotation recovered but the in-plane translation drifting: test()'s f is not a distance (its slope over 1 cm
+# is about a third of its gradient), so the linearisation is poor until the pose is within millimetres -- a measured miss
+# against the issue's estimate, kept here as a guard rather than a claim.
+SYN_BOUND = (0.066, 1.03)                  # metres, degrees (measured 0.0434 m, 0.681 deg from 0.02 m, 2 deg)
+BB_BOUND = {2: (0.015, 1.2), 17: (0.029, 2.25)}    # measured 2: 0.0097 m 0.79 deg; 17: 0.0189 m 1.49 deg (not recovered)
+GZ_BOUND = (0.016, 0.22)                   # measured 0.0083 - 0.0106 m, 0.047 - 0.146 deg from 0.1 m, 2 deg
+
+
+def test_recovery_synthetic():
+    """Depth rendered from SYN_TRUE (1.5 cm and 1 degree off the identity), tracked from a further 2 cm / 2 degrees."""
+    gm = _synthetic_map()
+    depth, _, st = gm.render_depth(SYN_TRUE)
+    start = _perturb3(SYN_TRUE, 0.02, 2.0)
+    pose, info = gm.track_depth(depth, start)
+    e0, e = _err3(start, SYN_TRUE), _err3(pose, SYN_TRUE)
+    print("synthetic 640x480: start %.4f m %.3f deg -> %.2e m %.2e deg; status %d, %d iterations, %d points, %d inliers"
+          % (e0 + e + (info["status"], info["iterations"], info["points"], info["inliers"])))
+    assert info["status"] in (0, 1) and info["cost"] < info["cost0"]
+    assert e[1] < e0[1]
+    assert e[0] <= SYN_BOUND[0] and e[1] <= SYN_BOUND[1]
+
+
+def _neighbours(frames, k, n):
+    c = np.array([f["pose"][:3] for f in frames], np.float64)
+    d = np.linalg.norm(c - c[k], axis=1)
+    d[k] = np.inf
+    return sorted(np.argsort(d)[:n].tolist())
+
+
+def test_recovery_bigbird_held_out_frames():
+    frames = replay.load_bigbird()
+    errs = []
+    for k in (2, 17):
+        ids = _neighbours(frames, k, 4)
+        gm, _ = _bigbird_map(ids)
+        fr = frames[k]
+        start = _perturb3(fr["pose"], 0.02, 2.0)
+        pose, info = gm.track_depth(fr["depth"], start, cam6=fr["cam"])
+        e0, e = _err3(start, fr["pose"]), _err3(pose, fr["pose"])
+        print("bigbird frame %d (map %s): start %.4f m %.3f deg -> %.2e m %.3f deg; status %d, %d iterations, %d of %d inliers"
+              % ((k, ids) + e0 + e + (info["status"], info["iterations"], info["inliers"], info["points"])))
+        errs.append((k, e))
+        assert info["status"] in (0, 1)
+    for k, e in errs:
+        assert e[0] <= BB_BOUND[k][0] and e[1] <= BB_BOUND[k][1], (k, e)
+
+
+def test_recovery_gazebo_scans():
+    frames = replay.load_gazebo()
+    for k in (6, 14, 22):
+        gm, _ = _gazebo_map(range(k))
+        fr = frames[k]
+        start = _perturb2(fr["pose"], 0.1, 2.0)
+        pose, info = gm.track_scan(fr["thetas"], fr["ranges"], start)
+        e0, e = _err2(start, fr["pose"]), _err2(pose, fr["pose"])
+        odo = _err2(frames[k - 1]["pose"], fr["pose"])
+        print("gazebo scan %d (map of scans < %d): start %.3f m %.2f deg -> %.2e m %.3f deg; status %d, %d iterations, %d of %d "
+              "inliers; motion from scan %d: %.2f m %.1f deg"
+              % ((k, k) + e0 + e + (info["status"], info["iterations"], info["inliers"], info["points"], k - 1) + odo))
+        assert info["status"] in (0, 1)
+        assert e[0] <= GZ_BOUND[0] and e[1] <= GZ_BOUND[1]
+
+
+# ---- invariance -----------------------------------------------------------------------------------------------------------
+def test_deterministic_across_runs_chunks_modes_devices():
+    import gpismap_amd
+    gm, frames = _bigbird_map()
+    fr = frames[2]
+    depth, cam = _quarter(fr, 2)
+    start = _perturb3(fr["pose"], 0.01, 1.0)
+    t = gpismap_amd.Tracker()
+    a = gm.track_depth(depth, start, cam6=cam, tracker=t)
+    b = gm.track_depth(depth, start, cam6=cam, tracker=t)
+    others = [b]
+    for ch in (1000, 7):
+        tc = gpismap_amd.Tracker()
+        tc.set_chunk(ch)
+        others.append(gm.track_depth(depth, start, cam6=cam, tracker=tc))
+    others.append(_bigbird_map(pipeline=False)[0].track_depth(depth, start, cam6=cam))
+    others.append(_bigbird_map(devices=[0, 0])[0].track_depth(depth, start, cam6=cam))
+    assert a[1]["inliers"] > 300
+    for o in others:
+        assert _same(o, a)
+    g2, f2 = _gazebo_map()
+    s2, _ = _gazebo_map(pipeline=False)
+    th, rg, p2 = f2[5]["thetas"], f2[5]["ranges"], _perturb2(f2[5]["pose"], 0.05, 1.0)
+    x = g2.track_scan(th, rg, p2)
+    m2 = gpismap_amd.Tracker()
+    m2.set_chunk(7)
+    y = g2.track_scan(th, rg, p2, tracker=m2)
+    z = s2.track_scan(th, rg, p2)
+    assert _same(x, y) and _same(x, z)
+
+
+# ---- evaluation, degeneracy, errors ---------------------------------------------------------------------------------------
+def test_max_iters_zero_evaluates_the_given_pose():
+    gm = _synthetic_map()
+    depth, _, _ = gm.render_depth(SYN_TRUE, cam6=SYN_CAM)
+    P = _perturb3(SYN_TRUE, 0.005, 0.5)
+    pose, info = gm.track_depth(depth, P, cam6=SYN_CAM, max_iters=0)
+    assert info["status"] == 1 and info["iterations"] == 0 and info["passes"] == 1
+    assert _bits_equal(pose, P)
+    assert info["cost"] == info["cost0"] > 0
+    ref = _ref3(lambda x, res: gm.test(x, res), depth, SYN_CAM, P, max_iters=0)
+    assert _bits_equal(info["H"], ref["H"]) and info["cost"] == ref["cost"]
+
+
+# smallest / largest eigenvalue of H on a plane: 1.72e-3 on the first MI355X run, x 1.5
+WALL_COND = 2.6e-3
+
+
+def test_plane_is_ill_conditioned():
+    """A map of a tilted plane: sliding along it and turning about its normal leave r unchanged, so three eigenvalues of H
+    are small.  (A wall of one constant depth gives the map no surface at all: its test() answers f = 0, no gradient.)"""
+    import gpismap_amd
+    gm = gpismap_amd.GPisMap3()
+    k = np.arange(640 * 480)
+    u = ((k // 480) - 310.0) / 568.0
+    wall = (1.0 / (1.0 - 0.3 * u)).astype(F32)          # the plane z = 1 + 0.3 x seen from the identity pose
+    for _ in range(2):
+        gm.update(wall, replay.IDENTITY_POSE)
+    pose, info = gm.track_depth(wall, replay.IDENTITY_POSE, max_iters=0)
+    assert np.all(np.isfinite(info["H"])), info["H"]
+    ev = np.linalg.eigvalsh(info["H"])
+    print("plane: %d inliers, eigenvalues of H %s, smallest / largest %.3e" % (info["inliers"], ev, ev[0] / ev[-1]))
+    assert info["inliers"] > 1000
+    assert ev[0] / ev[-1] < WALL_COND
+
+
+def test_empty_map_gives_status_2():
+    import gpismap_amd
+    gm = gpismap_amd.GPisMap3()
+    pose, info = gm.track_depth(replay.synthetic_depth(0), replay.IDENTITY_POSE)
+    assert info["status"] == 2 and info["inliers"] == 0 and info["passes"] == 1 and info["points"] > 0
+    assert _bits_equal(pose, replay.IDENTITY_POSE) and np.all(np.isnan(info["resid"]))
+    g2 = gpismap_amd.GPisMap()
+    fr = replay.load_gazebo()[0]
+    pose, info = g2.track_scan(fr["thetas"], fr["ranges"], fr["pose"])
+    assert info["status"] == 2 and info["inliers"] == 0
+
+
+def test_errors():
+    import gpismap_amd
+    L = gpismap_amd.lib()
+    gm = _synthetic_map(frames=2)
+    t = gpismap_amd.Tracker()
+    cam = (142.0, 142.0, 77.5, 56.0, 160, 120)
+    depth, _, _ = gm.render_depth(SYN_TRUE, cam6=cam)
+    start = _perturb3(SYN_TRUE, 0.01, 1.0)
+    a = gm.track_depth(depth, start, cam6=cam, tracker=t)
+    assert a[1]["inliers"] > 500
+
+    def call3(pose=start, cam6=cam, d=depth, map_h=None, t_h=None, **kw):
+        p = np.ascontiguousarray(pose, F32)
+        o = gpismap_amd.track_opts(3, **kw)
+        c = C.byref(gpismap_amd._cam(cam6)) if cam6 is not None else None
+        out = np.zeros(12, F32)
+        P = lambda x: x.ctypes.data_as(C.POINTER(C.c_float))
+        return L.gpis3_track_depth(gm.h if map_h is None else map_h, t.h if t_h is None else t_h, c, P(d), P(p), C.byref(o),
+                                   P(out), None)
+
+    def still_there():
+        assert _same((a[0], t.result()), a)
+
+    bad_pose = start.copy(); bad_pose[4] = np.nan
+    inf_pose = start.copy(); inf_pose[0] = np.inf
+    for kw in (dict(pose=bad_pose), dict(pose=inf_pose), dict(cam6=(0.0, 142.0, 77.5, 56.0, 160, 120)),
+               dict(cam6=(142.0, np.nan, 77.5, 56.0, 160, 120)), dict(cam6=(142.0, 142.0, 77.5, 56.0, 0, 120)),
+               dict(stride=0), dict(max_iters=-1), dict(min_inliers=-1), dict(max_residual=-0.1), dict(max_residual=np.nan),
+               dict(huber=0.0), dict(huber=np.inf), dict(max_var=np.nan), dict(damping=-1.0), dict(damping=np.inf),
+               dict(eps_t=np.nan), dict(eps_r=-1.0), dict(level=np.inf)):
+        assert call3(**kw) == -1, kw
+        still_there()
+    P = lambda x: np.ascontiguousarray(x, F32).ctypes.data_as(C.POINTER(C.c_float))
+    assert L.gpis3_track_depth(gm.h, t.h, None, None, P(start), None, None, None) == -1
+    assert L.gpis3_track_depth(gm.h, t.h, None, P(depth), None, None, None, None) == -1
+    assert L.gpis3_track_depth(None, t.h, None, P(depth), P(start), None, None, None) == -1
+    assert L.gpis3_track_depth(gm.h, None, None, P(depth), P(start), None, None, None) == -1
+    still_there()
+    # more than 2^26 pixels: refused before anything is allocated (or read), the result kept
+    assert call3(cam6=(142.0, 142.0, 77.5, 56.0, 8193, 8192)) == -4
+    still_there()
+    with pytest.raises(gpismap_amd.GpisError):
+        gm.track_depth(depth[:-1], start, cam6=cam)
+    with pytest.raises(gpismap_amd.GpisError):
+        gm.track_depth(depth, start, cam6=cam, bogus=1.0)
+    # 2-D arguments
+    g2, f2 = _gazebo_map(range(10))
+    fr = f2[5]
+    t2 = gpismap_amd.Tracker()
+    b = g2.track_scan(fr["thetas"], fr["ranges"], fr["pose"], tracker=t2)
+    bad_th = fr["thetas"].copy(); bad_th[3] = np.nan
+    bad_p2 = fr["pose"].copy(); bad_p2[2] = np.inf
+    n = fr["thetas"].size
+    assert L.gpis2_track_scan(g2.h, t2.h, P(bad_th), P(fr["ranges"]), n, P(fr["pose"]), None, None, None) == -1
+    assert L.gpis2_track_scan(g2.h, t2.h, P(fr["thetas"]), P(fr["ranges"]), n, P(bad_p2), None, None, None) == -1
+    assert L.gpis2_track_scan(g2.h, t2.h, P(fr["thetas"]), P(fr["ranges"]), 0, P(fr["pose"]), None, None, None) == -1
+    assert L.gpis2_track_scan(g2.h, t2.h, None, P(fr["ranges"]), n, P(fr["pose"]), None, None, None) == -1
+    o = gpismap_amd.track_opts(2, huber=-1.0)
+    assert L.gpis2_track_scan(g2.h, t2.h, P(fr["thetas"]), P(fr["ranges"]), n, P(fr["pose"]), C.byref(o), None, None) == -1
+    assert _same((b[0], t2.result()), b)
+    assert L.gpis_track_set_chunk(t.h, -1) == -1
+    # a tracker without a result
+    fresh = gpismap_amd.Tracker()
+    assert L.gpis_track_get(fresh.h, None, None, None) == -3
+    # after an error the tracker works again
+    assert _same(gm.track_depth(depth, start, cam6=cam, tracker=t), a)
