@@ -148,6 +148,18 @@ def lib():
         L.gpis_mesh_get.argtypes = [vp, fp, ip, fp]
         L.gpis_mesh_get_grid.argtypes = [vp, fp]
         L.gpis_mesh_device.argtypes = [vp, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
+    if hasattr(L, "gpis_dfield_create"):
+        L.gpis_dfield_create.restype = vp
+        L.gpis_dfield_create.argtypes = []
+        L.gpis_dfield_destroy.argtypes = [vp]
+        L.gpis_dfield_set_chunk.argtypes = [vp, C.c_int]
+        L.gpis_dfield_from_grid.argtypes = [vp, vp, C.c_int, ip, fp, fp, C.c_float, vp]
+        L.gpis3_distance_field.argtypes = [vp, vp, ip, fp, fp, C.c_float, C.c_float, vp]
+        L.gpis2_distance_field.argtypes = [vp, vp, ip, fp, fp, C.c_float, C.c_float, vp]
+        L.gpis_dfield_info.argtypes = [vp, ip, ip, fp, fp]
+        L.gpis_dfield_get.argtypes = [vp, fp, ip, fp]
+        L.gpis_dfield_device.argtypes = [vp, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
+        L.gpis_dfield_sample.argtypes = [vp, vp, C.c_longlong, vp, vp]
     if hasattr(L, "gpis_render_create"):
         L.gpis_render_default_opts.argtypes = [C.c_int, C.POINTER(gpis_render_opts)]
         L.gpis_render_create.restype = vp
@@ -414,6 +426,20 @@ class GPisMap3:
             self._mesh = Mesh()
         return self._mesh
 
+    def distance_field(self, origin, step, shape, level=None, max_var=None, field=None):
+        """The map's signed Euclidean distance field on the device (gpis3_distance_field): test() on the lattice origin + i * step
+        of shape (nx, ny, nz) with one step on every axis (a scalar step is accepted), an exact distance transform to the
+        level surface (None: -fbias), negative inside (f < level; unknown f counts as outside).  max_var: points whose var_f is
+        above it are unknown.  Returns the DistanceField holding the result (field: one to reuse; default: one kept by this map)."""
+        df = field if field is not None else self._own_dfield()
+        df._compute(self.L.gpis3_distance_field, self.h, self.device(), 3, origin, step, shape, level, max_var, "gpis3_distance_field")
+        return df
+
+    def _own_dfield(self):
+        if getattr(self, "_dfield", None) is None:
+            self._dfield = DistanceField()
+        return self._dfield
+
     def render_depth(self, pose, cam6=None, renderer=None, **opts):
         """What the depth camera would see from `pose` (gpis3_render_depth): rays marched through the map's test() on the device.
         Returns (depth [W*H] f32, rec [W*H, 8] f32, status [W*H] u8) in update()'s column-major layout (k = col * H + row), so
@@ -535,6 +561,16 @@ class GPisMap:
         mesh._extract(self.L.gpis2_extract_contour, self.h, 2, origin, step, shape, level, "gpis2_extract_contour")
         v, f, r = mesh.get()
         return _filter_var(v, f, r, 3, max_var)
+
+    def distance_field(self, origin, step, shape, level=None, max_var=None, field=None):
+        """The map's signed Euclidean distance field (gpis2_distance_field) on the lattice of shape (nx, ny); as
+        GPisMap3.distance_field, var_f = record slot 3."""
+        if field is None:
+            if getattr(self, "_dfield", None) is None:
+                self._dfield = DistanceField()
+            field = self._dfield
+        field._compute(self.L.gpis2_distance_field, self.h, self.L.gpis2_device(self.h), 2, origin, step, shape, level, max_var, "gpis2_distance_field")
+        return field
 
     def render_scan(self, thetas, pose6, renderer=None, **opts):
         """What the laser would see from `pose6` (gpis2_render_scan) along the beams `thetas`.  Returns (range [n] f32,
@@ -664,6 +700,105 @@ class Mesh:
         a, b, c = C.c_void_p(0), C.c_void_p(0), C.c_void_p(0)
         _check(self.L.gpis_mesh_device(self.h, C.byref(a), C.byref(b), C.byref(c)), "gpis_mesh_device")
         return a.value or 0, b.value or 0, c.value or 0
+
+
+class DistanceField:
+    """Result holder of the signed distance field (gpis_dfield_*): device buffers reused across calls.  Kernel level:
+    from_grid() on any device-resident f grid.  get() -> (dist, site, f), sample() -> interpolated distance and gradient."""
+
+    def __init__(self):
+        self.L = lib()
+        if self.L.gpis_device_count() < 1:
+            raise GpisError("no HIP device: gpismap_amd has no CPU fallback")
+        self.h = C.c_void_p(self.L.gpis_dfield_create())
+        if not self.h:
+            raise GpisError("gpis_dfield_create failed")
+        self._device = get_device()
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.gpis_dfield_destroy(self.h)
+            self.h = None
+
+    __del__ = close
+
+    def set_chunk(self, points):
+        """Lattice points per test() pass of a map-level call (0 = default 2^22; results do not depend on it)."""
+        _check(self.L.gpis_dfield_set_chunk(self.h, int(points)), "gpis_dfield_set_chunk")
+
+    def _compute(self, fn, map_h, map_dev, dim, origin, step, shape, level, max_var, what):
+        n, o, s = Mesh._lattice_args(dim, origin, step, shape)
+        lv = float("nan") if level is None else float(level)
+        mv = float("inf") if max_var is None else float(max_var)
+        rc = fn(map_h, self.h, _p(n, C.c_int), _p(o), _p(s), lv, mv, None)
+        if rc == 0:                                     # (the buffers now live on the map's lead device)
+            self._device = map_dev
+        _check(rc, what)
+
+    def from_grid(self, d_val_ptr, shape, origin, step, level, stream=0):
+        """Kernel level (gpis_dfield_from_grid): d_val_ptr = device address of prod(shape) float32 values, x fastest."""
+        dim = len(shape)
+        n, o, s = Mesh._lattice_args(dim, origin, step, shape)
+        _check(self.L.gpis_dfield_from_grid(self.h, C.c_void_p(d_val_ptr), dim, _p(n, C.c_int), _p(o), _p(s), float(level),
+                                            C.c_void_p(stream)), "gpis_dfield_from_grid")
+        return self
+
+    def info(self):
+        """dict(dim, shape, origin, step) of the last result (dim 0: none)."""
+        d, n = C.c_int(0), np.zeros(3, np.int32)
+        o, s = np.zeros(3, np.float32), C.c_float(0)
+        _check(self.L.gpis_dfield_info(self.h, C.byref(d), _p(n, C.c_int), _p(o), C.byref(s)), "gpis_dfield_info")
+        dim = int(d.value)
+        return dict(dim=dim, shape=tuple(int(v) for v in n[:dim]), origin=tuple(float(v) for v in o[:dim]), step=float(s.value))
+
+    def get(self, f=None):
+        """(dist, site, f) host copies of the last result, each of shape shape[::-1] (x fastest); f is None after from_grid
+        (f=True demands it)."""
+        inf = self.info()
+        if inf["dim"] == 0:
+            raise GpisError("distance field holds no result")
+        shape = inf["shape"][::-1]
+        n = int(np.prod(shape))
+        want_f = self.device_ptrs()[2] != 0 if f is None else bool(f)
+        dist = np.zeros(n, np.float32)
+        site = np.zeros(n, np.int32)
+        fv = np.zeros(n, np.float32) if want_f else None
+        _check(self.L.gpis_dfield_get(self.h, _p(dist), _p(site, C.c_int), _p(fv) if fv is not None else None), "gpis_dfield_get")
+        return dist.reshape(shape), site.reshape(shape), (fv.reshape(shape) if fv is not None else None)
+
+    def device_ptrs(self):
+        """(d_dist, d_site, d_f) device addresses of the last result (0 where there is none)."""
+        a, b, c = C.c_void_p(0), C.c_void_p(0), C.c_void_p(0)
+        _check(self.L.gpis_dfield_device(self.h, C.byref(a), C.byref(b), C.byref(c)), "gpis_dfield_device")
+        return a.value or 0, b.value or 0, c.value or 0
+
+    def sample(self, points, m=None, d_out=None, stream=0):
+        """Interpolated distance and gradient (gpis_dfield_sample).  points: a numpy [m, dim] array -> returns [m, 1 + dim]
+        float32; or a device address of m * dim floats with d_out the device address of m * (1 + dim) floats (returns None).
+        Points outside the lattice give NaN."""
+        if isinstance(points, int):
+            if m is None or d_out is None:
+                raise GpisError("sample on a device pointer needs m and d_out")
+            _check(self.L.gpis_dfield_sample(self.h, C.c_void_p(points), int(m), C.c_void_p(d_out), C.c_void_p(stream)),
+                   "gpis_dfield_sample")
+            return None
+        import torch
+        dim = self.info()["dim"]
+        if dim == 0:
+            raise GpisError("distance field holds no result")
+        x = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, dim)
+        dev = torch.device("cuda", self.device())
+        tx = torch.from_numpy(x).to(dev)
+        to = torch.empty((x.shape[0], 1 + dim), dtype=torch.float32, device=dev)
+        torch.cuda.synchronize(dev)
+        _check(self.L.gpis_dfield_sample(self.h, C.c_void_p(tx.data_ptr()), x.shape[0], C.c_void_p(to.data_ptr()), None),
+               "gpis_dfield_sample")
+        return to.cpu().numpy()
+
+    def device(self):
+        """The HIP device the buffers live on (the one current at creation; a map-level call moves them to the map's lead
+        device)."""
+        return self._device
 
 
 def render_opts(dim, **opts):

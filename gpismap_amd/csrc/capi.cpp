@@ -8,6 +8,7 @@
 #include "../../include/gpismap_amd.h"
 #include "map_query.h"
 #include "mesh.h"
+#include "dfield.h"
 #include "render.h"
 #include "track.h"
 #include "obsgp.h"
@@ -48,6 +49,10 @@ int gpis2_impl_sync(GPisMap* m);
 void gpis2_impl_set_pipeline(GPisMap* m, int on);
 int gpis3_impl_extract(GPisMap3* g, MeshExtractor& me, const int* n3, const float* origin3, const float* step3, float level, void* stream);
 int gpis2_impl_extract(GPisMap* g, MeshExtractor& me, const int* n2, const float* origin2, const float* step2, float level, void* stream);
+int gpis3_impl_dfield(GPisMap3* g, DistanceField& df, const int* n3, const float* origin3, const float* step3, float level, float max_var,
+                      void* stream);
+int gpis2_impl_dfield(GPisMap* g, DistanceField& df, const int* n2, const float* origin2, const float* step2, float level, float max_var,
+                      void* stream);
 int gpis3_impl_render(GPisMap3* g, Renderer& r, const float* cam4, const int* wh, const float* pose12, RenderOpts o, void* stream);
 int gpis2_impl_render(GPisMap* g, Renderer& r, const float* thetas, int n, const float* pose6, RenderOpts o, void* stream);
 int gpis3_impl_track(GPisMap3* g, Tracker& t, const float* cam4, const int* wh, const float* depth, const float* pose12, TrackOpts o,
@@ -485,6 +490,101 @@ int gpis_mesh_device(void* mesh, const float** d_verts, const int** d_prims, con
     if (d_prims) *d_prims = me.d_prims;
     if (d_vrec) *d_vrec = me.rec_valid ? me.d_vrec : nullptr;
     return GPIS_OK;
+}
+
+// ---- distance field ---------------------------------------------------------------------------------------------------
+void* gpis_dfield_create(void) {
+    if (gpis_device_count() < 1) { fprintf(stderr, "[gpismap_amd] no HIP device\n"); return nullptr; }
+    DistanceField* df = new (std::nothrow) DistanceField();
+    if (df && !df->own) { delete df; return nullptr; }
+    return df;
+}
+void gpis_dfield_destroy(void* df) { delete (DistanceField*)df; }
+int gpis_dfield_set_chunk(void* df, int points) {
+    if (!df || points < 0) return GPIS_ERR_ARG;
+    ((DistanceField*)df)->chunk = points ? points : (1 << 22);
+    return GPIS_OK;
+}
+// (the result is dropped only once the arguments passed: an argument error leaves the previous one readable)
+static int dfield_args(void* df, int dim, const int* n, const float* origin, const float* step) {
+    if (!df) return GPIS_ERR_ARG;
+    long long np = 0;
+    return dfield_check_lattice(dim, n, origin, step, &np);
+}
+int gpis_dfield_from_grid(void* d, const float* d_val, int dim, const int* n, const float* origin, const float* step, float level,
+                          void* stream) {
+    if (int rc = dfield_args(d, dim, n, origin, step)) return rc;
+    if (!d_val || !std::isfinite(level)) return GPIS_ERR_ARG;
+    DistanceField& df = *(DistanceField*)d;
+    DeviceScope ds(df.device);
+    df.clear_result();
+    try {
+        const int rc = df.from_grid(d_val, dim, n, origin, step, level, stream ? (hipStream_t)stream : df.own);
+        if (rc != GPIS_OK) df.clear_result();
+        return rc;
+    } catch (...) { df.clear_result(); return GPIS_ERR_STATE; }
+}
+int gpis3_distance_field(void* m, void* d, const int* n3, const float* origin3, const float* step3, float level, float max_var,
+                         void* stream) {
+    if (!m) return GPIS_ERR_ARG;
+    if (int rc = dfield_args(d, 3, n3, origin3, step3)) return rc;
+    if (std::isinf(level) || std::isnan(max_var)) return GPIS_ERR_ARG;
+    DistanceField& df = *(DistanceField*)d;
+    df.clear_result();
+    const int rc = gpis3_impl_dfield((GPisMap3*)m, df, n3, origin3, step3, level, max_var, stream);
+    if (rc != GPIS_OK) df.clear_result();
+    return rc;
+}
+int gpis2_distance_field(void* m, void* d, const int* n2, const float* origin2, const float* step2, float level, float max_var,
+                         void* stream) {
+    if (!m) return GPIS_ERR_ARG;
+    if (int rc = dfield_args(d, 2, n2, origin2, step2)) return rc;
+    if (std::isinf(level) || std::isnan(max_var)) return GPIS_ERR_ARG;
+    DistanceField& df = *(DistanceField*)d;
+    df.clear_result();
+    const int rc = gpis2_impl_dfield((GPisMap*)m, df, n2, origin2, step2, level, max_var, stream);
+    if (rc != GPIS_OK) df.clear_result();
+    return rc;
+}
+int gpis_dfield_info(void* d, int* dim, int* n3, float* origin3, float* step) {
+    if (!d) return GPIS_ERR_ARG;
+    const DistanceField& df = *(DistanceField*)d;
+    if (dim) *dim = df.valid ? df.dim : 0;
+    for (int a = 0; a < 3; ++a) {
+        if (n3) n3[a] = df.valid ? df.n[a] : 0;
+        if (origin3) origin3[a] = df.valid ? df.origin[a] : 0.f;
+    }
+    if (step) *step = df.valid ? df.step : 0.f;
+    return GPIS_OK;
+}
+int gpis_dfield_get(void* d, float* dist, int* site, float* f) {
+    if (!d) return GPIS_ERR_ARG;
+    DistanceField& df = *(DistanceField*)d;
+    if ((dist || site || f) && !df.valid) return GPIS_ERR_STATE;
+    if (f && !df.f_valid) return GPIS_ERR_STATE;
+    DeviceScope ds(df.device);
+    const size_t n = (size_t)df.ngrid;
+    if (dist) GPIS_HIP(hipMemcpyAsync(dist, df.d_dist, sizeof(float) * n, hipMemcpyDeviceToHost, df.own));
+    if (site) GPIS_HIP(hipMemcpyAsync(site, df.d_site(), sizeof(int) * n, hipMemcpyDeviceToHost, df.own));
+    if (f) GPIS_HIP(hipMemcpyAsync(f, df.d_val, sizeof(float) * n, hipMemcpyDeviceToHost, df.own));
+    GPIS_HIP(hipStreamSynchronize(df.own));
+    return GPIS_OK;
+}
+int gpis_dfield_device(void* d, const float** d_dist, const int** d_site, const float** d_f) {
+    if (!d) return GPIS_ERR_ARG;
+    const DistanceField& df = *(DistanceField*)d;
+    if (d_dist) *d_dist = df.valid ? df.d_dist : nullptr;
+    if (d_site) *d_site = df.d_site();
+    if (d_f) *d_f = df.f_valid ? df.d_val : nullptr;
+    return GPIS_OK;
+}
+int gpis_dfield_sample(void* d, const float* d_x, long long m, float* d_out, void* stream) {
+    if (!d || m < 0 || (m > 0 && (!d_x || !d_out))) return GPIS_ERR_ARG;
+    DistanceField& df = *(DistanceField*)d;
+    DeviceScope ds(df.device);
+    try {
+        return df.sample(d_x, m, d_out, stream ? (hipStream_t)stream : df.own);
+    } catch (...) { return GPIS_ERR_STATE; }
 }
 
 // ---- rendering ---------------------------------------------------------------------------------------------------------

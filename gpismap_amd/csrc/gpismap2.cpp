@@ -12,6 +12,7 @@
 #include "flat_tree.h"
 #include "map_query.h"
 #include "mesh.h"
+#include "dfield.h"
 #include "render.h"
 #include "track.h"
 #include "obsgp.h"
@@ -661,6 +662,23 @@ int gpis2_impl_extract(GPisMap* g, MeshExtractor& me, const int* n2, const float
     if (rc != GPIS_OK) { m.fail_rc = rc; fprintf(stderr, "[gpismap_amd] gpis2_extract_contour: device path failed (%d)\n", rc); }
     return rc;
 } catch (const std::exception& e) { nothrow_report("gpis2_extract_contour", e.what()); return GPIS_ERR_STATE; } catch (...) { nothrow_report("gpis2_extract_contour", "unknown exception"); return GPIS_ERR_STATE; }
+
+// Distance field (gpis2_distance_field): the extraction's checks and joins, then the lattice through the map's MapQuery on the lead device.
+int gpis2_impl_dfield(GPisMap* g, DistanceField& df, const int* n, const float* origin, const float* step, float level, float max_var,
+                      void* hip_stream) try {
+    GPisMap::Impl& m = *g->impl();
+    DeviceScope dev_scope_(m.device);
+    m.fail_rc = 0;
+    if (!m.ok) return GPIS_ERR_HIP;
+    if (!m.has_tree) return GPIS_ERR_STATE;
+    if (std::isnan(level)) level = -m.setting.fbias;
+    if (int rc = df.bind(m.device)) return rc;
+    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : m.stream;
+    (void)m.join_training();
+    const int rc = df.from_map(m.mq, m.store, 2, n, origin, step, level, max_var, s);
+    if (rc != GPIS_OK) { m.fail_rc = rc; fprintf(stderr, "[gpismap_amd] gpis2_distance_field: device path failed (%d)\n", rc); }
+    return rc;
+} catch (const std::exception& e) { nothrow_report("gpis2_distance_field", e.what()); return GPIS_ERR_STATE; } catch (...) { nothrow_report("gpis2_distance_field", "unknown exception"); return GPIS_ERR_STATE; }
 
 // Scan rendering (gpis2_render_scan): testDevice's checks and join, then the march through the map's MapQuery.  The beams'
 // cos / sin in double on the host (polar2Cart); the sensor offset of the map's parameters.

@@ -25,6 +25,7 @@
 #include "host_pool.h"
 #include "map_query.h"
 #include "mesh.h"
+#include "dfield.h"
 #include "render.h"
 #include "track.h"
 #include "obsgp.h"
@@ -1961,6 +1962,25 @@ int gpis3_impl_extract(GPisMap3* g, MeshExtractor& me, const int* n3, const floa
     if (rc == GPIS_ERR_STATE) m.build_cluster_table();   // (models dropped by the inverse pass: their cells have no GP any more)
     return rc;
 } catch (const std::exception& e) { nothrow_report("gpis3_extract_mesh", e.what()); return GPIS_ERR_STATE; } catch (...) { nothrow_report("gpis3_extract_mesh", "unknown exception"); return GPIS_ERR_STATE; }
+
+// Distance field (gpis3_distance_field): the extraction's checks and joins, then the lattice through the map's MapQuery on the lead device.
+int gpis3_impl_dfield(GPisMap3* g, DistanceField& df, const int* n, const float* origin, const float* step, float level, float max_var,
+                      void* hip_stream) try {
+    GPisMap3::Impl& m = *g->impl();
+    DeviceScope dev_scope_(m.device);
+    m.fail_rc = 0;
+    if (!m.ok) return GPIS_ERR_HIP;
+    if (!m.has_tree) return GPIS_ERR_STATE;
+    if (m.table_pending) { fprintf(stderr, "[gpismap_amd] gpis3_distance_field: sharded update not finished (gpis3_shard_finish)\n"); return GPIS_ERR_STATE; }
+    if (std::isnan(level)) level = -m.setting.fbias;
+    if (int rc = df.bind(m.device)) return rc;
+    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : m.stream;
+    m.finish_training();
+    const int rc = df.from_map(m.mq, m.store, 3, n, origin, step, level, max_var, s);
+    if (rc != GPIS_OK) { m.fail_rc = rc; fprintf(stderr, "[gpismap_amd] gpis3_distance_field: device path failed (%d)\n", rc); }
+    if (rc == GPIS_ERR_STATE) m.build_cluster_table();
+    return rc;
+} catch (const std::exception& e) { nothrow_report("gpis3_distance_field", e.what()); return GPIS_ERR_STATE; } catch (...) { nothrow_report("gpis3_distance_field", "unknown exception"); return GPIS_ERR_STATE; }
 
 // Depth rendering (gpis3_render_depth): testDevice's checks and joins, then the march through the map's own MapQuery on the lead
 // device.  cam4 (fx, fy, cx, cy) and wh (width, height) NULL: the map's camera; o.level NaN: -fbias; o.far_step NaN: 0.9 x the search half-width.

@@ -53,4 +53,10 @@ private:
 // (more than kMaxLattice points).  *npts receives the lattice size.
 int mesh_check_lattice(int dim, const int* n, const float* origin, const float* step, long long* npts);
 
+// The map's f on a lattice (shared by the mesh and the distance field): chunks of at most `chunk` lattice points through
+// mq.run_prepared (one mq.prepare per call) into zero-prefilled records staged in d_x / d_rec (grown here), slot 0 of each
+// record into d_val[np].  A point whose var_f (record slot 1 + dim) is above max_var gets NaN (+inf: no gate).  Enqueued on `s`.
+int lattice_values(MapQuery& mq, OnGPISStore& store, int dim, const int* n, const float* origin, const float* step, long long np,
+                   int chunk, float max_var, float*& d_x, size_t& cap_x, float*& d_rec, size_t& cap_rec, float* d_val, hipStream_t s);
+
 }  // namespace gpis

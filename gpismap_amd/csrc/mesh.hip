@@ -61,9 +61,13 @@ __global__ void __launch_bounds__(kBlock) mesh_lattice_kernel(long long off, int
     }
 }
 
-// slot 0 (f) of a chunk's test() records into the value grid
-__global__ void __launch_bounds__(kBlock) mesh_fcol_kernel(const float* __restrict__ rec, int nc, int len, float* __restrict__ val) {
-    for (int q = blockIdx.x * blockDim.x + threadIdx.x; q < len; q += gridDim.x * blockDim.x) val[q] = rec[(size_t)q * nc];
+// slot 0 (f) of a chunk's test() records into the value grid; NaN where var_f (slot vs) is above max_var
+__global__ void __launch_bounds__(kBlock) mesh_fcol_kernel(const float* __restrict__ rec, int nc, int vs, float max_var, int len,
+                                                           float* __restrict__ val) {
+    for (int q = blockIdx.x * blockDim.x + threadIdx.x; q < len; q += gridDim.x * blockDim.x) {
+        const float* r = rec + (size_t)q * nc;
+        val[q] = r[vs] > max_var ? __int_as_float(0x7fc00000) : r[0];
+    }
 }
 
 // crossing mask and vertex count per point, primitive count per cell
@@ -320,6 +324,36 @@ int mesh_check_lattice(int dim, const int* n, const float* origin, const float* 
     return GPIS_OK;
 }
 
+template <class T>
+static int grow(T*& p, size_t& cap, size_t need) {
+    if (need <= cap) return GPIS_OK;
+    (void)hipFree(p); p = nullptr; cap = 0;
+    GPIS_HIP(hipMalloc((void**)&p, sizeof(T) * need));
+    cap = need;
+    return GPIS_OK;
+}
+
+int lattice_values(MapQuery& mq, OnGPISStore& store, int dm, const int* n, const float* origin, const float* step, long long np,
+                   int chunk, float max_var, float*& d_x, size_t& cap_x, float*& d_rec, size_t& cap_rec, float* d_val, hipStream_t s) {
+    const int nc = 2 * (1 + dm);
+    const int C = (int)std::min<long long>(std::max(1, chunk), np);
+    if (int rc = grow(d_x, cap_x, (size_t)C * dm)) return rc;
+    if (int rc = grow(d_rec, cap_rec, (size_t)C * nc)) return rc;
+    if (int rc = mq.prepare(store, s)) return rc;
+    const float oz = dm == 3 ? origin[2] : 0.f, sz = dm == 3 ? step[2] : 0.f;
+    for (long long off = 0; off < np; off += C) {
+        const int len = (int)std::min<long long>(C, np - off);
+        hipLaunchKernelGGL(mesh_lattice_kernel, dim3(grid_for(len)), dim3(kBlock), 0, s, off, len, dm, n[0], n[1], origin[0], origin[1], oz,
+                           step[0], step[1], sz, d_x);
+        GPIS_HIP(hipGetLastError());
+        GPIS_HIP(hipMemsetAsync(d_rec, 0, sizeof(float) * (size_t)len * nc, s));   // (the mex gateway's zero pre-fill)
+        if (int rc = mq.run_prepared(store, d_x, len, d_rec, s)) return rc;
+        hipLaunchKernelGGL(mesh_fcol_kernel, dim3(grid_for(len)), dim3(kBlock), 0, s, d_rec, nc, 1 + dm, max_var, len, d_val + off);
+        GPIS_HIP(hipGetLastError());
+    }
+    return GPIS_OK;
+}
+
 MeshExtractor::MeshExtractor() {
     (void)hipGetDevice(&device);
     if (hipStreamCreateWithFlags(&own, hipStreamNonBlocking) != hipSuccess) own = nullptr;
@@ -346,15 +380,6 @@ int MeshExtractor::bind(int dev) {
     if (dev < 0) return GPIS_OK;
     DeviceScope ds(dev);
     GPIS_HIP(hipStreamCreateWithFlags(&own, hipStreamNonBlocking));
-    return GPIS_OK;
-}
-
-template <class T>
-static int grow(T*& p, size_t& cap, size_t need) {
-    if (need <= cap) return GPIS_OK;
-    (void)hipFree(p); p = nullptr; cap = 0;
-    GPIS_HIP(hipMalloc((void**)&p, sizeof(T) * need));
-    cap = need;
     return GPIS_OK;
 }
 
@@ -426,20 +451,7 @@ int MeshExtractor::from_map(MapQuery& mq, OnGPISStore& store, int dm, const int*
     if (int rc = mesh_check_lattice(dm, n, origin, step, &np)) return rc;
     if (int rc = ensure_grid(np, true)) return rc;
     const int nc = 2 * (1 + dm);
-    const int C = (int)std::min<long long>(chunk, np);
-    if (int rc = grow(d_x, cap_x, (size_t)C * dm)) return rc;
-    if (int rc = grow(d_rec, cap_rec, (size_t)C * nc)) return rc;
-    const float oz = dm == 3 ? origin[2] : 0.f, sz = dm == 3 ? step[2] : 0.f;
-    for (long long off = 0; off < np; off += C) {
-        const int len = (int)std::min<long long>(C, np - off);
-        hipLaunchKernelGGL(mesh_lattice_kernel, dim3(grid_for(len)), dim3(kBlock), 0, s, off, len, dm, n[0], n[1], origin[0], origin[1], oz,
-                           step[0], step[1], sz, d_x);
-        GPIS_HIP(hipGetLastError());
-        GPIS_HIP(hipMemsetAsync(d_rec, 0, sizeof(float) * (size_t)len * nc, s));   // (the mex gateway's zero pre-fill)
-        if (int rc = mq.run(store, d_x, len, d_rec, s)) return rc;
-        hipLaunchKernelGGL(mesh_fcol_kernel, dim3(grid_for(len)), dim3(kBlock), 0, s, d_rec, nc, len, d_val + off);
-        GPIS_HIP(hipGetLastError());
-    }
+    if (int rc = lattice_values(mq, store, dm, n, origin, step, np, chunk, INFINITY, d_x, cap_x, d_rec, cap_rec, d_val, s)) return rc;
     if (int rc = from_grid(d_val, dm, n, origin, step, level, s)) return rc;
     grid_valid = true;
     if (int rc = grow(d_vrec, cap_vrec, (size_t)std::max(1ll, nvert) * nc)) return rc;

@@ -291,6 +291,47 @@ int   gpis_mesh_get_grid(void* mesh, float* vals);
 /* device pointers of the last result, valid until the next extraction or gpis_mesh_destroy (*d_vrec = NULL without records) */
 int   gpis_mesh_device(void* mesh, const float** d_verts, const int** d_prims, const float** d_vrec);
 
+/* ---- distance field: the map's signed Euclidean distance field on the device ------------------------------
+ * The map's test() on the mesh's lattice (index p = (k ny + j) nx + i, x fastest; coordinates origin + (float)i * step,
+ * float32, no FMA; f = slot 0 of each zero-prefilled record) with one step on every axis (cubic cells).  Inside iff f < level
+ * (NaN = -fbias of the map's parameters); f NaN is unknown and counts as outside, so the sign is only as good as f.  max_var:
+ * a point whose var_f (record slot 4 in 3-D, 3 in 2-D) is above it gets f = NaN first (+inf: no gate).  A site is a point with
+ * a finite f and an axis neighbour with a finite f on the other side of the level; its anchor is the crossing of its crossed
+ * axis edges closest to it along the edge's axis (ties: -x, +x, -y, +y, -z, +z), bit for bit the mesh vertex of that edge.
+ * Every point takes the site q* of the smallest integer squared lattice distance (ties: the smallest index) -- an exact
+ * Euclidean distance transform -- and dist = +-sqrtf of the float32 squared distance to q*'s anchor, negative iff inside;
+ * d_min <= |dist| <= d_min + 2 step, d_min the distance to the nearest anchor.  No site at all: dist +-inf, site -1.  No atomics:
+ * the same bits on every run and for any chunk size.  A field object is a result holder whose device buffers (about 28 B per
+ * lattice point) are reused across calls; every call returns with its work finished.  Arguments: a size < 2 on any axis, a
+ * non-finite origin, a non-positive, non-finite or anisotropic step, an infinite level, a NaN max_var, null pointers ->
+ * GPIS_ERR_ARG, the previous result untouched.  More than 2^28 lattice points or more than 16384 on an axis -> GPIS_ERR_LIMIT
+ * before anything is allocated.  Any other failure leaves no result. */
+void* gpis_dfield_create(void);                            /* on the current device; NULL without one */
+void  gpis_dfield_destroy(void* df);
+/* lattice points per test() pass of a map-level call (test hook: the results do not depend on it); 0 = 2^22 */
+int   gpis_dfield_set_chunk(void* df, int points);
+/* kernel level: any device-resident f grid d_val[prod(n)] (x fastest) of the field's device, no map involved; dim 2 or 3, level
+ * finite, step[dim] all equal.  hip_stream NULL: the field's own stream. */
+int   gpis_dfield_from_grid(void* df, const float* d_val, int dim, const int* n, const float* origin, const float* step,
+                            float level, void* hip_stream);
+/* map level.  Behaves like gpis3_extract_mesh: GPIS_ERR_STATE while a sharded update is unfinished or when the map holds no
+ * tree, joins a pipelined training; a map over several devices computes on its lead device.  hip_stream NULL: the map's stream. */
+int   gpis3_distance_field(void* map, void* df, const int* n3, const float* origin3, const float* step3, float level,
+                           float max_var, void* hip_stream);
+int   gpis2_distance_field(void* map, void* df, const int* n2, const float* origin2, const float* step2, float level,
+                           float max_var, void* hip_stream);
+/* the last result's lattice: dim (0: no result), n[3], origin[3] (unused axes 1 and 0), the step */
+int   gpis_dfield_info(void* df, int* dim, int* n3, float* origin3, float* step);
+/* host copies of the last result, prod(n) each (any pointer may be NULL); no result -> GPIS_ERR_STATE; f non-NULL after
+ * gpis_dfield_from_grid -> GPIS_ERR_STATE */
+int   gpis_dfield_get(void* df, float* dist, int* site, float* f);
+/* device pointers of the last result, valid until the next call or gpis_dfield_destroy (NULL where there is none) */
+int   gpis_dfield_device(void* df, const float** d_dist, const int** d_site, const float** d_f);
+/* d_out[m][1 + dim] = (d, dd/dx, dd/dy[, dd/dz]) at the device points d_x[m][dim]: the trilinear (2-D: bilinear) interpolant of
+ * dist with u = (x - origin) / step per axis, i0 = min(floor(u), n - 2); a point with !(0 <= u <= n - 1) on any axis gives NaN.
+ * No result -> GPIS_ERR_STATE.  hip_stream NULL: the field's own stream. */
+int   gpis_dfield_sample(void* df, const float* d_x, long long m, float* d_out, void* hip_stream);
+
 /* ---- rendering: depth images and laser scans from the map on the device --------------------------------
  * The inverse of update(): what the sensor would see from a pose.  Every ray is marched through the map's test(); every march
  * step is one test() pass over the rays still active, and nothing but one count per pass leaves the device.
