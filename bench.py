@@ -3,7 +3,11 @@
 640x480 synthetic depth and a 256^3 query grid (SURVEY.md 8d, config 4, F = 5 frames).
 
 A "step" is one GPisMap3 test() pass over the query grid, inputs already resident in HBM
-(gpis3_test_device).  update() of the synthetic frames is timed during set-up and reported beside it: in the library's
+(gpis3_test_device).  A plain run does only what that figure needs: it fuses the frames once (the map the steps test),
+warms up, times the steps, writes --dump-outputs and prints the line with the headline, `roofline` (K4 time and flops of
+the timed steps) and the multi-rank records.  Everything below that is measured or checked beside it runs with --full.
+
+With --full, update() of the synthetic frames is timed during set-up and reported beside it: in the library's
 default pipelined mode (`update_ms_per_frame` = (frames 2..F + the drain of the last frame's training) / (F - 1), median
 repeat), synchronous as the reference's (`update_ms_per_frame_synchronous`, median of frames 2..F, with the per-phase
 split and the K3 chain's own time) and synchronous with the eager inverse (`update_ms_per_frame_with_inverse`).
@@ -18,10 +22,11 @@ share of the frame's clusters, the packed models are all-gathered; DESIGN.md sec
 
 Prints ONE JSON line on rank 0 carrying `roofline` (dominant kernel = K4 ongpis_eval_kernel,
 MFMA/FLOP-bound; achieved = algorithmic flops / time inside the K4 launches measured with HIP events
-on the launch stream), `cpu_baseline` (CPU oracle on the host cores, rank 0, N = 1, one pass over a
+on the launch stream) and, with --full, `cpu_baseline` (CPU oracle on the host cores, rank 0, N = 1, one pass over a
 bounded 64^3 subsample, plus the parity records: own-map and SAME-MAP comparisons) and the sub-records `update_roofline` (K3 on the frame's clusters), `stress`
 (BASELINE config 5: 50 000 clusters x 64 points, train + predict) and `value_host_api` (the same pass
-through the host-pointer API the mex gateway uses, PCIe included).
+through the host-pointer API the mex gateway uses, PCIe included).  Multi-rank gloo rehearsals compare the assembled map
+with a single-rank pass with --full; --verify is an option of its own.
 """
 import argparse
 import hashlib
@@ -43,13 +48,16 @@ def parse():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--frames", type=int, default=5, help="synthetic depth frames fused before testing (SURVEY 8d: F = 5)")
     ap.add_argument("--grid", type=int, default=256, help="query grid is grid^3 points")
-    ap.add_argument("--update-repeats", type=int, default=5, help="fuse the frame sequence this many times (fresh maps); headline = median of frames 2..F of the MEDIAN repeat (the minimum over the repeats is a side field)")
+    ap.add_argument("--full", action="store_true", help="besides the headline, time update() in its three modes, run the value_host_api pass, the stress "
+                    "sub-record, the CPU baseline with its parity records and the gloo rehearsal's comparison with a single-rank pass "
+                    "(--update-repeats, --no-host-api, --stress and --cpu-sample only apply here)")
+    ap.add_argument("--update-repeats", type=int, default=5, help="--full: fuse the frame sequence this many times (fresh maps); headline = median of frames 2..F of the MEDIAN repeat (the minimum over the repeats is a side field)")
     ap.add_argument("--train", default="replicated", choices=["replicated", "sharded", "lead"], help="multi-rank update(): every rank trains everything, or its K^3-balanced share + all-gather of the models; lead = sharded with the host logic run once on rank 0 (frame records broadcast, the other ranks apply them)")
     ap.add_argument("--backend", default="nccl", help="nccl (= RCCL, the measured path) or gloo (rehearsal of the multi-rank logic on fewer GPUs: transfers staged through host memory)")
     ap.add_argument("--block", type=int, default=65536, help="queries per block of the block-cyclic cut")
-    ap.add_argument("--cpu-sample", type=int, default=64, help="CPU baseline runs on a sample^3 subgrid (0 = skip); SURVEY 8(d): 64^3")
-    ap.add_argument("--stress", type=int, default=50000, help="clusters of the stress sub-record (0 = skip)")
-    ap.add_argument("--no-host-api", action="store_true", help="skip the value_host_api pass")
+    ap.add_argument("--cpu-sample", type=int, default=64, help="--full: CPU baseline runs on a sample^3 subgrid (0 = skip); SURVEY 8(d): 64^3")
+    ap.add_argument("--stress", type=int, default=50000, help="--full: clusters of the stress sub-record (0 = skip)")
+    ap.add_argument("--no-host-api", action="store_true", help="--full: skip the value_host_api pass")
     ap.add_argument("--verify", action="store_true", help="multi-rank runs: after the timed region, check the assembled map bit for bit against a single-rank pass of rank 0 over a 64^3 sub-grid (any backend), and report per-rank pass / gather / exchange ms")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last timed step computed to DIR/*.npy (rank 0): "
                     "test_result.npy = rows of the [grid^3, 8] float32 test() result (all of them up to %d rows, else a fixed seeded sample "
@@ -133,8 +141,10 @@ def main():
     # ---- set-up (untimed): fuse the synthetic frames; time update() per frame ----
     # The host side of update() (single-threaded tree replay) varies by +-30 % from box to box and run to run, so the
     # sequence is fused --update-repeats times into fresh maps and every frame is reported at its MINIMUM over the repeats
-    # (`update_repeats`, `update_ms_frames_all`); the last map is the one the test passes run on.
-    reps = max(1, args.update_repeats)
+    # (`update_repeats`, `update_ms_frames_all`); the last map is the one the test passes run on.  A plain run fuses the
+    # sequence once, into that map (lazy inverse), and reports none of these times.
+    reps = max(1, args.update_repeats) if args.full else 1
+    eager_reps = reps if args.full else 0
     upd_all, ph_all, k3_all = [], [], []
     exch_bytes = exch_padded = exch_records = 0
     exch_ms = []
@@ -142,8 +152,8 @@ def main():
     # Two update() accountings, reps fusions each: first with the EAGER inverse (K3b behind K3 inside every
     # update(): what a caller that tests after every update pays per frame), then the default LAZY inverse (update() stops at
     # the factor and alpha like OnGPIS::train; the inverse runs once at the first test()).  The last (lazy) map is the one tested.
-    for rep in range(2 * reps):
-        eager = rep < reps
+    for rep in range(eager_reps + reps):
+        eager = rep < eager_reps
         if gm is not None:
             del gm
         gm = gpismap_amd.GPisMap3()          # default camera 640x480, fx=fy=568, cx=310, cy=224
@@ -187,10 +197,12 @@ def main():
         """index of the repeat in [lo, hi) whose median over frames 2..F is the median among the repeats (upper median)"""
         order = sorted(range(lo, hi), key=lambda r: med_tail(upd_all[r]))
         return order[len(order) // 2]
-    r_eager, r_lazy = median_repeat(0, reps), median_repeat(reps, 2 * reps)
+    r_lazy = median_repeat(eager_reps, eager_reps + reps)
     upd_ms, phases, k3 = upd_all[r_lazy], ph_all[r_lazy], k3_all[r_lazy]
-    upd_ms_eager, k3_eager = upd_all[r_eager], k3_all[r_eager]
-    upd_min = [min(u[f] for u in upd_all[reps:]) for f in range(args.frames)]
+    if args.full:
+        r_eager = median_repeat(0, reps)
+        upd_ms_eager, k3_eager = upd_all[r_eager], k3_all[r_eager]
+    upd_min = [min(u[f] for u in upd_all[eager_reps:]) for f in range(args.frames)]
     # Lazy inverse (the default): update() trained factors and alpha; the explicit inverses of the clusters retrained since the
     # last prediction are computed by the first test() -- timed here on its own and reported (`deferred_inverse_ms`), so that
     # the timed passes below start from the same state as with the eager inverse.
@@ -203,7 +215,7 @@ def main():
     # between the frames, and the drain of the last frame's training is timed and CHARGED: per frame = (frames 2..F + drain) / (F-1).
     upd_pipe, drain_ms = [], 0.0
     pipe_all = []
-    if not sharded:
+    if args.full and not sharded:
         for rep in range(reps):
             gp = gpismap_amd.GPisMap3()
             gp.set_pipeline(True)
@@ -312,7 +324,7 @@ def main():
             if not same:
                 raise SystemExit("multi-rank assembly differs from the single-rank result")
 
-    if host_staged and world > 1 and rank == 0:
+    if args.full and host_staged and world > 1 and rank == 0:
         # rehearsal only: the assembled map must equal a single-rank pass over the whole grid, bit for bit
         xf = torch.from_numpy(grid).to(dev)
         ref = torch.zeros((n_total, 8), dtype=torch.float32, device=dev)
@@ -327,7 +339,7 @@ def main():
 
     # ---- value_host_api: the same pass through gpis3_test with HOST pointers (what the mex gateway calls) ----
     host_api = None
-    if rank == 0 and world == 1 and not args.no_host_api:
+    if args.full and rank == 0 and world == 1 and not args.no_host_api:
         hres = np.zeros((n_total, 8), dtype=np.float32)
         gm.test(grid, hres)                                    # warm the staging buffers
         t0 = time.perf_counter()
@@ -337,12 +349,12 @@ def main():
 
     # ---- stress sub-record: BASELINE config 5 through the kernel-level C-ABI ----
     stress = None
-    if args.stress > 0:
+    if args.full and args.stress > 0:
         stress = run_stress(args, world, rank, dev, host_staged)
 
     # ---- CPU baseline: the oracle on the host cores, bounded subsample of the same grid ----
     cpu = None
-    if rank == 0 and world == 1 and args.cpu_sample > 0:   # N = 1 only (bench contract)
+    if args.full and rank == 0 and world == 1 and args.cpu_sample > 0:   # N = 1 only (bench contract)
         import oracle_lib
         # timed in the oracle's "natural" arithmetic = the reference's own algorithm (Cholesky + substitution per query,
         # OnGPIS.cpp:177-216); the "tiled" mode carries an explicit inverse that only exists for the GPU formulation
@@ -449,14 +461,6 @@ def main():
                     and tj.get("grid") == args.grid and tj.get("frames") == args.frames):
                 traffic = tj.get("hbm_bytes_per_launch")
                 traffic_step = tj.get("hbm_bytes_per_pass")
-        med = med_tail
-        ph = np.array(phases)
-        ksel = k3[1:] if len(k3) > 1 else k3
-        k3_ms = float(np.median([k["ms"] for k in ksel]))
-        k3_fl = float(np.median([k["flops"] for k in ksel]))
-        ksel_e = k3_eager[1:] if len(k3_eager) > 1 else k3_eager
-        k3e_ms = float(np.median([k["ms"] for k in ksel_e]))
-        k3e_fl = float(np.median([k["flops"] for k in ksel_e]))
         out = {
             "metric": "sdf_test_points_per_sec",
             "value": value,
@@ -470,37 +474,13 @@ def main():
             "vs_baseline": None,
             "dtype": "f32",
             "data": "synthetic",
+            "full": args.full,
             "config": {"workload": "synthetic 640x480 depth z=1+0.05 sin(6(u+0.01f)) cos(5v), %d frames fused, "
                                    "%d^3 SDF query grid over [-0.6,0.6]x[-0.45,0.45]x[0.85,1.15] m" % (args.frames, args.grid),
                        "frames": args.frames, "grid": args.grid,
                        "clusters": int(st0["clusters"]), "map_points": gm.num_points(),
                        "parallelism": ("%s training, query blocks of %d dealt round-robin to %d ranks, RCCL point-to-point gather"
                                        % (args.train, args.block, world)) if world > 1 else "single GPU"},
-            # headline = the library's default mode (pipelined since round 4); sharded multi-rank runs are synchronous (every frame ends with the exchange)
-            "update_ms_per_frame": upd_pipe_mean if upd_pipe_mean is not None else med(upd_ms),
-            "update_mode": ("default mode: pipelined update() (returns once the frame's training is enqueued, the next training / test() / gpis3_sync joins it), lazy inverse; "
-                            "= (wall time of update() of frames 2..F + the drain of the last frame's training, gpis3_sync) / (F - 1), MEDIAN repeat of update_repeats fusions; "
-                            "nothing is skipped: the drain is charged") if upd_pipe_mean is not None else "synchronous (sharded training: every frame ends with the model exchange)",
-            "update_ms_per_frame_synchronous": med(upd_ms),
-            "update_synchronous_mode": "gpis3_set_pipeline(map, 0) / GPIS_PIPELINE_UPDATE=0: every update() joins its own training before it returns (the reference's behaviour), lazy inverse: median of frames 2..F of the MEDIAN repeat",
-            "update_ms_per_frame_with_inverse": med(upd_ms_eager),
-            "update_with_inverse_mode": "synchronous with the eager inverse (gpis3_set_lazy_inverse(map, 0) / GPIS_EAGER_INVERSE=1: K3b inside every update()) -- what a test-after-every-update caller pays per frame; median repeat",
-            "update_ms_per_frame_min_over_repeats": med(upd_min),
-            "update_ms_frames": upd_ms,
-            "update_ms_frames_with_inverse": upd_ms_eager,
-            "update_repeats": reps,
-            "update_ms_frames_all": {"eager_inverse": upd_all[:reps], "lazy_inverse": upd_all[reps:]},
-            "update_ms_per_frame_pipelined": upd_pipe_mean,
-            "update_pipelined": {"note": "the default mode: (frames 2..F + drain) / (F - 1) of the median repeat; all repeats listed",
-                                 "ms_frames": upd_pipe, "drain_ms": drain_ms,
-                                 "all_repeats": [{"ms_per_frame": a, "ms_frames": u, "drain_ms": d} for a, u, d in pipe_all]},
-            "deferred_inverse_ms": deferred_ms,
-            "deferred_inverse": {"clusters": int(st0["last_inverse_jobs"]), "device_ms": st0["last_inverse_ms"],
-                                 "note": "lazy inverse (default): the explicit inverses K4 multiplies with are computed once, at the first "
-                                         "test() after the updates, for the clusters retrained since the last prediction; with a test() after "
-                                         "every update() add this to the per-frame update time (GPIS_EAGER_INVERSE=1 restores that split)"},
-            "update_phases_ms": dict(zip(["preproc", "obsgp_train", "reeval_points", "new_points", "update_gps"],
-                                         [float(v) for v in (np.median(ph[1:], axis=0) if len(ph) > 1 else ph[0])])),
             "gp_evals_per_point": sum(p[0] for p in per_rank) / n_total,
             # host_replays: executions of update()'s host logic per rank over the last fusion (F per rank when every rank replays; --train lead: F on rank 0, 0 elsewhere)
             "per_rank": dict({"gp_evals": [p[0] for p in per_rank], "k4_ms_per_step": [p[1] for p in per_rank], "host_replays": [int(p[2]) for p in per_rank]}, **(detail or {})),
@@ -521,22 +501,58 @@ def main():
                          "k4_launches_per_step": launches / args.steps,
                          "algorithmic_flops_per_step": flops / args.steps,
                          "model_bytes": st0["model_bytes"]},
-            "update_roofline": {"kernel": "K6 gather + kernel build + K3 Cholesky (K3b inverse: deferred to the first test(), see deferred_inverse)", "bound": "mfma",
-                                "ms_per_frame": k3_ms, "algorithmic_flops_per_frame": k3_fl,
-                                "achieved": (k3_fl / 1e12) / (k3_ms / 1e3) if k3_ms > 0 else None, "peak": 157.3, "unit": "TFLOP/s",
-                                "with_inverse": {"ms_per_frame": k3e_ms, "achieved": (k3e_fl / 1e12) / (k3e_ms / 1e3) if k3e_ms > 0 else None,
-                                                 "note": "eager mode: K6 + build + K3 + K3b per frame; same flop count (the inverse's K^3/3 is NOT counted)"},
-                                "clusters": ksel[-1]["clusters"], "max_K": max(k["maxK"] for k in ksel),
-                                "note": "flops = sum K^3/3 + 2 K^2 over the clusters retrained per frame (SURVEY 8d); the explicit inverse (another K^3/3, never counted) runs once at the first test() after the updates: deferred_inverse"},
             # sharded training: bytes of model records rank 0 receives per frame (records at their own sizes, back to back), what the
             # one all_gather_into_tensor delivers (slots padded to the largest RANK total), and the sum of all records of a frame
             "exchange_bytes_per_frame": (exch_bytes / max(1, args.frames)) if sharded else 0,
             "exchange_bytes_per_frame_delivered": (exch_padded / max(1, args.frames)) if sharded else 0,
             "exchange_record_bytes_per_frame": (exch_records / max(1, args.frames)) if sharded else 0,
-            "value_host_api": host_api,
-            "stress": stress,
-            "cpu_baseline": cpu,
         }
+        if args.full:
+            med = med_tail
+            ph = np.array(phases)
+            ksel = k3[1:] if len(k3) > 1 else k3
+            k3_ms = float(np.median([k["ms"] for k in ksel]))
+            k3_fl = float(np.median([k["flops"] for k in ksel]))
+            ksel_e = k3_eager[1:] if len(k3_eager) > 1 else k3_eager
+            k3e_ms = float(np.median([k["ms"] for k in ksel_e]))
+            k3e_fl = float(np.median([k["flops"] for k in ksel_e]))
+            out.update({
+                # headline = the library's default mode (pipelined since round 4); sharded multi-rank runs are synchronous (every frame ends with the exchange)
+                "update_ms_per_frame": upd_pipe_mean if upd_pipe_mean is not None else med(upd_ms),
+                "update_mode": ("default mode: pipelined update() (returns once the frame's training is enqueued, the next training / test() / gpis3_sync joins it), lazy inverse; "
+                                "= (wall time of update() of frames 2..F + the drain of the last frame's training, gpis3_sync) / (F - 1), MEDIAN repeat of update_repeats fusions; "
+                                "nothing is skipped: the drain is charged") if upd_pipe_mean is not None else "synchronous (sharded training: every frame ends with the model exchange)",
+                "update_ms_per_frame_synchronous": med(upd_ms),
+                "update_synchronous_mode": "gpis3_set_pipeline(map, 0) / GPIS_PIPELINE_UPDATE=0: every update() joins its own training before it returns (the reference's behaviour), lazy inverse: median of frames 2..F of the MEDIAN repeat",
+                "update_ms_per_frame_with_inverse": med(upd_ms_eager),
+                "update_with_inverse_mode": "synchronous with the eager inverse (gpis3_set_lazy_inverse(map, 0) / GPIS_EAGER_INVERSE=1: K3b inside every update()) -- what a test-after-every-update caller pays per frame; median repeat",
+                "update_ms_per_frame_min_over_repeats": med(upd_min),
+                "update_ms_frames": upd_ms,
+                "update_ms_frames_with_inverse": upd_ms_eager,
+                "update_repeats": reps,
+                "update_ms_frames_all": {"eager_inverse": upd_all[:reps], "lazy_inverse": upd_all[reps:]},
+                "update_ms_per_frame_pipelined": upd_pipe_mean,
+                "update_pipelined": {"note": "the default mode: (frames 2..F + drain) / (F - 1) of the median repeat; all repeats listed",
+                                     "ms_frames": upd_pipe, "drain_ms": drain_ms,
+                                     "all_repeats": [{"ms_per_frame": a, "ms_frames": u, "drain_ms": d} for a, u, d in pipe_all]},
+                "deferred_inverse_ms": deferred_ms,
+                "deferred_inverse": {"clusters": int(st0["last_inverse_jobs"]), "device_ms": st0["last_inverse_ms"],
+                                     "note": "lazy inverse (default): the explicit inverses K4 multiplies with are computed once, at the first "
+                                             "test() after the updates, for the clusters retrained since the last prediction; with a test() after "
+                                             "every update() add this to the per-frame update time (GPIS_EAGER_INVERSE=1 restores that split)"},
+                "update_phases_ms": dict(zip(["preproc", "obsgp_train", "reeval_points", "new_points", "update_gps"],
+                                             [float(v) for v in (np.median(ph[1:], axis=0) if len(ph) > 1 else ph[0])])),
+                "update_roofline": {"kernel": "K6 gather + kernel build + K3 Cholesky (K3b inverse: deferred to the first test(), see deferred_inverse)", "bound": "mfma",
+                                    "ms_per_frame": k3_ms, "algorithmic_flops_per_frame": k3_fl,
+                                    "achieved": (k3_fl / 1e12) / (k3_ms / 1e3) if k3_ms > 0 else None, "peak": 157.3, "unit": "TFLOP/s",
+                                    "with_inverse": {"ms_per_frame": k3e_ms, "achieved": (k3e_fl / 1e12) / (k3e_ms / 1e3) if k3e_ms > 0 else None,
+                                                     "note": "eager mode: K6 + build + K3 + K3b per frame; same flop count (the inverse's K^3/3 is NOT counted)"},
+                                    "clusters": ksel[-1]["clusters"], "max_K": max(k["maxK"] for k in ksel),
+                                    "note": "flops = sum K^3/3 + 2 K^2 over the clusters retrained per frame (SURVEY 8d); the explicit inverse (another K^3/3, never counted) runs once at the first test() after the updates: deferred_inverse"},
+                "value_host_api": host_api,
+                "stress": stress,
+                "cpu_baseline": cpu,
+            })
         print(json.dumps(out))
     if world > 1:
         dist.barrier()

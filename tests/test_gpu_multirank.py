@@ -18,7 +18,7 @@ def _run(world, train, extra=()):
     env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
     port = 29600 + (os.getpid() % 300) + world + (7 if train == "sharded" else (13 if train == "lead" else 0))
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world), "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--backend", "gloo", "--train", train,
+           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--full", "--gpus", str(world), "--backend", "gloo", "--train", train,
            "--grid", "64", "--frames", "2", "--steps", "1", "--warmup", "0", "--cpu-sample", "0", "--stress", "96", "--block", "4096"] + list(extra)
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -67,7 +67,7 @@ def test_bench_self_launches_from_a_plain_python_call():
     env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--grid", "48", "--frames", "1", "--steps", "1",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--backend", "gloo", "--grid", "48", "--frames", "1", "--steps", "1",
            "--warmup", "0", "--cpu-sample", "0", "--stress", "0", "--block", "4096"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]

@@ -61,5 +61,5 @@ fi
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -Igpismap_amd/csrc -Iinclude tools/ubench/pivot_chain.hip -o /tmp/pivot_chain > /dev/null 2>&1 && /tmp/pivot_chain > gpurun_out/${R}_pivot_step_raw.txt 2>&1
 { python3 tools/seq_bench.py --gpu-alone; python3 tools/seq_bench.py; } > gpurun_out/${R}_seq_bench.txt 2>&1
 mkdir -p profiles; cp gpurun_out/${R}_k4_traffic.json profiles/ 2>/dev/null     # (bench.py reports roofline.traffic from it while ongpis_test.hip keeps its sha)
-python bench.py > gpurun_out/${R}_bench_line.json 2> gpurun_out/${R}_bench_err.txt
+python bench.py --full > profiles/${R}_bench_line.json 2> "$TMPDIR/${R}_bench_err.txt"     # the round's whole bench line, every record (--full)
 head -12 gpurun_out/${R}_bench_kernel_stats.txt | cut -c1-150; head -6 gpurun_out/${R}_stress_kstats.txt | cut -c1-150; cat gpurun_out/${R}_k4_traffic.json; cat gpurun_out/${R}_k4_curve.txt; head -8 gpurun_out/${R}_seq_bench.txt | cut -c1-250

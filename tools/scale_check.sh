@@ -1,7 +1,7 @@
 #!/bin/bash
 # 8-GPU node (driver): the scaling curve and the checks the one-GPU box cannot do over RCCL.
 #   tools/scale_check.sh [max_gpus]        default 8
-# For N = 1, 2, 4, 8 and the three training modes (replicated, sharded, lead = sharded with update()'s host logic run once on rank 0): `python3 bench.py --gpus N --verify` -- prints the bench line's value, per-rank
+# For N = 1, 2, 4, 8 and the three training modes (replicated, sharded, lead = sharded with update()'s host logic run once on rank 0): `python3 bench.py --full --gpus N --verify` -- prints the bench line's value, update ms, per-rank
 # GP evaluations, K4 ms, pass / gather / exchange ms, and FAILS if the assembled 256^3 map differs by a bit from rank 0's
 # single-rank pass on a 64^3 sub-grid (bench.py --verify raises).  Then the in-library multi-device map (one process, N
 # devices: gpis3_create_multi) against a one-device map.  Logs: gpurun_out/scale_*.json.
@@ -15,7 +15,7 @@ for N in 1 2 4 8; do
   for MODE in replicated sharded lead; do
     [ $N -eq 1 ] && [ $MODE != replicated ] && continue
     OUT=gpurun_out/scale_${N}_${MODE}.json
-    python3 bench.py --gpus $N --train $MODE --verify --cpu-sample 0 --stress 0 --no-host-api > $OUT
+    python3 bench.py --full --gpus $N --train $MODE --verify --cpu-sample 0 --stress 0 --no-host-api > $OUT
     python3 - "$OUT" $N $MODE <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1]))
