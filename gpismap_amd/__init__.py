@@ -88,6 +88,7 @@ def lib():
     L.gpis3_get_points.argtypes = [vp, fp, C.c_int]
     L.gpis3_get_nodes.argtypes = [vp, fp, C.c_int]
     L.gpis3_stats.argtypes = [vp, dp, C.c_int]
+    L.gpis3_pass_jobs.argtypes = [vp, C.POINTER(C.c_longlong)]
     L.gpis3_set_profile.argtypes = [vp, C.c_int]
     L.gpis3_sync.argtypes = [vp]
     L.gpis3_set_pipeline.argtypes = [vp, C.c_int]
@@ -102,6 +103,7 @@ def lib():
     L.gpis2_test_device.argtypes = [vp, vp, C.c_int, vp, vp]
     L.gpis2_get_nodes.argtypes = [vp, fp, C.c_int]
     L.gpis2_stats.argtypes = [vp, dp, C.c_int]
+    L.gpis2_pass_jobs.argtypes = [vp, C.POINTER(C.c_longlong)]
     if hasattr(L, "gpis2_sync"):
         L.gpis2_sync.argtypes = [vp]
         L.gpis2_set_pipeline.argtypes = [vp, C.c_int]
@@ -122,6 +124,7 @@ def lib():
     L.gpis_ongpis_model_dims.argtypes = [vp, C.c_int, ip]
     L.gpis_ongpis_get_model.argtypes = [vp, C.c_int, fp, fp, ip]
     L.gpis_ongpis_eval.argtypes = [vp, fp, C.c_int, ip, ip, C.c_int, fp]
+    L.gpis_ongpis_eval_layout.argtypes = [vp, fp, C.c_int, ip, ip, C.c_int, C.c_int, fp]
     L.gpis_ongpis_last_ms.argtypes = [vp, fp, fp]
     L.gpis_ongpis_set_exp_table.argtypes = [vp, C.c_int]
     L.gpis_ongpis_kernel_matrix.argtypes = [vp, fp, ip, fp, fp, C.c_int, fp]
@@ -374,6 +377,14 @@ class GPisMap3:
         _check(self.L.gpis3_stats(self.h, a, 28), "gpis3_stats")
         return dict(zip(self.STAT_KEYS, list(a)))
 
+    PASS_KEYS = ("pass1", "pass2_full", "pass2a_value", "pass2b_grad")
+
+    def pass_jobs(self):
+        """K4 jobs of the last test() per evaluation pass (gpis3_pass_jobs)."""
+        a = (C.c_longlong * 4)()
+        _check(self.L.gpis3_pass_jobs(self.h, a), "gpis3_pass_jobs")
+        return dict(zip(self.PASS_KEYS, list(a)))
+
     def save(self, path):
         """Map checkpoint: spatial index, surface points and the packed prediction records of the trained models (gpis3_save)."""
         _check(self.L.gpis3_save(self.h, os.fsencode(path)), "gpis3_save")
@@ -542,6 +553,12 @@ class GPisMap:
         a = (C.c_double * 12)()
         _check(self.L.gpis2_stats(self.h, a, 12), "gpis2_stats")
         return dict(zip(GPisMap3.STAT_KEYS, list(a)))
+
+    def pass_jobs(self):
+        """K4 jobs of the last test() per evaluation pass (gpis2_pass_jobs)."""
+        a = (C.c_longlong * 4)()
+        _check(self.L.gpis2_pass_jobs(self.h, a), "gpis2_pass_jobs")
+        return dict(zip(GPisMap3.PASS_KEYS, list(a)))
 
     def sync(self):
         """Join the training the last update() left in flight (pipelined mode); raises when it failed."""
@@ -1016,14 +1033,16 @@ class OnGPIS:
         _check(self.L.gpis_ongpis_get_model(self.h, int(slot), _p(Lm), _p(alpha), _p(gidx, C.c_int)), "gpis_ongpis_get_model")
         return dict(N=N, ng=ng, K=K, ld=ld, L=Lm.T.copy(), alpha=alpha, gidx=gidx)  # L[r, c]
 
-    def eval(self, xq, job_q, job_model, return_status=False):
+    def eval(self, xq, job_q, job_model, return_status=False, layout=0):
         """return_status=True: (status, out) instead of raising -- GPIS_ERR_STATE (-3, the kernels' error word) still delivers
-        `out`, with the affected results NaN."""
+        `out`, with the affected results NaN.  layout: 0 every result column, 1 component 0 only, 2 components 1..dim only
+        (the other slots of `out` are 0)."""
         xq = np.ascontiguousarray(xq, dtype=np.float32)
         job_q = np.ascontiguousarray(job_q, dtype=np.int32)
         job_model = np.ascontiguousarray(job_model, dtype=np.int32)
         out = np.zeros((job_q.size, 8), dtype=np.float32)
-        rc = self.L.gpis_ongpis_eval(self.h, _p(xq), xq.shape[0], _p(job_q, C.c_int), _p(job_model, C.c_int), job_q.size, _p(out))
+        rc = self.L.gpis_ongpis_eval_layout(self.h, _p(xq), xq.shape[0], _p(job_q, C.c_int), _p(job_model, C.c_int), job_q.size,
+                                            int(layout), _p(out))
         if return_status:
             return int(rc), out
         _check(rc, "gpis_ongpis_eval")

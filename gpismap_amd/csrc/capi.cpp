@@ -20,6 +20,8 @@ using namespace gpis;
 void gpis3_impl_stats(GPisMap3* m, double* out, int n);
 void gpis3_impl_profile(GPisMap3* m, int on);
 void gpis2_impl_stats(GPisMap* m, double* out, int n);
+void gpis3_impl_pass_jobs(GPisMap3* m, long long* out);
+void gpis2_impl_pass_jobs(GPisMap* m, long long* out);
 int gpis3_impl_fail(GPisMap3* m);
 int gpis2_impl_fail(GPisMap* m);
 int gpis3_impl_update_fail(GPisMap3* m);
@@ -177,6 +179,7 @@ int gpis3_load(void* m, const char* path) {
     return rc ? rc : GPIS_ERR_ARG;
 }
 int gpis3_stats(void* m, double* out, int n) { if (!m || !out) return GPIS_ERR_ARG; gpis3_impl_stats((GPisMap3*)m, out, n); return GPIS_OK; }
+int gpis3_pass_jobs(void* m, long long* out4) { if (!m || !out4) return GPIS_ERR_ARG; gpis3_impl_pass_jobs((GPisMap3*)m, out4); return GPIS_OK; }
 int gpis3_sync(void* m) { if (!m) return GPIS_ERR_ARG; try { return gpis3_impl_sync((GPisMap3*)m); } catch (...) { return GPIS_ERR_STATE; } }
 int gpis3_set_pipeline(void* m, int on) { if (!m) return GPIS_ERR_ARG; try { gpis3_impl_set_pipeline((GPisMap3*)m, on); return GPIS_OK; } catch (...) { return GPIS_ERR_STATE; } }
 int gpis3_set_host_gather(void* m, int on) { if (!m) return GPIS_ERR_ARG; gpis3_impl_set_host_gather((GPisMap3*)m, on); return GPIS_OK; }
@@ -221,6 +224,7 @@ int gpis2_get_nodes(void* m, float* out, int cap) {
     return n;
 }
 int gpis2_stats(void* m, double* out, int n) { if (!m || !out) return GPIS_ERR_ARG; gpis2_impl_stats((GPisMap*)m, out, n); return GPIS_OK; }
+int gpis2_pass_jobs(void* m, long long* out4) { if (!m || !out4) return GPIS_ERR_ARG; gpis2_impl_pass_jobs((GPisMap*)m, out4); return GPIS_OK; }
 
 // ---- ObsGP --------------------------------------------------------------------
 struct ObsHandle { int device = -1; ObsGPDevice g; hipStream_t s = nullptr; };
@@ -313,7 +317,10 @@ int gpis_ongpis_get_model(void* s, int model, float* L, float* alpha, int* gidx)
     return GPIS_OK;
 }
 int gpis_ongpis_eval(void* s, const float* xq, int nq, const int* job_q, const int* job_model, int njobs, float* out8) {
-    if (!s || !xq || !job_q || !job_model || !out8 || nq < 1 || njobs < 1) return GPIS_ERR_ARG;
+    return gpis_ongpis_eval_layout(s, xq, nq, job_q, job_model, njobs, 0, out8);
+}
+int gpis_ongpis_eval_layout(void* s, const float* xq, int nq, const int* job_q, const int* job_model, int njobs, int layout, float* out8) {
+    if (!s || !xq || !job_q || !job_model || !out8 || nq < 1 || njobs < 1 || layout < 0 || layout >= ONGPIS_NLAYOUT) return GPIS_ERR_ARG;
     OnHandle* h = (OnHandle*)s;
     DeviceScope dev_scope_(h->device);
     int dim = h->st.dim();
@@ -324,7 +331,7 @@ int gpis_ongpis_eval(void* s, const float* xq, int nq, const int* job_q, const i
     if (no > h->cap_out) { (void)hipFree(h->d_out); h->d_out = nullptr; GPIS_HIP(hipMalloc(&h->d_out, sizeof(float) * no)); h->cap_out = no; }
     GPIS_HIP(hipMemcpyAsync(h->d_xq, x4.data(), sizeof(float) * x4.size(), hipMemcpyHostToDevice, h->s));
     GPIS_HIP(hipMemsetAsync(h->d_out, 0, sizeof(float) * no, h->s));
-    int rc = h->st.eval_jobs(h->d_xq, job_q, job_model, njobs, h->d_out, h->s);
+    int rc = h->st.eval_jobs(h->d_xq, job_q, job_model, njobs, h->d_out, h->s, layout);
     if (rc && rc != GPIS_ERR_STATE) return rc;
     // (GPIS_ERR_STATE = the kernels' error word: the results still travel -- the affected ones are NaN -- and the call fails)
     GPIS_HIP(hipMemcpyAsync(out8, h->d_out, sizeof(float) * no, hipMemcpyDeviceToHost, h->s));

@@ -646,6 +646,10 @@ void gpis2_impl_stats(GPisMap* g, double* out, int n) {
                     (double)m.store.last_train_ms, 0.0};
     for (int i = 0; i < n && i < 12; ++i) out[i] = v[i];
 }
+void gpis2_impl_pass_jobs(GPisMap* g, long long* out) {
+    GPisMap::Impl& m = *g->impl();
+    for (int i = 0; i < 4; ++i) out[i] = m.mq.last_pass_jobs[i];
+}
 
 // Contour extraction (gpis2_extract_contour): testDevice's checks and join, then the lattice and the vertices through the map's MapQuery.
 int gpis2_impl_extract(GPisMap* g, MeshExtractor& me, const int* n2, const float* origin2, const float* step2, float level, void* hip_stream) try {

@@ -2153,6 +2153,10 @@ void gpis3_impl_stats(GPisMap3* g, double* out, int n) {
     for (GPisMap3* q : m.peers) v[26] += (double)q->impl()->stat_host_replays;
     for (int i = 0; i < n && i < 28; ++i) out[i] = v[i];
 }
+void gpis3_impl_pass_jobs(GPisMap3* g, long long* out) {
+    GPisMap3::Impl& m = *g->impl();
+    for (int i = 0; i < 4; ++i) out[i] = m.mq.last_pass_jobs[i];
+}
 // join the training the last update() left in flight; returns the update status (0: fine)
 int gpis3_impl_sync(GPisMap3* g) {
     GPisMap3::Impl& m = *g->impl();

@@ -1,5 +1,5 @@
 // K5 + test() driver: per-query cluster lookup, device-side binning of queries by
-// cluster, two evaluation passes through K4 and the variance-weighted blend.
+// cluster, the evaluation passes through K4 (map_query.hip) and the variance-weighted blend.
 // Reference: GPisMap3::test_kernel cpp/src/GPisMap3.cpp:794-902 and
 // GPisMap::test_kernel cpp/src/GPisMap.cpp:665-763.
 #pragma once
@@ -60,6 +60,8 @@ public:
     int num_clusters() const { return ncl_; }
     // statistics of the last run
     long long last_evals = 0, last_flops = 0, last_touched = 0;
+    // K4 jobs of the last run per pass: 1, 2 full (two-candidate queries), 2a (value column), 2b (gradient columns)
+    long long last_pass_jobs[4] = {0, 0, 0, 0};
     int last_launches = 0;      // K4 launches of the last run
     float last_eval_ms = 0.f;   // time inside the K4 launches (hipEvents on the stream)
     int chunk = 1 << 22;
@@ -68,7 +70,7 @@ public:
 private:
     int ensure_scratch(int n, int nmodels);
     int run_chunk(OnGPISStore& store, const float* d_x, int n, float* d_res, hipStream_t s);
-    int eval_pass(OnGPISStore& store, int njobs, int shift, int rec_base, int nmodels, hipStream_t s);
+    int eval_pass(OnGPISStore& store, int njobs, int shift, int rec_base, int nmodels, hipStream_t s, int layout, int pass);
     int dim_;
     float search_half_, var_thre_, prior_var_;
     int ncl_ = 0;

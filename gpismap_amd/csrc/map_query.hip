@@ -7,6 +7,12 @@
 //            + the sort at GPisMap3.cpp:826-829 (2-D: GPisMap.cpp:695-698).
 //   bin    : counting sort of evaluation jobs by cluster model (histogram, scan,
 //            scatter) and tile list construction -- all on the device.
+//   passes : 1 = every query against its nearest candidate, all columns (mean, gradient, four
+//            variances).  A query whose value variance exceeds thre falls back to its next two:
+//            with two candidates, candidate 2 in full (it is always read); with three, 2a =
+//            the value column only of candidates 2 and 3, then `decide` runs the blend's sort
+//            on the three value variances and 2b = the gradient columns of the candidates
+//            among 2 and 3 the blend reads.  The other gradient columns are never computed.
 //   blend  : GPisMap3.cpp:816-898 / GPisMap.cpp:685-757 (nearest, fallback to the next two
 //            when var > thre, pick or variance-weighted blend).
 #include <algorithm>
@@ -148,20 +154,50 @@ __global__ void jobs_pass1_kernel(const int* __restrict__ cand, const int* __res
     jm[q] = (ncand[q] >= 1) ? cand[q] : -1;
 }
 
-// pass-2 jobs: job j = 2q+s (s = 0,1) -> candidate s+1 when the first variance exceeds thre
+// pass-2 jobs of the queries with exactly want_nc candidates: job j = 2q+s (s = 0,1) -> candidate s+1 when the first
+// variance exceeds thre (want_nc = 2: candidate 2, all columns; 3: candidates 2 and 3, value column -- pass 2a)
 __global__ void jobs_pass2_kernel(const int* __restrict__ cand, const int* __restrict__ ncand, int n, int cap,
-                                  const float* __restrict__ out, float var_thre, float prior_var, int vidx,
+                                  const float* __restrict__ out, float var_thre, float prior_var, int want_nc,
                                   int* __restrict__ jm) {
     int q = blockIdx.x * 256 + threadIdx.x;
     if (q >= n) return;
     int nc = ncand[q];
     bool more = false;
-    if (nc > 1) {
+    if (nc == want_nc) {
         float v0 = (cand[q] >= 0) ? out[(size_t)q * 8 + 4] : prior_var;
         more = v0 > var_thre;
     }
     jm[2 * q] = (more && nc >= 2) ? cand[(size_t)cap + q] : -1;
     jm[2 * q + 1] = (more && nc >= 3) ? cand[(size_t)2 * cap + q] : -1;
+}
+
+// pass-2b jobs (decide): for a three-candidate query in pass 2, blend_kernel's stable sort of the three value variances picks
+// the record(s) it reads in full: the best alone when its variance is below thre, else the best two.  Job 2q+s (s = 0,1) ->
+// candidate s+1 when it is one of them and has a model (one without contributes the prior and got no pass-2a job).
+__global__ void jobs_decide_kernel(const int* __restrict__ cand, const int* __restrict__ ncand, int n, int cap,
+                                   const float* __restrict__ out, float var_thre, float prior_var, int* __restrict__ jm) {
+    int q = blockIdx.x * 256 + threadIdx.x;
+    if (q >= n) return;
+    jm[2 * q] = -1; jm[2 * q + 1] = -1;
+    const int nc = ncand[q];
+    if (nc != 3) return;
+    const float v0 = (cand[q] >= 0) ? out[(size_t)q * 8 + 4] : prior_var;
+    if (!(v0 > var_thre)) return;
+    const int m1 = cand[(size_t)cap + q], m2 = cand[(size_t)2 * cap + q];
+    const float v1 = (m1 >= 0) ? out[((size_t)cap + 2 * (size_t)q) * 8 + 4] : prior_var;
+    const float v2 = (m2 >= 0) ? out[((size_t)cap + 2 * (size_t)q + 1) * 8 + 4] : prior_var;
+    // blend_kernel's stable insertion sort of the indices {0, 1, 2} by value variance, comparison for comparison (written out:
+    // an indexed array here lives in scratch memory)
+    auto var = [&](int i) { return i == 0 ? v0 : (i == 1 ? v1 : v2); };
+    int b0 = 0, b1 = 1;
+    if (v1 < v0) { b0 = 1; b1 = 0; }
+    if (v2 < var(b1)) {
+        b1 = 2;
+        if (v2 < var(b0)) { b1 = b0; b0 = 2; }
+    }
+    if (var(b0) < var_thre) b1 = -1;          // the best alone
+    if (m1 >= 0 && (b0 == 1 || b1 == 1)) jm[2 * q] = m1;
+    if (m2 >= 0 && (b0 == 2 || b1 == 2)) jm[2 * q + 1] = m2;
 }
 
 // ------------------------------------------------------------------ binning ----
@@ -238,12 +274,14 @@ __global__ __launch_bounds__(256) void scatter_lds_kernel(const int* __restrict_
     }
 }
 
-// single block: exclusive scan of job counts; per-class tile bases.  tot[0..3] = tiles per
-// class (tot[0..6]), tot[15] = total jobs, tot[8..14] = class tile offsets.
+// single block: exclusive scan of job counts; per-class tile bases (tq queries per tile).  tot[0..3] = tiles per
+// class (tot[0..6]), tot[15] = total jobs, tot[8..14] = class tile offsets.  Flops per job: the layout's ncol result columns
+// (-1: all 1 + d) and, with gen, the covariance generation.
 __global__ __launch_bounds__(1024) void scan_kernel(const ClusterModel* __restrict__ models, int nmodels,
                                                     const int* __restrict__ cnt, int* __restrict__ base,
                                                     int* __restrict__ tbase, int* __restrict__ cursor,
-                                                    int* __restrict__ tot, unsigned long long* __restrict__ flops) {
+                                                    int* __restrict__ tot, unsigned long long* __restrict__ flops,
+                                                    int tq, int ncol, int gen) {
     __shared__ int sj[1024];
     __shared__ unsigned long long sf[1024];
     __shared__ int st[ONGPIS_NCLASS][1024];
@@ -256,10 +294,11 @@ __global__ __launch_bounds__(1024) void scan_kernel(const ClusterModel* __restri
         int c = cnt[m];
         if (c > 0) {
             int cls = ongpis_class_of_nbx(models[m].ld >> 5);
-            aj += c; at[cls] += (c + ONGPIS_TILE_Q - 1) / ONGPIS_TILE_Q;
-            // algorithmic flops of one evaluation: (1+d) K^2 + 2 (1+d) K + 25 N
-            unsigned long long K = models[m].K, N = models[m].N, d1 = 1 + models[m].dim;
-            af += (unsigned long long)c * (d1 * K * K + 2 * d1 * K + 25 * N);
+            aj += c; at[cls] += (c + tq - 1) / tq;
+            // algorithmic flops of one evaluation: (1+d) K^2 + 2 (1+d) K + 25 N; of a column subset: its columns'
+            // share of the first two terms, the generation term once per evaluation (in the pass that computes the value column)
+            unsigned long long K = models[m].K, N = models[m].N, d1 = ncol < 0 ? 1 + models[m].dim : (unsigned long long)ncol;
+            af += (unsigned long long)c * (d1 * K * K + 2 * d1 * K + (gen ? 25 * N : 0));
         }
     }
     sj[tid] = aj; sf[tid] = af;
@@ -287,7 +326,7 @@ __global__ __launch_bounds__(1024) void scan_kernel(const ClusterModel* __restri
         if (c > 0) {
             int cls = ongpis_class_of_nbx(models[m].ld >> 5);
             tbase[m] = rt[cls];
-            rt[cls] += (c + ONGPIS_TILE_Q - 1) / ONGPIS_TILE_Q;
+            rt[cls] += (c + tq - 1) / tq;
             rj += c;
         } else tbase[m] = 0;
     }
@@ -309,17 +348,17 @@ __global__ void scatter_kernel(const int* __restrict__ jm, int njobs, int shift,
 __global__ void tiles_kernel(const ClusterModel* __restrict__ models, int nmodels, const int* __restrict__ cnt,
                              const int* __restrict__ base, const int* __restrict__ tbase,
                              const int* __restrict__ tot, int* __restrict__ tile_model, int* __restrict__ tile_off,
-                             int* __restrict__ tile_cnt) {
+                             int* __restrict__ tile_cnt, int tq) {
     int m = blockIdx.x;
     int c = cnt[m];
     if (c <= 0) return;
     int cls = ongpis_class_of_nbx(models[m].ld >> 5);
     int t0 = tot[8 + cls] + tbase[m];
-    int nt = (c + ONGPIS_TILE_Q - 1) / ONGPIS_TILE_Q;
+    int nt = (c + tq - 1) / tq;
     for (int i = threadIdx.x; i < nt; i += blockDim.x) {
         tile_model[t0 + i] = m;
-        tile_off[t0 + i] = base[m] + ONGPIS_TILE_Q * i;
-        tile_cnt[t0 + i] = min(ONGPIS_TILE_Q, c - ONGPIS_TILE_Q * i);
+        tile_off[t0 + i] = base[m] + tq * i;
+        tile_cnt[t0 + i] = min(tq, c - tq * i);
     }
 }
 
@@ -499,8 +538,10 @@ int MapQuery::ensure_scratch(int n, int nmodels) {
     return GPIS_OK;
 }
 
-// Bin the jobs in d_jm_ (njobs entries) by model and run K4 over the tiles.
-int MapQuery::eval_pass(OnGPISStore& store, int njobs, int shift, int rec_base, int nmodels, hipStream_t s) {
+// Bin the jobs in d_jm_ (njobs entries) by model and run K4 over the tiles of the layout (EvalLayout).
+int MapQuery::eval_pass(OnGPISStore& store, int njobs, int shift, int rec_base, int nmodels, hipStream_t s, int layout, int pass) {
+    const int tq = ongpis_layout_q(layout);
+    const int ncol = layout == ONGPIS_LAYOUT_VALUE ? 1 : (layout == ONGPIS_LAYOUT_GRAD ? dim_ : -1);
     GPIS_HIP(hipMemsetAsync(d_cnt_, 0, sizeof(int) * (size_t)nmodels, s));
     const bool lds_bins = nmodels <= 8192;   // 2 x 32 KB of LDS at most
     const int nbin_blocks = (njobs + BIN_CHUNK - 1) / BIN_CHUNK;
@@ -509,7 +550,7 @@ int MapQuery::eval_pass(OnGPISStore& store, int njobs, int shift, int rec_base, 
     else
         hipLaunchKernelGGL(hist_kernel, dim3((njobs + 255) / 256), dim3(256), 0, s, d_jm_, njobs, d_cnt_);
     hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(1024), 0, s, store.d_models(), nmodels, d_cnt_, d_base_, d_tbase_,
-                       d_cursor_, d_tot_, reinterpret_cast<unsigned long long*>(d_tot_ + 16));
+                       d_cursor_, d_tot_, reinterpret_cast<unsigned long long*>(d_tot_ + 16), tq, ncol, layout != ONGPIS_LAYOUT_GRAD);
     if (lds_bins)
         hipLaunchKernelGGL(scatter_lds_kernel, dim3(nbin_blocks), dim3(256), sizeof(int) * 2 * (size_t)nmodels, s, d_jm_, njobs,
                            nmodels, shift, rec_base, d_base_, d_cursor_, d_jq_, d_jo_);
@@ -520,11 +561,13 @@ int MapQuery::eval_pass(OnGPISStore& store, int njobs, int shift, int rec_base, 
     int* t_off = d_tile_ + tile_cap_;
     int* t_cnt = d_tile_ + 2 * (size_t)tile_cap_;
     hipLaunchKernelGGL(tiles_kernel, dim3(nmodels), dim3(64), 0, s, store.d_models(), nmodels, d_cnt_, d_base_, d_tbase_,
-                       d_tot_, t_model, t_off, t_cnt);
+                       d_tot_, t_model, t_off, t_cnt, tq);
     int tot[20];
     GPIS_HIP(hipMemcpyAsync(tot, d_tot_, sizeof(int) * 20, hipMemcpyDeviceToHost, s));
     GPIS_HIP(hipStreamSynchronize(s));
-    last_evals += tot[15];
+    // (an evaluation in the reference's sense is a (query, candidate) pair: pass 2b completes evaluations pass 2a counted)
+    if (layout != ONGPIS_LAYOUT_GRAD) last_evals += tot[15];
+    last_pass_jobs[pass] += tot[15];
     { unsigned long long f; std::memcpy(&f, tot + 16, sizeof(f)); last_flops += (long long)f; }
     for (int c = 0; c < ONGPIS_NCLASS; ++c) if (tot[c] > 0) ++last_launches;
     if (profile) {
@@ -572,7 +615,7 @@ int MapQuery::eval_pass(OnGPISStore& store, int njobs, int shift, int rec_base, 
             st = side_[i];
             if (!used[i]) { GPIS_HIP(hipStreamWaitEvent(st, evfork_, 0)); used[i] = true; }
         }
-        int rc = ongpis_eval_launch(c, nt, h_maxN_[c], h_maxLd_[c], a, st);
+        int rc = ongpis_eval_launch(c, nt, h_maxN_[c], h_maxLd_[c], a, st, layout);
         if (rc) { join_sides(); return rc; }
         ++nlaunched;
     }
@@ -605,11 +648,22 @@ int MapQuery::run_chunk(OnGPISStore& store, const float* d_x, int n, float* d_re
         hipLaunchKernelGGL((lookup_tie_kernel<2>), dim3(512), dim3(kTieLanes), 0, s, tv_, d_x, search_half_, d_cand_, cap_n_, d_tie_, d_jq_);
     if (nmodels > 0) {
         hipLaunchKernelGGL(jobs_pass1_kernel, dim3(nblk), dim3(256), 0, s, d_cand_, d_ncand_, n, d_jm_);
-        rc = eval_pass(store, n, 0, 0, nmodels, s);
+        rc = eval_pass(store, n, 0, 0, nmodels, s, ONGPIS_LAYOUT_FULL, 0);
         if (rc) return rc;
+        // pass 2, two-candidate queries: candidate 2 in full
         hipLaunchKernelGGL(jobs_pass2_kernel, dim3(nblk), dim3(256), 0, s, d_cand_, d_ncand_, n, cap_n_, d_out_, var_thre_,
-                           prior_var_, 1 + dim_, d_jm_);
-        rc = eval_pass(store, 2 * n, 1, cap_n_, nmodels, s);
+                           prior_var_, 2, d_jm_);
+        rc = eval_pass(store, 2 * n, 1, cap_n_, nmodels, s, ONGPIS_LAYOUT_FULL, 1);
+        if (rc) return rc;
+        // pass 2a, three-candidate queries: the value column of candidates 2 and 3
+        hipLaunchKernelGGL(jobs_pass2_kernel, dim3(nblk), dim3(256), 0, s, d_cand_, d_ncand_, n, cap_n_, d_out_, var_thre_,
+                           prior_var_, 3, d_jm_);
+        rc = eval_pass(store, 2 * n, 1, cap_n_, nmodels, s, ONGPIS_LAYOUT_VALUE, 2);
+        if (rc) return rc;
+        // pass 2b: the gradient columns of the records the blend reads in full
+        hipLaunchKernelGGL(jobs_decide_kernel, dim3(nblk), dim3(256), 0, s, d_cand_, d_ncand_, n, cap_n_, d_out_, var_thre_,
+                           prior_var_, d_jm_);
+        rc = eval_pass(store, 2 * n, 1, cap_n_, nmodels, s, ONGPIS_LAYOUT_GRAD, 3);
         if (rc) return rc;
     }
     if (dim_ == 3)
@@ -622,6 +676,7 @@ int MapQuery::run_chunk(OnGPISStore& store, const float* d_x, int n, float* d_re
 
 int MapQuery::run(OnGPISStore& store, const float* d_x, int n, float* d_res, hipStream_t s) {
     last_evals = 0; last_eval_ms = 0.f; last_flops = 0; last_launches = 0;
+    for (long long& j : last_pass_jobs) j = 0;
     if (n <= 0) return GPIS_OK;
     int rc = prepare(store, s);
     if (rc) return rc;
@@ -654,6 +709,7 @@ bool MapQuery::cluster_box(float* lo, float* hi) const {
 
 int MapQuery::run_prepared(OnGPISStore& store, const float* d_x, int n, float* d_res, hipStream_t s) {
     last_evals = 0; last_eval_ms = 0.f; last_flops = 0; last_launches = 0;
+    for (long long& j : last_pass_jobs) j = 0;
     if (n <= 0) return GPIS_OK;
     int rc = GPIS_OK;
     const int nc = 2 * (1 + dim_);

@@ -78,9 +78,10 @@ public:
                       int* counts, hipStream_t s);
     int train_batch_dev(const std::vector<TrainJob>& jobs, hipStream_t s);
     // Predict: jobs (query index, model slot) evaluated against xq (device, [nq][4]); out
-    // (device) receives 2*(1+dim) floats per job: mean(1+dim), var(1+dim).
+    // (device) receives 2*(1+dim) floats per job: mean(1+dim), var(1+dim) -- of the components the layout holds
+    // (EvalLayout; the other slots of a record are left as they are).
     int eval_jobs(const float* d_xq4, const int* h_job_q, const int* h_job_model, int njobs, float* d_out,
-                  hipStream_t s);
+                  hipStream_t s, int layout = 0);
     // ---- multi-GPU exchange (model_pack.hip): packed records of what K4 needs from a trained model ----
     size_t packed_bytes(const int* slots, int n) const;                 // largest record among the listed models
     // record i at byte offset offs[i] of d_buf (offs == nullptr: i * stride; otherwise stride is ignored and the records
@@ -245,7 +246,7 @@ struct EvalArgs {
     const float4* xq;        // [nq] query points (x, y, z|0, 0)
     const int* tile_model;   // [ntiles]
     const int* tile_off;     // [ntiles] first job of the tile in job_q / job_out
-    const int* tile_cnt;     // [ntiles] 1..ONGPIS_TILE_Q
+    const int* tile_cnt;     // [ntiles] 1..ongpis_layout_q(layout) queries
     const int* job_q;        // query index per job (sorted by model)
     const int* job_out;      // output record per job
     float* out;              // [records][8]: mean(4) var(4)  (2-D uses 3+3, slots 3 and 7 unused)
@@ -272,8 +273,18 @@ __host__ __device__ inline int ongpis_class_of_nbx(int nbx) {
 size_t ongpis_eval_small_lds(int maxN, int maxLd);
 int ongpis_eval_small_launch(int ntiles, int maxN, int maxLd, const EvalArgs& args, hipStream_t s);
 #endif
+// Result columns of a K4 tile: which (query, component) pairs its 32 B columns hold.  Column n of a tile is query n / CPQ,
+// component C0 + n % CPQ; every column is computed with the same expressions and reduced in the same order whatever the layout,
+// so a component comes out with the same bits in each.
+enum EvalLayout {
+    ONGPIS_LAYOUT_FULL = 0,   // 8 queries x components 0..3: mean, gradient, the four variances
+    ONGPIS_LAYOUT_VALUE = 1,  // 32 queries x component 0: mean f and value variance only
+    ONGPIS_LAYOUT_GRAD = 2,   // 10 queries x components 1..3 (columns 30, 31 empty): gradient and its variances only
+    ONGPIS_NLAYOUT = 3
+};
+__host__ __device__ inline int ongpis_layout_q(int layout) { return layout == ONGPIS_LAYOUT_VALUE ? 32 : (layout == ONGPIS_LAYOUT_GRAD ? 10 : ONGPIS_TILE_Q); }
 int ongpis_eval_class(int nbx);
 bool ongpis_eval_fits(int N, int ld);
-int ongpis_eval_launch(int wclass, int ntiles, int maxN, int maxLd, const EvalArgs& args, hipStream_t s);
+int ongpis_eval_launch(int wclass, int ntiles, int maxN, int maxLd, const EvalArgs& args, hipStream_t s, int layout = ONGPIS_LAYOUT_FULL);
 
 }  // namespace gpis

@@ -1037,11 +1037,13 @@ int OnGPISStore::unpack_models(const void* d_buf, int n, size_t stride, int* slo
     return GPIS_OK;
 }
 
-// Job-level predict with host job arrays: sort by model, cut into tiles of ONGPIS_TILE_Q (16), launch per
+// Job-level predict with host job arrays: sort by model, cut into tiles of the layout's query count, launch per
 // size class.  (The map-level test path bins on the device instead, see map_query.hip.)
 int OnGPISStore::eval_jobs(const float* d_xq4, const int* h_job_q, const int* h_job_model, int njobs, float* d_out,
-                           hipStream_t s) {
+                           hipStream_t s, int layout) {
     if (njobs <= 0) return GPIS_OK;
+    if (layout < 0 || layout >= ONGPIS_NLAYOUT) return GPIS_ERR_ARG;
+    const int tq = ongpis_layout_q(layout);
     int rc = ensure_inverses(s);
     if (rc) return rc;
     rc = sync_models(s);
@@ -1059,8 +1061,8 @@ int OnGPISStore::eval_jobs(const float* d_xq4, const int* h_job_q, const int* h_
         int cls = ongpis_eval_class(m->ld / 32);
         int e = i;
         while (e < njobs && h_job_model[order[e]] == mslot) ++e;
-        for (int t = i; t < e; t += ONGPIS_TILE_Q) {
-            tmodel[cls].push_back(mslot); toff[cls].push_back(t); tcnt[cls].push_back(std::min(ONGPIS_TILE_Q, e - t));
+        for (int t = i; t < e; t += tq) {
+            tmodel[cls].push_back(mslot); toff[cls].push_back(t); tcnt[cls].push_back(std::min(tq, e - t));
         }
         maxN[cls] = std::max(maxN[cls], m->N); maxLd[cls] = std::max(maxLd[cls], m->ld);
         for (int t = i; t < e; ++t) { jq[t] = h_job_q[order[t]]; jo[t] = order[t]; }
@@ -1100,7 +1102,7 @@ int OnGPISStore::eval_jobs(const float* d_xq4, const int* h_job_q, const int* h_
         a.models = d_models_; a.xq = reinterpret_cast<const float4*>(d_xq4);
         a.tile_model = d_t + base[c]; a.tile_off = d_t + base[c] + nt; a.tile_cnt = d_t + base[c] + 2 * nt;
         a.job_q = d_jq; a.job_out = d_jo; a.out = d_out; a.cb = 0; a.debug = debug_inject; a.err = eval_err(); a.trace = nullptr;
-        rc = ongpis_eval_launch(c, nt, maxN[c], maxLd[c], a, s);
+        rc = ongpis_eval_launch(c, nt, maxN[c], maxLd[c], a, s, layout);
         if (rc) return rc;
     }
     if (profile) GPIS_HIP(hipEventRecord(ev1_, s));

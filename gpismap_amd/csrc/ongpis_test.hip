@@ -1,4 +1,5 @@
-// K4: batched OnGPIS prediction -- mean (value + gradient) and the four variances for tiles of 8 queries against one cluster model.
+// K4: batched OnGPIS prediction -- mean (value + gradient) and the four variances for tiles of 8 queries against one cluster model,
+// or a subset of those result columns for more queries per tile (EvalLayout, ongpis.h).
 //
 // Replaces the reference per-point chain
 //   GPisMap3::test_kernel        cpp/src/GPisMap3.cpp:794-902  (2-D: GPisMap.cpp:665-763)
@@ -6,7 +7,8 @@
 //        -> matern32_sparse_deriv1_3D (cross)  cpp/src/covFnc.cpp:258-314 (2-D: :404-450)
 //        -> k*^T alpha ; L^-1 k* ; column sums of squares
 //
-// The (1+d) cross-covariance columns of 8 queries form a K x 32 block B.  The reference solves L V = B by substitution (K dependent
+// The (1+d) cross-covariance columns of 8 queries form a K x 32 block B (the other layouts: the value columns of 32 queries, or the
+// d gradient columns of 10).  The reference solves L V = B by substitution (K dependent
 // steps); here the factor's explicit inverse X = L^-1 comes out of training (K3b), so V = X B (32 x 32 tiles,
 // v_mfma_f32_32x32x2_f32) has NO dependency between its block rows: every wavefront owns a few block rows (accumulators in
 // registers), streams their X tiles from L2 once and reads the B tiles all wavefronts share from LDS.  alpha rides as row K of X.
@@ -74,9 +76,22 @@ __device__ __forceinline__ void k4_ring_signal(lds_cnt_t p, int lane) {
     if (lane == 0) __hip_atomic_fetch_add((int __attribute__((address_space(3)))*)p, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
 
+// Result columns per layout (EvalLayout): QPT queries per tile, CPQ components per query starting at component C0; column n of the
+// tile = (query n / CPQ, component C0 + n % CPQ).
+template <int LAYOUT> struct K4Layout {
+    static constexpr int QPT = LAYOUT == ONGPIS_LAYOUT_VALUE ? 32 : (LAYOUT == ONGPIS_LAYOUT_GRAD ? 10 : 8);
+    static constexpr int CPQ = LAYOUT == ONGPIS_LAYOUT_VALUE ? 1 : (LAYOUT == ONGPIS_LAYOUT_GRAD ? 3 : 4);
+    static constexpr int C0 = LAYOUT == ONGPIS_LAYOUT_GRAD ? 1 : 0;
+    static constexpr int NXQ = QPT > 16 ? QPT : 16;                           // staged query slots in LDS
+    static constexpr int UNROLL = LAYOUT == ONGPIS_LAYOUT_VALUE ? 4 : 2;      // query chains per lane in flight during generation
+};
+static_assert(K4Layout<ONGPIS_LAYOUT_FULL>::QPT == ONGPIS_TILE_Q, "the full layout is the tile of the job-level path");
+
 // W wavefronts per workgroup, every one generating B tiles and multiplying; kNBW block rows per wavefront and row group
-template <int W>
+template <int W, int LAYOUT>
 __global__ __launch_bounds__(64 * W, kMinW) void ongpis_eval_kernel(EvalArgs A) {
+    typedef K4Layout<LAYOUT> LY;
+    static_assert(LY::QPT * LY::CPQ <= 32 && LY::QPT % 2 == 0, "a tile holds at most 32 columns, half of its queries per lane half");
     constexpr int NBW = kNBW;
     constexpr int RG = NBW * W;   // block rows per row group
     constexpr int NSLOT = kSlots;
@@ -102,7 +117,7 @@ __global__ __launch_bounds__(64 * W, kMinW) void ongpis_eval_kernel(EvalArgs A) 
     // fed from the same ring slots -- the same chain (ascending k from zero) the matrix instruction would run.
     const bool mean_alone = (K & 31) == 0;
     const int nbv = mean_alone ? nbx - 1 : nbx;       // block rows of V dealt to the wavefronts (= nb, the column blocks of B)
-    const int joff = A.tile_off[tile], jcnt = A.tile_cnt[tile];   // 1..8 queries
+    const int joff = A.tile_off[tile], jcnt = A.tile_cnt[tile];   // 1..QPT queries
     const int CB = A.cb;
     // test hook (gpis_ongpis_set_debug, inject bit 4): in the launch's first workgroup wavefront 0 withholds its first ring signal
     const bool withhold = (A.debug & 16) != 0 && blockIdx.x == 0;
@@ -112,9 +127,9 @@ __global__ __launch_bounds__(64 * W, kMinW) void ongpis_eval_kernel(EvalArgs A) 
     // LDS carve (all dynamic, 16-byte aligned pieces)
     constexpr int NC = 32;        // result columns of the workgroup
     float* red = reinterpret_cast<float*>(smem);                       // [W][NC] sums of squares, then [NC] means
-    float4* s_xq = reinterpret_cast<float4*>(red + W * NC + NC);       // [16] the tile's query points
-    int* s_ri = reinterpret_cast<int*>(s_xq + 16) + 32;                // [ld] row -> point | component
-    lds_cnt_t ring_cnt = (lds_cnt_t)(reinterpret_cast<int*>(s_xq + 16));    // [0..2] tiles generated per slot, [8..10] wavefronts done per slot (cumulative), [15] a wait expired
+    float4* s_xq = reinterpret_cast<float4*>(red + W * NC + NC);       // [NXQ] the tile's query points
+    int* s_ri = reinterpret_cast<int*>(s_xq + LY::NXQ) + 32;           // [ld] row -> point | component
+    lds_cnt_t ring_cnt = (lds_cnt_t)(reinterpret_cast<int*>(s_xq + LY::NXQ));    // [0..2] tiles generated per slot, [8..10] wavefronts done per slot (cumulative), [15] a wait expired
     if (tid < 16) ring_cnt[tid] = 0;
     float4* s_x4 = reinterpret_cast<float4*>(s_ri + ld);               // [N]   (ld is a multiple of 32 -> 16-B aligned)
     f64x2* s_exp = reinterpret_cast<f64x2*>(s_x4 + N);                 // [64] 2^(j/64) as (hi, lo): exp_tab.h
@@ -126,7 +141,7 @@ __global__ __launch_bounds__(64 * W, kMinW) void ongpis_eval_kernel(EvalArgs A) 
         gfptr g_x4 = (gfptr)mp->x4;
         for (int i = tid; i < ld; i += 64 * W) s_ri[i] = g_ri[i];
         for (int i = tid; i < 4 * N; i += 64 * W) reinterpret_cast<float*>(s_x4)[i] = g_x4[i];
-        if (tid < 16) s_xq[tid] = (tid < jcnt) ? A.xq[A.job_q[joff + tid]] : make_float4(0.f, 0.f, 0.f, 0.f);
+        if (tid < LY::NXQ) s_xq[tid] = (tid < jcnt) ? A.xq[A.job_q[joff + tid]] : make_float4(0.f, 0.f, 0.f, 0.f);
         if (tid < 64) s_exp[tid] = *reinterpret_cast<const f64x2*>(kExp64Tab[tid]);
         __syncthreads();
     }
@@ -138,10 +153,10 @@ __global__ __launch_bounds__(64 * W, kMinW) void ongpis_eval_kernel(EvalArgs A) 
     const __amdgpu_buffer_rsrc_t Xrs = __builtin_amdgcn_make_buffer_rsrc((void*)mp->Xt, 0, (unsigned)ntl * 4096u, 0x00020000);
     const int Tvoff = lane * 16;
     K4_STAMP();
-    // ---- generation of one B tile (column block c) into an LDS tile: lane (r, qh) produces the 16 entries of tile row r for the
-    // queries 4qh..4qh+3.  KIND = row type of the whole tile when it is uniform (0: value rows, 1..3: d/dx_c rows -- rows are ordered
+    // ---- generation of one B tile (column block c) into an LDS tile: lane (r, qh) produces the entries of tile row r for the
+    // queries QPL qh .. QPL qh + QPL - 1 (QPL = QPT / 2; full layout: 16 entries, queries 4qh..4qh+3).  KIND = row type of the whole tile when it is uniform (0: value rows, 1..3: d/dx_c rows -- rows are ordered
     // by type, so almost every tile is uniform and the type selects of covFnc.cpp:292-308 fold away), -1: mixed tile.
-    // Stored k-contiguous per column: element (row, n = 16 qh + 4 j + comp) -> tbuf[n * 36 + (row & 1) * 16 + (row >> 1)], i.e.
+    // Stored k-contiguous per column: element (row, n = CPQ q + comp - C0) -> tbuf[n * 36 + (row & 1) * 16 + (row >> 1)], i.e.
     // Bt[n][h][kk] = B[2 kk + h][n]: a lane's 16 operand values are FOUR 16-byte reads, a wavefront's stores hit 32 different banks.
     const int ngr = (dim > 0) ? (K - N) / dim : 0;   // rows per derivative component
     auto row_type = [&](int r) { return r < N ? 0 : 1 + (r - N) / (ngr > 0 ? ngr : 1); };
@@ -156,35 +171,81 @@ __global__ __launch_bounds__(64 * W, kMinW) void ongpis_eval_kernel(EvalArgs A) 
             cr = (KIND >= 0) ? KIND : ((info >> 28) & 0xF);
             xp = x4[info & 0x0FFFFFFF];
         }
+        if constexpr (LAYOUT == ONGPIS_LAYOUT_FULL) {   // (its own loop: the generic one below costs the full layout 4 VGPRs)
 #pragma unroll 2      // (two independent chains hide the double-precision latencies; 4 measured slower)
-        for (int j = 0; j < 4; ++j) {
-            const int q = 4 * qh + j;
-            float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (row < K && q < jcnt) {
-                const float4 xq = s_xq[q];
-                float d[3] = {xp.x - xq.x, xp.y - xq.y, xp.z - xq.z};
-                float rr = sqrt_ranged((dim == 3) ? (d[0] * d[0] + d[1] * d[1]) + d[2] * d[2] : d[0] * d[0] + d[1] * d[1]);   // (= sqrtf: squared distances are 0 or far above 2^-96)
-                const double e = exp_neg_tab(-a * rr, s_exp);
-                float v0, v1, v2, v3;
-                if (cr == 0) {
-                    v0 = d_kf(rr, a, e); v1 = d_kf1(d[0], a, e); v2 = d_kf1(d[1], a, e); v3 = d_kf1(d[2], a, e);
-                } else {
-                    const float dr = cr == 1 ? d[0] : (cr == 2 ? d[1] : d[2]);
-                    v0 = -d_kf1(dr, a, e);
-                    // mixed second derivatives: lower component first (covFnc.cpp:300-308).  The three divisions by r share the divisor's
-                    // refined reciprocal (tile_solve.h div_ranged: the bits of `/`; r = 0 -- a query ON a training point -- gives the
-                    // reference's NaN)
-                    const float ri = rcp_refined(rr);
-                    auto kf2 = [&](float dx1, float dx2, float delta) { return (float)((double)(a * a * (delta - div_ranged_anyzero(a * dx1 * dx2, rr, ri))) * e); };   // (delta - (+-0) is delta either way)
-                    v1 = (cr == 1) ? kf2(d[0], d[0], 1.0f) : kf2(d[0], dr, 0.0f);
-                    v2 = (cr == 2) ? kf2(d[1], d[1], 1.0f) : (cr == 1 ? kf2(d[0], d[1], 0.0f) : kf2(d[1], d[2], 0.0f));
-                    v3 = (cr == 3) ? kf2(d[2], d[2], 1.0f) : kf2(dr, d[2], 0.0f);
+            for (int j = 0; j < 4; ++j) {
+                const int q = 4 * qh + j;
+                float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (row < K && q < jcnt) {
+                    const float4 xq = s_xq[q];
+                    float d[3] = {xp.x - xq.x, xp.y - xq.y, xp.z - xq.z};
+                    float rr = sqrt_ranged((dim == 3) ? (d[0] * d[0] + d[1] * d[1]) + d[2] * d[2] : d[0] * d[0] + d[1] * d[1]);   // (= sqrtf: squared distances are 0 or far above 2^-96)
+                    const double e = exp_neg_tab(-a * rr, s_exp);
+                    float v0, v1, v2, v3;
+                    if (cr == 0) {
+                        v0 = d_kf(rr, a, e); v1 = d_kf1(d[0], a, e); v2 = d_kf1(d[1], a, e); v3 = d_kf1(d[2], a, e);
+                    } else {
+                        const float dr = cr == 1 ? d[0] : (cr == 2 ? d[1] : d[2]);
+                        v0 = -d_kf1(dr, a, e);
+                        // mixed second derivatives: lower component first (covFnc.cpp:300-308).  The three divisions by r share the divisor's
+                        // refined reciprocal (tile_solve.h div_ranged: the bits of `/`; r = 0 -- a query ON a training point -- gives the
+                        // reference's NaN)
+                        const float ri = rcp_refined(rr);
+                        auto kf2 = [&](float dx1, float dx2, float delta) { return (float)((double)(a * a * (delta - div_ranged_anyzero(a * dx1 * dx2, rr, ri))) * e); };   // (delta - (+-0) is delta either way)
+                        v1 = (cr == 1) ? kf2(d[0], d[0], 1.0f) : kf2(d[0], dr, 0.0f);
+                        v2 = (cr == 2) ? kf2(d[1], d[1], 1.0f) : (cr == 1 ? kf2(d[0], d[1], 0.0f) : kf2(d[1], d[2], 0.0f));
+                        v3 = (cr == 3) ? kf2(d[2], d[2], 1.0f) : kf2(dr, d[2], 0.0f);
+                    }
+                    if (dim == 2) v3 = 0.f;
+                    o = make_float4(v0, v1, v2, v3);
                 }
-                if (dim == 2) v3 = 0.f;
-                o = make_float4(v0, v1, v2, v3);
+                float* tcol = tbuf + (16 * qh + 4 * j) * kTileStride + (rr_ & 1) * 16 + (rr_ >> 1);
+                tcol[0] = o.x; tcol[kTileStride] = o.y; tcol[2 * kTileStride] = o.z; tcol[3 * kTileStride] = o.w;
             }
-            float* tcol = tbuf + (16 * qh + 4 * j) * kTileStride + (rr_ & 1) * 16 + (rr_ >> 1);
-            tcol[0] = o.x; tcol[kTileStride] = o.y; tcol[2 * kTileStride] = o.z; tcol[3 * kTileStride] = o.w;
+        } else {
+            // the other layouts: the same expressions per component as the loop above, only for the layout's components
+            constexpr int QPL = LY::QPT / 2, CPQ = LY::CPQ, C0 = LY::C0;
+#pragma unroll LY::UNROLL
+            for (int j = 0; j < QPL; ++j) {
+                const int q = QPL * qh + j;
+                // component c of the query lands in o[c - C0]; only the layout's components are computed (each with the expression
+                // the full layout uses, so every column has the same bits in every layout)
+                float o[CPQ];
+#pragma unroll
+                for (int k = 0; k < CPQ; ++k) o[k] = 0.f;
+                if (row < K && q < jcnt) {
+                    const float4 xq = s_xq[q];
+                    float d[3] = {xp.x - xq.x, xp.y - xq.y, xp.z - xq.z};
+                    float rr = sqrt_ranged((dim == 3) ? (d[0] * d[0] + d[1] * d[1]) + d[2] * d[2] : d[0] * d[0] + d[1] * d[1]);   // (= sqrtf: squared distances are 0 or far above 2^-96)
+                    const double e = exp_neg_tab(-a * rr, s_exp);
+                    if (cr == 0) {
+                        if constexpr (C0 == 0) o[0] = d_kf(rr, a, e);
+                        if constexpr (C0 + CPQ > 1) { o[1 - C0] = d_kf1(d[0], a, e); o[2 - C0] = d_kf1(d[1], a, e); o[3 - C0] = d_kf1(d[2], a, e); }
+                    } else {
+                        const float dr = cr == 1 ? d[0] : (cr == 2 ? d[1] : d[2]);
+                        if constexpr (C0 == 0) o[0] = -d_kf1(dr, a, e);
+                        if constexpr (C0 + CPQ > 1) {
+                            // mixed second derivatives: lower component first (covFnc.cpp:300-308).  The three divisions by r share the divisor's
+                            // refined reciprocal (tile_solve.h div_ranged: the bits of `/`; r = 0 -- a query ON a training point -- gives the
+                            // reference's NaN)
+                            const float ri = rcp_refined(rr);
+                            auto kf2 = [&](float dx1, float dx2, float delta) { return (float)((double)(a * a * (delta - div_ranged_anyzero(a * dx1 * dx2, rr, ri))) * e); };   // (delta - (+-0) is delta either way)
+                            o[1 - C0] = (cr == 1) ? kf2(d[0], d[0], 1.0f) : kf2(d[0], dr, 0.0f);
+                            o[2 - C0] = (cr == 2) ? kf2(d[1], d[1], 1.0f) : (cr == 1 ? kf2(d[0], d[1], 0.0f) : kf2(d[1], d[2], 0.0f));
+                            o[3 - C0] = (cr == 3) ? kf2(d[2], d[2], 1.0f) : kf2(dr, d[2], 0.0f);
+                        }
+                    }
+                    if constexpr (C0 + CPQ > 3) { if (dim == 2) o[3 - C0] = 0.f; }
+                }
+                float* tcol = tbuf + (CPQ * q) * kTileStride + (rr_ & 1) * 16 + (rr_ >> 1);
+#pragma unroll
+                for (int k = 0; k < CPQ; ++k) tcol[k * kTileStride] = o[k];
+            }
+            // columns no query of the layout owns (gradient layout: 30, 31) are zero, not what the slot held before
+            if constexpr (LY::QPT * CPQ < 32) {
+#pragma unroll
+                for (int n = LY::QPT * CPQ + qh; n < 32; n += 2) tbuf[n * kTileStride + (rr_ & 1) * 16 + (rr_ >> 1)] = 0.f;
+            }
         }
     };
     auto gen_tile = [&](int c, float* tbuf) {
@@ -370,7 +431,7 @@ __global__ __launch_bounds__(64 * W, kMinW) void ongpis_eval_kernel(EvalArgs A) 
     __syncthreads();
     {
         const int col = tid & 63;                       // wave 0: one lane per (query, component) column
-        const int qi = col >> 2, cq = col & 3;
+        const int qi = col / LY::CPQ, cq = LY::C0 + col % LY::CPQ;
         const bool ring_failed = ring_cnt[15] != 0;     // a bounded ring wait ran out (protocol error): poison, loudly
         if (ring_failed && tid == 0 && A.err) __hip_atomic_fetch_or(A.err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         if (wave == 0 && col < NC && qi < jcnt && cq <= dim) {
@@ -395,13 +456,15 @@ __global__ __launch_bounds__(64 * W, kMinW) void ongpis_eval_kernel(EvalArgs A) 
 static const int kClassW[ONGPIS_NCLASS] = {1, 2, 4, 4, kW3, kW3, kW3};
 constexpr int kWavesPerCU = 4 * kMinW;   // resident wavefronts per CU the register budget of the kernels admits
 
-static size_t eval_lds_fixed(int W, int maxN, int maxLd) {
-    return sizeof(float) * (W * 32 + 32) + 16 * sizeof(float4) + 32 * sizeof(int) + sizeof(int) * (size_t)maxLd + 16 * (size_t)maxN + 64 * 16;
+// (nxq: staged query slots, K4Layout::NXQ -- 16, or 32 for the value layout)
+static size_t eval_lds_fixed(int W, int maxN, int maxLd, int nxq) {
+    return sizeof(float) * (W * 32 + 32) + nxq * sizeof(float4) + 32 * sizeof(int) + sizeof(int) * (size_t)maxLd + 16 * (size_t)maxN + 64 * 16;
 }
+constexpr int kMaxNXQ = 32;   // the largest staged query table of the layouts
 
-int ongpis_eval_launch(int wclass, int ntiles, int maxN, int maxLd, const EvalArgs& args_in, hipStream_t s) {
+int ongpis_eval_launch(int wclass, int ntiles, int maxN, int maxLd, const EvalArgs& args_in, hipStream_t s, int layout) {
     if (ntiles <= 0) return GPIS_OK;
-    if (wclass < 0 || wclass >= ONGPIS_NCLASS) return GPIS_ERR_ARG;
+    if (wclass < 0 || wclass >= ONGPIS_NCLASS || layout < 0 || layout >= ONGPIS_NLAYOUT) return GPIS_ERR_ARG;
     EvalArgs args = args_in;
 #ifdef GPIS_EXPERIMENTS   // the archived resident-X kernel for clusters of at most ONGPIS_SMALL_NBX block rows (tools/experiments/)
     if (getenv("GPIS_SMALL_KERNEL") && atoi(getenv("GPIS_SMALL_KERNEL")) && wclass <= 2 && maxLd / 32 <= ONGPIS_SMALL_NBX && ongpis_eval_small_lds(maxN, maxLd) <= (size_t)160 * 1024) return ongpis_eval_small_launch(ntiles, maxN, maxLd, args_in, s);
@@ -412,7 +475,9 @@ int ongpis_eval_launch(int wclass, int ntiles, int maxN, int maxLd, const EvalAr
     const size_t hard = 158 * 1024;
     const size_t share = std::min(hard, hard * W / kWavesPerCU);
     const size_t blk = sizeof(float) * kTileFloats;    // one column block
-    const size_t fixed = eval_lds_fixed(W, maxN, maxLd);
+    const int nxq = layout == ONGPIS_LAYOUT_VALUE ? K4Layout<ONGPIS_LAYOUT_VALUE>::NXQ : K4Layout<ONGPIS_LAYOUT_FULL>::NXQ;
+    static_assert(K4Layout<ONGPIS_LAYOUT_GRAD>::NXQ == K4Layout<ONGPIS_LAYOUT_FULL>::NXQ && K4Layout<ONGPIS_LAYOUT_VALUE>::NXQ == kMaxNXQ, "staged query slots");
+    const size_t fixed = eval_lds_fixed(W, maxN, maxLd, nxq);
     if (fixed + kSlots * blk > hard) return GPIS_ERR_LIMIT;
     // (the small classes keep their occupancy: wider chunks at the price of fewer workgroups per CU measured 35 -> 30 % at K = 204)
     const size_t budget = std::min(hard, std::max(share, fixed + kSlots * blk));
@@ -422,13 +487,16 @@ int ongpis_eval_launch(int wclass, int ntiles, int maxN, int maxLd, const EvalAr
     args.cb = cb;
     const size_t lds = fixed + (size_t)kSlots * cb * blk;
     typedef void (*kern_t)(EvalArgs);
-    static const kern_t kern[4] = {ongpis_eval_kernel<1>, ongpis_eval_kernel<2>, ongpis_eval_kernel<4>, ongpis_eval_kernel<kW3>};
+    static const kern_t kern[ONGPIS_NLAYOUT][4] = {
+        {ongpis_eval_kernel<1, ONGPIS_LAYOUT_FULL>, ongpis_eval_kernel<2, ONGPIS_LAYOUT_FULL>, ongpis_eval_kernel<4, ONGPIS_LAYOUT_FULL>, ongpis_eval_kernel<kW3, ONGPIS_LAYOUT_FULL>},
+        {ongpis_eval_kernel<1, ONGPIS_LAYOUT_VALUE>, ongpis_eval_kernel<2, ONGPIS_LAYOUT_VALUE>, ongpis_eval_kernel<4, ONGPIS_LAYOUT_VALUE>, ongpis_eval_kernel<kW3, ONGPIS_LAYOUT_VALUE>},
+        {ongpis_eval_kernel<1, ONGPIS_LAYOUT_GRAD>, ongpis_eval_kernel<2, ONGPIS_LAYOUT_GRAD>, ongpis_eval_kernel<4, ONGPIS_LAYOUT_GRAD>, ongpis_eval_kernel<kW3, ONGPIS_LAYOUT_GRAD>}};
     const int kidx = wclass < 3 ? wclass : (wclass == 3 ? 2 : 3);
-    if (ensure_dynamic_lds((const void*)kern[kidx], 160 * 1024) != GPIS_OK) return GPIS_ERR_HIP;
+    if (ensure_dynamic_lds((const void*)kern[layout][kidx], 160 * 1024) != GPIS_OK) return GPIS_ERR_HIP;
 #ifdef GPIS_INSTRUMENT
     k4_trace_arm(args, s);
 #endif
-    hipLaunchKernelGGL(kern[kidx], dim3(ntiles), dim3(64 * W), lds, s, args);
+    hipLaunchKernelGGL(kern[layout][kidx], dim3(ntiles), dim3(64 * W), lds, s, args);
 #ifdef GPIS_INSTRUMENT
     k4_trace_dump(s, W, 0, ntiles, maxN, maxLd, cb);
 #endif
@@ -439,11 +507,11 @@ int ongpis_eval_launch(int wclass, int ntiles, int maxN, int maxLd, const EvalAr
 
 int ongpis_eval_class(int nbx) { return ongpis_class_of_nbx(nbx); }
 
-// Can K4 hold a cluster (row table + points in LDS beside a three-slot ring of one column block each)?  Asked at TRAINING time: a
-// cluster that could be factorised but never evaluated is refused there (GPIS_ERR_LIMIT, the previous model is kept).
+// Can K4 hold a cluster (row table + points in LDS beside a three-slot ring of one column block each) in every layout?  Asked at
+// TRAINING time: a cluster that could be factorised but never evaluated is refused there (GPIS_ERR_LIMIT, the previous model is kept).
 bool ongpis_eval_fits(int N, int ld) {
     const int W = kClassW[ongpis_class_of_nbx(ld / 32)];
-    return eval_lds_fixed(W, N, ld) + kSlots * sizeof(float) * kTileFloats <= (size_t)158 * 1024;
+    return eval_lds_fixed(W, N, ld, kMaxNXQ) + kSlots * sizeof(float) * kTileFloats <= (size_t)158 * 1024;
 }
 
 }  // namespace gpis

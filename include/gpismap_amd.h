@@ -123,6 +123,10 @@ int   gpis3_get_nodes(void* map, float* out9, int cap);         /* pos3 grad3 va
  * CUs the training streams leave free, host replays of the last update() over all devices of the map (1: the host logic ran
  * once, on the lead device, however many devices train), factor records received in the last model exchange (inverses deferred) */
 int   gpis3_stats(void* map, double* out, int n);
+/* K4 jobs of the last test() per evaluation pass: [0] pass 1 (nearest candidate, all columns), [1] pass 2 of two-candidate
+ * queries (candidate 2, all columns), [2] pass 2a (value column of candidates 2 and 3), [3] pass 2b (gradient columns of the
+ * candidates the blend reads) */
+int   gpis3_pass_jobs(void* map, long long* out4);
 /* Map checkpoint (optional; the reference keeps its map only in the mex singleton): gpis3_save writes the spatial
  * index, the surface points with their data and every trained model as its packed prediction record (about 2 K^2 bytes per
  * cluster: the file of a 500-cluster map is ~1.2 GB) (GPisMap3::saveMap); gpis3_load replaces the map's state with a file's.
@@ -176,6 +180,7 @@ int   gpis2_sync(void* map);
 int   gpis2_set_pipeline(void* map, int on);
 int   gpis2_get_nodes(void* map, float* out7, int cap);         /* pos2 grad2 val sigx sigg, tree order */
 int   gpis2_stats(void* map, double* out, int n);               /* same slots as gpis3_stats */
+int   gpis2_pass_jobs(void* map, long long* out4);              /* same slots as gpis3_pass_jobs */
 
 /* ---- kernel level: observation GP (K1, K2) -------------------------------- */
 void* gpis_obsgp_create(void);
@@ -206,6 +211,10 @@ int   gpis_ongpis_get_model(void* s, int model, float* L_ldxld, float* alpha_K, 
  * xq: nq*dim interleaved; out: njobs*8 = mean(4) var(4) (2-D uses 3+3, slots 3 and 7 unused) */
 int   gpis_ongpis_eval(void* s, const float* xq, int nq, const int* job_q, const int* job_model, int njobs,
                        float* out8);
+/* the same for a subset of the result columns: layout 0 = all (= gpis_ongpis_eval), 1 = component 0 (mean f, value variance),
+ * 2 = components 1..dim (gradient and its variances); the slots of the other components are 0 */
+int   gpis_ongpis_eval_layout(void* s, const float* xq, int nq, const int* job_q, const int* job_model, int njobs, int layout,
+                              float* out8);
 /* Rounds 2-4: K4 kept one double-precision exp per (training point, query) in an LDS table when it fit.  The kernel since round 5
  * (B chunks in a three-slot ring) spends that LDS on wider chunks and evaluates the exponential per entry for every cluster:
  * gpis_ongpis_set_exp_table is accepted for compatibility and changes nothing (results were identical either way). */
