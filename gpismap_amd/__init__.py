@@ -184,6 +184,9 @@ def lib():
         L.gpis2_track_scan.argtypes = [vp, vp, fp, fp, C.c_int, fp, C.POINTER(gpis_track_opts), fp, vp]
         L.gpis_track_get.argtypes = [vp, dp, dp, fp]
         L.gpis_track_info.argtypes = [vp, dp, C.c_int]
+    if hasattr(L, "gpis3_track_depth_field"):
+        L.gpis3_track_depth_field.argtypes = [vp, vp, vp, C.POINTER(gpis_cam), fp, fp, C.POINTER(gpis_track_opts), fp, vp]
+        L.gpis2_track_scan_field.argtypes = [vp, vp, vp, fp, fp, C.c_int, fp, fp, C.POINTER(gpis_track_opts), fp, vp]
     _lib = L
     return L
 
@@ -498,6 +501,12 @@ class GPisMap3:
             self._tracker = Tracker()
         return self._tracker
 
+    def track_depth_field(self, field, depth, pose0, cam6=None, tracker=None, **opts):
+        """track_depth against a DistanceField instead of the map (gpis3_track_depth_field): r = the sampled distance, one
+        fused kernel per pass.  cam6 None = this map's camera; nothing else of the map is read.  level and max_var are not
+        read (the field's level is zero; its gate was applied when it was built).  Returns (pose, info) as track_depth."""
+        return field._track_depth(self.h, self._wh, depth, pose0, cam6, tracker, opts)
+
 
 class GPisMap:
     """Mirror of the reference's mexGPisMap command set ('update', 'test', 'reset') on the HIP path."""
@@ -623,6 +632,11 @@ class GPisMap:
         _check(self.L.gpis2_track_scan(self.h, tracker.h, _p(thetas), _p(ranges), thetas.size, _p(pose0), C.byref(o), _p(out),
                                        None), "gpis2_track_scan")
         return out, tracker.result()
+
+    def track_scan_field(self, field, thetas, ranges, pose0, tracker=None, **opts):
+        """track_scan against a DistanceField instead of the map (gpis2_track_scan_field), with this map's sensor offset;
+        opts and the result as GPisMap3.track_depth_field."""
+        return field._track_scan(self.h, thetas, ranges, pose0, None, tracker, opts)
 
 
 def _filter_var(verts, prims, rec, slot, max_var):
@@ -816,6 +830,57 @@ class DistanceField:
         """The HIP device the buffers live on (the one current at creation; a map-level call moves them to the map's lead
         device)."""
         return self._device
+
+    def track_depth(self, depth, pose0, cam6, tracker=None, **opts):
+        """The camera pose from which this field explains `depth` best (gpis3_track_depth_field without a map): track_depth's
+        Gauss-Newton with r = the sampled distance, one fused kernel per pass.  cam6: (fx, fy, cx, cy, width, height).  level
+        and max_var are not read.  Returns (pose [12] f32, info) as GPisMap3.track_depth."""
+        return self._track_depth(None, None, depth, pose0, cam6, tracker, opts)
+
+    def track_scan(self, thetas, ranges, pose0, off2, tracker=None, **opts):
+        """The laser pose from which this field explains the scan best (gpis2_track_scan_field without a map); off2: the
+        sensor offset (x, y) in the laser frame.  Returns (pose [6] f32, info) as GPisMap.track_scan."""
+        return self._track_scan(None, thetas, ranges, pose0, off2, tracker, opts)
+
+    def _own_tracker(self):
+        if getattr(self, "_tracker", None) is None:
+            self._tracker = Tracker()
+        return self._tracker
+
+    def _track_depth(self, map_h, map_wh, depth, pose0, cam6, tracker, opts):
+        depth = np.ascontiguousarray(depth, dtype=np.float32).ravel()
+        pose0 = np.ascontiguousarray(pose0, dtype=np.float32).ravel()
+        if pose0.size != 12:
+            raise GpisError("pose must have 12 elements")
+        if cam6 is None and map_h is None:
+            raise GpisError("a field-only track_depth needs cam6")
+        w, h = (int(cam6[4]), int(cam6[5])) if cam6 is not None else map_wh
+        if depth.size != w * h:
+            raise GpisError("depth must have width * height = %d elements" % (w * h))
+        t = tracker if tracker is not None else self._own_tracker()
+        o = track_opts(3, **opts)
+        cam = C.byref(_cam(cam6)) if cam6 is not None else None
+        out = np.zeros(12, dtype=np.float32)
+        _check(self.L.gpis3_track_depth_field(map_h, self.h, t.h, cam, _p(depth), _p(pose0), C.byref(o), _p(out), None),
+               "gpis3_track_depth_field")
+        return out, t.result()
+
+    def _track_scan(self, map_h, thetas, ranges, pose0, off2, tracker, opts):
+        thetas = np.ascontiguousarray(thetas, dtype=np.float32).ravel()
+        ranges = np.ascontiguousarray(ranges, dtype=np.float32).ravel()
+        pose0 = np.ascontiguousarray(pose0, dtype=np.float32).ravel()
+        if pose0.size != 6 or thetas.size != ranges.size:
+            raise GpisError("bad 2-D track arguments")
+        off = np.ascontiguousarray(off2, dtype=np.float32).ravel() if off2 is not None else None
+        if off is not None and off.size != 2:
+            raise GpisError("off2 must have 2 elements")
+        t = tracker if tracker is not None else self._own_tracker()
+        o = track_opts(2, **opts)
+        out = np.zeros(6, dtype=np.float32)
+        _check(self.L.gpis2_track_scan_field(map_h, self.h, t.h, _p(thetas), _p(ranges), thetas.size,
+                                             _p(off) if off is not None else None, _p(pose0), C.byref(o), _p(out), None),
+               "gpis2_track_scan_field")
+        return out, t.result()
 
 
 def render_opts(dim, **opts):

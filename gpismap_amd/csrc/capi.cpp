@@ -61,6 +61,8 @@ int gpis3_impl_track(GPisMap3* g, Tracker& t, const float* cam4, const int* wh, 
                      float* pose12_out, void* stream);
 int gpis2_impl_track(GPisMap* g, Tracker& t, const float* thetas, const float* ranges, int n, const float* pose6, TrackOpts o,
                      float* pose6_out, void* stream);
+void gpis3_impl_camera(GPisMap3* g, float* cam4, int* wh);
+void gpis2_impl_sensor_offset(GPisMap* g, float* off2);
 
 namespace gpis { int selftest_ranged_arith(unsigned long long seed, int blocks, int per_thread, int mode, unsigned long long* mismatches); }
 extern "C" {
@@ -722,14 +724,15 @@ int gpis_track_set_chunk(void* tracker, int points) {
     ((Tracker*)tracker)->chunk = points ? points : (1 << 22);
     return GPIS_OK;
 }
-// the checks that need no map: an argument error leaves the previous result readable
-static int track_args(void* tracker, int dim, const float* pose, const gpis_track_opts* opts, TrackOpts* o) {
+// the checks that need no map: an argument error leaves the previous result readable.  field: level and max_var are not read.
+static int track_args(void* tracker, int dim, const float* pose, const gpis_track_opts* opts, TrackOpts* o, bool field = false) {
     if (!tracker || !pose) return GPIS_ERR_ARG;
     gpis_track_opts d;
     if (!opts) { (void)gpis_track_default_opts(dim, &d); opts = &d; }
     *o = track_opts(opts);
     const int np = dim == 3 ? 12 : 6;
     for (int k = 0; k < np; ++k) if (!std::isfinite(pose[k])) return GPIS_ERR_ARG;
+    if (field) { o->level = 0.f; o->max_var = INFINITY; }
     if (std::isinf(o->level)) return GPIS_ERR_ARG;
     TrackOpts c = *o;
     c.level = 0.f;                              // (resolved against the map by the entry)
@@ -764,6 +767,57 @@ int gpis2_track_scan(void* m, void* tracker, const float* thetas, const float* r
     const int rc = gpis2_impl_track((GPisMap*)m, t, thetas, ranges, n, pose6_init, o, pose6_out, stream);
     if (rc != GPIS_OK && rc != GPIS_ERR_ARG && rc != GPIS_ERR_LIMIT) t.clear_result();
     return rc;
+}
+// the field's state and dim (before anything is dropped), then the call on the field's device
+static int track_field_call(void* d, Tracker& t, const TrackGeom& g, const float* in, const double* cs, long long n,
+                            const float* pose_init, int np, const TrackOpts& o, float* pose_out, void* stream) {
+    const DistanceField& df = *(const DistanceField*)d;
+    if (!df.valid) return GPIS_ERR_STATE;
+    if (df.dim != g.dim) return GPIS_ERR_ARG;
+    DeviceScope ds(df.device);
+    try {
+        if (int rc = t.bind(df.device)) { t.clear_result(); return rc; }
+        double p0[12];
+        for (int k = 0; k < np; ++k) p0[k] = pose_init[k];
+        const int rc = t.track_field(df, g, in, cs, n, p0, o, stream ? (hipStream_t)stream : df.own);
+        if (rc != GPIS_OK) { t.clear_result(); return rc; }
+        if (pose_out) for (int k = 0; k < np; ++k) pose_out[k] = (float)t.pose[k];
+        return GPIS_OK;
+    } catch (...) { t.clear_result(); return GPIS_ERR_STATE; }
+}
+int gpis3_track_depth_field(void* m, void* df, void* tracker, const gpis_cam* cam, const float* depth, const float* pose12_init,
+                            const gpis_track_opts* opts, float* pose12_out, void* stream) {
+    if (!df || !depth || (!cam && !m)) return GPIS_ERR_ARG;
+    TrackOpts o;
+    if (int rc = track_args(tracker, 3, pose12_init, opts, &o, true)) return rc;
+    float c4[4];
+    int wh[2];
+    if (cam) { c4[0] = cam->fx; c4[1] = cam->fy; c4[2] = cam->cx; c4[3] = cam->cy; wh[0] = cam->width; wh[1] = cam->height; }
+    else gpis3_impl_camera((GPisMap3*)m, c4, wh);
+    TrackGeom g{};
+    g.dim = 3; g.fx = c4[0]; g.fy = c4[1]; g.cx = c4[2]; g.cy = c4[3]; g.width = wh[0]; g.height = wh[1];
+    const long long n = (long long)wh[0] * wh[1];
+    if (int rc = track_check_geom(g, n)) return rc;
+    return track_field_call(df, *(Tracker*)tracker, g, depth, nullptr, n, pose12_init, 12, o, pose12_out, stream);
+}
+int gpis2_track_scan_field(void* m, void* df, void* tracker, const float* thetas, const float* ranges, int n, const float* off2,
+                           const float* pose6_init, const gpis_track_opts* opts, float* pose6_out, void* stream) {
+    if (!df || !thetas || !ranges || n < 1 || (!off2 && !m)) return GPIS_ERR_ARG;
+    TrackOpts o;
+    if (int rc = track_args(tracker, 2, pose6_init, opts, &o, true)) return rc;
+    for (int k = 0; k < n; ++k) if (!std::isfinite(thetas[k])) return GPIS_ERR_ARG;
+    TrackGeom g{};
+    g.dim = 2;
+    if (off2) { g.off[0] = off2[0]; g.off[1] = off2[1]; }
+    else gpis2_impl_sensor_offset((GPisMap*)m, g.off);
+    if (int rc = track_check_geom(g, n)) return rc;
+    std::vector<double> cs;
+    try { cs.resize((size_t)2 * n); } catch (...) { ((Tracker*)tracker)->clear_result(); return GPIS_ERR_STATE; }
+    for (int k = 0; k < n; ++k) {
+        cs[2 * (size_t)k] = std::cos((double)thetas[k]);
+        cs[2 * (size_t)k + 1] = std::sin((double)thetas[k]);
+    }
+    return track_field_call(df, *(Tracker*)tracker, g, ranges, cs.data(), n, pose6_init, 6, o, pose6_out, stream);
 }
 int gpis_track_get(void* tracker, double* H, double* b, float* resid) {
     if (!tracker) return GPIS_ERR_ARG;

@@ -6,6 +6,7 @@
 #pragma once
 #include <cstdint>
 #include "dev_common.h"
+#include "dfield_sample.h"
 
 namespace gpis {
 
@@ -52,6 +53,7 @@ struct DistanceField {
     int sample(const float* d_x, long long m, float* d_out, hipStream_t s);
 
     const int* d_site() const { return valid ? d_feat[site_buf] : nullptr; }
+    DfLattice lattice() const { return DfLattice{dim, n[0], n[1], n[2], origin[0], origin[1], origin[2], step}; }
 
 private:
     int ensure(long long n);

@@ -13,6 +13,7 @@
 #include <algorithm>
 #include <cmath>
 #include "dfield.h"
+#include "dfield_sample.h"
 #include "map_query.h"
 #include "mesh.h"
 
@@ -161,47 +162,13 @@ __global__ void __launch_bounds__(kBlock) df_output_kernel(const float* __restri
     }
 }
 
-__device__ __forceinline__ float lerp(float a, float b, float w) { return a + w * (b - a); }
-
-// out[q][0] = trilinear / bilinear interpolant, out[q][1 + a] = its derivative along axis a (DESIGN §7e's operation order)
-__global__ void __launch_bounds__(kBlock) df_sample_kernel(const float* __restrict__ F, int dim, int nx, int ny, int nz, float ox, float oy,
-                                                           float oz, float st, const float* __restrict__ x, long long m,
+// out[q][0] = trilinear / bilinear interpolant, out[q][1 + a] = its derivative along axis a (df_sample_at)
+__global__ void __launch_bounds__(kBlock) df_sample_kernel(const float* __restrict__ F, DfLattice L, const float* __restrict__ x, long long m,
                                                            float* __restrict__ out) {
-    const long long nxy = (long long)nx * ny;
+    const int dim = L.dim;
     for (long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x; q < m; q += (long long)gridDim.x * blockDim.x) {
         const float* xq = x + (size_t)q * dim;
-        float* o = out + (size_t)q * (1 + dim);
-        const float ux = (xq[0] - ox) / st, uy = (xq[1] - oy) / st, uz = dim == 3 ? (xq[2] - oz) / st : 0.f;
-        const bool in = (ux >= 0.f && ux <= (float)(nx - 1)) && (uy >= 0.f && uy <= (float)(ny - 1)) &&
-                        (dim == 2 || (uz >= 0.f && uz <= (float)(nz - 1)));
-        if (!in) {
-            for (int a = 0; a <= dim; ++a) o[a] = __int_as_float(0x7fc00000);
-            continue;
-        }
-        const int i0 = min((int)floorf(ux), nx - 2), j0 = min((int)floorf(uy), ny - 2);
-        const float wx = ux - (float)i0, wy = uy - (float)j0;
-        const long long b = (long long)j0 * nx + i0;
-        if (dim == 2) {
-            const float c00 = F[b], c10 = F[b + 1], c01 = F[b + nx], c11 = F[b + nx + 1];
-            const float e0 = lerp(c00, c10, wx), e1 = lerp(c01, c11, wx);
-            o[0] = lerp(e0, e1, wy);
-            o[1] = lerp(c10 - c00, c11 - c01, wy) / st;
-            o[2] = (e1 - e0) / st;
-            continue;
-        }
-        const int k0 = min((int)floorf(uz), nz - 2);
-        const float wz = uz - (float)k0;
-        const long long b0 = b + k0 * nxy, b1 = b0 + nxy;
-        const float c000 = F[b0], c100 = F[b0 + 1], c010 = F[b0 + nx], c110 = F[b0 + nx + 1];
-        const float c001 = F[b1], c101 = F[b1 + 1], c011 = F[b1 + nx], c111 = F[b1 + nx + 1];
-        // e_{dy dz}: x lerps; f_{dz}: y lerps
-        const float e00 = lerp(c000, c100, wx), e10 = lerp(c010, c110, wx), e01 = lerp(c001, c101, wx), e11 = lerp(c011, c111, wx);
-        const float f0 = lerp(e00, e10, wy), f1 = lerp(e01, e11, wy);
-        o[0] = lerp(f0, f1, wz);
-        const float hy0 = lerp(c100 - c000, c110 - c010, wy), hy1 = lerp(c101 - c001, c111 - c011, wy);
-        o[1] = lerp(hy0, hy1, wz) / st;
-        o[2] = lerp(e10 - e00, e11 - e01, wz) / st;
-        o[3] = (f1 - f0) / st;
+        df_sample_at(F, L, xq[0], xq[1], dim == 3 ? xq[2] : 0.f, out + (size_t)q * (1 + dim));
     }
 }
 
@@ -306,8 +273,7 @@ int DistanceField::from_map(MapQuery& mq, OnGPISStore& store, int dm, const int*
 int DistanceField::sample(const float* d_xs, long long m, float* d_out, hipStream_t s) {
     if (!valid) return GPIS_ERR_STATE;
     if (m <= 0) return GPIS_OK;
-    hipLaunchKernelGGL(df_sample_kernel, dim3(grid_for(m)), dim3(kBlock), 0, s, d_dist, dim, n[0], n[1], n[2], origin[0], origin[1],
-                       origin[2], step, d_xs, m, d_out);
+    hipLaunchKernelGGL(df_sample_kernel, dim3(grid_for(m)), dim3(kBlock), 0, s, d_dist, lattice(), d_xs, m, d_out);
     GPIS_HIP(hipGetLastError());
     GPIS_HIP(hipStreamSynchronize(s));
     return GPIS_OK;

@@ -748,4 +748,8 @@ int gpis2_impl_track(GPisMap* g, Tracker& t, const float* thetas, const float* r
 
 int gpis2_impl_fail(GPisMap* g) { return g->impl()->fail_rc; }
 int gpis2_impl_device(GPisMap* g) { return g->impl()->device; }
+void gpis2_impl_sensor_offset(GPisMap* g, float* off2) {
+    off2[0] = g->impl()->setting.sensor_offset[0];
+    off2[1] = g->impl()->setting.sensor_offset[1];
+}
 int gpis2_impl_update_fail(GPisMap* g) { return g->impl()->upd_rc; }

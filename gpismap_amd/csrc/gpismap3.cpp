@@ -2046,6 +2046,10 @@ int gpis3_impl_track(GPisMap3* g, Tracker& t, const float* cam4, const int* wh, 
 // accessors used by the C-ABI (capi.cpp)
 int gpis3_impl_fail(GPisMap3* g) { return g->impl()->fail_rc; }
 int gpis3_impl_device(GPisMap3* g) { return g->impl()->device; }
+void gpis3_impl_camera(GPisMap3* g, float* cam4, int* wh) {
+    const camParam& c = g->impl()->cam;
+    cam4[0] = c.fx; cam4[1] = c.fy; cam4[2] = c.cx; cam4[3] = c.cy; wh[0] = c.width; wh[1] = c.height;
+}
 int gpis3_impl_num_devices(GPisMap3* g) { return 1 + (int)g->impl()->peers.size(); }
 int gpis3_impl_set_shard(GPisMap3* g, int rank, int world) {
     GPisMap3::Impl& m = *g->impl();

@@ -1,15 +1,19 @@
 // Sensor tracking against the map on the device: damped Gauss-Newton on SE(3) (3-D) / SE(2) (2-D) of a depth
-// image / laser scan against the map's zero level.  One MapQuery pass per iteration over the frame's valid points; the residual
+// image / laser scan against the map's zero level, or against a distance field's (§7f).  One MapQuery pass (a field: one fused
+// kernel) per iteration over the frame's valid points; the residual
 // and Jacobian terms are reduced to the normal equations on the device by a fixed two-stage halving tree (no atomics), and only
 // the sums (29 / 11 doubles) leave it.  The host solves the 6x6 / 3x3 system and moves the pose.
 #pragma once
+#include <chrono>
 #include <cstdint>
+#include <functional>
 #include "dev_common.h"
 
 namespace gpis {
 
 class MapQuery;
 class OnGPISStore;
+struct DistanceField;
 
 struct TrackOpts {
     double max_residual;   // inlier: |r| <= max_residual
@@ -78,11 +82,22 @@ struct Tracker {
     // have_map false: no tree yet (every record keeps f = NaN: status 2).  Arguments are checked by the caller (track_check_*).
     int track(MapQuery& mq, OnGPISStore& store, bool have_map, const TrackGeom& geo, const float* in, const double* cs, long long n,
               const double* pose0, const TrackOpts& o, hipStream_t s);
+    // The same call against a distance field: r = the sampled distance, one fused kernel per pass; o.level and
+    // o.max_var are not read; evals and k4_ms stay 0.  The field must live on this tracker's device.  A field without a result:
+    // GPIS_ERR_STATE, one of another dim: GPIS_ERR_ARG, both before the previous result is dropped.
+    int track_field(const DistanceField& df, const TrackGeom& geo, const float* in, const double* cs, long long n,
+                    const double* pose0, const TrackOpts& o, hipStream_t s);
 
 private:
+    using PassFn = std::function<int(const double* pose, double* sums)>;
     int ensure(long long npix, long long ngrid, int dm);
+    int setup(const TrackGeom& geo, const float* in, const double* cs, long long n, const TrackOpts& o, hipStream_t s);
+    int iterate(int dm, const double* pose0, const TrackOpts& o, const PassFn& pass_at, double* cur, double* S, int& st, int& it);
+    void finish(int dm, long long n, const double* cur, const double* S, int st, int it);
     int pass(MapQuery& mq, OnGPISStore& store, bool have_map, const TrackGeom& geo, const double* pose, const TrackOpts& o,
              hipStream_t s, double* sums);
+    int field_pass(const DistanceField& df, int dm, const double* pose, const TrackOpts& o, hipStream_t s, double* sums);
+    int pass_sums(int dm, long long np, hipStream_t s, double* sums, std::chrono::steady_clock::time_point t0);
 };
 
 // Argument checks shared by the C-ABI entries: GPIS_OK, GPIS_ERR_ARG, or GPIS_ERR_LIMIT (more than kMaxPoints pixels / beams).

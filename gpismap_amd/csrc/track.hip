@@ -13,6 +13,7 @@
 #include <chrono>
 #include <cmath>
 #include <cstring>
+#include "dfield.h"
 #include "map_query.h"
 #include "render.h"
 #include "track.h"
@@ -76,35 +77,108 @@ __global__ void __launch_bounds__(kBlock) track_gather_kernel(TrackGeom g, int s
     }
 }
 
+// the world point of a local point: R local + t left to right in float (no FMA: -ffp-contract=off)
+template <int D>
+__device__ __forceinline__ void world_point(const PassPose& P, const float4 l, float* __restrict__ x) {
+    if constexpr (D == 3) {
+        x[0] = P.R[0] * l.x + P.R[3] * l.y + P.R[6] * l.z + P.t[0];
+        x[1] = P.R[1] * l.x + P.R[4] * l.y + P.R[7] * l.z + P.t[1];
+        x[2] = P.R[2] * l.x + P.R[5] * l.y + P.R[8] * l.z + P.t[2];
+    } else {
+        x[0] = P.R[0] * l.x + P.R[2] * l.y + P.t[0];
+        x[1] = P.R[1] * l.x + P.R[3] * l.y + P.t[1];
+    }
+}
+
 // world points of the pass and their pre-filled records (f = NaN, zeros elsewhere)
 __global__ void __launch_bounds__(kBlock) track_transform_kernel(int dim, PassPose P, const float4* __restrict__ loc, int m,
                                                                  float* __restrict__ x, float* __restrict__ rec) {
     const int nc = 2 * (1 + dim);
     for (int j = blockIdx.x * blockDim.x + threadIdx.x; j < m; j += gridDim.x * blockDim.x) {
         const float4 l = loc[j];
-        if (dim == 3) {
-            x[3 * (size_t)j] = P.R[0] * l.x + P.R[3] * l.y + P.R[6] * l.z + P.t[0];
-            x[3 * (size_t)j + 1] = P.R[1] * l.x + P.R[4] * l.y + P.R[7] * l.z + P.t[1];
-            x[3 * (size_t)j + 2] = P.R[2] * l.x + P.R[5] * l.y + P.R[8] * l.z + P.t[2];
-        } else {
-            x[2 * (size_t)j] = P.R[0] * l.x + P.R[2] * l.y + P.t[0];
-            x[2 * (size_t)j + 1] = P.R[1] * l.x + P.R[3] * l.y + P.t[1];
-        }
+        if (dim == 3) world_point<3>(P, l, x + 3 * (size_t)j);
+        else world_point<2>(P, l, x + 2 * (size_t)j);
         rec[(size_t)j * nc] = __int_as_float(0x7fc00000);
         for (int c = 1; c < nc; ++c) rec[(size_t)j * nc + c] = 0.f;
     }
 }
 
-// The terms of every point and their sum per segment of 256 consecutive points (zero-padded): the halving tree
-// a[i] += a[i + s], s = 128 .. 1 -- LDS for s = 128, 64, lane shuffles of wave 0 below.  part[c * P + segment], c < NS:
+template <int D> struct Sums {
+    static constexpr int NJ = D == 3 ? 6 : 3;
+    static constexpr int NS = NJ * (NJ + 1) / 2 + NJ + 2;
+};
+
+// the terms of one inlier into a[]: r, its gradient g and its world point x in float; J = [g ; (x - t) x g] (2-D
+// [gx, gy, (x - tx) gy - (y - ty) gx]) in double; the upper triangle of w J J^T row by row, w J r, w r^2, 1
+template <int D>
+__device__ __forceinline__ void point_terms(const PassPose& P, float r, const float* __restrict__ g, const float* __restrict__ x,
+                                            double huber, double* __restrict__ a) {
+    constexpr int NJ = Sums<D>::NJ, NS = Sums<D>::NS;
+    const double rr = (double)r, ar = fabs(rr);
+    const double w = ar <= huber ? 1.0 : huber / ar;
+    double J[NJ];
+    if constexpr (D == 3) {
+        const double g0 = g[0], g1 = g[1], g2 = g[2];
+        const double d0 = (double)x[0] - (double)P.t[0];
+        const double d1 = (double)x[1] - (double)P.t[1];
+        const double d2 = (double)x[2] - (double)P.t[2];
+        J[0] = g0; J[1] = g1; J[2] = g2;
+        J[3] = d1 * g2 - d2 * g1;
+        J[4] = d2 * g0 - d0 * g2;
+        J[5] = d0 * g1 - d1 * g0;
+    } else {
+        const double g0 = g[0], g1 = g[1];
+        const double d0 = (double)x[0] - (double)P.t[0];
+        const double d1 = (double)x[1] - (double)P.t[1];
+        J[0] = g0; J[1] = g1;
+        J[2] = d0 * g1 - d1 * g0;
+    }
+    int c = 0;
+#pragma unroll
+    for (int i = 0; i < NJ; ++i) {
+        const double wj = w * J[i];
+#pragma unroll
+        for (int k = i; k < NJ; ++k) a[c++] = wj * J[k];
+    }
+#pragma unroll
+    for (int i = 0; i < NJ; ++i) a[NJ * (NJ + 1) / 2 + i] = (w * J[i]) * rr;
+    a[NS - 2] = (w * rr) * rr;
+    a[NS - 1] = 1.0;
+}
+
+// the halving tree a[i] += a[i + s], s = 128 .. 1 over the block's 256 threads -- LDS for s = 128, 64, lane shuffles of wave 0
+// below -- into part[c * P + seg]
+template <int NS>
+__device__ __forceinline__ void segment_reduce(double* __restrict__ a, double (*sh)[kBlock / 2], int tid, int seg, int nseg_pow2,
+                                               double* __restrict__ part) {
+    __syncthreads();                       // (sh of the previous segment is read)
+    if (tid >= kBlock / 2)
+        for (int c = 0; c < NS; ++c) sh[c][tid - kBlock / 2] = a[c];
+    __syncthreads();
+    if (tid < kBlock / 2)
+        for (int c = 0; c < NS; ++c) a[c] = a[c] + sh[c][tid];
+    __syncthreads();
+    if (tid >= kBlock / 4 && tid < kBlock / 2)
+        for (int c = 0; c < NS; ++c) sh[c][tid - kBlock / 4] = a[c];
+    __syncthreads();
+    if (tid < kBlock / 4) {
+#pragma unroll
+        for (int c = 0; c < NS; ++c) {
+            double v = a[c] + sh[c][tid];
+            for (int s = 32; s >= 1; s >>= 1) v = v + __shfl_down(v, s, 64);
+            if (tid == 0) part[(size_t)c * nseg_pow2 + seg] = v;
+        }
+    }
+}
+
+// The terms of every point and their sum per segment of 256 consecutive points (zero-padded): part[c * P + segment], c < NS:
 // the upper triangle of H = sum w J J^T row by row, b = sum w J r, sum w r^2, the inlier count.  Segments nseg .. P - 1 are
 // all padding (+0).  Terms in double from the float values; non-inliers contribute +0.
 template <int D>
 __global__ void __launch_bounds__(kBlock) track_terms_kernel(PassPose P, const float* __restrict__ x, const float* __restrict__ rec, int m,
                                                              int nseg_pow2, float level, double max_residual, double huber,
                                                              double max_var, double* __restrict__ part) {
-    constexpr int NJ = D == 3 ? 6 : 3;
-    constexpr int NS = NJ * (NJ + 1) / 2 + NJ + 2;
+    constexpr int NS = Sums<D>::NS;
     constexpr int NC = 2 * (1 + D);
     __shared__ double sh[NS][kBlock / 2];
     const int tid = threadIdx.x;
@@ -114,57 +188,42 @@ __global__ void __launch_bounds__(kBlock) track_terms_kernel(PassPose P, const f
 #pragma unroll
         for (int c = 0; c < NS; ++c) a[c] = 0.0;
         float r;
-        if (j < m && residual(rec + (size_t)j * NC, D, level, max_residual, max_var, r)) {
-            const float* q = rec + (size_t)j * NC;
-            const double rr = (double)r, ar = fabs(rr);
-            const double w = ar <= huber ? 1.0 : huber / ar;
-            double J[NJ];
-            if constexpr (D == 3) {
-                const double g0 = q[1], g1 = q[2], g2 = q[3];
-                const double d0 = (double)x[3 * (size_t)j] - (double)P.t[0];
-                const double d1 = (double)x[3 * (size_t)j + 1] - (double)P.t[1];
-                const double d2 = (double)x[3 * (size_t)j + 2] - (double)P.t[2];
-                J[0] = g0; J[1] = g1; J[2] = g2;
-                J[3] = d1 * g2 - d2 * g1;
-                J[4] = d2 * g0 - d0 * g2;
-                J[5] = d0 * g1 - d1 * g0;
-            } else {
-                const double g0 = q[1], g1 = q[2];
-                const double d0 = (double)x[2 * (size_t)j] - (double)P.t[0];
-                const double d1 = (double)x[2 * (size_t)j + 1] - (double)P.t[1];
-                J[0] = g0; J[1] = g1;
-                J[2] = d0 * g1 - d1 * g0;
-            }
-            int c = 0;
+        if (j < m && residual(rec + (size_t)j * NC, D, level, max_residual, max_var, r))
+            point_terms<D>(P, r, rec + (size_t)j * NC + 1, x + (size_t)j * D, huber, a);
+        segment_reduce<NS>(a, sh, tid, seg, nseg_pow2, part);
+    }
+}
+
+// The field's residual of a local point at the pass pose: its world point x, the sampled distance and gradient o (df_sample_at);
+// r = o[0] (the field's level is zero: o[0] - 0.0f has the same bits); inlier iff o is finite and |r| <= max_residual (compared
+// in double; no variance test)
+template <int D>
+__device__ __forceinline__ bool field_residual(const PassPose& P, const float4 l, const float* __restrict__ F, const DfLattice& L,
+                                               double max_residual, float* __restrict__ x, float* __restrict__ o) {
+    world_point<D>(P, l, x);
+    df_sample_at(F, L, x[0], x[1], D == 3 ? x[2] : 0.f, o);
+    const bool g_ok = isfinite(o[1]) && isfinite(o[2]) && (D == 2 || isfinite(o[3]));
+    return isfinite(o[0]) && g_ok && fabs((double)o[0]) <= max_residual;
+}
+
+// One pass against a distance field, fused: world point, sample, terms and the segment tree of track_terms_kernel, from the
+// local points (16 B per point); nothing is written per point.  L.dim == D.
+template <int D>
+__global__ void __launch_bounds__(kBlock) track_field_terms_kernel(PassPose P, const float4* __restrict__ loc, int m, int nseg_pow2,
+                                                                   const float* __restrict__ F, DfLattice L, double max_residual,
+                                                                   double huber, double* __restrict__ part) {
+    constexpr int NS = Sums<D>::NS;
+    __shared__ double sh[NS][kBlock / 2];
+    L.dim = D;
+    const int tid = threadIdx.x;
+    for (int seg = blockIdx.x; seg < nseg_pow2; seg += gridDim.x) {
+        const int j = seg * kBlock + tid;
+        double a[NS];
 #pragma unroll
-            for (int i = 0; i < NJ; ++i) {
-                const double wj = w * J[i];
-#pragma unroll
-                for (int k = i; k < NJ; ++k) a[c++] = wj * J[k];
-            }
-#pragma unroll
-            for (int i = 0; i < NJ; ++i) a[NJ * (NJ + 1) / 2 + i] = (w * J[i]) * rr;
-            a[NS - 2] = (w * rr) * rr;
-            a[NS - 1] = 1.0;
-        }
-        __syncthreads();                       // (sh of the previous segment is read)
-        if (tid >= kBlock / 2)
-            for (int c = 0; c < NS; ++c) sh[c][tid - kBlock / 2] = a[c];
-        __syncthreads();
-        if (tid < kBlock / 2)
-            for (int c = 0; c < NS; ++c) a[c] = a[c] + sh[c][tid];
-        __syncthreads();
-        if (tid >= kBlock / 4 && tid < kBlock / 2)
-            for (int c = 0; c < NS; ++c) sh[c][tid - kBlock / 4] = a[c];
-        __syncthreads();
-        if (tid < kBlock / 4) {
-#pragma unroll
-            for (int c = 0; c < NS; ++c) {
-                double v = a[c] + sh[c][tid];
-                for (int s = 32; s >= 1; s >>= 1) v = v + __shfl_down(v, s, 64);
-                if (tid == 0) part[(size_t)c * nseg_pow2 + seg] = v;
-            }
-        }
+        for (int c = 0; c < NS; ++c) a[c] = 0.0;
+        float x[D], o[1 + D];
+        if (j < m && field_residual<D>(P, loc[j], F, L, max_residual, x, o)) point_terms<D>(P, o[0], o + 1, x, huber, a);
+        segment_reduce<NS>(a, sh, tid, seg, nseg_pow2, part);
     }
 }
 
@@ -189,6 +248,19 @@ __global__ void __launch_bounds__(kBlock) track_resid_kernel(int dim, const floa
     for (int j = blockIdx.x * blockDim.x + threadIdx.x; j < m; j += gridDim.x * blockDim.x) {
         float r;
         if (residual(rec + (size_t)j * nc, dim, level, max_residual, max_var, r)) resid[__float_as_int(loc[j].w)] = r;
+    }
+}
+
+// the residual image of the final pass against a field: the points sampled again at that pass's pose
+template <int D>
+__global__ void __launch_bounds__(kBlock) track_field_resid_kernel(PassPose P, const float4* __restrict__ loc, int m,
+                                                                   const float* __restrict__ F, DfLattice L, double max_residual,
+                                                                   float* __restrict__ resid) {
+    L.dim = D;
+    for (int j = blockIdx.x * blockDim.x + threadIdx.x; j < m; j += gridDim.x * blockDim.x) {
+        const float4 l = loc[j];
+        float x[D], o[1 + D];
+        if (field_residual<D>(P, l, F, L, max_residual, x, o)) resid[__float_as_int(l.w)] = o[0];
     }
 }
 
@@ -367,7 +439,7 @@ int Tracker::ensure(long long npix, long long ngrid, int dm) {
 int Tracker::pass(MapQuery& mq, OnGPISStore& store, bool have_map, const TrackGeom& geo, const double* pose, const TrackOpts& o,
                   hipStream_t s, double* sums) {
     const auto t0 = std::chrono::steady_clock::now();
-    const int dm = geo.dim, nc = 2 * (1 + dm), ns = dm == 3 ? kSums3 : kSums2;
+    const int dm = geo.dim, nc = 2 * (1 + dm);
     const long long m = points;
     const PassPose P = pass_pose(dm, pose);
     if (m > 0) {
@@ -391,6 +463,28 @@ int Tracker::pass(MapQuery& mq, OnGPISStore& store, bool have_map, const TrackGe
     else
         hipLaunchKernelGGL(track_terms_kernel<2>, dim3(grid), dim3(kBlock), 0, s, P, d_x, d_rec, (int)m, (int)np, o.level, o.max_residual,
                            o.huber, o.max_var, d_part);
+    return pass_sums(dm, np, s, sums, t0);
+}
+
+// one fused kernel (world point, sample, terms, segment tree), reduction, the sums to the host
+int Tracker::field_pass(const DistanceField& df, int dm, const double* pose, const TrackOpts& o, hipStream_t s, double* sums) {
+    const auto t0 = std::chrono::steady_clock::now();
+    const long long m = points;
+    const PassPose P = pass_pose(dm, pose);
+    const long long np = pow2_at_least((m + kSeg - 1) / kSeg);
+    const int grid = (int)std::min((long long)kGridCap, np);
+    if (dm == 3)
+        hipLaunchKernelGGL(track_field_terms_kernel<3>, dim3(grid), dim3(kBlock), 0, s, P, (const float4*)d_loc, (int)m, (int)np, df.d_dist,
+                           df.lattice(), o.max_residual, o.huber, d_part);
+    else
+        hipLaunchKernelGGL(track_field_terms_kernel<2>, dim3(grid), dim3(kBlock), 0, s, P, (const float4*)d_loc, (int)m, (int)np, df.d_dist,
+                           df.lattice(), o.max_residual, o.huber, d_part);
+    return pass_sums(dm, np, s, sums, t0);
+}
+
+// the top tree over the np segment partials, the one page-locked copy of the sums; counts the pass and its host wall time
+int Tracker::pass_sums(int dm, long long np, hipStream_t s, double* sums, std::chrono::steady_clock::time_point t0) {
+    const int ns = dm == 3 ? kSums3 : kSums2;
     hipLaunchKernelGGL(track_top_kernel, dim3(1), dim3(1024), 0, s, ns, (int)np, d_part, d_sum);
     GPIS_HIP(hipGetLastError());
     GPIS_HIP(hipMemcpyAsync(h_sum, d_sum, sizeof(double) * ns, hipMemcpyDeviceToHost, s));
@@ -401,12 +495,13 @@ int Tracker::pass(MapQuery& mq, OnGPISStore& store, bool have_map, const TrackGe
     return GPIS_OK;
 }
 
-int Tracker::track(MapQuery& mq, OnGPISStore& store, bool have_map, const TrackGeom& geo, const float* in, const double* cs, long long n,
-                   const double* pose0, const TrackOpts& o, hipStream_t s) {
+// the set-up shared by every call: checks, buffers, the input uploaded, the valid samples flagged, compacted and gathered into
+// local points (`points` of them)
+int Tracker::setup(const TrackGeom& geo, const float* in, const double* cs, long long n, const TrackOpts& o, hipStream_t s) {
     clear_result();
     if (int rc = track_check_opts(o)) return rc;
     if (int rc = track_check_geom(geo, n)) return rc;
-    const int dm = geo.dim, nj = dm == 3 ? 6 : 3, nt = dm, np = dm == 3 ? 12 : 6;
+    const int dm = geo.dim;
     const int mh = dm == 3 ? geo.height / o.stride : 0;
     const long long ngrid = dm == 3 ? (long long)(geo.width / o.stride) * mh : n;
     if (int rc = ensure(n, ngrid, dm)) return rc;
@@ -428,16 +523,19 @@ int Tracker::track(MapQuery& mq, OnGPISStore& store, bool have_map, const TrackG
         GPIS_HIP(hipGetLastError());
     }
     points = m;
-    const bool query = have_map && m > 0;
-    if (query)
-        if (int rc = mq.prepare(store, s)) return rc;
+    return GPIS_OK;
+}
 
-    double cur[12], prev[12], S[kSums3] = {}, delta[6];
+// The Gauss-Newton loop from pose0 with `pass_at(pose, sums)` as the pass: cur = the returned pose, S = the sums of the last
+// pass (which ran at cur), st / it the status and the steps taken; sets cost0
+int Tracker::iterate(int dm, const double* pose0, const TrackOpts& o, const PassFn& pass_at, double* cur, double* S, int& st, int& it) {
+    const int nj = dm == 3 ? 6 : 3, nt = dm, np = dm == 3 ? 12 : 6;
+    double prev[12], delta[6];
     for (int k = 0; k < np; ++k) cur[k] = pose0[k];
     const int nh = nj * (nj + 1) / 2;
-    if (int rc = pass(mq, store, query, geo, cur, o, s, S)) return rc;
+    if (int rc = pass_at(cur, S)) return rc;
     cost0 = S[nh + nj];
-    int st = 1, it = 0;
+    st = 1; it = 0;
     bool again = false;                      // one more pass at the returned pose
     for (;;) {
         if (S[nh + nj + 1] < (double)o.min_inliers) {
@@ -457,17 +555,16 @@ int Tracker::track(MapQuery& mq, OnGPISStore& store, bool have_map, const TrackG
         for (int k = 0; k < nt; ++k) nv = nv + delta[k] * delta[k];
         for (int k = nt; k < nj; ++k) nw = nw + delta[k] * delta[k];
         if (std::sqrt(nv) < o.eps_t && std::sqrt(nw) < o.eps_r) { st = 0; again = true; break; }
-        if (int rc = pass(mq, store, query, geo, cur, o, s, S)) return rc;
+        if (int rc = pass_at(cur, S)) return rc;
     }
     if (again)
-        if (int rc = pass(mq, store, query, geo, cur, o, s, S)) return rc;
-    // the residual image of the final pass
-    GPIS_HIP(hipMemsetD32Async((hipDeviceptr_t)d_resid, 0x7fc00000, (size_t)n, s));
-    if (m > 0)
-        hipLaunchKernelGGL(track_resid_kernel, dim3(grid_for(m)), dim3(kBlock), 0, s, dm, (const float4*)d_loc, d_rec, (int)m, o.level,
-                           o.max_residual, o.max_var, d_resid);
-    GPIS_HIP(hipGetLastError());
-    GPIS_HIP(hipStreamSynchronize(s));
+        if (int rc = pass_at(cur, S)) return rc;
+    return GPIS_OK;
+}
+
+// the result of a finished call (the residual image is written)
+void Tracker::finish(int dm, long long n, const double* cur, const double* S, int st, int it) {
+    const int nj = dm == 3 ? 6 : 3, np = dm == 3 ? 12 : 6, nh = nj * (nj + 1) / 2;
     for (int i = 0, c = 0; i < nj; ++i)
         for (int k = i; k < nj; ++k, ++c) H[i * nj + k] = H[k * nj + i] = S[c];
     for (int i = 0; i < nj; ++i) b[i] = S[nh + i];
@@ -475,6 +572,59 @@ int Tracker::track(MapQuery& mq, OnGPISStore& store, bool have_map, const TrackG
     inliers = S[nh + nj + 1];
     for (int k = 0; k < np; ++k) pose[k] = cur[k];
     status = st; iterations = it; dim = dm; pixels = n; valid = true;
+}
+
+int Tracker::track(MapQuery& mq, OnGPISStore& store, bool have_map, const TrackGeom& geo, const float* in, const double* cs, long long n,
+                   const double* pose0, const TrackOpts& o, hipStream_t s) {
+    if (int rc = setup(geo, in, cs, n, o, s)) return rc;
+    const int dm = geo.dim;
+    const long long m = points;
+    const bool query = have_map && m > 0;
+    if (query)
+        if (int rc = mq.prepare(store, s)) return rc;
+    double cur[12], S[kSums3] = {};
+    int st = 1, it = 0;
+    const PassFn pass_at = [&](const double* p, double* sums) { return pass(mq, store, query, geo, p, o, s, sums); };
+    if (int rc = iterate(dm, pose0, o, pass_at, cur, S, st, it)) return rc;
+    // the residual image of the final pass
+    GPIS_HIP(hipMemsetD32Async((hipDeviceptr_t)d_resid, 0x7fc00000, (size_t)n, s));
+    if (m > 0)
+        hipLaunchKernelGGL(track_resid_kernel, dim3(grid_for(m)), dim3(kBlock), 0, s, dm, (const float4*)d_loc, d_rec, (int)m, o.level,
+                           o.max_residual, o.max_var, d_resid);
+    GPIS_HIP(hipGetLastError());
+    GPIS_HIP(hipStreamSynchronize(s));
+    finish(dm, n, cur, S, st, it);
+    return GPIS_OK;
+}
+
+int Tracker::track_field(const DistanceField& df, const TrackGeom& geo, const float* in, const double* cs, long long n,
+                         const double* pose0, const TrackOpts& o, hipStream_t s) {
+    if (!df.valid) return GPIS_ERR_STATE;
+    if (df.dim != geo.dim) return GPIS_ERR_ARG;
+    TrackOpts of = o;
+    of.level = 0.f;                          // (not read: the field's level is zero by construction)
+    of.max_var = INFINITY;                   // (not read: the field applied its gate when it was built)
+    if (int rc = setup(geo, in, cs, n, of, s)) return rc;
+    const int dm = geo.dim;
+    const long long m = points;
+    double cur[12], S[kSums3] = {};
+    int st = 1, it = 0;
+    const PassFn pass_at = [&](const double* p, double* sums) { return field_pass(df, dm, p, of, s, sums); };
+    if (int rc = iterate(dm, pose0, of, pass_at, cur, S, st, it)) return rc;
+    // the residual image of the final pass: its points sampled again at the returned pose
+    GPIS_HIP(hipMemsetD32Async((hipDeviceptr_t)d_resid, 0x7fc00000, (size_t)n, s));
+    if (m > 0) {
+        const PassPose P = pass_pose(dm, cur);
+        if (dm == 3)
+            hipLaunchKernelGGL(track_field_resid_kernel<3>, dim3(grid_for(m)), dim3(kBlock), 0, s, P, (const float4*)d_loc, (int)m, df.d_dist,
+                               df.lattice(), of.max_residual, d_resid);
+        else
+            hipLaunchKernelGGL(track_field_resid_kernel<2>, dim3(grid_for(m)), dim3(kBlock), 0, s, P, (const float4*)d_loc, (int)m, df.d_dist,
+                               df.lattice(), of.max_residual, d_resid);
+    }
+    GPIS_HIP(hipGetLastError());
+    GPIS_HIP(hipStreamSynchronize(s));
+    finish(dm, n, cur, S, st, it);
     return GPIS_OK;
 }
 

@@ -459,6 +459,29 @@ int   gpis_track_get(void* tracker, double* H, double* b, float* resid);
  * ms inside K4 (only while the map's profiling is on), 1 if a result is held, dim, pixels / beams, K4 evaluations */
 int   gpis_track_info(void* tracker, double* out, int n);
 
+/* ---- tracking against a distance field -----------------------------------------------------------------
+ * gpis3_track_depth / gpis2_track_scan with the map's test() replaced by the field's sampler: the same points, Gauss-Newton
+ * loop, statuses, reduction tree, options and result, with r = d, the sampled distance (gpis_dfield_sample's interpolant and
+ * gradient at the fp32 world point of the pass: the field's level is zero by construction).  A point is an inlier iff d and its
+ * gradient are finite and |(double)r| <= max_residual; there is no variance test (max_var was applied when the field was built)
+ * and level is not read.  A point outside the lattice samples NaN and is no inlier.  Every pass is one fused kernel from the
+ * local points (world point, sample, terms, the segment tree), the top tree and the one copy of 29 / 11 doubles; nothing is
+ * written per point except the residual image, sampled again at the returned pose.  Same bits for every launch, stream, map
+ * update mode and device count that built the same field.
+ * map: may be NULL; it is read only for what the caller leaves NULL: the camera (cam NULL) in 3-D, the sensor offset (off2
+ * NULL) in 2-D.  The map's tree, training and shard state are not used: a field from gpis_dfield_from_grid tracks without a
+ * map.  The tracker moves to the field's device; hip_stream NULL: the field's own stream.  In gpis_track_info, K4
+ * evaluations and ms are 0.
+ * Errors: cam / off2 NULL without a map, a NULL field, depth, thetas or ranges, and gpis3_track_depth's argument errors (level
+ * and max_var excepted) -> GPIS_ERR_ARG; a field of another dim -> GPIS_ERR_ARG; a field without a result -> GPIS_ERR_STATE;
+ * more than 2^26 pixels / beams -> GPIS_ERR_LIMIT: all with the previous result untouched.  Any other failure leaves no result. */
+int   gpis3_track_depth_field(void* map, void* df, void* tracker, const gpis_cam* cam, const float* depth,
+                              const float* pose12_init, const gpis_track_opts* opts, float* pose12_out, void* hip_stream);
+/* off2: the sensor offset (x, y) in the laser frame, NULL = the map's */
+int   gpis2_track_scan_field(void* map, void* df, void* tracker, const float* thetas, const float* ranges, int n,
+                             const float* off2, const float* pose6_init, const gpis_track_opts* opts, float* pose6_out,
+                             void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif
