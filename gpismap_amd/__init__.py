@@ -33,6 +33,11 @@ class gpis_render_opts(C.Structure):
                 ("max_steps", C.c_int)]
 
 
+class gpis_render_field_opts(C.Structure):
+    _fields_ = [("tnear", C.c_float), ("tfar", C.c_float), ("min_step", C.c_float), ("max_step", C.c_float),
+                ("slack", C.c_float), ("refine", C.c_int), ("max_steps", C.c_int)]
+
+
 class gpis_track_opts(C.Structure):
     _fields_ = [("max_residual", C.c_double), ("huber", C.c_double), ("max_var", C.c_double), ("damping", C.c_double),
                 ("eps_t", C.c_double), ("eps_r", C.c_double), ("level", C.c_float), ("stride", C.c_int),
@@ -187,6 +192,12 @@ def lib():
     if hasattr(L, "gpis3_track_depth_field"):
         L.gpis3_track_depth_field.argtypes = [vp, vp, vp, C.POINTER(gpis_cam), fp, fp, C.POINTER(gpis_track_opts), fp, vp]
         L.gpis2_track_scan_field.argtypes = [vp, vp, vp, fp, fp, C.c_int, fp, fp, C.POINTER(gpis_track_opts), fp, vp]
+    if hasattr(L, "gpis3_render_depth_field"):
+        fo = C.POINTER(gpis_render_field_opts)
+        L.gpis_render_field_default_opts.argtypes = [C.c_int, C.c_float, fo]
+        L.gpis_render_set_field_tiles.argtypes = [vp, C.c_int]
+        L.gpis3_render_depth_field.argtypes = [vp, vp, vp, C.POINTER(gpis_cam), fp, fo, vp]
+        L.gpis2_render_scan_field.argtypes = [vp, vp, vp, fp, C.c_int, fp, fp, fo, vp]
     _lib = L
     return L
 
@@ -507,6 +518,12 @@ class GPisMap3:
         read (the field's level is zero; its gate was applied when it was built).  Returns (pose, info) as track_depth."""
         return field._track_depth(self.h, self._wh, depth, pose0, cam6, tracker, opts)
 
+    def render_depth_field(self, field, pose, cam6=None, renderer=None, **opts):
+        """render_depth from a DistanceField instead of the map (gpis3_render_depth_field): sphere tracing through the field's
+        sampler, one fused kernel.  cam6 None = this map's camera; nothing else of the map is read.  Returns (depth [W*H],
+        rec [W*H, 4] = (d, gradient), status) as DistanceField.render_depth; opts: the gpis_render_field_opts fields."""
+        return field._render_depth(self.h, pose, cam6, renderer, opts)
+
 
 class GPisMap:
     """Mirror of the reference's mexGPisMap command set ('update', 'test', 'reset') on the HIP path."""
@@ -637,6 +654,11 @@ class GPisMap:
         """track_scan against a DistanceField instead of the map (gpis2_track_scan_field), with this map's sensor offset;
         opts and the result as GPisMap3.track_depth_field."""
         return field._track_scan(self.h, thetas, ranges, pose0, None, tracker, opts)
+
+    def render_scan_field(self, field, thetas, pose6, renderer=None, **opts):
+        """render_scan from a DistanceField instead of the map (gpis2_render_scan_field), with this map's sensor offset;
+        opts and the result as DistanceField.render_scan."""
+        return field._render_scan(self.h, thetas, pose6, None, renderer, opts)
 
 
 def _filter_var(verts, prims, rec, slot, max_var):
@@ -882,6 +904,73 @@ class DistanceField:
                "gpis2_track_scan_field")
         return out, t.result()
 
+    def render_depth(self, pose, cam6, renderer=None, **opts):
+        """What a depth camera at `pose` would see of this field (gpis3_render_depth_field without a map): every ray sphere-traced
+        through the sampler in one thread of one kernel.  cam6: (fx, fy, cx, cy, width, height).  Returns (depth [W*H] f32,
+        rec [W*H, 4] f32 = (d, gradient) at the reported point, status [W*H] u8) in update()'s column-major layout; no hit:
+        NaN.  Status 0 hit, 1 left the interval, 2 step limit.  opts: the gpis_render_field_opts fields (tnear, tfar, min_step,
+        max_step, slack, refine, max_steps; defaults for this field's step).  A step clamped up to min_step (default half a
+        cell) can pass through anything thinner.  renderer: a Renderer to hold the device result (default: one kept by this
+        field)."""
+        return self._render_depth(None, pose, cam6, renderer, opts)
+
+    def render_scan(self, thetas, pose6, off2, renderer=None, **opts):
+        """What a laser at `pose6` would see of this field along the beams `thetas` (gpis2_render_scan_field without a map);
+        off2: the sensor offset (x, y) in the laser frame.  Returns (range [n], rec [n, 3], status [n])."""
+        return self._render_scan(None, thetas, pose6, off2, renderer, opts)
+
+    def _own_renderer(self):
+        if getattr(self, "_renderer", None) is None:
+            self._renderer = Renderer()
+        return self._renderer
+
+    def _step(self):
+        inf = self.info()
+        if inf["dim"] == 0:
+            raise GpisError("distance field holds no result")
+        return inf["step"]
+
+    def _render_depth(self, map_h, pose, cam6, renderer, opts):
+        pose = np.ascontiguousarray(pose, dtype=np.float32).ravel()
+        if pose.size != 12:
+            raise GpisError("pose must have 12 elements")
+        if cam6 is None and map_h is None:
+            raise GpisError("a field-only render_depth needs cam6")
+        r = renderer if renderer is not None else self._own_renderer()
+        o = render_field_opts(3, self._step(), **opts)
+        cam = C.byref(_cam(cam6)) if cam6 is not None else None
+        _check(self.L.gpis3_render_depth_field(map_h, self.h, r.h, cam, _p(pose), C.byref(o), None), "gpis3_render_depth_field")
+        return r.get()
+
+    def _render_scan(self, map_h, thetas, pose6, off2, renderer, opts):
+        thetas = np.ascontiguousarray(thetas, dtype=np.float32).ravel()
+        pose6 = np.ascontiguousarray(pose6, dtype=np.float32).ravel()
+        if pose6.size != 6:
+            raise GpisError("pose6 must have 6 elements")
+        off = np.ascontiguousarray(off2, dtype=np.float32).ravel() if off2 is not None else None
+        if off is not None and off.size != 2:
+            raise GpisError("off2 must have 2 elements")
+        if off is None and map_h is None:
+            raise GpisError("a field-only render_scan needs off2")
+        r = renderer if renderer is not None else self._own_renderer()
+        o = render_field_opts(2, self._step(), **opts)
+        _check(self.L.gpis2_render_scan_field(map_h, self.h, r.h, _p(thetas), thetas.size, _p(off) if off is not None else None,
+                                              _p(pose6), C.byref(o), None), "gpis2_render_scan_field")
+        return r.get()
+
+
+def render_field_opts(dim, step, **opts):
+    """gpis_render_field_opts of the library's defaults for `dim` and a field of lattice step `step`
+    (gpis_render_field_default_opts) with the given fields replaced."""
+    o = gpis_render_field_opts()
+    _check(lib().gpis_render_field_default_opts(int(dim), float(step), C.byref(o)), "gpis_render_field_default_opts")
+    names = {f[0] for f in gpis_render_field_opts._fields_}
+    for k, v in opts.items():
+        if k not in names:
+            raise GpisError("unknown field render option %r" % k)
+        setattr(o, k, v)
+    return o
+
 
 def render_opts(dim, **opts):
     """gpis_render_opts of the library's defaults for `dim` (gpis_render_default_opts) with the given fields replaced."""
@@ -899,7 +988,7 @@ class Renderer:
     """Result holder of the renderer (gpis_render_*): device buffers reused across calls."""
 
     INFO_KEYS = ("rays", "dim", "passes", "march_passes", "samples", "evals", "k4_ms", "hits",
-                 "box_lo_x", "box_lo_y", "box_lo_z", "box_hi_x", "box_hi_y", "box_hi_z", "valid", "mq_ms")
+                 "box_lo_x", "box_lo_y", "box_lo_z", "box_hi_x", "box_hi_y", "box_hi_z", "valid", "mq_ms", "field", "max_samples")
 
     def __init__(self):
         self.L = lib()
@@ -931,12 +1020,18 @@ class Renderer:
         return (np.array([i["box_lo_x"], i["box_lo_y"], i["box_lo_z"]], np.float32),
                 np.array([i["box_hi_x"], i["box_hi_y"], i["box_hi_z"]], np.float32))
 
+    def set_field_tiles(self, on):
+        """Thread-to-pixel mapping of the 3-D field kernel: 8 x 8 pixel tiles per wavefront (default) or consecutive rays; the
+        results do not depend on it."""
+        _check(self.L.gpis_render_set_field_tiles(self.h, int(bool(on))), "gpis_render_set_field_tiles")
+
     def get(self):
-        """(depth [n], rec [n, 2(1+dim)], status [n] u8): host copies of the last result."""
+        """(depth [n], rec [n, 2(1+dim)] after a map render / [n, 1+dim] after a field render, status [n] u8): host copies of
+        the last result."""
         i = self.info()
         n, d = int(i["rays"]), int(i["dim"])
         depth = np.zeros(n, dtype=np.float32)
-        rec = np.zeros((n, 2 * (1 + d)), dtype=np.float32)
+        rec = np.zeros((n, (1 + d) if i["field"] else 2 * (1 + d)), dtype=np.float32)
         status = np.zeros(n, dtype=np.uint8)
         _check(self.L.gpis_render_get(self.h, _p(depth), _p(rec), _p(status, C.c_ubyte)), "gpis_render_get")
         return depth, rec, status

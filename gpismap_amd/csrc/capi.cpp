@@ -671,7 +671,7 @@ int gpis_render_get(void* render, float* depth, float* rec, unsigned char* statu
     Renderer& r = *(Renderer*)render;
     if (!r.valid) return GPIS_ERR_STATE;
     DeviceScope ds(r.device);
-    const size_t n = (size_t)r.nrays, nc = 2 * (1 + (size_t)r.dim);
+    const size_t n = (size_t)r.nrays, nc = (size_t)r.rec_width();
     if (depth) GPIS_HIP(hipMemcpyAsync(depth, r.d_depth, sizeof(float) * n, hipMemcpyDeviceToHost, r.own));
     if (rec) GPIS_HIP(hipMemcpyAsync(rec, r.d_rec, sizeof(float) * nc * n, hipMemcpyDeviceToHost, r.own));
     if (status) GPIS_HIP(hipMemcpyAsync(status, r.d_status, n, hipMemcpyDeviceToHost, r.own));
@@ -689,11 +689,83 @@ int gpis_render_device(void* render, const float** d_depth, const float** d_rec,
 int gpis_render_info(void* render, double* out, int n) {
     if (!render || !out || n < 0) return GPIS_ERR_ARG;
     const Renderer& r = *(Renderer*)render;
-    const double v[16] = {(double)r.nrays, (double)r.dim, (double)r.passes, (double)r.march_passes, (double)r.samples,
+    const double v[18] = {(double)r.nrays, (double)r.dim, (double)r.passes, (double)r.march_passes, (double)r.samples,
                           (double)r.evals, r.k4_ms, (double)r.hits, (double)r.box_lo[0], (double)r.box_lo[1], (double)r.box_lo[2],
-                          (double)r.box_hi[0], (double)r.box_hi[1], (double)r.box_hi[2], r.valid ? 1.0 : 0.0, r.mq_ms};
-    for (int i = 0; i < n && i < 16; ++i) out[i] = v[i];
+                          (double)r.box_hi[0], (double)r.box_hi[1], (double)r.box_hi[2], r.valid ? 1.0 : 0.0, r.mq_ms,
+                          r.field ? 1.0 : 0.0, (double)r.max_samples};
+    for (int i = 0; i < n && i < 18; ++i) out[i] = v[i];
     return GPIS_OK;
+}
+
+// ---- rendering from a distance field ---------------------------------------------------------------------------------------
+int gpis_render_field_default_opts(int dim, float step, gpis_render_field_opts* o) {
+    if (!o || (dim != 2 && dim != 3) || !(std::isfinite(step) && step > 0.f)) return GPIS_ERR_ARG;
+    gpis_render_opts d;
+    (void)gpis_render_default_opts(dim, &d);
+    o->tnear = d.tnear; o->tfar = d.tfar; o->max_steps = d.max_steps; o->refine = d.refine;
+    o->min_step = step * 0.5f; o->max_step = INFINITY; o->slack = 3.0f;
+    return GPIS_OK;
+}
+int gpis_render_set_field_tiles(void* render, int on) {
+    if (!render) return GPIS_ERR_ARG;
+    ((Renderer*)render)->field_tiles = on != 0;
+    return GPIS_OK;
+}
+// the checks that need neither field nor map, then the field's state and dim (before anything is dropped) and the call on the
+// field's device: an argument, state or limit error leaves the previous result readable
+static int render_field_call(void* d, void* render, RayGeom& g, const float* pose, const gpis_render_field_opts* opts,
+                             const double* cs, long long n, void* stream) {
+    if (!d || !render || !pose) return GPIS_ERR_ARG;
+    const int np = g.dim == 3 ? 12 : 6;
+    for (int k = 0; k < np; ++k) if (!std::isfinite(pose[k])) return GPIS_ERR_ARG;
+    for (int k = 0; k < g.dim; ++k) g.t[k] = pose[k];
+    for (int k = 0; k < g.dim * g.dim; ++k) g.R[k] = pose[g.dim + k];
+    const DistanceField& df = *(const DistanceField*)d;
+    if (!df.valid) return GPIS_ERR_STATE;
+    if (df.dim != g.dim) return GPIS_ERR_ARG;
+    gpis_render_field_opts dflt;
+    if (!opts) { (void)gpis_render_field_default_opts(g.dim, df.step, &dflt); opts = &dflt; }
+    RenderFieldOpts o;
+    o.tnear = opts->tnear; o.tfar = opts->tfar; o.min_step = opts->min_step; o.max_step = opts->max_step; o.slack = opts->slack;
+    o.refine = opts->refine; o.max_steps = opts->max_steps;
+    if (int rc = render_field_check_opts(o)) return rc;
+    if (int rc = render_check_geom(g, n)) return rc;
+    Renderer& r = *(Renderer*)render;
+    DeviceScope ds(df.device);
+    try {
+        if (int rc = r.bind(df.device)) { r.clear_result(); return rc; }
+        const int rc = r.render_field(df, g, cs, n, o, stream ? (hipStream_t)stream : df.own);
+        if (rc != GPIS_OK) r.clear_result();
+        return rc;
+    } catch (...) { r.clear_result(); return GPIS_ERR_STATE; }
+}
+int gpis3_render_depth_field(void* m, void* df, void* render, const gpis_cam* cam, const float* pose12,
+                             const gpis_render_field_opts* opts, void* stream) {
+    if (!cam && !m) return GPIS_ERR_ARG;
+    float c4[4];
+    int wh[2];
+    if (cam) { c4[0] = cam->fx; c4[1] = cam->fy; c4[2] = cam->cx; c4[3] = cam->cy; wh[0] = cam->width; wh[1] = cam->height; }
+    else gpis3_impl_camera((GPisMap3*)m, c4, wh);
+    RayGeom g{};
+    g.dim = 3; g.fx = c4[0]; g.fy = c4[1]; g.cx = c4[2]; g.cy = c4[3]; g.width = wh[0]; g.height = wh[1];
+    return render_field_call(df, render, g, pose12, opts, nullptr, (long long)wh[0] * wh[1], stream);
+}
+int gpis2_render_scan_field(void* m, void* df, void* render, const float* thetas, int n, const float* off2, const float* pose6,
+                            const gpis_render_field_opts* opts, void* stream) {
+    if (!thetas || n < 1 || (!off2 && !m)) return GPIS_ERR_ARG;
+    for (int k = 0; k < n; ++k) if (!std::isfinite(thetas[k])) return GPIS_ERR_ARG;
+    if ((long long)n > Renderer::kMaxRays) return GPIS_ERR_LIMIT;
+    RayGeom g{};
+    g.dim = 2;
+    if (off2) { g.off[0] = off2[0]; g.off[1] = off2[1]; }
+    else gpis2_impl_sensor_offset((GPisMap*)m, g.off);
+    std::vector<double> cs;
+    try { cs.resize((size_t)2 * n); } catch (...) { return GPIS_ERR_STATE; }
+    for (int k = 0; k < n; ++k) {
+        cs[2 * (size_t)k] = std::cos((double)thetas[k]);
+        cs[2 * (size_t)k + 1] = std::sin((double)thetas[k]);
+    }
+    return render_field_call(df, render, g, pose6, opts, cs.data(), n, stream);
 }
 
 // ---- tracking ----------------------------------------------------------------------------------------------------------

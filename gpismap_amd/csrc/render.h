@@ -1,6 +1,7 @@
 // Depth images and laser scans rendered from the map on the device: rays marched through the map's test(), one
 // MapQuery pass over the rays still active per step, the crossing refined by bisection and a secant point.  The active rays are
 // compacted by a deterministic exclusive scan after every pass (no atomics), so the result is the same bits on every run.
+// The same views from a distance field (§7g): sphere tracing through the field's sampler, one thread per ray in one fused kernel.
 #pragma once
 #include <cstdint>
 #include "dev_common.h"
@@ -9,6 +10,7 @@ namespace gpis {
 
 class MapQuery;
 class OnGPISStore;
+struct DistanceField;
 
 struct RenderOpts {
     float tnear, tfar;          // ray interval: depth z (3-D) / range r (2-D)
@@ -16,6 +18,16 @@ struct RenderOpts {
     float far_step;             // arc-length step after a sample without a GP answer (f NaN)
     float level;                // surface level (inside iff f < level)
     float max_var;              // both samples of a crossing need var_f <= max_var
+    int refine;                 // bisection rounds on the bracket of a hit
+    int max_steps;              // samples per ray before it stops with status 2
+};
+
+// the march through a distance field (§7g): no level and no variance gate (the field's level is zero, its gate was applied when
+// it was built)
+struct RenderFieldOpts {
+    float tnear, tfar;          // ray interval: depth z (3-D) / range r (2-D)
+    float min_step, max_step;   // clamp of the arc-length step |d| - slack * step (metres); max_step may be +inf
+    float slack;                // lattice steps taken off |d| before it is used as a step
     int refine;                 // bisection rounds on the bracket of a hit
     int max_steps;              // samples per ray before it stops with status 2
 };
@@ -53,6 +65,10 @@ struct Renderer {
     double* h_cs = nullptr; size_t cap_hcs = 0;      // page-locked staging of the 2-D directions
     int* d_part = nullptr;       // compaction: per-block counts (kScanBlocks + 1)
     int* h_cnt = nullptr;        // page-locked: the count of the last compaction
+    unsigned long long* d_fpart = nullptr; size_t cap_fpart = 0;   // field render: per-block counters (3 each) and their sums
+    unsigned long long* h_fcnt = nullptr;                          // page-locked: samples, hits, largest per-ray sample count
+    bool field_tiles = true;     // field render, 3-D: a wavefront owns an 8 x 8 pixel tile (false: 64 consecutive rays of the
+                                 // column-major image); the results do not depend on it
     // outputs
     float* d_depth = nullptr; float* d_rec = nullptr; uint8_t* d_status = nullptr;
 
@@ -60,19 +76,27 @@ struct Renderer {
     int dim = 0;
     long long nrays = 0;
     bool valid = false;
+    bool field = false;          // the result is a field render: d_rec is [n][1 + dim] (d, gradient), else [n][2(1 + dim)]
     long long passes = 0, march_passes = 0, samples = 0, evals = 0, hits = 0;
+    long long max_samples = 0;   // field render: the largest number of samples a single ray took
     double k4_ms = 0.0;
     double mq_ms = 0.0;          // host wall time inside MapQuery::run_prepared (each call ends with its stream synchronised)
     float box_lo[3] = {0.f, 0.f, 0.f}, box_hi[3] = {0.f, 0.f, 0.f};   // the clip box used (search half-width included)
 
     Renderer();
     ~Renderer();
-    void clear_result() { valid = false; nrays = 0; dim = 0; passes = march_passes = samples = evals = hits = 0; k4_ms = mq_ms = 0.0; }
+    void clear_result() { valid = field = false; nrays = 0; dim = 0; passes = march_passes = samples = evals = hits = max_samples = 0; k4_ms = mq_ms = 0.0; }
+    int rec_width() const { return field ? 1 + dim : 2 * (1 + dim); }
     int bind(int dev);           // move to `dev` (frees the buffers of another device); GPIS_OK / GPIS_ERR_HIP
     // The whole render: set-up and clip, the march, refinement, the output; synchronises `s`.  cs: 2-D beam cos / sin (host,
     // 2n doubles), ignored in 3-D.  Arguments are checked by the caller (render_check_*).
     int render(MapQuery& mq, OnGPISStore& store, const RayGeom& geo, const double* cs, long long n, const RenderOpts& o,
                hipStream_t s);
+    // The same views from a distance field: one fused kernel, a thread per ray; synchronises `s`.  The field must
+    // live on this renderer's device.  A field without a result: GPIS_ERR_STATE; one of another dim, bad options or geometry:
+    // GPIS_ERR_ARG / GPIS_ERR_LIMIT; all before the previous result is dropped.  passes = march_passes = 1, evals = 0.
+    int render_field(const DistanceField& df, const RayGeom& geo, const double* cs, long long n, const RenderFieldOpts& o,
+                     hipStream_t s);
 
 private:
     int ensure(long long n, int dm);
@@ -89,6 +113,7 @@ int compact_flags(const uint8_t* flag, const int* in, long long n, int* out, int
 
 // Argument checks shared by the C-ABI entries: GPIS_OK, GPIS_ERR_ARG, or GPIS_ERR_LIMIT (more than kMaxRays rays).
 int render_check_opts(const RenderOpts& o);
+int render_field_check_opts(const RenderFieldOpts& o);
 int render_check_geom(const RayGeom& g, long long n);
 
 }  // namespace gpis

@@ -9,6 +9,7 @@
 #include <algorithm>
 #include <chrono>
 #include <cmath>
+#include "dfield.h"
 #include "map_query.h"
 #include "render.h"
 
@@ -23,24 +24,61 @@ constexpr uint8_t kRunning = 255;     // status of a ray still marching
 
 inline int grid_for(long long n) { return (int)std::max(1ll, std::min((long long)kGridCap, (n + kBlock - 1) / kBlock)); }
 
-__device__ __forceinline__ void world_point(const RayGeom& g, const float* __restrict__ ray, const double* __restrict__ cs, int i,
-                                            float z, float& p0, float& p1, float& p2) {
+// the world point of parameter z on a ray: 3-D from its (u, v); 2-D from its host-double (c, s)
+__device__ __forceinline__ void world_point_at(const RayGeom& g, float u, float v, double c, double s, float z, float& p0, float& p1,
+                                               float& p2) {
     if (g.dim == 3) {
-        const float xl = ray[4 * (size_t)i] * z, yl = ray[4 * (size_t)i + 1] * z;
+        const float xl = u * z, yl = v * z;
         p0 = g.R[0] * xl + g.R[3] * yl + g.R[6] * z + g.t[0];
         p1 = g.R[1] * xl + g.R[4] * yl + g.R[7] * z + g.t[1];
         p2 = g.R[2] * xl + g.R[5] * yl + g.R[8] * z + g.t[2];
     } else {
-        const float xl = (float)((double)z * cs[2 * (size_t)i]) + g.off[0];
-        const float yl = (float)((double)z * cs[2 * (size_t)i + 1]) + g.off[1];
+        const float xl = (float)((double)z * c) + g.off[0];
+        const float yl = (float)((double)z * s) + g.off[1];
         p0 = g.R[0] * xl + g.R[2] * yl + g.t[0];
         p1 = g.R[1] * xl + g.R[3] * yl + g.t[1];
         p2 = 0.f;
     }
 }
 
-// Per ray: direction terms, the slab clip of [tnear, tfar] against the box (IEEE division; fmin / fmax drop the NaN of an axis
-// the ray runs in the plane of), the march state, NaN outputs.  flag = 1 for the rays whose clipped interval is not empty.
+__device__ __forceinline__ void world_point(const RayGeom& g, const float* __restrict__ ray, const double* __restrict__ cs, int i,
+                                            float z, float& p0, float& p1, float& p2) {
+    if (g.dim == 3) world_point_at(g, ray[4 * (size_t)i], ray[4 * (size_t)i + 1], 0.0, 0.0, z, p0, p1, p2);
+    else world_point_at(g, 0.f, 0.f, cs[2 * (size_t)i], cs[2 * (size_t)i + 1], z, p0, p1, p2);
+}
+
+// Set-up of ray i: its direction terms (3-D: u, v, il = 1 / sqrt(u^2 + v^2 + 1); 2-D: c, s of the beam), then the slab clip of
+// [tnear, tfar] against the box [lo, hi] (IEEE division; fmin / fmax drop the NaN of an axis the ray runs in the plane of)
+// into [t0, t1].
+__device__ __forceinline__ void ray_setup(const RayGeom& g, const double* __restrict__ cs, int i, float tnear, float tfar,
+                                          const float* lo, const float* hi, float& u, float& v, float& il, double& cd, double& sd,
+                                          float& t0, float& t1) {
+    float o[3], d[3];
+    if (g.dim == 3) {
+        const int col = i / g.height, row = i - col * g.height;
+        u = ((float)col - g.cx) / g.fx; v = ((float)row - g.cy) / g.fy;
+        il = 1.0f / sqrtf(u * u + v * v + 1.0f);
+        cd = sd = 0.0;
+        for (int a = 0; a < 3; ++a) { o[a] = g.t[a]; d[a] = g.R[a] * u + g.R[3 + a] * v + g.R[6 + a]; }
+    } else {
+        cd = cs[2 * (size_t)i]; sd = cs[2 * (size_t)i + 1];
+        u = v = 0.f; il = 1.0f;
+        const float c = (float)cd, s = (float)sd;
+        o[0] = g.R[0] * g.off[0] + g.R[2] * g.off[1] + g.t[0];
+        o[1] = g.R[1] * g.off[0] + g.R[3] * g.off[1] + g.t[1];
+        d[0] = g.R[0] * c + g.R[2] * s;
+        d[1] = g.R[1] * c + g.R[3] * s;
+    }
+    t0 = tnear; t1 = tfar;
+    for (int a = 0; a < g.dim; ++a) {
+        const float ta = (lo[a] - o[a]) / d[a], tb = (hi[a] - o[a]) / d[a];
+        t0 = fmaxf(t0, fminf(ta, tb));
+        t1 = fminf(t1, fmaxf(ta, tb));
+    }
+}
+
+// Per ray: ray_setup's direction terms and clip, the march state, NaN outputs.  flag = 1 for the rays whose clipped interval is
+// not empty.
 __global__ void __launch_bounds__(kBlock) render_setup_kernel(RayGeom g, const double* __restrict__ cs, int n, bool empty, float tnear,
                                                               float tfar, float lx, float ly, float lz, float hx, float hy, float hz,
                                                               float* __restrict__ ray, float* __restrict__ z, float* __restrict__ zend,
@@ -50,26 +88,10 @@ __global__ void __launch_bounds__(kBlock) render_setup_kernel(RayGeom g, const d
     const int nc = 2 * (1 + g.dim);
     const float lo[3] = {lx, ly, lz}, hi[3] = {hx, hy, hz};
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-        float o[3], d[3];
-        if (g.dim == 3) {
-            const int col = i / g.height, row = i - col * g.height;
-            const float u = ((float)col - g.cx) / g.fx, v = ((float)row - g.cy) / g.fy;
-            const float il = 1.0f / sqrtf(u * u + v * v + 1.0f);
-            ray[4 * (size_t)i] = u; ray[4 * (size_t)i + 1] = v; ray[4 * (size_t)i + 2] = il; ray[4 * (size_t)i + 3] = 0.f;
-            for (int a = 0; a < 3; ++a) { o[a] = g.t[a]; d[a] = g.R[a] * u + g.R[3 + a] * v + g.R[6 + a]; }
-        } else {
-            const float c = (float)cs[2 * (size_t)i], s = (float)cs[2 * (size_t)i + 1];
-            o[0] = g.R[0] * g.off[0] + g.R[2] * g.off[1] + g.t[0];
-            o[1] = g.R[1] * g.off[0] + g.R[3] * g.off[1] + g.t[1];
-            d[0] = g.R[0] * c + g.R[2] * s;
-            d[1] = g.R[1] * c + g.R[3] * s;
-        }
-        float t0 = tnear, t1 = tfar;
-        for (int a = 0; a < g.dim; ++a) {
-            const float ta = (lo[a] - o[a]) / d[a], tb = (hi[a] - o[a]) / d[a];
-            t0 = fmaxf(t0, fminf(ta, tb));
-            t1 = fminf(t1, fmaxf(ta, tb));
-        }
+        float u, v, il, t0, t1;
+        double cd, sd;
+        ray_setup(g, cs, i, tnear, tfar, lo, hi, u, v, il, cd, sd, t0, t1);
+        if (g.dim == 3) { ray[4 * (size_t)i] = u; ray[4 * (size_t)i + 1] = v; ray[4 * (size_t)i + 2] = il; ray[4 * (size_t)i + 3] = 0.f; }
         const bool go = !empty && t0 <= t1;
         z[i] = t0; zend[i] = t1; nstep[i] = 0; state[i] = 0;
         status[i] = go ? kRunning : 1;
@@ -228,7 +250,143 @@ __global__ void __launch_bounds__(kBlock) render_scatter_kernel(const int* __res
     }
 }
 
+// ---- rendering from a distance field --------------------------------------------------------------------------
+// Thread -> ray.  Linear: thread t owns ray t.  Tiled (3-D): wavefront w owns the 8 x 8 pixel tile (w / tiles_r, w % tiles_r),
+// lane l its pixel (8 (w / tiles_r) + l / 8, 8 (w % tiles_r) + l % 8); -1 where the tile hangs over the image.  The rays of a
+// wavefront then end close together and sample neighbouring cells.
+__device__ __forceinline__ int field_ray_of_thread(const RayGeom& g, int n, bool tiled) {
+    const long long t = (long long)blockIdx.x * kBlock + threadIdx.x;
+    if (!tiled) return t < n ? (int)t : -1;
+    const int tiles_r = (g.height + 7) >> 3;
+    const long long w = t >> 6;
+    const int l = (int)(t & 63);
+    const long long col = (w / tiles_r) * 8 + (l >> 3);
+    const int row = (int)(w % tiles_r) * 8 + (l & 7);
+    return (col < g.width && row < g.height) ? (int)(col * g.height + row) : -1;
+}
+
+// One thread marches one ray from set-up to output (sphere tracing): ray_setup's terms and clip, then one loop whose every
+// turn takes one sample of the field -- a march sample, a bisection midpoint or the final secant point, by the ray's phase -- so
+// the lanes of a wavefront share one sampler whatever their phases.  Step, hit, refinement and status: tests/render_field_ref.py.
+// Nothing is written per sample.  part[3 b ..]: the block's samples, hits and largest per-ray sample count, reduced in a fixed
+// order (wave shuffles, then the four waves in order).
+template <int D>
+__global__ void __launch_bounds__(kBlock) render_field_kernel(RayGeom g, const double* __restrict__ cs, int n, bool tiled,
+                                                              RenderFieldOpts o, float lx, float ly, float lz, float hx, float hy,
+                                                              float hz, const float* __restrict__ F, DfLattice Lrt,
+                                                              float* __restrict__ depth, float* __restrict__ rec,
+                                                              uint8_t* __restrict__ status, unsigned long long* __restrict__ part) {
+    constexpr int NC = 1 + D;
+    __shared__ unsigned long long sh[3][kBlock / 64];
+    const float nanf_ = __int_as_float(0x7fc00000);
+    const int i = field_ray_of_thread(g, n, tiled);
+    DfLattice L = Lrt;
+    L.dim = D;                                   // (checked by the host: the sampler's loops unroll, the sample stays in registers)
+    int ns = 0, hit = 0;
+    if (i >= 0) {
+        const float lo[3] = {lx, ly, lz}, hi[3] = {hx, hy, hz};
+        float u, v, il, z, zend;
+        double cd, sd;
+        ray_setup(g, cs, i, o.tnear, o.tfar, lo, hi, u, v, il, cd, sd, z, zend);
+        const float sl = o.slack * L.st;
+        float zlo = 0.f, glo = 0.f, ghi = 0.f, q = z;
+        float smp[NC];
+        int st = (z <= zend) ? kRunning : 1;
+        int phase = 0, nstep = 0, round = 0;     // phase 0 march, 1 bisection, 2 the final sample
+        bool has = false;
+        while (st == kRunning) {
+            float p0, p1, p2;
+            world_point_at(g, u, v, cd, sd, q, p0, p1, p2);
+            df_sample_at(F, L, p0, p1, p2, smp);
+            ++ns;
+            const float d = smp[0];
+            if (phase == 0) {
+                if (has && d < 0.f && !(glo < 0.f)) {
+                    ghi = d;                     // bracket [zlo, z]
+                    phase = o.refine > 0 ? 1 : 2;
+                } else {
+                    zlo = z; glo = d; has = true;
+                    if (++nstep >= o.max_steps) { st = 2; break; }
+                    const float ds = isnan(d) ? o.min_step : fminf(fmaxf(fabsf(d) - sl, o.min_step), o.max_step);
+                    const float zn = z + (D == 3 ? ds * il : ds);
+                    if (!(zn <= zend)) { st = 1; break; }
+                    z = zn; q = zn;
+                    continue;
+                }
+            } else if (phase == 1) {
+                if (d < 0.f) { z = q; ghi = d; }
+                else { zlo = q; glo = d; }
+                if (++round >= o.refine) phase = 2;
+            } else {
+                st = 0;
+                break;
+            }
+            if (phase == 1) {
+                q = zlo + (z - zlo) * 0.5f;
+            } else if (isnan(glo)) {
+                q = z;
+            } else {
+                q = zlo + (z - zlo) * (glo / (glo - ghi));
+                q = fminf(fmaxf(q, zlo), z);
+            }
+        }
+        hit = st == 0;
+        depth[i] = hit ? q : nanf_;
+#pragma unroll
+        for (int c = 0; c < NC; ++c) rec[(size_t)i * NC + c] = hit ? smp[c] : nanf_;
+        status[i] = (uint8_t)st;
+    }
+    // the block's counters
+    unsigned long long a = (unsigned long long)ns, b = (unsigned long long)hit, m = (unsigned long long)ns;
+    for (int s = 32; s >= 1; s >>= 1) {
+        a += __shfl_down(a, s, 64);
+        b += __shfl_down(b, s, 64);
+        const unsigned long long y = __shfl_down(m, s, 64);
+        m = y > m ? y : m;
+    }
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    if (lane == 0) { sh[0][w] = a; sh[1][w] = b; sh[2][w] = m; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned long long sa = 0, sb = 0, sm = 0;
+        for (int k = 0; k < kBlock / 64; ++k) { sa += sh[0][k]; sb += sh[1][k]; sm = sh[2][k] > sm ? sh[2][k] : sm; }
+        part[3 * (size_t)blockIdx.x] = sa; part[3 * (size_t)blockIdx.x + 1] = sb; part[3 * (size_t)blockIdx.x + 2] = sm;
+    }
+}
+
+// the block partials reduced by one block: thread t takes the blocks t, t + 1024, ... in order, then the halving tree over the
+// threads; out = samples, hits, largest per-ray count
+__global__ void __launch_bounds__(1024) render_field_top_kernel(const unsigned long long* __restrict__ part, int nb,
+                                                                unsigned long long* __restrict__ out) {
+    __shared__ unsigned long long sh[3][1024];
+    unsigned long long a = 0, b = 0, m = 0;
+    for (int k = threadIdx.x; k < nb; k += 1024) {
+        a += part[3 * (size_t)k]; b += part[3 * (size_t)k + 1];
+        const unsigned long long y = part[3 * (size_t)k + 2];
+        m = y > m ? y : m;
+    }
+    sh[0][threadIdx.x] = a; sh[1][threadIdx.x] = b; sh[2][threadIdx.x] = m;
+    __syncthreads();
+    for (int s = 512; s >= 1; s >>= 1) {
+        if ((int)threadIdx.x < s) {
+            sh[0][threadIdx.x] += sh[0][threadIdx.x + s];
+            sh[1][threadIdx.x] += sh[1][threadIdx.x + s];
+            const unsigned long long y = sh[2][threadIdx.x + s];
+            if (y > sh[2][threadIdx.x]) sh[2][threadIdx.x] = y;
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) { out[0] = sh[0][0]; out[1] = sh[1][0]; out[2] = sh[2][0]; }
+}
+
 }  // namespace
+
+int render_field_check_opts(const RenderFieldOpts& o) {
+    if (!std::isfinite(o.tnear) || !std::isfinite(o.tfar) || !(o.tnear >= 0.f) || !(o.tnear < o.tfar)) return GPIS_ERR_ARG;
+    if (!(std::isfinite(o.min_step) && o.min_step > 0.f) || std::isnan(o.max_step) || !(o.min_step <= o.max_step)) return GPIS_ERR_ARG;
+    if (!std::isfinite(o.slack) || o.slack < 0.f || o.refine < 0 || o.refine > 64 || o.max_steps < 1) return GPIS_ERR_ARG;
+    return GPIS_OK;
+}
 
 int render_check_opts(const RenderOpts& o) {
     auto pos = [](float v) { return std::isfinite(v) && v > 0.f; };
@@ -272,12 +430,15 @@ int Renderer::bind(int dev) {
             (void)hipFree(p);
         if (h_cs) (void)hipHostFree(h_cs);
         if (h_cnt) (void)hipHostFree(h_cnt);
+        (void)hipFree(d_fpart);
+        if (h_fcnt) (void)hipHostFree(h_fcnt);
         if (own) (void)hipStreamDestroy(own);
     }
     d_ray = nullptr; d_cs = nullptr; d_z = d_zend = d_zlo = d_glo = d_ghi = d_q = nullptr; d_nstep = nullptr;
     d_state = d_flag = nullptr; d_list[0] = d_list[1] = d_list[2] = nullptr; d_x = d_qrec = nullptr; d_part = nullptr;
     d_depth = d_rec = nullptr; d_status = nullptr; h_cs = nullptr; h_cnt = nullptr; own = nullptr;
-    cap = cap_hcs = 0;
+    d_fpart = nullptr; h_fcnt = nullptr;
+    cap = cap_hcs = cap_fpart = 0;
     clear_result();
     device = dev;
     if (dev < 0) return GPIS_OK;
@@ -418,6 +579,52 @@ int Renderer::render(MapQuery& mq, OnGPISStore& store, const RayGeom& geo, const
     GPIS_HIP(hipStreamSynchronize(s));
     for (int a = 0; a < 3; ++a) { box_lo[a] = lo[a]; box_hi[a] = hi[a]; }
     dim = dm; nrays = n; hits = nh; valid = true;
+    return GPIS_OK;
+}
+
+// The whole field render: one fused kernel over the rays, the top reduction of its counters, one page-locked copy
+int Renderer::render_field(const DistanceField& df, const RayGeom& geo, const double* cs, long long n, const RenderFieldOpts& o,
+                           hipStream_t s) {
+    if (!df.valid) return GPIS_ERR_STATE;
+    if (df.dim != geo.dim) return GPIS_ERR_ARG;
+    if (int rc = render_field_check_opts(o)) return rc;
+    if (int rc = render_check_geom(geo, n)) return rc;
+    clear_result();
+    if (int rc = ensure(n, geo.dim)) return rc;
+    const int dm = geo.dim;
+    const bool tiled = dm == 3 && field_tiles;
+    const long long waves = tiled ? (long long)((geo.width + 7) / 8) * ((geo.height + 7) / 8) : (n + 63) / 64;
+    const int nb = (int)((waves + kBlock / 64 - 1) / (kBlock / 64));
+    if ((size_t)nb > cap_fpart) {
+        (void)hipFree(d_fpart);
+        d_fpart = nullptr; cap_fpart = 0;
+        GPIS_HIP(hipMalloc((void**)&d_fpart, sizeof(unsigned long long) * 3 * ((size_t)nb + 1)));
+        cap_fpart = (size_t)nb;
+    }
+    if (!h_fcnt) GPIS_HIP(hipHostMalloc((void**)&h_fcnt, sizeof(unsigned long long) * 3));
+    const DfLattice L = df.lattice();
+    float lo[3] = {L.ox, L.oy, L.oz}, hi[3];
+    const int ln[3] = {L.nx, L.ny, L.nz};
+    for (int a = 0; a < 3; ++a) hi[a] = lo[a] + (float)(ln[a] - 1) * L.st;
+    if (dm == 2) {
+        for (long long i = 0; i < 2 * n; ++i) h_cs[i] = cs[i];
+        GPIS_HIP(hipMemcpyAsync(d_cs, h_cs, sizeof(double) * 2 * (size_t)n, hipMemcpyHostToDevice, s));
+        hipLaunchKernelGGL(render_field_kernel<2>, dim3(nb), dim3(kBlock), 0, s, geo, d_cs, (int)n, tiled, o, lo[0], lo[1], lo[2], hi[0],
+                           hi[1], hi[2], df.d_dist, L, d_depth, d_rec, d_status, d_fpart);
+    } else {
+        hipLaunchKernelGGL(render_field_kernel<3>, dim3(nb), dim3(kBlock), 0, s, geo, d_cs, (int)n, tiled, o, lo[0], lo[1], lo[2], hi[0],
+                           hi[1], hi[2], df.d_dist, L, d_depth, d_rec, d_status, d_fpart);
+    }
+    GPIS_HIP(hipGetLastError());
+    unsigned long long* d_out = d_fpart + 3 * (size_t)cap_fpart;
+    hipLaunchKernelGGL(render_field_top_kernel, dim3(1), dim3(1024), 0, s, d_fpart, nb, d_out);
+    GPIS_HIP(hipGetLastError());
+    GPIS_HIP(hipMemcpyAsync(h_fcnt, d_out, sizeof(unsigned long long) * 3, hipMemcpyDeviceToHost, s));
+    GPIS_HIP(hipStreamSynchronize(s));
+    for (int a = 0; a < 3; ++a) { box_lo[a] = lo[a]; box_hi[a] = hi[a]; }
+    dim = dm; nrays = n; field = true; valid = true;
+    passes = 1; march_passes = 1;
+    samples = (long long)h_fcnt[0]; hits = (long long)h_fcnt[1]; max_samples = (long long)h_fcnt[2];
     return GPIS_OK;
 }
 

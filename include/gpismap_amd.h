@@ -389,13 +389,17 @@ int   gpis3_render_depth(void* map, void* render, const gpis_cam* cam, const flo
 /* range [n], record [n][6], status [n] */
 int   gpis2_render_scan(void* map, void* render, const float* thetas, int n, const float* pose6, const gpis_render_opts* opts,
                         void* hip_stream);
-/* host copies of the last result (any pointer may be NULL); GPIS_ERR_STATE without one */
+/* host copies of the last result (any pointer may be NULL); GPIS_ERR_STATE without one.  rec is [rays][2 (1 + dim)] after a map
+ * render and [rays][1 + dim] after a field render (gpis_render_info's out[16] says which is held) */
 int   gpis_render_get(void* render, float* depth, float* rec, unsigned char* status);
 /* device pointers of the last result (NULL without one), valid until the next render or gpis_render_destroy */
 int   gpis_render_device(void* render, const float** d_depth, const float** d_rec, const unsigned char** d_status);
 /* out[0..n): rays, dim, test() passes (march + refinement + output), march passes, samples (rays over all passes), K4
  * evaluations, ms inside K4 (only while the map's profiling is on), hits, clip box lo[3], hi[3] (NaN for an empty map),
- * 1 if a result is held, ms of host wall time inside the test() passes (each ends synchronised) */
+ * 1 if a result is held, ms of host wall time inside the test() passes (each ends synchronised), the kind of result held
+ * (0 a map render, 1 a field render: gpis3_render_depth_field / gpis2_render_scan_field), the largest number of samples a single
+ * ray took (field renders; 0 after a map render).  After a field render passes = march passes = 1 (the one kernel), samples
+ * counts every sample of every ray, K4 evaluations and both ms are 0 and the clip box is the lattice's. */
 int   gpis_render_info(void* render, double* out, int n);
 
 /* ---- tracking: depth-camera and laser poses against the map on the device -----------------------------
@@ -481,6 +485,51 @@ int   gpis3_track_depth_field(void* map, void* df, void* tracker, const gpis_cam
 int   gpis2_track_scan_field(void* map, void* df, void* tracker, const float* thetas, const float* ranges, int n,
                              const float* off2, const float* pose6_init, const gpis_track_opts* opts, float* pose6_out,
                              void* hip_stream);
+
+/* ---- rendering from a distance field --------------------------------------------------------------------
+ * gpis3_render_depth / gpis2_render_scan with the map's test() replaced by the field's sampler (sphere tracing): the same rays,
+ * parameter, world point, slab clip, hit rule, refinement, statuses and output layout, with these differences.
+ * Clip box: the lattice, [origin, origin + (float)(n - 1) * step] per axis.  Sample: gpis_dfield_sample's interpolant d and its
+ * gradient at the fp32 world point; inside iff d < 0 (the field's level is zero by construction; there is no level and no
+ * variance gate: max_var was applied when the field was built).  A NaN sample (outside the lattice: after the clip only at the
+ * box's faces, through rounding) counts as outside / unknown and advances the ray by min_step.  Step: clamp(|d| - slack * step,
+ * min_step, max_step) of arc length, slack in lattice steps.  On lattice points the stored |d| exceeds the distance to the
+ * nearest anchor by at most 2 steps (§7e) and the interpolant adds at most sqrt(3)/2 steps (sqrt(2)/2 in 2-D), so with
+ * slack >= 2.87 an unclamped step never exceeds the distance to the nearest anchor.  Anchors sample the surface once per crossed
+ * lattice edge: this bounds tunnelling at the field's own resolution, not below it, and a step clamped up to min_step can pass
+ * through anything thinner than min_step.  d = +-inf (a field without sites) steps max_step and ends as a miss.
+ * Output per ray: depth (z / r), record [d, grad(dim)] at the reported point -- the gradient is the surface normal the field
+ * sees -- and status (0 hit, 1 left the clipped interval, 2 max_steps samples); no hit: NaN.  One fused kernel marches every ray
+ * from set-up to output in one thread; nothing is written per sample; the counters (samples, hits, the largest sample count of
+ * a ray) come from a fixed-order reduction.  Same bits on every run, stream and thread-to-pixel mapping.
+ * map: may be NULL; it is read only for what the caller leaves NULL: the camera (cam NULL) in 3-D, the sensor offset (off2
+ * NULL) in 2-D.  A field from gpis_dfield_from_grid renders without a map.  The renderer moves to the field's device;
+ * hip_stream NULL: the field's own stream.  The result is read through gpis_render_get / _device / _info.
+ * Errors: a NULL field, renderer or pose, cam / off2 NULL without a map, a bad camera, a non-finite pose or beam angle, a field of
+ * another dim, non-finite tnear / tfar, tnear < 0, tnear >= tfar, min_step <= 0, non-finite or > max_step, a NaN max_step, a
+ * negative or non-finite slack, refine outside [0, 64], max_steps < 1 -> GPIS_ERR_ARG; a field without a result ->
+ * GPIS_ERR_STATE; more than 2^26 rays -> GPIS_ERR_LIMIT: all with the previous result untouched.  Any other failure leaves no
+ * result. */
+typedef struct gpis_render_field_opts {
+    float tnear, tfar;          /* ray interval: depth (3-D) / range (2-D) */
+    float min_step, max_step;   /* clamp of |d| - slack * step as the arc-length step; max_step may be +inf */
+    float slack;                /* lattice steps taken off |d| */
+    int refine;                 /* bisection rounds */
+    int max_steps;              /* samples per ray */
+} gpis_render_field_opts;
+/* defaults for a field of lattice step `step`: tnear, tfar and max_steps as gpis_render_default_opts; min_step = step / 2 (the
+ * field holds no feature thinner than a cell), max_step +inf, slack 3, refine 8.  A step that is not finite and positive ->
+ * GPIS_ERR_ARG */
+int   gpis_render_field_default_opts(int dim, float step, gpis_render_field_opts* opts);
+/* thread-to-pixel mapping of the 3-D field kernel (test hook: the results do not depend on it): 1 = a wavefront owns an 8 x 8
+ * pixel tile (the default), 0 = 64 consecutive rays of the column-major image */
+int   gpis_render_set_field_tiles(void* render, int on);
+/* depth [W*H], record [W*H][4], status [W*H].  opts NULL: the defaults for the field's step */
+int   gpis3_render_depth_field(void* map, void* df, void* render, const gpis_cam* cam, const float* pose12,
+                               const gpis_render_field_opts* opts, void* hip_stream);
+/* range [n], record [n][3], status [n].  off2: the sensor offset (x, y) in the laser frame, NULL = the map's */
+int   gpis2_render_scan_field(void* map, void* df, void* render, const float* thetas, int n, const float* off2,
+                              const float* pose6, const gpis_render_field_opts* opts, void* hip_stream);
 
 #ifdef __cplusplus
 }
