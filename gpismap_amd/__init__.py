@@ -117,6 +117,8 @@ def lib():
     L.gpis_obsgp_train2d.argtypes = [vp, fp, fp, C.c_int, C.c_int]
     L.gpis_obsgp_train1d.argtypes = [vp, fp, fp, C.c_int]
     L.gpis_obsgp_query.argtypes = [vp, fp, C.c_int, fp, fp]
+    L.gpis_obsgp_query_route.argtypes = [vp, C.c_int, fp, C.c_int, fp, fp]
+    L.gpis_obsgp_pending.argtypes = [vp]
     L.gpis_obsgp_num_groups.argtypes = [vp]
     L.gpis_obsgp_get_group.argtypes = [vp, C.c_int, ip, fp, fp, fp]
     L.gpis_ongpis_create.restype = vp
@@ -1138,6 +1140,32 @@ class ObsGP:
         var = np.zeros(n, dtype=np.float32)
         _check(self.L.gpis_obsgp_query(self.h, _p(q), n, _p(val), _p(var)), "gpis_obsgp_query")
         return val, var
+
+    def query_route(self, route, q, val0=0.0):
+        """The batch through route 0 (query), 1 (stage_q + query_staged) or 2 (stage_qb + query_staged_b_async + wait_b);
+        routes 1 and 2 start from val = 0 whatever val0 says."""
+        q = np.ascontiguousarray(q, dtype=np.float32)
+        n = q.shape[0]
+        val = np.full(n, val0, dtype=np.float32)
+        var = np.zeros(n, dtype=np.float32)
+        _check(self.L.gpis_obsgp_query_route(self.h, route, _p(q), n, _p(val), _p(var)), "gpis_obsgp_query_route")
+        return val, var
+
+    def query_begin_b(self, q):
+        """First half of route 2: the batch is left pending on the second staging set (collect with query_end_b)."""
+        q = np.ascontiguousarray(q, dtype=np.float32)
+        _check(self.L.gpis_obsgp_query_route(self.h, 3, _p(q), q.shape[0], None, None), "gpis_obsgp_query_route")
+        return q.shape[0]
+
+    def query_end_b(self, n):
+        val = np.zeros(n, dtype=np.float32)
+        var = np.zeros(n, dtype=np.float32)
+        _check(self.L.gpis_obsgp_query_route(self.h, 4, None, n, _p(val), _p(var)), "gpis_obsgp_query_route")
+        return val, var
+
+    def pending(self):
+        """True while a batch of the second staging set is issued and not yet waited for."""
+        return self.L.gpis_obsgp_pending(self.h) == 1
 
     def num_groups(self):
         return self.L.gpis_obsgp_num_groups(self.h)

@@ -229,7 +229,7 @@ int gpis2_stats(void* m, double* out, int n) { if (!m || !out) return GPIS_ERR_A
 int gpis2_pass_jobs(void* m, long long* out4) { if (!m || !out4) return GPIS_ERR_ARG; gpis2_impl_pass_jobs((GPisMap*)m, out4); return GPIS_OK; }
 
 // ---- ObsGP --------------------------------------------------------------------
-struct ObsHandle { int device = -1; ObsGPDevice g; hipStream_t s = nullptr; };
+struct ObsHandle { int device = -1; ObsGPDevice g; hipStream_t s = nullptr; hipStream_t sb = nullptr; int nb = -1; };   // sb: the second staging set's stream, nb: queries of its batch not collected yet, -1 none (gpis_obsgp_query_route)
 void* gpis_obsgp_create(void) {
     if (gpis_device_count() < 1) { fprintf(stderr, "[gpismap_amd] no HIP device\n"); return nullptr; }
     ObsHandle* h = new (std::nothrow) ObsHandle();
@@ -237,7 +237,7 @@ void* gpis_obsgp_create(void) {
     if (h && hipStreamCreate(&h->s) != hipSuccess) { delete h; return nullptr; }
     return h;
 }
-void gpis_obsgp_destroy(void* g) { if (!g) return; ObsHandle* h = (ObsHandle*)g; DeviceScope dev_scope_(h->device); if (h->s) (void)hipStreamDestroy(h->s); delete h; }
+void gpis_obsgp_destroy(void* g) { if (!g) return; ObsHandle* h = (ObsHandle*)g; DeviceScope dev_scope_(h->device); (void)h->g.wait_b(); if (h->sb) (void)hipStreamDestroy(h->sb); if (h->s) (void)hipStreamDestroy(h->s); delete h; }
 int gpis_obsgp_train2d(void* g, const float* vu, const float* f, int ni, int nj) {
     if (!g) return GPIS_ERR_ARG; ObsHandle* h = (ObsHandle*)g; DeviceScope dev_scope_(h->device); return h->g.train2d(vu, f, ni, nj, h->s);
 }
@@ -247,6 +247,59 @@ int gpis_obsgp_train1d(void* g, const float* th, const float* f, int n) {
 int gpis_obsgp_query(void* g, const float* q, int nq, float* val, float* var) {
     if (!g || !q || !val || !var) return GPIS_ERR_ARG; ObsHandle* h = (ObsHandle*)g; DeviceScope dev_scope_(h->device); return h->g.query(q, nq, val, var, h->s);
 }
+// One batch through one of the routes the maps' update() takes (kernel-level tests of the staging paths):
+//   0  query()                                   val is read and written (untouched where no group answers)
+//   1  stage_q() + query_staged()                val starts from 0; below 4096 queries the kernel works on the page-locked staging itself
+//   2  stage_qb() + query_staged_b_async() + wait_b(), the batch on a stream of its own as in update(); val starts from 0
+//   3  the first half of route 2: returns with the batch pending (val / var are not touched)
+//   4  the second half: wait_b() and the answers of the batch route 3 left behind (q is not read); GPIS_ERR_STATE when there is
+//      none, GPIS_ERR_ARG when nq is not that batch's size
+int gpis_obsgp_query_route(void* g, int route, const float* q, int nq, float* val, float* var) {
+    if (!g || route < 0 || route > 4 || nq < 0) return GPIS_ERR_ARG;
+    if (nq > 0 && ((route != 4 && !q) || (route != 3 && (!val || !var)))) return GPIS_ERR_ARG;
+    ObsHandle* h = (ObsHandle*)g; DeviceScope dev_scope_(h->device);
+    if (route == 0) return h->g.query(q, nq, val, var, h->s);
+    if (!h->g.trained()) return GPIS_ERR_STATE;
+    const size_t per = (h->g.mode() == 2) ? 2 : 1;
+    if (route == 1) {
+        if (nq == 0) return GPIS_OK;
+        float* sq = h->g.stage_q(nq);
+        if (!sq) return GPIS_ERR_HIP;
+        std::memcpy(sq, q, sizeof(float) * per * (size_t)nq);
+        const int rc = h->g.query_staged(nq, h->s);
+        if (rc) return rc;
+        std::memcpy(val, h->g.staged_val(), sizeof(float) * (size_t)nq);
+        std::memcpy(var, h->g.staged_var(), sizeof(float) * (size_t)nq);
+        return GPIS_OK;
+    }
+    if (route == 2 || route == 3) {
+        if (nq > 0) {
+            if (!h->sb && hipStreamCreateWithFlags(&h->sb, hipStreamNonBlocking) != hipSuccess) { h->sb = nullptr; return GPIS_ERR_HIP; }
+            float* sq = h->g.stage_qb(nq);
+            if (!sq) return GPIS_ERR_HIP;
+            std::memcpy(sq, q, sizeof(float) * per * (size_t)nq);
+            h->nb = -1;                       // (stage_qb collected whatever was pending: its answers are gone)
+            const int rc = h->g.query_staged_b_async(nq, h->sb);
+            if (rc) return rc;
+        }
+        if (route == 3) { if (nq > 0) h->nb = nq; return GPIS_OK; }
+    } else {                                  // route 4: exactly the batch that route 3 left behind
+        if (h->nb < 0) return GPIS_ERR_STATE;
+        if (nq != h->nb) return GPIS_ERR_ARG;
+        h->nb = -1;
+    }
+    const int rc = h->g.wait_b();
+    if (rc) return rc;
+    if (nq > 0) {
+        if (!h->g.staged_val_b() || !h->g.staged_var_b()) return GPIS_ERR_STATE;
+        std::memcpy(val, h->g.staged_val_b(), sizeof(float) * (size_t)nq);
+        std::memcpy(var, h->g.staged_var_b(), sizeof(float) * (size_t)nq);
+    }
+    return GPIS_OK;
+}
+// 1 while a batch of the second staging set has been issued and not yet waited for (by route 4, by the next route 2 / 3, or by a
+// training call, which waits before it rewrites the groups the batch reads), else 0
+int gpis_obsgp_pending(void* g) { if (!g) return GPIS_ERR_ARG; return ((ObsHandle*)g)->g.pending_b() ? 1 : 0; }
 int gpis_obsgp_num_groups(void* g) { if (!g) return GPIS_ERR_ARG; return ((ObsHandle*)g)->g.ngroups(); }
 int gpis_obsgp_get_group(void* g, int group, int* n, float* x, float* alpha, float* L) {
     if (!g || !n) return GPIS_ERR_ARG; ObsHandle* h = (ObsHandle*)g; DeviceScope dev_scope_(h->device); return h->g.get_group(group, n, x, alpha, L, h->s);

@@ -58,6 +58,7 @@ public:
     float* stage_qb(int nq);
     int query_staged_b_async(int nq, hipStream_t s);
     int wait_b();
+    bool pending_b() const { return b_pending_; }   // a batch of the second set was issued and not waited for yet
     const float* staged_val_b() const { return hb_val_; }
     const float* staged_var_b() const { return hb_var_; }
     bool trained() const { return trained_; }

@@ -254,6 +254,7 @@ int ObsGPDevice::train2d(const float* xt, const float* f, int ni, int nj, hipStr
 }
 
 int ObsGPDevice::train1d(const float* xt, const float* f, int N, hipStream_t s) {
+    if (b_pending_) (void)wait_b();    // (as train2d: a batch of the second staging set, on its own stream, still reads the groups)
     trained_ = false;
     if (!(N > 0 && xt && f)) return GPIS_ERR_ARG;
     sz0_ = sz1_ = 0;  // a later train2d must re-partition

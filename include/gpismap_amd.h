@@ -193,6 +193,14 @@ int   gpis_obsgp_train1d(void* g, const float* theta, const float* f, int n);
  * q: nq*2 (2-D) or nq (1-D); val is pre-filled by the caller and left untouched where no
  * group answers (var = 1e6 there) */
 int   gpis_obsgp_query(void* g, const float* q, int nq, float* val, float* var);
+/* The same batch through one of the routes update() takes (kernel-level tests of the staging paths): route 0 = gpis_obsgp_query;
+ * 1 = page-locked staging, the kernel working on it directly below 4096 queries; 2 = the second staging set, asynchronous on
+ * a stream of its own, then waited for.  Routes 1 and 2 start from val = 0 (a miss leaves 0 and var = 1e6).  Route 3 is the
+ * first half of route 2 (returns with the batch pending; val / var untouched), route 4 the second (waits, copies the
+ * answers of that batch; q is not read; GPIS_ERR_STATE when route 3 left none, GPIS_ERR_ARG when nq is not its size).  A
+ * training call issued in between waits for the batch: gpis_obsgp_pending() is 1 from route 3 until then, else 0. */
+int   gpis_obsgp_query_route(void* g, int route, const float* q, int nq, float* val, float* var);
+int   gpis_obsgp_pending(void* g);
 int   gpis_obsgp_num_groups(void* g);
 int   gpis_obsgp_get_group(void* g, int group, int* n, float* x128, float* alpha64, float* L4096);
 
