@@ -44,6 +44,11 @@ class gpis_track_opts(C.Structure):
                 ("max_iters", C.c_int), ("min_inliers", C.c_int)]
 
 
+class gpis_plan_opts(C.Structure):
+    _fields_ = [("clearance", C.c_float), ("margin", C.c_float), ("gain", C.c_float), ("connectivity", C.c_int),
+                ("max_rounds", C.c_int)]
+
+
 def _p(a, t=C.c_float):
     return a.ctypes.data_as(C.POINTER(t))
 
@@ -200,6 +205,20 @@ def lib():
         L.gpis_render_set_field_tiles.argtypes = [vp, C.c_int]
         L.gpis3_render_depth_field.argtypes = [vp, vp, vp, C.POINTER(gpis_cam), fp, fo, vp]
         L.gpis2_render_scan_field.argtypes = [vp, vp, vp, fp, C.c_int, fp, fp, fo, vp]
+    if hasattr(L, "gpis_plan_create"):
+        ll, ub = C.POINTER(C.c_longlong), C.POINTER(C.c_ubyte)
+        L.gpis_plan_default_opts.argtypes = [C.c_int, C.c_float, C.POINTER(gpis_plan_opts)]
+        L.gpis_plan_create.restype = vp
+        L.gpis_plan_create.argtypes = []
+        L.gpis_plan_destroy.argtypes = [vp]
+        L.gpis_plan_solve.argtypes = [vp, vp, fp, C.c_int, C.POINTER(gpis_plan_opts), vp]
+        L.gpis_plan_info.argtypes = [vp, dp, C.c_int]
+        L.gpis_plan_get.argtypes = [vp, fp, ub]
+        L.gpis_plan_device.argtypes = [vp, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
+        L.gpis_plan_paths.argtypes = [vp, fp, C.c_int, C.c_int, vp]
+        L.gpis_plan_path_counts.argtypes = [vp, ll, ll]
+        L.gpis_plan_get_paths.argtypes = [vp, ll, fp, fp, ub]
+        L.gpis_plan_set_schedule.argtypes = [vp, C.c_int, C.c_int]
     _lib = L
     return L
 
@@ -926,6 +945,19 @@ class DistanceField:
             self._renderer = Renderer()
         return self._renderer
 
+    def plan(self, goals, planner=None, **opts):
+        """Cost-to-go and policy over this field's free space towards `goals` [g, dim] (gpis_plan_solve).  opts: the
+        gpis_plan_opts fields (clearance, margin, gain, connectivity, max_rounds; defaults for this field's step).  Unknown
+        space is outside in the field and therefore free.  Returns the Planner holding the result (default: one kept by this
+        field); it stays valid when the field is recomputed."""
+        p = planner if planner is not None else self._own_planner()
+        return p.solve(self, goals, **opts)
+
+    def _own_planner(self):
+        if getattr(self, "_planner", None) is None:
+            self._planner = Planner()
+        return self._planner
+
     def _step(self):
         inf = self.info()
         if inf["dim"] == 0:
@@ -959,6 +991,106 @@ class DistanceField:
         _check(self.L.gpis2_render_scan_field(map_h, self.h, r.h, _p(thetas), thetas.size, _p(off) if off is not None else None,
                                               _p(pose6), C.byref(o), None), "gpis2_render_scan_field")
         return r.get()
+
+
+def plan_opts(dim, step, **opts):
+    """gpis_plan_opts of the library's defaults for `dim` and a field of lattice step `step` (gpis_plan_default_opts) with the
+    given fields replaced."""
+    o = gpis_plan_opts()
+    _check(lib().gpis_plan_default_opts(int(dim), float(step), C.byref(o)), "gpis_plan_default_opts")
+    names = {f[0] for f in gpis_plan_opts._fields_}
+    for k, v in opts.items():
+        if k not in names:
+            raise GpisError("unknown plan option %r" % k)
+        setattr(o, k, v)
+    return o
+
+
+class Planner:
+    """Result holder of the path planner (gpis_plan_*): cost-to-go, policy and paths on the device, buffers reused across
+    calls.  A finished plan does not depend on the field it was solved on."""
+
+    INFO_KEYS = ("valid", "dim", "nx", "ny", "nz", "step", "goals", "goals_kept", "free", "reachable", "rounds",
+                 "tile_launches", "solve_ms", "max_cost")
+    INT_KEYS = ("valid", "dim", "nx", "ny", "nz", "goals", "goals_kept", "free", "reachable", "rounds", "tile_launches")
+
+    def __init__(self):
+        self.L = lib()
+        if self.L.gpis_device_count() < 1:
+            raise GpisError("no HIP device: gpismap_amd has no CPU fallback")
+        self.h = C.c_void_p(self.L.gpis_plan_create())
+        if not self.h:
+            raise GpisError("gpis_plan_create failed")
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.gpis_plan_destroy(self.h)
+            self.h = None
+
+    __del__ = close
+
+    def set_schedule(self, check_every=0, inner_cap=0):
+        """Outer rounds per convergence read-back and relaxation sweeps of a tile per round (0 = defaults 8 / 256; the results
+        do not depend on either)."""
+        _check(self.L.gpis_plan_set_schedule(self.h, int(check_every), int(inner_cap)), "gpis_plan_set_schedule")
+
+    def solve(self, field, goals, stream=0, **opts):
+        """gpis_plan_solve on a DistanceField holding a result; goals [g, dim].  Returns self."""
+        inf = field.info()
+        if inf["dim"] == 0:
+            raise GpisError("distance field holds no result")
+        g = np.ascontiguousarray(goals, dtype=np.float32).reshape(-1, inf["dim"])
+        o = plan_opts(inf["dim"], inf["step"], **opts)
+        _check(self.L.gpis_plan_solve(self.h, field.h, _p(g), g.shape[0], C.byref(o), C.c_void_p(stream)), "gpis_plan_solve")
+        return self
+
+    def info(self):
+        out = np.zeros(len(self.INFO_KEYS), dtype=np.float64)
+        _check(self.L.gpis_plan_info(self.h, _p(out, C.c_double), out.size), "gpis_plan_info")
+        d = dict(zip(self.INFO_KEYS, out.tolist()))
+        for k in self.INT_KEYS:
+            d[k] = int(d[k])
+        return d
+
+    def get(self):
+        """(cost f32, policy u8) host copies of the last result, each of shape shape[::-1] (x fastest)."""
+        i = self.info()
+        if not i["valid"]:
+            raise GpisError("planner holds no result")
+        shape = (i["nx"], i["ny"], i["nz"])[:i["dim"]][::-1]
+        n = int(np.prod(shape))
+        cost = np.zeros(n, np.float32)
+        pol = np.zeros(n, np.uint8)
+        _check(self.L.gpis_plan_get(self.h, _p(cost), _p(pol, C.c_ubyte)), "gpis_plan_get")
+        return cost.reshape(shape), pol.reshape(shape)
+
+    def device_ptrs(self):
+        """(d_cost, d_policy) device addresses of the last result (0 where there is none)."""
+        a, b = C.c_void_p(0), C.c_void_p(0)
+        _check(self.L.gpis_plan_device(self.h, C.byref(a), C.byref(b)), "gpis_plan_device")
+        return a.value or 0, b.value or 0
+
+    def paths(self, starts, max_points=None, stream=0):
+        """Lattice paths from `starts` [m, dim] along the policy (gpis_plan_paths).  Returns (list of [len, dim] float32 arrays,
+        start_cost [m], status [m] u8): status 0 arrived, 1 outside / non-finite, 2 not free, 3 unreachable, 4 cut off at
+        max_points (default: the number of lattice points, which no path can exceed)."""
+        i = self.info()
+        if not i["valid"]:
+            raise GpisError("planner holds no result")
+        dim = i["dim"]
+        x = np.ascontiguousarray(starts, dtype=np.float32).reshape(-1, dim)
+        if max_points is None:
+            max_points = max(2, min(i["nx"] * i["ny"] * i["nz"], 2 ** 31 - 1))
+        _check(self.L.gpis_plan_paths(self.h, _p(x), x.shape[0], int(max_points), C.c_void_p(stream)), "gpis_plan_paths")
+        m, tot = C.c_longlong(0), C.c_longlong(0)
+        _check(self.L.gpis_plan_path_counts(self.h, C.byref(m), C.byref(tot)), "gpis_plan_path_counts")
+        off = np.zeros(m.value + 1, np.int64)
+        pts = np.zeros((max(tot.value, 1), dim), np.float32)
+        sc = np.zeros(m.value, np.float32)
+        st = np.zeros(m.value, np.uint8)
+        _check(self.L.gpis_plan_get_paths(self.h, _p(off, C.c_longlong), _p(pts), _p(sc), _p(st, C.c_ubyte)), "gpis_plan_get_paths")
+        self.last_off = off
+        return [pts[off[k]:off[k + 1]] for k in range(m.value)], sc, st
 
 
 def render_field_opts(dim, step, **opts):

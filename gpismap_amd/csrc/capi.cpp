@@ -1,4 +1,5 @@
 // C-ABI (include/gpismap_amd.h) over the C++ classes.  Nothing throws across it.
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <new>
@@ -11,6 +12,7 @@
 #include "dfield.h"
 #include "render.h"
 #include "track.h"
+#include "plan.h"
 #include "obsgp.h"
 #include "ongpis.h"
 
@@ -647,6 +649,113 @@ int gpis_dfield_sample(void* d, const float* d_x, long long m, float* d_out, voi
     try {
         return df.sample(d_x, m, d_out, stream ? (hipStream_t)stream : df.own);
     } catch (...) { return GPIS_ERR_STATE; }
+}
+
+// ---- planning through a distance field ---------------------------------------------------------------------------------------
+int gpis_plan_default_opts(int dim, float step, gpis_plan_opts* o) {
+    if (!o || (dim != 2 && dim != 3) || !(std::isfinite(step) && step > 0.f)) return GPIS_ERR_ARG;
+    o->clearance = 0.f; o->margin = 4.f * step; o->gain = 4.f; o->connectivity = 1; o->max_rounds = 0;
+    return GPIS_OK;
+}
+void* gpis_plan_create(void) {
+    if (gpis_device_count() < 1) { fprintf(stderr, "[gpismap_amd] no HIP device\n"); return nullptr; }
+    Planner* p = new (std::nothrow) Planner();
+    if (p && !p->own) { delete p; return nullptr; }
+    return p;
+}
+void gpis_plan_destroy(void* plan) { delete (Planner*)plan; }
+int gpis_plan_set_schedule(void* plan, int check_every, int inner_cap) {
+    if (!plan || check_every < 0 || inner_cap < 0) return GPIS_ERR_ARG;
+    Planner& p = *(Planner*)plan;
+    p.check_every = check_every ? std::min(check_every, (int)Planner::kMaxBatch) : 8;
+    p.inner_cap = inner_cap ? inner_cap : 256;
+    return GPIS_OK;
+}
+// the argument and state checks come before anything is dropped: such an error leaves the previous result readable
+int gpis_plan_solve(void* plan, void* d, const float* goals, int ngoals, const gpis_plan_opts* opts, void* stream) {
+    if (!plan || !d || !goals || ngoals < 1) return GPIS_ERR_ARG;
+    const DistanceField& df = *(const DistanceField*)d;
+    gpis_plan_opts dflt;
+    if (!opts) {
+        if (!df.valid) return GPIS_ERR_STATE;
+        (void)gpis_plan_default_opts(df.dim, df.step, &dflt);
+        opts = &dflt;
+    }
+    PlanOpts o;
+    o.clearance = opts->clearance; o.margin = opts->margin; o.gain = opts->gain; o.connectivity = opts->connectivity;
+    o.max_rounds = opts->max_rounds;
+    if (int rc = plan_check_opts(o)) return rc;
+    if (!df.valid) return GPIS_ERR_STATE;
+    Planner& p = *(Planner*)plan;
+    DeviceScope ds(df.device);
+    try {
+        if (int rc = p.bind(df.device)) { p.clear_result(); return rc; }
+        const int rc = p.solve(df, goals, ngoals, o, stream ? (hipStream_t)stream : df.own);
+        if (rc != GPIS_OK) p.clear_result();
+        return rc;
+    } catch (...) { p.clear_result(); return GPIS_ERR_STATE; }
+}
+int gpis_plan_info(void* plan, double* out, int n) {
+    if (!plan || !out || n < 0) return GPIS_ERR_ARG;
+    const Planner& p = *(Planner*)plan;
+    const bool v = p.valid;
+    const double w[14] = {v ? 1.0 : 0.0, v ? (double)p.dim : 0.0, v ? (double)p.n[0] : 0.0, v ? (double)p.n[1] : 0.0,
+                          v ? (double)p.n[2] : 0.0, v ? (double)p.step : 0.0, (double)p.goals_given, (double)p.goals_kept,
+                          (double)p.nfree, (double)p.nreach, (double)p.rounds, (double)p.launches, p.solve_ms, (double)p.max_cost};
+    for (int i = 0; i < n && i < 14; ++i) out[i] = w[i];
+    return GPIS_OK;
+}
+int gpis_plan_get(void* plan, float* cost, unsigned char* policy) {
+    if (!plan) return GPIS_ERR_ARG;
+    Planner& p = *(Planner*)plan;
+    if (!p.valid) return GPIS_ERR_STATE;
+    DeviceScope ds(p.device);
+    const size_t n = (size_t)p.ngrid;
+    if (cost) GPIS_HIP(hipMemcpyAsync(cost, p.d_cost, sizeof(float) * n, hipMemcpyDeviceToHost, p.own));
+    if (policy) GPIS_HIP(hipMemcpyAsync(policy, p.d_policy, n, hipMemcpyDeviceToHost, p.own));
+    GPIS_HIP(hipStreamSynchronize(p.own));
+    return GPIS_OK;
+}
+int gpis_plan_device(void* plan, const float** d_cost, const unsigned char** d_policy) {
+    if (!plan) return GPIS_ERR_ARG;
+    const Planner& p = *(Planner*)plan;
+    if (d_cost) *d_cost = p.valid ? p.d_cost : nullptr;
+    if (d_policy) *d_policy = p.valid ? p.d_policy : nullptr;
+    return GPIS_OK;
+}
+int gpis_plan_paths(void* plan, const float* starts, int m, int max_points, void* stream) {
+    if (!plan || !starts || m < 1 || max_points < 2) return GPIS_ERR_ARG;
+    Planner& p = *(Planner*)plan;
+    if (!p.valid) return GPIS_ERR_STATE;
+    if (m > Planner::kMaxStarts) return GPIS_ERR_LIMIT;
+    DeviceScope ds(p.device);
+    try {
+        const int rc = p.paths(starts, m, max_points, stream ? (hipStream_t)stream : p.own);
+        if (rc != GPIS_OK) p.paths_valid = false;
+        return rc;
+    } catch (...) { p.paths_valid = false; return GPIS_ERR_STATE; }
+}
+int gpis_plan_path_counts(void* plan, long long* npaths, long long* npoints) {
+    if (!plan) return GPIS_ERR_ARG;
+    const Planner& p = *(Planner*)plan;
+    if (!p.valid || !p.paths_valid) return GPIS_ERR_STATE;
+    if (npaths) *npaths = p.npaths;
+    if (npoints) *npoints = p.npoints;
+    return GPIS_OK;
+}
+int gpis_plan_get_paths(void* plan, long long* off, float* points, float* start_cost, unsigned char* status) {
+    if (!plan) return GPIS_ERR_ARG;
+    Planner& p = *(Planner*)plan;
+    if (!p.valid || !p.paths_valid) return GPIS_ERR_STATE;
+    DeviceScope ds(p.device);
+    const size_t m = (size_t)p.npaths;
+    if (off) GPIS_HIP(hipMemcpyAsync(off, p.d_off, sizeof(long long) * (m + 1), hipMemcpyDeviceToHost, p.own));
+    if (points && p.npoints > 0)
+        GPIS_HIP(hipMemcpyAsync(points, p.d_points, sizeof(float) * (size_t)p.npoints * p.dim, hipMemcpyDeviceToHost, p.own));
+    if (start_cost) GPIS_HIP(hipMemcpyAsync(start_cost, p.d_scost, sizeof(float) * m, hipMemcpyDeviceToHost, p.own));
+    if (status) GPIS_HIP(hipMemcpyAsync(status, p.d_status, m, hipMemcpyDeviceToHost, p.own));
+    GPIS_HIP(hipStreamSynchronize(p.own));
+    return GPIS_OK;
 }
 
 // ---- rendering ---------------------------------------------------------------------------------------------------------

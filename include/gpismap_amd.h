@@ -539,6 +539,61 @@ int   gpis3_render_depth_field(void* map, void* df, void* render, const gpis_cam
 int   gpis2_render_scan_field(void* map, void* df, void* render, const float* thetas, int n, const float* off2,
                               const float* pose6, const gpis_render_field_opts* opts, void* hip_stream);
 
+/* ---- planning: shortest collision-free paths through a distance field on the device ----------------------
+ * A navigation function over the free space of the field's lattice (dim, n, origin, step; index p = (k ny + j) nx + i; world
+ * point origin + (float)i * step), in float32 without FMA.  Free iff dist[p] >= clearance (+inf is free, negative values and
+ * -inf are not); unknown space was made "outside" when the field was built (§7e) and therefore counts as FREE: the plan is
+ * only as good as the field's sign.  Point cost c = 1 + gain * (t * t), t = max(0, margin - (dist - clearance)) / margin
+ * (margin 0: c = 1).  Offsets (dx, dy, dz) in {-1, 0, 1}^dim, direction index k = ((dz + 1) 3 + (dy + 1)) 3 + (dx + 1), 13 =
+ * stay; connectivity 0: the 4 / 6 axis offsets, 1: all 8 / 26.  A move p -> q = p + o exists iff q is in the lattice and p +
+ * every non-empty subset of o's non-zero components is free (no squeezing between blocked corners); its weight is
+ * w = (len * step) * (0.5f * (c[p] + c[q])), len = 1, sqrtf(2.f), sqrtf(3.f).  A goal snaps to i = (int)floorf(u + 0.5f),
+ * u = (x - origin) / step per axis; one that is outside the lattice, non-finite or not free is dropped.  cost = the greatest
+ * solution of cost[p] = min over moves of fl(cost[q] + w) with 0 at the kept goals: +inf where not free or unreachable.  The
+ * fixed point does not depend on the order of relaxations, so the bits are those of a float32 Dijkstra, on every run and for
+ * every schedule.  policy[p] = 13 at a goal, else the k minimising fl(cost[q] + w) (ties: the smaller cost[q], then the
+ * smaller k), 255 where there is none.  No goal kept: the solve succeeds with every cost +inf and every policy 255.
+ * The planner owns its buffers (10 B per lattice point, grow-only, reused), copies the lattice geometry and reads dist only
+ * during gpis_plan_solve: a finished plan stays valid when the field is recomputed or destroyed.  It moves to the field's
+ * device; hip_stream NULL: the field's own stream (gpis_plan_paths: the planner's); every call returns with its work finished.
+ * Errors: a NULL plan, field, goals or starts, ngoals < 1, m < 1, a non-finite or negative margin or gain, a non-finite
+ * clearance, connectivity outside {0, 1}, max_rounds < 0, max_points < 2, gain > 1e4 (which keeps every w far above an ulp of
+ * any reachable cost, so that a policy step always lowers the cost) -> GPIS_ERR_ARG; a field without a result, or paths /
+ * getters without a solve -> GPIS_ERR_STATE; more than 2^24 starts -> GPIS_ERR_LIMIT: all with the previous result untouched.
+ * max_rounds > 0 exceeded -> GPIS_ERR_LIMIT and no result (0: no cap other than lattice points + 1, which a converging solve
+ * cannot reach).  Any other failure leaves no result. */
+typedef struct gpis_plan_opts {
+    float clearance;            /* free iff dist >= clearance */
+    float margin, gain;         /* point cost 1 + gain at contact with the clearance, falling to 1 at clearance + margin */
+    int connectivity;           /* 0: axis moves, 1: diagonals too */
+    int max_rounds;             /* cap on the outer rounds; 0 = none */
+} gpis_plan_opts;
+/* clearance 0, margin 4 * step, gain 4, connectivity 1, max_rounds 0 */
+int   gpis_plan_default_opts(int dim, float step, gpis_plan_opts* opts);
+void* gpis_plan_create(void);                              /* on the current device; NULL without one */
+void  gpis_plan_destroy(void* plan);
+/* goals: host [ngoals][dim].  opts NULL: the defaults for the field's step */
+int   gpis_plan_solve(void* plan, void* df, const float* goals, int ngoals, const gpis_plan_opts* opts, void* hip_stream);
+/* out[0..n): 1 if a result is held, dim, n[3], the step, goals given, goals kept, free points, reachable points, outer rounds,
+ * tile launches, ms of host wall time in the solve, the largest finite cost (14 values) */
+int   gpis_plan_info(void* plan, double* out, int n);
+/* host copies, prod(n) each; either may be NULL */
+int   gpis_plan_get(void* plan, float* cost, unsigned char* policy);
+/* device pointers of the last result, valid until the next solve or gpis_plan_destroy (NULL where there is none) */
+int   gpis_plan_device(void* plan, const float** d_cost, const unsigned char** d_policy);
+/* Paths from the host starts [m][dim], each snapped like a goal.  Status 1: outside the lattice or non-finite; 2: not free;
+ * 3: free but cost +inf (these three give no points); otherwise the policy is followed to a goal and the world point of every
+ * lattice point visited is emitted, start and goal included: status 0.  A step whose target does not have a strictly smaller
+ * cost, or reaching max_points before the goal, ends the path with status 4, the points so far kept.  The paths are packed
+ * back to back at offsets from an exclusive scan of their lengths: the same on every run. */
+int   gpis_plan_paths(void* plan, const float* starts, int m, int max_points, void* hip_stream);
+int   gpis_plan_path_counts(void* plan, long long* npaths, long long* npoints);
+/* off[m + 1], points[off[m]][dim], start_cost[m] (NaN for status 1), status[m]; any may be NULL */
+int   gpis_plan_get_paths(void* plan, long long* off, float* points, float* start_cost, unsigned char* status);
+/* test hook (the results do not depend on it): outer rounds per read-back of the convergence count (0 = 8, at most 64) and
+ * relaxation sweeps of a tile per outer round (0 = 256) */
+int   gpis_plan_set_schedule(void* plan, int check_every, int inner_cap);
+
 #ifdef __cplusplus
 }
 #endif
