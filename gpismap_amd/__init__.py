@@ -151,6 +151,15 @@ def lib():
     L.gpis_ongpis_set_lazy_inverse.argtypes = [vp, C.c_int]
     L.gpis3_prepare_test.argtypes = [vp]
     L.gpis3_set_lazy_inverse.argtypes = [vp, C.c_int]
+    if hasattr(L, "gpis_mapquery_create"):
+        L.gpis_mapquery_create.restype = vp
+        L.gpis_mapquery_create.argtypes = [vp, C.c_float, C.c_float, C.c_float]
+        L.gpis_mapquery_destroy.argtypes = [vp]
+        L.gpis_mapquery_set_table.argtypes = [vp, C.c_int, fp, fp, fp, ip, ip, C.c_int, fp, fp, ip, C.c_double]
+        L.gpis_mapquery_set_chunk.argtypes = [vp, C.c_int]
+        L.gpis_mapquery_run.argtypes = [vp, fp, C.c_int, fp]
+        L.gpis_mapquery_candidates.argtypes = [vp, ip, ip]
+        L.gpis_mapquery_pass_jobs.argtypes = [vp, C.POINTER(C.c_longlong)]
     if hasattr(L, "gpis_mesh_create"):
         L.gpis_mesh_create.restype = vp
         L.gpis_mesh_create.argtypes = []
@@ -1413,3 +1422,60 @@ class OnGPIS:
         a, b = C.c_float(0), C.c_float(0)
         self.L.gpis_ongpis_last_ms(self.h, C.byref(a), C.byref(b))
         return a.value, b.value
+
+
+class MapQueryProbe:
+    """Kernel-level K5: the driver of test() (cluster lookup, binning, the evaluation passes, the blend) over the store of an
+    OnGPIS handle and a caller-given cluster table.  Test infrastructure: the maps build the same object from their trees."""
+
+    def __init__(self, ongpis, search_half, var_thre, prior_var):
+        self.L = lib()
+        self.on = ongpis              # (keeps the store alive)
+        self.dim = ongpis.dim
+        self.h = C.c_void_p(self.L.gpis_mapquery_create(ongpis.h, float(search_half), float(var_thre), float(prior_var)))
+        if not self.h:
+            raise GpisError("gpis_mapquery_create failed")
+
+    def close(self):
+        if getattr(self, "h", None):
+            if getattr(self.on, "h", None):
+                self.L.gpis_mapquery_destroy(self.h)
+            self.h = None
+
+    __del__ = close
+
+    def set_table(self, c, lo, hi, model, parent, anc_lo=None, anc_hi=None, anc_parent=None, pitch=1.0):
+        """Entries in traversal order; c / lo / hi [ncl, 3] (third column 0 in 2-D); ancestors parents-first."""
+        f32 = lambda a: np.ascontiguousarray(np.zeros((0, 3)) if a is None else a, dtype=np.float32).reshape(-1, 3)
+        i32 = lambda a: np.ascontiguousarray(np.zeros(0) if a is None else a, dtype=np.int32).reshape(-1)
+        c, lo, hi, anc_lo, anc_hi = f32(c), f32(lo), f32(hi), f32(anc_lo), f32(anc_hi)
+        model, parent, anc_parent = i32(model), i32(parent), i32(anc_parent)
+        ncl, nanc = c.shape[0], anc_lo.shape[0]
+        if not (lo.shape[0] == hi.shape[0] == model.size == parent.size == ncl and anc_hi.shape[0] == anc_parent.size == nanc):
+            raise ValueError("set_table: array sizes disagree")
+        _check(self.L.gpis_mapquery_set_table(self.h, ncl, _p(c), _p(lo), _p(hi), _p(model, C.c_int), _p(parent, C.c_int), nanc,
+                                              _p(anc_lo), _p(anc_hi), _p(anc_parent, C.c_int), float(pitch)), "gpis_mapquery_set_table")
+
+    def set_chunk(self, n):
+        _check(self.L.gpis_mapquery_set_chunk(self.h, int(n)), "gpis_mapquery_set_chunk")
+
+    def run(self, x, res):
+        """res [n, 2(1+dim)] is input and output: returns a new array, the pre-fill where the reference writes nothing."""
+        x = np.ascontiguousarray(x, dtype=np.float32).reshape(-1, self.dim)
+        res = np.array(res, dtype=np.float32, order="C", copy=True).reshape(x.shape[0], 2 * (1 + self.dim))
+        _check(self.L.gpis_mapquery_run(self.h, _p(x), x.shape[0], _p(res)), "gpis_mapquery_run")
+        self._n = x.shape[0]
+        return res
+
+    def candidates(self):
+        """(ncand [n], cand [3, n]) of the last run (one chunk, non-empty table)."""
+        n = getattr(self, "_n", 0)
+        ncand = np.zeros(n, dtype=np.int32)
+        cand = np.zeros((3, n), dtype=np.int32)
+        _check(self.L.gpis_mapquery_candidates(self.h, _p(ncand, C.c_int), _p(cand, C.c_int)), "gpis_mapquery_candidates")
+        return ncand, cand
+
+    def pass_jobs(self):
+        a = (C.c_longlong * 4)()
+        _check(self.L.gpis_mapquery_pass_jobs(self.h, a), "gpis_mapquery_pass_jobs")
+        return [int(v) for v in a]

@@ -467,6 +467,110 @@ int gpis_ongpis_last_ms(void* s, float* t, float* e) {
     return GPIS_OK;
 }
 
+// ---- K5 probe: a MapQuery over an OnGPIS handle's store and a caller-given cluster table --------------------------
+struct MqHandle {
+    OnHandle* on;
+    MapQuery mq;
+    float* d_x = nullptr; float* d_res = nullptr; size_t cap_x = 0, cap_res = 0;
+    int last_n = -1;     // queries of the last run when its candidates can be read back (one chunk, a table), else -1
+    MqHandle(OnHandle* o, float half, float thre, float prior) : on(o), mq(o->st.dim(), half, thre, prior) {}
+};
+void* gpis_mapquery_create(void* ongpis, float search_half, float var_thre, float prior_var) {
+    if (!ongpis || !(search_half > 0.f) || !std::isfinite(search_half) || std::isnan(var_thre) || std::isnan(prior_var)) return nullptr;
+    OnHandle* o = (OnHandle*)ongpis;
+    DeviceScope dev_scope_(o->device);
+    return new (std::nothrow) MqHandle(o, search_half, var_thre, prior_var);
+}
+void gpis_mapquery_destroy(void* h) {
+    if (!h) return; MqHandle* q = (MqHandle*)h;
+    DeviceScope dev_scope_(q->on->device);
+    (void)hipStreamSynchronize(q->on->s);
+    (void)hipFree(q->d_x); (void)hipFree(q->d_res);
+    delete q;
+}
+int gpis_mapquery_set_table(void* h, int ncl, const float* c, const float* lo, const float* hi, const int* model, const int* parent,
+                            int nanc, const float* anc_lo, const float* anc_hi, const int* anc_parent, double pitch) {
+    if (!h || ncl < 0 || nanc < 0 || !(pitch > 0.0) || !std::isfinite(pitch)) return GPIS_ERR_ARG;
+    if (ncl > 0 && (!c || !lo || !hi || !model || !parent)) return GPIS_ERR_ARG;
+    if (nanc > 0 && (!anc_lo || !anc_hi || !anc_parent)) return GPIS_ERR_ARG;
+    MqHandle* q = (MqHandle*)h;
+    // everything a kernel would index with is checked here: a model must be a trained slot of the store or -1, a parent an
+    // ancestor or -1, an ancestor's parent an earlier ancestor or -1 (so that every chain ends)
+    for (int a = 0; a < nanc; ++a) if (anc_parent[a] < -1 || anc_parent[a] >= a) return GPIS_ERR_ARG;
+    for (int i = 0; i < ncl; ++i) {
+        if (parent[i] < -1 || parent[i] >= nanc) return GPIS_ERR_ARG;
+        if (model[i] < -1) return GPIS_ERR_ARG;
+        if (model[i] >= 0) { const ClusterModel* m = q->on->st.model(model[i]); if (!m || !m->base) return GPIS_ERR_ARG; }
+        for (int d = 0; d < 3; ++d) if (!std::isfinite(c[3 * i + d])) return GPIS_ERR_ARG;
+    }
+    DeviceScope dev_scope_(q->on->device);
+    try {
+        std::vector<ClusterEntry> ent((size_t)ncl);
+        std::vector<AncestorEntry> anc((size_t)nanc);
+        for (int i = 0; i < ncl; ++i) {
+            for (int d = 0; d < 3; ++d) { ent[i].c[d] = c[3 * i + d]; ent[i].lo[d] = lo[3 * i + d]; ent[i].hi[d] = hi[3 * i + d]; }
+            ent[i].model = model[i]; ent[i].parent = parent[i];
+        }
+        for (int a = 0; a < nanc; ++a) {
+            for (int d = 0; d < 3; ++d) { anc[a].lo[d] = anc_lo[3 * a + d]; anc[a].hi[d] = anc_hi[3 * a + d]; }
+            anc[a].parent = anc_parent[a];
+        }
+        q->last_n = -1;
+        (void)hipStreamSynchronize(q->on->s);
+        return q->mq.set_clusters(ent, anc, pitch, q->on->s);
+    } catch (...) { return GPIS_ERR_STATE; }
+}
+int gpis_mapquery_set_chunk(void* h, int n) {
+    if (!h || n < 0) return GPIS_ERR_ARG;
+    ((MqHandle*)h)->mq.chunk = n ? n : (1 << 22);
+    return GPIS_OK;
+}
+int gpis_mapquery_run(void* h, const float* x, int n, float* res_inout) {
+    if (!h || n < 0 || (n > 0 && (!x || !res_inout))) return GPIS_ERR_ARG;
+    MqHandle* q = (MqHandle*)h;
+    DeviceScope dev_scope_(q->on->device);
+    q->last_n = -1;
+    const int dim = q->on->st.dim();
+    const size_t nx = (size_t)dim * n, nr = (size_t)2 * (1 + dim) * n;
+    if (nx > q->cap_x) { (void)hipFree(q->d_x); q->d_x = nullptr; q->cap_x = 0; GPIS_HIP(hipMalloc(&q->d_x, sizeof(float) * nx)); q->cap_x = nx; }
+    if (nr > q->cap_res) { (void)hipFree(q->d_res); q->d_res = nullptr; q->cap_res = 0; GPIS_HIP(hipMalloc(&q->d_res, sizeof(float) * nr)); q->cap_res = nr; }
+    hipStream_t s = q->on->s;
+    if (n > 0) {
+        GPIS_HIP(hipMemcpyAsync(q->d_x, x, sizeof(float) * nx, hipMemcpyHostToDevice, s));
+        GPIS_HIP(hipMemcpyAsync(q->d_res, res_inout, sizeof(float) * nr, hipMemcpyHostToDevice, s));
+    }
+    int rc;
+    try { rc = q->mq.run(q->on->st, q->d_x, n, q->d_res, s); } catch (...) { return GPIS_ERR_STATE; }
+    // (GPIS_ERR_STATE is the kernels' error word -- the affected results are NaN -- or a tile list that outgrew its array: res is
+    // delivered for inspection as gpis_ongpis_eval_layout does, and the call still fails; any other error returns at once)
+    if (rc && rc != GPIS_ERR_STATE) return rc;
+    if (n > 0) GPIS_HIP(hipMemcpyAsync(res_inout, q->d_res, sizeof(float) * nr, hipMemcpyDeviceToHost, s));
+    GPIS_HIP(hipStreamSynchronize(s));
+    if (rc == GPIS_OK && n > 0 && n <= q->mq.chunk && q->mq.num_clusters() > 0) q->last_n = n;
+    return rc;
+}
+int gpis_mapquery_candidates(void* h, int* ncand, int* cand3) {
+    if (!h || !ncand || !cand3) return GPIS_ERR_ARG;
+    MqHandle* q = (MqHandle*)h;
+    if (q->last_n < 0) return GPIS_ERR_STATE;
+    DeviceScope dev_scope_(q->on->device);
+    const int* d_nc; const int* d_c; int cap;
+    q->mq.last_candidates(&d_nc, &d_c, &cap);
+    const int n = q->last_n;
+    if (!d_nc || !d_c || cap < n) return GPIS_ERR_STATE;
+    hipStream_t s = q->on->s;
+    GPIS_HIP(hipMemcpyAsync(ncand, d_nc, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, s));
+    for (int k = 0; k < 3; ++k)
+        GPIS_HIP(hipMemcpyAsync(cand3 + (size_t)k * n, d_c + (size_t)k * cap, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, s));
+    GPIS_HIP(hipStreamSynchronize(s));
+    return GPIS_OK;
+}
+int gpis_mapquery_pass_jobs(void* h, long long* out4) {
+    if (!h || !out4) return GPIS_ERR_ARG;
+    for (int k = 0; k < 4; ++k) out4[k] = ((MqHandle*)h)->mq.last_pass_jobs[k];
+    return GPIS_OK;
+}
+
 // ---- surface extraction ---------------------------------------------------------------------------------------
 void* gpis_mesh_create(void) {
     if (gpis_device_count() < 1) { fprintf(stderr, "[gpismap_amd] no HIP device\n"); return nullptr; }

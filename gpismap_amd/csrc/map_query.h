@@ -58,6 +58,8 @@ public:
     bool cluster_box(float* lo, float* hi) const;
     float search_half() const { return search_half_; }
     int num_clusters() const { return ncl_; }
+    // the lookup's result of the last chunk run (test probe, read-only): ncand [cap], cand [3][cap] device arrays
+    void last_candidates(const int** ncand, const int** cand, int* cap) const { *ncand = d_ncand_; *cand = d_cand_; *cap = cap_n_; }
     // statistics of the last run
     long long last_evals = 0, last_flops = 0, last_touched = 0;
     // K4 jobs of the last run per pass: 1, 2 full (two-candidate queries), 2a (value column), 2b (gradient columns)

@@ -269,6 +269,31 @@ int   gpis_ongpis_set_cu_reserve(void* s, int n);
 int   gpis_selftest_ranged_arith(unsigned long long seed, int blocks, int per_thread, int mode, unsigned long long* mismatches2);
 int   gpis_ongpis_last_ms(void* s, float* train_ms, float* eval_ms);
 
+/* ---- kernel level: K5, the driver of test() (lookup, binning, passes, blend) on a caller-given cluster table -------------
+ * A probe for tests: the MapQuery the maps use, over the store of a gpis_ongpis_create handle (its device, its stream, its
+ * dimension) and a synthetic table.  The handle must outlive the probe.  search_half: half side of the query box; var_thre:
+ * the blend's gate; prior_var: the variance written before anything else.  NULL on a null handle or non-finite arguments. */
+void* gpis_mapquery_create(void* ongpis, float search_half, float var_thre, float prior_var);
+void  gpis_mapquery_destroy(void* mq);
+/* The cluster table, entries in tree traversal order: centre c, box lo / hi ([ncl][3], the third 0 in 2-D), model = a trained
+ * slot of the store or -1, parent = index of the first ancestor or -1; ancestors: boxes and the next ancestor (an EARLIER index
+ * or -1).  Centres lie on a lattice of `pitch`.  Checked on the host before anything reaches a kernel: null handle, ncl < 0,
+ * a parent or model out of range, an ancestor parent that is not an earlier one -> GPIS_ERR_ARG; two centres in one lattice
+ * cell -> GPIS_ERR_STATE.  May be called again on a live handle (any size). */
+int   gpis_mapquery_set_table(void* mq, int ncl, const float* c, const float* lo, const float* hi, const int* model,
+                              const int* parent, int nanc, const float* anc_lo, const float* anc_hi, const int* anc_parent,
+                              double pitch);
+/* queries per pass of the chunk loop (the results do not depend on it); 0 = 2^22, negative -> GPIS_ERR_ARG */
+int   gpis_mapquery_set_chunk(void* mq, int n);
+/* x [n][dim], res [n][2(1+dim)] host arrays; res is uploaded first (as gpis3_test does): only the entries the reference
+ * writes change.  n = 0 is a no-op. */
+int   gpis_mapquery_run(void* mq, const float* x, int n, float* res_inout);
+/* the lookup's result of the last run: ncand [n], cand [3][n] (model slot or -1).  Only after a run of one chunk over a
+ * non-empty table, GPIS_ERR_STATE otherwise. */
+int   gpis_mapquery_candidates(void* mq, int* ncand, int* cand3);
+/* K4 jobs of the last run per pass: 1, 2 (two-candidate queries, all columns), 2a (value column), 2b (gradient columns) */
+int   gpis_mapquery_pass_jobs(void* mq, long long* out4);
+
 /* ---- surface extraction: the map's zero-level surface on the device (DESIGN.md "Surface extraction") ------------------
  * The map's test() on a lattice of nx x ny (x nz) points (index p = (k ny + j) nx + i, x fastest; coordinates
  * origin + (float)i * step per axis, float32, no FMA), f = slot 0 of each zero-prefilled record; marching tetrahedra on the

@@ -1,10 +1,91 @@
 // ORACLE (test infrastructure only; parity unpinned -- see linalg.hpp).
 // Flat C-ABI over the CPU restatement so tests/ and bench.py's cpu_baseline leg
 // can drive it through ctypes.  Nothing in gpismap_amd/ may link or load this.
+#include <algorithm>
 #include <cstring>
+#include <unordered_map>
 #include "map2.hpp"
 
 using namespace orc;
+
+namespace {
+// every cluster-level cell a query can return, in the order the tree walk visits them (Tree::queryClusters without the range
+// test), and the chain of nodes above each
+template <int DIM>
+struct K5Table {
+    std::vector<Tree<DIM>*> cells, ancs;
+    std::vector<int> parent, anc_parent;
+    std::unordered_map<Tree<DIM>*, int> index;
+    void walk(Tree<DIM>* t, int up) {
+        const TreeParam* prm = t->prm;
+        if (t->emptyLeaf()) return;
+        if (t->leaf && (double)t->box.h > (double)prm->cluster_half + prm->qleaf_eps_dist) return;
+        if ((double)t->box.h > (double)prm->cluster_half + prm->qdesc_eps) {
+            ancs.push_back(t); anc_parent.push_back(up);
+            const int me = (int)ancs.size() - 1;
+            for (int i = 0; i < Tree<DIM>::NC; ++i) walk(t->ch[i], me);
+        } else {
+            index[t] = (int)cells.size();
+            cells.push_back(t); parent.push_back(up);
+        }
+    }
+};
+template <int DIM>
+int k5_table(Tree<DIM>* root, int cap_cl, float* c, float* lo, float* hi, int* has_gp, int* parent, int cap_anc, float* alo,
+             float* ahi, int* aparent, int* nanc_out) {
+    K5Table<DIM> T;
+    if (root) T.walk(root, -1);
+    const int ncl = (int)T.cells.size(), nanc = (int)T.ancs.size();
+    if (nanc_out) *nanc_out = nanc;
+    if (ncl <= cap_cl && nanc <= cap_anc) {
+        for (int i = 0; i < ncl; ++i) {
+            for (int d = 0; d < 3; ++d) {
+                c[3 * i + d] = d < DIM ? T.cells[i]->box.c[d] : 0.f;
+                lo[3 * i + d] = d < DIM ? T.cells[i]->box.lo[d] : 0.f;
+                hi[3 * i + d] = d < DIM ? T.cells[i]->box.hi[d] : 0.f;
+            }
+            has_gp[i] = (T.cells[i]->gp && T.cells[i]->gp->trained) ? 1 : 0;
+            parent[i] = T.parent[i];
+        }
+        for (int a = 0; a < nanc; ++a) {
+            for (int d = 0; d < 3; ++d) {
+                alo[3 * a + d] = d < DIM ? T.ancs[a]->box.lo[d] : 0.f;
+                ahi[3 * a + d] = d < DIM ? T.ancs[a]->box.hi[d] : 0.f;
+            }
+            aparent[a] = T.anc_parent[a];
+        }
+    }
+    return ncl;
+}
+// the sorted candidates of each query as test_one finds them (the tree walk, then std::sort): count[n], idx [n][maxc] table
+// indices (the first min(count, maxc)), rec [n][3][8] the test1 record (mean 4, variances 4; 2-D 3 + 3) of each of the first
+// three that has a trained GP, zeros otherwise
+template <int DIM>
+void k5_candidates(Tree<DIM>* root, float half, const float* x, int n, int maxc, int* count, int* idx, float* rec) {
+    K5Table<DIM> T;
+    if (root) T.walk(root, -1);
+    for (int q = 0; q < n; ++q) {
+        const float* xt = x + (size_t)DIM * q;
+        std::vector<Tree<DIM>*> quads;
+        std::vector<float> sqdst;
+        if (root) root->queryClusters(Box<DIM>(xt, half), quads, &sqdst);
+        std::vector<int> id(sqdst.size());
+        for (size_t i = 0; i < id.size(); ++i) id[i] = (int)i;
+        if (sqdst.size() > 1) std::sort(id.begin(), id.end(), [&](int a, int b) { return sqdst[a] < sqdst[b]; });
+        count[q] = (int)quads.size();
+        for (int k = 0; k < maxc; ++k) idx[(size_t)q * maxc + k] = k < (int)id.size() ? T.index.at(quads[id[k]]) : -1;
+        for (int k = 0; k < 3; ++k) {
+            float* r = rec + ((size_t)q * 3 + k) * 8;
+            for (int j = 0; j < 8; ++j) r[j] = 0.f;
+            if (k < (int)id.size() && quads[id[k]]->gp && quads[id[k]]->gp->trained) {
+                float m[4] = {0, 0, 0, 0}, v[4] = {0, 0, 0, 0};
+                quads[id[k]]->gp->test1(xt, m, v);
+                for (int j = 0; j < 1 + DIM; ++j) { r[j] = m[j]; r[4 + j] = v[j]; }
+            }
+        }
+    }
+}
+}  // namespace
 
 extern "C" {
 
@@ -171,6 +252,35 @@ int orc_ongpis_predict(int dim, float scale, const float* pos, const float* grad
     int nc = 1 + dim;
     for (int i = 0; i < nq; ++i) gp.test1(xq + (size_t)dim * i, out + (size_t)2 * nc * i, out + (size_t)2 * nc * i + nc);
     return gp.K;
+}
+
+// ---- K5 reference support (tests/k5_ref.py) -----------------------------------
+// The order std::sort gives candidate indices under the maps' comparator (GPisMap3.cpp:826-829): for each query i the keys
+// keys[off[i] .. off[i+1]) are its squared distances in traversal order, perm (same layout) receives the sorted indices.
+void orc_sort_perm(const float* keys, const long long* off, int nq, int* perm) {
+    for (int i = 0; i < nq; ++i) {
+        const float* k = keys + off[i];
+        int* p = perm + off[i];
+        const int n = (int)(off[i + 1] - off[i]);
+        for (int j = 0; j < n; ++j) p[j] = j;
+        if (n > 1) std::sort(p, p + n, [&](int a, int b) { return k[a] < k[b]; });
+    }
+}
+
+int orc3_k5_table(void* h, int cap_cl, float* c, float* lo, float* hi, int* has_gp, int* parent, int cap_anc, float* alo, float* ahi,
+                  int* aparent, int* nanc_out) {
+    return k5_table<3>(((GPisMap3*)h)->t, cap_cl, c, lo, hi, has_gp, parent, cap_anc, alo, ahi, aparent, nanc_out);
+}
+int orc2_k5_table(void* h, int cap_cl, float* c, float* lo, float* hi, int* has_gp, int* parent, int cap_anc, float* alo, float* ahi,
+                  int* aparent, int* nanc_out) {
+    return k5_table<2>(((GPisMap2*)h)->t, cap_cl, c, lo, hi, has_gp, parent, cap_anc, alo, ahi, aparent, nanc_out);
+}
+void orc3_k5_candidates(void* h, const float* x, int n, int maxc, int* count, int* idx, float* rec) {
+    k5_candidates<3>(((GPisMap3*)h)->t, (float)((double)0.025f * 3.0), x, n, maxc, count, idx, rec);   // map3.hpp test_one
+}
+void orc2_k5_candidates(void* h, const float* x, int n, int maxc, int* count, int* idx, float* rec) {
+    auto* m = (GPisMap2*)h;
+    k5_candidates<2>(m->t, (float)((double)m->setting.map_scale_param * 4.0), x, n, maxc, count, idx, rec);              // map2.hpp test_one
 }
 
 }  // extern "C"

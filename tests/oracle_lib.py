@@ -71,8 +71,47 @@ def lib():
         L.orc_matern32_train.argtypes = [C.c_int, C.c_int, fp, ip, C.c_int, C.c_float, fp, fp, fp]
         L.orc_matern32_cross.argtypes = [C.c_int, C.c_int, fp, ip, C.c_int, C.c_float, fp, fp]
         L.orc_ongpis_predict.argtypes = [C.c_int, C.c_float, fp, fp, fp, fp, fp, C.c_int, fp, C.c_int, fp]
+        tab = [C.c_void_p, C.c_int, fp, fp, fp, ip, ip, C.c_int, fp, fp, ip, ip]
+        L.orc3_k5_table.argtypes = tab
+        L.orc2_k5_table.argtypes = tab
+        L.orc3_k5_candidates.argtypes = [C.c_void_p, fp, C.c_int, C.c_int, ip, ip, fp]
+        L.orc2_k5_candidates.argtypes = [C.c_void_p, fp, C.c_int, C.c_int, ip, ip, fp]
+        L.orc_sort_perm.argtypes = [fp, C.POINTER(C.c_longlong), C.c_int, ip]
         _LIB = L
     return _LIB
+
+
+def sort_perm(keys, off):
+    """libstdc++'s std::sort of each query's candidate indices under the maps' comparator (sqdst[a] < sqdst[b]): keys float32,
+    CSR offsets off [nq + 1]; returns the permutation in the same layout."""
+    keys = np.ascontiguousarray(keys, dtype=np.float32)
+    off = np.ascontiguousarray(off, dtype=np.int64)
+    perm = np.zeros(keys.size, dtype=np.int32)
+    lib().orc_sort_perm(_p(keys), _p(off, C.c_longlong), off.size - 1, _p(perm, C.c_int))
+    return perm
+
+
+def _k5_table(fn, h, dim):
+    nanc = C.c_int(0)
+    ncl = fn(h, 0, None, None, None, None, None, 0, None, None, None, C.byref(nanc))
+    na = nanc.value
+    c, lo, hi = (np.zeros((ncl, 3), dtype=np.float32) for _ in range(3))
+    alo, ahi = (np.zeros((na, 3), dtype=np.float32) for _ in range(2))
+    has_gp, parent, ap = np.zeros(ncl, dtype=np.int32), np.zeros(ncl, dtype=np.int32), np.zeros(na, dtype=np.int32)
+    fn(h, ncl, _p(c), _p(lo), _p(hi), _p(has_gp, C.c_int), _p(parent, C.c_int), na, _p(alo), _p(ahi), _p(ap, C.c_int), C.byref(nanc))
+    # (model = the table index where the cell has a trained GP: what the candidates entry reports)
+    return dict(dim=dim, c=c, lo=lo, hi=hi, model=np.where(has_gp > 0, np.arange(ncl), -1).astype(np.int32), parent=parent,
+                anc_lo=alo, anc_hi=ahi, anc_parent=ap)
+
+
+def _k5_candidates(fn, h, dim, x, maxc):
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    n = x.shape[0]
+    count = np.zeros(n, dtype=np.int32)
+    idx = np.zeros((n, maxc), dtype=np.int32)
+    rec = np.zeros((n, 3, 8), dtype=np.float32)
+    fn(h, _p(x), n, maxc, _p(count, C.c_int), _p(idx, C.c_int), _p(rec))
+    return count, idx, rec
 
 
 ARITH_MODES = {"tiled": 0, "natural": 1, "fp64acc": 2, "eigen33": 3}
@@ -181,6 +220,14 @@ class OracleMap3:
     def num_clusters(self):
         return self.L.orc3_num_clusters(self.h)
 
+    def k5_table(self):
+        """The cluster table of test(): every cluster cell in traversal order, boxes, ancestor chains (tests/k5_ref.py)."""
+        return _k5_table(self.L.orc3_k5_table, self.h, 3)
+
+    def k5_candidates(self, x, maxc=3):
+        """(count [n], sorted table indices [n, maxc], test1 records [n, 3, 8]) as test_one finds them."""
+        return _k5_candidates(self.L.orc3_k5_candidates, self.h, 3, x, maxc)
+
     def cluster_samples(self, i):
         """Training set of the i-th trained cluster (traversal order): [n, 9] pos3 grad3 val sigx sigg, or None."""
         n = self.L.orc3_cluster_samples(self.h, i, None, 0)
@@ -254,6 +301,12 @@ class OracleMap2:
         n = self.L.orc2_retrain_all(self.h)
         set_arith_mode("tiled")
         return n
+
+    def k5_table(self):
+        return _k5_table(self.L.orc2_k5_table, self.h, 2)
+
+    def k5_candidates(self, x, maxc=3):
+        return _k5_candidates(self.L.orc2_k5_candidates, self.h, 2, x, maxc)
 
     def nodes(self):
         n = self.L.orc2_get_nodes(self.h, None, 0)
