@@ -49,6 +49,11 @@ class gpis_plan_opts(C.Structure):
                 ("max_rounds", C.c_int)]
 
 
+class gpis_traj_opts(C.Structure):
+    _fields_ = [("clearance", C.c_float), ("margin", C.c_float), ("w_smooth", C.c_float), ("w_obs", C.c_float),
+                ("rate", C.c_float), ("max_move", C.c_float), ("tol", C.c_float), ("iters", C.c_int), ("sub", C.c_int)]
+
+
 def _p(a, t=C.c_float):
     return a.ctypes.data_as(C.POINTER(t))
 
@@ -228,6 +233,18 @@ def lib():
         L.gpis_plan_path_counts.argtypes = [vp, ll, ll]
         L.gpis_plan_get_paths.argtypes = [vp, ll, fp, fp, ub]
         L.gpis_plan_set_schedule.argtypes = [vp, C.c_int, C.c_int]
+    if hasattr(L, "gpis_traj_create"):
+        ub = C.POINTER(C.c_ubyte)
+        L.gpis_traj_default_opts.argtypes = [C.c_int, C.c_float, C.POINTER(gpis_traj_opts)]
+        L.gpis_traj_create.restype = vp
+        L.gpis_traj_create.argtypes = []
+        L.gpis_traj_destroy.argtypes = [vp]
+        L.gpis_traj_from_paths.argtypes = [vp, vp, C.c_int]
+        L.gpis_traj_set.argtypes = [vp, fp, C.c_int, C.c_int, C.c_int]
+        L.gpis_traj_optimize.argtypes = [vp, vp, C.POINTER(gpis_traj_opts), vp]
+        L.gpis_traj_info.argtypes = [vp, dp, C.c_int]
+        L.gpis_traj_get.argtypes = [vp, fp, ub, ip, fp, fp, fp, fp, ip, ub]
+        L.gpis_traj_device.argtypes = [vp, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
     _lib = L
     return L
 
@@ -967,6 +984,24 @@ class DistanceField:
             self._planner = Planner()
         return self._planner
 
+    def smooth(self, x_or_planner, N=64, trajectories=None, stream=0, **opts):
+        """Trajectories through this field (gpis_traj_*): the last paths of a Planner resampled to N waypoints each, or the
+        caller's waypoints [m, N, dim], run through the covariant gradient descent and evaluated.  opts: the gpis_traj_opts
+        fields (clearance, margin, w_smooth, w_obs, rate, max_move, tol, iters, sub; defaults for this field's step);
+        iters=0 is the collision check alone.  Returns the Trajectories holding the result (default: one kept by this field);
+        it stays valid when the field is recomputed."""
+        t = trajectories if trajectories is not None else self._own_trajectories()
+        if isinstance(x_or_planner, Planner):
+            t.from_paths(x_or_planner, N)
+        else:
+            t.set(x_or_planner)
+        return t.optimize(self, stream=stream, **opts)
+
+    def _own_trajectories(self):
+        if getattr(self, "_trajectories", None) is None:
+            self._trajectories = Trajectories()
+        return self._trajectories
+
     def _step(self):
         inf = self.info()
         if inf["dim"] == 0:
@@ -1100,6 +1135,101 @@ class Planner:
         _check(self.L.gpis_plan_get_paths(self.h, _p(off, C.c_longlong), _p(pts), _p(sc), _p(st, C.c_ubyte)), "gpis_plan_get_paths")
         self.last_off = off
         return [pts[off[k]:off[k + 1]] for k in range(m.value)], sc, st
+
+    def trajectories(self, N=64, trajectories=None):
+        """The last paths() resampled by arc length to N waypoints each (gpis_traj_from_paths).  Returns the Trajectories
+        holding the input (default: a new one), ready for optimize()."""
+        t = trajectories if trajectories is not None else Trajectories()
+        return t.from_paths(self, N)
+
+
+def traj_opts(dim, step, **opts):
+    """gpis_traj_opts of the library's defaults for `dim` and a field of lattice step `step` (gpis_traj_default_opts) with the
+    given fields replaced."""
+    o = gpis_traj_opts()
+    _check(lib().gpis_traj_default_opts(int(dim), float(step), C.byref(o)), "gpis_traj_default_opts")
+    names = {f[0] for f in gpis_traj_opts._fields_}
+    for k, v in opts.items():
+        if k not in names:
+            raise GpisError("unknown trajectory option %r" % k)
+        setattr(o, k, v)
+    return o
+
+
+class Trajectories:
+    """Input and result holder of the trajectory optimiser (gpis_traj_*): a batch of m trajectories of N waypoints on the
+    device, buffers reused across calls.  optimize() always starts from the input; a result does not depend on the field or the
+    planner it came from."""
+
+    INFO_KEYS = ("input", "valid", "m", "N", "dim", "ms")
+    INT_KEYS = ("input", "valid", "m", "N", "dim")
+
+    def __init__(self):
+        self.L = lib()
+        if self.L.gpis_device_count() < 1:
+            raise GpisError("no HIP device: gpismap_amd has no CPU fallback")
+        self.h = C.c_void_p(self.L.gpis_traj_create())
+        if not self.h:
+            raise GpisError("gpis_traj_create failed")
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.gpis_traj_destroy(self.h)
+            self.h = None
+
+    __del__ = close
+
+    def from_paths(self, planner, N=64):
+        """The input from the planner's last paths() resampled by arc length to N waypoints each (gpis_traj_from_paths); a
+        path of another status than 0 gives a trajectory of status 2.  Returns self."""
+        _check(self.L.gpis_traj_from_paths(self.h, planner.h, int(N)), "gpis_traj_from_paths")
+        return self
+
+    def set(self, x):
+        """The input from waypoints x [m, N, dim] (gpis_traj_set).  Returns self."""
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        if x.ndim != 3:
+            raise GpisError("waypoints must be [m, N, dim]")
+        _check(self.L.gpis_traj_set(self.h, _p(x), x.shape[0], x.shape[1], x.shape[2]), "gpis_traj_set")
+        return self
+
+    def optimize(self, field, stream=0, **opts):
+        """gpis_traj_optimize on a DistanceField holding a result.  Returns self."""
+        inf = field.info()
+        if inf["dim"] == 0:
+            raise GpisError("distance field holds no result")
+        o = traj_opts(inf["dim"], inf["step"], **opts)
+        _check(self.L.gpis_traj_optimize(self.h, field.h, C.byref(o), C.c_void_p(stream)), "gpis_traj_optimize")
+        return self
+
+    def info(self):
+        out = np.zeros(len(self.INFO_KEYS), dtype=np.float64)
+        _check(self.L.gpis_traj_info(self.h, _p(out, C.c_double), out.size), "gpis_traj_info")
+        d = dict(zip(self.INFO_KEYS, out.tolist()))
+        for k in self.INT_KEYS:
+            d[k] = int(d[k])
+        return d
+
+    def get(self):
+        """dict of host copies of the last result: x [m, N, dim] f32, status [m] u8 (0 stopped by tol, 1 iteration cap, 2 no
+        input), iterations [m] i32, length, smooth, obstacle, min_dist [m] f32, nonfinite [m] i32, collides [m] u8."""
+        i = self.info()
+        if not i["valid"]:
+            raise GpisError("trajectories hold no result")
+        m = i["m"]
+        r = dict(x=np.zeros((m, i["N"], i["dim"]), np.float32), status=np.zeros(m, np.uint8), iterations=np.zeros(m, np.int32),
+                 length=np.zeros(m, np.float32), smooth=np.zeros(m, np.float32), obstacle=np.zeros(m, np.float32),
+                 min_dist=np.zeros(m, np.float32), nonfinite=np.zeros(m, np.int32), collides=np.zeros(m, np.uint8))
+        _check(self.L.gpis_traj_get(self.h, _p(r["x"]), _p(r["status"], C.c_ubyte), _p(r["iterations"], C.c_int), _p(r["length"]),
+                                    _p(r["smooth"]), _p(r["obstacle"]), _p(r["min_dist"]), _p(r["nonfinite"], C.c_int),
+                                    _p(r["collides"], C.c_ubyte)), "gpis_traj_get")
+        return r
+
+    def device_ptrs(self):
+        """(d_x, d_fres, d_ires) device addresses of the last result (0 where there is none)."""
+        a, b, c = C.c_void_p(0), C.c_void_p(0), C.c_void_p(0)
+        _check(self.L.gpis_traj_device(self.h, C.byref(a), C.byref(b), C.byref(c)), "gpis_traj_device")
+        return a.value or 0, b.value or 0, c.value or 0
 
 
 def render_field_opts(dim, step, **opts):

@@ -13,6 +13,7 @@
 #include "render.h"
 #include "track.h"
 #include "plan.h"
+#include "traj.h"
 #include "obsgp.h"
 #include "ongpis.h"
 
@@ -859,6 +860,100 @@ int gpis_plan_get_paths(void* plan, long long* off, float* points, float* start_
     if (start_cost) GPIS_HIP(hipMemcpyAsync(start_cost, p.d_scost, sizeof(float) * m, hipMemcpyDeviceToHost, p.own));
     if (status) GPIS_HIP(hipMemcpyAsync(status, p.d_status, m, hipMemcpyDeviceToHost, p.own));
     GPIS_HIP(hipStreamSynchronize(p.own));
+    return GPIS_OK;
+}
+
+// ---- trajectories through a distance field -----------------------------------------------------------------------------------
+int gpis_traj_default_opts(int dim, float step, gpis_traj_opts* o) {
+    if (!o || (dim != 2 && dim != 3) || !(std::isfinite(step) && step > 0.f)) return GPIS_ERR_ARG;
+    o->clearance = 0.f; o->margin = 3.f * step; o->w_smooth = 1.f; o->w_obs = 0.25f * step; o->rate = 0.02f;
+    o->max_move = 0.5f * step; o->tol = 0.01f * step; o->iters = 100; o->sub = 3;
+    return GPIS_OK;
+}
+void* gpis_traj_create(void) {
+    if (gpis_device_count() < 1) { fprintf(stderr, "[gpismap_amd] no HIP device\n"); return nullptr; }
+    Trajectories* t = new (std::nothrow) Trajectories();
+    if (t && !t->own) { delete t; return nullptr; }
+    return t;
+}
+void gpis_traj_destroy(void* traj) { delete (Trajectories*)traj; }
+// Trajectories::from_paths and ::set check their arguments and the planner's state before they drop anything, so such an error
+// leaves the previous input and result readable; a failure after that leaves the handle without input.
+int gpis_traj_from_paths(void* traj, void* plan, int N) {
+    if (!traj || !plan) return GPIS_ERR_ARG;
+    Trajectories& t = *(Trajectories*)traj;
+    const Planner& p = *(const Planner*)plan;
+    DeviceScope ds(p.device);
+    try { return t.from_paths(p, N); } catch (...) { t.has_input = t.valid = false; return GPIS_ERR_STATE; }
+}
+int gpis_traj_set(void* traj, const float* x, int m, int N, int dim) {
+    if (!traj) return GPIS_ERR_ARG;
+    Trajectories& t = *(Trajectories*)traj;
+    DeviceScope ds(t.device);
+    try { return t.set(x, m, N, dim); } catch (...) { t.has_input = t.valid = false; return GPIS_ERR_STATE; }
+}
+int gpis_traj_optimize(void* traj, void* d, const gpis_traj_opts* opts, void* stream) {
+    if (!traj || !d) return GPIS_ERR_ARG;
+    Trajectories& t = *(Trajectories*)traj;
+    const DistanceField& df = *(const DistanceField*)d;
+    gpis_traj_opts dflt;
+    if (!opts) {
+        if (!df.valid) return GPIS_ERR_STATE;
+        (void)gpis_traj_default_opts(df.dim, df.step, &dflt);
+        opts = &dflt;
+    }
+    TrajOpts o;
+    o.clearance = opts->clearance; o.margin = opts->margin; o.w_smooth = opts->w_smooth; o.w_obs = opts->w_obs; o.rate = opts->rate;
+    o.max_move = opts->max_move; o.tol = opts->tol; o.iters = opts->iters; o.sub = opts->sub;
+    DeviceScope ds(df.device);
+    try { return t.optimize(df, o, stream ? (hipStream_t)stream : df.own); } catch (...) { t.valid = false; return GPIS_ERR_STATE; }
+}
+int gpis_traj_info(void* traj, double* out, int n) {
+    if (!traj || !out || n < 0) return GPIS_ERR_ARG;
+    const Trajectories& t = *(const Trajectories*)traj;
+    const bool h = t.has_input;
+    const double w[6] = {h ? 1.0 : 0.0, t.valid ? 1.0 : 0.0, h ? (double)t.m : 0.0, h ? (double)t.N : 0.0, h ? (double)t.dim : 0.0,
+                         t.valid ? t.opt_ms : 0.0};
+    for (int i = 0; i < n && i < 6; ++i) out[i] = w[i];
+    return GPIS_OK;
+}
+int gpis_traj_get(void* traj, float* x, unsigned char* status, int* iterations, float* length, float* smooth, float* obstacle,
+                  float* min_dist, int* nonfinite, unsigned char* collides) {
+    if (!traj) return GPIS_ERR_ARG;
+    Trajectories& t = *(Trajectories*)traj;
+    if (!t.valid) return GPIS_ERR_STATE;
+    DeviceScope ds(t.device);
+    const size_t m = (size_t)t.m;
+    std::vector<float> fr;
+    std::vector<int> ir;
+    if (x) GPIS_HIP(hipMemcpyAsync(x, t.d_x, sizeof(float) * m * t.N * t.dim, hipMemcpyDeviceToHost, t.own));
+    if (length || smooth || obstacle || min_dist) {
+        fr.resize(4 * m);
+        GPIS_HIP(hipMemcpyAsync(fr.data(), t.d_fres, sizeof(float) * 4 * m, hipMemcpyDeviceToHost, t.own));
+    }
+    if (status || iterations || nonfinite || collides) {
+        ir.resize(4 * m);
+        GPIS_HIP(hipMemcpyAsync(ir.data(), t.d_ires, sizeof(int) * 4 * m, hipMemcpyDeviceToHost, t.own));
+    }
+    GPIS_HIP(hipStreamSynchronize(t.own));
+    for (size_t k = 0; k < m; ++k) {
+        if (length) length[k] = fr[4 * k];
+        if (smooth) smooth[k] = fr[4 * k + 1];
+        if (obstacle) obstacle[k] = fr[4 * k + 2];
+        if (min_dist) min_dist[k] = fr[4 * k + 3];
+        if (status) status[k] = (unsigned char)ir[4 * k];
+        if (iterations) iterations[k] = ir[4 * k + 1];
+        if (nonfinite) nonfinite[k] = ir[4 * k + 2];
+        if (collides) collides[k] = (unsigned char)ir[4 * k + 3];
+    }
+    return GPIS_OK;
+}
+int gpis_traj_device(void* traj, const float** d_x, const float** d_fres, const int** d_ires) {
+    if (!traj) return GPIS_ERR_ARG;
+    const Trajectories& t = *(const Trajectories*)traj;
+    if (d_x) *d_x = t.valid ? t.d_x : nullptr;
+    if (d_fres) *d_fres = t.valid ? t.d_fres : nullptr;
+    if (d_ires) *d_ires = t.valid ? t.d_ires : nullptr;
     return GPIS_OK;
 }
 

@@ -619,6 +619,75 @@ int   gpis_plan_get_paths(void* plan, long long* off, float* points, float* star
  * relaxation sweeps of a tile per outer round (0 = 256) */
 int   gpis_plan_set_schedule(void* plan, int check_every, int inner_cap);
 
+/* ---- trajectories: planned paths smoothed into clearance-keeping trajectories on the device --------------
+ * A batch of m trajectories of N waypoints x_0 .. x_{N-1} (dim 2 or 3, 3 <= N <= 256), x[(t N + i) dim + a]; x_0 and x_{N-1}
+ * never move, n = N - 2 interior points.  Everything is float32 without FMA and every sum has one order (tests/traj_ref.py
+ * states it in numpy), so the bits are the same on every run, stream and batch composition.
+ * Input, either of
+ *  - gpis_traj_from_paths: every path Q_0 .. Q_{L-1} of the planner's last gpis_plan_paths resampled by arc length:
+ *    s_0 = 0, s_k = s_{k-1} + |Q_k - Q_{k-1}| (serial; the norm is sqrtf of squares summed left to right),
+ *    t_i = (float)i * (s_{L-1} / (float)(N - 1)), k = the largest index <= L - 2 with s_k <= t_i, w = (t_i - s_k) / (s_{k+1} -
+ *    s_k), x_i = Q_k + w (Q_{k+1} - Q_k); x_0 = Q_0 and x_{N-1} = Q_{L-1} are copies; L = 1: N copies of Q_0.  A path of any
+ *    status but 0 gives no input: NaN waypoints, status 2;
+ *  - gpis_traj_set: host waypoints [m][N][dim]; a trajectory with a non-finite coordinate has status 2 and is returned untouched.
+ * gpis_traj_optimize always starts from the input (it may be called again with other options or another field) and runs up to
+ * `iters` iterations on every trajectory with an input, each independent of the others:
+ *  1. (d_i, grad_i) = gpis_dfield_sample's interpolant at x_i, e_i = d_i - clearance.  d_i or a gradient component non-finite
+ *     (outside the lattice, a field without sites, +-inf corners): q_i = 0 and grad_i is taken as 0 -- unknown space is free,
+ *     as for the planner.  Else q_i = 0 if e_i >= margin, (e_i - margin) / margin if e_i >= 0, else -1; the matching point cost
+ *     c_i is 0, ((e_i - margin) * (e_i - margin)) / (2.f * margin), or 0.5f * margin - e_i.
+ *  2. a_i = (x_i - x_{i-1}) + (x_i - x_{i+1}), g_i = w_smooth * a_i + w_obs * (q_i * grad_i), per coordinate.
+ *  3. delta = inverse(tridiag(-1, 2, -1)) g in closed form: delta_i = (sum over ascending j = 1 .. n, from 0.f, of
+ *     (float)(min(i, j) * (n + 1 - max(i, j))) * g_j) / (float)(n + 1).
+ *  4. r_i = sqrtf of delta_i's squares summed left to right, R = max r_i; kappa = rate if rate * R <= max_move, else
+ *     max_move / R; x_i <- x_i - kappa * delta_i.  The max keeps a NaN: finite waypoints whose a_i or metric row overflows
+ *     (inf - inf) end as NaN waypoints with status 1, never as "converged".
+ *  5. fl(kappa * R) < tol: done, status 0.  After `iters` iterations without that (also iters = 0): status 1.
+ * Evaluation (after the loop; alone with iters = 0): length = sum |x_{i+1} - x_i|, smooth = sum |x_{i+1} - x_i|^2, obstacle =
+ * sum of c_i over the interior points, min_dist = the smallest finite sampled distance over every waypoint and over the `sub`
+ * points x_i + ((float)s / (float)(sub + 1)) * (x_{i+1} - x_i), s = 1 .. sub, of every segment (+inf if none is finite),
+ * nonfinite = the number of those samples whose distance is not finite, collides = min_dist < clearance.  Sums: the values
+ * padded with 0 to 256, then for h = 128, 64, .., 1: v[k] += v[k + h] for k < h.  A trajectory of status 2 has iterations 0,
+ * NaN length, smooth, obstacle and min_dist, nonfinite 0 and collides 0.
+ * The optimiser owns its buffers (grow-only, reused), moves to the planner's (from_paths) or the field's (optimize) device
+ * with its input, reads dist only during gpis_traj_optimize and returns with its work finished: a result outlives its field
+ * and its planner.  hip_stream NULL: the field's own stream.  A new input drops the result.
+ * Errors: a NULL handle, planner, field or x, N outside [3, 256], m < 1, dim outside {2, 3}, a field of another dim than the
+ * input, iters < 0, sub < 0 or > 16, a non-finite or negative w_smooth, w_obs, rate, max_move or tol, margin <= 0 or
+ * non-finite, a non-finite clearance -> GPIS_ERR_ARG; a field without a result, a planner without paths, optimize without an
+ * input, getters without a result -> GPIS_ERR_STATE; more than 2^20 trajectories -> GPIS_ERR_LIMIT: all with the previous
+ * input and result untouched.  Any other failure leaves no result. */
+typedef struct gpis_traj_opts {
+    float clearance;            /* a sample collides iff its distance < clearance */
+    float margin;               /* the obstacle term acts where distance - clearance < margin; > 0 */
+    float w_smooth, w_obs;      /* weights of the smoothness and the obstacle gradient */
+    float rate;                 /* step length along the covariant gradient */
+    float max_move;             /* trust region: the largest move of a waypoint in one iteration */
+    float tol;                  /* stop once the largest move of an iteration falls below */
+    int iters;                  /* iteration cap; 0: evaluation alone */
+    int sub;                    /* evaluation points inside every segment, 0 .. 16 */
+} gpis_traj_opts;
+/* clearance 0, margin 3 * step, w_smooth 1, w_obs 0.25 * step, rate 0.02, max_move 0.5 * step, tol 0.01 * step, iters 100,
+ * sub 3.  dim outside {2, 3}, a step that is not finite and positive, NULL opts -> GPIS_ERR_ARG.  Needs no device. */
+int   gpis_traj_default_opts(int dim, float step, gpis_traj_opts* opts);
+void* gpis_traj_create(void);                              /* on the current device; NULL without one */
+void  gpis_traj_destroy(void* traj);
+/* the input from the planner's last paths, N waypoints each; the planner's data is read during the call only */
+int   gpis_traj_from_paths(void* traj, void* plan, int N);
+/* the input from host waypoints x[m][N][dim] */
+int   gpis_traj_set(void* traj, const float* x, int m, int N, int dim);
+/* opts NULL: the defaults for the field's step */
+int   gpis_traj_optimize(void* traj, void* df, const gpis_traj_opts* opts, void* hip_stream);
+/* out[0..n): 1 if an input is held, 1 if a result is held, m, N, dim, ms of host wall time in the last optimize (6 values) */
+int   gpis_traj_info(void* traj, double* out, int n);
+/* host copies of the last result: x[m][N][dim], and per trajectory status (0 stopped by tol, 1 iteration cap, 2 no input),
+ * iterations used, length, smooth, obstacle, min_dist, nonfinite, collides; any may be NULL */
+int   gpis_traj_get(void* traj, float* x, unsigned char* status, int* iterations, float* length, float* smooth, float* obstacle,
+                    float* min_dist, int* nonfinite, unsigned char* collides);
+/* device pointers of the last result, valid until the next input, optimize or gpis_traj_destroy (NULL where there is none):
+ * d_x[m][N][dim]; d_fres[m][4] = length, smooth, obstacle, min_dist; d_ires[m][4] = status, iterations, nonfinite, collides */
+int   gpis_traj_device(void* traj, const float** d_x, const float** d_fres, const int** d_ires);
+
 #ifdef __cplusplus
 }
 #endif
