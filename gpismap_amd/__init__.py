@@ -44,6 +44,10 @@ class gpis_track_opts(C.Structure):
                 ("max_iters", C.c_int), ("min_inliers", C.c_int)]
 
 
+class gpis_locate_opts(C.Structure):
+    _fields_ = [("max_residual", C.c_double), ("stride", C.c_int), ("top_k", C.c_int)]
+
+
 class gpis_plan_opts(C.Structure):
     _fields_ = [("clearance", C.c_float), ("margin", C.c_float), ("gain", C.c_float), ("connectivity", C.c_int),
                 ("max_rounds", C.c_int)]
@@ -245,6 +249,17 @@ def lib():
         L.gpis_traj_info.argtypes = [vp, dp, C.c_int]
         L.gpis_traj_get.argtypes = [vp, fp, ub, ip, fp, fp, fp, fp, ip, ub]
         L.gpis_traj_device.argtypes = [vp, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
+    if hasattr(L, "gpis_locate_create"):
+        lo = C.POINTER(gpis_locate_opts)
+        L.gpis_locate_default_opts.argtypes = [C.c_int, lo]
+        L.gpis_locate_create.restype = vp
+        L.gpis_locate_create.argtypes = []
+        L.gpis_locate_destroy.argtypes = [vp]
+        L.gpis3_locate_depth_field.argtypes = [vp, vp, vp, C.POINTER(gpis_cam), fp, fp, C.c_int, lo, vp]
+        L.gpis2_locate_scan_field.argtypes = [vp, vp, vp, fp, fp, C.c_int, fp, fp, C.c_int, lo, vp]
+        L.gpis_locate_get.argtypes = [vp, dp, ip, ip]
+        L.gpis_locate_info.argtypes = [vp, dp, C.c_int]
+        L.gpis_locate_device.argtypes = [vp, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
     _lib = L
     return L
 
@@ -565,6 +580,15 @@ class GPisMap3:
         read (the field's level is zero; its gate was applied when it was built).  Returns (pose, info) as track_depth."""
         return field._track_depth(self.h, self._wh, depth, pose0, cam6, tracker, opts)
 
+    def score_depth_field(self, field, depth, poses, cam6=None, locator=None, **opts):
+        """DistanceField.score_depth with this map's camera when cam6 is None (gpis3_locate_depth_field); nothing else of the
+        map is read."""
+        return field._score_depth(self.h, self._wh, depth, poses, cam6, locator, opts)
+
+    def locate_depth_field(self, field, depth, poses, cam6=None, refine=8, track=None, **opts):
+        """DistanceField.locate_depth with this map's camera when cam6 is None."""
+        return field._locate(3, (self.h, self._wh, depth, cam6), poses, refine, track, opts)
+
     def render_depth_field(self, field, pose, cam6=None, renderer=None, **opts):
         """render_depth from a DistanceField instead of the map (gpis3_render_depth_field): sphere tracing through the field's
         sampler, one fused kernel.  cam6 None = this map's camera; nothing else of the map is read.  Returns (depth [W*H],
@@ -701,6 +725,14 @@ class GPisMap:
         """track_scan against a DistanceField instead of the map (gpis2_track_scan_field), with this map's sensor offset;
         opts and the result as GPisMap3.track_depth_field."""
         return field._track_scan(self.h, thetas, ranges, pose0, None, tracker, opts)
+
+    def score_scan_field(self, field, thetas, ranges, poses, locator=None, **opts):
+        """DistanceField.score_scan with this map's sensor offset (gpis2_locate_scan_field); nothing else of the map is read."""
+        return field._score_scan(self.h, thetas, ranges, poses, None, locator, opts)
+
+    def locate_scan_field(self, field, thetas, ranges, poses, refine=8, track=None, **opts):
+        """DistanceField.locate_scan with this map's sensor offset."""
+        return field._locate(2, (self.h, thetas, ranges, None), poses, refine, track, opts)
 
     def render_scan_field(self, field, thetas, pose6, renderer=None, **opts):
         """render_scan from a DistanceField instead of the map (gpis2_render_scan_field), with this map's sensor offset;
@@ -950,6 +982,98 @@ class DistanceField:
                                              _p(off) if off is not None else None, _p(pose0), C.byref(o), _p(out), None),
                "gpis2_track_scan_field")
         return out, t.result()
+
+    def score_depth(self, depth, poses, cam6, locator=None, **opts):
+        """Which of `poses` [m, 12] (float32 [t(3), R(9)]) explains `depth` against this field (gpis3_locate_depth_field without
+        a map): per pose the truncated sum of squared field distances of the tracker's points, one wavefront per pose in one
+        kernel.  Returns (cost [m] f64, inliers [m] i32, order [min(top_k, m)] i32: cost ascending, ties by the lower index).
+        opts: the gpis_locate_opts fields (max_residual, stride, top_k; top_k=0 ranks all).  locator: a Locator to hold the
+        device result (default: one kept by this field)."""
+        return self._score_depth(None, None, depth, poses, cam6, locator, opts)
+
+    def score_scan(self, thetas, ranges, poses, off2, locator=None, **opts):
+        """Which of `poses` [m, 6] (float32 [t(2), R(4)]) explains the scan against this field (gpis2_locate_scan_field without a
+        map); off2: the sensor offset (x, y) in the laser frame.  Returns (cost, inliers, order) as score_depth."""
+        return self._score_scan(None, thetas, ranges, poses, off2, locator, opts)
+
+    def locate_depth(self, depth, poses, cam6, refine=8, track=None, **opts):
+        """Locate and refine: score `poses` (score_depth with opts), run the field tracker (track_depth with the options in
+        `track`) from each of the first `refine` ranked poses, score the refined poses in a second call with the same options
+        and return the one of the lowest cost (ties: the better first rank).  Returns (pose [12] f32, info): info holds the
+        first ranking ("cost", "inliers", "order"), "candidates" (the ranked indices refined), "tracks" (their tracker infos),
+        "refined" [r, 12], "refined_cost", "refined_inliers" and "best" (the index into the candidates).  refine=0 returns the
+        best-ranked pose itself."""
+        return self._locate(3, (None, None, depth, cam6), poses, refine, track, opts)
+
+    def locate_scan(self, thetas, ranges, poses, off2, refine=8, track=None, **opts):
+        """locate_depth for a laser scan: score_scan, track_scan from the first `refine` ranked poses, score_scan again."""
+        return self._locate(2, (None, thetas, ranges, off2), poses, refine, track, opts)
+
+    def _own_locator(self):
+        if getattr(self, "_locator", None) is None:
+            self._locator = Locator()
+        return self._locator
+
+    def _score_depth(self, map_h, map_wh, depth, poses, cam6, locator, opts):
+        depth = np.ascontiguousarray(depth, dtype=np.float32).ravel()
+        poses = np.ascontiguousarray(poses, dtype=np.float32)
+        if poses.size == 0 or poses.size % 12:
+            raise GpisError("poses must be [m, 12] with m >= 1")
+        if cam6 is None and map_h is None:
+            raise GpisError("a field-only score_depth needs cam6")
+        w, h = (int(cam6[4]), int(cam6[5])) if cam6 is not None else map_wh
+        if depth.size != w * h:
+            raise GpisError("depth must have width * height = %d elements" % (w * h))
+        l = locator if locator is not None else self._own_locator()
+        o = locate_opts(3, **opts)
+        cam = C.byref(_cam(cam6)) if cam6 is not None else None
+        _check(self.L.gpis3_locate_depth_field(map_h, self.h, l.h, cam, _p(depth), _p(poses), poses.size // 12, C.byref(o), None),
+               "gpis3_locate_depth_field")
+        return l.get()
+
+    def _score_scan(self, map_h, thetas, ranges, poses, off2, locator, opts):
+        thetas = np.ascontiguousarray(thetas, dtype=np.float32).ravel()
+        ranges = np.ascontiguousarray(ranges, dtype=np.float32).ravel()
+        poses = np.ascontiguousarray(poses, dtype=np.float32)
+        if poses.size == 0 or poses.size % 6 or thetas.size != ranges.size:
+            raise GpisError("bad 2-D score arguments")
+        off = np.ascontiguousarray(off2, dtype=np.float32).ravel() if off2 is not None else None
+        if off is not None and off.size != 2:
+            raise GpisError("off2 must have 2 elements")
+        if off is None and map_h is None:
+            raise GpisError("a field-only score_scan needs off2")
+        l = locator if locator is not None else self._own_locator()
+        o = locate_opts(2, **opts)
+        _check(self.L.gpis2_locate_scan_field(map_h, self.h, l.h, _p(thetas), _p(ranges), thetas.size,
+                                              _p(off) if off is not None else None, _p(poses), poses.size // 6, C.byref(o), None),
+               "gpis2_locate_scan_field")
+        return l.get()
+
+    def _locate(self, dim, frame, poses, refine, track, opts):
+        np_ = 12 if dim == 3 else 6
+        poses = np.ascontiguousarray(poses, dtype=np.float32).reshape(-1, np_)
+        if dim == 3:
+            map_h, map_wh, depth, cam6 = frame
+            score = lambda P: self._score_depth(map_h, map_wh, depth, P, cam6, None, opts)
+            polish = lambda P: self._track_depth(map_h, map_wh, depth, P, cam6, None, dict(track or {}))
+        else:
+            map_h, thetas, ranges, off2 = frame
+            score = lambda P: self._score_scan(map_h, thetas, ranges, P, off2, None, opts)
+            polish = lambda P: self._track_scan(map_h, thetas, ranges, P, off2, None, dict(track or {}))
+        cost, inliers, order = score(poses)
+        cand = order[:max(0, int(refine))]
+        info = dict(cost=cost, inliers=inliers, order=order, candidates=cand, tracks=[], refined=None, refined_cost=None,
+                    refined_inliers=None, best=0)
+        if cand.size == 0:
+            return poses[order[0]].copy(), info
+        refined = np.zeros((cand.size, np_), np.float32)
+        for k, i in enumerate(cand):
+            refined[k], t = polish(poses[i])
+            info["tracks"].append(t)
+        c2, n2, _ = score(refined)
+        best = int(np.argmin(c2))                       # (the first of equal costs: the better first rank)
+        info.update(refined=refined, refined_cost=c2, refined_inliers=n2, best=best)
+        return refined[best].copy(), info
 
     def render_depth(self, pose, cam6, renderer=None, **opts):
         """What a depth camera at `pose` would see of this field (gpis3_render_depth_field without a map): every ray sphere-traced
@@ -1313,6 +1437,96 @@ class Renderer:
         a, b, c = C.c_void_p(0), C.c_void_p(0), C.c_void_p(0)
         _check(self.L.gpis_render_device(self.h, C.byref(a), C.byref(b), C.byref(c)), "gpis_render_device")
         return a.value or 0, b.value or 0, c.value or 0
+
+
+def locate_opts(dim, **opts):
+    """gpis_locate_opts of the library's defaults for `dim` (gpis_locate_default_opts) with the given fields replaced."""
+    o = gpis_locate_opts()
+    _check(lib().gpis_locate_default_opts(int(dim), C.byref(o)), "gpis_locate_default_opts")
+    names = {f[0] for f in gpis_locate_opts._fields_}
+    for k, v in opts.items():
+        if k not in names:
+            raise GpisError("unknown locate option %r" % k)
+        setattr(o, k, v)
+    return o
+
+
+class Locator:
+    """Result holder of the pose scorer (gpis_locate_*): device buffers reused across calls."""
+
+    INFO_KEYS = ("held", "dim", "poses", "points", "ranked", "pixels", "ms")
+    INT_KEYS = ("held", "dim", "poses", "points", "ranked", "pixels")
+
+    def __init__(self):
+        self.L = lib()
+        if self.L.gpis_device_count() < 1:
+            raise GpisError("no HIP device: gpismap_amd has no CPU fallback")
+        self.h = C.c_void_p(self.L.gpis_locate_create())
+        if not self.h:
+            raise GpisError("gpis_locate_create failed")
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.gpis_locate_destroy(self.h)
+            self.h = None
+
+    __del__ = close
+
+    def info(self):
+        out = np.zeros(len(self.INFO_KEYS), dtype=np.float64)
+        _check(self.L.gpis_locate_info(self.h, _p(out, C.c_double), out.size), "gpis_locate_info")
+        d = dict(zip(self.INFO_KEYS, out.tolist()))
+        for k in self.INT_KEYS:
+            d[k] = int(d[k])
+        return d
+
+    def get(self):
+        """(cost [m] f64, inliers [m] i32, order [ranked] i32) of the last call."""
+        i = self.info()
+        if not i["held"]:
+            raise GpisError("locator holds no result")
+        cost = np.zeros(i["poses"], dtype=np.float64)
+        inliers = np.zeros(i["poses"], dtype=np.int32)
+        order = np.zeros(i["ranked"], dtype=np.int32)
+        _check(self.L.gpis_locate_get(self.h, _p(cost, C.c_double), _p(inliers, C.c_int), _p(order, C.c_int)), "gpis_locate_get")
+        return cost, inliers, order
+
+    def device_ptrs(self):
+        """(d_cost, d_inliers) device addresses of the last result (valid until the next call)."""
+        a, b = C.c_void_p(0), C.c_void_p(0)
+        _check(self.L.gpis_locate_device(self.h, C.byref(a), C.byref(b)), "gpis_locate_device")
+        return a.value or 0, b.value or 0
+
+
+def pose_grid2(xs, ys, thetas):
+    """[m, 6] float32 poses [t(2), R(4)] of every (x, y, angle): the angle is the slowest axis, then y, then x; cos and sin in
+    float64, cast."""
+    xs, ys, th = (np.asarray(v, np.float64).ravel() for v in (xs, ys, thetas))
+    T, Y, X = np.meshgrid(th, ys, xs, indexing="ij")
+    c, s = np.cos(T), np.sin(T)
+    return np.stack([X, Y, c, s, -s, c], axis=-1).reshape(-1, 6).astype(np.float32)
+
+
+def _exp_so3(w):
+    w = np.asarray(w, np.float64)
+    th = float(np.linalg.norm(w))
+    K = np.array([[0.0, -w[2], w[1]], [w[2], 0.0, -w[0]], [-w[1], w[0], 0.0]])
+    if th < 1e-12:
+        return np.eye(3) + K
+    return np.eye(3) + (np.sin(th) / th) * K + ((1.0 - np.cos(th)) / (th * th)) * (K @ K)
+
+
+def pose_grid3(pose12, offsets, rotvecs):
+    """[a b, 12] float32 poses [t(3), R(9)] around pose12: Exp(rotvec) R and t + offset for every offset [a, 3] and rotation
+    vector [b, 3], in float64, cast; the rotation vector is the slowest axis."""
+    P = np.asarray(pose12, np.float64).ravel()
+    t, R = P[:3], P[3:].reshape(3, 3).T
+    off = np.asarray(offsets, np.float64).reshape(-1, 3)
+    out = []
+    for w in np.asarray(rotvecs, np.float64).reshape(-1, 3):
+        Rw = _exp_so3(w) @ R
+        out.append(np.concatenate([t[None, :] + off, np.tile(Rw.T.ravel(), (off.shape[0], 1))], axis=1))
+    return np.concatenate(out, axis=0).astype(np.float32)
 
 
 def track_opts(dim, **opts):

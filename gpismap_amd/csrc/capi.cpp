@@ -12,6 +12,7 @@
 #include "dfield.h"
 #include "render.h"
 #include "track.h"
+#include "locate.h"
 #include "plan.h"
 #include "traj.h"
 #include "obsgp.h"
@@ -1272,6 +1273,107 @@ int gpis_track_info(void* tracker, double* out, int n) {
     const double v[13] = {(double)t.status, (double)t.iterations, (double)t.passes, (double)t.points, t.inliers, t.cost0, t.cost,
                           t.pass_ms, t.k4_ms, t.valid ? 1.0 : 0.0, (double)t.dim, (double)t.pixels, (double)t.evals};
     for (int i = 0; i < n && i < 13; ++i) out[i] = v[i];
+    return GPIS_OK;
+}
+
+// ---- pose-hypothesis scoring against a distance field ---------------------------------------------------------------------
+int gpis_locate_default_opts(int dim, gpis_locate_opts* o) {
+    if (!o || (dim != 2 && dim != 3)) return GPIS_ERR_ARG;
+    if (dim == 3) { o->max_residual = 0.05; o->stride = 8; }
+    else { o->max_residual = 0.5; o->stride = 1; }
+    o->top_k = 16;
+    return GPIS_OK;
+}
+void* gpis_locate_create(void) {
+    if (gpis_device_count() < 1) { fprintf(stderr, "[gpismap_amd] no HIP device\n"); return nullptr; }
+    Locator* l = new (std::nothrow) Locator();
+    if (l && !l->trk.own) { delete l; return nullptr; }
+    return l;
+}
+void gpis_locate_destroy(void* locator) { delete (Locator*)locator; }
+// the checks that need neither the field nor the frame: GPIS_ERR_ARG / GPIS_ERR_LIMIT leave the previous result readable
+static int locate_args(void* locator, int dim, const float* poses, int m, const gpis_locate_opts* opts, LocateOpts* o) {
+    if (!locator || !poses || m < 1) return GPIS_ERR_ARG;
+    gpis_locate_opts d;
+    if (!opts) { (void)gpis_locate_default_opts(dim, &d); opts = &d; }
+    o->max_residual = opts->max_residual; o->stride = opts->stride; o->top_k = opts->top_k;
+    return locate_check_opts(*o);
+}
+// the pose count's limit (before the poses are read), the poses, the field's state and dim, then the call on the field's device
+static int locate_call(void* d, Locator& l, const TrackGeom& g, const float* in, const double* cs, long long n, const float* poses,
+                       int m, const LocateOpts& o, void* stream) {
+    if ((long long)m > Locator::kMaxPoses) return GPIS_ERR_LIMIT;
+    const size_t np = (size_t)(g.dim == 3 ? 12 : 6) * (size_t)m;
+    for (size_t k = 0; k < np; ++k) if (!std::isfinite(poses[k])) return GPIS_ERR_ARG;
+    const DistanceField& df = *(const DistanceField*)d;
+    if (!df.valid) return GPIS_ERR_STATE;
+    if (df.dim != g.dim) return GPIS_ERR_ARG;
+    DeviceScope ds(df.device);
+    try {
+        if (int rc = l.bind(df.device)) { l.clear_result(); return rc; }
+        const int rc = l.score(df, g, in, cs, n, poses, m, o, stream ? (hipStream_t)stream : df.own);
+        if (rc != GPIS_OK) l.clear_result();
+        return rc;
+    } catch (...) { l.clear_result(); return GPIS_ERR_STATE; }
+}
+int gpis3_locate_depth_field(void* m, void* df, void* locator, const gpis_cam* cam, const float* depth, const float* poses12, int np,
+                             const gpis_locate_opts* opts, void* stream) {
+    if (!df || !depth || (!cam && !m)) return GPIS_ERR_ARG;
+    LocateOpts o;
+    if (int rc = locate_args(locator, 3, poses12, np, opts, &o)) return rc;
+    float c4[4];
+    int wh[2];
+    if (cam) { c4[0] = cam->fx; c4[1] = cam->fy; c4[2] = cam->cx; c4[3] = cam->cy; wh[0] = cam->width; wh[1] = cam->height; }
+    else gpis3_impl_camera((GPisMap3*)m, c4, wh);
+    TrackGeom g{};
+    g.dim = 3; g.fx = c4[0]; g.fy = c4[1]; g.cx = c4[2]; g.cy = c4[3]; g.width = wh[0]; g.height = wh[1];
+    const long long n = (long long)wh[0] * wh[1];
+    if (int rc = track_check_geom(g, n)) return rc;
+    return locate_call(df, *(Locator*)locator, g, depth, nullptr, n, poses12, np, o, stream);
+}
+int gpis2_locate_scan_field(void* m, void* df, void* locator, const float* thetas, const float* ranges, int n, const float* off2,
+                            const float* poses6, int np, const gpis_locate_opts* opts, void* stream) {
+    if (!df || !thetas || !ranges || n < 1 || (!off2 && !m)) return GPIS_ERR_ARG;
+    LocateOpts o;
+    if (int rc = locate_args(locator, 2, poses6, np, opts, &o)) return rc;
+    TrackGeom g{};
+    g.dim = 2;
+    if (off2) { g.off[0] = off2[0]; g.off[1] = off2[1]; }
+    else gpis2_impl_sensor_offset((GPisMap*)m, g.off);
+    if (int rc = track_check_geom(g, n)) return rc;
+    if ((long long)np > Locator::kMaxPoses) return GPIS_ERR_LIMIT;
+    for (int k = 0; k < n; ++k) if (!std::isfinite(thetas[k])) return GPIS_ERR_ARG;
+    std::vector<double> cs;
+    try { cs.resize((size_t)2 * n); } catch (...) { ((Locator*)locator)->clear_result(); return GPIS_ERR_STATE; }
+    for (int k = 0; k < n; ++k) {
+        cs[2 * (size_t)k] = std::cos((double)thetas[k]);
+        cs[2 * (size_t)k + 1] = std::sin((double)thetas[k]);
+    }
+    return locate_call(df, *(Locator*)locator, g, ranges, cs.data(), n, poses6, np, o, stream);
+}
+int gpis_locate_get(void* locator, double* cost, int* inliers, int* order) {
+    if (!locator) return GPIS_ERR_ARG;
+    const Locator& l = *(const Locator*)locator;
+    if (!l.valid) return GPIS_ERR_STATE;
+    if (cost) std::memcpy(cost, l.cost.data(), sizeof(double) * l.cost.size());
+    if (inliers) std::memcpy(inliers, l.inliers.data(), sizeof(int) * l.inliers.size());
+    if (order) std::memcpy(order, l.order.data(), sizeof(int) * l.order.size());
+    return GPIS_OK;
+}
+int gpis_locate_info(void* locator, double* out, int n) {
+    if (!locator || !out || n < 0) return GPIS_ERR_ARG;
+    const Locator& l = *(const Locator*)locator;
+    const double v[7] = {l.valid ? 1.0 : 0.0, (double)l.dim, (double)l.poses, (double)l.npoints, (double)l.order.size(),
+                         (double)l.pixels, l.ms};
+    for (int i = 0; i < n && i < 7; ++i) out[i] = v[i];
+    return GPIS_OK;
+}
+int gpis_locate_device(void* locator, void** d_cost, void** d_inliers) {
+    if (!locator) return GPIS_ERR_ARG;
+    const Locator& l = *(const Locator*)locator;
+    if (!l.valid) return GPIS_ERR_STATE;
+    if (d_cost) *d_cost = (void*)l.d_cost();
+    if (d_inliers) *d_inliers = (void*)l.d_inliers();
     return GPIS_OK;
 }
 

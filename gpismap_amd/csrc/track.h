@@ -87,11 +87,13 @@ struct Tracker {
     // GPIS_ERR_STATE, one of another dim: GPIS_ERR_ARG, both before the previous result is dropped.
     int track_field(const DistanceField& df, const TrackGeom& geo, const float* in, const double* cs, long long n,
                     const double* pose0, const TrackOpts& o, hipStream_t s);
+    // The set-up shared by every call, also the locator's (locate.h): drops the result, checks, uploads the input, flags,
+    // compacts and gathers the valid samples into d_loc (`points` of them; synchronises `s`).  Only o.stride is read beyond the checks.
+    int setup(const TrackGeom& geo, const float* in, const double* cs, long long n, const TrackOpts& o, hipStream_t s);
 
 private:
     using PassFn = std::function<int(const double* pose, double* sums)>;
     int ensure(long long npix, long long ngrid, int dm);
-    int setup(const TrackGeom& geo, const float* in, const double* cs, long long n, const TrackOpts& o, hipStream_t s);
     int iterate(int dm, const double* pose0, const TrackOpts& o, const PassFn& pass_at, double* cur, double* S, int& st, int& it);
     void finish(int dm, long long n, const double* cur, const double* S, int st, int it);
     int pass(MapQuery& mq, OnGPISStore& store, bool have_map, const TrackGeom& geo, const double* pose, const TrackOpts& o,

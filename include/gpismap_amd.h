@@ -688,6 +688,60 @@ int   gpis_traj_get(void* traj, float* x, unsigned char* status, int* iterations
  * d_x[m][N][dim]; d_fres[m][4] = length, smooth, obstacle, min_dist; d_ires[m][4] = status, iterations, nonfinite, collides */
 int   gpis_traj_device(void* traj, const float** d_x, const float** d_fres, const int** d_ires);
 
+/* ---- locating: batches of pose hypotheses scored against a distance field on the device -----------------
+ * Which of these m poses explains this frame?  The measurement update of Monte-Carlo localisation, the inner loop of
+ * correlative scan matching, relocalisation after the tracker lost the pose (status 2): every pose gets the truncated sum of
+ * squared field distances of the frame's points, and the poses are ranked by it.  The field tracker (§7f) polishes the best.
+ * Points: exactly the tracker's.  3-D: pixels (col, row) = (n stride, m stride), n < W / stride, m < H / stride, column-major,
+ * used iff 0.4 < (double)z < 4, local point (u z, v z, z) with u = ((float)col - cx) / fx, v = ((float)row - cy) / fy.  2-D:
+ * beams with 0.2 < (double)r < 30 in input order, local ((float)(r c) + off0, (float)(r s) + off1), c, s = cos, sin((double)theta)
+ * on the host.  p of them, in that order.
+ * Poses: float32, poses12 [m][12] = [t(3), R(9)] column-major, poses6 [m][6] = [t(2), R(4)] (the tracker's layouts).  World
+ * point of a local point under a pose: R[a] x + R[3+a] y + R[6+a] z + t[a] (2-D: R[a] x + R[2+a] y + t[a]) left to right in
+ * float32 without FMA, R and t straight from the float32 pose: the point the tracker samples when it is handed that pose.
+ * Per point: d = gpis_dfield_sample's interpolant at the world point (NaN outside the lattice); e = |(double)d|; the point is
+ * an inlier iff d is finite and e <= max_residual; q = e for an inlier, else max_residual; the point adds q * q (double) to
+ * the pose's cost and 1 to its inlier count when it is an inlier.  Every other point pays the full truncated price: a pose
+ * that throws its points off the lattice ranks last, not first.  The cost is always finite.
+ * Per pose, one summation order: slot l (0 <= l < 64) adds the terms of points l, l + 64, l + 128, ... in ascending order from
+ * 0.0; the 64 slots are reduced by the halving tree v[k] = v[k] + v[k + h], h = 32 .. 1; cost = v[0].  p = 0: cost 0.0 and 0
+ * inliers for every pose.  Poses are independent: a pose has the same bits alone, in any batch, at any batch position, on any
+ * stream.
+ * Ranking: order = the first min(top_k, m) pose indices by cost ascending, ties by the lower index; top_k = 0: all m.
+ * One kernel launch (a wavefront per pose; no atomics), one copy back of 12 bytes per pose, the ranking on the host; every call
+ * returns with its work finished.  A locator holds grow-only device buffers (the tracker's set-up: about 30 B per sample,
+ * 8 B per pixel; 60 B per pose) reused across calls.
+ * map: may be NULL; it is read only for what the caller leaves NULL: the camera (cam NULL) in 3-D, the sensor offset (off2
+ * NULL) in 2-D.  The locator moves to the field's device; hip_stream NULL: the field's own stream.
+ * Errors: a NULL field, locator, depth, thetas, ranges or poses; cam / off2 NULL without a map; a bad camera (size < 1, fx or fy
+ * zero or non-finite); n < 1; m < 1; stride < 1; top_k < 0; a negative, NaN or infinite max_residual; a non-finite beam angle
+ * or pose entry; a field of another dim -> GPIS_ERR_ARG.  A field without a result -> GPIS_ERR_STATE.  More than 2^26 pixels /
+ * beams or more than 2^24 poses -> GPIS_ERR_LIMIT before anything is allocated (the poses are not read).  All of these leave
+ * the previous result untouched; any other failure leaves none. */
+typedef struct gpis_locate_opts {
+    double max_residual;        /* inlier: |d| <= max_residual; every other point pays max_residual^2 */
+    int stride;                 /* 3-D pixel stride of the points; ignored in 2-D (but checked) */
+    int top_k;                  /* poses ranked; 0: all */
+} gpis_locate_opts;
+/* defaults.  3-D: max_residual 0.05, stride 8, top_k 16; 2-D: max_residual 0.5, stride 1 (ignored), top_k 16.  dim outside
+ * {2, 3} or NULL opts -> GPIS_ERR_ARG.  Needs no device. */
+int   gpis_locate_default_opts(int dim, gpis_locate_opts* opts);
+void* gpis_locate_create(void);                            /* on the current device; NULL without one */
+void  gpis_locate_destroy(void* locator);
+/* depth [W*H] column-major as update(); cam NULL: the map's camera; opts NULL: the defaults */
+int   gpis3_locate_depth_field(void* map, void* df, void* locator, const gpis_cam* cam, const float* depth,
+                               const float* poses12, int m, const gpis_locate_opts* opts, void* hip_stream);
+/* thetas, ranges [n] as update(); off2: the sensor offset (x, y) in the laser frame, NULL = the map's */
+int   gpis2_locate_scan_field(void* map, void* df, void* locator, const float* thetas, const float* ranges, int n,
+                              const float* off2, const float* poses6, int m, const gpis_locate_opts* opts, void* hip_stream);
+/* host copies of the last result (any pointer may be NULL): cost [m], inliers [m], order [ranked]; GPIS_ERR_STATE without one */
+int   gpis_locate_get(void* locator, double* cost, int* inliers, int* order);
+/* out[0..n): 1 if a result is held, dim, poses, points used, poses ranked, pixels / beams, ms of host wall time of the call */
+int   gpis_locate_info(void* locator, double* out, int n);
+/* device pointers of the last result, valid until the next call or gpis_locate_destroy: d_cost [m] doubles, d_inliers [m]
+ * ints; either may be NULL; GPIS_ERR_STATE without a result */
+int   gpis_locate_device(void* locator, void** d_cost, void** d_inliers);
+
 #ifdef __cplusplus
 }
 #endif
