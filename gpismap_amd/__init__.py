@@ -6,6 +6,7 @@ the reference's mex gateways (mex/mexGPisMap3.cpp: 'setCamera' / 'update' / 'tes
 device is present, the compute entry points raise.
 """
 import ctypes as C
+import math
 import os
 import numpy as np
 
@@ -46,6 +47,11 @@ class gpis_track_opts(C.Structure):
 
 class gpis_locate_opts(C.Structure):
     _fields_ = [("max_residual", C.c_double), ("stride", C.c_int), ("top_k", C.c_int)]
+
+
+class gpis_pf_opts(C.Structure):
+    _fields_ = [("max_residual", C.c_double), ("beta", C.c_double), ("sigma_t", C.c_double * 3), ("sigma_r", C.c_double),
+                ("resample_below", C.c_double), ("stride", C.c_int)]
 
 
 class gpis_plan_opts(C.Structure):
@@ -260,6 +266,22 @@ def lib():
         L.gpis_locate_get.argtypes = [vp, dp, ip, ip]
         L.gpis_locate_info.argtypes = [vp, dp, C.c_int]
         L.gpis_locate_device.argtypes = [vp, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
+    if hasattr(L, "gpis_pf_create"):
+        po = C.POINTER(gpis_pf_opts)
+        u64p = C.POINTER(C.c_ulonglong)
+        L.gpis_pf_default_opts.argtypes = [C.c_int, po]
+        L.gpis_pf_create.restype = vp
+        L.gpis_pf_create.argtypes = []
+        L.gpis_pf_destroy.argtypes = [vp]
+        L.gpis_pf_init.argtypes = [vp, C.c_int, fp, C.c_int, C.c_ulonglong]
+        L.gpis_pf_predict.argtypes = [vp, dp, po, vp]
+        L.gpis2_pf_update_scan.argtypes = [vp, vp, vp, fp, fp, C.c_int, fp, po, vp]
+        L.gpis3_pf_update_depth.argtypes = [vp, vp, vp, C.POINTER(gpis_cam), fp, po, vp]
+        L.gpis_pf_resample.argtypes = [vp, vp]
+        L.gpis_pf_estimate.argtypes = [vp, dp, dp, u64p, ip]
+        L.gpis_pf_get.argtypes = [vp, dp, dp, u64p, dp, ip, ip, fp]
+        L.gpis_pf_device.argtypes = [vp, C.POINTER(C.c_void_p), C.c_int]
+        L.gpis_pf_info.argtypes = [vp, dp, C.c_int]
     _lib = L
     return L
 
@@ -589,6 +611,11 @@ class GPisMap3:
         """DistanceField.locate_depth with this map's camera when cam6 is None."""
         return field._locate(3, (self.h, self._wh, depth, cam6), poses, refine, track, opts)
 
+    def pf_update_depth_field(self, field, pf, depth, cam6=None, stream=None, **opts):
+        """ParticleFilter.update_depth with this map's camera when cam6 is None (gpis3_pf_update_depth); nothing else of the
+        map is read."""
+        return pf._update_depth(self.h, self._wh, field, depth, cam6, stream, opts)
+
     def render_depth_field(self, field, pose, cam6=None, renderer=None, **opts):
         """render_depth from a DistanceField instead of the map (gpis3_render_depth_field): sphere tracing through the field's
         sampler, one fused kernel.  cam6 None = this map's camera; nothing else of the map is read.  Returns (depth [W*H],
@@ -733,6 +760,10 @@ class GPisMap:
     def locate_scan_field(self, field, thetas, ranges, poses, refine=8, track=None, **opts):
         """DistanceField.locate_scan with this map's sensor offset."""
         return field._locate(2, (self.h, thetas, ranges, None), poses, refine, track, opts)
+
+    def pf_update_scan_field(self, field, pf, thetas, ranges, stream=None, **opts):
+        """ParticleFilter.update_scan with this map's sensor offset (gpis2_pf_update_scan); nothing else of the map is read."""
+        return pf._update_scan(self.h, field, thetas, ranges, None, stream, opts)
 
     def render_scan_field(self, field, thetas, pose6, renderer=None, **opts):
         """render_scan from a DistanceField instead of the map (gpis2_render_scan_field), with this map's sensor offset;
@@ -1496,6 +1527,179 @@ class Locator:
         a, b = C.c_void_p(0), C.c_void_p(0)
         _check(self.L.gpis_locate_device(self.h, C.byref(a), C.byref(b)), "gpis_locate_device")
         return a.value or 0, b.value or 0
+
+
+def pf_opts(dim, **opts):
+    """gpis_pf_opts of the library's defaults for `dim` (gpis_pf_default_opts) with the given fields replaced; sigma_t takes a
+    scalar or a sequence of `dim` values."""
+    o = gpis_pf_opts()
+    _check(lib().gpis_pf_default_opts(int(dim), C.byref(o)), "gpis_pf_default_opts")
+    names = {f[0] for f in gpis_pf_opts._fields_}
+    for k, v in opts.items():
+        if k not in names:
+            raise GpisError("unknown particle-filter option %r" % k)
+        if k == "sigma_t":
+            v = np.broadcast_to(np.asarray(v, np.float64).ravel(), (int(dim),)) if np.ndim(v) == 0 else np.asarray(v, np.float64).ravel()
+            if v.size not in (int(dim), 3):
+                raise GpisError("sigma_t must have %d values" % int(dim))
+            for a in range(3):
+                o.sigma_t[a] = float(v[a]) if a < v.size else 0.0
+        else:
+            setattr(o, k, v)
+    return o
+
+
+class ParticleFilter:
+    """Monte-Carlo localisation against a DistanceField, resident on the device (gpis_pf_*): init from float32 poses, then
+    predict / update_scan or update_depth per frame; an update returns the estimate, and only that leaves the device."""
+
+    INFO_KEYS = ("inited", "dim", "particles", "tick", "points", "pixels", "updates", "resamplings", "resampled", "neff", "ms")
+    INT_KEYS = INFO_KEYS[:9]
+    PTR_KEYS = ("state", "poses", "L", "q", "cost", "inliers", "ancestors")
+
+    def __init__(self, **opts):
+        """opts: gpis_pf_opts fields that replace the defaults in every call of this filter."""
+        self.L = lib()
+        if not hasattr(self.L, "gpis_pf_create"):
+            raise GpisError("the native library has no particle filter (gpis_pf_create)")
+        if self.L.gpis_device_count() < 1:
+            raise GpisError("no HIP device: gpismap_amd has no CPU fallback")
+        self.h = C.c_void_p(self.L.gpis_pf_create())
+        if not self.h:
+            raise GpisError("gpis_pf_create failed")
+        self.opts = dict(opts)
+        self.dim = 0
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.gpis_pf_destroy(self.h)
+            self.h = None
+
+    __del__ = close
+
+    def _opts(self, opts):
+        d = dict(self.opts)
+        d.update(opts)
+        return pf_opts(self.dim, **d)
+
+    def init(self, poses, seed=0):
+        """The particle set from float32 poses [m, 6] (2-D) / [m, 12] (3-D); L = 0, tick = 0."""
+        poses = np.ascontiguousarray(poses, dtype=np.float32)
+        if poses.ndim != 2 or poses.shape[1] not in (6, 12) or poses.shape[0] < 1:
+            raise GpisError("poses must be [m, 6] or [m, 12] with m >= 1")
+        dim = 3 if poses.shape[1] == 12 else 2
+        _check(self.L.gpis_pf_init(self.h, dim, _p(poses), poses.shape[0], C.c_ulonglong(int(seed) & 0xFFFFFFFFFFFFFFFF)), "gpis_pf_init")
+        self.dim = dim
+        return self
+
+    def motion(self, motion):
+        """The relative pose [t, R] (float64 [6] / [12]) of `motion`: that layout itself, (dx, dy, dtheta) in 2-D, or
+        (d [3], rotvec [3]) in 3-D."""
+        if self.dim == 3 and len(motion) == 2:
+            d, w = (np.asarray(v, np.float64).ravel() for v in motion)
+            if d.size != 3 or w.size != 3:
+                raise GpisError("a 3-D motion is (d [3], rotvec [3]) or a pose [12]")
+            return np.concatenate([d, _exp_so3(w).T.ravel()])
+        mo = np.asarray(motion, np.float64).ravel()
+        if self.dim == 2 and mo.size == 3:
+            c, s = math.cos(float(mo[2])), math.sin(float(mo[2]))
+            return np.array([mo[0], mo[1], c, s, -s, c], np.float64)
+        if mo.size != (12 if self.dim == 3 else 6):
+            raise GpisError("bad motion for a %d-D filter" % self.dim)
+        return np.ascontiguousarray(mo)
+
+    def predict(self, motion, stream=None, **opts):
+        """Move every particle by `motion` (see motion()) in its own frame plus noise (sigma_t, sigma_r)."""
+        if not self.dim:
+            raise GpisError("predict before init")
+        mo = self.motion(motion)
+        o = self._opts(opts)
+        _check(self.L.gpis_pf_predict(self.h, _p(mo, C.c_double), C.byref(o), stream), "gpis_pf_predict")
+
+    def update_scan(self, field, thetas, ranges, off2, stream=None, **opts):
+        """Weigh the set against a laser scan in `field` (gpis2_pf_update_scan), estimate, resample if N_eff asks for it.
+        Returns estimate()."""
+        return self._update_scan(None, field, thetas, ranges, off2, stream, opts)
+
+    def update_depth(self, field, depth, cam6, stream=None, **opts):
+        """update_scan for a depth image (gpis3_pf_update_depth)."""
+        return self._update_depth(None, None, field, depth, cam6, stream, opts)
+
+    def _update_scan(self, map_h, field, thetas, ranges, off2, stream, opts):
+        thetas = np.ascontiguousarray(thetas, dtype=np.float32).ravel()
+        ranges = np.ascontiguousarray(ranges, dtype=np.float32).ravel()
+        if thetas.size != ranges.size:
+            raise GpisError("thetas and ranges differ in size")
+        off = np.ascontiguousarray(off2, dtype=np.float32).ravel() if off2 is not None else None
+        if off is not None and off.size != 2:
+            raise GpisError("off2 must have 2 elements")
+        if off is None and map_h is None:
+            raise GpisError("a field-only update_scan needs off2")
+        o = self._opts(opts)
+        _check(self.L.gpis2_pf_update_scan(map_h, field.h, self.h, _p(thetas), _p(ranges), thetas.size,
+                                           _p(off) if off is not None else None, C.byref(o), stream), "gpis2_pf_update_scan")
+        return self.estimate()
+
+    def _update_depth(self, map_h, map_wh, field, depth, cam6, stream, opts):
+        depth = np.ascontiguousarray(depth, dtype=np.float32).ravel()
+        if cam6 is None and map_h is None:
+            raise GpisError("a field-only update_depth needs cam6")
+        w, h = (int(cam6[4]), int(cam6[5])) if cam6 is not None else map_wh
+        if depth.size != w * h:
+            raise GpisError("depth must have width * height = %d elements" % (w * h))
+        o = self._opts(opts)
+        cam = C.byref(_cam(cam6)) if cam6 is not None else None
+        _check(self.L.gpis3_pf_update_depth(map_h, field.h, self.h, cam, _p(depth), C.byref(o), stream), "gpis3_pf_update_depth")
+        return self.estimate()
+
+    def resample(self, stream=None):
+        """Systematic resampling from the last update's weights (uniform after init), whatever N_eff says."""
+        _check(self.L.gpis_pf_resample(self.h, stream), "gpis_pf_resample")
+
+    def estimate(self):
+        """dict of the last update: pose (float64 [6] / [12] = [t, R]), neff, T, Th, S2 (Python ints), resampled."""
+        pose = np.zeros(12 if self.dim == 3 else 6, dtype=np.float64)
+        neff, tot, rs = C.c_double(0.0), (C.c_ulonglong * 3)(), C.c_int(0)
+        _check(self.L.gpis_pf_estimate(self.h, _p(pose, C.c_double), C.byref(neff), tot, C.byref(rs)), "gpis_pf_estimate")
+        return dict(pose=pose, neff=neff.value, T=int(tot[0]), Th=int(tot[1]), S2=int(tot[2]), resampled=bool(rs.value))
+
+    def info(self):
+        out = np.zeros(len(self.INFO_KEYS), dtype=np.float64)
+        _check(self.L.gpis_pf_info(self.h, _p(out, C.c_double), out.size), "gpis_pf_info")
+        d = dict(zip(self.INFO_KEYS, out.tolist()))
+        for k in self.INT_KEYS:
+            d[k] = int(d[k])
+        return d
+
+    def get(self):
+        """dict of host copies: state [m, 4 / 7] f64, L [m] f64, q [m] u64, cost [m] f64, inliers [m] i32, ancestors [m] i32,
+        poses [m, 6 / 12] f32."""
+        i = self.info()
+        if not i["inited"]:
+            raise GpisError("the particle filter holds no set")
+        m, d3 = i["particles"], i["dim"] == 3
+        out = dict(state=np.zeros((m, 7 if d3 else 4), np.float64), L=np.zeros(m, np.float64), q=np.zeros(m, np.uint64),
+                   cost=np.zeros(m, np.float64), inliers=np.zeros(m, np.int32), ancestors=np.zeros(m, np.int32),
+                   poses=np.zeros((m, 12 if d3 else 6), np.float32))
+        _check(self.L.gpis_pf_get(self.h, _p(out["state"], C.c_double), _p(out["L"], C.c_double), _p(out["q"], C.c_ulonglong),
+                                  _p(out["cost"], C.c_double), _p(out["inliers"], C.c_int), _p(out["ancestors"], C.c_int),
+                                  _p(out["poses"])), "gpis_pf_get")
+        return out
+
+    def poses(self):
+        """The float32 poses [m, 6 / 12] the scorer reads."""
+        i = self.info()
+        if not i["inited"]:
+            raise GpisError("the particle filter holds no set")
+        out = np.zeros((i["particles"], 12 if i["dim"] == 3 else 6), np.float32)
+        _check(self.L.gpis_pf_get(self.h, None, None, None, None, None, None, _p(out)), "gpis_pf_get")
+        return out
+
+    def device_ptrs(self):
+        """dict of device addresses (state, poses, L, q, cost, inliers, ancestors), valid until the next init or resampling."""
+        a = (C.c_void_p * 7)()
+        _check(self.L.gpis_pf_device(self.h, a, 7), "gpis_pf_device")
+        return dict(zip(self.PTR_KEYS, [v or 0 for v in a]))
 
 
 def pose_grid2(xs, ys, thetas):

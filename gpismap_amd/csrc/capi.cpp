@@ -13,6 +13,7 @@
 #include "render.h"
 #include "track.h"
 #include "locate.h"
+#include "pf.h"
 #include "plan.h"
 #include "traj.h"
 #include "obsgp.h"
@@ -1374,6 +1375,154 @@ int gpis_locate_device(void* locator, void** d_cost, void** d_inliers) {
     if (!l.valid) return GPIS_ERR_STATE;
     if (d_cost) *d_cost = (void*)l.d_cost();
     if (d_inliers) *d_inliers = (void*)l.d_inliers();
+    return GPIS_OK;
+}
+
+// ---- the particle filter --------------------------------------------------------------------------------------------------
+int gpis_pf_default_opts(int dim, gpis_pf_opts* o) {
+    if (!o || (dim != 2 && dim != 3)) return GPIS_ERR_ARG;
+    if (dim == 3) {
+        o->max_residual = 0.05; o->beta = 100.0; o->sigma_t[0] = o->sigma_t[1] = o->sigma_t[2] = 0.003; o->sigma_r = 0.003; o->stride = 8;
+    } else {
+        o->max_residual = 0.5; o->beta = 2.0; o->sigma_t[0] = o->sigma_t[1] = 0.03; o->sigma_t[2] = 0.0; o->sigma_r = 0.03; o->stride = 1;
+    }
+    o->resample_below = 0.5;
+    return GPIS_OK;
+}
+void* gpis_pf_create(void) {
+    if (gpis_device_count() < 1) { fprintf(stderr, "[gpismap_amd] no HIP device\n"); return nullptr; }
+    ParticleFilter* f = new (std::nothrow) ParticleFilter();
+    if (f && !f->trk.own) { delete f; return nullptr; }
+    return f;
+}
+void gpis_pf_destroy(void* pf) { delete (ParticleFilter*)pf; }
+int gpis_pf_init(void* pf, int dim, const float* poses, int m, unsigned long long seed) {
+    if (!pf || !poses || (dim != 2 && dim != 3) || m < 1) return GPIS_ERR_ARG;
+    if ((long long)m > ParticleFilter::kMaxParticles) return GPIS_ERR_LIMIT;
+    const size_t np = (size_t)(dim == 3 ? 12 : 6) * (size_t)m;
+    for (size_t k = 0; k < np; ++k) if (!std::isfinite(poses[k])) return GPIS_ERR_ARG;
+    ParticleFilter& f = *(ParticleFilter*)pf;
+    try { return f.init(dim, poses, m, seed); } catch (...) { f.inited = false; return GPIS_ERR_STATE; }
+}
+// the options of a call (NULL: the defaults of the filter's dim), checked
+static int pf_args(const ParticleFilter& f, const gpis_pf_opts* opts, PfOpts* o) {
+    gpis_pf_opts d;
+    if (!opts) { (void)gpis_pf_default_opts(f.dim, &d); opts = &d; }
+    o->max_residual = opts->max_residual; o->beta = opts->beta; o->sigma_r = opts->sigma_r; o->resample_below = opts->resample_below;
+    for (int a = 0; a < 3; ++a) o->sigma_t[a] = opts->sigma_t[a];
+    o->stride = opts->stride;
+    return pf_check_opts(*o);
+}
+int gpis_pf_predict(void* pf, const double* motion, const gpis_pf_opts* opts, void* stream) {
+    if (!pf || !motion) return GPIS_ERR_ARG;
+    ParticleFilter& f = *(ParticleFilter*)pf;
+    if (!f.inited) return GPIS_ERR_STATE;
+    PfOpts o;
+    if (int rc = pf_args(f, opts, &o)) return rc;
+    for (int k = 0; k < (f.dim == 3 ? 12 : 6); ++k) if (!std::isfinite(motion[k])) return GPIS_ERR_ARG;
+    double mo[7];
+    for (int k = 0; k < f.dim; ++k) mo[k] = motion[k];
+    if (f.dim == 3) pf_mat_to_quat(motion + 3, mo + 3);
+    else { mo[2] = motion[2]; mo[3] = motion[3]; }
+    DeviceScope ds(f.device);
+    return f.predict(mo, o, f.stream_or_own((hipStream_t)stream));
+}
+// the filter's and the field's state, dim and device (before anything is touched), then the call on that device
+static int pf_update_call(void* d, ParticleFilter& f, const TrackGeom& g, const float* in, const double* cs, long long n,
+                          const PfOpts& o, void* stream) {
+    const DistanceField& df = *(const DistanceField*)d;
+    if (!df.valid) return GPIS_ERR_STATE;
+    if (df.dim != g.dim || df.device != f.device) return GPIS_ERR_ARG;
+    DeviceScope ds(f.device);
+    try { return f.update(df, g, in, cs, n, o, f.stream_or_own((hipStream_t)stream)); } catch (...) { return GPIS_ERR_STATE; }
+}
+int gpis3_pf_update_depth(void* m, void* df, void* pf, const gpis_cam* cam, const float* depth, const gpis_pf_opts* opts, void* stream) {
+    if (!df || !pf || !depth || (!cam && !m)) return GPIS_ERR_ARG;
+    ParticleFilter& f = *(ParticleFilter*)pf;
+    if (!f.inited) return GPIS_ERR_STATE;
+    if (f.dim != 3) return GPIS_ERR_ARG;
+    PfOpts o;
+    if (int rc = pf_args(f, opts, &o)) return rc;
+    float c4[4];
+    int wh[2];
+    if (cam) { c4[0] = cam->fx; c4[1] = cam->fy; c4[2] = cam->cx; c4[3] = cam->cy; wh[0] = cam->width; wh[1] = cam->height; }
+    else gpis3_impl_camera((GPisMap3*)m, c4, wh);
+    TrackGeom g{};
+    g.dim = 3; g.fx = c4[0]; g.fy = c4[1]; g.cx = c4[2]; g.cy = c4[3]; g.width = wh[0]; g.height = wh[1];
+    const long long n = (long long)wh[0] * wh[1];
+    if (int rc = track_check_geom(g, n)) return rc;
+    return pf_update_call(df, f, g, depth, nullptr, n, o, stream);
+}
+int gpis2_pf_update_scan(void* m, void* df, void* pf, const float* thetas, const float* ranges, int n, const float* off2,
+                         const gpis_pf_opts* opts, void* stream) {
+    if (!df || !pf || !thetas || !ranges || n < 1 || (!off2 && !m)) return GPIS_ERR_ARG;
+    ParticleFilter& f = *(ParticleFilter*)pf;
+    if (!f.inited) return GPIS_ERR_STATE;
+    if (f.dim != 2) return GPIS_ERR_ARG;
+    PfOpts o;
+    if (int rc = pf_args(f, opts, &o)) return rc;
+    TrackGeom g{};
+    g.dim = 2;
+    if (off2) { g.off[0] = off2[0]; g.off[1] = off2[1]; }
+    else gpis2_impl_sensor_offset((GPisMap*)m, g.off);
+    if (int rc = track_check_geom(g, n)) return rc;
+    for (int k = 0; k < n; ++k) if (!std::isfinite(thetas[k])) return GPIS_ERR_ARG;
+    std::vector<double> cs;
+    try { cs.resize((size_t)2 * n); } catch (...) { return GPIS_ERR_STATE; }
+    for (int k = 0; k < n; ++k) {
+        cs[2 * (size_t)k] = std::cos((double)thetas[k]);
+        cs[2 * (size_t)k + 1] = std::sin((double)thetas[k]);
+    }
+    return pf_update_call(df, f, g, ranges, cs.data(), n, o, stream);
+}
+int gpis_pf_resample(void* pf, void* stream) {
+    if (!pf) return GPIS_ERR_ARG;
+    ParticleFilter& f = *(ParticleFilter*)pf;
+    if (!f.inited) return GPIS_ERR_STATE;
+    DeviceScope ds(f.device);
+    return f.resample(f.stream_or_own((hipStream_t)stream));
+}
+int gpis_pf_estimate(void* pf, double* pose, double* neff, unsigned long long* totals, int* resampled) {
+    if (!pf) return GPIS_ERR_ARG;
+    const ParticleFilter& f = *(const ParticleFilter*)pf;
+    if (!f.inited || !f.have_estimate) return GPIS_ERR_STATE;
+    if (pose) for (int k = 0; k < (f.dim == 3 ? 12 : 6); ++k) pose[k] = f.est_pose[k];
+    if (neff) *neff = f.neff;
+    if (totals) { totals[0] = f.stats.T; totals[1] = f.stats.Th; totals[2] = f.stats.S2; }
+    if (resampled) *resampled = f.resampled ? 1 : 0;
+    return GPIS_OK;
+}
+int gpis_pf_get(void* pf, double* state, double* L, unsigned long long* q, double* cost, int* inliers, int* ancestors, float* poses) {
+    if (!pf) return GPIS_ERR_ARG;
+    const ParticleFilter& f = *(const ParticleFilter*)pf;
+    if (!f.inited) return GPIS_ERR_STATE;
+    DeviceScope ds(f.device);
+    const size_t n = (size_t)f.m;
+    hipStream_t s = f.trk.own;
+    if (state) GPIS_HIP(hipMemcpyAsync(state, f.state(), sizeof(double) * (f.dim == 3 ? 7 : 4) * n, hipMemcpyDeviceToHost, s));
+    if (L) GPIS_HIP(hipMemcpyAsync(L, f.d_L, sizeof(double) * n, hipMemcpyDeviceToHost, s));
+    if (q) GPIS_HIP(hipMemcpyAsync(q, f.d_q, sizeof(unsigned long long) * n, hipMemcpyDeviceToHost, s));
+    if (cost) GPIS_HIP(hipMemcpyAsync(cost, f.d_cost, sizeof(double) * n, hipMemcpyDeviceToHost, s));
+    if (inliers) GPIS_HIP(hipMemcpyAsync(inliers, f.d_inl, sizeof(int) * n, hipMemcpyDeviceToHost, s));
+    if (ancestors) GPIS_HIP(hipMemcpyAsync(ancestors, f.d_anc, sizeof(int) * n, hipMemcpyDeviceToHost, s));
+    if (poses) GPIS_HIP(hipMemcpyAsync(poses, f.poses(), sizeof(float) * (f.dim == 3 ? 12 : 6) * n, hipMemcpyDeviceToHost, s));
+    GPIS_HIP(hipStreamSynchronize(s));
+    return GPIS_OK;
+}
+int gpis_pf_device(void* pf, void** ptrs, int n) {
+    if (!pf || !ptrs || n < 0) return GPIS_ERR_ARG;
+    const ParticleFilter& f = *(const ParticleFilter*)pf;
+    if (!f.inited) return GPIS_ERR_STATE;
+    void* v[7] = {(void*)f.state(), (void*)f.poses(), (void*)f.d_L, (void*)f.d_q, (void*)f.d_cost, (void*)f.d_inl, (void*)f.d_anc};
+    for (int i = 0; i < n && i < 7; ++i) ptrs[i] = v[i];
+    return GPIS_OK;
+}
+int gpis_pf_info(void* pf, double* out, int n) {
+    if (!pf || !out || n < 0) return GPIS_ERR_ARG;
+    const ParticleFilter& f = *(const ParticleFilter*)pf;
+    const double v[11] = {f.inited ? 1.0 : 0.0, (double)f.dim, (double)f.m, (double)f.tick, (double)f.npoints, (double)f.pixels,
+                          (double)f.updates, (double)f.resamples, f.resampled ? 1.0 : 0.0, f.neff, f.ms};
+    for (int i = 0; i < n && i < 11; ++i) out[i] = v[i];
     return GPIS_OK;
 }
 

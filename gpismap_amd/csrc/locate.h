@@ -56,6 +56,12 @@ private:
     int ensure(long long m);
 };
 
+// One launch of the scoring kernel on `s`, also the particle filter's (pf.h): cost [m] and inliers [m] (device) of the device poses
+// d_pose [m][12 / 6] against the device points d_loc [p] (float4 each, the tracker's) and the field's result.  dim = df.dim in
+// {2, 3}; m >= 1; nothing is synchronised.  GPIS_OK / GPIS_ERR_HIP.
+int locate_score_launch(const DistanceField& df, int dim, const float* d_pose, int m, const float* d_loc, long long p,
+                        double max_residual, double* d_cost, int* d_inliers, hipStream_t s);
+
 // GPIS_OK or GPIS_ERR_ARG: stride < 1, top_k < 0, a negative, NaN or infinite max_residual
 int locate_check_opts(const LocateOpts& o);
 

@@ -79,6 +79,19 @@ int locate_check_opts(const LocateOpts& o) {
     return GPIS_OK;
 }
 
+int locate_score_launch(const DistanceField& df, int dim, const float* d_pose, int m, const float* d_loc, long long p,
+                        double max_residual, double* d_cost, int* d_inliers, hipStream_t s) {
+    const int grid = (m + Locator::kWaves - 1) / Locator::kWaves;
+    if (dim == 3)
+        hipLaunchKernelGGL(locate_score_kernel<3>, dim3(grid), dim3(kBlock), 0, s, d_pose, m, (const float4*)d_loc, (int)p,
+                           (const float*)df.d_dist, df.lattice(), max_residual, d_cost, d_inliers);
+    else
+        hipLaunchKernelGGL(locate_score_kernel<2>, dim3(grid), dim3(kBlock), 0, s, d_pose, m, (const float4*)d_loc, (int)p,
+                           (const float*)df.d_dist, df.lattice(), max_residual, d_cost, d_inliers);
+    GPIS_HIP(hipGetLastError());
+    return GPIS_OK;
+}
+
 Locator::Locator() { (void)hipGetDevice(&device); }
 
 Locator::~Locator() { (void)bind(-1); }
@@ -130,14 +143,7 @@ int Locator::score(const DistanceField& df, const TrackGeom& geo, const float* i
     GPIS_HIP(hipMemcpyAsync(d_pose, h_pose, sizeof(float) * np * mm, hipMemcpyHostToDevice, s));
     double* dc = (double*)d_out;
     int* di = (int*)(d_out + sizeof(double) * mm);
-    const int grid = (m + kWaves - 1) / kWaves;
-    if (dm == 3)
-        hipLaunchKernelGGL(locate_score_kernel<3>, dim3(grid), dim3(kBlock), 0, s, (const float*)d_pose, m, (const float4*)trk.d_loc, (int)p,
-                           (const float*)df.d_dist, df.lattice(), o.max_residual, dc, di);
-    else
-        hipLaunchKernelGGL(locate_score_kernel<2>, dim3(grid), dim3(kBlock), 0, s, (const float*)d_pose, m, (const float4*)trk.d_loc, (int)p,
-                           (const float*)df.d_dist, df.lattice(), o.max_residual, dc, di);
-    GPIS_HIP(hipGetLastError());
+    if (int rc = locate_score_launch(df, dm, d_pose, m, trk.d_loc, p, o.max_residual, dc, di, s)) return rc;
     GPIS_HIP(hipMemcpyAsync(h_out, d_out, (sizeof(double) + sizeof(int)) * mm, hipMemcpyDeviceToHost, s));
     GPIS_HIP(hipStreamSynchronize(s));
     cost.assign((const double*)h_out, (const double*)h_out + mm);

@@ -742,6 +742,86 @@ int   gpis_locate_info(void* locator, double* out, int n);
  * ints; either may be NULL; GPIS_ERR_STATE without a result */
 int   gpis_locate_device(void* locator, void** d_cost, void** d_inliers);
 
+/* ---- Monte-Carlo localisation: a particle filter resident on the device ------------------------------------
+ * The loop that keeps a pose belief alive across frames: m <= 2^24 particles in SE(2) / SE(3) live on the device; predict moves
+ * them, an update weighs them against a frame with the scorer's cost above, resampling redraws them, and one small block (the
+ * estimate's sums, the integer totals, the best index) is all that comes back per step.  tests/pf_ref.py restates every stage
+ * in numpy; each stage except one exp has exactly one result, and that exp moves a weight by at most 1 in 2^32.
+ * Every floating-point expression below is double, evaluated left to right, not contracted; division and sqrt are IEEE.
+ * State: 2-D (x, y, c, s); 3-D (t(3), w, x, y, z), the quaternion of unit norm; per particle an accumulated negative log
+ * weight L; per filter a 32-bit tick and the 64-bit seed.  The float32 pose the scorer reads is every component cast from the
+ * state: 2-D [x, y, c, s, -s, c]; 3-D [t, R], R column-major from the quaternion: R0 = 1-2(yy+zz), R1 = 2(xy+wz),
+ * R2 = 2(xz-wy), R3 = 2(xy-wz), R4 = 1-2(xx+zz), R5 = 2(yz+wx), R6 = 2(xz+wy), R7 = 2(yz-wx), R8 = 1-2(xx+yy).
+ * init: the state from float32 poses (the locate layouts): 2-D (t, R[0], R[1]); 3-D t and the quaternion of R by the trace /
+ * largest-diagonal branches (tr = R0+R4+R8 > 0: s = 2 sqrt(tr+1), (s/4, (R5-R7)/s, (R6-R2)/s, (R1-R3)/s); else R0 largest:
+ * s = 2 sqrt(1+R0-R4-R8), ((R5-R7)/s, s/4, (R3+R1)/s, (R6+R2)/s); else R4 > R8: s = 2 sqrt(1+R4-R0-R8), ((R6-R2)/s, (R3+R1)/s,
+ * s/4, (R7+R5)/s); else s = 2 sqrt(1+R8-R0-R4), ((R1-R3)/s, (R6+R2)/s, (R7+R5)/s, s/4)), then divided by its norm.  L = 0,
+ * tick = 0, every weight q = 2^32.  The set lives on the device current in the caller; an update needs a field of that device.
+ * Random numbers: Philox4x32-10 (multipliers 0xD2511F53 / 0xCD9E8D57, Weyl constants 0x9E3779B9 / 0xBB67AE85), key
+ * (seed & 0xffffffff, seed >> 32), counter (particle slot, tick, k, tag); tag 0 motion noise, tag 1 the resampling offset.
+ * Deviate k: S = the integer sum of the eight 16-bit halves of the block, z = (double)(2 S - 8 * 65535) * 0x1.3988e1412ed76p-17:
+ * the sum-of-uniforms normal deviate, unit variance, |z| <= 4.899; no transcendental runs on the device.
+ * predict: tick += 1; motion is the relative pose in the body frame as double [t, R] (2-D 6, 3-D 12 values; R becomes
+ * (cu, su) = (R[0], R[1]) / the quaternion Qu as in init).  2-D, z0..z2: bx = dx + sigma_t[0] z0, by = dy + sigma_t[1] z1,
+ * a = (0.5 sigma_r) z2, cn = (1 - a a) / (1 + a a), sn = (a + a) / (1 + a a) (the Cayley map), x += c bx - s by,
+ * y += s bx + c by, (c, s) <- ((c, s) (cu, su)) (cn, sn) as complex products, divided by sqrt(c c + s s).  3-D, z0..z5:
+ * b[a] = d[a] + sigma_t[a] z_a, t[a] += R[a] b0 + R[3+a] b1 + R[6+a] b2 (R of the quaternion before the step),
+ * Q <- (Q (x) Qu) (x) (1, a0, a1, a2), a_k = (0.5 sigma_r) z_{3+k}, divided by its norm.
+ * update: cost and inliers per particle = the locate block's, of the float32 poses against the frame's points (bit for bit
+ * what gpis*_locate_* returns for gpis_pf_get's poses); L += beta cost; Lmin = min L; q = (uint64)floor(exp(-(L - Lmin)) 2^32);
+ * T = sum q, Th = sum (q >> 16), S2 = sum (q >> 16)^2 (integers); neff = (double)Th (double)Th / (double)S2; the estimate =
+ * sum (double)q * state column (3-D: every quaternion times +-1 so that its dot product with the quaternion of the
+ * lowest-index particle of maximal q is >= 0) in the tracker's reduction order (256-particle segments by a halving tree, the
+ * partials zero-padded to a power of two, the same tree), divided by (double)T, the heading / quaternion divided by its
+ * norm; then resample iff neff < resample_below * m.
+ * resample: tick += 1; C = the inclusive prefix sum of q (the last update's; 2^32 each after init); qs, rem = divmod(T, m);
+ * r = ((w0 << 32) | w1) mod qs from the block of counter (0xFFFFFFFF, tick, 0, 1); p_j = j qs + (j rem) div m + r; ancestor
+ * a_j = the first i with C_i > p_j; state and pose gathered into the other half of a ping-pong buffer, L = 0.  Equal weights
+ * give a_j = j.
+ * No kernel waits on another workgroup, no floating-point atomics; results do not depend on schedule or stream.  Every call
+ * returns with its work finished.  hip_stream NULL: the filter's own stream.  map: as for locate, read only for what the
+ * caller leaves NULL.
+ * Errors (each leaves the previous state untouched): a NULL filter, poses, motion, field or frame; dim outside {2, 3}; m < 1; a
+ * non-finite pose or motion entry; a negative or non-finite sigma, beta, max_residual or resample_below; stride < 1; a bad
+ * camera / beam angle / offset as for locate; a field of another dim or another device -> GPIS_ERR_ARG.  predict, update,
+ * resample or get before init, estimate before the first update, a field without a result -> GPIS_ERR_STATE.  More than 2^24
+ * particles or 2^26 pixels / beams -> GPIS_ERR_LIMIT before anything is read or allocated. */
+typedef struct gpis_pf_opts {
+    double max_residual;        /* the scorer's truncation */
+    double beta;                /* L += beta * cost */
+    double sigma_t[3];          /* motion noise of the translation, body frame (2-D: the first two) */
+    double sigma_r;             /* motion noise of the rotation */
+    double resample_below;      /* an update resamples iff neff < resample_below * m; 0: never */
+    int stride;                 /* 3-D pixel stride of the points; ignored in 2-D (but checked) */
+} gpis_pf_opts;
+/* defaults.  2-D: max_residual 0.5, beta 2, sigma_t (0.03, 0.03, 0), sigma_r 0.03, resample_below 0.5, stride 1; 3-D:
+ * max_residual 0.05, beta 100, sigma_t 0.003 each, sigma_r 0.003, resample_below 0.5, stride 8.  Needs no device. */
+int   gpis_pf_default_opts(int dim, gpis_pf_opts* opts);
+void* gpis_pf_create(void);                                 /* on the current device; NULL without one */
+void  gpis_pf_destroy(void* pf);
+/* poses: float32 [m][6] (dim 2) / [m][12] (dim 3) */
+int   gpis_pf_init(void* pf, int dim, const float* poses, int m, unsigned long long seed);
+/* motion: double [6] / [12]; opts NULL: the defaults (sigma_t and sigma_r are read) */
+int   gpis_pf_predict(void* pf, const double* motion, const gpis_pf_opts* opts, void* hip_stream);
+int   gpis2_pf_update_scan(void* map, void* df, void* pf, const float* thetas, const float* ranges, int n, const float* off2,
+                           const gpis_pf_opts* opts, void* hip_stream);
+int   gpis3_pf_update_depth(void* map, void* df, void* pf, const gpis_cam* cam, const float* depth, const gpis_pf_opts* opts,
+                            void* hip_stream);
+int   gpis_pf_resample(void* pf, void* hip_stream);
+/* the last update's estimate (any pointer may be NULL): pose double [6] / [12] = [t, R], neff, totals [3] = T, Th, S2,
+ * resampled = 1 if that update resampled */
+int   gpis_pf_estimate(void* pf, double* pose, double* neff, unsigned long long* totals, int* resampled);
+/* host copies (any pointer may be NULL): state [m][4 / 7], L [m], q [m], cost [m], inliers [m], ancestors [m] of the last
+ * resampling (the identity after init), poses float32 [m][6 / 12].  q, cost and inliers are the last update's, in its order */
+int   gpis_pf_get(void* pf, double* state, double* L, unsigned long long* q, double* cost, int* inliers, int* ancestors,
+                  float* poses);
+/* device pointers ptrs[0..n): state, poses, L, q, cost, inliers, ancestors; valid until the next init or resampling (state and
+ * poses change halves).  A caller that overwrites the state writes the matching float32 poses too */
+int   gpis_pf_device(void* pf, void** ptrs, int n);
+/* out[0..n): 1 after init, dim, m, tick, points used, pixels / beams, updates, resamplings, 1 if the last update resampled,
+ * neff, ms of host wall time of the last update */
+int   gpis_pf_info(void* pf, double* out, int n);
+
 #ifdef __cplusplus
 }
 #endif
