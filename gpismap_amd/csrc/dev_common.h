@@ -14,6 +14,7 @@
 // fmaf()/MFMA fuse.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <algorithm>
 #include <cstdint>
 #include <cstdio>
 
@@ -71,6 +72,30 @@ struct DeviceScope {
     }
     ~DeviceScope() { if (dev >= 0 && prev >= 0 && prev != dev) (void)hipSetDevice(prev); }
 };
+
+// ---- host helpers of the memory-bound passes ----------------------------------------------------------------------------------
+constexpr int kGridCap = 2048;
+
+// blocks of a grid-stride launch over n elements: at least one, at most cap
+inline int grid_for(long long n, int block = 256, long long cap = kGridCap) {
+    return (int)std::max(1ll, std::min(cap, (n + block - 1) / block));
+}
+
+inline long long pow2_at_least(long long n) {
+    long long p = 1;
+    while (p < n) p <<= 1;
+    return p;
+}
+
+// a grow-only device buffer: at least `need` elements after the call; the contents are not kept
+template <class T>
+int grow(T*& p, size_t& cap, size_t need) {
+    if (need <= cap) return GPIS_OK;
+    (void)hipFree(p); p = nullptr; cap = 0;
+    GPIS_HIP(hipMalloc((void**)&p, sizeof(T) * need));
+    cap = need;
+    return GPIS_OK;
+}
 
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) once per (device, kernel): the attribute is per device, and one process may
 // drive maps on several GPUs.  Thread safe.  Returns GPIS_OK or GPIS_ERR_HIP.

@@ -22,9 +22,6 @@ namespace gpis {
 namespace {
 
 constexpr int kBlock = 256;
-constexpr int kGridCap = 2048;
-
-inline int grid_for(long long n) { return (int)std::max(1ll, std::min((long long)kGridCap, (n + kBlock - 1) / kBlock)); }
 
 __device__ __forceinline__ bool crosses(float fa, float fb, float level) {
     return isfinite(fa) && isfinite(fb) && ((fa < level) != (fb < level));
@@ -170,15 +167,6 @@ __global__ void __launch_bounds__(kBlock) df_sample_kernel(const float* __restri
         const float* xq = x + (size_t)q * dim;
         df_sample_at(F, L, xq[0], xq[1], dim == 3 ? xq[2] : 0.f, out + (size_t)q * (1 + dim));
     }
-}
-
-template <class T>
-int grow(T*& p, size_t& cap, size_t need) {
-    if (need <= cap) return GPIS_OK;
-    (void)hipFree(p); p = nullptr; cap = 0;
-    GPIS_HIP(hipMalloc((void**)&p, sizeof(T) * need));
-    cap = need;
-    return GPIS_OK;
 }
 
 }  // namespace

@@ -4,11 +4,11 @@
 // poses of a batch and the lanes of a wavefront sample neighbouring cells); the local points are re-read by every wavefront
 // from L2.
 //
-// Per point: world point R local + t left to right in float (no FMA: -ffp-contract=off) with R, t straight from the float pose
-// -- the point the tracker samples for that pose; d = df_sample_at's o[0]; e = |(double)d|; inlier iff d is finite and
-// e <= max_residual; q = e for an inlier, else max_residual; the term is q * q in double.  Per pose: lane l adds the terms of
-// points l, l + 64, ... in ascending order from 0.0, then v[k] = v[k] + v[k + h], h = 32 .. 1 through lane shuffles; lane 0 holds
-// the sum.  One order, whatever the batch: a pose has the same bits alone and at any batch position.
+// Per point: the world point (world_point.h) with R, t straight from the float pose -- the tracker's function, so the point the
+// tracker samples for that pose; d = df_sample_at's o[0]; e = |(double)d|; inlier iff d is finite and e <= max_residual; q = e
+// for an inlier, else max_residual; the term is q * q in double.  Per pose: lane l adds the terms of points l, l + 64, ... in
+// ascending order from 0.0, then v[k] = v[k] + v[k + h], h = 32 .. 1 through lane shuffles (block_ops.h: wave_reduce's order);
+// lane 0 holds the sum.  One order, whatever the batch: a pose has the same bits alone and at any batch position.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -16,12 +16,13 @@
 #include <numeric>
 #include "dfield.h"
 #include "locate.h"
+#include "block_ops.h"
+#include "world_point.h"
 
 namespace gpis {
 
 namespace {
 
-constexpr int kWave = 64;
 constexpr int kBlock = Locator::kWaves * kWave;
 
 template <int D>
@@ -45,14 +46,7 @@ __global__ void __launch_bounds__(kBlock) locate_score_kernel(const float* __res
     for (int i = lane; i < p; i += kWave) {
         const float4 l = loc[i];
         float x[3] = {0.f, 0.f, 0.f}, o[1 + D];
-        if constexpr (D == 3) {
-            x[0] = R[0] * l.x + R[3] * l.y + R[6] * l.z + t[0];
-            x[1] = R[1] * l.x + R[4] * l.y + R[7] * l.z + t[1];
-            x[2] = R[2] * l.x + R[5] * l.y + R[8] * l.z + t[2];
-        } else {
-            x[0] = R[0] * l.x + R[2] * l.y + t[0];
-            x[1] = R[1] * l.x + R[3] * l.y + t[1];
-        }
+        world_point<D>(R, t, l, x);
         df_sample_at(F, L, x[0], x[1], x[2], o);
         const float d = o[0];
         const double e = fabs((double)d);
@@ -62,7 +56,7 @@ __global__ void __launch_bounds__(kBlock) locate_score_kernel(const float* __res
         cnt += in ? 1 : 0;
     }
 #pragma unroll
-    for (int h = kWave / 2; h >= 1; h >>= 1) {
+    for (int h = kWave / 2; h >= 1; h >>= 1) {       // (block_ops.h: wave_reduce's order, the two chains interleaved)
         acc = acc + __shfl_down(acc, h, kWave);
         cnt += __shfl_down(cnt, h, kWave);
     }

@@ -11,17 +11,15 @@
 #include <cmath>
 #include "map_query.h"
 #include "mesh.h"
+#include "block_ops.h"
 
 namespace gpis {
 
 namespace {
 
 constexpr int kBlock = 256;
-constexpr int kGridCap = 2048;
 constexpr int kScanBlocks = 2048;     // partial sums per scan
 constexpr int kTile = kBlock * 4;     // scan elements per block iteration (one int4 per lane)
-
-inline int grid_for(long long n) { return (int)std::max(1ll, std::min((long long)kGridCap, (n + kBlock - 1) / kBlock)); }
 
 // Kuhn tetrahedra 0 -> e_a -> e_a + e_b -> (1,1,1) as corner bit sets (bit a = +e_a), axis orders xyz, xzy, yxz, yzx, zxy, zyx,
 // and the sign of each order as a permutation (= the sign of the tetrahedron's volume).
@@ -110,7 +108,8 @@ __global__ void __launch_bounds__(kBlock) mesh_classify_kernel(const float* __re
 }
 
 // ---- deterministic exclusive scan: per-block sums, one block over the sums, per-block rescan ----------------------------------
-// Block b owns elements [b * seg, min(n, (b + 1) * seg)), seg a multiple of kTile; the block walks its range in tiles of kTile.
+// Block b owns elements [b * seg, min(n, (b + 1) * seg)), seg a multiple of kTile; the block walks its range in tiles of kTile;
+// a tile is scanned by block_ops.h: block_incl_scan.
 __device__ __forceinline__ int4 load4(const int* __restrict__ a, long long e, long long n) {
     if (e + 4 <= n) return *reinterpret_cast<const int4*>(a + e);
     int4 v = make_int4(0, 0, 0, 0);
@@ -118,23 +117,6 @@ __device__ __forceinline__ int4 load4(const int* __restrict__ a, long long e, lo
     if (e + 1 < n) v.y = a[e + 1];
     if (e + 2 < n) v.z = a[e + 2];
     return v;
-}
-
-// inclusive scan of one value per thread over the block (64-lane wavefronts); returns it, *total = the block's sum
-template <int NT>
-__device__ __forceinline__ long long block_incl_scan(long long v, long long* sh, long long* total) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    for (int o = 1; o < 64; o <<= 1) {
-        const long long y = __shfl_up(v, o, 64);
-        if (lane >= o) v += y;
-    }
-    if (lane == 63) sh[w] = v;
-    __syncthreads();
-    long long before = 0, all = 0;
-    for (int q = 0; q < NT / 64; ++q) { if (q < w) before += sh[q]; all += sh[q]; }
-    __syncthreads();
-    *total = all;
-    return before + v;
 }
 
 __global__ void __launch_bounds__(kBlock) mesh_scan_partial_kernel(const int* __restrict__ a, long long n, long long seg,
@@ -321,15 +303,6 @@ int mesh_check_lattice(int dim, const int* n, const float* origin, const float* 
     }
     if (big || tot > MeshExtractor::kMaxLattice) return GPIS_ERR_LIMIT;
     if (npts) *npts = tot;
-    return GPIS_OK;
-}
-
-template <class T>
-static int grow(T*& p, size_t& cap, size_t need) {
-    if (need <= cap) return GPIS_OK;
-    (void)hipFree(p); p = nullptr; cap = 0;
-    GPIS_HIP(hipMalloc((void**)&p, sizeof(T) * need));
-    cap = need;
     return GPIS_OK;
 }
 

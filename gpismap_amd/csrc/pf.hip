@@ -14,6 +14,7 @@
 #include "dfield.h"
 #include "locate.h"
 #include "pf.h"
+#include "block_ops.h"
 
 namespace gpis {
 
@@ -21,7 +22,6 @@ namespace {
 
 typedef unsigned long long u64;
 constexpr int kBlock = ParticleFilter::kBlock;
-constexpr int kWave = 64;
 constexpr double kKZ = 0x1.3988e1412ed76p-17;        // 1 / sqrt(8 (65536^2 - 1) / 3)
 constexpr double kTwo32 = 4294967296.0;
 constexpr u64 kIdxMask = (1ull << 24) - 1;
@@ -141,28 +141,8 @@ __global__ void __launch_bounds__(kBlock) pf_fill_kernel(int m, double* __restri
     L[i] = 0.0; q[i] = 1ull << 32; cost[i] = 0.0; inl[i] = 0; anc[i] = i;
 }
 
-// ---- block reductions (order-free operations only: min of doubles without NaN, integer sums and maxima) --------------------
-struct OpMin { __device__ double operator()(double a, double b) const { return b < a ? b : a; } };
-struct OpAdd { __device__ u64 operator()(u64 a, u64 b) const { return a + b; } };
-struct OpMax { __device__ u64 operator()(u64 a, u64 b) const { return b > a ? b : a; } };
-
-// the value of every thread of the block combined; valid in thread 0.  sh: one slot per wavefront.  nt: the block's threads
-template <class T, class Op>
-__device__ __forceinline__ T block_reduce(T v, Op op, T* sh, int nt, T neutral) {
-    const int tid = threadIdx.x, lane = tid & (kWave - 1), wv = tid / kWave, nw = nt / kWave;
-#pragma unroll
-    for (int h = kWave / 2; h >= 1; h >>= 1) v = op(v, __shfl_down(v, h, kWave));
-    __syncthreads();                       // (sh of the previous reduction is read)
-    if (lane == 0) sh[wv] = v;
-    __syncthreads();
-    if (wv == 0) {
-        v = lane < nw ? sh[lane] : neutral;
-#pragma unroll
-        for (int h = kWave / 2; h >= 1; h >>= 1) v = op(v, __shfl_down(v, h, kWave));
-    }
-    return v;
-}
-
+// ---- block reductions (block_ops.h: block_reduce) of order-free operations only: min of doubles without NaN, integer sums
+// and maxima ------------------------------------------------------------------------------------------------------------------
 // L += beta cost and the block's minimum of the new L
 __global__ void __launch_bounds__(kBlock) pf_accum_kernel(double* __restrict__ L, const double* __restrict__ cost, int m, double beta,
                                                           double* __restrict__ bmin) {
@@ -228,32 +208,7 @@ __global__ void __launch_bounds__(1024) pf_totals_top_kernel(const u64* __restri
     }
 }
 
-// ---- the estimate: the tracker's tree (track.hip: segment_reduce and track_top_kernel state the same order) ---------------
-// a[i] += a[i + s], s = 128 .. 1 over the block's 256 threads -- LDS for s = 128, 64, lane shuffles of wave 0 below -- into
-// part[c * P + seg]
-template <int NS>
-__device__ __forceinline__ void segment_reduce(double* __restrict__ a, double (*sh)[kBlock / 2], int tid, int seg, int nseg_pow2,
-                                               double* __restrict__ part) {
-    __syncthreads();                       // (sh of the previous segment is read)
-    if (tid >= kBlock / 2)
-        for (int c = 0; c < NS; ++c) sh[c][tid - kBlock / 2] = a[c];
-    __syncthreads();
-    if (tid < kBlock / 2)
-        for (int c = 0; c < NS; ++c) a[c] = a[c] + sh[c][tid];
-    __syncthreads();
-    if (tid >= kBlock / 4 && tid < kBlock / 2)
-        for (int c = 0; c < NS; ++c) sh[c][tid - kBlock / 4] = a[c];
-    __syncthreads();
-    if (tid < kBlock / 4) {
-#pragma unroll
-        for (int c = 0; c < NS; ++c) {
-            double v = a[c] + sh[c][tid];
-            for (int s = 32; s >= 1; s >>= 1) v = v + __shfl_down(v, s, kWave);
-            if (tid == 0) part[(size_t)c * nseg_pow2 + seg] = v;
-        }
-    }
-}
-
+// ---- the estimate: the tracker's tree (block_ops.h: segment_reduce and tree_top state the order) ---------------------------
 // the terms (double)q * state column (3-D: the quaternion times +-1 towards the best particle's) and their sum per segment
 template <int D>
 __global__ void __launch_bounds__(kBlock) pf_est_terms_kernel(const double* __restrict__ state, const u64* __restrict__ q, int m,
@@ -287,26 +242,20 @@ __global__ void __launch_bounds__(kBlock) pf_est_terms_kernel(const double* __re
                 for (int c = 3; c < NS; ++c) a[c] = w * (S[c] * sg);
             }
         }
-        segment_reduce<NS>(a, sh, tid, seg, nseg_pow2, part);
+        segment_reduce<NS, kBlock>(a, sh, tid, seg, nseg_pow2, part);
     }
 }
 
-// the segment partials of every sum reduced by the same halving tree (P a power of two, in place); one block
+// the segment partials of every sum reduced by the same halving tree (tree_top; P a power of two, in place); one block
 __global__ void __launch_bounds__(1024) pf_est_top_kernel(int ns, int P, double* __restrict__ part, PfStats* __restrict__ st) {
-    for (int s = P / 2; s >= 1; s >>= 1) {
-        for (int e = threadIdx.x; e < ns * s; e += blockDim.x) {
-            const int c = e / s, i = e - c * s;
-            double* col = part + (size_t)c * P;
-            col[i] = col[i] + col[i + s];
-        }
-        __syncthreads();
-    }
+    tree_top(ns, P, part);
     if ((int)threadIdx.x < ns) st->sums[threadIdx.x] = part[(size_t)threadIdx.x * P];
 }
 
 // ---- the scan ---------------------------------------------------------------------------------------------------------------
 // out[i] = the inclusive sum of in[] within the block of 256; sums[block] = the block's total.  in == out is allowed (a thread
-// reads its own element, then writes it).
+// reads its own element, then writes it).  A one-shot scan with one barrier: block_ops.h's block_incl_scan, made for loops, pays
+// a second barrier and 10 more VGPRs here and measured slower.
 __global__ void __launch_bounds__(kBlock) pf_scan_block_kernel(const u64* in, u64* out, int n, u64* __restrict__ sums) {
     __shared__ u64 sh[kBlock / kWave];
     const int tid = threadIdx.x, lane = tid & (kWave - 1), wv = tid / kWave;
@@ -360,13 +309,8 @@ __global__ void __launch_bounds__(kBlock) pf_resample_kernel(const u64* __restri
     anc[j] = lo;
 }
 
-int grid_for(long long n) { return (int)((n + kBlock - 1) / kBlock); }
-
-long long pow2_at_least(long long n) {
-    long long p = 1;
-    while (p < n) p <<= 1;
-    return p;
-}
+// blocks of kBlock that cover n elements, uncapped: it sizes buffers and scan levels as well as launches
+int blocks_of(long long n) { return (int)((n + kBlock - 1) / kBlock); }
 
 }  // namespace
 
@@ -439,7 +383,7 @@ int ParticleFilter::ensure(long long mm) {
     if (h_stage) (void)hipHostFree(h_stage);
     d_state[0] = d_state[1] = nullptr; d_pose[0] = d_pose[1] = nullptr; d_L = nullptr; d_q = d_C = nullptr; d_cost = nullptr;
     d_inl = d_anc = nullptr; d_bmin = nullptr; d_bsum = d_bkey = d_s1 = nullptr; d_part = nullptr; h_stage = nullptr; cap_m = 0;
-    const size_t n = (size_t)mm, nb = (size_t)grid_for(mm), P = (size_t)pow2_at_least((long long)nb);
+    const size_t n = (size_t)mm, nb = (size_t)blocks_of(mm), P = (size_t)pow2_at_least((long long)nb);
     for (int k = 0; k < 2; ++k) {
         GPIS_HIP(hipMalloc((void**)&d_state[k], sizeof(double) * 7 * n));
         GPIS_HIP(hipMalloc((void**)&d_pose[k], sizeof(float) * 12 * n));
@@ -488,7 +432,7 @@ int ParticleFilter::init(int dm, const float* poses, long long mm, uint64_t sd) 
     hipStream_t s = trk.own;
     GPIS_HIP(hipMemcpyAsync(d_state[0], hs, sizeof(double) * ns * n, hipMemcpyHostToDevice, s));
     GPIS_HIP(hipMemcpyAsync(d_pose[0], hp, sizeof(float) * np * n, hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(pf_fill_kernel, dim3(grid_for(mm)), dim3(kBlock), 0, s, (int)mm, d_L, d_q, d_cost, d_inl, d_anc);
+    hipLaunchKernelGGL(pf_fill_kernel, dim3(blocks_of(mm)), dim3(kBlock), 0, s, (int)mm, d_L, d_q, d_cost, d_inl, d_anc);
     GPIS_HIP(hipGetLastError());
     GPIS_HIP(hipStreamSynchronize(s));
     dim = dm; m = mm; cur = 0; tick = 0; seed = sd;
@@ -507,9 +451,9 @@ int ParticleFilter::predict(const double* motion, const PfOpts& o, hipStream_t s
     tick += 1;
     const uint32_t k0 = (uint32_t)(seed & 0xffffffffull), k1 = (uint32_t)(seed >> 32);
     if (dim == 3)
-        hipLaunchKernelGGL(pf_predict_kernel<3>, dim3(grid_for(m)), dim3(kBlock), 0, s, d_state[cur], d_pose[cur], (int)m, tick, k0, k1, mo);
+        hipLaunchKernelGGL(pf_predict_kernel<3>, dim3(blocks_of(m)), dim3(kBlock), 0, s, d_state[cur], d_pose[cur], (int)m, tick, k0, k1, mo);
     else
-        hipLaunchKernelGGL(pf_predict_kernel<2>, dim3(grid_for(m)), dim3(kBlock), 0, s, d_state[cur], d_pose[cur], (int)m, tick, k0, k1, mo);
+        hipLaunchKernelGGL(pf_predict_kernel<2>, dim3(blocks_of(m)), dim3(kBlock), 0, s, d_state[cur], d_pose[cur], (int)m, tick, k0, k1, mo);
     GPIS_HIP(hipGetLastError());
     GPIS_HIP(hipStreamSynchronize(s));
     return GPIS_OK;
@@ -523,7 +467,7 @@ int ParticleFilter::update(const DistanceField& df, const TrackGeom& geo, const 
     to.max_residual = o.max_residual; to.huber = 1.0; to.max_var = INFINITY; to.stride = dim == 3 ? o.stride : 1;
     if (int rc = trk.setup(geo, in, cs, n, to, s)) return rc;
     const long long p = trk.points;
-    const int mi = (int)m, nb = grid_for(m), P = (int)pow2_at_least(nb), ns = dim == 3 ? 7 : 4;
+    const int mi = (int)m, nb = blocks_of(m), P = (int)pow2_at_least(nb), ns = dim == 3 ? 7 : 4;
     if (int rc = locate_score_launch(df, dim, d_pose[cur], mi, trk.d_loc, p, o.max_residual, d_cost, d_inl, s)) return rc;
     hipLaunchKernelGGL(pf_accum_kernel, dim3(nb), dim3(kBlock), 0, s, d_L, (const double*)d_cost, mi, o.beta, d_bmin);
     hipLaunchKernelGGL(pf_min_top_kernel, dim3(1), dim3(1024), 0, s, (const double*)d_bmin, nb, d_stats);
@@ -574,7 +518,7 @@ int ParticleFilter::resample(hipStream_t s) {
 // the scan of q (block scan, the scan of the block sums -- two more levels cover 2^24 -- and the adds), then the gather
 int ParticleFilter::resample_launch(hipStream_t s) {
     tick += 1;
-    const int mi = (int)m, nb1 = grid_for(m), nb2 = grid_for(nb1);
+    const int mi = (int)m, nb1 = blocks_of(m), nb2 = blocks_of(nb1);
     const u64 T = stats.T, qs = T / (u64)m, rem = T % (u64)m;
     const uint32_t ctr[4] = {0xFFFFFFFFu, tick, 0u, 1u}, key[2] = {(uint32_t)(seed & 0xffffffffull), (uint32_t)(seed >> 32)};
     uint32_t w[4];

@@ -23,11 +23,8 @@ namespace gpis {
 namespace {
 
 constexpr int kBlock = 256;
-constexpr int kGridCap = 2048;
 constexpr int kStatKept = 0, kStatLaunch = 1, kStatFree = 2, kStatReach = 3, kStatMax = 4, kStatRaised = 8;
 constexpr int kStatWords = kStatRaised + Planner::kMaxBatch;
-
-inline int grid_for(long long n) { return (int)std::max(1ll, std::min((long long)kGridCap, (n + kBlock - 1) / kBlock)); }
 
 struct PlanLat {
     int dim, nx, ny, nz;
@@ -352,15 +349,6 @@ __global__ void __launch_bounds__(1024) plan_scan_kernel(long long* __restrict__
         __syncthreads();
     }
     if (tid == 0) off[m] = carry;
-}
-
-template <class T>
-int grow(T*& p, size_t& cap, size_t need) {
-    if (need <= cap) return GPIS_OK;
-    (void)hipFree(p); p = nullptr; cap = 0;
-    GPIS_HIP(hipMalloc((void**)&p, sizeof(T) * need));
-    cap = need;
-    return GPIS_OK;
 }
 
 }  // namespace

@@ -12,17 +12,15 @@
 #include "dfield.h"
 #include "map_query.h"
 #include "render.h"
+#include "block_ops.h"
 
 namespace gpis {
 
 namespace {
 
 constexpr int kBlock = 256;
-constexpr int kGridCap = 2048;
 constexpr int kScanBlocks = kCompactBlocks;   // compaction segments (one thread each in the top scan)
 constexpr uint8_t kRunning = 255;     // status of a ray still marching
-
-inline int grid_for(long long n) { return (int)std::max(1ll, std::min((long long)kGridCap, (n + kBlock - 1) / kBlock)); }
 
 // the world point of parameter z on a ray: 3-D from its (u, v); 2-D from its host-double (c, s)
 __device__ __forceinline__ void world_point_at(const RayGeom& g, float u, float v, double c, double s, float z, float& p0, float& p1,
@@ -212,7 +210,8 @@ __global__ void __launch_bounds__(kBlock) render_count_kernel(const uint8_t* __r
     if (threadIdx.x == 0) part[blockIdx.x] = acc;
 }
 
-// exclusive prefix of the nb (<= 1024) counts in place; part[nb] = the total
+// exclusive prefix of the nb (<= 1024) counts in place; part[nb] = the total.  A one-shot scan with one barrier: block_ops.h's
+// block_incl_scan, made for loops, pays a second barrier and 11 more VGPRs here and measured slower.
 __global__ void __launch_bounds__(1024) render_top_kernel(int* __restrict__ part, int nb) {
     __shared__ int sh[1024 / 64];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -354,29 +353,21 @@ __global__ void __launch_bounds__(kBlock) render_field_kernel(RayGeom g, const d
     }
 }
 
-// the block partials reduced by one block: thread t takes the blocks t, t + 1024, ... in order, then the halving tree over the
-// threads; out = samples, hits, largest per-ray count
+// the block partials reduced by one block: thread t takes the blocks t, t + 1024, ... in order, then block_reduce over the
+// threads (integers: any order gives the same bits); out = samples, hits, largest per-ray count
 __global__ void __launch_bounds__(1024) render_field_top_kernel(const unsigned long long* __restrict__ part, int nb,
                                                                 unsigned long long* __restrict__ out) {
-    __shared__ unsigned long long sh[3][1024];
+    __shared__ unsigned long long sh[1024 / 64];
     unsigned long long a = 0, b = 0, m = 0;
     for (int k = threadIdx.x; k < nb; k += 1024) {
         a += part[3 * (size_t)k]; b += part[3 * (size_t)k + 1];
         const unsigned long long y = part[3 * (size_t)k + 2];
         m = y > m ? y : m;
     }
-    sh[0][threadIdx.x] = a; sh[1][threadIdx.x] = b; sh[2][threadIdx.x] = m;
-    __syncthreads();
-    for (int s = 512; s >= 1; s >>= 1) {
-        if ((int)threadIdx.x < s) {
-            sh[0][threadIdx.x] += sh[0][threadIdx.x + s];
-            sh[1][threadIdx.x] += sh[1][threadIdx.x + s];
-            const unsigned long long y = sh[2][threadIdx.x + s];
-            if (y > sh[2][threadIdx.x]) sh[2][threadIdx.x] = y;
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) { out[0] = sh[0][0]; out[1] = sh[1][0]; out[2] = sh[2][0]; }
+    a = block_reduce(a, OpAdd(), sh, 1024, 0ull);
+    b = block_reduce(b, OpAdd(), sh, 1024, 0ull);
+    m = block_reduce(m, OpMax(), sh, 1024, 0ull);
+    if (threadIdx.x == 0) { out[0] = a; out[1] = b; out[2] = m; }
 }
 
 }  // namespace

@@ -17,15 +17,14 @@
 #include "map_query.h"
 #include "render.h"
 #include "track.h"
+#include "block_ops.h"
+#include "world_point.h"
 
 namespace gpis {
 
 namespace {
 
 constexpr int kBlock = Tracker::kSeg;     // one segment per block in the term kernel
-constexpr int kGridCap = 2048;
-
-inline int grid_for(long long n) { return (int)std::max(1ll, std::min((long long)kGridCap, (n + kBlock - 1) / kBlock)); }
 
 struct PassPose { float R[9], t[3]; };     // the pose of one pass in float (3-D R column-major; 2-D R[0..3], t[0..1])
 
@@ -77,27 +76,14 @@ __global__ void __launch_bounds__(kBlock) track_gather_kernel(TrackGeom g, int s
     }
 }
 
-// the world point of a local point: R local + t left to right in float (no FMA: -ffp-contract=off)
-template <int D>
-__device__ __forceinline__ void world_point(const PassPose& P, const float4 l, float* __restrict__ x) {
-    if constexpr (D == 3) {
-        x[0] = P.R[0] * l.x + P.R[3] * l.y + P.R[6] * l.z + P.t[0];
-        x[1] = P.R[1] * l.x + P.R[4] * l.y + P.R[7] * l.z + P.t[1];
-        x[2] = P.R[2] * l.x + P.R[5] * l.y + P.R[8] * l.z + P.t[2];
-    } else {
-        x[0] = P.R[0] * l.x + P.R[2] * l.y + P.t[0];
-        x[1] = P.R[1] * l.x + P.R[3] * l.y + P.t[1];
-    }
-}
-
-// world points of the pass and their pre-filled records (f = NaN, zeros elsewhere)
+// world points of the pass (world_point.h) and their pre-filled records (f = NaN, zeros elsewhere)
 __global__ void __launch_bounds__(kBlock) track_transform_kernel(int dim, PassPose P, const float4* __restrict__ loc, int m,
                                                                  float* __restrict__ x, float* __restrict__ rec) {
     const int nc = 2 * (1 + dim);
     for (int j = blockIdx.x * blockDim.x + threadIdx.x; j < m; j += gridDim.x * blockDim.x) {
         const float4 l = loc[j];
-        if (dim == 3) world_point<3>(P, l, x + 3 * (size_t)j);
-        else world_point<2>(P, l, x + 2 * (size_t)j);
+        if (dim == 3) world_point<3>(P.R, P.t, l, x + 3 * (size_t)j);
+        else world_point<2>(P.R, P.t, l, x + 2 * (size_t)j);
         rec[(size_t)j * nc] = __int_as_float(0x7fc00000);
         for (int c = 1; c < nc; ++c) rec[(size_t)j * nc + c] = 0.f;
     }
@@ -146,32 +132,8 @@ __device__ __forceinline__ void point_terms(const PassPose& P, float r, const fl
     a[NS - 1] = 1.0;
 }
 
-// the halving tree a[i] += a[i + s], s = 128 .. 1 over the block's 256 threads -- LDS for s = 128, 64, lane shuffles of wave 0
-// below -- into part[c * P + seg]
-template <int NS>
-__device__ __forceinline__ void segment_reduce(double* __restrict__ a, double (*sh)[kBlock / 2], int tid, int seg, int nseg_pow2,
-                                               double* __restrict__ part) {
-    __syncthreads();                       // (sh of the previous segment is read)
-    if (tid >= kBlock / 2)
-        for (int c = 0; c < NS; ++c) sh[c][tid - kBlock / 2] = a[c];
-    __syncthreads();
-    if (tid < kBlock / 2)
-        for (int c = 0; c < NS; ++c) a[c] = a[c] + sh[c][tid];
-    __syncthreads();
-    if (tid >= kBlock / 4 && tid < kBlock / 2)
-        for (int c = 0; c < NS; ++c) sh[c][tid - kBlock / 4] = a[c];
-    __syncthreads();
-    if (tid < kBlock / 4) {
-#pragma unroll
-        for (int c = 0; c < NS; ++c) {
-            double v = a[c] + sh[c][tid];
-            for (int s = 32; s >= 1; s >>= 1) v = v + __shfl_down(v, s, 64);
-            if (tid == 0) part[(size_t)c * nseg_pow2 + seg] = v;
-        }
-    }
-}
-
-// The terms of every point and their sum per segment of 256 consecutive points (zero-padded): part[c * P + segment], c < NS:
+// The terms of every point and their sum per segment of 256 consecutive points (zero-padded; block_ops.h: segment_reduce states
+// the order): part[c * P + segment], c < NS:
 // the upper triangle of H = sum w J J^T row by row, b = sum w J r, sum w r^2, the inlier count.  Segments nseg .. P - 1 are
 // all padding (+0).  Terms in double from the float values; non-inliers contribute +0.
 template <int D>
@@ -190,7 +152,7 @@ __global__ void __launch_bounds__(kBlock) track_terms_kernel(PassPose P, const f
         float r;
         if (j < m && residual(rec + (size_t)j * NC, D, level, max_residual, max_var, r))
             point_terms<D>(P, r, rec + (size_t)j * NC + 1, x + (size_t)j * D, huber, a);
-        segment_reduce<NS>(a, sh, tid, seg, nseg_pow2, part);
+        segment_reduce<NS, kBlock>(a, sh, tid, seg, nseg_pow2, part);
     }
 }
 
@@ -200,7 +162,7 @@ __global__ void __launch_bounds__(kBlock) track_terms_kernel(PassPose P, const f
 template <int D>
 __device__ __forceinline__ bool field_residual(const PassPose& P, const float4 l, const float* __restrict__ F, const DfLattice& L,
                                                double max_residual, float* __restrict__ x, float* __restrict__ o) {
-    world_point<D>(P, l, x);
+    world_point<D>(P.R, P.t, l, x);
     df_sample_at(F, L, x[0], x[1], D == 3 ? x[2] : 0.f, o);
     const bool g_ok = isfinite(o[1]) && isfinite(o[2]) && (D == 2 || isfinite(o[3]));
     return isfinite(o[0]) && g_ok && fabs((double)o[0]) <= max_residual;
@@ -223,21 +185,14 @@ __global__ void __launch_bounds__(kBlock) track_field_terms_kernel(PassPose P, c
         for (int c = 0; c < NS; ++c) a[c] = 0.0;
         float x[D], o[1 + D];
         if (j < m && field_residual<D>(P, loc[j], F, L, max_residual, x, o)) point_terms<D>(P, o[0], o + 1, x, huber, a);
-        segment_reduce<NS>(a, sh, tid, seg, nseg_pow2, part);
+        segment_reduce<NS, kBlock>(a, sh, tid, seg, nseg_pow2, part);
     }
 }
 
-// The segment partials of every sum reduced by the same halving tree (P a power of two, in place); sum[c] = the result.  One
-// block: every level is finished (__syncthreads) before the next reads it.
+// The segment partials of every sum reduced by the same halving tree (block_ops.h: tree_top; P a power of two, in place);
+// sum[c] = the result.  One block.
 __global__ void __launch_bounds__(1024) track_top_kernel(int ns, int P, double* __restrict__ part, double* __restrict__ sum) {
-    for (int s = P / 2; s >= 1; s >>= 1) {
-        for (int e = threadIdx.x; e < ns * s; e += blockDim.x) {
-            const int c = e / s, i = e - c * s;
-            double* col = part + (size_t)c * P;
-            col[i] = col[i] + col[i + s];
-        }
-        __syncthreads();
-    }
+    tree_top(ns, P, part);
     if ((int)threadIdx.x < ns) sum[threadIdx.x] = part[(size_t)threadIdx.x * P];
 }
 
@@ -270,12 +225,6 @@ PassPose pass_pose(int dim, const double* pose) {
     for (int k = 0; k < nt; ++k) P.t[k] = (float)pose[k];
     for (int k = 0; k < nr; ++k) P.R[k] = (float)pose[nt + k];
     return P;
-}
-
-long long pow2_at_least(long long n) {
-    long long p = 1;
-    while (p < n) p <<= 1;
-    return p;
 }
 
 }  // namespace

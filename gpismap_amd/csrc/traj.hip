@@ -21,7 +21,7 @@ namespace {
 constexpr int kBlock = 256;
 constexpr int kTree = Trajectories::kMaxN;
 
-inline int grid_for(long long n) { return (int)std::max(1ll, std::min(65535ll * 16, (n + kBlock - 1) / kBlock)); }
+constexpr long long kGridCapTraj = 65535ll * 16;
 
 // s[off[p] + k] = length of path p up to its point k: a serial ascending sum of sqrtf(squares summed left to right)
 __global__ void __launch_bounds__(kBlock) traj_arc_kernel(const long long* __restrict__ off, const float* __restrict__ pts,
@@ -260,15 +260,6 @@ __global__ void __launch_bounds__(kBlock) traj_opt_kernel(const float* __restric
     }
 }
 
-template <class T>
-int grow(T*& p, size_t& cap, size_t need) {
-    if (need <= cap) return GPIS_OK;
-    (void)hipFree(p); p = nullptr; cap = 0;
-    GPIS_HIP(hipMalloc((void**)&p, sizeof(T) * need));
-    cap = need;
-    return GPIS_OK;
-}
-
 }  // namespace
 
 int traj_check_opts(const TrajOpts& o) {
@@ -357,10 +348,11 @@ int Trajectories::from_paths(const Planner& p, int NN) {
     const int mm = (int)p.npaths;
     if (int rc = ensure(mm, NN, p.dim)) return rc;
     if (int rc = grow(d_arc, cap_arc, (size_t)std::max(1ll, p.npoints))) return rc;
-    hipLaunchKernelGGL(traj_arc_kernel, dim3(grid_for(mm)), dim3(kBlock), 0, own, p.d_off, p.d_points, p.d_status, mm, p.dim, d_arc);
+    hipLaunchKernelGGL(traj_arc_kernel, dim3(grid_for(mm, kBlock, kGridCapTraj)), dim3(kBlock), 0, own, p.d_off, p.d_points, p.d_status, mm,
+                       p.dim, d_arc);
     GPIS_HIP(hipGetLastError());
-    hipLaunchKernelGGL(traj_resample_kernel, dim3(grid_for((long long)mm * NN)), dim3(kBlock), 0, own, p.d_off, p.d_points, p.d_status,
-                       d_arc, mm, NN, p.dim, d_in, d_instat);
+    hipLaunchKernelGGL(traj_resample_kernel, dim3(grid_for((long long)mm * NN, kBlock, kGridCapTraj)), dim3(kBlock), 0, own, p.d_off,
+                       p.d_points, p.d_status, d_arc, mm, NN, p.dim, d_in, d_instat);
     GPIS_HIP(hipGetLastError());
     GPIS_HIP(hipStreamSynchronize(own));
     m = mm; N = NN; dim = p.dim;

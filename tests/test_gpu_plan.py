@@ -261,6 +261,12 @@ def test_paths_equal_reference_and_hold_their_invariants():
         paths, sc, st = _paths_vs_ref(pl, pb, rc, rp, starts, 7)
         assert (st == 4).sum() > 300 and all(len(p) == 7 for p, s in zip(paths, st) if s == 4)
         _paths_vs_ref(pl, pb, rc, rp, starts[:3], 2)
+        if len(shape) == 2:
+            # more starts than one chunk of the offsets' scan holds: its carry runs across one and two chunk seams
+            many = (lo + np.random.default_rng(12).uniform(-0.08, 1.08, (2049, 2)) * (hi - lo)).astype(F32)
+            for m in (1024, 1025, 2049):
+                _, _, st = _paths_vs_ref(pl, pb, rc, rp, many[:m], 7)
+                assert (st == 4).sum() > m // 5                                               # (the mix of the 1000 above)
 
 
 # ---- determinism -------------------------------------------------------------------------------------------------------------
