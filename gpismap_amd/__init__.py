@@ -54,6 +54,12 @@ class gpis_pf_opts(C.Structure):
                 ("resample_below", C.c_double), ("stride", C.c_int)]
 
 
+class gpis_mppi_opts(C.Structure):
+    _fields_ = [("dt", C.c_double), ("lambda", C.c_double), ("gamma", C.c_double), ("sigma", C.c_double * 4),
+                ("umin", C.c_double * 4), ("umax", C.c_double * 4), ("clearance", C.c_double), ("margin", C.c_double),
+                ("w_obs", C.c_double), ("w_col", C.c_double), ("w_off", C.c_double), ("w_goal", C.c_double)]
+
+
 class gpis_plan_opts(C.Structure):
     _fields_ = [("clearance", C.c_float), ("margin", C.c_float), ("gain", C.c_float), ("connectivity", C.c_int),
                 ("max_rounds", C.c_int)]
@@ -282,6 +288,19 @@ def lib():
         L.gpis_pf_get.argtypes = [vp, dp, dp, u64p, dp, ip, ip, fp]
         L.gpis_pf_device.argtypes = [vp, C.POINTER(C.c_void_p), C.c_int]
         L.gpis_pf_info.argtypes = [vp, dp, C.c_int]
+    if hasattr(L, "gpis_mppi_create"):
+        mo = C.POINTER(gpis_mppi_opts)
+        L.gpis_mppi_default_opts.argtypes = [C.c_int, C.c_float, mo]
+        L.gpis_mppi_create.restype = vp
+        L.gpis_mppi_create.argtypes = []
+        L.gpis_mppi_destroy.argtypes = [vp]
+        L.gpis_mppi_init.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_ulonglong]
+        L.gpis_mppi_set_nominal.argtypes = [vp, dp]
+        L.gpis_mppi_step.argtypes = [vp, vp, vp, dp, dp, mo, dp, vp]
+        L.gpis_mppi_shift.argtypes = [vp]
+        L.gpis_mppi_get.argtypes = [vp, dp, dp, C.POINTER(C.c_ulonglong), ip, dp, dp]
+        L.gpis_mppi_device.argtypes = [vp, C.POINTER(C.c_void_p), C.c_int]
+        L.gpis_mppi_info.argtypes = [vp, dp, C.c_int]
     _lib = L
     return L
 
@@ -1157,6 +1176,13 @@ class DistanceField:
             self._trajectories = Trajectories()
         return self._trajectories
 
+    def control(self, controller, pose, goal=None, planner=None, stream=None, **opts):
+        """One step of a sampling Controller through this field (gpis_mppi_step): pose [t, R] as a filter's estimate returns
+        it; exactly one of `goal` (a point [dim]) and `planner` (a Planner solved on this field's lattice) gives the terminal
+        cost.  opts: the gpis_mppi_opts fields (`lam` for lambda; defaults for this field's step).  Returns (u0, info): the
+        first control of the new nominal sequence and dict(Jmin, best, neff, hits, nominal_cost, nominal_hits, T, Th, S2)."""
+        return controller.step(self, pose, goal=goal, planner=planner, stream=stream, **opts)
+
     def _step(self):
         inf = self.info()
         if inf["dim"] == 0:
@@ -1699,6 +1725,145 @@ class ParticleFilter:
         """dict of device addresses (state, poses, L, q, cost, inliers, ancestors), valid until the next init or resampling."""
         a = (C.c_void_p * 7)()
         _check(self.L.gpis_pf_device(self.h, a, 7), "gpis_pf_device")
+        return dict(zip(self.PTR_KEYS, [v or 0 for v in a]))
+
+
+def mppi_opts(dim, step=1.0, **opts):
+    """gpis_mppi_opts of the library's defaults for `dim` and a field of lattice step `step` (gpis_mppi_default_opts) with the
+    given fields replaced; `lam` stands for lambda; sigma, umin and umax take a sequence of 2 (dim 2) or 4 values."""
+    o = gpis_mppi_opts()
+    _check(lib().gpis_mppi_default_opts(int(dim), float(step), C.byref(o)), "gpis_mppi_default_opts")
+    names = {f[0] for f in gpis_mppi_opts._fields_}
+    nu = 4 if int(dim) == 3 else 2
+    for k, v in opts.items():
+        k = "lambda" if k == "lam" else k
+        if k not in names:
+            raise GpisError("unknown controller option %r" % k)
+        if k in ("sigma", "umin", "umax"):
+            v = np.asarray(v, np.float64).ravel()
+            if v.size not in (nu, 4):
+                raise GpisError("%s must have %d values" % (k, nu))
+            a = getattr(o, k)
+            for u in range(4):
+                a[u] = float(v[u]) if u < v.size else 0.0
+        else:
+            setattr(o, k, float(v))
+    return o
+
+
+class Controller:
+    """Sampled model-predictive control (MPPI) against a DistanceField, resident on the device (gpis_mppi_*): init, then per
+    control period step (or DistanceField.control) and shift; a step returns the next command, and only a small block leaves
+    the device."""
+
+    INFO_KEYS = ("inited", "dim", "rollouts", "horizon", "tick", "steps", "have_step", "ms")
+    INT_KEYS = INFO_KEYS[:7]
+    PTR_KEYS = ("U", "J", "q", "hits", "nominal_states")
+    STAT_KEYS = ("Jmin", "best", "neff", "T", "Th", "S2", "hits", "nominal_cost", "nominal_hits", "have_step")
+
+    def __init__(self, **opts):
+        """opts: gpis_mppi_opts fields that replace the defaults in every step of this controller."""
+        self.L = lib()
+        if not hasattr(self.L, "gpis_mppi_create"):
+            raise GpisError("the native library has no sampling controller (gpis_mppi_create)")
+        if self.L.gpis_device_count() < 1:
+            raise GpisError("no HIP device: gpismap_amd has no CPU fallback")
+        self.h = C.c_void_p(self.L.gpis_mppi_create())
+        if not self.h:
+            raise GpisError("gpis_mppi_create failed")
+        self.opts = dict(opts)
+        self.dim = 0
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.gpis_mppi_destroy(self.h)
+            self.h = None
+
+    __del__ = close
+
+    def init(self, dim, K, T, seed=0):
+        """K rollouts of T steps for a field of `dim`; the nominal sequence zero, tick = 0."""
+        _check(self.L.gpis_mppi_init(self.h, int(dim), int(K), int(T), C.c_ulonglong(int(seed) & 0xFFFFFFFFFFFFFFFF)), "gpis_mppi_init")
+        self.dim = int(dim)
+        return self
+
+    def set_nominal(self, U):
+        """Replace the nominal sequence by U [T, 2 / 4]."""
+        i = self.info()
+        if not i["inited"]:
+            raise GpisError("set_nominal before init")
+        U = np.ascontiguousarray(U, dtype=np.float64)
+        if U.size != i["horizon"] * (4 if i["dim"] == 3 else 2):
+            raise GpisError("U must be [T, %d]" % (4 if i["dim"] == 3 else 2))
+        _check(self.L.gpis_mppi_set_nominal(self.h, _p(U, C.c_double)), "gpis_mppi_set_nominal")
+
+    def step(self, field, pose, goal=None, planner=None, stream=None, **opts):
+        """gpis_mppi_step: see DistanceField.control."""
+        if not self.dim:
+            raise GpisError("step before init")
+        if (goal is None) == (planner is None):
+            raise GpisError("exactly one of goal and planner gives the terminal cost")
+        pose = np.ascontiguousarray(pose, dtype=np.float64).ravel()
+        if pose.size != (12 if self.dim == 3 else 6):
+            raise GpisError("pose must have %d elements" % (12 if self.dim == 3 else 6))
+        g = None
+        if goal is not None:
+            g = np.ascontiguousarray(goal, dtype=np.float64).ravel()
+            if g.size != self.dim:
+                raise GpisError("goal must have %d elements" % self.dim)
+        d = dict(self.opts)
+        d.update(opts)
+        o = mppi_opts(self.dim, field._step(), **d)
+        u0 = np.zeros(4 if self.dim == 3 else 2, dtype=np.float64)
+        _check(self.L.gpis_mppi_step(self.h, field.h, planner.h if planner is not None else None, _p(pose, C.c_double),
+                                     _p(g, C.c_double) if g is not None else None, C.byref(o), _p(u0, C.c_double), stream),
+               "gpis_mppi_step")
+        return u0, self.stats()
+
+    def shift(self):
+        """Drop the first row of the nominal sequence (the command that has been applied); the last row stays."""
+        _check(self.L.gpis_mppi_shift(self.h), "gpis_mppi_shift")
+
+    def stats(self):
+        """dict of the last step: Jmin, best, neff, T, Th, S2 (Python ints), hits (rollouts that touched an obstacle),
+        nominal_cost, nominal_hits."""
+        out = np.zeros(10, dtype=np.float64)
+        _check(self.L.gpis_mppi_get(self.h, None, None, None, None, None, _p(out, C.c_double)), "gpis_mppi_get")
+        d = dict(zip(self.STAT_KEYS, out.tolist()))
+        for k in ("best", "T", "Th", "S2", "hits", "nominal_hits", "have_step"):
+            d[k] = int(d[k])
+        return d
+
+    def info(self):
+        out = np.zeros(len(self.INFO_KEYS), dtype=np.float64)
+        _check(self.L.gpis_mppi_info(self.h, _p(out, C.c_double), out.size), "gpis_mppi_info")
+        d = dict(zip(self.INFO_KEYS, out.tolist()))
+        for k in self.INT_KEYS:
+            d[k] = int(d[k])
+        return d
+
+    def get(self):
+        """dict of host copies: U [T, 2 / 4] f64 (the nominal sequence), and of the last step J [K] f64, q [K] u64, hits [K]
+        i32, nominal_states [T + 1, dim + 2] f64, stats (see stats())."""
+        i = self.info()
+        if not i["inited"]:
+            raise GpisError("the controller is not initialised")
+        K, T, nu, ns = i["rollouts"], i["horizon"], 4 if i["dim"] == 3 else 2, i["dim"] + 2
+        out = dict(U=np.zeros((T, nu), np.float64), J=np.zeros(K, np.float64), q=np.zeros(K, np.uint64), hits=np.zeros(K, np.int32),
+                   nominal_states=np.zeros((T + 1, ns), np.float64))
+        st = np.zeros(10, dtype=np.float64)
+        _check(self.L.gpis_mppi_get(self.h, _p(out["U"], C.c_double), _p(out["J"], C.c_double), _p(out["q"], C.c_ulonglong),
+                                    _p(out["hits"], C.c_int), _p(out["nominal_states"], C.c_double), _p(st, C.c_double)), "gpis_mppi_get")
+        d = dict(zip(self.STAT_KEYS, st.tolist()))
+        for k in ("best", "T", "Th", "S2", "hits", "nominal_hits", "have_step"):
+            d[k] = int(d[k])
+        out["stats"] = d
+        return out
+
+    def device_ptrs(self):
+        """dict of device addresses (U, J, q, hits, nominal_states); U changes halves with every step and shift."""
+        a = (C.c_void_p * 5)()
+        _check(self.L.gpis_mppi_device(self.h, a, 5), "gpis_mppi_device")
         return dict(zip(self.PTR_KEYS, [v or 0 for v in a]))
 
 

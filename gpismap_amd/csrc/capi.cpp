@@ -16,6 +16,7 @@
 #include "pf.h"
 #include "plan.h"
 #include "traj.h"
+#include "mppi.h"
 #include "obsgp.h"
 #include "ongpis.h"
 
@@ -1523,6 +1524,121 @@ int gpis_pf_info(void* pf, double* out, int n) {
     const double v[11] = {f.inited ? 1.0 : 0.0, (double)f.dim, (double)f.m, (double)f.tick, (double)f.npoints, (double)f.pixels,
                           (double)f.updates, (double)f.resamples, f.resampled ? 1.0 : 0.0, f.neff, f.ms};
     for (int i = 0; i < n && i < 11; ++i) out[i] = v[i];
+    return GPIS_OK;
+}
+
+// ---- the sampling controller ----------------------------------------------------------------------------------------------
+static void mppi_opts_out(const MppiOpts& d, gpis_mppi_opts* o) {
+    o->dt = d.dt; o->lambda = d.lambda; o->gamma = d.gamma; o->clearance = d.clearance; o->margin = d.margin;
+    o->w_obs = d.w_obs; o->w_col = d.w_col; o->w_off = d.w_off; o->w_goal = d.w_goal;
+    for (int u = 0; u < 4; ++u) { o->sigma[u] = d.sigma[u]; o->umin[u] = d.umin[u]; o->umax[u] = d.umax[u]; }
+}
+int gpis_mppi_default_opts(int dim, float step, gpis_mppi_opts* o) {
+    if (!o || (dim != 2 && dim != 3) || !std::isfinite(step) || !(step > 0.f)) return GPIS_ERR_ARG;
+    MppiOpts d;
+    mppi_default_opts(dim, step, &d);
+    mppi_opts_out(d, o);
+    return GPIS_OK;
+}
+void* gpis_mppi_create(void) {
+    if (gpis_device_count() < 1) { fprintf(stderr, "[gpismap_amd] no HIP device\n"); return nullptr; }
+    Controller* c = new (std::nothrow) Controller();
+    if (c && !c->own) { delete c; return nullptr; }
+    return c;
+}
+void gpis_mppi_destroy(void* mppi) { delete (Controller*)mppi; }
+int gpis_mppi_init(void* mppi, int dim, int K, int T, unsigned long long seed) {
+    if (!mppi || (dim != 2 && dim != 3) || K < 1 || T < 1) return GPIS_ERR_ARG;
+    if (K > Controller::kMaxRollouts || T > Controller::kMaxSteps) return GPIS_ERR_LIMIT;
+    Controller& c = *(Controller*)mppi;
+    try { return c.init(dim, K, T, seed); } catch (...) { c.inited = false; return GPIS_ERR_STATE; }
+}
+int gpis_mppi_set_nominal(void* mppi, const double* U) {
+    if (!mppi || !U) return GPIS_ERR_ARG;
+    Controller& c = *(Controller*)mppi;
+    if (!c.inited) return GPIS_ERR_STATE;
+    for (int k = 0; k < c.T * c.nu(); ++k) if (!std::isfinite(U[k])) return GPIS_ERR_ARG;
+    DeviceScope ds(c.device);
+    return c.set_nominal(U);
+}
+int gpis_mppi_step(void* mppi, void* df, void* plan, const double* pose, const double* goal, const gpis_mppi_opts* opts, double* u0,
+                   void* stream) {
+    if (!mppi || !df || !pose || (plan != nullptr) == (goal != nullptr)) return GPIS_ERR_ARG;
+    Controller& c = *(Controller*)mppi;
+    if (!c.inited) return GPIS_ERR_STATE;
+    const DistanceField& f = *(const DistanceField*)df;
+    if (!f.valid) return GPIS_ERR_STATE;
+    if (f.dim != c.dim || f.device != c.device) return GPIS_ERR_ARG;
+    MppiOpts o;
+    if (opts) {
+        o.dt = opts->dt; o.lambda = opts->lambda; o.gamma = opts->gamma; o.clearance = opts->clearance; o.margin = opts->margin;
+        o.w_obs = opts->w_obs; o.w_col = opts->w_col; o.w_off = opts->w_off; o.w_goal = opts->w_goal;
+        for (int u = 0; u < 4; ++u) { o.sigma[u] = opts->sigma[u]; o.umin[u] = opts->umin[u]; o.umax[u] = opts->umax[u]; }
+    } else mppi_default_opts(c.dim, f.step, &o);
+    if (int rc = mppi_check_opts(o)) return rc;
+    const int dim = c.dim;
+    double start[5];
+    for (int a = 0; a < dim + 2; ++a) if (!std::isfinite(pose[a])) return GPIS_ERR_ARG;
+    const double r0 = pose[dim], r1 = pose[dim + 1], n = std::sqrt(r0 * r0 + r1 * r1);
+    if (!(n > 0.0) || !std::isfinite(n)) return GPIS_ERR_ARG;
+    for (int a = 0; a < dim; ++a) start[a] = pose[a];
+    start[dim] = r0 / n; start[dim + 1] = r1 / n;
+    if (goal) for (int a = 0; a < dim; ++a) if (!std::isfinite(goal[a])) return GPIS_ERR_ARG;
+    const Planner* pl = (const Planner*)plan;
+    if (pl) {
+        if (!pl->valid) return GPIS_ERR_STATE;
+        if (pl->dim != dim || pl->device != c.device || pl->step != f.step) return GPIS_ERR_ARG;
+        for (int a = 0; a < 3; ++a) if (pl->n[a] != f.n[a] || pl->origin[a] != f.origin[a]) return GPIS_ERR_ARG;
+    }
+    DeviceScope ds(c.device);
+    try {
+        const int rc = c.step(f, pl, start, goal, o, c.stream_or_own((hipStream_t)stream));
+        if (rc == GPIS_OK && u0) for (int u = 0; u < c.nu(); ++u) u0[u] = c.stats.u0[u];
+        return rc;
+    } catch (...) { return GPIS_ERR_STATE; }
+}
+int gpis_mppi_shift(void* mppi) {
+    if (!mppi) return GPIS_ERR_ARG;
+    Controller& c = *(Controller*)mppi;
+    if (!c.inited) return GPIS_ERR_STATE;
+    DeviceScope ds(c.device);
+    return c.shift();
+}
+int gpis_mppi_get(void* mppi, double* U, double* J, unsigned long long* q, int* hits, double* nominal_states, double* stats) {
+    if (!mppi) return GPIS_ERR_ARG;
+    const Controller& c = *(const Controller*)mppi;
+    if (!c.inited) return GPIS_ERR_STATE;
+    DeviceScope ds(c.device);
+    const size_t k = (size_t)c.K;
+    hipStream_t s = c.own;
+    if (U) GPIS_HIP(hipMemcpyAsync(U, c.d_U[c.cur], sizeof(double) * (size_t)c.T * c.nu(), hipMemcpyDeviceToHost, s));
+    if (J) GPIS_HIP(hipMemcpyAsync(J, c.d_J, sizeof(double) * k, hipMemcpyDeviceToHost, s));
+    if (q) GPIS_HIP(hipMemcpyAsync(q, c.d_q, sizeof(unsigned long long) * k, hipMemcpyDeviceToHost, s));
+    if (hits) GPIS_HIP(hipMemcpyAsync(hits, c.d_hits, sizeof(int) * k, hipMemcpyDeviceToHost, s));
+    if (nominal_states)
+        GPIS_HIP(hipMemcpyAsync(nominal_states, c.d_nom, sizeof(double) * (size_t)(c.T + 1) * (c.dim + 2), hipMemcpyDeviceToHost, s));
+    GPIS_HIP(hipStreamSynchronize(s));
+    if (stats) {
+        const double v[10] = {c.stats.jmin, (double)c.stats.best, c.neff, (double)c.stats.T, (double)c.stats.Th, (double)c.stats.S2,
+                              (double)c.stats.nhit, c.stats.nominal_cost, (double)c.stats.nominal_hits, c.have_step ? 1.0 : 0.0};
+        for (int i = 0; i < 10; ++i) stats[i] = v[i];
+    }
+    return GPIS_OK;
+}
+int gpis_mppi_device(void* mppi, void** ptrs, int n) {
+    if (!mppi || !ptrs || n < 0) return GPIS_ERR_ARG;
+    const Controller& c = *(const Controller*)mppi;
+    if (!c.inited) return GPIS_ERR_STATE;
+    void* v[5] = {(void*)c.d_U[c.cur], (void*)c.d_J, (void*)c.d_q, (void*)c.d_hits, (void*)c.d_nom};
+    for (int i = 0; i < n && i < 5; ++i) ptrs[i] = v[i];
+    return GPIS_OK;
+}
+int gpis_mppi_info(void* mppi, double* out, int n) {
+    if (!mppi || !out || n < 0) return GPIS_ERR_ARG;
+    const Controller& c = *(const Controller*)mppi;
+    const double v[8] = {c.inited ? 1.0 : 0.0, (double)c.dim, (double)c.K, (double)c.T, (double)c.tick, (double)c.steps,
+                         c.have_step ? 1.0 : 0.0, c.ms};
+    for (int i = 0; i < n && i < 8; ++i) out[i] = v[i];
     return GPIS_OK;
 }
 

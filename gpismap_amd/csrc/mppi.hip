@@ -1,0 +1,443 @@
+// The sampling controller on the device (mppi.h; the contract: tests/mppi_ref.py).  Per step, four launches:
+// the rollouts (one thread per rollout, 64-thread workgroups: T serial steps of U Philox blocks, the unicycle / body-frame
+// model, the Cayley heading, one field sample; J, the hit count and the block's minimum of J), the weights (every workgroup
+// reduces the block minima itself, then q = floor(exp(-(J - Jmin) / lambda) 2^32) with the block's integer totals and best
+// key), the update's terms (a workgroup per 256-rollout segment and 8 (t, u) columns: every thread regenerates its clamped
+// perturbation from the counter and the old Ubar, then the tracker's segment tree), and one top workgroup (the integer totals,
+// the tree over the segment partials, the new Ubar into the other half of the ping-pong buffer, the nominal rollout by one
+// thread, the stats block).  No kernel waits on another workgroup; no atomics; every double expression is written left to right
+// as the reference states it (-ffp-contract=off).
+#include <chrono>
+#include <cmath>
+#include <cstring>
+#include "dfield.h"
+#include "plan.h"
+#include "mppi.h"
+#include "block_ops.h"
+#include "philox.h"
+
+namespace gpis {
+
+namespace {
+
+typedef unsigned long long u64;
+constexpr int kBlock = Controller::kBlock, kRollBlock = Controller::kRollBlock, kCols = Controller::kCols;
+constexpr double kTwo32 = 4294967296.0;
+constexpr uint32_t kTag = 2u;            // the counter's last word: 0 and 1 are the particle filter's
+constexpr int kSums = 5;                 // block partials of the weigh kernel: q, q >> 16, (q >> 16)^2, hit > 0, the best key
+
+struct MppiParams {
+    double dt, half_dt, gamma, lambda;
+    double sigma[4], umin[4], umax[4];
+    double clearance, band, margin;      // band = clearance + margin
+    double w_obs, w_col, w_off, w_goal;
+    double start[5], goal[3];
+    int K, T, use_plan;
+    uint32_t tick, k0, k1;
+};
+
+// the clamped control and its perturbation of rollout k at column t * U + u
+__device__ __forceinline__ double mppi_control(uint32_t k, uint32_t col, double ub, double sigma, double lo, double hi, const MppiParams& p,
+                                               double* __restrict__ du) {
+    const double z = k == 0u ? 0.0 : philox_deviate(k, p.tick, col, kTag, p.k0, p.k1);
+    const double e = sigma * z;
+    double v = ub + e;
+    v = v < lo ? lo : v;
+    v = v > hi ? hi : v;
+    *du = v - ub;
+    return v;
+}
+
+// One rollout: the T steps, the stage and control costs, the terminal term.  Ubar is read through a plain pointer: the top
+// kernel rolls the sequence it has just written.
+template <int D, bool STATES>
+__device__ __forceinline__ void mppi_roll(uint32_t k, const float* __restrict__ F, const DfLattice& L, const float* __restrict__ cost,
+                                          const double* Ubar, const MppiParams& p, double* states, double* __restrict__ Jout,
+                                          int* __restrict__ hout) {
+    constexpr int U = D == 3 ? 4 : 2, NS = D + 2;
+    DfLattice Lc = L;
+    Lc.dim = D;                                          // (a constant dim keeps the sampler's output in registers)
+    double pos[3] = {p.start[0], p.start[1], D == 3 ? p.start[2] : 0.0};
+    double c = p.start[D], s = p.start[D + 1];
+    double J = 0.0;
+    int hits = 0;
+    if constexpr (STATES) {
+#pragma unroll
+        for (int a = 0; a < D; ++a) states[a] = pos[a];
+        states[D] = c; states[D + 1] = s;
+    }
+    for (int t = 0; t < p.T; ++t) {
+        double v[U], acc = 0.0;
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const double ub = Ubar[t * U + u];
+            double du;
+            v[u] = mppi_control(k, (uint32_t)(t * U + u), ub, p.sigma[u], p.umin[u], p.umax[u], p, &du);
+            if (p.sigma[u] > 0.0) acc = acc + (ub * du) / (p.sigma[u] * p.sigma[u]);
+        }
+        // translation with the heading from before the step
+        const double bx = v[0] * p.dt;
+        if constexpr (D == 2) {
+            pos[0] = pos[0] + c * bx;
+            pos[1] = pos[1] + s * bx;
+        } else {
+            const double by = v[1] * p.dt;
+            pos[0] = pos[0] + (c * bx - s * by);
+            pos[1] = pos[1] + (s * bx + c * by);
+            pos[2] = pos[2] + v[2] * p.dt;
+        }
+        // heading: the Cayley map of half the turn
+        const double a = p.half_dt * v[U - 1];
+        const double den = 1.0 + a * a;
+        const double cn = (1.0 - a * a) / den, sn = (a + a) / den;
+        const double c1 = c * cn - s * sn, s1 = s * cn + c * sn;
+        const double n = sqrt(c1 * c1 + s1 * s1);
+        c = c1 / n; s = s1 / n;
+        if constexpr (STATES) {
+            double* S = states + (size_t)(t + 1) * NS;
+#pragma unroll
+            for (int q = 0; q < D; ++q) S[q] = pos[q];
+            S[D] = c; S[D + 1] = s;
+        }
+        // stage cost
+        float o[1 + D];
+        df_sample_at(F, Lc, (float)pos[0], (float)pos[1], D == 3 ? (float)pos[2] : 0.f, o);
+        const double d = (double)o[0];
+        double j = 0.0;
+        if (d != d) j = p.w_off;
+        else if (d < p.clearance) { j = p.w_col; hits += 1; }
+        else if (d < p.band) {
+            const double r = (p.band - d) / p.margin;
+            j = (p.w_obs * r) * r;
+        }
+        const double g = p.gamma * acc;
+        J = (J + j) + g;
+    }
+    // terminal term
+    if (p.use_plan) {
+        const float st = L.st;
+        const float ux = ((float)pos[0] - L.ox) / st, uy = ((float)pos[1] - L.oy) / st, uz = D == 3 ? ((float)pos[2] - L.oz) / st : 0.f;
+        const bool in = (ux >= 0.f && ux <= (float)(L.nx - 1)) && (uy >= 0.f && uy <= (float)(L.ny - 1)) &&
+                        (D == 2 || (uz >= 0.f && uz <= (float)(L.nz - 1)));
+        if (!in) J = J + p.w_off;
+        else {
+            const int ix = min((int)floorf(ux + 0.5f), L.nx - 1), iy = min((int)floorf(uy + 0.5f), L.ny - 1);
+            const int iz = D == 3 ? min((int)floorf(uz + 0.5f), L.nz - 1) : 0;
+            const float G = cost[((long long)iz * L.ny + iy) * L.nx + ix];
+            if (isinf(G)) J = J + p.w_col;
+            else J = J + p.w_goal * (double)G;
+        }
+    } else {
+        double s2 = (pos[0] - p.goal[0]) * (pos[0] - p.goal[0]);
+        s2 = s2 + (pos[1] - p.goal[1]) * (pos[1] - p.goal[1]);
+        if constexpr (D == 3) s2 = s2 + (pos[2] - p.goal[2]) * (pos[2] - p.goal[2]);
+        J = J + p.w_goal * sqrt(s2);
+    }
+    *Jout = J;
+    *hout = hits;
+}
+
+template <int D>
+__global__ void __launch_bounds__(kRollBlock) mppi_rollout_kernel(const float* __restrict__ F, DfLattice L, const float* __restrict__ cost,
+                                                                  const double* __restrict__ Ubar, MppiParams p, double* __restrict__ J,
+                                                                  int* __restrict__ hits, double* __restrict__ bmin) {
+    __shared__ double sh[1];
+    const int k = (int)(blockIdx.x * kRollBlock + threadIdx.x);
+    double v = INFINITY;
+    if (k < p.K) {
+        int h;
+        mppi_roll<D, false>((uint32_t)k, F, L, cost, Ubar, p, nullptr, &v, &h);
+        J[k] = v;
+        hits[k] = h;
+    }
+    v = block_reduce(v, OpMin(), sh, kRollBlock, (double)INFINITY);
+    if (threadIdx.x == 0) bmin[blockIdx.x] = v;
+}
+
+// ---- block reductions (block_ops.h: block_reduce) of order-free operations only: min of doubles without NaN, integer sums and
+// minima ------------------------------------------------------------------------------------------------------------------------
+// Jmin from the block minima (every workgroup for itself), then q and the block's integer partials
+__global__ void __launch_bounds__(kBlock) mppi_weigh_kernel(const double* __restrict__ J, const int* __restrict__ hits, int K, int nbr,
+                                                            int nb, const double* __restrict__ bmin, double lambda,
+                                                            u64* __restrict__ q, u64* __restrict__ bsum, MppiStats* __restrict__ st) {
+    __shared__ double shd[kBlock / kWave];
+    __shared__ u64 sh[kBlock / kWave];
+    __shared__ double jmin_s;
+    double m = INFINITY;
+    for (int b = threadIdx.x; b < nbr; b += kBlock) m = OpMin()(m, bmin[b]);
+    m = block_reduce(m, OpMin(), shd, kBlock, (double)INFINITY);
+    if (threadIdx.x == 0) jmin_s = m;
+    __syncthreads();
+    const double jmin = jmin_s;
+    const int i = (int)(blockIdx.x * kBlock + threadIdx.x);
+    u64 v = 0, hit = 0, key = ~0ull;
+    if (i < K) {
+        const double Ji = J[i];
+        const double w = exp(-((Ji - jmin) / lambda));
+        v = (u64)floor(w * kTwo32);
+        q[i] = v;
+        hit = hits[i] > 0 ? 1ull : 0ull;
+        if (Ji == jmin) key = (u64)i;
+    }
+    const u64 h = v >> 16;
+    const u64 t = block_reduce(v, OpAdd(), sh, kBlock, 0ull);
+    const u64 th = block_reduce(h, OpAdd(), sh, kBlock, 0ull);
+    const u64 s2 = block_reduce(h * h, OpAdd(), sh, kBlock, 0ull);
+    const u64 nh = block_reduce(hit, OpAdd(), sh, kBlock, 0ull);
+    const u64 kb = block_reduce(key, OpMin(), sh, kBlock, ~0ull);
+    if (threadIdx.x == 0) {
+        bsum[blockIdx.x] = t; bsum[(size_t)nb + blockIdx.x] = th; bsum[2 * (size_t)nb + blockIdx.x] = s2;
+        bsum[3 * (size_t)nb + blockIdx.x] = nh; bsum[4 * (size_t)nb + blockIdx.x] = kb;
+        if (blockIdx.x == 0) st->jmin = jmin;
+    }
+}
+
+// ---- the update: the tracker's tree (block_ops.h: segment_reduce and tree_top state the order) -------------------------------
+// the terms (double)q * d_u of kCols columns and their sums per segment; d_u regenerated from the counter and the old Ubar
+template <int D>
+__global__ void __launch_bounds__(kBlock) mppi_update_kernel(const double* __restrict__ Ubar, const u64* __restrict__ q, MppiParams p,
+                                                             int nseg_pow2, double* __restrict__ part) {
+    constexpr int U = D == 3 ? 4 : 2;
+    static_assert(kCols % U == 0, "a chunk of columns starts at control 0");
+    __shared__ double sh[kCols][kBlock / 2];
+    const int tid = threadIdx.x, seg = blockIdx.x, col0 = (int)blockIdx.y * kCols, ncol = p.T * U;
+    const int k = seg * kBlock + tid;
+    double a[kCols];
+#pragma unroll
+    for (int c = 0; c < kCols; ++c) a[c] = 0.0;
+    if (k < p.K) {
+        const double w = (double)q[k];
+#pragma unroll
+        for (int c = 0; c < kCols; ++c) {
+            const int col = col0 + c;
+            if (col < ncol) {
+                double du;
+                (void)mppi_control((uint32_t)k, (uint32_t)col, Ubar[col], p.sigma[c % U], p.umin[c % U], p.umax[c % U], p, &du);
+                a[c] = w * du;
+            }
+        }
+    }
+    segment_reduce<kCols, kBlock>(a, sh, tid, seg, nseg_pow2, part + (size_t)col0 * nseg_pow2);
+}
+
+// One workgroup: the integer totals, the tree over the segment partials (tree_top; P a power of two, in place), the new Ubar
+// into the other half, then thread 0 rolls it (z = 0, the rollout's own code) and writes the stats block.
+template <int D>
+__global__ void __launch_bounds__(kBlock) mppi_top_kernel(const float* __restrict__ F, DfLattice L, const float* __restrict__ cost,
+                                                          const double* __restrict__ Uold, double* Unew, MppiParams p, int nb, int P,
+                                                          const u64* __restrict__ bsum, double* __restrict__ part,
+                                                          double* __restrict__ nom, MppiStats* __restrict__ st) {
+    constexpr int U = D == 3 ? 4 : 2;
+    __shared__ u64 sh[kBlock / kWave];
+    __shared__ u64 tot_s;
+    u64 t = 0, th = 0, s2 = 0, nh = 0, key = ~0ull;
+    for (int b = threadIdx.x; b < nb; b += kBlock) {
+        t += bsum[b]; th += bsum[(size_t)nb + b]; s2 += bsum[2 * (size_t)nb + b]; nh += bsum[3 * (size_t)nb + b];
+        key = OpMin()(key, bsum[4 * (size_t)nb + b]);
+    }
+    t = block_reduce(t, OpAdd(), sh, kBlock, 0ull);
+    th = block_reduce(th, OpAdd(), sh, kBlock, 0ull);
+    s2 = block_reduce(s2, OpAdd(), sh, kBlock, 0ull);
+    nh = block_reduce(nh, OpAdd(), sh, kBlock, 0ull);
+    key = block_reduce(key, OpMin(), sh, kBlock, ~0ull);
+    if (threadIdx.x == 0) {
+        st->T = t; st->Th = th; st->S2 = s2; st->nhit = (int)nh; st->best = (int)key; st->pad = 0;
+        tot_s = t;
+    }
+    const int ncol = p.T * U;
+    tree_top(ncol, P, part);
+    __syncthreads();                                     // (P = 1: the tree has no level and no barrier)
+    const double Tq = (double)tot_s;
+    for (int e = threadIdx.x; e < ncol; e += kBlock) {
+        const int u = e % U;
+        const double lo = u == 0 ? p.umin[0] : u == 1 ? p.umin[1] : u == 2 ? p.umin[2] : p.umin[3];
+        const double hi = u == 0 ? p.umax[0] : u == 1 ? p.umax[1] : u == 2 ? p.umax[2] : p.umax[3];
+        double v = Uold[e] + part[(size_t)e * P] / Tq;
+        v = v < lo ? lo : v;
+        v = v > hi ? hi : v;
+        Unew[e] = v;
+    }
+    __threadfence();
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double Jn;
+        int hn;
+        mppi_roll<D, true>(0u, F, L, cost, Unew, p, nom, &Jn, &hn);
+        st->nominal_cost = Jn; st->nominal_hits = hn;
+#pragma unroll
+        for (int u = 0; u < 4; ++u) st->u0[u] = u < U ? Unew[u] : 0.0;
+    }
+}
+
+}  // namespace
+
+// ---- host -------------------------------------------------------------------------------------------------------------------
+void mppi_default_opts(int dim, float step, MppiOpts* o) {
+    const double st = (double)step;
+    o->dt = 0.1; o->lambda = 1.0; o->gamma = 0.1;
+    o->clearance = st; o->margin = 2.0 * st;
+    o->w_obs = 1.0; o->w_col = 100.0; o->w_off = 100.0; o->w_goal = 1.0;
+    for (int u = 0; u < 4; ++u) { o->sigma[u] = 0.0; o->umin[u] = 0.0; o->umax[u] = 0.0; }
+    if (dim == 3) {
+        for (int u = 0; u < 4; ++u) { o->sigma[u] = 0.25; o->umin[u] = -1.0; o->umax[u] = 1.0; }
+        o->sigma[3] = 0.5;
+    } else {
+        o->sigma[0] = 0.25; o->sigma[1] = 0.5;
+        o->umin[0] = 0.0; o->umax[0] = 1.0; o->umin[1] = -1.0; o->umax[1] = 1.0;
+    }
+}
+
+int mppi_check_opts(const MppiOpts& o) {
+    const double* all = &o.dt;
+    for (size_t i = 0; i < sizeof(MppiOpts) / sizeof(double); ++i) if (!std::isfinite(all[i])) return GPIS_ERR_ARG;
+    if (o.dt <= 0.0 || o.lambda <= 0.0 || o.margin < 0.0 || o.w_obs < 0.0 || o.w_col < 0.0 || o.w_off < 0.0 || o.w_goal < 0.0)
+        return GPIS_ERR_ARG;
+    for (int u = 0; u < 4; ++u) if (o.sigma[u] < 0.0 || o.umin[u] > o.umax[u]) return GPIS_ERR_ARG;
+    return GPIS_OK;
+}
+
+Controller::Controller() {
+    (void)hipGetDevice(&device);
+    if (hipStreamCreateWithFlags(&own, hipStreamNonBlocking) != hipSuccess) own = nullptr;
+}
+
+Controller::~Controller() { (void)bind(-1); }
+
+int Controller::bind(int dev) {
+    if (dev == device && dev >= 0) return GPIS_OK;
+    {
+        DeviceScope ds(device);
+        if (own) (void)hipStreamSynchronize(own);
+        for (void* p : {(void*)d_U[0], (void*)d_U[1], (void*)d_J, (void*)d_q, (void*)d_hits, (void*)d_bmin, (void*)d_bsum, (void*)d_part,
+                        (void*)d_nom, (void*)d_stats})
+            (void)hipFree(p);
+        if (h_stats) (void)hipHostFree(h_stats);
+        if (own) (void)hipStreamDestroy(own);
+    }
+    d_U[0] = d_U[1] = nullptr; d_J = nullptr; d_q = nullptr; d_hits = nullptr; d_bmin = nullptr; d_bsum = nullptr; d_part = nullptr;
+    d_nom = nullptr; d_stats = nullptr; h_stats = nullptr; own = nullptr;
+    cap_u = cap_k = cap_part = cap_nom = 0;
+    inited = have_step = false; dim = K = T = 0;
+    device = dev;
+    if (dev < 0) return GPIS_OK;
+    DeviceScope ds(dev);
+    GPIS_HIP(hipStreamCreateWithFlags(&own, hipStreamNonBlocking));
+    return GPIS_OK;
+}
+
+int Controller::ensure(int dm, int k, int t) {
+    if (!d_stats) GPIS_HIP(hipMalloc((void**)&d_stats, sizeof(MppiStats)));
+    if (!h_stats) GPIS_HIP(hipHostMalloc((void**)&h_stats, sizeof(MppiStats)));
+    const size_t nu_ = dm == 3 ? 4 : 2, ncol = (size_t)t * nu_, colp = (ncol + kCols - 1) / kCols * kCols;
+    const size_t nseg = ((size_t)k + kBlock - 1) / kBlock, P = (size_t)pow2_at_least((long long)nseg);
+    if (ncol > cap_u) {
+        for (int h = 0; h < 2; ++h) { (void)hipFree(d_U[h]); d_U[h] = nullptr; }
+        cap_u = 0;
+        for (int h = 0; h < 2; ++h) GPIS_HIP(hipMalloc((void**)&d_U[h], sizeof(double) * ncol));     // (halves apart: no shared line)
+        cap_u = ncol;
+    }
+    if ((size_t)k > cap_k) {
+        for (void* p : {(void*)d_J, (void*)d_q, (void*)d_hits, (void*)d_bmin, (void*)d_bsum}) (void)hipFree(p);
+        d_J = nullptr; d_q = nullptr; d_hits = nullptr; d_bmin = nullptr; d_bsum = nullptr; cap_k = 0;
+        GPIS_HIP(hipMalloc((void**)&d_J, sizeof(double) * k));
+        GPIS_HIP(hipMalloc((void**)&d_q, sizeof(u64) * k));
+        GPIS_HIP(hipMalloc((void**)&d_hits, sizeof(int) * k));
+        GPIS_HIP(hipMalloc((void**)&d_bmin, sizeof(double) * (((size_t)k + kRollBlock - 1) / kRollBlock)));
+        GPIS_HIP(hipMalloc((void**)&d_bsum, sizeof(u64) * kSums * nseg));
+        cap_k = (size_t)k;
+    }
+    if (colp * P > cap_part) {
+        (void)hipFree(d_part); d_part = nullptr; cap_part = 0;
+        GPIS_HIP(hipMalloc((void**)&d_part, sizeof(double) * colp * P));
+        cap_part = colp * P;
+    }
+    const size_t nn = (size_t)(t + 1) * (size_t)(dm + 2);
+    if (nn > cap_nom) {
+        (void)hipFree(d_nom); d_nom = nullptr; cap_nom = 0;
+        GPIS_HIP(hipMalloc((void**)&d_nom, sizeof(double) * nn));
+        cap_nom = nn;
+    }
+    return GPIS_OK;
+}
+
+int Controller::init(int dm, int k, int t, uint64_t sd) {
+    int dev = -1;
+    GPIS_HIP(hipGetDevice(&dev));
+    if (int rc = bind(dev)) return rc;
+    if (!own) return GPIS_ERR_HIP;
+    inited = have_step = false;
+    if (int rc = ensure(dm, k, t)) return rc;
+    const size_t ncol = (size_t)t * (dm == 3 ? 4 : 2);
+    GPIS_HIP(hipMemsetAsync(d_U[0], 0, sizeof(double) * ncol, own));
+    GPIS_HIP(hipMemsetAsync(d_U[1], 0, sizeof(double) * ncol, own));
+    GPIS_HIP(hipMemsetAsync(d_J, 0, sizeof(double) * k, own));
+    GPIS_HIP(hipMemsetAsync(d_q, 0, sizeof(u64) * k, own));
+    GPIS_HIP(hipMemsetAsync(d_hits, 0, sizeof(int) * k, own));
+    GPIS_HIP(hipMemsetAsync(d_nom, 0, sizeof(double) * (size_t)(t + 1) * (size_t)(dm + 2), own));
+    GPIS_HIP(hipStreamSynchronize(own));
+    dim = dm; K = k; T = t; cur = 0; tick = 0; seed = sd; steps = 0; neff = 0.0; ms = 0.0;
+    stats = MppiStats{};
+    inited = true;
+    return GPIS_OK;
+}
+
+int Controller::set_nominal(const double* U) {
+    GPIS_HIP(hipMemcpyAsync(d_U[cur], U, sizeof(double) * (size_t)T * nu(), hipMemcpyHostToDevice, own));
+    GPIS_HIP(hipStreamSynchronize(own));
+    return GPIS_OK;
+}
+
+int Controller::shift() {
+    // rows 1 .. T - 1 into rows 0 .. T - 2 of the other half, the last row twice
+    const size_t row = sizeof(double) * (size_t)nu();
+    const int to = cur ^ 1;
+    if (T > 1) GPIS_HIP(hipMemcpyAsync(d_U[to], d_U[cur] + nu(), row * (size_t)(T - 1), hipMemcpyDeviceToDevice, own));
+    GPIS_HIP(hipMemcpyAsync(d_U[to] + (size_t)(T - 1) * nu(), d_U[cur] + (size_t)(T - 1) * nu(), row, hipMemcpyDeviceToDevice, own));
+    GPIS_HIP(hipStreamSynchronize(own));
+    cur = to;
+    return GPIS_OK;
+}
+
+int Controller::step(const DistanceField& df, const Planner* pl, const double* start, const double* goal, const MppiOpts& o,
+                     hipStream_t s) {
+    const auto t0 = std::chrono::steady_clock::now();
+    MppiParams p{};
+    p.dt = o.dt; p.half_dt = 0.5 * o.dt; p.gamma = o.gamma; p.lambda = o.lambda;
+    for (int u = 0; u < 4; ++u) { p.sigma[u] = o.sigma[u]; p.umin[u] = o.umin[u]; p.umax[u] = o.umax[u]; }
+    p.clearance = o.clearance; p.band = o.clearance + o.margin; p.margin = o.margin;
+    p.w_obs = o.w_obs; p.w_col = o.w_col; p.w_off = o.w_off; p.w_goal = o.w_goal;
+    for (int a = 0; a < dim + 2; ++a) p.start[a] = start[a];
+    if (goal) for (int a = 0; a < dim; ++a) p.goal[a] = goal[a];
+    p.K = K; p.T = T; p.use_plan = pl ? 1 : 0;
+    p.tick = tick + 1; p.k0 = (uint32_t)(seed & 0xffffffffull); p.k1 = (uint32_t)(seed >> 32);
+    const DfLattice L = df.lattice();
+    const float* cost = pl ? pl->d_cost : nullptr;
+    const int nbr = (K + kRollBlock - 1) / kRollBlock, nb = (K + kBlock - 1) / kBlock, P = (int)pow2_at_least(nb);
+    const int ncol = T * nu(), nchunk = (ncol + kCols - 1) / kCols, to = cur ^ 1;
+    const double* Uc = d_U[cur];
+    if (dim == 3) {
+        hipLaunchKernelGGL(mppi_rollout_kernel<3>, dim3(nbr), dim3(kRollBlock), 0, s, (const float*)df.d_dist, L, cost, Uc, p, d_J, d_hits, d_bmin);
+        hipLaunchKernelGGL(mppi_weigh_kernel, dim3(nb), dim3(kBlock), 0, s, (const double*)d_J, (const int*)d_hits, K, nbr, nb,
+                           (const double*)d_bmin, o.lambda, d_q, d_bsum, d_stats);
+        hipLaunchKernelGGL(mppi_update_kernel<3>, dim3(P, nchunk), dim3(kBlock), 0, s, Uc, (const u64*)d_q, p, P, d_part);
+        hipLaunchKernelGGL(mppi_top_kernel<3>, dim3(1), dim3(kBlock), 0, s, (const float*)df.d_dist, L, cost, Uc, d_U[to], p, nb, P,
+                           (const u64*)d_bsum, d_part, d_nom, d_stats);
+    } else {
+        hipLaunchKernelGGL(mppi_rollout_kernel<2>, dim3(nbr), dim3(kRollBlock), 0, s, (const float*)df.d_dist, L, cost, Uc, p, d_J, d_hits, d_bmin);
+        hipLaunchKernelGGL(mppi_weigh_kernel, dim3(nb), dim3(kBlock), 0, s, (const double*)d_J, (const int*)d_hits, K, nbr, nb,
+                           (const double*)d_bmin, o.lambda, d_q, d_bsum, d_stats);
+        hipLaunchKernelGGL(mppi_update_kernel<2>, dim3(P, nchunk), dim3(kBlock), 0, s, Uc, (const u64*)d_q, p, P, d_part);
+        hipLaunchKernelGGL(mppi_top_kernel<2>, dim3(1), dim3(kBlock), 0, s, (const float*)df.d_dist, L, cost, Uc, d_U[to], p, nb, P,
+                           (const u64*)d_bsum, d_part, d_nom, d_stats);
+    }
+    GPIS_HIP(hipGetLastError());
+    GPIS_HIP(hipMemcpyAsync(h_stats, d_stats, sizeof(MppiStats), hipMemcpyDeviceToHost, s));
+    GPIS_HIP(hipStreamSynchronize(s));
+    stats = *h_stats;
+    neff = (double)stats.Th * (double)stats.Th / (double)stats.S2;
+    tick += 1; cur = to; steps += 1; have_step = true;
+    ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return GPIS_OK;
+}
+
+}  // namespace gpis

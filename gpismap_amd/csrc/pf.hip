@@ -15,6 +15,7 @@
 #include "locate.h"
 #include "pf.h"
 #include "block_ops.h"
+#include "philox.h"
 
 namespace gpis {
 
@@ -22,31 +23,13 @@ namespace {
 
 typedef unsigned long long u64;
 constexpr int kBlock = ParticleFilter::kBlock;
-constexpr double kKZ = 0x1.3988e1412ed76p-17;        // 1 / sqrt(8 (65536^2 - 1) / 3)
 constexpr double kTwo32 = 4294967296.0;
 constexpr u64 kIdxMask = (1ull << 24) - 1;
 
-// ---- the generator ----------------------------------------------------------------------------------------------------------
-__host__ __device__ __forceinline__ void philox10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,
-                                                  uint32_t* __restrict__ out) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const u64 p0 = (u64)0xD2511F53u * c0, p1 = (u64)0xCD9E8D57u * c2;
-        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
-        c1 = (uint32_t)p1; c3 = (uint32_t)p0; c0 = n0; c2 = n2;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
-
-// deviate k of a slot at a tick: the eight 16-bit halves of one block summed as integers, one conversion, one product
+// ---- the generator (philox.h) -----------------------------------------------------------------------------------------------
+// deviate k of a slot at a tick: tag 0
 __device__ __forceinline__ double deviate(uint32_t slot, uint32_t tick, uint32_t k, uint32_t k0, uint32_t k1) {
-    uint32_t w[4];
-    philox10(slot, tick, k, 0u, k0, k1, w);
-    int S = 0;
-#pragma unroll
-    for (int a = 0; a < 4; ++a) S += (int)(w[a] & 0xFFFFu) + (int)(w[a] >> 16);
-    return (double)(2 * S - 8 * 65535) * kKZ;
+    return philox_deviate(slot, tick, k, 0u, k0, k1);
 }
 
 // ---- state and pose ---------------------------------------------------------------------------------------------------------

@@ -822,6 +822,79 @@ int   gpis_pf_device(void* pf, void** ptrs, int n);
  * neff, ms of host wall time of the last update */
 int   gpis_pf_info(void* pf, double* out, int n);
 
+/* ---- sampled model-predictive control against a distance field (MPPI) --------------------------------------
+ * The stage that turns "where I am, where the cost-to-go falls, where the obstacles are" into the next velocity command: K
+ * noisy control sequences around a nominal one are rolled through a kinematic model for T steps, charged the field's obstacle
+ * cost along the way and the planner's cost-to-go (or the distance to a goal point) at the end, and the nominal sequence moves
+ * towards their exponentially weighted mean.  The controller lives on the device; a step copies back one block of 88 bytes.
+ * tests/mppi_ref.py restates every stage in numpy; each stage except one exp has exactly one result, and that exp moves a
+ * weight by at most 1 in 2^32.  Every floating-point expression below is double, evaluated left to right, not contracted;
+ * division and sqrt are IEEE; no sin, cos or log runs on the device.  The field sample is float32 exactly as
+ * gpis_dfield_sample, taken at the float32 cast of the position.
+ * Model, by the field's dim: dim 2: state (x, y, c, s), U = 2 controls (v, w), a unicycle; dim 3: state (x, y, z, c, s), U = 4
+ * controls (vx, vy, vz, w), body-frame velocity and yaw rate about z.
+ * State of the controller: the nominal sequence Ubar[T][U] (zero after init), a 32-bit tick (0 after init), the 64-bit seed,
+ * 1 <= K <= 65536 rollouts, 1 <= T <= 256 steps.
+ * Noise: the particle filter's generator and deviate (above) on the counter (k, tick, t * U + u, 2): tag 2; tags 0 and 1 stay
+ * the filter's.  Rollout 0 has z = 0 throughout: it is the nominal sequence itself.
+ * step: tick += 1; the start is pose's translation and (c, s) = (R[0], R[1]) / sqrt(R[0] R[0] + R[1] R[1]).  For rollout k and
+ * t = 0 .. T - 1: e = sigma[u] z, v_u = min(max(Ubar[t][u] + e, umin[u]), umax[u]), d_u = v_u - Ubar[t][u].  Translation with
+ * the heading from before the step: dim 2: bx = v0 dt, x += c bx, y += s bx; dim 3: bx = v0 dt, by = v1 dt, x += c bx - s by,
+ * y += s bx + c by, z += v2 dt.  Heading: a = (0.5 dt) w, cn = (1 - a a) / (1 + a a), sn = (a + a) / (1 + a a), (c, s) <-
+ * (c cn - s sn, s cn + c sn), each divided by sqrt(c c + s s).  Stage cost j of d, the sampled distance at the new position:
+ * NaN (off the lattice) -> w_off; d < clearance -> w_col and the rollout's hit count += 1; d < clearance + margin -> r =
+ * ((clearance + margin) - d) / margin, j = (w_obs r) r; else 0.  Control cost g = gamma * sum over the u with sigma[u] > 0,
+ * ascending from 0.0, of (Ubar[t][u] d_u) / (sigma[u] sigma[u]).  J = (J + j) + g.
+ * Terminal term with a planner (its last solve on the field's lattice): per axis u_a = the sampler's float32 lattice
+ * coordinate with the same inside test, i_a = min((int)floorf(u_a + 0.5f), n_a - 1), G = cost[i]; off the lattice -> J +=
+ * w_off; G infinite -> J += w_col; else J += w_goal (double)G.  With a goal point: J += w_goal sqrt(sum_a (p_a - g_a)^2), the
+ * sum in axis order.
+ * Weights: Jmin = min J; q_k = (uint64)floor(exp(-((J_k - Jmin) / lambda)) 2^32); T_q = sum q, Th = sum (q >> 16), S2 =
+ * sum (q >> 16)^2 as integers; neff = (double)Th (double)Th / (double)S2; best = the lowest index of minimal J.
+ * Update: S[t][u] = sum_k (double)q_k d_u[k][t] in the tracker's reduction order (256-rollout segments by a halving tree, the
+ * partials zero-padded to a power of two, the same tree); Ubar[t][u] = min(max(Ubar[t][u] + S[t][u] / (double)T_q, umin[u]),
+ * umax[u]); then the nominal rollout: rollout 0 of the new Ubar by the same code, its T + 1 states, cost and hit count.
+ * u0 = the new Ubar[0].  shift: Ubar[t] = Ubar[t + 1], the last row stays, the tick does not change.
+ * No kernel waits on another workgroup, no atomics; results do not depend on schedule or stream.  Every call returns with its
+ * work finished.  hip_stream NULL: the controller's own stream.
+ * Errors (each leaves the previous state untouched): a NULL controller, field, pose or U; dim outside {2, 3}; K < 1 or T < 1; a
+ * non-finite pose (the translation, R[0], R[1]; in 3-D the rest of R is not read), goal or U entry, a heading of norm 0; a
+ * non-finite option, dt <= 0, lambda <= 0, a negative sigma / weight / margin, umin[u] > umax[u]; a field or planner of another
+ * dim, lattice or device; both or neither of planner and goal -> GPIS_ERR_ARG.  step, get, shift, set_nominal or device before
+ * init, a field or planner without a result -> GPIS_ERR_STATE.  K > 65536 or T > 256 -> GPIS_ERR_LIMIT before anything is read
+ * or allocated. */
+typedef struct gpis_mppi_opts {
+    double dt;                  /* the model's time step */
+    double lambda;              /* temperature of the weights */
+    double gamma;               /* weight of the control cost */
+    double sigma[4];            /* noise of each control (dim 2: the first two); 0: that control is not sampled */
+    double umin[4], umax[4];    /* control limits */
+    double clearance, margin;   /* collision below clearance; the obstacle cost's band above it */
+    double w_obs, w_col, w_off, w_goal;
+} gpis_mppi_opts;
+/* defaults for a field of lattice step `step`: dt 0.1, lambda 1, gamma 0.1, clearance step, margin 2 step, w_obs 1, w_col 100,
+ * w_off 100, w_goal 1; dim 2: sigma (0.25, 0.5), umin (0, -1), umax (1, 1), the rest 0; dim 3: sigma (0.25, 0.25, 0.25, 0.5),
+ * umin -1 and umax 1 each.  Needs no device. */
+int   gpis_mppi_default_opts(int dim, float step, gpis_mppi_opts* opts);
+void* gpis_mppi_create(void);                               /* on the current device; NULL without one */
+void  gpis_mppi_destroy(void* mppi);
+int   gpis_mppi_init(void* mppi, int dim, int K, int T, unsigned long long seed);
+/* U: double [T][U], finite; replaces the nominal sequence as it is (the next step clamps what it samples, not Ubar) */
+int   gpis_mppi_set_nominal(void* mppi, const double* U);
+/* pose: double [6] / [12] = [t, R] as gpis_pf_estimate returns it; exactly one of plan (a planner handle) and goal (double
+ * [dim]) is not NULL; opts NULL: the defaults for the field's step; u0: double [U] or NULL */
+int   gpis_mppi_step(void* mppi, void* df, void* plan, const double* pose, const double* goal, const gpis_mppi_opts* opts, double* u0,
+                     void* hip_stream);
+int   gpis_mppi_shift(void* mppi);
+/* host copies (any pointer may be NULL): U [T][U] the nominal sequence; of the last step (zero before it) J [K], q [K],
+ * hits [K], nominal_states [T + 1][dim + 2]; stats [10] = Jmin, best, neff, T_q, Th, S2, rollouts with a hit, the nominal
+ * rollout's cost and hit count, 1 after the first step */
+int   gpis_mppi_get(void* mppi, double* U, double* J, unsigned long long* q, int* hits, double* nominal_states, double* stats);
+/* device pointers ptrs[0..n): U, J, q, hits, nominal_states; U changes halves with every step and shift */
+int   gpis_mppi_device(void* mppi, void** ptrs, int n);
+/* out[0..n): 1 after init, dim, K, T, tick, steps, 1 after the first step, ms of host wall time of the last step */
+int   gpis_mppi_info(void* mppi, double* out, int n);
+
 #ifdef __cplusplus
 }
 #endif
