@@ -354,6 +354,37 @@ def _cam(cam6):
     return gpis_cam(float(c[0]), float(c[1]), float(c[2]), float(c[3]), int(c[4]), int(c[5]))
 
 
+def _depth_frame(what, depth, cam6, map_h, map_wh):
+    """A depth frame for the C-ABI: (depth [W*H] f32, or None for a call that takes no image; the gpis_cam argument).  cam6
+    None = the camera of the map `map_h`, whose (width, height) is map_wh."""
+    if cam6 is None and map_h is None:
+        raise GpisError("a field-only %s needs cam6" % what)
+    if depth is not None:
+        depth = np.ascontiguousarray(depth, dtype=np.float32).ravel()
+        w, h = (int(cam6[4]), int(cam6[5])) if cam6 is not None else map_wh
+        if depth.size != w * h:
+            raise GpisError("depth must have width * height = %d elements" % (w * h))
+    return depth, (C.byref(_cam(cam6)) if cam6 is not None else None)
+
+
+def _scan_frame(what, thetas, ranges, off2, map_h):
+    """A scan frame for the C-ABI: (thetas [n] f32, ranges [n] f32 or None for a call that takes none, the off2 argument).  off2
+    None = the sensor offset of the map `map_h`."""
+    thetas = np.ascontiguousarray(thetas, dtype=np.float32).ravel()
+    if ranges is not None:
+        ranges = np.ascontiguousarray(ranges, dtype=np.float32).ravel()
+        if thetas.size != ranges.size:
+            raise GpisError("thetas and ranges differ in size")
+    if off2 is None:
+        if map_h is None:
+            raise GpisError("a field-only %s needs off2" % what)
+        return thetas, ranges, None
+    off = np.ascontiguousarray(off2, dtype=np.float32).ravel()
+    if off.size != 2:
+        raise GpisError("off2 must have 2 elements")
+    return thetas, ranges, _p(off)
+
+
 class GPisMap3:
     """Mirror of the reference's mexGPisMap3 command set on the HIP path."""
 
@@ -580,7 +611,7 @@ class GPisMap3:
             raise GpisError("pose must have 12 elements")
         r = renderer if renderer is not None else self._own_renderer()
         o = render_opts(3, **opts)
-        cam = C.byref(_cam(cam6)) if cam6 is not None else None
+        _, cam = _depth_frame("render_depth", None, cam6, self.h, self._wh)
         _check(self.L.gpis3_render_depth(self.h, r.h, cam, _p(pose), C.byref(o), None), "gpis3_render_depth")
         return r.get()
 
@@ -596,16 +627,12 @@ class GPisMap3:
         plus H [6, 6], b [6] (xi = (v, omega)) at the returned pose and "resid" [W*H] (r of the inliers, NaN elsewhere).
         Non-convergence is info["status"] (0 converged, 1 max_iters, 2 too few inliers, 3 degenerate), not an exception.
         cam6: (fx, fy, cx, cy, width, height), None = the map's camera.  opts: the gpis_track_opts fields."""
-        depth = np.ascontiguousarray(depth, dtype=np.float32).ravel()
         pose0 = np.ascontiguousarray(pose0, dtype=np.float32).ravel()
         if pose0.size != 12:
             raise GpisError("pose must have 12 elements")
-        w, h = (int(cam6[4]), int(cam6[5])) if cam6 is not None else self._wh
-        if depth.size != w * h:
-            raise GpisError("depth must have width * height = %d elements" % (w * h))
+        depth, cam = _depth_frame("track_depth", depth, cam6, self.h, self._wh)
         t = tracker if tracker is not None else self._own_tracker()
         o = track_opts(3, **opts)
-        cam = C.byref(_cam(cam6)) if cam6 is not None else None
         out = np.zeros(12, dtype=np.float32)
         _check(self.L.gpis3_track_depth(self.h, t.h, cam, _p(depth), _p(pose0), C.byref(o), _p(out), None), "gpis3_track_depth")
         return out, t.result()
@@ -735,7 +762,7 @@ class GPisMap:
     def render_scan(self, thetas, pose6, renderer=None, **opts):
         """What the laser would see from `pose6` (gpis2_render_scan) along the beams `thetas`.  Returns (range [n] f32,
         rec [n, 6] f32, status [n] u8); no hit: range NaN, record NaN.  opts: as GPisMap3.render_depth."""
-        thetas = np.ascontiguousarray(thetas, dtype=np.float32).ravel()
+        thetas, _, _ = _scan_frame("render_scan", thetas, None, None, self.h)
         pose6 = np.ascontiguousarray(pose6, dtype=np.float32).ravel()
         if pose6.size != 6:
             raise GpisError("pose6 must have 6 elements")
@@ -752,11 +779,10 @@ class GPisMap:
         """The laser pose from which the map explains the scan best (gpis2_track_scan): damped Gauss-Newton on SE(2) from
         pose0 (6 floats [t(2), R(4)]).  Returns (pose [6] f32, info) with H [3, 3], b [3] (xi = (vx, vy, omega)) and
         "resid" [n]; opts and statuses as GPisMap3.track_depth."""
-        thetas = np.ascontiguousarray(thetas, dtype=np.float32).ravel()
-        ranges = np.ascontiguousarray(ranges, dtype=np.float32).ravel()
+        thetas, ranges, _ = _scan_frame("track_scan", thetas, ranges, None, self.h)
         pose0 = np.ascontiguousarray(pose0, dtype=np.float32).ravel()
-        if pose0.size != 6 or thetas.size != ranges.size:
-            raise GpisError("bad 2-D track arguments")
+        if pose0.size != 6:
+            raise GpisError("pose must have 6 elements")
         if tracker is None:
             if getattr(self, "_tracker", None) is None:
                 self._tracker = Tracker()
@@ -999,38 +1025,27 @@ class DistanceField:
         return self._tracker
 
     def _track_depth(self, map_h, map_wh, depth, pose0, cam6, tracker, opts):
-        depth = np.ascontiguousarray(depth, dtype=np.float32).ravel()
         pose0 = np.ascontiguousarray(pose0, dtype=np.float32).ravel()
         if pose0.size != 12:
             raise GpisError("pose must have 12 elements")
-        if cam6 is None and map_h is None:
-            raise GpisError("a field-only track_depth needs cam6")
-        w, h = (int(cam6[4]), int(cam6[5])) if cam6 is not None else map_wh
-        if depth.size != w * h:
-            raise GpisError("depth must have width * height = %d elements" % (w * h))
+        depth, cam = _depth_frame("track_depth", depth, cam6, map_h, map_wh)
         t = tracker if tracker is not None else self._own_tracker()
         o = track_opts(3, **opts)
-        cam = C.byref(_cam(cam6)) if cam6 is not None else None
         out = np.zeros(12, dtype=np.float32)
         _check(self.L.gpis3_track_depth_field(map_h, self.h, t.h, cam, _p(depth), _p(pose0), C.byref(o), _p(out), None),
                "gpis3_track_depth_field")
         return out, t.result()
 
     def _track_scan(self, map_h, thetas, ranges, pose0, off2, tracker, opts):
-        thetas = np.ascontiguousarray(thetas, dtype=np.float32).ravel()
-        ranges = np.ascontiguousarray(ranges, dtype=np.float32).ravel()
+        thetas, ranges, off = _scan_frame("track_scan", thetas, ranges, off2, map_h)
         pose0 = np.ascontiguousarray(pose0, dtype=np.float32).ravel()
-        if pose0.size != 6 or thetas.size != ranges.size:
-            raise GpisError("bad 2-D track arguments")
-        off = np.ascontiguousarray(off2, dtype=np.float32).ravel() if off2 is not None else None
-        if off is not None and off.size != 2:
-            raise GpisError("off2 must have 2 elements")
+        if pose0.size != 6:
+            raise GpisError("pose must have 6 elements")
         t = tracker if tracker is not None else self._own_tracker()
         o = track_opts(2, **opts)
         out = np.zeros(6, dtype=np.float32)
-        _check(self.L.gpis2_track_scan_field(map_h, self.h, t.h, _p(thetas), _p(ranges), thetas.size,
-                                             _p(off) if off is not None else None, _p(pose0), C.byref(o), _p(out), None),
-               "gpis2_track_scan_field")
+        _check(self.L.gpis2_track_scan_field(map_h, self.h, t.h, _p(thetas), _p(ranges), thetas.size, off, _p(pose0), C.byref(o),
+                                             _p(out), None), "gpis2_track_scan_field")
         return out, t.result()
 
     def score_depth(self, depth, poses, cam6, locator=None, **opts):
@@ -1065,38 +1080,25 @@ class DistanceField:
         return self._locator
 
     def _score_depth(self, map_h, map_wh, depth, poses, cam6, locator, opts):
-        depth = np.ascontiguousarray(depth, dtype=np.float32).ravel()
         poses = np.ascontiguousarray(poses, dtype=np.float32)
         if poses.size == 0 or poses.size % 12:
             raise GpisError("poses must be [m, 12] with m >= 1")
-        if cam6 is None and map_h is None:
-            raise GpisError("a field-only score_depth needs cam6")
-        w, h = (int(cam6[4]), int(cam6[5])) if cam6 is not None else map_wh
-        if depth.size != w * h:
-            raise GpisError("depth must have width * height = %d elements" % (w * h))
+        depth, cam = _depth_frame("score_depth", depth, cam6, map_h, map_wh)
         l = locator if locator is not None else self._own_locator()
         o = locate_opts(3, **opts)
-        cam = C.byref(_cam(cam6)) if cam6 is not None else None
         _check(self.L.gpis3_locate_depth_field(map_h, self.h, l.h, cam, _p(depth), _p(poses), poses.size // 12, C.byref(o), None),
                "gpis3_locate_depth_field")
         return l.get()
 
     def _score_scan(self, map_h, thetas, ranges, poses, off2, locator, opts):
-        thetas = np.ascontiguousarray(thetas, dtype=np.float32).ravel()
-        ranges = np.ascontiguousarray(ranges, dtype=np.float32).ravel()
         poses = np.ascontiguousarray(poses, dtype=np.float32)
-        if poses.size == 0 or poses.size % 6 or thetas.size != ranges.size:
-            raise GpisError("bad 2-D score arguments")
-        off = np.ascontiguousarray(off2, dtype=np.float32).ravel() if off2 is not None else None
-        if off is not None and off.size != 2:
-            raise GpisError("off2 must have 2 elements")
-        if off is None and map_h is None:
-            raise GpisError("a field-only score_scan needs off2")
+        if poses.size == 0 or poses.size % 6:
+            raise GpisError("poses must be [m, 6] with m >= 1")
+        thetas, ranges, off = _scan_frame("score_scan", thetas, ranges, off2, map_h)
         l = locator if locator is not None else self._own_locator()
         o = locate_opts(2, **opts)
-        _check(self.L.gpis2_locate_scan_field(map_h, self.h, l.h, _p(thetas), _p(ranges), thetas.size,
-                                              _p(off) if off is not None else None, _p(poses), poses.size // 6, C.byref(o), None),
-               "gpis2_locate_scan_field")
+        _check(self.L.gpis2_locate_scan_field(map_h, self.h, l.h, _p(thetas), _p(ranges), thetas.size, off, _p(poses),
+                                              poses.size // 6, C.byref(o), None), "gpis2_locate_scan_field")
         return l.get()
 
     def _locate(self, dim, frame, poses, refine, track, opts):
@@ -1193,28 +1195,21 @@ class DistanceField:
         pose = np.ascontiguousarray(pose, dtype=np.float32).ravel()
         if pose.size != 12:
             raise GpisError("pose must have 12 elements")
-        if cam6 is None and map_h is None:
-            raise GpisError("a field-only render_depth needs cam6")
+        _, cam = _depth_frame("render_depth", None, cam6, map_h, None)
         r = renderer if renderer is not None else self._own_renderer()
         o = render_field_opts(3, self._step(), **opts)
-        cam = C.byref(_cam(cam6)) if cam6 is not None else None
         _check(self.L.gpis3_render_depth_field(map_h, self.h, r.h, cam, _p(pose), C.byref(o), None), "gpis3_render_depth_field")
         return r.get()
 
     def _render_scan(self, map_h, thetas, pose6, off2, renderer, opts):
-        thetas = np.ascontiguousarray(thetas, dtype=np.float32).ravel()
+        thetas, _, off = _scan_frame("render_scan", thetas, None, off2, map_h)
         pose6 = np.ascontiguousarray(pose6, dtype=np.float32).ravel()
         if pose6.size != 6:
             raise GpisError("pose6 must have 6 elements")
-        off = np.ascontiguousarray(off2, dtype=np.float32).ravel() if off2 is not None else None
-        if off is not None and off.size != 2:
-            raise GpisError("off2 must have 2 elements")
-        if off is None and map_h is None:
-            raise GpisError("a field-only render_scan needs off2")
         r = renderer if renderer is not None else self._own_renderer()
         o = render_field_opts(2, self._step(), **opts)
-        _check(self.L.gpis2_render_scan_field(map_h, self.h, r.h, _p(thetas), thetas.size, _p(off) if off is not None else None,
-                                              _p(pose6), C.byref(o), None), "gpis2_render_scan_field")
+        _check(self.L.gpis2_render_scan_field(map_h, self.h, r.h, _p(thetas), thetas.size, off, _p(pose6), C.byref(o), None),
+               "gpis2_render_scan_field")
         return r.get()
 
 
@@ -1652,29 +1647,15 @@ class ParticleFilter:
         return self._update_depth(None, None, field, depth, cam6, stream, opts)
 
     def _update_scan(self, map_h, field, thetas, ranges, off2, stream, opts):
-        thetas = np.ascontiguousarray(thetas, dtype=np.float32).ravel()
-        ranges = np.ascontiguousarray(ranges, dtype=np.float32).ravel()
-        if thetas.size != ranges.size:
-            raise GpisError("thetas and ranges differ in size")
-        off = np.ascontiguousarray(off2, dtype=np.float32).ravel() if off2 is not None else None
-        if off is not None and off.size != 2:
-            raise GpisError("off2 must have 2 elements")
-        if off is None and map_h is None:
-            raise GpisError("a field-only update_scan needs off2")
+        thetas, ranges, off = _scan_frame("update_scan", thetas, ranges, off2, map_h)
         o = self._opts(opts)
-        _check(self.L.gpis2_pf_update_scan(map_h, field.h, self.h, _p(thetas), _p(ranges), thetas.size,
-                                           _p(off) if off is not None else None, C.byref(o), stream), "gpis2_pf_update_scan")
+        _check(self.L.gpis2_pf_update_scan(map_h, field.h, self.h, _p(thetas), _p(ranges), thetas.size, off, C.byref(o), stream),
+               "gpis2_pf_update_scan")
         return self.estimate()
 
     def _update_depth(self, map_h, map_wh, field, depth, cam6, stream, opts):
-        depth = np.ascontiguousarray(depth, dtype=np.float32).ravel()
-        if cam6 is None and map_h is None:
-            raise GpisError("a field-only update_depth needs cam6")
-        w, h = (int(cam6[4]), int(cam6[5])) if cam6 is not None else map_wh
-        if depth.size != w * h:
-            raise GpisError("depth must have width * height = %d elements" % (w * h))
+        depth, cam = _depth_frame("update_depth", depth, cam6, map_h, map_wh)
         o = self._opts(opts)
-        cam = C.byref(_cam(cam6)) if cam6 is not None else None
         _check(self.L.gpis3_pf_update_depth(map_h, field.h, self.h, cam, _p(depth), C.byref(o), stream), "gpis3_pf_update_depth")
         return self.estimate()
 

@@ -61,14 +61,29 @@ int gpis3_impl_dfield(GPisMap3* g, DistanceField& df, const int* n3, const float
                       void* stream);
 int gpis2_impl_dfield(GPisMap* g, DistanceField& df, const int* n2, const float* origin2, const float* step2, float level, float max_var,
                       void* stream);
-int gpis3_impl_render(GPisMap3* g, Renderer& r, const float* cam4, const int* wh, const float* pose12, RenderOpts o, void* stream);
-int gpis2_impl_render(GPisMap* g, Renderer& r, const float* thetas, int n, const float* pose6, RenderOpts o, void* stream);
-int gpis3_impl_track(GPisMap3* g, Tracker& t, const float* cam4, const int* wh, const float* depth, const float* pose12, TrackOpts o,
+int gpis3_impl_render(GPisMap3* g, Renderer& r, const SensorFrame& f, const float* pose12, RenderOpts o, void* stream);
+int gpis2_impl_render(GPisMap* g, Renderer& r, const SensorFrame& f, const float* pose6, RenderOpts o, void* stream);
+int gpis3_impl_track(GPisMap3* g, Tracker& t, const SensorFrame& f, const float* depth, const float* pose12, TrackOpts o,
                      float* pose12_out, void* stream);
-int gpis2_impl_track(GPisMap* g, Tracker& t, const float* thetas, const float* ranges, int n, const float* pose6, TrackOpts o,
+int gpis2_impl_track(GPisMap* g, Tracker& t, const SensorFrame& f, const float* ranges, const float* pose6, TrackOpts o,
                      float* pose6_out, void* stream);
 void gpis3_impl_camera(GPisMap3* g, float* cam4, int* wh);
 void gpis2_impl_sensor_offset(GPisMap* g, float* off2);
+
+// The frame of an entry (frame.h): the caller's camera / sensor offset, else the map's.  Checked once, here, for every consumer.
+static int depth_frame(void* m, const gpis_cam* cam, SensorFrame* f) {
+    float c4[4];
+    int wh[2];
+    if (cam) { c4[0] = cam->fx; c4[1] = cam->fy; c4[2] = cam->cx; c4[3] = cam->cy; wh[0] = cam->width; wh[1] = cam->height; }
+    else gpis3_impl_camera((GPisMap3*)m, c4, wh);
+    return frame_from_camera(c4, wh, f);
+}
+static int scan_frame(void* m, const float* thetas, int n, const float* off2, SensorFrame* f) {
+    float off[2];
+    if (off2) { off[0] = off2[0]; off[1] = off2[1]; }
+    else gpis2_impl_sensor_offset((GPisMap*)m, off);
+    return frame_from_scan(thetas, n, off, f);
+}
 
 namespace gpis { int selftest_ranged_arith(unsigned long long seed, int blocks, int per_thread, int mode, unsigned long long* mismatches); }
 extern "C" {
@@ -1004,18 +1019,10 @@ int gpis3_render_depth(void* m, void* render, const gpis_cam* cam, const float* 
     if (!m) return GPIS_ERR_ARG;
     RenderOpts o;
     if (int rc = render_args(render, 3, pose12, opts, &o)) return rc;
-    float c4[4];
-    int wh[2];
-    if (cam) {
-        c4[0] = cam->fx; c4[1] = cam->fy; c4[2] = cam->cx; c4[3] = cam->cy; wh[0] = cam->width; wh[1] = cam->height;
-        RayGeom g{};
-        g.dim = 3; g.fx = c4[0]; g.fy = c4[1]; g.cx = c4[2]; g.cy = c4[3]; g.width = wh[0]; g.height = wh[1];
-        for (int k = 0; k < 3; ++k) g.t[k] = pose12[k];
-        for (int k = 0; k < 9; ++k) g.R[k] = pose12[3 + k];
-        if (int rc = render_check_geom(g, (long long)wh[0] * wh[1])) return rc;
-    }
+    SensorFrame f;
+    if (int rc = depth_frame(m, cam, &f)) return rc;
     Renderer& r = *(Renderer*)render;
-    const int rc = gpis3_impl_render((GPisMap3*)m, r, cam ? c4 : nullptr, cam ? wh : nullptr, pose12, o, stream);
+    const int rc = gpis3_impl_render((GPisMap3*)m, r, f, pose12, o, stream);
     if (rc != GPIS_OK && rc != GPIS_ERR_ARG && rc != GPIS_ERR_LIMIT) r.clear_result();
     return rc;
 }
@@ -1023,10 +1030,10 @@ int gpis2_render_scan(void* m, void* render, const float* thetas, int n, const f
     if (!m || !thetas || n < 1) return GPIS_ERR_ARG;
     RenderOpts o;
     if (int rc = render_args(render, 2, pose6, opts, &o)) return rc;
-    for (int k = 0; k < n; ++k) if (!std::isfinite(thetas[k])) return GPIS_ERR_ARG;
-    if ((long long)n > Renderer::kMaxRays) return GPIS_ERR_LIMIT;
     Renderer& r = *(Renderer*)render;
-    const int rc = gpis2_impl_render((GPisMap*)m, r, thetas, n, pose6, o, stream);
+    SensorFrame f;
+    int rc = scan_frame(m, thetas, n, nullptr, &f);
+    if (rc == GPIS_OK) rc = gpis2_impl_render((GPisMap*)m, r, f, pose6, o, stream);
     if (rc != GPIS_OK && rc != GPIS_ERR_ARG && rc != GPIS_ERR_LIMIT) r.clear_result();
     return rc;
 }
@@ -1077,13 +1084,12 @@ int gpis_render_set_field_tiles(void* render, int on) {
 }
 // the checks that need neither field nor map, then the field's state and dim (before anything is dropped) and the call on the
 // field's device: an argument, state or limit error leaves the previous result readable
-static int render_field_call(void* d, void* render, RayGeom& g, const float* pose, const gpis_render_field_opts* opts,
-                             const double* cs, long long n, void* stream) {
+static int render_field_call(void* d, void* render, const SensorFrame& f, const float* pose, const gpis_render_field_opts* opts,
+                             void* stream) {
     if (!d || !render || !pose) return GPIS_ERR_ARG;
-    const int np = g.dim == 3 ? 12 : 6;
+    const int np = f.geo.dim == 3 ? 12 : 6;
     for (int k = 0; k < np; ++k) if (!std::isfinite(pose[k])) return GPIS_ERR_ARG;
-    for (int k = 0; k < g.dim; ++k) g.t[k] = pose[k];
-    for (int k = 0; k < g.dim * g.dim; ++k) g.R[k] = pose[g.dim + k];
+    const RayGeom g = ray_geom(f, pose);
     const DistanceField& df = *(const DistanceField*)d;
     if (!df.valid) return GPIS_ERR_STATE;
     if (df.dim != g.dim) return GPIS_ERR_ARG;
@@ -1093,12 +1099,11 @@ static int render_field_call(void* d, void* render, RayGeom& g, const float* pos
     o.tnear = opts->tnear; o.tfar = opts->tfar; o.min_step = opts->min_step; o.max_step = opts->max_step; o.slack = opts->slack;
     o.refine = opts->refine; o.max_steps = opts->max_steps;
     if (int rc = render_field_check_opts(o)) return rc;
-    if (int rc = render_check_geom(g, n)) return rc;
     Renderer& r = *(Renderer*)render;
     DeviceScope ds(df.device);
     try {
         if (int rc = r.bind(df.device)) { r.clear_result(); return rc; }
-        const int rc = r.render_field(df, g, cs, n, o, stream ? (hipStream_t)stream : df.own);
+        const int rc = r.render_field(df, g, f.cs_or_null(), f.n, o, stream ? (hipStream_t)stream : df.own);
         if (rc != GPIS_OK) r.clear_result();
         return rc;
     } catch (...) { r.clear_result(); return GPIS_ERR_STATE; }
@@ -1106,30 +1111,16 @@ static int render_field_call(void* d, void* render, RayGeom& g, const float* pos
 int gpis3_render_depth_field(void* m, void* df, void* render, const gpis_cam* cam, const float* pose12,
                              const gpis_render_field_opts* opts, void* stream) {
     if (!cam && !m) return GPIS_ERR_ARG;
-    float c4[4];
-    int wh[2];
-    if (cam) { c4[0] = cam->fx; c4[1] = cam->fy; c4[2] = cam->cx; c4[3] = cam->cy; wh[0] = cam->width; wh[1] = cam->height; }
-    else gpis3_impl_camera((GPisMap3*)m, c4, wh);
-    RayGeom g{};
-    g.dim = 3; g.fx = c4[0]; g.fy = c4[1]; g.cx = c4[2]; g.cy = c4[3]; g.width = wh[0]; g.height = wh[1];
-    return render_field_call(df, render, g, pose12, opts, nullptr, (long long)wh[0] * wh[1], stream);
+    SensorFrame f;
+    if (int rc = depth_frame(m, cam, &f)) return rc;
+    return render_field_call(df, render, f, pose12, opts, stream);
 }
 int gpis2_render_scan_field(void* m, void* df, void* render, const float* thetas, int n, const float* off2, const float* pose6,
                             const gpis_render_field_opts* opts, void* stream) {
     if (!thetas || n < 1 || (!off2 && !m)) return GPIS_ERR_ARG;
-    for (int k = 0; k < n; ++k) if (!std::isfinite(thetas[k])) return GPIS_ERR_ARG;
-    if ((long long)n > Renderer::kMaxRays) return GPIS_ERR_LIMIT;
-    RayGeom g{};
-    g.dim = 2;
-    if (off2) { g.off[0] = off2[0]; g.off[1] = off2[1]; }
-    else gpis2_impl_sensor_offset((GPisMap*)m, g.off);
-    std::vector<double> cs;
-    try { cs.resize((size_t)2 * n); } catch (...) { return GPIS_ERR_STATE; }
-    for (int k = 0; k < n; ++k) {
-        cs[2 * (size_t)k] = std::cos((double)thetas[k]);
-        cs[2 * (size_t)k + 1] = std::sin((double)thetas[k]);
-    }
-    return render_field_call(df, render, g, pose6, opts, cs.data(), n, stream);
+    SensorFrame f;
+    if (int rc = scan_frame(m, thetas, n, off2, &f)) return rc;
+    return render_field_call(df, render, f, pose6, opts, stream);
 }
 
 // ---- tracking ----------------------------------------------------------------------------------------------------------
@@ -1179,16 +1170,10 @@ int gpis3_track_depth(void* m, void* tracker, const gpis_cam* cam, const float* 
     if (!m || !depth) return GPIS_ERR_ARG;
     TrackOpts o;
     if (int rc = track_args(tracker, 3, pose12_init, opts, &o)) return rc;
-    float c4[4];
-    int wh[2];
-    if (cam) {
-        c4[0] = cam->fx; c4[1] = cam->fy; c4[2] = cam->cx; c4[3] = cam->cy; wh[0] = cam->width; wh[1] = cam->height;
-        TrackGeom g{};
-        g.dim = 3; g.fx = c4[0]; g.fy = c4[1]; g.cx = c4[2]; g.cy = c4[3]; g.width = wh[0]; g.height = wh[1];
-        if (int rc = track_check_geom(g, (long long)wh[0] * wh[1])) return rc;
-    }
+    SensorFrame f;
+    if (int rc = depth_frame(m, cam, &f)) return rc;
     Tracker& t = *(Tracker*)tracker;
-    const int rc = gpis3_impl_track((GPisMap3*)m, t, cam ? c4 : nullptr, cam ? wh : nullptr, depth, pose12_init, o, pose12_out, stream);
+    const int rc = gpis3_impl_track((GPisMap3*)m, t, f, depth, pose12_init, o, pose12_out, stream);
     if (rc != GPIS_OK && rc != GPIS_ERR_ARG && rc != GPIS_ERR_LIMIT) t.clear_result();
     return rc;
 }
@@ -1197,25 +1182,26 @@ int gpis2_track_scan(void* m, void* tracker, const float* thetas, const float* r
     if (!m || !thetas || !ranges || n < 1) return GPIS_ERR_ARG;
     TrackOpts o;
     if (int rc = track_args(tracker, 2, pose6_init, opts, &o)) return rc;
-    for (int k = 0; k < n; ++k) if (!std::isfinite(thetas[k])) return GPIS_ERR_ARG;
-    if ((long long)n > Tracker::kMaxPoints) return GPIS_ERR_LIMIT;
     Tracker& t = *(Tracker*)tracker;
-    const int rc = gpis2_impl_track((GPisMap*)m, t, thetas, ranges, n, pose6_init, o, pose6_out, stream);
+    SensorFrame f;
+    int rc = scan_frame(m, thetas, n, nullptr, &f);
+    if (rc == GPIS_OK) rc = gpis2_impl_track((GPisMap*)m, t, f, ranges, pose6_init, o, pose6_out, stream);
     if (rc != GPIS_OK && rc != GPIS_ERR_ARG && rc != GPIS_ERR_LIMIT) t.clear_result();
     return rc;
 }
 // the field's state and dim (before anything is dropped), then the call on the field's device
-static int track_field_call(void* d, Tracker& t, const TrackGeom& g, const float* in, const double* cs, long long n,
-                            const float* pose_init, int np, const TrackOpts& o, float* pose_out, void* stream) {
+static int track_field_call(void* d, Tracker& t, const SensorFrame& f, const float* in, const float* pose_init, const TrackOpts& o,
+                            float* pose_out, void* stream) {
     const DistanceField& df = *(const DistanceField*)d;
     if (!df.valid) return GPIS_ERR_STATE;
-    if (df.dim != g.dim) return GPIS_ERR_ARG;
+    if (df.dim != f.geo.dim) return GPIS_ERR_ARG;
+    const int np = f.geo.dim == 3 ? 12 : 6;
     DeviceScope ds(df.device);
     try {
         if (int rc = t.bind(df.device)) { t.clear_result(); return rc; }
         double p0[12];
         for (int k = 0; k < np; ++k) p0[k] = pose_init[k];
-        const int rc = t.track_field(df, g, in, cs, n, p0, o, stream ? (hipStream_t)stream : df.own);
+        const int rc = t.track_field(df, f.geo, in, f.cs_or_null(), f.n, p0, o, stream ? (hipStream_t)stream : df.own);
         if (rc != GPIS_OK) { t.clear_result(); return rc; }
         if (pose_out) for (int k = 0; k < np; ++k) pose_out[k] = (float)t.pose[k];
         return GPIS_OK;
@@ -1226,34 +1212,18 @@ int gpis3_track_depth_field(void* m, void* df, void* tracker, const gpis_cam* ca
     if (!df || !depth || (!cam && !m)) return GPIS_ERR_ARG;
     TrackOpts o;
     if (int rc = track_args(tracker, 3, pose12_init, opts, &o, true)) return rc;
-    float c4[4];
-    int wh[2];
-    if (cam) { c4[0] = cam->fx; c4[1] = cam->fy; c4[2] = cam->cx; c4[3] = cam->cy; wh[0] = cam->width; wh[1] = cam->height; }
-    else gpis3_impl_camera((GPisMap3*)m, c4, wh);
-    TrackGeom g{};
-    g.dim = 3; g.fx = c4[0]; g.fy = c4[1]; g.cx = c4[2]; g.cy = c4[3]; g.width = wh[0]; g.height = wh[1];
-    const long long n = (long long)wh[0] * wh[1];
-    if (int rc = track_check_geom(g, n)) return rc;
-    return track_field_call(df, *(Tracker*)tracker, g, depth, nullptr, n, pose12_init, 12, o, pose12_out, stream);
+    SensorFrame f;
+    if (int rc = depth_frame(m, cam, &f)) return rc;
+    return track_field_call(df, *(Tracker*)tracker, f, depth, pose12_init, o, pose12_out, stream);
 }
 int gpis2_track_scan_field(void* m, void* df, void* tracker, const float* thetas, const float* ranges, int n, const float* off2,
                            const float* pose6_init, const gpis_track_opts* opts, float* pose6_out, void* stream) {
     if (!df || !thetas || !ranges || n < 1 || (!off2 && !m)) return GPIS_ERR_ARG;
     TrackOpts o;
     if (int rc = track_args(tracker, 2, pose6_init, opts, &o, true)) return rc;
-    for (int k = 0; k < n; ++k) if (!std::isfinite(thetas[k])) return GPIS_ERR_ARG;
-    TrackGeom g{};
-    g.dim = 2;
-    if (off2) { g.off[0] = off2[0]; g.off[1] = off2[1]; }
-    else gpis2_impl_sensor_offset((GPisMap*)m, g.off);
-    if (int rc = track_check_geom(g, n)) return rc;
-    std::vector<double> cs;
-    try { cs.resize((size_t)2 * n); } catch (...) { ((Tracker*)tracker)->clear_result(); return GPIS_ERR_STATE; }
-    for (int k = 0; k < n; ++k) {
-        cs[2 * (size_t)k] = std::cos((double)thetas[k]);
-        cs[2 * (size_t)k + 1] = std::sin((double)thetas[k]);
-    }
-    return track_field_call(df, *(Tracker*)tracker, g, ranges, cs.data(), n, pose6_init, 6, o, pose6_out, stream);
+    SensorFrame f;
+    if (int rc = scan_frame(m, thetas, n, off2, &f)) { if (rc == GPIS_ERR_STATE) ((Tracker*)tracker)->clear_result(); return rc; }
+    return track_field_call(df, *(Tracker*)tracker, f, ranges, pose6_init, o, pose6_out, stream);
 }
 int gpis_track_get(void* tracker, double* H, double* b, float* resid) {
     if (!tracker) return GPIS_ERR_ARG;
@@ -1302,8 +1272,9 @@ static int locate_args(void* locator, int dim, const float* poses, int m, const 
     return locate_check_opts(*o);
 }
 // the pose count's limit (before the poses are read), the poses, the field's state and dim, then the call on the field's device
-static int locate_call(void* d, Locator& l, const TrackGeom& g, const float* in, const double* cs, long long n, const float* poses,
-                       int m, const LocateOpts& o, void* stream) {
+static int locate_call(void* d, Locator& l, const SensorFrame& f, const float* in, const float* poses, int m, const LocateOpts& o,
+                       void* stream) {
+    const TrackGeom& g = f.geo;
     if ((long long)m > Locator::kMaxPoses) return GPIS_ERR_LIMIT;
     const size_t np = (size_t)(g.dim == 3 ? 12 : 6) * (size_t)m;
     for (size_t k = 0; k < np; ++k) if (!std::isfinite(poses[k])) return GPIS_ERR_ARG;
@@ -1313,7 +1284,7 @@ static int locate_call(void* d, Locator& l, const TrackGeom& g, const float* in,
     DeviceScope ds(df.device);
     try {
         if (int rc = l.bind(df.device)) { l.clear_result(); return rc; }
-        const int rc = l.score(df, g, in, cs, n, poses, m, o, stream ? (hipStream_t)stream : df.own);
+        const int rc = l.score(df, g, in, f.cs_or_null(), f.n, poses, m, o, stream ? (hipStream_t)stream : df.own);
         if (rc != GPIS_OK) l.clear_result();
         return rc;
     } catch (...) { l.clear_result(); return GPIS_ERR_STATE; }
@@ -1323,35 +1294,19 @@ int gpis3_locate_depth_field(void* m, void* df, void* locator, const gpis_cam* c
     if (!df || !depth || (!cam && !m)) return GPIS_ERR_ARG;
     LocateOpts o;
     if (int rc = locate_args(locator, 3, poses12, np, opts, &o)) return rc;
-    float c4[4];
-    int wh[2];
-    if (cam) { c4[0] = cam->fx; c4[1] = cam->fy; c4[2] = cam->cx; c4[3] = cam->cy; wh[0] = cam->width; wh[1] = cam->height; }
-    else gpis3_impl_camera((GPisMap3*)m, c4, wh);
-    TrackGeom g{};
-    g.dim = 3; g.fx = c4[0]; g.fy = c4[1]; g.cx = c4[2]; g.cy = c4[3]; g.width = wh[0]; g.height = wh[1];
-    const long long n = (long long)wh[0] * wh[1];
-    if (int rc = track_check_geom(g, n)) return rc;
-    return locate_call(df, *(Locator*)locator, g, depth, nullptr, n, poses12, np, o, stream);
+    SensorFrame f;
+    if (int rc = depth_frame(m, cam, &f)) return rc;
+    return locate_call(df, *(Locator*)locator, f, depth, poses12, np, o, stream);
 }
 int gpis2_locate_scan_field(void* m, void* df, void* locator, const float* thetas, const float* ranges, int n, const float* off2,
                             const float* poses6, int np, const gpis_locate_opts* opts, void* stream) {
     if (!df || !thetas || !ranges || n < 1 || (!off2 && !m)) return GPIS_ERR_ARG;
     LocateOpts o;
     if (int rc = locate_args(locator, 2, poses6, np, opts, &o)) return rc;
-    TrackGeom g{};
-    g.dim = 2;
-    if (off2) { g.off[0] = off2[0]; g.off[1] = off2[1]; }
-    else gpis2_impl_sensor_offset((GPisMap*)m, g.off);
-    if (int rc = track_check_geom(g, n)) return rc;
-    if ((long long)np > Locator::kMaxPoses) return GPIS_ERR_LIMIT;
-    for (int k = 0; k < n; ++k) if (!std::isfinite(thetas[k])) return GPIS_ERR_ARG;
-    std::vector<double> cs;
-    try { cs.resize((size_t)2 * n); } catch (...) { ((Locator*)locator)->clear_result(); return GPIS_ERR_STATE; }
-    for (int k = 0; k < n; ++k) {
-        cs[2 * (size_t)k] = std::cos((double)thetas[k]);
-        cs[2 * (size_t)k + 1] = std::sin((double)thetas[k]);
-    }
-    return locate_call(df, *(Locator*)locator, g, ranges, cs.data(), n, poses6, np, o, stream);
+    if ((long long)np > Locator::kMaxPoses) return GPIS_ERR_LIMIT;   // (as ever in this entry: before the angles are read)
+    SensorFrame f;
+    if (int rc = scan_frame(m, thetas, n, off2, &f)) { if (rc == GPIS_ERR_STATE) ((Locator*)locator)->clear_result(); return rc; }
+    return locate_call(df, *(Locator*)locator, f, ranges, poses6, np, o, stream);
 }
 int gpis_locate_get(void* locator, double* cost, int* inliers, int* order) {
     if (!locator) return GPIS_ERR_ARG;
@@ -1429,13 +1384,12 @@ int gpis_pf_predict(void* pf, const double* motion, const gpis_pf_opts* opts, vo
     return f.predict(mo, o, f.stream_or_own((hipStream_t)stream));
 }
 // the filter's and the field's state, dim and device (before anything is touched), then the call on that device
-static int pf_update_call(void* d, ParticleFilter& f, const TrackGeom& g, const float* in, const double* cs, long long n,
-                          const PfOpts& o, void* stream) {
+static int pf_update_call(void* d, ParticleFilter& f, const SensorFrame& fr, const float* in, const PfOpts& o, void* stream) {
     const DistanceField& df = *(const DistanceField*)d;
     if (!df.valid) return GPIS_ERR_STATE;
-    if (df.dim != g.dim || df.device != f.device) return GPIS_ERR_ARG;
+    if (df.dim != fr.geo.dim || df.device != f.device) return GPIS_ERR_ARG;
     DeviceScope ds(f.device);
-    try { return f.update(df, g, in, cs, n, o, f.stream_or_own((hipStream_t)stream)); } catch (...) { return GPIS_ERR_STATE; }
+    try { return f.update(df, fr.geo, in, fr.cs_or_null(), fr.n, o, f.stream_or_own((hipStream_t)stream)); } catch (...) { return GPIS_ERR_STATE; }
 }
 int gpis3_pf_update_depth(void* m, void* df, void* pf, const gpis_cam* cam, const float* depth, const gpis_pf_opts* opts, void* stream) {
     if (!df || !pf || !depth || (!cam && !m)) return GPIS_ERR_ARG;
@@ -1444,15 +1398,9 @@ int gpis3_pf_update_depth(void* m, void* df, void* pf, const gpis_cam* cam, cons
     if (f.dim != 3) return GPIS_ERR_ARG;
     PfOpts o;
     if (int rc = pf_args(f, opts, &o)) return rc;
-    float c4[4];
-    int wh[2];
-    if (cam) { c4[0] = cam->fx; c4[1] = cam->fy; c4[2] = cam->cx; c4[3] = cam->cy; wh[0] = cam->width; wh[1] = cam->height; }
-    else gpis3_impl_camera((GPisMap3*)m, c4, wh);
-    TrackGeom g{};
-    g.dim = 3; g.fx = c4[0]; g.fy = c4[1]; g.cx = c4[2]; g.cy = c4[3]; g.width = wh[0]; g.height = wh[1];
-    const long long n = (long long)wh[0] * wh[1];
-    if (int rc = track_check_geom(g, n)) return rc;
-    return pf_update_call(df, f, g, depth, nullptr, n, o, stream);
+    SensorFrame fr;
+    if (int rc = depth_frame(m, cam, &fr)) return rc;
+    return pf_update_call(df, f, fr, depth, o, stream);
 }
 int gpis2_pf_update_scan(void* m, void* df, void* pf, const float* thetas, const float* ranges, int n, const float* off2,
                          const gpis_pf_opts* opts, void* stream) {
@@ -1462,19 +1410,9 @@ int gpis2_pf_update_scan(void* m, void* df, void* pf, const float* thetas, const
     if (f.dim != 2) return GPIS_ERR_ARG;
     PfOpts o;
     if (int rc = pf_args(f, opts, &o)) return rc;
-    TrackGeom g{};
-    g.dim = 2;
-    if (off2) { g.off[0] = off2[0]; g.off[1] = off2[1]; }
-    else gpis2_impl_sensor_offset((GPisMap*)m, g.off);
-    if (int rc = track_check_geom(g, n)) return rc;
-    for (int k = 0; k < n; ++k) if (!std::isfinite(thetas[k])) return GPIS_ERR_ARG;
-    std::vector<double> cs;
-    try { cs.resize((size_t)2 * n); } catch (...) { return GPIS_ERR_STATE; }
-    for (int k = 0; k < n; ++k) {
-        cs[2 * (size_t)k] = std::cos((double)thetas[k]);
-        cs[2 * (size_t)k + 1] = std::sin((double)thetas[k]);
-    }
-    return pf_update_call(df, f, g, ranges, cs.data(), n, o, stream);
+    SensorFrame fr;
+    if (int rc = scan_frame(m, thetas, n, off2, &fr)) return rc;
+    return pf_update_call(df, f, fr, ranges, o, stream);
 }
 int gpis_pf_resample(void* pf, void* stream) {
     if (!pf) return GPIS_ERR_ARG;

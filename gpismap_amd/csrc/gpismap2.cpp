@@ -82,6 +82,8 @@ struct GPisMap::Impl {
         return rc;
     }
     void rebuild_table();
+    template <class Prepare, class Call>   // what the consumer entries share (gpis2_impl_extract ...)
+    int consume(const char* name, bool need_tree, void* hip_stream, const Prepare& prepare, const Call& call);
 
     explicit Impl(const GPisMapParam& par)
         : tree(tree_param2()), store(2, par.map_scale_param),
@@ -651,100 +653,65 @@ void gpis2_impl_pass_jobs(GPisMap* g, long long* out) {
     for (int i = 0; i < 4; ++i) out[i] = m.mq.last_pass_jobs[i];
 }
 
-// Contour extraction (gpis2_extract_contour): testDevice's checks and join, then the lattice and the vertices through the map's MapQuery.
-int gpis2_impl_extract(GPisMap* g, MeshExtractor& me, const int* n2, const float* origin2, const float* step2, float level, void* hip_stream) try {
-    GPisMap::Impl& m = *g->impl();
-    DeviceScope dev_scope_(m.device);
-    m.fail_rc = 0;
-    if (!m.ok) return GPIS_ERR_HIP;
-    if (!m.has_tree) return GPIS_ERR_STATE;
-    if (std::isnan(level)) level = -m.setting.fbias;
-    if (int rc = me.bind(m.device)) return rc;
-    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : m.stream;
-    (void)m.join_training();
-    const int rc = me.from_map(m.mq, m.store, 2, n2, origin2, step2, level, s);
-    if (rc != GPIS_OK) { m.fail_rc = rc; fprintf(stderr, "[gpismap_amd] gpis2_extract_contour: device path failed (%d)\n", rc); }
+// What gpis2_extract_contour, gpis2_distance_field, gpis2_render_scan and gpis2_track_scan share: testDevice's checks and join,
+// the consumer moved to the map's device, its call on the caller's stream or the map's, and the report of a failed device path.
+// prepare(device): what the entry does once the map's state has passed -- the check of its resolved options, the consumer's
+// bind; call(stream): the consumer's call; `name`: the entry, for the messages.
+template <class Prepare, class Call>
+int GPisMap::Impl::consume(const char* name, bool need_tree, void* hip_stream, const Prepare& prepare, const Call& call) try {
+    DeviceScope dev_scope_(device);
+    fail_rc = 0;
+    if (!ok) return GPIS_ERR_HIP;
+    if (need_tree && !has_tree) return GPIS_ERR_STATE;
+    if (int rc = prepare(device)) return rc;
+    if (has_tree) (void)join_training();
+    const int rc = call(hip_stream ? (hipStream_t)hip_stream : stream);
+    if (rc != GPIS_OK) { fail_rc = rc; fprintf(stderr, "[gpismap_amd] %s: device path failed (%d)\n", name, rc); }
     return rc;
-} catch (const std::exception& e) { nothrow_report("gpis2_extract_contour", e.what()); return GPIS_ERR_STATE; } catch (...) { nothrow_report("gpis2_extract_contour", "unknown exception"); return GPIS_ERR_STATE; }
+} catch (const std::exception& e) { nothrow_report(name, e.what()); return GPIS_ERR_STATE; } catch (...) { nothrow_report(name, "unknown exception"); return GPIS_ERR_STATE; }
 
-// Distance field (gpis2_distance_field): the extraction's checks and joins, then the lattice through the map's MapQuery on the lead device.
+// Contour extraction (gpis2_extract_contour): the lattice and the vertices through the map's MapQuery.  level NaN: -fbias.
+int gpis2_impl_extract(GPisMap* g, MeshExtractor& me, const int* n2, const float* origin2, const float* step2, float level, void* hip_stream) {
+    GPisMap::Impl& m = *g->impl();
+    if (std::isnan(level)) level = -m.setting.fbias;
+    return m.consume("gpis2_extract_contour", true, hip_stream, [&](int dev) { return me.bind(dev); },
+                     [&](hipStream_t s) { return me.from_map(m.mq, m.store, 2, n2, origin2, step2, level, s); });
+}
+
+// Distance field (gpis2_distance_field): the lattice through the map's MapQuery.
 int gpis2_impl_dfield(GPisMap* g, DistanceField& df, const int* n, const float* origin, const float* step, float level, float max_var,
-                      void* hip_stream) try {
+                      void* hip_stream) {
     GPisMap::Impl& m = *g->impl();
-    DeviceScope dev_scope_(m.device);
-    m.fail_rc = 0;
-    if (!m.ok) return GPIS_ERR_HIP;
-    if (!m.has_tree) return GPIS_ERR_STATE;
     if (std::isnan(level)) level = -m.setting.fbias;
-    if (int rc = df.bind(m.device)) return rc;
-    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : m.stream;
-    (void)m.join_training();
-    const int rc = df.from_map(m.mq, m.store, 2, n, origin, step, level, max_var, s);
-    if (rc != GPIS_OK) { m.fail_rc = rc; fprintf(stderr, "[gpismap_amd] gpis2_distance_field: device path failed (%d)\n", rc); }
-    return rc;
-} catch (const std::exception& e) { nothrow_report("gpis2_distance_field", e.what()); return GPIS_ERR_STATE; } catch (...) { nothrow_report("gpis2_distance_field", "unknown exception"); return GPIS_ERR_STATE; }
+    return m.consume("gpis2_distance_field", true, hip_stream, [&](int dev) { return df.bind(dev); },
+                     [&](hipStream_t s) { return df.from_map(m.mq, m.store, 2, n, origin, step, level, max_var, s); });
+}
 
-// Scan rendering (gpis2_render_scan): testDevice's checks and join, then the march through the map's MapQuery.  The beams'
-// cos / sin in double on the host (polar2Cart); the sensor offset of the map's parameters.
-int gpis2_impl_render(GPisMap* g, Renderer& r, const float* thetas, int n, const float* pose6, RenderOpts o, void* hip_stream) try {
+// Scan rendering (gpis2_render_scan): the march through the map's MapQuery along the frame's beams (cos / sin in host double,
+// as polar2Cart).  o.level NaN: -fbias; o.far_step NaN: 0.9 x the search half-width.
+int gpis2_impl_render(GPisMap* g, Renderer& r, const SensorFrame& f, const float* pose6, RenderOpts o, void* hip_stream) {
     GPisMap::Impl& m = *g->impl();
-    DeviceScope dev_scope_(m.device);
-    m.fail_rc = 0;
-    if (!m.ok) return GPIS_ERR_HIP;
-    if (!m.has_tree) return GPIS_ERR_STATE;
-    RayGeom geo{};
-    geo.dim = 2;
-    geo.t[0] = pose6[0]; geo.t[1] = pose6[1];
-    for (int i = 0; i < 4; ++i) geo.R[i] = pose6[2 + i];
-    geo.off[0] = m.setting.sensor_offset[0]; geo.off[1] = m.setting.sensor_offset[1];
     if (std::isnan(o.level)) o.level = -m.setting.fbias;
     if (std::isnan(o.far_step)) o.far_step = 0.9f * m.mq.search_half();
-    if (int rc = render_check_geom(geo, n)) return rc;
-    if (int rc = render_check_opts(o)) return rc;
-    std::vector<double> cs((size_t)2 * n);
-    for (int k = 0; k < n; ++k) {
-        if (!std::isfinite(thetas[k])) return GPIS_ERR_ARG;
-        cs[2 * (size_t)k] = std::cos((double)thetas[k]);
-        cs[2 * (size_t)k + 1] = std::sin((double)thetas[k]);
-    }
-    if (int rc = r.bind(m.device)) return rc;
-    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : m.stream;
-    (void)m.join_training();
-    const int rc = r.render(m.mq, m.store, geo, cs.data(), n, o, s);
-    if (rc != GPIS_OK) { m.fail_rc = rc; fprintf(stderr, "[gpismap_amd] gpis2_render_scan: device path failed (%d)\n", rc); }
-    return rc;
-} catch (const std::exception& e) { nothrow_report("gpis2_render_scan", e.what()); return GPIS_ERR_STATE; } catch (...) { nothrow_report("gpis2_render_scan", "unknown exception"); return GPIS_ERR_STATE; }
+    return m.consume("gpis2_render_scan", true, hip_stream,
+                     [&](int dev) { if (int e = render_check_opts(o)) return e; return r.bind(dev); },
+                     [&](hipStream_t s) { return r.render(m.mq, m.store, ray_geom(f, pose6), f.cs.data(), f.n, o, s); });
+}
 
-// Scan tracking (gpis2_track_scan): testDevice's checks and join, then the iterations through the map's MapQuery.  The beams'
-// cos / sin in double on the host (polar2Cart); the sensor offset of the map's parameters.  A map without a tree: status 2.
-int gpis2_impl_track(GPisMap* g, Tracker& t, const float* thetas, const float* ranges, int n, const float* pose6, TrackOpts o,
-                     float* pose6_out, void* hip_stream) try {
+// Scan tracking (gpis2_track_scan): the iterations through the map's MapQuery.  o.level NaN: -fbias.  A map without a tree:
+// status 2.
+int gpis2_impl_track(GPisMap* g, Tracker& t, const SensorFrame& f, const float* ranges, const float* pose6, TrackOpts o,
+                     float* pose6_out, void* hip_stream) {
     GPisMap::Impl& m = *g->impl();
-    DeviceScope dev_scope_(m.device);
-    m.fail_rc = 0;
-    if (!m.ok) return GPIS_ERR_HIP;
-    TrackGeom geo{};
-    geo.dim = 2;
-    geo.off[0] = m.setting.sensor_offset[0]; geo.off[1] = m.setting.sensor_offset[1];
     if (std::isnan(o.level)) o.level = -m.setting.fbias;
-    if (int rc = track_check_geom(geo, n)) return rc;
-    if (int rc = track_check_opts(o)) return rc;
-    std::vector<double> cs((size_t)2 * n);
-    for (int k = 0; k < n; ++k) {
-        if (!std::isfinite(thetas[k])) return GPIS_ERR_ARG;
-        cs[2 * (size_t)k] = std::cos((double)thetas[k]);
-        cs[2 * (size_t)k + 1] = std::sin((double)thetas[k]);
-    }
-    if (int rc = t.bind(m.device)) return rc;
-    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : m.stream;
-    if (m.has_tree) (void)m.join_training();
     double p0[6];
     for (int k = 0; k < 6; ++k) p0[k] = pose6[k];
-    const int rc = t.track(m.mq, m.store, m.has_tree, geo, ranges, cs.data(), n, p0, o, s);
-    if (rc != GPIS_OK) { m.fail_rc = rc; fprintf(stderr, "[gpismap_amd] gpis2_track_scan: device path failed (%d)\n", rc); }
+    const int rc = m.consume("gpis2_track_scan", false, hip_stream,
+                             [&](int dev) { if (int e = track_check_opts(o)) return e; return t.bind(dev); },
+                             [&](hipStream_t s) { return t.track(m.mq, m.store, m.has_tree, f.geo, ranges, f.cs.data(), f.n, p0, o, s); });
     if (rc == GPIS_OK && pose6_out) for (int k = 0; k < 6; ++k) pose6_out[k] = (float)t.pose[k];
     return rc;
-} catch (const std::exception& e) { nothrow_report("gpis2_track_scan", e.what()); return GPIS_ERR_STATE; } catch (...) { nothrow_report("gpis2_track_scan", "unknown exception"); return GPIS_ERR_STATE; }
+}
 
 int gpis2_impl_fail(GPisMap* g) { return g->impl()->fail_rc; }
 int gpis2_impl_device(GPisMap* g) { return g->impl()->device; }

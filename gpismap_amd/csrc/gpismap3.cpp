@@ -121,6 +121,8 @@ struct GPisMap3::Impl {
     bool pipeline = false;
     bool device_gather = true;   // K6 range part on the device (gpis3_set_host_gather: the host walk, kept for the cross-check)
     int finish_training();
+    template <class Prepare, class Call>   // what the consumer entries share (gpis3_impl_extract ...)
+    int consume(const char* name, bool need_tree, void* hip_stream, const Prepare& prepare, const Call& call);
     bool ok = false;        // device objects usable
     bool has_tree = false;  // reference: t != 0
     bool gpo_created = false;
@@ -1944,104 +1946,69 @@ bool GPisMap3::loadMap_one(const char* path) try {
     return m.upd_rc == 0;
 } catch (const std::exception& e) { nothrow_report("GPisMap3::loadMap", e.what()); return false; } catch (...) { nothrow_report("GPisMap3::loadMap", "unknown exception"); return false; }
 
-// Surface extraction (gpis3_extract_mesh): testDevice's checks and joins, then the lattice and the vertices through the map's own
-// MapQuery.  A map over several devices extracts on its lead device, which holds the whole map (as testDevice answers there).
-int gpis3_impl_extract(GPisMap3* g, MeshExtractor& me, const int* n3, const float* origin3, const float* step3, float level, void* hip_stream) try {
-    GPisMap3::Impl& m = *g->impl();
-    DeviceScope dev_scope_(m.device);
-    m.fail_rc = 0;
-    if (!m.ok) return GPIS_ERR_HIP;
-    if (!m.has_tree) return GPIS_ERR_STATE;          // nothing to answer with (testDevice refuses the same map)
-    if (m.table_pending) { fprintf(stderr, "[gpismap_amd] gpis3_extract_mesh: sharded update not finished (gpis3_shard_finish)\n"); return GPIS_ERR_STATE; }
-    if (std::isnan(level)) level = -m.setting.fbias;  // the level the map stores its surface points at
-    if (int rc = me.bind(m.device)) return rc;
-    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : m.stream;
-    m.finish_training();
-    const int rc = me.from_map(m.mq, m.store, 3, n3, origin3, step3, level, s);
-    if (rc != GPIS_OK) { m.fail_rc = rc; fprintf(stderr, "[gpismap_amd] gpis3_extract_mesh: device path failed (%d)\n", rc); }
-    if (rc == GPIS_ERR_STATE) m.build_cluster_table();   // (models dropped by the inverse pass: their cells have no GP any more)
+// What gpis3_extract_mesh, gpis3_distance_field, gpis3_render_depth and gpis3_track_depth share: testDevice's checks and joins
+// on the lead device (which holds the whole map, as testDevice answers there), the consumer moved to that device, its call on
+// the caller's stream or the map's, and the report of a failed device path.  prepare(device): what the entry does once the
+// map's state has passed -- the check of its resolved options, the consumer's bind; call(stream): the consumer's call; `name`:
+// the entry, for the messages.
+template <class Prepare, class Call>
+int GPisMap3::Impl::consume(const char* name, bool need_tree, void* hip_stream, const Prepare& prepare, const Call& call) try {
+    DeviceScope dev_scope_(device);
+    fail_rc = 0;
+    if (!ok) return GPIS_ERR_HIP;
+    if (need_tree && !has_tree) return GPIS_ERR_STATE;   // nothing to answer with (testDevice refuses the same map)
+    if (table_pending) { fprintf(stderr, "[gpismap_amd] %s: sharded update not finished (gpis3_shard_finish)\n", name); return GPIS_ERR_STATE; }
+    if (int rc = prepare(device)) return rc;
+    if (has_tree) finish_training();
+    const int rc = call(hip_stream ? (hipStream_t)hip_stream : stream);
+    if (rc != GPIS_OK) { fail_rc = rc; fprintf(stderr, "[gpismap_amd] %s: device path failed (%d)\n", name, rc); }
+    if (rc == GPIS_ERR_STATE) build_cluster_table();     // (models dropped by the inverse pass: their cells have no GP any more)
     return rc;
-} catch (const std::exception& e) { nothrow_report("gpis3_extract_mesh", e.what()); return GPIS_ERR_STATE; } catch (...) { nothrow_report("gpis3_extract_mesh", "unknown exception"); return GPIS_ERR_STATE; }
+} catch (const std::exception& e) { nothrow_report(name, e.what()); return GPIS_ERR_STATE; } catch (...) { nothrow_report(name, "unknown exception"); return GPIS_ERR_STATE; }
 
-// Distance field (gpis3_distance_field): the extraction's checks and joins, then the lattice through the map's MapQuery on the lead device.
-int gpis3_impl_dfield(GPisMap3* g, DistanceField& df, const int* n, const float* origin, const float* step, float level, float max_var,
-                      void* hip_stream) try {
+// Surface extraction (gpis3_extract_mesh): the lattice and the vertices through the map's own MapQuery.  level NaN: -fbias, the
+// level the map stores its surface points at.
+int gpis3_impl_extract(GPisMap3* g, MeshExtractor& me, const int* n3, const float* origin3, const float* step3, float level, void* hip_stream) {
     GPisMap3::Impl& m = *g->impl();
-    DeviceScope dev_scope_(m.device);
-    m.fail_rc = 0;
-    if (!m.ok) return GPIS_ERR_HIP;
-    if (!m.has_tree) return GPIS_ERR_STATE;
-    if (m.table_pending) { fprintf(stderr, "[gpismap_amd] gpis3_distance_field: sharded update not finished (gpis3_shard_finish)\n"); return GPIS_ERR_STATE; }
     if (std::isnan(level)) level = -m.setting.fbias;
-    if (int rc = df.bind(m.device)) return rc;
-    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : m.stream;
-    m.finish_training();
-    const int rc = df.from_map(m.mq, m.store, 3, n, origin, step, level, max_var, s);
-    if (rc != GPIS_OK) { m.fail_rc = rc; fprintf(stderr, "[gpismap_amd] gpis3_distance_field: device path failed (%d)\n", rc); }
-    if (rc == GPIS_ERR_STATE) m.build_cluster_table();
-    return rc;
-} catch (const std::exception& e) { nothrow_report("gpis3_distance_field", e.what()); return GPIS_ERR_STATE; } catch (...) { nothrow_report("gpis3_distance_field", "unknown exception"); return GPIS_ERR_STATE; }
+    return m.consume("gpis3_extract_mesh", true, hip_stream, [&](int dev) { return me.bind(dev); },
+                     [&](hipStream_t s) { return me.from_map(m.mq, m.store, 3, n3, origin3, step3, level, s); });
+}
 
-// Depth rendering (gpis3_render_depth): testDevice's checks and joins, then the march through the map's own MapQuery on the lead
-// device.  cam4 (fx, fy, cx, cy) and wh (width, height) NULL: the map's camera; o.level NaN: -fbias; o.far_step NaN: 0.9 x the search half-width.
-int gpis3_impl_render(GPisMap3* g, Renderer& r, const float* cam4, const int* wh, const float* pose12, RenderOpts o, void* hip_stream) try {
+// Distance field (gpis3_distance_field): the lattice through the map's MapQuery.
+int gpis3_impl_dfield(GPisMap3* g, DistanceField& df, const int* n, const float* origin, const float* step, float level, float max_var,
+                      void* hip_stream) {
     GPisMap3::Impl& m = *g->impl();
-    DeviceScope dev_scope_(m.device);
-    m.fail_rc = 0;
-    if (!m.ok) return GPIS_ERR_HIP;
-    if (!m.has_tree) return GPIS_ERR_STATE;
-    if (m.table_pending) { fprintf(stderr, "[gpismap_amd] gpis3_render_depth: sharded update not finished (gpis3_shard_finish)\n"); return GPIS_ERR_STATE; }
-    RayGeom geo{};
-    geo.dim = 3;
-    geo.fx = cam4 ? cam4[0] : m.cam.fx; geo.fy = cam4 ? cam4[1] : m.cam.fy;
-    geo.cx = cam4 ? cam4[2] : m.cam.cx; geo.cy = cam4 ? cam4[3] : m.cam.cy;
-    geo.width = cam4 ? wh[0] : m.cam.width; geo.height = cam4 ? wh[1] : m.cam.height;
-    for (int i = 0; i < 3; ++i) geo.t[i] = pose12[i];
-    for (int i = 0; i < 9; ++i) geo.R[i] = pose12[3 + i];
+    if (std::isnan(level)) level = -m.setting.fbias;
+    return m.consume("gpis3_distance_field", true, hip_stream, [&](int dev) { return df.bind(dev); },
+                     [&](hipStream_t s) { return df.from_map(m.mq, m.store, 3, n, origin, step, level, max_var, s); });
+}
+
+// Depth rendering (gpis3_render_depth): the march through the map's own MapQuery.  o.level NaN: -fbias; o.far_step NaN: 0.9 x the
+// search half-width.
+int gpis3_impl_render(GPisMap3* g, Renderer& r, const SensorFrame& f, const float* pose12, RenderOpts o, void* hip_stream) {
+    GPisMap3::Impl& m = *g->impl();
     if (std::isnan(o.level)) o.level = -m.setting.fbias;
     if (std::isnan(o.far_step)) o.far_step = 0.9f * m.mq.search_half();
-    const long long n = (long long)geo.width * geo.height;
-    if (int rc = render_check_geom(geo, n)) return rc;
-    if (int rc = render_check_opts(o)) return rc;
-    if (int rc = r.bind(m.device)) return rc;
-    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : m.stream;
-    m.finish_training();
-    const int rc = r.render(m.mq, m.store, geo, nullptr, n, o, s);
-    if (rc != GPIS_OK) { m.fail_rc = rc; fprintf(stderr, "[gpismap_amd] gpis3_render_depth: device path failed (%d)\n", rc); }
-    if (rc == GPIS_ERR_STATE) m.build_cluster_table();   // (models dropped by the inverse pass: their cells have no GP any more)
-    return rc;
-} catch (const std::exception& e) { nothrow_report("gpis3_render_depth", e.what()); return GPIS_ERR_STATE; } catch (...) { nothrow_report("gpis3_render_depth", "unknown exception"); return GPIS_ERR_STATE; }
+    return m.consume("gpis3_render_depth", true, hip_stream,
+                     [&](int dev) { if (int e = render_check_opts(o)) return e; return r.bind(dev); },
+                     [&](hipStream_t s) { return r.render(m.mq, m.store, ray_geom(f, pose12), nullptr, f.n, o, s); });
+}
 
-// Depth tracking (gpis3_track_depth): testDevice's checks and joins, then the iterations through the map's own MapQuery on the
-// lead device.  cam4 (fx, fy, cx, cy) and wh (width, height) NULL: the map's camera; o.level NaN: -fbias.  A map without a tree
+// Depth tracking (gpis3_track_depth): the iterations through the map's own MapQuery.  o.level NaN: -fbias.  A map without a tree
 // is no error: every record keeps f = NaN (status 2).
-int gpis3_impl_track(GPisMap3* g, Tracker& t, const float* cam4, const int* wh, const float* depth, const float* pose12, TrackOpts o,
-                     float* pose12_out, void* hip_stream) try {
+int gpis3_impl_track(GPisMap3* g, Tracker& t, const SensorFrame& f, const float* depth, const float* pose12, TrackOpts o,
+                     float* pose12_out, void* hip_stream) {
     GPisMap3::Impl& m = *g->impl();
-    DeviceScope dev_scope_(m.device);
-    m.fail_rc = 0;
-    if (!m.ok) return GPIS_ERR_HIP;
-    if (m.table_pending) { fprintf(stderr, "[gpismap_amd] gpis3_track_depth: sharded update not finished (gpis3_shard_finish)\n"); return GPIS_ERR_STATE; }
-    TrackGeom geo{};
-    geo.dim = 3;
-    geo.fx = cam4 ? cam4[0] : m.cam.fx; geo.fy = cam4 ? cam4[1] : m.cam.fy;
-    geo.cx = cam4 ? cam4[2] : m.cam.cx; geo.cy = cam4 ? cam4[3] : m.cam.cy;
-    geo.width = cam4 ? wh[0] : m.cam.width; geo.height = cam4 ? wh[1] : m.cam.height;
     if (std::isnan(o.level)) o.level = -m.setting.fbias;
-    const long long n = (long long)geo.width * geo.height;
-    if (int rc = track_check_geom(geo, n)) return rc;
-    if (int rc = track_check_opts(o)) return rc;
-    if (int rc = t.bind(m.device)) return rc;
-    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : m.stream;
-    if (m.has_tree) m.finish_training();
     double p0[12];
     for (int k = 0; k < 12; ++k) p0[k] = pose12[k];
-    const int rc = t.track(m.mq, m.store, m.has_tree, geo, depth, nullptr, n, p0, o, s);
-    if (rc != GPIS_OK) { m.fail_rc = rc; fprintf(stderr, "[gpismap_amd] gpis3_track_depth: device path failed (%d)\n", rc); }
-    if (rc == GPIS_ERR_STATE) m.build_cluster_table();   // (models dropped by the inverse pass: their cells have no GP any more)
+    const int rc = m.consume("gpis3_track_depth", false, hip_stream,
+                             [&](int dev) { if (int e = track_check_opts(o)) return e; return t.bind(dev); },
+                             [&](hipStream_t s) { return t.track(m.mq, m.store, m.has_tree, f.geo, depth, nullptr, f.n, p0, o, s); });
     if (rc == GPIS_OK && pose12_out) for (int k = 0; k < 12; ++k) pose12_out[k] = (float)t.pose[k];
     return rc;
-} catch (const std::exception& e) { nothrow_report("gpis3_track_depth", e.what()); return GPIS_ERR_STATE; } catch (...) { nothrow_report("gpis3_track_depth", "unknown exception"); return GPIS_ERR_STATE; }
+}
 
 // accessors used by the C-ABI (capi.cpp)
 int gpis3_impl_fail(GPisMap3* g) { return g->impl()->fail_rc; }

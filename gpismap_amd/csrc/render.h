@@ -5,6 +5,7 @@
 #pragma once
 #include <cstdint>
 #include "dev_common.h"
+#include "frame.h"
 
 namespace gpis {
 
@@ -41,6 +42,7 @@ struct RayGeom {
 
 struct Renderer {
     static constexpr long long kMaxRays = 1ll << 26;
+    static_assert(kMaxRays == kMaxFramePoints, "frame.h checks a frame against the renderer's limit");
 
     int device = -1;             // buffers live here (the device current at creation; rebound to a map's device on use)
     hipStream_t own = nullptr;   // stream used when the caller passes none
@@ -115,5 +117,14 @@ int compact_flags(const uint8_t* flag, const int* in, long long n, int* out, int
 int render_check_opts(const RenderOpts& o);
 int render_field_check_opts(const RenderFieldOpts& o);
 int render_check_geom(const RayGeom& g, long long n);
+
+// the rays of a checked frame seen from `pose` (3-D [t(3), R(9) column-major], 2-D [t(2), R(4)])
+inline RayGeom ray_geom(const SensorFrame& f, const float* pose) {
+    const TrackGeom& g = f.geo;
+    RayGeom r{g.dim, g.width, g.height, g.fx, g.fy, g.cx, g.cy, {}, {}, {g.off[0], g.off[1]}};
+    for (int k = 0; k < g.dim; ++k) r.t[k] = pose[k];
+    for (int k = 0; k < g.dim * g.dim; ++k) r.R[k] = pose[g.dim + k];
+    return r;
+}
 
 }  // namespace gpis

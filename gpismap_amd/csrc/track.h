@@ -8,6 +8,7 @@
 #include <cstdint>
 #include <functional>
 #include "dev_common.h"
+#include "frame.h"
 
 namespace gpis {
 
@@ -27,16 +28,9 @@ struct TrackOpts {
     int min_inliers;       // fewer: status 2
 };
 
-// the sensor of one call (3-D: camera, depth image [width * height] column-major; 2-D: beams with host-double cos / sin, the
-// map's sensor offset)
-struct TrackGeom {
-    int dim, width, height;
-    float fx, fy, cx, cy;
-    float off[2];
-};
-
 struct Tracker {
     static constexpr long long kMaxPoints = 1ll << 26;
+    static_assert(kMaxPoints == kMaxFramePoints, "frame.h checks a frame against the tracker's limit");
     static constexpr int kSeg = 256;             // points per segment of the first reduction stage
     static constexpr int kSums3 = 29, kSums2 = 11;
 

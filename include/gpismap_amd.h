@@ -419,7 +419,7 @@ int   gpis_render_set_chunk(void* render, int rays);
 /* depth [W*H], record [W*H][8], status [W*H].  cam NULL: the map's camera; opts NULL: the defaults; hip_stream NULL: the map's */
 int   gpis3_render_depth(void* map, void* render, const gpis_cam* cam, const float* pose12, const gpis_render_opts* opts,
                          void* hip_stream);
-/* range [n], record [n][6], status [n] */
+/* range [n], record [n][6], status [n].  More than 2^26 beams -> GPIS_ERR_LIMIT before thetas is read */
 int   gpis2_render_scan(void* map, void* render, const float* thetas, int n, const float* pose6, const gpis_render_opts* opts,
                         void* hip_stream);
 /* host copies of the last result (any pointer may be NULL); GPIS_ERR_STATE without one.  rec is [rays][2 (1 + dim)] after a map
@@ -486,7 +486,7 @@ int   gpis_track_set_chunk(void* tracker, int points);
  * returned pose; hip_stream NULL: the map's */
 int   gpis3_track_depth(void* map, void* tracker, const gpis_cam* cam, const float* depth, const float* pose12_init,
                         const gpis_track_opts* opts, float* pose12_out, void* hip_stream);
-/* thetas, ranges [n] as update() */
+/* thetas, ranges [n] as update().  More than 2^26 beams -> GPIS_ERR_LIMIT before thetas is read */
 int   gpis2_track_scan(void* map, void* tracker, const float* thetas, const float* ranges, int n, const float* pose6_init,
                        const gpis_track_opts* opts, float* pose6_out, void* hip_stream);
 /* host copies of the last result (any pointer may be NULL): H [n x n] row-major and b [n] (n = 6 / 3) at the returned pose,
@@ -514,7 +514,8 @@ int   gpis_track_info(void* tracker, double* out, int n);
  * more than 2^26 pixels / beams -> GPIS_ERR_LIMIT: all with the previous result untouched.  Any other failure leaves no result. */
 int   gpis3_track_depth_field(void* map, void* df, void* tracker, const gpis_cam* cam, const float* depth,
                               const float* pose12_init, const gpis_track_opts* opts, float* pose12_out, void* hip_stream);
-/* off2: the sensor offset (x, y) in the laser frame, NULL = the map's */
+/* off2: the sensor offset (x, y) in the laser frame, NULL = the map's.  More than 2^26 beams -> GPIS_ERR_LIMIT before thetas is
+ * read */
 int   gpis2_track_scan_field(void* map, void* df, void* tracker, const float* thetas, const float* ranges, int n,
                              const float* off2, const float* pose6_init, const gpis_track_opts* opts, float* pose6_out,
                              void* hip_stream);
@@ -560,7 +561,8 @@ int   gpis_render_set_field_tiles(void* render, int on);
 /* depth [W*H], record [W*H][4], status [W*H].  opts NULL: the defaults for the field's step */
 int   gpis3_render_depth_field(void* map, void* df, void* render, const gpis_cam* cam, const float* pose12,
                                const gpis_render_field_opts* opts, void* hip_stream);
-/* range [n], record [n][3], status [n].  off2: the sensor offset (x, y) in the laser frame, NULL = the map's */
+/* range [n], record [n][3], status [n].  off2: the sensor offset (x, y) in the laser frame, NULL = the map's.  More than 2^26
+ * beams -> GPIS_ERR_LIMIT before thetas is read */
 int   gpis2_render_scan_field(void* map, void* df, void* render, const float* thetas, int n, const float* off2,
                               const float* pose6, const gpis_render_field_opts* opts, void* hip_stream);
 

@@ -308,6 +308,19 @@ def test_errors():
     o = gpismap_amd.render_opts(2, tnear=5.0, tfar=1.0)
     assert L.gpis2_render_scan(g2.h, r2.h, P(th), th.size, P(p2), C.byref(o), None) == -1
     assert _same(r2.get(), b)
+    # more than 2^26 beams: refused before thetas is read, also when it holds a NaN (the array is whole, so another order of
+    # the checks would read valid memory and return another code); the result kept
+    big = np.zeros((1 << 26) + 1, F32)
+    assert L.gpis2_render_scan(g2.h, r2.h, P(big), big.size, P(p2), None, None) == -4
+    assert _same(r2.get(), b)
+    big[2] = np.nan
+    assert L.gpis2_render_scan(g2.h, r2.h, P(big), big.size, P(p2), None, None) == -4
+    assert _same(r2.get(), b)
+    del big
+    # the map's own camera when the caller passes none: the same bits as the same values passed
+    x = gm.render_depth(replay.IDENTITY_POSE, renderer=r)
+    assert x[0].size == 640 * 480 and np.count_nonzero(x[2] == 0) > 1000
+    assert _same(gm.render_depth(replay.IDENTITY_POSE, cam6=(568.0, 568.0, 310.0, 224.0, 640, 480), renderer=r), x)
     # a map with no tree: an error, no result
     empty = gpismap_amd.GPisMap3()
     assert call3(map_h=empty.h) == -3

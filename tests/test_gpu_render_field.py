@@ -373,6 +373,15 @@ def test_errors_and_map_defaults():
     assert _call2(L, g2.h, df2, r2, bad_th, fr["pose"]) == -1
     assert _call2(L, g2.h, df2, r2, fr["thetas"], fr["pose"], slack=-1.0) == -1
     assert _same(r2.get(), b)
+    # more than 2^26 beams: refused before thetas is read, also when it holds a NaN (the array is whole, so another order of
+    # the checks would read valid memory and return another code); the result kept
+    big = np.zeros((1 << 26) + 1, F32)
+    assert _call2(L, g2.h, df2, r2, big, fr["pose"]) == -4
+    assert _same(r2.get(), b)
+    big[2] = np.nan
+    assert _call2(L, g2.h, df2, r2, big, fr["pose"]) == -4
+    assert _same(r2.get(), b)
+    del big
     # the map's camera / sensor offset when the caller passes none: the same bits as passing them
     assert _call3(L, gm.h, df, r, SYN_TRUE) == 0
     x = r.get()

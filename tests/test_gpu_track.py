@@ -388,6 +388,20 @@ def test_errors():
     o = gpismap_amd.track_opts(2, huber=-1.0)
     assert L.gpis2_track_scan(g2.h, t2.h, P(fr["thetas"]), P(fr["ranges"]), n, P(fr["pose"]), C.byref(o), None, None) == -1
     assert _same((b[0], t2.result()), b)
+    # more than 2^26 beams: refused before thetas is read, also when it holds a NaN (the arrays are whole, so another order of
+    # the checks would read valid memory and return another code); the result kept
+    big = np.zeros((1 << 26) + 1, F32)
+    assert L.gpis2_track_scan(g2.h, t2.h, P(big), P(big), big.size, P(fr["pose"]), None, None, None) == -4
+    assert _same((b[0], t2.result()), b)
+    big_nan = np.zeros((1 << 26) + 1, F32); big_nan[2] = np.nan
+    assert L.gpis2_track_scan(g2.h, t2.h, P(big_nan), P(big), big.size, P(fr["pose"]), None, None, None) == -4
+    assert _same((b[0], t2.result()), b)
+    del big, big_nan
+    # the map's own camera when the caller passes none: the same bits as the same values passed
+    d640 = replay.synthetic_depth(1)
+    x = gm.track_depth(d640, start, tracker=t)
+    assert x[1]["inliers"] > 1000 and x[1]["resid"].size == 640 * 480
+    assert _same(gm.track_depth(d640, start, cam6=(568.0, 568.0, 310.0, 224.0, 640, 480), tracker=t), x)
     assert L.gpis_track_set_chunk(t.h, -1) == -1
     # a tracker without a result
     fresh = gpismap_amd.Tracker()

@@ -330,6 +330,15 @@ def test_errors_and_map_defaults():
     bad_th = dict(fr, thetas=fr["thetas"].copy()); bad_th["thetas"][2] = np.nan
     assert _call2(L, g2.h, df2, t2, bad_th, fr["pose"])[0] == -1
     assert _same((b[0], t2.result()), b)
+    # more than 2^26 beams: refused before thetas is read, also when it holds a NaN (the arrays are whole, so another order of
+    # the checks would read valid memory and return another code); the result kept
+    big = np.zeros((1 << 26) + 1, F32)
+    assert _call2(L, g2.h, df2, t2, dict(thetas=big, ranges=big), fr["pose"])[0] == -4
+    assert _same((b[0], t2.result()), b)
+    big_nan = np.zeros((1 << 26) + 1, F32); big_nan[2] = np.nan
+    assert _call2(L, g2.h, df2, t2, dict(thetas=big_nan, ranges=big), fr["pose"])[0] == -4
+    assert _same((b[0], t2.result()), b)
+    del big, big_nan
     # the map's camera / sensor offset when the caller passes none: the same bits as passing them
     d640 = replay.synthetic_depth(1)
     rc, p = _call3(L, gm.h, df, t, d640, start)
