@@ -65,6 +65,11 @@ class gpis_plan_opts(C.Structure):
                 ("max_rounds", C.c_int)]
 
 
+class gpis_cover_opts(C.Structure):
+    _fields_ = [("back_off", C.c_float), ("max_gap", C.c_float), ("clearance", C.c_float), ("min_size", C.c_int),
+                ("max_rounds", C.c_int)]
+
+
 class gpis_traj_opts(C.Structure):
     _fields_ = [("clearance", C.c_float), ("margin", C.c_float), ("w_smooth", C.c_float), ("w_obs", C.c_float),
                 ("rate", C.c_float), ("max_move", C.c_float), ("tol", C.c_float), ("iters", C.c_int), ("sub", C.c_int)]
@@ -301,6 +306,23 @@ def lib():
         L.gpis_mppi_get.argtypes = [vp, dp, dp, C.POINTER(C.c_ulonglong), ip, dp, dp]
         L.gpis_mppi_device.argtypes = [vp, C.POINTER(C.c_void_p), C.c_int]
         L.gpis_mppi_info.argtypes = [vp, dp, C.c_int]
+    if hasattr(L, "gpis_cover_create"):
+        co, ub, ll = C.POINTER(gpis_cover_opts), C.POINTER(C.c_ubyte), C.POINTER(C.c_longlong)
+        L.gpis_cover_default_opts.argtypes = [C.c_int, C.c_float, co]
+        L.gpis_cover_create.restype = vp
+        L.gpis_cover_create.argtypes = []
+        L.gpis_cover_destroy.argtypes = [vp]
+        L.gpis_cover_reset.argtypes = [vp, vp]
+        L.gpis_cover_set.argtypes = [vp, ub, C.c_longlong]
+        L.gpis_cover_get.argtypes = [vp, ub, C.c_longlong]
+        L.gpis_cover_device.argtypes = [vp, C.POINTER(C.c_void_p)]
+        L.gpis3_cover_depth.argtypes = [vp, vp, C.POINTER(gpis_cam), fp, fp, co, vp]
+        L.gpis2_cover_scan.argtypes = [vp, vp, fp, fp, C.c_int, fp, fp, co, vp]
+        L.gpis_cover_frontiers.argtypes = [vp, vp, co, vp]
+        L.gpis_cover_counts.argtypes = [vp, ll, ll, ll]
+        L.gpis_cover_get_frontiers.argtypes = [vp, ip, ip, ll, ip, ip, ip, ip]
+        L.gpis_cover_restrict.argtypes = [vp, vp, vp, C.c_float, vp]
+        L.gpis_cover_info.argtypes = [vp, dp, C.c_int]
     _lib = L
     return L
 
@@ -662,6 +684,10 @@ class GPisMap3:
         map is read."""
         return pf._update_depth(self.h, self._wh, field, depth, cam6, stream, opts)
 
+    def cover_depth(self, cover, depth, pose, cam6=None, stream=None, **opts):
+        """Coverage.integrate_depth with this map's camera (cam6 None)."""
+        return cover._integrate_depth(self.h, self._wh, depth, pose, cam6, stream, opts)
+
     def render_depth_field(self, field, pose, cam6=None, renderer=None, **opts):
         """render_depth from a DistanceField instead of the map (gpis3_render_depth_field): sphere tracing through the field's
         sampler, one fused kernel.  cam6 None = this map's camera; nothing else of the map is read.  Returns (depth [W*H],
@@ -809,6 +835,10 @@ class GPisMap:
     def pf_update_scan_field(self, field, pf, thetas, ranges, stream=None, **opts):
         """ParticleFilter.update_scan with this map's sensor offset (gpis2_pf_update_scan); nothing else of the map is read."""
         return pf._update_scan(self.h, field, thetas, ranges, None, stream, opts)
+
+    def cover_scan(self, cover, thetas, ranges, pose6, off2=None, stream=None, **opts):
+        """Coverage.integrate_scan with this map's sensor offset (off2 None)."""
+        return cover._integrate_scan(self.h, thetas, ranges, pose6, off2, stream, opts)
 
     def render_scan_field(self, field, thetas, pose6, renderer=None, **opts):
         """render_scan from a DistanceField instead of the map (gpis2_render_scan_field), with this map's sensor offset;
@@ -1185,6 +1215,27 @@ class DistanceField:
         first control of the new nominal sequence and dict(Jmin, best, neff, hits, nominal_cost, nominal_hits, T, Th, S2)."""
         return controller.step(self, pose, goal=goal, planner=planner, stream=stream, **opts)
 
+    def explore(self, cover, start, planner=None, out=None, unseen_dist=None, **opts):
+        """Where to go next to see more: the frontiers of `cover` (a Coverage on this field's lattice), this field restricted to
+        seen space, a plan on the restricted field with the cluster representatives as goals, and the path from `start`
+        [dim].  opts: the gpis_plan_opts fields plus the coverage's min_size; `clearance` (default the coverage's, 3 steps) is
+        shared by the frontiers and the planner, max_rounds is the planner's.  Returns (path [len, dim] f32, status,
+        clusters): the planner's path status, or 4 and an empty path when there is no frontier; clusters as
+        Coverage.frontiers.  A composition of calls that exist: no device code of its own."""
+        copts = {k: opts.pop(k) for k in ("min_size", "back_off", "max_gap") if k in opts}
+        if "clearance" in opts:
+            copts["clearance"] = opts["clearance"]
+        clusters = cover.frontiers(self, **copts)
+        dim = self.info()["dim"]
+        if clusters["label"].size == 0:
+            return np.zeros((0, dim), np.float32), 4, clusters
+        opts.setdefault("clearance", cover_opts(dim, self._step()).clearance)
+        r = cover.restrict(self, out=out, unseen_dist=unseen_dist)
+        p = planner if planner is not None else self._own_planner()
+        p.solve(r, clusters["rep"], **opts)
+        paths, _, status = p.paths(np.ascontiguousarray(start, dtype=np.float32).reshape(1, dim))
+        return paths[0], int(status[0]), clusters
+
     def _step(self):
         inf = self.info()
         if inf["dim"] == 0:
@@ -1317,6 +1368,170 @@ class Planner:
         holding the input (default: a new one), ready for optimize()."""
         t = trajectories if trajectories is not None else Trajectories()
         return t.from_paths(self, N)
+
+
+def cover_opts(dim, step, **opts):
+    """gpis_cover_opts of the library's defaults for `dim` and a field of lattice step `step` (gpis_cover_default_opts) with the
+    given fields replaced."""
+    o = gpis_cover_opts()
+    _check(lib().gpis_cover_default_opts(int(dim), float(step), C.byref(o)), "gpis_cover_default_opts")
+    names = {f[0] for f in gpis_cover_opts._fields_}
+    for k, v in opts.items():
+        if k not in names:
+            raise GpisError("unknown coverage option %r" % k)
+        setattr(o, k, v)
+    return o
+
+
+class Coverage:
+    """Which lattice points of a field a sensor has seen as free space (gpis_cover_*): one byte per point on the device, the
+    frontiers of the seen space, and fields restricted to it.  reset(field) takes the field's lattice; every later call wants a
+    field of that lattice."""
+
+    INFO_KEYS = ("valid", "dim", "nx", "ny", "nz", "step", "frames", "frontiers", "points", "components", "clusters", "rounds",
+                 "integrate_ms", "frontiers_ms")
+    INT_KEYS = ("valid", "dim", "nx", "ny", "nz", "frames", "frontiers", "points", "components", "clusters", "rounds")
+
+    def __init__(self):
+        self.L = lib()
+        if self.L.gpis_device_count() < 1:
+            raise GpisError("no HIP device: gpismap_amd has no CPU fallback")
+        self.h = C.c_void_p(self.L.gpis_cover_create())
+        if not self.h:
+            raise GpisError("gpis_cover_create failed")
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.gpis_cover_destroy(self.h)
+            self.h = None
+
+    __del__ = close
+
+    def reset(self, field):
+        """The lattice of `field` (a DistanceField holding a result), nothing seen.  Returns self."""
+        _check(self.L.gpis_cover_reset(self.h, field.h), "gpis_cover_reset")
+        return self
+
+    def info(self):
+        out = np.zeros(len(self.INFO_KEYS), dtype=np.float64)
+        _check(self.L.gpis_cover_info(self.h, _p(out, C.c_double), out.size), "gpis_cover_info")
+        d = dict(zip(self.INFO_KEYS, out.tolist()))
+        for k in self.INT_KEYS:
+            d[k] = int(d[k])
+        return d
+
+    def _lattice(self):
+        i = self.info()
+        if not i["valid"]:
+            raise GpisError("coverage holds no lattice: reset(field) first")
+        return i, (i["nx"], i["ny"], i["nz"])[:i["dim"]]
+
+    def _opts(self, opts):
+        i, _ = self._lattice()
+        return cover_opts(i["dim"], i["step"], **opts)
+
+    def integrate_depth(self, depth, pose, cam6, map=None, stream=None, **opts):
+        """Mark what a depth frame sees as free space (gpis3_cover_depth): a lattice point is seen iff it projects into the
+        image, its nearest pixel's depth is valid and the point lies more than back_off in front of it.  depth [W*H]
+        column-major as update(); pose [12] f32; cam6 None: the camera of `map` (a GPisMap3).  opts: back_off.  Returns self."""
+        return self._integrate_depth(map.h if map is not None else None, map._wh if map is not None else None,
+                                     depth, pose, cam6, stream, opts)
+
+    def integrate_scan(self, thetas, ranges, pose6, off2, map=None, stream=None, **opts):
+        """Mark what a laser scan sees as free space (gpis2_cover_scan): a lattice point is seen iff it lies between two
+        neighbouring valid beams no more than max_gap apart and closer than the nearer of their ranges less back_off.  off2
+        None: the sensor offset of `map` (a GPisMap).  opts: back_off, max_gap.  Returns self."""
+        return self._integrate_scan(map.h if map is not None else None, thetas, ranges, pose6, off2, stream, opts)
+
+    def _integrate_depth(self, map_h, map_wh, depth, pose, cam6, stream, opts):
+        pose = np.ascontiguousarray(pose, dtype=np.float32).ravel()
+        if pose.size != 12:
+            raise GpisError("pose must have 12 elements")
+        depth, cam = _depth_frame("integrate_depth", depth, cam6, map_h, map_wh)
+        o = self._opts(opts)
+        _check(self.L.gpis3_cover_depth(map_h, self.h, cam, _p(depth), _p(pose), C.byref(o), C.c_void_p(stream or 0)),
+               "gpis3_cover_depth")
+        return self
+
+    def _integrate_scan(self, map_h, thetas, ranges, pose6, off2, stream, opts):
+        pose6 = np.ascontiguousarray(pose6, dtype=np.float32).ravel()
+        if pose6.size != 6:
+            raise GpisError("pose6 must have 6 elements")
+        thetas, ranges, off = _scan_frame("integrate_scan", thetas, ranges, off2, map_h)
+        o = self._opts(opts)
+        _check(self.L.gpis2_cover_scan(map_h, self.h, _p(thetas), _p(ranges), thetas.size, _p(pose6), off, C.byref(o),
+                                       C.c_void_p(stream or 0)), "gpis2_cover_scan")
+        return self
+
+    def set(self, seen):
+        """Upload the mask (any array of the lattice's point count, x fastest; non-zero = seen).  Returns self."""
+        _, shape = self._lattice()
+        m = np.ascontiguousarray(np.asarray(seen) != 0, dtype=np.uint8).ravel()
+        if m.size != int(np.prod(shape)):
+            raise GpisError("the mask must have %d elements" % int(np.prod(shape)))
+        _check(self.L.gpis_cover_set(self.h, _p(m, C.c_ubyte), m.size), "gpis_cover_set")
+        return self
+
+    def get(self):
+        """The mask, uint8 of shape shape[::-1] (x fastest)."""
+        _, shape = self._lattice()
+        m = np.zeros(int(np.prod(shape)), np.uint8)
+        _check(self.L.gpis_cover_get(self.h, _p(m, C.c_ubyte), m.size), "gpis_cover_get")
+        return m.reshape(shape[::-1])
+
+    def device_ptr(self):
+        """Device address of the mask (0 before reset)."""
+        a = C.c_void_p(0)
+        _check(self.L.gpis_cover_device(self.h, C.byref(a)), "gpis_cover_device")
+        return a.value or 0
+
+    def frontiers(self, field, points=False, stream=None, **opts):
+        """The frontiers of the seen space on `field` (gpis_cover_frontiers): seen points with dist >= clearance that have an
+        unseen axis neighbour with dist >= clearance, clustered under full connectivity.  opts: clearance, min_size,
+        max_rounds.  Returns a dict over the clusters of at least min_size points, ordered by label: label (the smallest
+        lattice index), count, centroid [c, dim] (world, double), rep [c, dim] (float32: the member lattice point nearest the
+        centroid), rep_index, sums [c, 3], box [c, 6] (min i, j, k, max i, j, k), and npoints / ncomponents; with points=True
+        also points [m] (ascending lattice indices) and point_label [m]."""
+        i, shape = self._lattice()
+        dim = i["dim"]
+        o = self._opts(opts)
+        _check(self.L.gpis_cover_frontiers(self.h, field.h, C.byref(o), C.c_void_p(stream or 0)), "gpis_cover_frontiers")
+        m, nc, c = C.c_longlong(0), C.c_longlong(0), C.c_longlong(0)
+        _check(self.L.gpis_cover_counts(self.h, C.byref(m), C.byref(nc), C.byref(c)), "gpis_cover_counts")
+        m, nc, c = m.value, nc.value, c.value
+        label, count, rep = np.zeros(c, np.int32), np.zeros(c, np.int32), np.zeros(c, np.int32)
+        sums, box = np.zeros((c, 3), np.int64), np.zeros((c, 6), np.int32)
+        pts = np.zeros(m, np.int32) if points else None
+        pl = np.zeros(m, np.int32) if points else None
+        _check(self.L.gpis_cover_get_frontiers(self.h, _p(label, C.c_int), _p(count, C.c_int), _p(sums, C.c_longlong), _p(box, C.c_int),
+                                               _p(rep, C.c_int), _p(pts, C.c_int) if points else None,
+                                               _p(pl, C.c_int) if points else None), "gpis_cover_get_frontiers")
+        finf = field.info()
+        o32 = np.asarray(finf["origin"], np.float32)
+        st = np.float32(finf["step"])
+        nx, ny = shape[0], shape[1]
+        r64 = rep.astype(np.int64)
+        ijk = np.stack([r64 % nx, (r64 // nx) % ny, r64 // (nx * ny)], axis=1)[:, :dim]
+        out = dict(label=label, count=count, sums=sums, box=box, rep_index=rep, npoints=m, ncomponents=nc,
+                   rep=(o32[None, :] + ijk.astype(np.float32) * st).astype(np.float32).reshape(c, dim),
+                   centroid=o32.astype(np.float64)[None, :] + (sums[:, :dim].astype(np.float64)
+                                                               / np.maximum(count, 1).astype(np.float64)[:, None]) * np.float64(st))
+        if points:
+            out["points"], out["point_label"] = pts, pl
+        return out
+
+    def restrict(self, field, out=None, unseen_dist=None, stream=None):
+        """A copy of `field` restricted to seen space (gpis_cover_restrict): dist = seen ? field's : unseen_dist (default -step:
+        blocked at any clearance >= 0, and finite for the sampler).  out: the DistanceField to fill (default: one kept by this
+        coverage; never `field` itself).  Returns it: everything that takes a DistanceField runs on it unchanged."""
+        if out is None:
+            if getattr(self, "_restricted", None) is None:
+                self._restricted = DistanceField()
+            out = self._restricted
+        u = -field._step() if unseen_dist is None else float(unseen_dist)
+        _check(self.L.gpis_cover_restrict(self.h, field.h, out.h, u, C.c_void_p(stream or 0)), "gpis_cover_restrict")
+        out._device = field.device()
+        return out
 
 
 def traj_opts(dim, step, **opts):

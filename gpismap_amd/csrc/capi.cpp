@@ -17,6 +17,7 @@
 #include "plan.h"
 #include "traj.h"
 #include "mppi.h"
+#include "cover.h"
 #include "obsgp.h"
 #include "ongpis.h"
 
@@ -1331,6 +1332,157 @@ int gpis_locate_device(void* locator, void** d_cost, void** d_inliers) {
     if (!l.valid) return GPIS_ERR_STATE;
     if (d_cost) *d_cost = (void*)l.d_cost();
     if (d_inliers) *d_inliers = (void*)l.d_inliers();
+    return GPIS_OK;
+}
+
+// ---- coverage, frontiers, the field restricted to seen space -----------------------------------------------------------------
+int gpis_cover_default_opts(int dim, float step, gpis_cover_opts* o) {
+    CoverOpts c;
+    if (!o) return GPIS_ERR_ARG;
+    if (int rc = cover_default_opts(dim, step, &c)) return rc;
+    o->back_off = c.back_off; o->max_gap = c.max_gap; o->clearance = c.clearance; o->min_size = c.min_size; o->max_rounds = c.max_rounds;
+    return GPIS_OK;
+}
+void* gpis_cover_create(void) {
+    if (gpis_device_count() < 1) { fprintf(stderr, "[gpismap_amd] no HIP device\n"); return nullptr; }
+    Coverage* c = new (std::nothrow) Coverage();
+    if (c && !c->own) { delete c; return nullptr; }
+    return c;
+}
+void gpis_cover_destroy(void* cover) { delete (Coverage*)cover; }
+// the options of a call: the caller's, or the defaults for the holder's lattice; checked before anything is dropped
+static int cover_args(void* cover, const gpis_cover_opts* opts, CoverOpts* o) {
+    if (!cover) return GPIS_ERR_ARG;
+    const Coverage& c = *(const Coverage*)cover;
+    if (opts) { o->back_off = opts->back_off; o->max_gap = opts->max_gap; o->clearance = opts->clearance; o->min_size = opts->min_size;
+                o->max_rounds = opts->max_rounds; }
+    else if (!c.has_lattice) return GPIS_ERR_STATE;
+    else (void)cover_default_opts(c.dim, c.step, o);
+    return cover_check_opts(*o);
+}
+int gpis_cover_reset(void* cover, void* d) {
+    if (!cover || !d) return GPIS_ERR_ARG;
+    const DistanceField& df = *(const DistanceField*)d;
+    if (!df.valid) return GPIS_ERR_STATE;
+    Coverage& c = *(Coverage*)cover;
+    DeviceScope ds(df.device);
+    try { return c.reset(df); } catch (...) { c.has_lattice = false; return GPIS_ERR_STATE; }
+}
+int gpis_cover_set(void* cover, const unsigned char* seen, long long n) {
+    if (!cover || !seen) return GPIS_ERR_ARG;
+    Coverage& c = *(Coverage*)cover;
+    if (!c.has_lattice) return GPIS_ERR_STATE;
+    if (n != c.ngrid) return GPIS_ERR_ARG;
+    DeviceScope ds(c.device);
+    return c.set(seen);
+}
+int gpis_cover_get(void* cover, unsigned char* seen, long long n) {
+    if (!cover || !seen) return GPIS_ERR_ARG;
+    Coverage& c = *(Coverage*)cover;
+    if (!c.has_lattice) return GPIS_ERR_STATE;
+    if (n != c.ngrid) return GPIS_ERR_ARG;
+    DeviceScope ds(c.device);
+    return c.get(seen);
+}
+int gpis_cover_device(void* cover, const unsigned char** d_seen) {
+    if (!cover) return GPIS_ERR_ARG;
+    const Coverage& c = *(const Coverage*)cover;
+    if (d_seen) *d_seen = c.has_lattice ? c.d_seen : nullptr;
+    return GPIS_OK;
+}
+// the pose, the holder's state and dim, then the gather on the holder's device
+static int cover_call(Coverage& c, const SensorFrame& f, const float* in, const float* pose, const CoverOpts& o, void* stream) {
+    for (int k = 0; k < (f.geo.dim == 3 ? 12 : 6); ++k) if (!std::isfinite(pose[k])) return GPIS_ERR_ARG;
+    if (!c.has_lattice) return GPIS_ERR_STATE;
+    if (c.dim != f.geo.dim) return GPIS_ERR_ARG;
+    DeviceScope ds(c.device);
+    try {
+        return c.integrate(f, in, pose, o, stream ? (hipStream_t)stream : c.own);
+    } catch (...) { return GPIS_ERR_STATE; }
+}
+int gpis3_cover_depth(void* m, void* cover, const gpis_cam* cam, const float* depth, const float* pose12, const gpis_cover_opts* opts,
+                      void* stream) {
+    if (!cover || !depth || !pose12 || (!cam && !m)) return GPIS_ERR_ARG;
+    CoverOpts o;
+    if (int rc = cover_args(cover, opts, &o)) return rc;
+    SensorFrame f;
+    if (int rc = depth_frame(m, cam, &f)) return rc;
+    return cover_call(*(Coverage*)cover, f, depth, pose12, o, stream);
+}
+int gpis2_cover_scan(void* m, void* cover, const float* thetas, const float* ranges, int n, const float* pose6, const float* off2,
+                     const gpis_cover_opts* opts, void* stream) {
+    if (!cover || !thetas || !ranges || !pose6 || n < 1 || (!off2 && !m)) return GPIS_ERR_ARG;
+    CoverOpts o;
+    if (int rc = cover_args(cover, opts, &o)) return rc;
+    SensorFrame f;
+    if (int rc = scan_frame(m, thetas, n, off2, &f)) return rc;
+    return cover_call(*(Coverage*)cover, f, ranges, pose6, o, stream);
+}
+int gpis_cover_frontiers(void* cover, void* d, const gpis_cover_opts* opts, void* stream) {
+    if (!cover || !d) return GPIS_ERR_ARG;
+    CoverOpts o;
+    if (int rc = cover_args(cover, opts, &o)) return rc;
+    Coverage& c = *(Coverage*)cover;
+    const DistanceField& df = *(const DistanceField*)d;
+    if (!c.has_lattice || !df.valid) return GPIS_ERR_STATE;
+    if (!c.same_lattice(df)) return GPIS_ERR_ARG;
+    DeviceScope ds(c.device);
+    try {
+        const int rc = c.frontiers(df, o, stream ? (hipStream_t)stream : c.own);
+        if (rc != GPIS_OK) c.clear_frontiers();
+        return rc;
+    } catch (...) { c.clear_frontiers(); return GPIS_ERR_STATE; }
+}
+int gpis_cover_counts(void* cover, long long* npoints, long long* ncomponents, long long* nclusters) {
+    if (!cover) return GPIS_ERR_ARG;
+    const Coverage& c = *(const Coverage*)cover;
+    if (!c.frontiers_valid) return GPIS_ERR_STATE;
+    if (npoints) *npoints = c.npoints;
+    if (ncomponents) *ncomponents = c.ncomponents;
+    if (nclusters) *nclusters = (long long)c.label.size();
+    return GPIS_OK;
+}
+int gpis_cover_get_frontiers(void* cover, int* label, int* count, long long* sums, int* box, int* rep, int* points, int* point_label) {
+    if (!cover) return GPIS_ERR_ARG;
+    Coverage& c = *(Coverage*)cover;
+    if (!c.frontiers_valid) return GPIS_ERR_STATE;
+    const size_t nc = c.label.size();
+    if (label && nc) std::memcpy(label, c.label.data(), sizeof(int) * nc);
+    if (count && nc) std::memcpy(count, c.count.data(), sizeof(int) * nc);
+    if (sums && nc) std::memcpy(sums, c.sums.data(), sizeof(long long) * 3 * nc);
+    if (box && nc) std::memcpy(box, c.box.data(), sizeof(int) * 6 * nc);
+    if (rep && nc) std::memcpy(rep, c.rep.data(), sizeof(int) * nc);
+    if ((points || point_label) && c.npoints > 0) {
+        DeviceScope ds(c.device);
+        const size_t m = (size_t)c.npoints;
+        if (points) GPIS_HIP(hipMemcpyAsync(points, c.d_list, sizeof(int) * m, hipMemcpyDeviceToHost, c.own));
+        if (point_label) GPIS_HIP(hipMemcpyAsync(point_label, c.d_plabel, sizeof(int) * m, hipMemcpyDeviceToHost, c.own));
+        GPIS_HIP(hipStreamSynchronize(c.own));
+    }
+    return GPIS_OK;
+}
+int gpis_cover_restrict(void* cover, void* d_in, void* d_out, float unseen_dist, void* stream) {
+    if (!cover || !d_in || !d_out || d_in == d_out || !std::isfinite(unseen_dist)) return GPIS_ERR_ARG;
+    Coverage& c = *(Coverage*)cover;
+    const DistanceField& in = *(const DistanceField*)d_in;
+    DistanceField& out = *(DistanceField*)d_out;
+    if (!c.has_lattice || !in.valid) return GPIS_ERR_STATE;
+    if (!c.same_lattice(in)) return GPIS_ERR_ARG;
+    DeviceScope ds(c.device);
+    try {
+        const int rc = c.restrict_field(in, out, unseen_dist, stream ? (hipStream_t)stream : c.own);
+        if (rc != GPIS_OK) out.clear_result();
+        return rc;
+    } catch (...) { out.clear_result(); return GPIS_ERR_STATE; }
+}
+int gpis_cover_info(void* cover, double* out, int n) {
+    if (!cover || !out || n < 0) return GPIS_ERR_ARG;
+    const Coverage& c = *(const Coverage*)cover;
+    const bool v = c.has_lattice;
+    const double w[14] = {v ? 1.0 : 0.0, v ? (double)c.dim : 0.0, v ? (double)c.n[0] : 0.0, v ? (double)c.n[1] : 0.0, v ? (double)c.n[2] : 0.0,
+                          v ? (double)c.step : 0.0, (double)c.frames, c.frontiers_valid ? 1.0 : 0.0, (double)c.npoints,
+                          (double)c.ncomponents, (double)c.label.size(), (double)c.rounds, c.integrate_ms, c.frontiers_ms};
+    for (int i = 0; i < n && i < 14; ++i) out[i] = w[i];
     return GPIS_OK;
 }
 

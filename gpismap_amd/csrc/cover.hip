@@ -1,0 +1,565 @@
+// Coverage, frontiers and the field restricted to seen space (cover.h).
+//
+// Lattice point (i, j, k): index p = (k ny + j) nx + i, world point o + (float)i * s (no FMA: -ffp-contract=off).  Every double
+// expression below is written in the order tests/cover_ref.py evaluates it; the build does not contract, so the bits agree.
+//
+// Integration: one thread per lattice point (grid stride) reads its own byte, leaves a seen point alone, else projects the point
+// into the frame (3-D: the nearest pixel's depth; 2-D: a binary search of the sector table) and writes its own byte.
+// Frontiers: count, scan, write over chunks of 2048 points (the lattice indices come out ascending) with the rank grid as a
+// by-product; labels by min-label propagation over the list -- thread r alone writes label[r], values only fall, so the fixed point
+// does not depend on the schedule --; the roots compacted by the same three kernels; the table by integer atomics.
+#include <chrono>
+#include <climits>
+#include <cmath>
+#include <cstring>
+#include "cover.h"
+#include "block_ops.h"
+#include "dfield.h"
+
+namespace gpis {
+
+namespace {
+
+constexpr int kBlock = Coverage::kBlock;
+constexpr int kItems = Coverage::kItems;
+constexpr int kChunk = Coverage::kChunk;
+constexpr int kTabWords = Coverage::kTabWords;
+
+struct CovLat {
+    int dim, nx, ny, nz;
+    float ox, oy, oz, step;
+};
+struct CovPose { float v[12]; };
+
+// ---- integration ----------------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(kBlock) cover_depth_kernel(CovLat L, int n, CovPose P, double fx, double fy, double cx, double cy, int W, int H,
+                                                             const float* __restrict__ depth, double back_off,
+                                                             unsigned char* __restrict__ seen) {
+    const int nxy = L.nx * L.ny;
+    const double t0 = (double)P.v[0], t1 = (double)P.v[1], t2 = (double)P.v[2];
+    for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < n; p += gridDim.x * blockDim.x) {
+        if (seen[p]) continue;
+        const int i = p % L.nx, j = (p / L.nx) % L.ny, k = p / nxy;
+        const float x0 = L.ox + (float)i * L.step, x1 = L.oy + (float)j * L.step, x2 = L.oz + (float)k * L.step;
+        const double d0 = (double)x0 - t0, d1 = (double)x1 - t1, d2 = (double)x2 - t2;
+        const double lx = (double)P.v[3] * d0 + (double)P.v[4] * d1 + (double)P.v[5] * d2;
+        const double ly = (double)P.v[6] * d0 + (double)P.v[7] * d1 + (double)P.v[8] * d2;
+        const double lz = (double)P.v[9] * d0 + (double)P.v[10] * d1 + (double)P.v[11] * d2;
+        if (!(lz > 0.0)) continue;
+        const double u = floor(fx * lx / lz + cx + 0.5), v = floor(fy * ly / lz + cy + 0.5);
+        if (!(u >= 0.0 && u < (double)W && v >= 0.0 && v < (double)H)) continue;
+        const double d = (double)depth[(int)u * H + (int)v];
+        if (d > 0.4 && d < 4.0 && lz < d - back_off) seen[p] = 1;
+    }
+}
+
+__global__ void __launch_bounds__(kBlock) cover_scan_kernel(CovLat L, int n, CovPose P, double off0, double off1, const double* __restrict__ q,
+                                                            const double* __restrict__ lim, int m, unsigned char* __restrict__ seen) {
+    const double t0 = (double)P.v[0], t1 = (double)P.v[1];
+    for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < n; p += gridDim.x * blockDim.x) {
+        if (seen[p]) continue;
+        const int i = p % L.nx, j = p / L.nx;
+        const float x0 = L.ox + (float)i * L.step, x1 = L.oy + (float)j * L.step;
+        const double d0 = (double)x0 - t0, d1 = (double)x1 - t1;
+        const double lx = ((double)P.v[2] * d0 + (double)P.v[3] * d1) - off0;
+        const double ly = ((double)P.v[4] * d0 + (double)P.v[5] * d1) - off1;
+        const double ll = lx * lx + ly * ly;
+        bool s = ll == 0.0;
+        if (!s) {
+            const double e = lim[sector_of(q, m, pseudo_angle(lx, ly))];
+            s = ll < e * e;                       // (e = 0 where the sector is wide or ends at the sensor)
+        }
+        if (s) seen[p] = 1;
+    }
+}
+
+__global__ void __launch_bounds__(kBlock) cover_binarise_kernel(unsigned char* __restrict__ seen, int n) {
+    for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < n; p += gridDim.x * blockDim.x) seen[p] = seen[p] ? 1 : 0;
+}
+
+// ---- compaction: count, scan, write -----------------------------------------------------------------------------------------
+// a frontier point: seen and traversable, with an unseen and traversable axis neighbour inside the lattice
+struct FrontierPred {
+    CovLat L;
+    const unsigned char* seen;
+    const float* dist;
+    float clearance;
+    __device__ bool operator()(int p) const {
+        if (!(seen[p] && dist[p] >= clearance)) return false;
+        const int nxy = L.nx * L.ny;
+        const int i = p % L.nx, j = (p / L.nx) % L.ny, k = p / nxy;
+        bool f = false;
+        if (i > 0) f = f || (!seen[p - 1] && dist[p - 1] >= clearance);
+        if (i + 1 < L.nx) f = f || (!seen[p + 1] && dist[p + 1] >= clearance);
+        if (j > 0) f = f || (!seen[p - L.nx] && dist[p - L.nx] >= clearance);
+        if (j + 1 < L.ny) f = f || (!seen[p + L.nx] && dist[p + L.nx] >= clearance);
+        if (k > 0) f = f || (!seen[p - nxy] && dist[p - nxy] >= clearance);
+        if (k + 1 < L.nz) f = f || (!seen[p + nxy] && dist[p + nxy] >= clearance);
+        return f;
+    }
+};
+// a root of the converged labels
+struct RootPred {
+    const int* label;
+    __device__ bool operator()(int r) const { return label[r] == r; }
+};
+
+template <class Pred>
+__global__ void __launch_bounds__(kBlock) cover_count_kernel(Pred pred, int n, int* __restrict__ bcount) {
+    const int base = blockIdx.x * kChunk;
+    int cnt = 0;
+    for (int it = 0; it < kItems; ++it) {
+        const int p = base + it * kBlock + threadIdx.x;
+        cnt += __syncthreads_count(p < n && pred(p));
+    }
+    if (threadIdx.x == 0) bcount[blockIdx.x] = cnt;
+}
+
+// in place: b[0..nb) = exclusive scan of the counts, b[nb] = their sum.  One workgroup.
+__global__ void __launch_bounds__(kBlock) cover_offsets_kernel(int* __restrict__ b, int nb) {
+    __shared__ int sh[kBlock / kWave];
+    int carry = 0;
+    for (int base = 0; base < nb; base += kBlock) {
+        const int idx = base + threadIdx.x;
+        const int v = idx < nb ? b[idx] : 0;
+        int total;
+        const int incl = block_incl_scan<kBlock, int>(v, sh, &total);
+        if (idx < nb) b[idx] = carry + incl - v;
+        carry += total;
+    }
+    if (threadIdx.x == 0) b[nb] = carry;
+}
+
+// list[off ..] = the elements of this chunk that pass, ascending; rank[p] = the position of p in the list, -1 if it fails
+template <class Pred>
+__global__ void __launch_bounds__(kBlock) cover_write_kernel(Pred pred, int n, const int* __restrict__ boff, int* __restrict__ list,
+                                                             int* __restrict__ rank) {
+    __shared__ int sh[kBlock / kWave];
+    const int base = blockIdx.x * kChunk;
+    int off = boff[blockIdx.x];
+    for (int it = 0; it < kItems; ++it) {
+        const int p = base + it * kBlock + threadIdx.x;
+        const int f = (p < n && pred(p)) ? 1 : 0;
+        int total;
+        const int incl = block_incl_scan<kBlock, int>(f, sh, &total);
+        if (p < n) {
+            const int r = off + incl - 1;
+            if (f) list[r] = p;
+            rank[p] = f ? r : -1;
+        }
+        off += total;
+    }
+}
+
+// ---- labels ---------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ int ld_label(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ void st_label(int* p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+__global__ void __launch_bounds__(kBlock) cover_iota_kernel(int* __restrict__ label, int m) {
+    for (int r = blockIdx.x * blockDim.x + threadIdx.x; r < m; r += gridDim.x * blockDim.x) label[r] = r;
+}
+
+// One round: label[r] = the smallest label among r and its 8 / 26 neighbours, followed down its chain of labels (a label is the
+// rank of a member of the same component and never exceeds the own rank, so the chain falls and ends).
+__global__ void __launch_bounds__(kBlock) cover_label_kernel(CovLat L, const int* __restrict__ list, const int* __restrict__ rank, int m, int* label,
+                                                             int* changed) {
+    const int nxy = L.nx * L.ny;
+    for (int r = blockIdx.x * blockDim.x + threadIdx.x; r < m; r += gridDim.x * blockDim.x) {
+        const int p = list[r];
+        const int i = p % L.nx, j = (p / L.nx) % L.ny, k = p / nxy;
+        const int old = ld_label(label + r);
+        int best = old;
+        for (int dz = -1; dz <= 1; ++dz) {
+            if (k + dz < 0 || k + dz >= L.nz) continue;
+            for (int dy = -1; dy <= 1; ++dy) {
+                if (j + dy < 0 || j + dy >= L.ny) continue;
+                for (int dx = -1; dx <= 1; ++dx) {
+                    if (i + dx < 0 || i + dx >= L.nx) continue;
+                    const int nr = rank[p + (dz * L.ny + dy) * L.nx + dx];
+                    if (nr >= 0) best = min(best, ld_label(label + nr));
+                }
+            }
+        }
+        for (;;) {
+            const int t = ld_label(label + best);
+            if (t >= best) break;
+            best = t;
+        }
+        if (best < old) { st_label(label + r, best); *changed = 1; }
+    }
+}
+
+// ---- the table ------------------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(kBlock) cover_tab_init_kernel(unsigned long long* __restrict__ tab, int* __restrict__ box, int nc) {
+    for (int c = blockIdx.x * blockDim.x + threadIdx.x; c < nc; c += gridDim.x * blockDim.x) {
+        unsigned long long* t = tab + (size_t)c * kTabWords;
+        t[0] = t[1] = t[2] = t[3] = 0ull;
+        t[4] = t[5] = ~0ull;
+        t[6] = t[7] = 0ull;
+        for (int a = 0; a < 3; ++a) { box[c * 6 + a] = INT_MAX; box[c * 6 + 3 + a] = -1; }
+    }
+}
+
+// count, integer sums and box of each component; the points' labels as lattice indices.  The list ascends and components are
+// compact, so the 64 points of a wavefront mostly share one component: such a wavefront reduces its integers through lane
+// shuffles and sends one atomic per word instead of 64 to the same address (integers: the order changes nothing).
+__global__ void __launch_bounds__(kBlock) cover_tab_sum_kernel(CovLat L, const int* __restrict__ list, const int* __restrict__ label,
+                                                               const int* __restrict__ cidx, int m, unsigned long long* tab, int* box,
+                                                               int* __restrict__ plabel) {
+    const int nxy = L.nx * L.ny;
+    for (int r0 = blockIdx.x * blockDim.x; r0 < m; r0 += gridDim.x * blockDim.x) {
+        const int r = r0 + threadIdx.x;
+        const bool ok = r < m;
+        int c = -1, ijk[3] = {0, 0, 0};
+        if (ok) {
+            const int p = list[r], root = label[r];
+            c = cidx[root];
+            ijk[0] = p % L.nx; ijk[1] = (p / L.nx) % L.ny; ijk[2] = p / nxy;
+            plabel[r] = list[root];
+        }
+        const int c0 = __shfl(c, 0, kWave);                    // (lane 0 holds the wavefront's smallest r)
+        if (c0 < 0) continue;                                  // the whole wavefront lies past the list
+        if (__all(!ok || c == c0)) {
+            const unsigned long long cnt = wave_reduce(ok ? 1ull : 0ull, OpAdd());
+            unsigned long long sm[3];
+            int lo[3], hi[3];
+#pragma unroll
+            for (int a = 0; a < 3; ++a) {
+                sm[a] = wave_reduce(ok ? (unsigned long long)ijk[a] : 0ull, OpAdd());
+                lo[a] = wave_reduce(ok ? ijk[a] : INT_MAX, OpMin());
+                hi[a] = wave_reduce(ok ? ijk[a] : -1, OpMax());
+            }
+            if ((threadIdx.x & (kWave - 1)) == 0) {
+                unsigned long long* t = tab + (size_t)c0 * kTabWords;
+                atomicAdd(&t[0], cnt);
+#pragma unroll
+                for (int a = 0; a < 3; ++a) {
+                    atomicAdd(&t[1 + a], sm[a]);
+                    atomicMin(&box[c0 * 6 + a], lo[a]);
+                    atomicMax(&box[c0 * 6 + 3 + a], hi[a]);
+                }
+            }
+        } else if (ok) {
+            unsigned long long* t = tab + (size_t)c * kTabWords;
+            atomicAdd(&t[0], 1ull);
+#pragma unroll
+            for (int a = 0; a < 3; ++a) {
+                atomicAdd(&t[1 + a], (unsigned long long)ijk[a]);
+                atomicMin(&box[c * 6 + a], ijk[a]);
+                atomicMax(&box[c * 6 + 3 + a], ijk[a]);
+            }
+        }
+    }
+}
+
+// the squared distance of point r to its component's centroid, in double: (i - si / n)^2 + (j - sj / n)^2 (+ (k - sk / n)^2)
+__device__ __forceinline__ double cover_d2(const CovLat& L, int p, const unsigned long long* t) {
+    const int nxy = L.nx * L.ny;
+    const double cnt = (double)t[0];
+    const double di = (double)(p % L.nx) - (double)t[1] / cnt, dj = (double)((p / L.nx) % L.ny) - (double)t[2] / cnt;
+    double d2 = di * di + dj * dj;
+    if (L.dim == 3) {
+        const double dk = (double)(p / nxy) - (double)t[3] / cnt;
+        d2 = d2 + dk * dk;
+    }
+    return d2;
+}
+
+// STAGE 0: t[4] = the smallest distance's bits (non-negative doubles order as their bits), one atomic per wavefront where its
+// points share a component; STAGE 1: t[5] = the smallest rank among the points at that distance
+template <int STAGE>
+__global__ void __launch_bounds__(kBlock) cover_tab_rep_kernel(CovLat L, const int* __restrict__ list, const int* __restrict__ label,
+                                                               const int* __restrict__ cidx, int m, unsigned long long* tab) {
+    for (int r0 = blockIdx.x * blockDim.x; r0 < m; r0 += gridDim.x * blockDim.x) {
+        const int r = r0 + threadIdx.x;
+        const bool ok = r < m;
+        const int c = ok ? cidx[label[r]] : -1;
+        unsigned long long b = ~0ull;
+        if (ok) b = (unsigned long long)__double_as_longlong(cover_d2(L, list[r], tab + (size_t)c * kTabWords));
+        if (STAGE == 1) {
+            if (ok && b == tab[(size_t)c * kTabWords + 4]) atomicMin(&tab[(size_t)c * kTabWords + 5], (unsigned long long)r);
+            continue;
+        }
+        const int c0 = __shfl(c, 0, kWave);
+        if (c0 < 0) continue;
+        if (__all(!ok || c == c0)) {
+            const unsigned long long bm = wave_reduce(b, OpMin());
+            if ((threadIdx.x & (kWave - 1)) == 0) atomicMin(&tab[(size_t)c0 * kTabWords + 4], bm);
+        } else if (ok) {
+            atomicMin(&tab[(size_t)c * kTabWords + 4], b);
+        }
+    }
+}
+
+// ranks to lattice indices: t[5] = the representative, t[6] = the label
+__global__ void __launch_bounds__(kBlock) cover_tab_final_kernel(const int* __restrict__ list, const int* __restrict__ roots, int nc,
+                                                                 unsigned long long* __restrict__ tab) {
+    for (int c = blockIdx.x * blockDim.x + threadIdx.x; c < nc; c += gridDim.x * blockDim.x) {
+        unsigned long long* t = tab + (size_t)c * kTabWords;
+        t[5] = (unsigned long long)list[(int)t[5]];
+        t[6] = (unsigned long long)list[roots[c]];
+    }
+}
+
+// ---- the restricted field -----------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(kBlock) cover_restrict_kernel(const unsigned char* __restrict__ seen, const float* __restrict__ dist,
+                                                                const int* __restrict__ site, int n, float unseen, float* __restrict__ dist_out,
+                                                                int* __restrict__ site_out) {
+    for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < n; p += gridDim.x * blockDim.x) {
+        dist_out[p] = seen[p] ? dist[p] : unseen;
+        site_out[p] = site[p];
+    }
+}
+
+inline CovLat lat_of(const Coverage& c) {
+    return CovLat{c.dim, c.n[0], c.n[1], c.n[2], c.origin[0], c.origin[1], c.origin[2], c.step};
+}
+
+double ms_since(std::chrono::steady_clock::time_point t0) {
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
+}  // namespace
+
+Coverage::Coverage() {
+    (void)hipGetDevice(&device);
+    if (hipStreamCreateWithFlags(&own, hipStreamNonBlocking) != hipSuccess) own = nullptr;
+}
+
+Coverage::~Coverage() { (void)bind(-1); }
+
+int Coverage::bind(int dev) {
+    if (dev == device && dev >= 0) return GPIS_OK;
+    {
+        DeviceScope ds(device);
+        if (own) (void)hipStreamSynchronize(own);
+        for (void* p : {(void*)d_seen, (void*)d_rank, (void*)d_bcount, (void*)d_list, (void*)d_label, (void*)d_plabel, (void*)d_cidx,
+                        (void*)d_roots, (void*)d_tab, (void*)d_box, (void*)d_sector, (void*)d_depth, (void*)d_word})
+            (void)hipFree(p);
+        if (h_word) (void)hipHostFree(h_word);
+        if (h_tab) (void)hipHostFree(h_tab);
+        if (own) (void)hipStreamDestroy(own);
+    }
+    d_seen = nullptr; d_rank = d_bcount = d_list = d_label = d_plabel = d_cidx = d_roots = d_box = d_word = nullptr; d_tab = nullptr;
+    d_sector = nullptr; d_depth = nullptr; h_word = nullptr; h_tab = nullptr; own = nullptr;
+    cap_n = cap_rank = cap_blocks = cap_m = cap_c = cap_beams = cap_pix = cap_htab = 0;
+    clear_frontiers();
+    has_lattice = false; dim = 0; ngrid = 0; frames = 0;
+    device = dev;
+    if (dev < 0) return GPIS_OK;
+    DeviceScope ds(dev);
+    GPIS_HIP(hipStreamCreateWithFlags(&own, hipStreamNonBlocking));
+    return GPIS_OK;
+}
+
+bool Coverage::same_lattice(const DistanceField& df) const {
+    if (!has_lattice || !df.valid || df.dim != dim || df.step != step || df.device != device) return false;
+    for (int a = 0; a < dim; ++a)
+        if (df.n[a] != n[a] || df.origin[a] != origin[a]) return false;
+    return true;
+}
+
+int Coverage::reset(const DistanceField& df) {
+    if (!df.valid) return GPIS_ERR_STATE;
+    if (int rc = bind(df.device)) return rc;
+    clear_frontiers();
+    has_lattice = false;
+    if (!d_word) GPIS_HIP(hipMalloc((void**)&d_word, sizeof(int) * 4));
+    if (!h_word) GPIS_HIP(hipHostMalloc((void**)&h_word, sizeof(int) * 4));
+    if (int rc = grow(d_seen, cap_n, (size_t)df.ngrid)) return rc;
+    GPIS_HIP(hipMemsetAsync(d_seen, 0, (size_t)df.ngrid, own));
+    GPIS_HIP(hipStreamSynchronize(own));
+    dim = df.dim; ngrid = df.ngrid; step = df.step;
+    for (int a = 0; a < 3; ++a) { n[a] = a < dim ? df.n[a] : 1; origin[a] = a < dim ? df.origin[a] : 0.f; }
+    frames = 0;
+    has_lattice = true;
+    return GPIS_OK;
+}
+
+int Coverage::set(const unsigned char* seen) {
+    if (!has_lattice) return GPIS_ERR_STATE;
+    clear_frontiers();
+    GPIS_HIP(hipMemcpyAsync(d_seen, seen, (size_t)ngrid, hipMemcpyHostToDevice, own));
+    hipLaunchKernelGGL(cover_binarise_kernel, dim3(grid_for(ngrid)), dim3(kBlock), 0, own, d_seen, (int)ngrid);
+    GPIS_HIP(hipGetLastError());
+    GPIS_HIP(hipStreamSynchronize(own));
+    return GPIS_OK;
+}
+
+int Coverage::get(unsigned char* seen) {
+    if (!has_lattice) return GPIS_ERR_STATE;
+    GPIS_HIP(hipMemcpyAsync(seen, d_seen, (size_t)ngrid, hipMemcpyDeviceToHost, own));
+    GPIS_HIP(hipStreamSynchronize(own));
+    return GPIS_OK;
+}
+
+int Coverage::integrate(const SensorFrame& f, const float* in, const float* pose, const CoverOpts& o, hipStream_t s) {
+    if (!has_lattice) return GPIS_ERR_STATE;
+    if (f.geo.dim != dim) return GPIS_ERR_ARG;
+    const auto t0 = std::chrono::steady_clock::now();
+    clear_frontiers();
+    const CovLat L = lat_of(*this);
+    CovPose P;
+    for (int k = 0; k < 12; ++k) P.v[k] = k < (dim == 3 ? 12 : 6) ? pose[k] : 0.f;
+    if (dim == 3) {
+        if (int rc = grow(d_depth, cap_pix, (size_t)f.n)) return rc;
+        GPIS_HIP(hipMemcpyAsync(d_depth, in, sizeof(float) * (size_t)f.n, hipMemcpyHostToDevice, s));
+        hipLaunchKernelGGL(cover_depth_kernel, dim3(grid_for(ngrid)), dim3(kBlock), 0, s, L, (int)ngrid, P, (double)f.geo.fx, (double)f.geo.fy,
+                           (double)f.geo.cx, (double)f.geo.cy, f.geo.width, f.geo.height, d_depth, (double)o.back_off, d_seen);
+        GPIS_HIP(hipGetLastError());
+        GPIS_HIP(hipStreamSynchronize(s));
+    } else {
+        SectorTable t;
+        sector_table(f.cs.data(), in, f.n, o.back_off, o.max_gap, &t);
+        const long long m = t.size();
+        if (m >= 2) {                                           // (fewer than two valid beams: nothing is seen)
+            if (int rc = grow(d_sector, cap_beams, (size_t)(2 * m))) return rc;
+            GPIS_HIP(hipMemcpyAsync(d_sector, t.q.data(), sizeof(double) * (size_t)m, hipMemcpyHostToDevice, s));
+            GPIS_HIP(hipMemcpyAsync(d_sector + m, t.lim_eff.data(), sizeof(double) * (size_t)m, hipMemcpyHostToDevice, s));
+            hipLaunchKernelGGL(cover_scan_kernel, dim3(grid_for(ngrid)), dim3(kBlock), 0, s, L, (int)ngrid, P, (double)f.geo.off[0],
+                               (double)f.geo.off[1], d_sector, d_sector + m, (int)m, d_seen);
+            GPIS_HIP(hipGetLastError());
+            GPIS_HIP(hipStreamSynchronize(s));                  // (the table lives until here)
+        }
+    }
+    ++frames;
+    integrate_ms = ms_since(t0);
+    return GPIS_OK;
+}
+
+namespace {
+
+// count, scan, write of the elements of [0, n) that pass pred: *total of them, ascending in d_list (grow_lists(total) makes room
+// once the count is known), their positions in d_rank; synchronises `s` after the scan
+template <class Pred, class Grow>
+int compact_run(Pred pred, int n, int* d_bcount, int* h_word, int* total, int*& d_list, int*& d_rank, hipStream_t s, const Grow& grow_lists) {
+    const int nb = (n + kChunk - 1) / kChunk;
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(cover_count_kernel<Pred>), dim3(nb), dim3(kBlock), 0, s, pred, n, d_bcount);
+    GPIS_HIP(hipGetLastError());
+    hipLaunchKernelGGL(cover_offsets_kernel, dim3(1), dim3(kBlock), 0, s, d_bcount, nb);
+    GPIS_HIP(hipGetLastError());
+    GPIS_HIP(hipMemcpyAsync(h_word, d_bcount + nb, sizeof(int), hipMemcpyDeviceToHost, s));
+    GPIS_HIP(hipStreamSynchronize(s));
+    *total = h_word[0];
+    if (int rc = grow_lists(*total)) return rc;
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(cover_write_kernel<Pred>), dim3(nb), dim3(kBlock), 0, s, pred, n, d_bcount, d_list, d_rank);
+    GPIS_HIP(hipGetLastError());
+    return GPIS_OK;
+}
+
+}  // namespace
+
+int Coverage::frontiers(const DistanceField& df, const CoverOpts& o, hipStream_t s) {
+    if (!has_lattice || !df.valid) return GPIS_ERR_STATE;
+    if (!same_lattice(df)) return GPIS_ERR_ARG;
+    if (int rc = cover_check_opts(o)) return rc;
+    const auto t0 = std::chrono::steady_clock::now();
+    clear_frontiers();
+    const CovLat L = lat_of(*this);
+    const int np = (int)ngrid, nb = (np + kChunk - 1) / kChunk;
+    if (int rc = grow(d_rank, cap_rank, (size_t)np)) return rc;
+    if (int rc = grow(d_bcount, cap_blocks, (size_t)nb + 1)) return rc;
+
+    // the per-point buffers grow together, once the count is known (the lists are at least one element long)
+    auto grow_lists = [&](int m) -> int {
+        const size_t need = (size_t)std::max(1, m);
+        if (need <= cap_m) return GPIS_OK;
+        for (void* p : {(void*)d_list, (void*)d_label, (void*)d_plabel, (void*)d_cidx, (void*)d_roots}) (void)hipFree(p);
+        d_list = d_label = d_plabel = d_cidx = d_roots = nullptr; cap_m = 0;
+        for (int** p : {&d_list, &d_label, &d_plabel, &d_cidx, &d_roots}) GPIS_HIP(hipMalloc((void**)p, sizeof(int) * need));
+        cap_m = need;
+        return GPIS_OK;
+    };
+    int m = 0;
+    if (int rc = compact_run(FrontierPred{L, d_seen, df.d_dist, o.clearance}, np, d_bcount, h_word, &m, d_list, d_rank, s, grow_lists))
+        return rc;
+
+    long long done = 0;
+    int nc = 0;
+    if (m > 0) {
+        hipLaunchKernelGGL(cover_iota_kernel, dim3(grid_for(m)), dim3(kBlock), 0, s, d_label, m);
+        GPIS_HIP(hipGetLastError());
+        const long long cap = o.max_rounds > 0 ? (long long)o.max_rounds : (long long)m + 1;
+        const int every = std::max(1, std::min(check_every, (int)kMaxBatch));
+        long long round = 0;
+        bool conv = false;
+        while (!conv && round < cap) {
+            const int nbatch = (int)std::min((long long)every, cap - round);
+            for (int b = 0; b < nbatch; ++b) {
+                if (b == nbatch - 1) GPIS_HIP(hipMemsetAsync(d_word, 0, sizeof(int), s));   // (the batch's last round decides)
+                hipLaunchKernelGGL(cover_label_kernel, dim3(grid_for(m)), dim3(kBlock), 0, s, L, d_list, d_rank, m, d_label, d_word);
+                GPIS_HIP(hipGetLastError());
+            }
+            GPIS_HIP(hipMemcpyAsync(h_word, d_word, sizeof(int), hipMemcpyDeviceToHost, s));
+            GPIS_HIP(hipStreamSynchronize(s));
+            round += nbatch;
+            conv = h_word[0] == 0;
+        }
+        if (!conv) return GPIS_ERR_LIMIT;
+        done = round;
+
+        // the roots, ascending: component c = the c-th smallest label
+        const int nbm = (m + kChunk - 1) / kChunk;
+        if (int rc = grow(d_bcount, cap_blocks, (size_t)std::max(nb, nbm) + 1)) return rc;
+        auto no_grow = [&](int) -> int { return GPIS_OK; };       // (at most m roots: d_roots holds them)
+        if (int rc = compact_run(RootPred{d_label}, m, d_bcount, h_word, &nc, d_roots, d_cidx, s, no_grow)) return rc;
+        if ((size_t)nc > cap_c) {
+            (void)hipFree(d_tab); (void)hipFree(d_box); d_tab = nullptr; d_box = nullptr; cap_c = 0;
+            GPIS_HIP(hipMalloc((void**)&d_tab, sizeof(unsigned long long) * kTabWords * (size_t)nc));
+            GPIS_HIP(hipMalloc((void**)&d_box, sizeof(int) * 6 * (size_t)nc));
+            cap_c = (size_t)nc;
+        }
+        const size_t hneed = (size_t)nc * (kTabWords + 3);
+        if (hneed > cap_htab) {
+            if (h_tab) (void)hipHostFree(h_tab);
+            h_tab = nullptr; cap_htab = 0;
+            GPIS_HIP(hipHostMalloc((void**)&h_tab, sizeof(unsigned long long) * hneed));
+            cap_htab = hneed;
+        }
+        hipLaunchKernelGGL(cover_tab_init_kernel, dim3(grid_for(nc)), dim3(kBlock), 0, s, d_tab, d_box, nc);
+        GPIS_HIP(hipGetLastError());
+        hipLaunchKernelGGL(cover_tab_sum_kernel, dim3(grid_for(m)), dim3(kBlock), 0, s, L, d_list, d_label, d_cidx, m, d_tab, d_box, d_plabel);
+        GPIS_HIP(hipGetLastError());
+        hipLaunchKernelGGL(cover_tab_rep_kernel<0>, dim3(grid_for(m)), dim3(kBlock), 0, s, L, d_list, d_label, d_cidx, m, d_tab);
+        GPIS_HIP(hipGetLastError());
+        hipLaunchKernelGGL(cover_tab_rep_kernel<1>, dim3(grid_for(m)), dim3(kBlock), 0, s, L, d_list, d_label, d_cidx, m, d_tab);
+        GPIS_HIP(hipGetLastError());
+        hipLaunchKernelGGL(cover_tab_final_kernel, dim3(grid_for(nc)), dim3(kBlock), 0, s, d_list, d_roots, nc, d_tab);
+        GPIS_HIP(hipGetLastError());
+        int* h_box = (int*)(h_tab + (size_t)nc * kTabWords);
+        GPIS_HIP(hipMemcpyAsync(h_tab, d_tab, sizeof(unsigned long long) * kTabWords * (size_t)nc, hipMemcpyDeviceToHost, s));
+        GPIS_HIP(hipMemcpyAsync(h_box, d_box, sizeof(int) * 6 * (size_t)nc, hipMemcpyDeviceToHost, s));
+        GPIS_HIP(hipStreamSynchronize(s));
+        for (int c = 0; c < nc; ++c) {
+            const unsigned long long* t = h_tab + (size_t)c * kTabWords;
+            if ((long long)t[0] < (long long)o.min_size) continue;
+            label.push_back((int)t[6]); count.push_back((int)t[0]); rep.push_back((int)t[5]);
+            for (int a = 0; a < 3; ++a) sums.push_back((long long)t[1 + a]);
+            for (int a = 0; a < 6; ++a) box.push_back(h_box[c * 6 + a]);
+        }
+    } else {
+        GPIS_HIP(hipStreamSynchronize(s));
+    }
+    npoints = m; ncomponents = nc; rounds = done;
+    frontiers_ms = ms_since(t0);
+    frontiers_valid = true;
+    return GPIS_OK;
+}
+
+int Coverage::restrict_field(const DistanceField& in, DistanceField& out, float unseen_dist, hipStream_t s) {
+    if (!has_lattice || !in.valid) return GPIS_ERR_STATE;
+    if (&in == &out || !std::isfinite(unseen_dist) || !same_lattice(in)) return GPIS_ERR_ARG;
+    if (int rc = out.bind(in.device)) return rc;
+    out.clear_result();
+    if (int rc = out.ensure(ngrid)) return rc;
+    hipLaunchKernelGGL(cover_restrict_kernel, dim3(grid_for(ngrid)), dim3(kBlock), 0, s, d_seen, in.d_dist, in.d_site(), (int)ngrid, unseen_dist,
+                       out.d_dist, out.d_feat[0]);
+    GPIS_HIP(hipGetLastError());
+    GPIS_HIP(hipStreamSynchronize(s));
+    out.dim = dim; out.ngrid = ngrid; out.site_buf = 0; out.step = step;
+    for (int a = 0; a < 3; ++a) { out.n[a] = n[a]; out.origin[a] = origin[a]; }
+    out.valid = true;
+    return GPIS_OK;
+}
+
+}  // namespace gpis

@@ -12,6 +12,7 @@ namespace gpis {
 
 class MapQuery;
 class OnGPISStore;
+struct Coverage;
 
 struct DistanceField {
     static constexpr long long kMaxLattice = 1ll << 28;   // lattice points per field
@@ -56,6 +57,7 @@ struct DistanceField {
     DfLattice lattice() const { return DfLattice{dim, n[0], n[1], n[2], origin[0], origin[1], origin[2], step}; }
 
 private:
+    friend struct Coverage;      // (cover.h: the restricted copy of a field fills another field's buffers)
     int ensure(long long n);
 };
 

@@ -897,6 +897,76 @@ int   gpis_mppi_device(void* mppi, void** ptrs, int n);
 /* out[0..n): 1 after init, dim, K, T, tick, steps, 1 after the first step, ms of host wall time of the last step */
 int   gpis_mppi_info(void* mppi, double* out, int n);
 
+/* ---- coverage: which lattice points of a field a sensor has seen as free space, and its frontiers ----------
+ * The field knows surfaces only; unknown space is "outside" in it and therefore free to the planner.  A coverage holder keeps one
+ * byte per lattice point of a field: 1 once some integrated depth frame or laser scan has looked through that point.  On it:
+ * the frontiers (seen, traversable points that border unseen, traversable ones; clustered and summarised) and a copy of the
+ * field restricted to seen space, which every consumer of a field takes unchanged.  tests/cover_ref.py states each rule below in
+ * numpy; every result is an integer or a double computed in one fixed order, and the device's bits are the reference's.
+ * Lattice point i of an axis: origin + (float)i * step in float32.  Local point of a lattice point x under a float32 pose
+ * [t, R column-major] (the tracker's layouts): l = R^T (x - t), l[c] = R[dim c] d[0] + R[dim c + 1] d[1] (+ R[dim c + 2] d[2]),
+ * d = (double)x - (double)t, left to right in double without FMA.
+ * 3-D (gpis3_cover_depth): seen iff l.z > 0, the nearest pixel (floor(fx l.x / l.z + cx + 0.5), floor(fy l.y / l.z + cy + 0.5))
+ * lies inside the image, its depth d is valid (0.4 < (double)d < 4, the tracker's window) and l.z < d - back_off.  Every pixel
+ * counts.  2-D (gpis2_cover_scan): the host keeps the valid beams (0.2 < (double)r < 30) with their host-double directions
+ * (c, s), sorts them stably by the diamond pseudo-angle q = 1 - c / (|c| + |s|) for s >= 0, else 3 + c / (|c| + |s|), and keeps
+ * per sector k -> k + 1 (the last wraps to the first) lim = min(r_k, r_k+1) - back_off and narrow = (dq < 2) and (c_k c_k+1 +
+ * s_k s_k+1 >= cos(max_gap)).  The device takes l = R^T (x - t) - off2 and its sector, the last k with q_k <= q(l) (none: the
+ * wrapping one); seen iff that sector is narrow, lim > 0 and l.l < lim^2.  Fewer than two valid beams: nothing is seen;
+ * l.l == 0: seen when two or more valid beams exist.  A beam without a return leaves a wide sector, hence unseen space.
+ * One thread per lattice point reads its own byte and writes its own byte: no atomics, the same bits on every run.
+ * Frontiers (gpis_cover_frontiers): p is a frontier point iff seen[p] and dist[p] >= clearance and some axis neighbour q inside
+ * the lattice has !seen[q] and dist[q] >= clearance (float32 compares: NaN fails).  Their lattice indices come out ascending;
+ * connected components under full connectivity (8 / 26 neighbours), labelled by their smallest lattice index; per component of
+ * at least min_size points, ordered by label: the point count, the integer sums of (i, j, k), the integer bounding box and the
+ * representative -- the member nearest the centroid, squared distance (i - sum_i / count)^2 + (j - ..)^2 (+ (k - ..)^2) in double
+ * left to right, ties to the smallest index.  Smaller components keep their labels and are dropped from the table.
+ * gpis_cover_restrict: df_out gets df_in's lattice and sites, dist_out = seen ? dist_in : unseen_dist; it holds no f grid.
+ * The holder owns its buffers (1 B per lattice point; frontiers: 4 B per lattice point and 20 B per frontier point; grow-only,
+ * reused) and moves to the field's device; hip_stream NULL: the holder's own stream; every call returns with its work finished.
+ * map: may be NULL; it is read only for what the caller leaves NULL (cam / off2), as for locate.
+ * Errors: a NULL handle, field, depth, thetas, ranges or pose; cam / off2 NULL without a map; a bad camera; n < 1; a non-finite
+ * pose entry or beam angle; back_off negative or non-finite; max_gap outside (0, 90 degrees); clearance <= back_off (every surface
+ * would raise a frontier) or non-finite; min_size < 1; max_rounds < 0; a frame of another dim than the lattice; a field of
+ * another lattice than the holder's; df_out == df_in; a non-finite unseen_dist -> GPIS_ERR_ARG.  A field without a result, a
+ * holder that was never reset, counts / get_frontiers without frontiers -> GPIS_ERR_STATE.  More than 2^26 pixels / beams, or
+ * more than max_rounds labelling rounds (the holder then holds no frontiers) -> GPIS_ERR_LIMIT. */
+typedef struct gpis_cover_opts {
+    float back_off;             /* free space ends this far in front of a measured surface */
+    float max_gap;              /* 2-D: the widest angle (radians) between neighbouring valid beams that still closes a sector */
+    float clearance;            /* traversable: dist >= clearance */
+    int min_size;               /* clusters below it are dropped from the table */
+    int max_rounds;             /* labelling rounds; 0: no limit */
+} gpis_cover_opts;
+/* defaults: back_off step, max_gap 2 degrees, clearance 3 step, min_size 8, max_rounds 0.  Needs no device. */
+int   gpis_cover_default_opts(int dim, float step, gpis_cover_opts* opts);
+void* gpis_cover_create(void);                              /* on the current device; NULL without one */
+void  gpis_cover_destroy(void* cover);
+/* the lattice of a field holding a result; seen = 0 everywhere */
+int   gpis_cover_reset(void* cover, void* df);
+/* the byte mask [prod(n)], x fastest (set: non-zero = seen; n must be the lattice's point count; drops the frontiers) */
+int   gpis_cover_set(void* cover, const unsigned char* seen, long long n);
+int   gpis_cover_get(void* cover, unsigned char* seen, long long n);
+/* device pointer of the mask, valid until gpis_cover_destroy or a reset to a larger lattice (NULL before reset) */
+int   gpis_cover_device(void* cover, const unsigned char** d_seen);
+/* depth [W*H] column-major as update(); cam NULL: the map's camera; opts NULL: the defaults (back_off is read) */
+int   gpis3_cover_depth(void* map, void* cover, const gpis_cam* cam, const float* depth, const float* pose12,
+                        const gpis_cover_opts* opts, void* hip_stream);
+/* thetas, ranges [n] as update(); off2 NULL: the map's sensor offset (back_off and max_gap are read) */
+int   gpis2_cover_scan(void* map, void* cover, const float* thetas, const float* ranges, int n, const float* pose6,
+                       const float* off2, const gpis_cover_opts* opts, void* hip_stream);
+int   gpis_cover_frontiers(void* cover, void* df, const gpis_cover_opts* opts, void* hip_stream);
+/* frontier points, components of any size, clusters in the table */
+int   gpis_cover_counts(void* cover, long long* npoints, long long* ncomponents, long long* nclusters);
+/* host copies of the last frontiers (any pointer may be NULL): per cluster label [c], count [c], sums [c][3], box [c][6] = min
+ * (i, j, k), max (i, j, k), rep [c] (lattice index); per frontier point its lattice index points [m] and label point_label [m] */
+int   gpis_cover_get_frontiers(void* cover, int* label, int* count, long long* sums, int* box, int* rep, int* points,
+                               int* point_label);
+int   gpis_cover_restrict(void* cover, void* df_in, void* df_out, float unseen_dist, void* hip_stream);
+/* out[0..n): 1 after reset, dim, n[0], n[1], n[2], step, frames integrated since reset, 1 if frontiers are held, frontier points,
+ * components, clusters, labelling rounds, ms of host wall time of the last integrate, of the last frontiers call */
+int   gpis_cover_info(void* cover, double* out, int n);
+
 #ifdef __cplusplus
 }
 #endif
