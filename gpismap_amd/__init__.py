@@ -70,6 +70,11 @@ class gpis_cover_opts(C.Structure):
                 ("max_rounds", C.c_int)]
 
 
+class gpis_view_opts(C.Structure):
+    _fields_ = [("march", gpis_render_field_opts), ("back_off", C.c_float), ("max_gap", C.c_float), ("miss", C.c_float),
+                ("min_dist", C.c_float)]
+
+
 class gpis_traj_opts(C.Structure):
     _fields_ = [("clearance", C.c_float), ("margin", C.c_float), ("w_smooth", C.c_float), ("w_obs", C.c_float),
                 ("rate", C.c_float), ("max_move", C.c_float), ("tol", C.c_float), ("iters", C.c_int), ("sub", C.c_int)]
@@ -323,6 +328,17 @@ def lib():
         L.gpis_cover_get_frontiers.argtypes = [vp, ip, ip, ll, ip, ip, ip, ip]
         L.gpis_cover_restrict.argtypes = [vp, vp, vp, C.c_float, vp]
         L.gpis_cover_info.argtypes = [vp, dp, C.c_int]
+    if hasattr(L, "gpis_view_create"):
+        vo = C.POINTER(gpis_view_opts)
+        L.gpis_view_default_opts.argtypes = [C.c_int, C.c_float, vo]
+        L.gpis_view_create.restype = vp
+        L.gpis_view_create.argtypes = []
+        L.gpis_view_destroy.argtypes = [vp]
+        L.gpis3_view_gain_depth.argtypes = [vp, vp, vp, vp, C.POINTER(gpis_cam), fp, C.c_int, vo, vp]
+        L.gpis2_view_gain_scan.argtypes = [vp, vp, vp, vp, fp, C.c_int, fp, fp, C.c_int, vo, vp]
+        L.gpis_view_get.argtypes = [vp, C.POINTER(C.c_longlong), ip, C.c_int]
+        L.gpis_view_get_predicted.argtypes = [vp, C.c_int, fp, C.c_longlong]
+        L.gpis_view_info.argtypes = [vp, dp, C.c_int]
     _lib = L
     return L
 
@@ -688,6 +704,11 @@ class GPisMap3:
         """Coverage.integrate_depth with this map's camera (cam6 None)."""
         return cover._integrate_depth(self.h, self._wh, depth, pose, cam6, stream, opts)
 
+    def view_gain_depth_field(self, field, cover, poses, cam6=None, scorer=None, stream=None, **opts):
+        """DistanceField.view_gain_depth with this map's camera when cam6 is None (gpis3_view_gain_depth); nothing else of the
+        map is read."""
+        return field._view_gain_depth(self.h, cover, cam6, poses, scorer, stream, opts)
+
     def render_depth_field(self, field, pose, cam6=None, renderer=None, **opts):
         """render_depth from a DistanceField instead of the map (gpis3_render_depth_field): sphere tracing through the field's
         sampler, one fused kernel.  cam6 None = this map's camera; nothing else of the map is read.  Returns (depth [W*H],
@@ -839,6 +860,11 @@ class GPisMap:
     def cover_scan(self, cover, thetas, ranges, pose6, off2=None, stream=None, **opts):
         """Coverage.integrate_scan with this map's sensor offset (off2 None)."""
         return cover._integrate_scan(self.h, thetas, ranges, pose6, off2, stream, opts)
+
+    def view_gain_scan_field(self, field, cover, thetas, poses, off2=None, scorer=None, stream=None, **opts):
+        """DistanceField.view_gain_scan with this map's sensor offset when off2 is None (gpis2_view_gain_scan); nothing else of
+        the map is read."""
+        return field._view_gain_scan(self.h, cover, thetas, poses, off2, scorer, stream, opts)
 
     def render_scan_field(self, field, thetas, pose6, renderer=None, **opts):
         """render_scan from a DistanceField instead of the map (gpis2_render_scan_field), with this map's sensor offset;
@@ -1236,6 +1262,95 @@ class DistanceField:
         paths, _, status = p.paths(np.ascontiguousarray(start, dtype=np.float32).reshape(1, dim))
         return paths[0], int(status[0]), clusters
 
+    def view_gain_depth(self, cover, cam6, poses, scorer=None, stream=None, **opts):
+        """How much unseen space a depth camera would reveal from each of `poses` [m, 12] (gpis3_view_gain_depth without a map):
+        per pose the field renderer's prediction of the frame, rays without a return measured as `miss`, and the number of
+        points of `cover` (a Coverage on this field's lattice) that integrating that frame would newly see, among those with
+        !(dist < min_dist).  Neither the field nor the mask changes.  opts: the gpis_view_opts fields (back_off, max_gap, miss,
+        min_dist) and the march's (gpis_render_field_opts).  scorer: a ViewScorer to hold the result (default: one kept by this
+        field).  Returns (gain int64 [m], hits int32 [m])."""
+        return self._view_gain_depth(None, cover, cam6, poses, scorer, stream, opts)
+
+    def view_gain_scan(self, cover, thetas, poses, off2, scorer=None, stream=None, **opts):
+        """view_gain_depth for a laser with beams `thetas` at each of `poses` [m, 6] (gpis2_view_gain_scan without a map); off2:
+        the sensor offset (x, y) in the laser frame."""
+        return self._view_gain_scan(None, cover, thetas, poses, off2, scorer, stream, opts)
+
+    def _own_scorer(self):
+        if getattr(self, "_scorer", None) is None:
+            self._scorer = ViewScorer()
+        return self._scorer
+
+    def _view_gain_depth(self, map_h, cover, cam6, poses, scorer, stream, opts):
+        poses = np.ascontiguousarray(poses, dtype=np.float32)
+        if poses.size == 0 or poses.size % 12:
+            raise GpisError("poses must be [m, 12] with m >= 1")
+        _, cam = _depth_frame("view_gain_depth", None, cam6, map_h, None)
+        v = scorer if scorer is not None else self._own_scorer()
+        o = view_opts(3, self._step(), **opts)
+        _check(self.L.gpis3_view_gain_depth(map_h, self.h, cover.h, v.h, cam, _p(poses), poses.size // 12, C.byref(o),
+                                            C.c_void_p(stream or 0)), "gpis3_view_gain_depth")
+        return v.get()
+
+    def _view_gain_scan(self, map_h, cover, thetas, poses, off2, scorer, stream, opts):
+        thetas, _, off = _scan_frame("view_gain_scan", thetas, None, off2, map_h)
+        poses = np.ascontiguousarray(poses, dtype=np.float32)
+        if poses.size == 0 or poses.size % 6:
+            raise GpisError("poses must be [m, 6] with m >= 1")
+        v = scorer if scorer is not None else self._own_scorer()
+        o = view_opts(2, self._step(), **opts)
+        _check(self.L.gpis2_view_gain_scan(map_h, self.h, cover.h, v.h, _p(thetas), thetas.size, off, _p(poses), poses.size // 6,
+                                           C.byref(o), C.c_void_p(stream or 0)), "gpis2_view_gain_scan")
+        return v.get()
+
+    def next_view(self, cover, start, sensor, yaws, base_pose=None, planner=None, out=None, unseen_dist=None, scorer=None, **opts):
+        """Which way to look next, and how to get there: the frontiers of `cover`, one candidate pose per (cluster representative,
+        yaw), the candidates scored by view_gain_*, the pose of largest gain (ties to the lowest index), and the path from
+        `start` to its representative through this field restricted to seen space, as explore plans it.  sensor: 2-D
+        (thetas, off2), 3-D cam6.  2-D candidates: pose_grid2 at the representative; 3-D: pose_grid3 around `base_pose` [12]
+        moved to the representative, rotation vectors (0, 0, yaw).  opts: explore's (the gpis_plan_opts fields, min_size) and
+        the gpis_view_opts fields with the march's.  Returns (path, status, pose, gains, clusters): the planner's status, or 4
+        with an empty path and a None pose when there is no cluster or every gain is 0; gains int64 [clusters, yaws].  A
+        composition of calls that exist: no device code of its own."""
+        dim = self.info()["dim"]
+        vnames = {f[0] for f in gpis_view_opts._fields_ + gpis_render_field_opts._fields_} - {"march"}
+        vopts = {k: opts.pop(k) for k in list(opts) if k in vnames}
+        copts = {k: opts.pop(k) for k in ("min_size",) if k in opts}
+        if "clearance" in opts:
+            copts["clearance"] = opts["clearance"]
+        clusters = cover.frontiers(self, **copts)
+        yaws = np.atleast_1d(np.asarray(yaws, dtype=np.float64))
+        nc = clusters["label"].size
+        empty = np.zeros((0, dim), np.float32)
+        if nc == 0 or yaws.size == 0:
+            return empty, 4, None, np.zeros((nc, yaws.size), np.int64), clusters
+        rep = clusters["rep"]
+        if dim == 2:
+            thetas, off2 = sensor
+            poses = np.concatenate([pose_grid2([r[0]], [r[1]], yaws) for r in rep])
+            gains, _ = self.view_gain_scan(cover, thetas, poses, off2, scorer=scorer, **vopts)
+        else:
+            if base_pose is None:
+                raise GpisError("a 3-D next_view needs base_pose")
+            base = np.ascontiguousarray(base_pose, dtype=np.float32).ravel().copy()
+            rv = np.stack([np.zeros_like(yaws), np.zeros_like(yaws), yaws], axis=1)
+            parts = []
+            for r in rep:
+                base[:3] = r
+                parts.append(pose_grid3(base, np.zeros((1, 3)), rv))
+            poses = np.concatenate(parts)
+            gains, _ = self.view_gain_depth(cover, sensor, poses, scorer=scorer, **vopts)
+        best = int(np.argmax(gains))                        # (the first maximum: the lowest index)
+        gains = gains.reshape(nc, yaws.size)
+        if gains.ravel()[best] == 0:
+            return empty, 4, None, gains, clusters
+        opts.setdefault("clearance", cover_opts(dim, self._step()).clearance)
+        r = cover.restrict(self, out=out, unseen_dist=unseen_dist)
+        p = planner if planner is not None else self._own_planner()
+        p.solve(r, rep[best // yaws.size].reshape(1, dim), **opts)
+        paths, _, status = p.paths(np.ascontiguousarray(start, dtype=np.float32).reshape(1, dim))
+        return paths[0], int(status[0]), poses.reshape(-1, 12 if dim == 3 else 6)[best].copy(), gains, clusters
+
     def _step(self):
         inf = self.info()
         if inf["dim"] == 0:
@@ -1531,6 +1646,73 @@ class Coverage:
         u = -field._step() if unseen_dist is None else float(unseen_dist)
         _check(self.L.gpis_cover_restrict(self.h, field.h, out.h, u, C.c_void_p(stream or 0)), "gpis_cover_restrict")
         out._device = field.device()
+        return out
+
+
+def view_opts(dim, step, **opts):
+    """gpis_view_opts of the library's defaults for `dim` and a field of lattice step `step` (gpis_view_default_opts) with the
+    given fields replaced; the fields of the march (gpis_render_field_opts) are taken by name as well."""
+    o = gpis_view_opts()
+    _check(lib().gpis_view_default_opts(int(dim), float(step), C.byref(o)), "gpis_view_default_opts")
+    own = {f[0] for f in gpis_view_opts._fields_} - {"march"}
+    march = {f[0] for f in gpis_render_field_opts._fields_}
+    for k, v in opts.items():
+        if k in own:
+            setattr(o, k, v)
+        elif k in march:
+            setattr(o.march, k, v)
+        else:
+            raise GpisError("unknown view option %r" % k)
+    return o
+
+
+class ViewScorer:
+    """Holds the device buffers and the last result of a batch of candidate viewpoints scored against a field and a coverage
+    (gpis*_view_gain_*): per pose the number of unseen lattice points it would reveal and the rays with a predicted return."""
+
+    INFO_KEYS = ("valid", "dim", "poses", "rays", "targets", "samples", "predict_ms", "table_ms", "target_ms", "gather_ms")
+    INT_KEYS = ("valid", "dim", "poses", "rays", "targets", "samples")
+
+    def __init__(self):
+        self.L = lib()
+        if self.L.gpis_device_count() < 1:
+            raise GpisError("no HIP device: gpismap_amd has no CPU fallback")
+        self.h = C.c_void_p(self.L.gpis_view_create())
+        if not self.h:
+            raise GpisError("gpis_view_create failed")
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.gpis_view_destroy(self.h)
+            self.h = None
+
+    __del__ = close
+
+    def info(self):
+        out = np.zeros(len(self.INFO_KEYS), dtype=np.float64)
+        _check(self.L.gpis_view_info(self.h, _p(out, C.c_double), out.size), "gpis_view_info")
+        d = dict(zip(self.INFO_KEYS, out.tolist()))
+        for k in self.INT_KEYS:
+            d[k] = int(d[k])
+        return d
+
+    def get(self):
+        """(gain int64 [m], hits int32 [m]) of the last call."""
+        m = self.info()["poses"]
+        gain, hits = np.zeros(m, np.int64), np.zeros(m, np.int32)
+        _check(self.L.gpis_view_get(self.h, _p(gain, C.c_longlong), _p(hits, C.c_int), m), "gpis_view_get")
+        return gain, hits
+
+    def gain(self):
+        return self.get()[0]
+
+    def hits(self):
+        return self.get()[1]
+
+    def predicted(self, k):
+        """The predicted measurement d' [rays] f32 of pose k of the last call (3-D: column-major as update())."""
+        out = np.zeros(self.info()["rays"], np.float32)
+        _check(self.L.gpis_view_get_predicted(self.h, int(k), _p(out), out.size), "gpis_view_get_predicted")
         return out
 
 

@@ -18,6 +18,7 @@
 #include "traj.h"
 #include "mppi.h"
 #include "cover.h"
+#include "view.h"
 #include "obsgp.h"
 #include "ongpis.h"
 
@@ -1483,6 +1484,98 @@ int gpis_cover_info(void* cover, double* out, int n) {
                           v ? (double)c.step : 0.0, (double)c.frames, c.frontiers_valid ? 1.0 : 0.0, (double)c.npoints,
                           (double)c.ncomponents, (double)c.label.size(), (double)c.rounds, c.integrate_ms, c.frontiers_ms};
     for (int i = 0; i < n && i < 14; ++i) out[i] = w[i];
+    return GPIS_OK;
+}
+
+// ---- candidate viewpoints scored by the unseen space they would reveal ------------------------------------------------------
+int gpis_view_default_opts(int dim, float step, gpis_view_opts* o) {
+    if (!o) return GPIS_ERR_ARG;
+    if (int rc = gpis_render_field_default_opts(dim, step, &o->march)) return rc;
+    return view_default_tail(dim, step, o);
+}
+void* gpis_view_create(void) {
+    if (gpis_device_count() < 1) { fprintf(stderr, "[gpismap_amd] no HIP device\n"); return nullptr; }
+    ViewScorer* v = new (std::nothrow) ViewScorer();
+    if (v && !v->own) { delete v; return nullptr; }
+    return v;
+}
+void gpis_view_destroy(void* view) { delete (ViewScorer*)view; }
+// the options of a call: the caller's, or the defaults for the field's step; the march's checks and the rule's
+static int view_args(void* d, int dim, const gpis_view_opts* opts, gpis_view_opts* o) {
+    if (opts) *o = *opts;
+    else {
+        const DistanceField& df = *(const DistanceField*)d;
+        if (!df.valid) return GPIS_ERR_STATE;
+        if (int rc = gpis_view_default_opts(dim, df.step, o)) return rc;
+    }
+    RenderFieldOpts r;
+    r.tnear = o->march.tnear; r.tfar = o->march.tfar; r.min_step = o->march.min_step; r.max_step = o->march.max_step;
+    r.slack = o->march.slack; r.refine = o->march.refine; r.max_steps = o->march.max_steps;
+    if (int rc = render_field_check_opts(r)) return rc;
+    return view_check_tail(*o);
+}
+// the batch's limits (before the poses are read), the poses, the field's and the coverage's state, then the call on the field's
+// device: every refusal leaves the previous result readable
+static int view_call(void* d, void* cover, ViewScorer& v, const SensorFrame& f, const float* poses, int m, const gpis_view_opts& o,
+                     void* stream) {
+    if (int rc = view_check_batch(m, f.n)) return rc;
+    const size_t np = (size_t)(f.geo.dim == 3 ? 12 : 6) * (size_t)m;
+    for (size_t k = 0; k < np; ++k) if (!std::isfinite(poses[k])) return GPIS_ERR_ARG;
+    const DistanceField& df = *(const DistanceField*)d;
+    const Coverage& c = *(const Coverage*)cover;
+    if (!df.valid) return GPIS_ERR_STATE;
+    if (df.dim != f.geo.dim) return GPIS_ERR_ARG;
+    if (!c.same_lattice(df)) return GPIS_ERR_STATE;
+    DeviceScope ds(df.device);
+    try {
+        if (int rc = v.bind(df.device)) { v.clear_result(); return rc; }
+        const int rc = v.score(df, c, f, poses, m, o, stream ? (hipStream_t)stream : df.own);
+        if (rc != GPIS_OK) v.clear_result();
+        return rc;
+    } catch (...) { v.clear_result(); return GPIS_ERR_STATE; }
+}
+int gpis3_view_gain_depth(void* m, void* df, void* cover, void* view, const gpis_cam* cam, const float* poses12, int np,
+                          const gpis_view_opts* opts, void* stream) {
+    if (!df || !cover || !view || !poses12 || np < 1 || (!cam && !m)) return GPIS_ERR_ARG;
+    gpis_view_opts o;
+    if (int rc = view_args(df, 3, opts, &o)) return rc;
+    SensorFrame f;
+    if (int rc = depth_frame(m, cam, &f)) return rc;
+    return view_call(df, cover, *(ViewScorer*)view, f, poses12, np, o, stream);
+}
+int gpis2_view_gain_scan(void* m, void* df, void* cover, void* view, const float* thetas, int n, const float* off2, const float* poses6,
+                         int np, const gpis_view_opts* opts, void* stream) {
+    if (!df || !cover || !view || !thetas || !poses6 || n < 1 || np < 1 || (!off2 && !m)) return GPIS_ERR_ARG;
+    gpis_view_opts o;
+    if (int rc = view_args(df, 2, opts, &o)) return rc;
+    if (int rc = view_check_batch(np, n)) return rc;         // (before the angles are read, too)
+    SensorFrame f;
+    if (int rc = scan_frame(m, thetas, n, off2, &f)) return rc;
+    return view_call(df, cover, *(ViewScorer*)view, f, poses6, np, o, stream);
+}
+int gpis_view_get(void* view, long long* gain, int* hits, int m) {
+    if (!view) return GPIS_ERR_ARG;
+    const ViewScorer& v = *(const ViewScorer*)view;
+    if (!v.valid) return GPIS_ERR_STATE;
+    if ((long long)m != v.poses) return GPIS_ERR_ARG;
+    if (gain) std::memcpy(gain, v.gain.data(), sizeof(long long) * v.gain.size());
+    if (hits) std::memcpy(hits, v.hits.data(), sizeof(int) * v.hits.size());
+    return GPIS_OK;
+}
+int gpis_view_get_predicted(void* view, int pose, float* out, long long n) {
+    if (!view || !out) return GPIS_ERR_ARG;
+    ViewScorer& v = *(ViewScorer*)view;
+    if (!v.valid) return GPIS_ERR_STATE;
+    if (pose < 0 || (long long)pose >= v.poses || n != v.rays) return GPIS_ERR_ARG;
+    DeviceScope ds(v.device);
+    return v.predicted(pose, out);
+}
+int gpis_view_info(void* view, double* out, int n) {
+    if (!view || !out || n < 0) return GPIS_ERR_ARG;
+    const ViewScorer& v = *(const ViewScorer*)view;
+    const double w[10] = {v.valid ? 1.0 : 0.0, (double)v.dim, (double)v.poses, (double)v.rays, (double)v.targets, (double)v.samples,
+                          v.predict_ms, v.table_ms, v.target_ms, v.gather_ms};
+    for (int i = 0; i < n && i < 10; ++i) out[i] = w[i];
     return GPIS_OK;
 }
 

@@ -14,6 +14,7 @@
 #include <cstring>
 #include "cover.h"
 #include "block_ops.h"
+#include "compact.h"
 #include "dfield.h"
 
 namespace gpis {
@@ -24,6 +25,7 @@ constexpr int kBlock = Coverage::kBlock;
 constexpr int kItems = Coverage::kItems;
 constexpr int kChunk = Coverage::kChunk;
 constexpr int kTabWords = Coverage::kTabWords;
+static_assert(kBlock == kCompactBlock && kChunk == kCompactChunk, "compact.h's chunks are the coverage's");
 
 struct CovLat {
     int dim, nx, ny, nz;
@@ -77,7 +79,7 @@ __global__ void __launch_bounds__(kBlock) cover_binarise_kernel(unsigned char* _
     for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < n; p += gridDim.x * blockDim.x) seen[p] = seen[p] ? 1 : 0;
 }
 
-// ---- compaction: count, scan, write -----------------------------------------------------------------------------------------
+// ---- compaction (compact.h): the predicates ---------------------------------------------------------------------------------
 // a frontier point: seen and traversable, with an unseen and traversable axis neighbour inside the lattice
 struct FrontierPred {
     CovLat L;
@@ -103,53 +105,6 @@ struct RootPred {
     const int* label;
     __device__ bool operator()(int r) const { return label[r] == r; }
 };
-
-template <class Pred>
-__global__ void __launch_bounds__(kBlock) cover_count_kernel(Pred pred, int n, int* __restrict__ bcount) {
-    const int base = blockIdx.x * kChunk;
-    int cnt = 0;
-    for (int it = 0; it < kItems; ++it) {
-        const int p = base + it * kBlock + threadIdx.x;
-        cnt += __syncthreads_count(p < n && pred(p));
-    }
-    if (threadIdx.x == 0) bcount[blockIdx.x] = cnt;
-}
-
-// in place: b[0..nb) = exclusive scan of the counts, b[nb] = their sum.  One workgroup.
-__global__ void __launch_bounds__(kBlock) cover_offsets_kernel(int* __restrict__ b, int nb) {
-    __shared__ int sh[kBlock / kWave];
-    int carry = 0;
-    for (int base = 0; base < nb; base += kBlock) {
-        const int idx = base + threadIdx.x;
-        const int v = idx < nb ? b[idx] : 0;
-        int total;
-        const int incl = block_incl_scan<kBlock, int>(v, sh, &total);
-        if (idx < nb) b[idx] = carry + incl - v;
-        carry += total;
-    }
-    if (threadIdx.x == 0) b[nb] = carry;
-}
-
-// list[off ..] = the elements of this chunk that pass, ascending; rank[p] = the position of p in the list, -1 if it fails
-template <class Pred>
-__global__ void __launch_bounds__(kBlock) cover_write_kernel(Pred pred, int n, const int* __restrict__ boff, int* __restrict__ list,
-                                                             int* __restrict__ rank) {
-    __shared__ int sh[kBlock / kWave];
-    const int base = blockIdx.x * kChunk;
-    int off = boff[blockIdx.x];
-    for (int it = 0; it < kItems; ++it) {
-        const int p = base + it * kBlock + threadIdx.x;
-        const int f = (p < n && pred(p)) ? 1 : 0;
-        int total;
-        const int incl = block_incl_scan<kBlock, int>(f, sh, &total);
-        if (p < n) {
-            const int r = off + incl - 1;
-            if (f) list[r] = p;
-            rank[p] = f ? r : -1;
-        }
-        off += total;
-    }
-}
 
 // ---- labels ---------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ int ld_label(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
@@ -426,28 +381,6 @@ int Coverage::integrate(const SensorFrame& f, const float* in, const float* pose
     integrate_ms = ms_since(t0);
     return GPIS_OK;
 }
-
-namespace {
-
-// count, scan, write of the elements of [0, n) that pass pred: *total of them, ascending in d_list (grow_lists(total) makes room
-// once the count is known), their positions in d_rank; synchronises `s` after the scan
-template <class Pred, class Grow>
-int compact_run(Pred pred, int n, int* d_bcount, int* h_word, int* total, int*& d_list, int*& d_rank, hipStream_t s, const Grow& grow_lists) {
-    const int nb = (n + kChunk - 1) / kChunk;
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(cover_count_kernel<Pred>), dim3(nb), dim3(kBlock), 0, s, pred, n, d_bcount);
-    GPIS_HIP(hipGetLastError());
-    hipLaunchKernelGGL(cover_offsets_kernel, dim3(1), dim3(kBlock), 0, s, d_bcount, nb);
-    GPIS_HIP(hipGetLastError());
-    GPIS_HIP(hipMemcpyAsync(h_word, d_bcount + nb, sizeof(int), hipMemcpyDeviceToHost, s));
-    GPIS_HIP(hipStreamSynchronize(s));
-    *total = h_word[0];
-    if (int rc = grow_lists(*total)) return rc;
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(cover_write_kernel<Pred>), dim3(nb), dim3(kBlock), 0, s, pred, n, d_bcount, d_list, d_rank);
-    GPIS_HIP(hipGetLastError());
-    return GPIS_OK;
-}
-
-}  // namespace
 
 int Coverage::frontiers(const DistanceField& df, const CoverOpts& o, hipStream_t s) {
     if (!has_lattice || !df.valid) return GPIS_ERR_STATE;

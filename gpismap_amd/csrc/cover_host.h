@@ -31,9 +31,15 @@ inline int cover_default_opts(int dim, float step, CoverOpts* o) {
 
 // GPIS_ERR_ARG: back_off negative or non-finite, max_gap outside (0, 90 degrees), clearance non-finite or <= back_off (below that
 // every surface would raise a frontier), min_size < 1, max_rounds < 0
+// the two options of the integration rule on their own (the view scorer applies the same rule: view_host.h)
+inline int cover_check_rule(float back_off, float max_gap) {
+    if (!(std::isfinite(back_off) && back_off >= 0.f)) return GPIS_ERR_ARG;
+    if (!(std::isfinite(max_gap) && max_gap > 0.f && (double)max_gap < 3.14159265358979323846 / 2)) return GPIS_ERR_ARG;
+    return GPIS_OK;
+}
+
 inline int cover_check_opts(const CoverOpts& o) {
-    if (!(std::isfinite(o.back_off) && o.back_off >= 0.f)) return GPIS_ERR_ARG;
-    if (!(std::isfinite(o.max_gap) && o.max_gap > 0.f && (double)o.max_gap < 3.14159265358979323846 / 2)) return GPIS_ERR_ARG;
+    if (int rc = cover_check_rule(o.back_off, o.max_gap)) return rc;
     if (!(std::isfinite(o.clearance) && o.clearance > o.back_off)) return GPIS_ERR_ARG;
     if (o.min_size < 1 || o.max_rounds < 0) return GPIS_ERR_ARG;
     return GPIS_OK;

@@ -13,6 +13,7 @@
 #include "map_query.h"
 #include "render.h"
 #include "block_ops.h"
+#include "field_march.h"
 
 namespace gpis {
 
@@ -20,59 +21,12 @@ namespace {
 
 constexpr int kBlock = 256;
 constexpr int kScanBlocks = kCompactBlocks;   // compaction segments (one thread each in the top scan)
-constexpr uint8_t kRunning = 255;     // status of a ray still marching
-
-// the world point of parameter z on a ray: 3-D from its (u, v); 2-D from its host-double (c, s)
-__device__ __forceinline__ void world_point_at(const RayGeom& g, float u, float v, double c, double s, float z, float& p0, float& p1,
-                                               float& p2) {
-    if (g.dim == 3) {
-        const float xl = u * z, yl = v * z;
-        p0 = g.R[0] * xl + g.R[3] * yl + g.R[6] * z + g.t[0];
-        p1 = g.R[1] * xl + g.R[4] * yl + g.R[7] * z + g.t[1];
-        p2 = g.R[2] * xl + g.R[5] * yl + g.R[8] * z + g.t[2];
-    } else {
-        const float xl = (float)((double)z * c) + g.off[0];
-        const float yl = (float)((double)z * s) + g.off[1];
-        p0 = g.R[0] * xl + g.R[2] * yl + g.t[0];
-        p1 = g.R[1] * xl + g.R[3] * yl + g.t[1];
-        p2 = 0.f;
-    }
-}
+constexpr uint8_t kRunning = kRayRunning;
 
 __device__ __forceinline__ void world_point(const RayGeom& g, const float* __restrict__ ray, const double* __restrict__ cs, int i,
                                             float z, float& p0, float& p1, float& p2) {
     if (g.dim == 3) world_point_at(g, ray[4 * (size_t)i], ray[4 * (size_t)i + 1], 0.0, 0.0, z, p0, p1, p2);
     else world_point_at(g, 0.f, 0.f, cs[2 * (size_t)i], cs[2 * (size_t)i + 1], z, p0, p1, p2);
-}
-
-// Set-up of ray i: its direction terms (3-D: u, v, il = 1 / sqrt(u^2 + v^2 + 1); 2-D: c, s of the beam), then the slab clip of
-// [tnear, tfar] against the box [lo, hi] (IEEE division; fmin / fmax drop the NaN of an axis the ray runs in the plane of)
-// into [t0, t1].
-__device__ __forceinline__ void ray_setup(const RayGeom& g, const double* __restrict__ cs, int i, float tnear, float tfar,
-                                          const float* lo, const float* hi, float& u, float& v, float& il, double& cd, double& sd,
-                                          float& t0, float& t1) {
-    float o[3], d[3];
-    if (g.dim == 3) {
-        const int col = i / g.height, row = i - col * g.height;
-        u = ((float)col - g.cx) / g.fx; v = ((float)row - g.cy) / g.fy;
-        il = 1.0f / sqrtf(u * u + v * v + 1.0f);
-        cd = sd = 0.0;
-        for (int a = 0; a < 3; ++a) { o[a] = g.t[a]; d[a] = g.R[a] * u + g.R[3 + a] * v + g.R[6 + a]; }
-    } else {
-        cd = cs[2 * (size_t)i]; sd = cs[2 * (size_t)i + 1];
-        u = v = 0.f; il = 1.0f;
-        const float c = (float)cd, s = (float)sd;
-        o[0] = g.R[0] * g.off[0] + g.R[2] * g.off[1] + g.t[0];
-        o[1] = g.R[1] * g.off[0] + g.R[3] * g.off[1] + g.t[1];
-        d[0] = g.R[0] * c + g.R[2] * s;
-        d[1] = g.R[1] * c + g.R[3] * s;
-    }
-    t0 = tnear; t1 = tfar;
-    for (int a = 0; a < g.dim; ++a) {
-        const float ta = (lo[a] - o[a]) / d[a], tb = (hi[a] - o[a]) / d[a];
-        t0 = fmaxf(t0, fminf(ta, tb));
-        t1 = fminf(t1, fmaxf(ta, tb));
-    }
 }
 
 // Per ray: ray_setup's direction terms and clip, the march state, NaN outputs.  flag = 1 for the rays whose clipped interval is
@@ -264,9 +218,8 @@ __device__ __forceinline__ int field_ray_of_thread(const RayGeom& g, int n, bool
     return (col < g.width && row < g.height) ? (int)(col * g.height + row) : -1;
 }
 
-// One thread marches one ray from set-up to output (sphere tracing): ray_setup's terms and clip, then one loop whose every
-// turn takes one sample of the field -- a march sample, a bisection midpoint or the final secant point, by the ray's phase -- so
-// the lanes of a wavefront share one sampler whatever their phases.  Step, hit, refinement and status: tests/render_field_ref.py.
+// One thread marches one ray from set-up to output (sphere tracing): ray_setup's terms and clip, then field_march
+// (field_march.h), which the batched prediction of view.hip shares.  Step, hit, refinement and status: tests/render_field_ref.py.
 // Nothing is written per sample.  part[3 b ..]: the block's samples, hits and largest per-ray sample count, reduced in a fixed
 // order (wave shuffles, then the four waves in order).
 template <int D>
@@ -287,48 +240,8 @@ __global__ void __launch_bounds__(kBlock) render_field_kernel(RayGeom g, const d
         float u, v, il, z, zend;
         double cd, sd;
         ray_setup(g, cs, i, o.tnear, o.tfar, lo, hi, u, v, il, cd, sd, z, zend);
-        const float sl = o.slack * L.st;
-        float zlo = 0.f, glo = 0.f, ghi = 0.f, q = z;
-        float smp[NC];
-        int st = (z <= zend) ? kRunning : 1;
-        int phase = 0, nstep = 0, round = 0;     // phase 0 march, 1 bisection, 2 the final sample
-        bool has = false;
-        while (st == kRunning) {
-            float p0, p1, p2;
-            world_point_at(g, u, v, cd, sd, q, p0, p1, p2);
-            df_sample_at(F, L, p0, p1, p2, smp);
-            ++ns;
-            const float d = smp[0];
-            if (phase == 0) {
-                if (has && d < 0.f && !(glo < 0.f)) {
-                    ghi = d;                     // bracket [zlo, z]
-                    phase = o.refine > 0 ? 1 : 2;
-                } else {
-                    zlo = z; glo = d; has = true;
-                    if (++nstep >= o.max_steps) { st = 2; break; }
-                    const float ds = isnan(d) ? o.min_step : fminf(fmaxf(fabsf(d) - sl, o.min_step), o.max_step);
-                    const float zn = z + (D == 3 ? ds * il : ds);
-                    if (!(zn <= zend)) { st = 1; break; }
-                    z = zn; q = zn;
-                    continue;
-                }
-            } else if (phase == 1) {
-                if (d < 0.f) { z = q; ghi = d; }
-                else { zlo = q; glo = d; }
-                if (++round >= o.refine) phase = 2;
-            } else {
-                st = 0;
-                break;
-            }
-            if (phase == 1) {
-                q = zlo + (z - zlo) * 0.5f;
-            } else if (isnan(glo)) {
-                q = z;
-            } else {
-                q = zlo + (z - zlo) * (glo / (glo - ghi));
-                q = fminf(fmaxf(q, zlo), z);
-            }
-        }
+        float q, smp[NC];
+        const int st = field_march<D>(g, u, v, il, cd, sd, z, zend, o, F, L, q, smp, ns);
         hit = st == 0;
         depth[i] = hit ? q : nanf_;
 #pragma unroll

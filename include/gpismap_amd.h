@@ -967,6 +967,53 @@ int   gpis_cover_restrict(void* cover, void* df_in, void* df_out, float unseen_d
  * components, clusters, labelling rounds, ms of host wall time of the last integrate, of the last frontiers call */
 int   gpis_cover_info(void* cover, double* out, int n);
 
+/* ---- scoring candidate viewpoints by the unseen space they would reveal -----------------------------------
+ * For each of m candidate poses: what would a sensor there measure of the field (the field renderer's march, §7g), and how many
+ * lattice points that are not yet seen would integrating that measurement into the coverage mask turn to seen (the coverage's
+ * rule, §7m)?  One call scores the batch on the device; neither the field nor the mask is changed.  tests/view_ref.py composes
+ * the two references; every result is an integer and the device's are the reference's.
+ * Per pose k: 1. the march of gpis3_render_depth_field / gpis2_render_scan_field with opts->march; the predicted measurement
+ * d'[ray] = status == 0 ? depth : miss (float32; status 1 and 2 both miss); hits[k] = rays of status 0.  2. The mask of pose k:
+ * the points gpis3_cover_depth / gpis2_cover_scan would see in d' from pose k with back_off (and max_gap), windows (0.4 < d' < 4,
+ * 0.2 < r' < 30), per-pose sector table, "fewer than two valid beams" and l.l == 0 rules included.  3. target[p] = !seen[p] and
+ * !(dist[p] < min_dist), a float32 compare (a NaN dist counts); gain[k] = the number of targets in the mask of pose k.  With
+ * min_dist = -inf, gain[k] is the number of bytes integrating the predicted frame would turn from 0 to 1.  A pose gets the
+ * same numbers alone and at any position of any batch.
+ * The holder owns its buffers (4 B per pose and ray, 4 B per target, 2-D: 20 B more per pose and beam; grow-only) and moves to the
+ * field's device; hip_stream NULL: the field's own stream; every call returns with its work finished.  map: may be NULL; it is
+ * read only for a NULL cam / off2.
+ * Errors: a NULL view, field, cover, thetas or poses; cam / off2 NULL without a map; a bad camera; n < 1; m < 1; a non-finite
+ * pose entry or beam angle; the march's refusals (gpis_render_field_opts); back_off negative or non-finite; max_gap outside
+ * (0, 90 degrees); a NaN min_dist; a field of another dim than the sensor -> GPIS_ERR_ARG.  m > 65536 or m x rays > 2^26 ->
+ * GPIS_ERR_LIMIT, before the poses are read.  A field without a result, a coverage that was never reset or lies on another
+ * lattice than the field's, get / get_predicted without a result -> GPIS_ERR_STATE.  A refused call leaves the
+ * previous result readable. */
+typedef struct gpis_view_opts {
+    gpis_render_field_opts march;   /* the prediction's march */
+    float back_off;             /* as gpis_cover_opts */
+    float max_gap;              /* as gpis_cover_opts (2-D) */
+    float miss;                 /* the measurement of a ray without a predicted return; outside the window, 0 or NaN: it reveals nothing */
+    float min_dist;             /* targets: unseen points with !(dist < min_dist); -inf: every unseen point */
+} gpis_view_opts;
+/* defaults: march gpis_render_field_default_opts(dim, step), back_off step, max_gap 2 degrees, miss = march.tfar - step (the
+ * farthest measurement the rule accepts, less one cell), min_dist -inf.  Needs no device. */
+int   gpis_view_default_opts(int dim, float step, gpis_view_opts* opts);
+void* gpis_view_create(void);                               /* on the current device; NULL without one */
+void  gpis_view_destroy(void* view);
+/* poses12 [m][12] = [t(3), R(9) column-major]; cam NULL: the map's camera; opts NULL: the defaults for the field's step */
+int   gpis3_view_gain_depth(void* map, void* df, void* cover, void* view, const gpis_cam* cam, const float* poses12, int m,
+                            const gpis_view_opts* opts, void* hip_stream);
+/* thetas [n] as update(); off2 NULL: the map's sensor offset; poses6 [m][6] = [t(2), R(4)] */
+int   gpis2_view_gain_scan(void* map, void* df, void* cover, void* view, const float* thetas, int n, const float* off2,
+                           const float* poses6, int m, const gpis_view_opts* opts, void* hip_stream);
+/* host copies of the last result (either pointer may be NULL); m must be its pose count */
+int   gpis_view_get(void* view, long long* gain, int* hits, int m);
+/* d' of pose `pose` of the last result; n must be its ray count (3-D: column-major as update()) */
+int   gpis_view_get_predicted(void* view, int pose, float* out, long long n);
+/* out[0..n): 1 if a result is held, dim, poses, rays per pose, targets, samples of the march, ms of host wall time of the
+ * prediction, of the sector tables (2-D), of the target list, of the gather */
+int   gpis_view_info(void* view, double* out, int n);
+
 #ifdef __cplusplus
 }
 #endif
