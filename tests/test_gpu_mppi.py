@@ -53,14 +53,15 @@ def env(dim):
 
 
 class Checked:
-    """A Controller whose every call is checked against the reference fed with the device's state from before the call."""
+    """A Controller (a new one, or `ctl`: one that has served other calls and is initialised again here) whose every call is
+    checked against the reference fed with the device's state from before the call."""
 
-    def __init__(self, c, stream=None):
+    def __init__(self, c, stream=None, ctl=None):
         import gpismap_amd
         self.c, self.dim, self.K, self.T, self.seed, self.tick = c, c["dim"], c["K"], c["T"], c["seed"], 0
         self.sc, self.df, self.dist, self.pl, self.cost = env(self.dim)
         self.stream = stream
-        self.ctl = gpismap_amd.Controller()
+        self.ctl = ctl if ctl is not None else gpismap_amd.Controller()
         self.ctl.init(self.dim, self.K, self.T, seed=self.seed)
         g = self.ctl.get()
         assert not g["U"].any() and not g["J"].any() and not g["q"].any() and not g["hits"].any() and not g["stats"]["have_step"]

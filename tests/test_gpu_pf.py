@@ -67,11 +67,12 @@ class Frame:
 
 
 class Checked:
-    """A ParticleFilter whose every call is checked against the reference fed with the device's state from before the call."""
+    """A ParticleFilter (a new one, or `pf`: one that has served other calls and is initialised again here) whose every call is
+    checked against the reference fed with the device's state from before the call."""
 
-    def __init__(self, poses, seed, dim):
+    def __init__(self, poses, seed, dim, pf=None):
         import gpismap_amd
-        self.pf = gpismap_amd.ParticleFilter()
+        self.pf = pf if pf is not None else gpismap_amd.ParticleFilter()
         self.dim, self.seed, self.tick = dim, seed, 0
         self.opts = pf_ref.default_opts(dim)
         self.pf.init(poses, seed=seed)
