@@ -80,6 +80,12 @@ class gpis_traj_opts(C.Structure):
                 ("rate", C.c_float), ("max_move", C.c_float), ("tol", C.c_float), ("iters", C.c_int), ("sub", C.c_int)]
 
 
+class gpis_traj_timing_opts(C.Structure):
+    _fields_ = [("v_max", C.c_float), ("v_min", C.c_float), ("a_max", C.c_float), ("d_max", C.c_float), ("a_lat", C.c_float),
+                ("w_max", C.c_float), ("v_start", C.c_float), ("v_end", C.c_float), ("clearance", C.c_float),
+                ("slow_dist", C.c_float)]
+
+
 def _p(a, t=C.c_float):
     return a.ctypes.data_as(C.POINTER(t))
 
@@ -271,6 +277,15 @@ def lib():
         L.gpis_traj_info.argtypes = [vp, dp, C.c_int]
         L.gpis_traj_get.argtypes = [vp, fp, ub, ip, fp, fp, fp, fp, ip, ub]
         L.gpis_traj_device.argtypes = [vp, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
+    if hasattr(L, "gpis_timing_time"):
+        ub = C.POINTER(C.c_ubyte)
+        d = C.c_double
+        L.gpis_timing_default_opts.argtypes = [C.c_int, C.c_float, C.POINTER(gpis_traj_timing_opts)]
+        L.gpis_timing_time.argtypes = [vp, vp, C.POINTER(gpis_traj_timing_opts), vp]
+        L.gpis_timing_info.argtypes = [vp, dp, C.c_int]
+        L.gpis_timing_get.argtypes = [vp, fp, fp, ub, ub, fp, fp, fp, ip]
+        L.gpis_timing_controls.argtypes = [vp, d, C.c_int, d, d, d, dp, dp, dp, ip]
+        L.gpis_timing_follow.argtypes = [vp, vp, C.c_int, d, d, d, d, dp, dp]
     if hasattr(L, "gpis_locate_create"):
         lo = C.POINTER(gpis_locate_opts)
         L.gpis_locate_default_opts.argtypes = [C.c_int, lo]
@@ -1804,6 +1819,70 @@ class Trajectories:
         _check(self.L.gpis_traj_device(self.h, C.byref(a), C.byref(b), C.byref(c)), "gpis_traj_device")
         return a.value or 0, b.value or 0, c.value or 0
 
+    TIMING_INFO_KEYS = ("timed", "time_ms", "controls_ms")
+
+    def time(self, df=None, stream=0, **opts):
+        """Speeds and times on the last result under speed and acceleration limits (gpis_timing_time).  df: a DistanceField for
+        the clearance slow-down, or None.  opts: gpis_traj_timing_opts fields.  Returns a dict of host copies: v, t [m, N] f32,
+        limiter [m, N] u8 (0 v_max, 1 lateral acceleration, 2 yaw rate, 3 clearance, 4 the v_min floor, 5 an end speed, 6 an
+        acceleration cone, 7 a braking cone), status [m] u8 (0 timed, 2 no input, 3 a non-finite time), duration, max_speed,
+        max_curvature [m] f32, limiter_counts [m, 8] i32."""
+        i = self.info()
+        if not i["valid"]:
+            raise GpisError("trajectories hold no result")
+        o = timing_opts(i["dim"], df._step() if df is not None else 1.0, **opts)
+        _check(self.L.gpis_timing_time(self.h, df.h if df is not None else None, C.byref(o), C.c_void_p(stream)), "gpis_timing_time")
+        return self.timing()
+
+    def timing_info(self):
+        """dict(timed, time_ms, controls_ms): whether a timing is held, host wall times of the last time() and controls()."""
+        out = np.zeros(len(self.TIMING_INFO_KEYS), dtype=np.float64)
+        _check(self.L.gpis_timing_info(self.h, _p(out, C.c_double), out.size), "gpis_timing_info")
+        d = dict(zip(self.TIMING_INFO_KEYS, out.tolist()))
+        d["timed"] = int(d["timed"])
+        return d
+
+    def timing(self):
+        """The dict time() returned, again (gpis_timing_get)."""
+        i = self.info()
+        if not self.timing_info()["timed"]:
+            raise GpisError("trajectories hold no timing")
+        m, N = i["m"], i["N"]
+        r = dict(v=np.zeros((m, N), np.float32), t=np.zeros((m, N), np.float32), limiter=np.zeros((m, N), np.uint8),
+                 status=np.zeros(m, np.uint8), duration=np.zeros(m, np.float32), max_speed=np.zeros(m, np.float32),
+                 max_curvature=np.zeros(m, np.float32), limiter_counts=np.zeros((m, 8), np.int32))
+        _check(self.L.gpis_timing_get(self.h, _p(r["v"]), _p(r["t"]), _p(r["limiter"], C.c_ubyte), _p(r["status"], C.c_ubyte),
+                                      _p(r["duration"]), _p(r["max_speed"]), _p(r["max_curvature"]),
+                                      _p(r["limiter_counts"], C.c_int)), "gpis_timing_get")
+        return r
+
+    def controls(self, dt, T, t0=0.0, w_limit=0.0, min_move=1e-9):
+        """Control sequences of the controller's model along the timed trajectories (gpis_timing_controls): (U [m, T, 2 / 4] f64,
+        heading0 [m, 2], p0 [m, dim], clamped [m] i32) for a robot that starts at p0 facing heading0."""
+        i = self.info()
+        if not self.timing_info()["timed"]:
+            raise GpisError("trajectories hold no timing")
+        m, T = i["m"], int(T)
+        nu = 4 if i["dim"] == 3 else 2
+        U = np.zeros((m, max(T, 0), nu), np.float64)
+        h0, p0, cl = np.zeros((m, 2), np.float64), np.zeros((m, i["dim"]), np.float64), np.zeros(m, np.int32)
+        _check(self.L.gpis_timing_controls(self.h, float(dt), T, float(t0), float(w_limit), float(min_move), _p(U, C.c_double),
+                                           _p(h0, C.c_double), _p(p0, C.c_double), _p(cl, C.c_int)), "gpis_timing_controls")
+        return U, h0, p0, cl
+
+
+def timing_opts(dim, step, **opts):
+    """gpis_traj_timing_opts of the library's defaults for `dim` and a field of lattice step `step` (gpis_timing_default_opts)
+    with the given fields replaced."""
+    o = gpis_traj_timing_opts()
+    _check(lib().gpis_timing_default_opts(int(dim), float(step), C.byref(o)), "gpis_timing_default_opts")
+    names = {f[0] for f in gpis_traj_timing_opts._fields_}
+    for k, v in opts.items():
+        if k not in names:
+            raise GpisError("unknown timing option %r" % k)
+        setattr(o, k, v)
+    return o
+
 
 def render_field_opts(dim, step, **opts):
     """gpis_render_field_opts of the library's defaults for `dim` and a field of lattice step `step`
@@ -2174,6 +2253,17 @@ class Controller:
         if U.size != i["horizon"] * (4 if i["dim"] == 3 else 2):
             raise GpisError("U must be [T, %d]" % (4 if i["dim"] == 3 else 2))
         _check(self.L.gpis_mppi_set_nominal(self.h, _p(U, C.c_double)), "gpis_mppi_set_nominal")
+
+    def follow(self, traj, index, dt, t0=0.0, w_limit=0.0, min_move=1e-9):
+        """Replace the nominal sequence by the control sequence of trajectory `index` of a timed Trajectories from time t0 on, in
+        steps of dt (gpis_timing_follow); the sequence is computed on the device and stays there.  Returns (p0 [dim],
+        heading0 [2]): where the sequence starts and which way it faces."""
+        if not self.dim:
+            raise GpisError("follow before init")
+        p0, h0 = np.zeros(self.dim, np.float64), np.zeros(2, np.float64)
+        _check(self.L.gpis_timing_follow(self.h, traj.h, int(index), float(dt), float(t0), float(w_limit), float(min_move),
+                                         _p(h0, C.c_double), _p(p0, C.c_double)), "gpis_timing_follow")
+        return p0, h0
 
     def step(self, field, pose, goal=None, planner=None, stream=None, **opts):
         """gpis_mppi_step: see DistanceField.control."""

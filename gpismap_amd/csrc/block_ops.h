@@ -53,6 +53,26 @@ __device__ __forceinline__ T block_incl_scan(T v, T* sh, T* total) {
     return before + v;
 }
 
+// an integer max-scan of flags: the largest thread index <= the own one whose flag is set (-1: none), *first = the smallest
+// index with a set flag in the block (-1: none).  A wavefront's ballot, then the wavefronts before (after) the own one through
+// sh; integers, so there is no order to fix.  sh: two slots per wavefront, free again on return.  nt: the block's threads
+__device__ __forceinline__ int block_latest_flag(bool flag, int* sh, int nt, int* first) {
+    const int tid = threadIdx.x, lane = tid & (kWave - 1), w = tid / kWave, nw = nt / kWave;
+    const unsigned long long mask = __ballot(flag);
+    const unsigned long long upto = mask & (~0ull >> (kWave - 1 - lane));
+    if (lane == 0) {
+        sh[2 * w] = mask ? w * kWave + (kWave - 1 - __clzll((long long)mask)) : -1;      // the wavefront's last
+        sh[2 * w + 1] = mask ? w * kWave + (__ffsll((unsigned long long)mask) - 1) : -1;  // and first
+    }
+    __syncthreads();
+    int latest = upto ? w * kWave + (kWave - 1 - __clzll((long long)upto)) : -1, fst = -1;
+    for (int q = 0; q < nw && fst < 0; ++q) fst = sh[2 * q + 1];
+    for (int q = w - 1; q >= 0 && latest < 0; --q) latest = sh[2 * q];
+    __syncthreads();
+    *first = fst;
+    return latest;
+}
+
 // the halving tree a[i] += a[i + s], s = NT / 2 .. 1 over the block's NT = 256 threads -- LDS for s = 128, 64, lane shuffles of
 // wave 0 below -- into part[c * P + seg]
 template <int NS, int NT>

@@ -977,6 +977,73 @@ int gpis_traj_device(void* traj, const float** d_x, const float** d_fres, const 
     return GPIS_OK;
 }
 
+// ---- time parametrisation of trajectories, control sequences, the controller's nominal sequence ------------------------------
+int gpis_timing_default_opts(int dim, float step, gpis_traj_timing_opts* o) {
+    if (!o || (dim != 2 && dim != 3) || !(std::isfinite(step) && step > 0.f)) return GPIS_ERR_ARG;
+    o->v_max = 1.f; o->v_min = 0.05f; o->a_max = 0.5f; o->d_max = 0.5f; o->a_lat = 0.5f; o->w_max = 1.f; o->v_start = 0.f;
+    o->v_end = 0.f; o->clearance = step; o->slow_dist = 4.f * step;
+    return GPIS_OK;
+}
+// The options and the handles' states are checked before anything is dropped, so such an error leaves the previous timing
+// readable; a failure after that leaves the result without a timing.
+int gpis_timing_time(void* traj, void* d, const gpis_traj_timing_opts* opts, void* stream) {
+    if (!traj || !opts) return GPIS_ERR_ARG;
+    Trajectories& t = *(Trajectories*)traj;
+    TimingOpts o;
+    o.v_max = opts->v_max; o.v_min = opts->v_min; o.a_max = opts->a_max; o.d_max = opts->d_max; o.a_lat = opts->a_lat;
+    o.w_max = opts->w_max; o.v_start = opts->v_start; o.v_end = opts->v_end; o.clearance = opts->clearance; o.slow_dist = opts->slow_dist;
+    DeviceScope ds(t.device);
+    try { return t.time((const DistanceField*)d, o, (hipStream_t)stream); } catch (...) { t.timed = false; return GPIS_ERR_STATE; }
+}
+int gpis_timing_info(void* traj, double* out, int n) {
+    if (!traj || !out || n < 0) return GPIS_ERR_ARG;
+    const Trajectories& t = *(const Trajectories*)traj;
+    const bool h = t.has_timing();
+    const double w[3] = {h ? 1.0 : 0.0, h ? t.time_ms : 0.0, h ? t.controls_ms : 0.0};
+    for (int i = 0; i < n && i < 3; ++i) out[i] = w[i];
+    return GPIS_OK;
+}
+int gpis_timing_get(void* traj, float* v, float* t_out, unsigned char* limiter, unsigned char* status, float* duration,
+                    float* max_speed, float* max_curvature, int* limiter_counts) {
+    if (!traj) return GPIS_ERR_ARG;
+    Trajectories& t = *(Trajectories*)traj;
+    if (!t.has_timing()) return GPIS_ERR_STATE;
+    DeviceScope ds(t.device);
+    const size_t m = (size_t)t.m, mn = m * t.N;
+    std::vector<float> fr;
+    if (v) GPIS_HIP(hipMemcpyAsync(v, t.d_tv, sizeof(float) * mn, hipMemcpyDeviceToHost, t.own));
+    if (t_out) GPIS_HIP(hipMemcpyAsync(t_out, t.d_tt, sizeof(float) * mn, hipMemcpyDeviceToHost, t.own));
+    if (limiter) GPIS_HIP(hipMemcpyAsync(limiter, t.d_lim, mn, hipMemcpyDeviceToHost, t.own));
+    if (duration || max_speed || max_curvature) {
+        fr.resize(3 * m);
+        GPIS_HIP(hipMemcpyAsync(fr.data(), t.d_tsum, sizeof(float) * 3 * m, hipMemcpyDeviceToHost, t.own));
+    }
+    GPIS_HIP(hipStreamSynchronize(t.own));
+    for (size_t k = 0; k < m; ++k) {
+        if (duration) duration[k] = fr[3 * k];
+        if (max_speed) max_speed[k] = fr[3 * k + 1];
+        if (max_curvature) max_curvature[k] = fr[3 * k + 2];
+        if (status) status[k] = (unsigned char)t.h_tint[9 * k];
+        if (limiter_counts) for (int c = 0; c < 8; ++c) limiter_counts[8 * k + c] = t.h_tint[9 * k + 1 + c];
+    }
+    return GPIS_OK;
+}
+int gpis_timing_controls(void* traj, double dt, int T, double t0, double w_limit, double min_move, double* U, double* heading0,
+                         double* p0, int* clamped) {
+    if (!traj) return GPIS_ERR_ARG;
+    Trajectories& t = *(Trajectories*)traj;
+    DeviceScope ds(t.device);
+    try { return t.controls(dt, T, t0, w_limit, min_move, U, heading0, p0, clamped); } catch (...) { return GPIS_ERR_STATE; }
+}
+int gpis_timing_follow(void* mppi, void* traj, int index, double dt, double t0, double w_limit, double min_move, double* heading0,
+                       double* p0) {
+    if (!mppi || !traj) return GPIS_ERR_ARG;
+    Controller& c = *(Controller*)mppi;
+    Trajectories& t = *(Trajectories*)traj;
+    DeviceScope ds(t.device);
+    try { return t.follow(c, index, dt, t0, w_limit, min_move, heading0, p0); } catch (...) { return GPIS_ERR_STATE; }
+}
+
 // ---- rendering ---------------------------------------------------------------------------------------------------------
 static RenderOpts render_opts(const gpis_render_opts* o) {
     RenderOpts r;

@@ -4,8 +4,12 @@
 // region) and an evaluation pass that doubles as a collision check.  float32, no FMA; every sum has one order, so the bits are
 // those of tests/traj_ref.py.  One workgroup per trajectory, every iteration inside one launch.  The optimiser keeps its input and
 // its result apart: a call always starts from the input, and a result outlives the field and the planner it came from.
+// On top of a result: speeds and times under speed and acceleration limits, control sequences of the sampling
+// controller's model through the timed positions, and one of them written into a controller's nominal sequence on the device;
+// the bits are those of tests/timing_ref.py.
 #pragma once
 #include <cstdint>
+#include <vector>
 #include "dev_common.h"
 
 namespace gpis {
@@ -18,8 +22,17 @@ struct TrajOpts {
     int iters = 0, sub = 0;
 };
 
+// the limits of the time parametrisation
+struct TimingOpts {
+    float v_max = 1.f, v_min = 1.f, a_max = 1.f, d_max = 1.f, a_lat = 0.f, w_max = 0.f, v_start = 0.f, v_end = 0.f, clearance = 0.f,
+          slow_dist = 0.f;
+};
+
+struct Controller;
+
 struct Trajectories {
     static constexpr int kMinN = 3, kMaxN = 256;     // waypoints per trajectory (the reduction tree's width)
+    static constexpr int kMaxT = 256;                // steps of a control sequence (the controller's horizon limit)
     static constexpr int kMaxSub = 16;               // evaluation points inside a segment
     static constexpr int kMaxTraj = 1 << 20;
 
@@ -36,9 +49,25 @@ struct Trajectories {
     size_t cap_m = 0;
     float* d_arc = nullptr; size_t cap_arc = 0;      // cumulative lengths, one float per path point
 
+    // the timing of the last result (§7p), dropped wherever the result is
+    float* d_tv = nullptr;                           // [m][N] speeds
+    float* d_tt = nullptr;                           // [m][N] times
+    unsigned char* d_lim = nullptr;                  // [m][N] limiter codes
+    size_t cap_tn = 0;
+    float* d_tsum = nullptr;                         // [m][3] duration, max speed, max curvature
+    int* d_tint = nullptr;                           // [m][9] timing status, waypoints per limiter code
+    size_t cap_tm = 0;
+    std::vector<int> h_tint;                         // d_tint's host copy
+    // the last control sequences
+    double* d_cu = nullptr; size_t cap_cu = 0;       // [m][T][nu]
+    double* d_chp = nullptr;                         // [m][5] heading0, p_0
+    int* d_cclamp = nullptr;                         // [m] clamped steps
+    size_t cap_cm = 0;
+    double* d_follow = nullptr;                      // [8] heading0, p_0 and the clamped count of the last follow()
+
     int m = 0, N = 0, dim = 0;
-    bool has_input = false, valid = false;
-    double opt_ms = 0.0;
+    bool has_input = false, valid = false, timed = false;
+    double opt_ms = 0.0, time_ms = 0.0, controls_ms = 0.0;
 
     Trajectories();
     ~Trajectories();
@@ -49,6 +78,14 @@ struct Trajectories {
     int set(const float* x, int m, int N, int dim);
     // descent and evaluation from the input on df's dist; synchronises `s`
     int optimize(const DistanceField& df, const TrajOpts& o, hipStream_t s);
+    // speeds, times and limiter codes of the last result; df: nullptr or a field on this device; s: nullptr for the field's
+    // (the own) stream; synchronises it
+    int time(const DistanceField* df, const TimingOpts& o, hipStream_t s);
+    bool has_timing() const { return valid && timed; }
+    // control sequences of T steps for every timed trajectory; host outputs, any may be nullptr; synchronises the own stream
+    int controls(double dt, int T, double t0, double w_limit, double min_move, double* U, double* heading0, double* p0, int* clamped);
+    // the sequence of trajectory `index` with the controller's T into the current half of its nominal sequence
+    int follow(Controller& c, int index, double dt, double t0, double w_limit, double min_move, double* heading0, double* p0);
 
 private:
     int ensure(int m, int N, int dim);
@@ -56,5 +93,9 @@ private:
 
 // GPIS_ERR_ARG on anything gpis_traj_optimize documents as an argument error of the options
 int traj_check_opts(const TrajOpts& o);
+// GPIS_ERR_ARG on anything gpis_timing_time documents as an argument error of the limits
+int timing_check_opts(const TimingOpts& o);
+// GPIS_ERR_ARG unless dt > 0, 1 <= T <= 256, t0 >= 0, w_limit >= 0, min_move >= 0, all finite
+int timing_check_args(double dt, int T, double t0, double w_limit, double min_move);
 
 }  // namespace gpis

@@ -6,11 +6,17 @@
 // of inverse(tridiag(-1, 2, -1)) times g accumulated in registers over ascending j with g_j a broadcast LDS read, the largest
 // step by a wavefront reduction (a max is exact in any order), the trust region, the update.  Sums of the evaluation use one
 // fixed tree over 256 slots.  No floating-point atomics; -ffp-contract=off keeps every product and sum apart.
+//
+// Time parametrisation of the last result and the control sequences it gives follow below: the same layout (a
+// workgroup per trajectory, a lane per waypoint or per step), prefixes summed ascending by each lane, the speed profile as a
+// minimum over cones.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
 #include <vector>
 #include "traj.h"
+#include "block_ops.h"
+#include "mppi.h"
 #include "dfield.h"
 #include "plan.h"
 
@@ -260,6 +266,262 @@ __global__ void __launch_bounds__(kBlock) traj_opt_kernel(const float* __restric
     }
 }
 
+// ---- time parametrisation --------------------------------------------------------------------------------------
+struct OpMaxNan { __device__ float operator()(float a, float b) const { return traj_max(a, b); } };
+
+// One workgroup per trajectory, blockDim.x = 64 ceil(N / 64), lane i = waypoint i (and segment i -> i + 1).  ds, S, L, the
+// speeds and dt live in LDS; a lane sums its own prefix over ascending j and takes its own row of the envelope, every operand
+// a broadcast LDS read.  tsum[t] = duration, max speed, max curvature; tint[t] = status, waypoints per limiter code.
+template <int DIM>
+__global__ void __launch_bounds__(kBlock) traj_time_kernel(const float* __restrict__ F, DfLattice L, int use_field,
+                                                           const float* __restrict__ x, const int* __restrict__ ires, int N,
+                                                           TimingOpts o, float* __restrict__ vout, float* __restrict__ tout,
+                                                           unsigned char* __restrict__ lim, float* __restrict__ tsum,
+                                                           int* __restrict__ tint) {
+    __shared__ float sx[DIM][kTree];
+    __shared__ float sds[kTree], sS[kTree], sL[kTree], sv[kTree], sdt[kTree];
+    __shared__ unsigned char scode[kTree];
+    __shared__ float swf[kBlock / 64];
+    __shared__ int swi[kBlock / 64];
+    const int tr = blockIdx.x, t = threadIdx.x, nthr = blockDim.x;
+    const size_t base = (size_t)tr * N;
+    const float nan = __int_as_float(0x7fc00000);
+
+    if (ires[(size_t)tr * 4] == 2) {                     // no input
+        if (t < N) { vout[base + t] = nan; tout[base + t] = nan; lim[base + t] = 0; }
+        if (t < 3) tsum[(size_t)tr * 3 + t] = nan;
+        if (t < 9) tint[(size_t)tr * 9 + t] = t == 0 ? 2 : 0;
+        return;
+    }
+
+    if (t < N) {
+#pragma unroll
+        for (int a = 0; a < DIM; ++a) sx[a][t] = x[(base + t) * DIM + a];
+    }
+    __syncthreads();
+    float ds = 0.f;
+    if (t <= N - 2) {
+        float sq = 0.f;
+#pragma unroll
+        for (int a = 0; a < DIM; ++a) {
+            const float d = sx[a][t + 1] - sx[a][t];
+            sq = a ? sq + d * d : d * d;
+        }
+        ds = sqrtf(sq);
+    }
+    sds[t] = ds;
+    __syncthreads();
+
+    const bool interior = t >= 1 && t <= N - 2;
+    float S = 0.f, kappa = 0.f;
+    if (t < N)
+        for (int j = 0; j < t; ++j) S = S + sds[j];
+    sS[t] = S;
+    if (interior) {
+        float a[DIM], b[DIM], sq = 0.f;
+#pragma unroll
+        for (int k = 0; k < DIM; ++k) {
+            a[k] = sx[k][t] - sx[k][t - 1];
+            b[k] = sx[k][t + 1] - sx[k][t];
+            const float c = sx[k][t + 1] - sx[k][t - 1];
+            sq = k ? sq + c * c : c * c;
+        }
+        float cr;
+        if (DIM == 2) cr = fabsf(a[0] * b[1] - a[1] * b[0]);
+        else {
+            const float cx = a[1] * b[DIM - 1] - a[DIM - 1] * b[1], cy = a[DIM - 1] * b[0] - a[0] * b[DIM - 1],
+                        cz = a[0] * b[1] - a[1] * b[0];
+            cr = sqrtf((cx * cx + cy * cy) + cz * cz);
+        }
+        const float num = 2.f * cr, den = (sds[t - 1] * ds) * sqrtf(sq);
+        kappa = den == 0.f ? 0.f : num / den;
+    }
+    float Li = o.v_max * o.v_max;
+    int code = 0;
+    if (t < N) {
+        if (kappa != 0.f) {
+            if (o.a_lat > 0.f) { const float c = o.a_lat / kappa; if (c < Li) { Li = c; code = 1; } }
+            if (o.w_max > 0.f) { const float q = o.w_max / kappa, c = q * q; if (c < Li) { Li = c; code = 2; } }
+        }
+        if (use_field && o.slow_dist > 0.f) {
+            float xi[DIM];
+#pragma unroll
+            for (int a = 0; a < DIM; ++a) xi[a] = sx[a][t];
+            const float d = traj_sample<DIM>(F, L, xi).d;
+            if (isfinite(d)) {
+                const float e = d - o.clearance;
+                const float vs = e <= 0.f ? o.v_min : o.v_min + (o.v_max - o.v_min) * fminf(e / o.slow_dist, 1.f);
+                const float c = vs * vs;
+                if (c < Li) { Li = c; code = 3; }
+            }
+        }
+        if (interior && Li < o.v_min * o.v_min) { Li = o.v_min * o.v_min; code = 4; }
+        if (t == 0) { const float c = o.v_start * o.v_start; if (c < Li) { Li = c; code = 5; } }
+        if (t == N - 1) { const float c = o.v_end * o.v_end; if (c < Li) { Li = c; code = 5; } }
+    }
+    sL[t] = Li;
+    __syncthreads();
+
+    // the own row of the lower envelope: a minimum, so the order of j is free; the code is the own limit's unless a cone is
+    // strictly below it, the acceleration cones (j < i) before the braking cones
+    const float ta = 2.f * o.a_max, td = 2.f * o.d_max;
+    float u = Li;
+    if (t < N) {
+        for (int j = 0; j < N; ++j) {
+            const float c = j < t ? sL[j] + ta * (S - sS[j]) : sL[j] + td * (sS[j] - S);
+            if (j != t && c < u) { u = c; code = j < t ? 6 : 7; }
+        }
+    }
+    const float v = t < N ? sqrtf(u) : 0.f;
+    sv[t] = v;
+    scode[t] = (unsigned char)code;
+    __syncthreads();
+    float dt = 0.f;
+    if (t <= N - 2 && ds != 0.f) dt = (2.f * ds) / (v + sv[t + 1]);
+    sdt[t] = dt;
+    __syncthreads();
+    float tm = 0.f;
+    if (t < N) {
+        for (int j = 0; j < t; ++j) tm = tm + sdt[j];
+        vout[base + t] = v; tout[base + t] = tm; lim[base + t] = (unsigned char)code;
+    }
+    const float vmax = block_reduce(v, OpMaxNan(), swf, nthr, 0.f);
+    const float kmax = block_reduce(kappa, OpMaxNan(), swf, nthr, 0.f);
+    const int bad = block_reduce(isfinite(dt) ? 0 : 1, OpMax(), swi, nthr, 0);
+    if (t == 0) {
+        tsum[(size_t)tr * 3 + 1] = vmax; tsum[(size_t)tr * 3 + 2] = kmax;
+        tint[(size_t)tr * 9] = bad ? 3 : 0;
+    }
+    if (t == N - 1) tsum[(size_t)tr * 3] = tm;
+    if (t < 8) {
+        int cnt = 0;
+        for (int j = 0; j < N; ++j) cnt += scode[j] == t ? 1 : 0;
+        tint[(size_t)tr * 9 + 1 + t] = cnt;
+    }
+}
+
+// The timed position at tau: the last waypoint from the duration on, else the segment by bisection (the largest i <= N - 2 with
+// t_i <= tau) and the distance along it under constant acceleration.
+template <int DIM>
+__device__ __forceinline__ void traj_position(const float* __restrict__ x, const float* __restrict__ v, const float* st, int N,
+                                              double tau, double* p) {
+    if (tau >= (double)st[N - 1]) {
+#pragma unroll
+        for (int a = 0; a < DIM; ++a) p[a] = (double)x[(size_t)(N - 1) * DIM + a];
+        return;
+    }
+    int lo = 0, hi = N - 2;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if ((double)st[mid] <= tau) lo = mid; else hi = mid - 1;
+    }
+    const double ti = (double)st[lo], h = (double)st[lo + 1] - ti, e = tau - ti, vi = (double)v[lo];
+    const double acc = ((double)v[lo + 1] - vi) / h;
+    const double s = vi * e + ((0.5 * acc) * e) * e;
+    double d[DIM], x0[DIM], sq = 0.0;
+#pragma unroll
+    for (int a = 0; a < DIM; ++a) {
+        x0[a] = (double)x[(size_t)lo * DIM + a];
+        d[a] = (double)x[(size_t)(lo + 1) * DIM + a] - x0[a];
+        sq = a ? sq + d[a] * d[a] : d[a] * d[a];
+    }
+    double w = s / sqrt(sq);
+    w = w > 0.0 ? w : 0.0;
+    w = w < 1.0 ? w : 1.0;
+#pragma unroll
+    for (int a = 0; a < DIM; ++a) p[a] = x0[a] + w * d[a];
+}
+
+// One workgroup per trajectory (first + blockIdx.x), blockDim.x = 64 ceil(T / 64), thread k = step k: its two timed positions,
+// the displacement, the heading of the latest moving step by an integer max-scan, the controls.  U[blockIdx.x][T][nu],
+// hp[blockIdx.x][5] = heading0, p_0, clamped[blockIdx.x].  Double, nothing contracted.
+template <int DIM>
+__global__ void __launch_bounds__(kBlock) traj_controls_kernel(const float* __restrict__ x, const float* __restrict__ v,
+                                                               const float* __restrict__ tt, const int* __restrict__ tint, int N,
+                                                               int T, int first, double dt, double t0, double w_limit,
+                                                               double min_move, double* __restrict__ U, double* __restrict__ hp,
+                                                               int* __restrict__ clamped) {
+    constexpr int NU = DIM == 3 ? 4 : 2;
+    __shared__ float st[kTree];
+    __shared__ double sh[2][kTree];
+    __shared__ int swi[2 * (kBlock / 64)];
+    __shared__ int sidx[kTree];
+    const int tr = first + blockIdx.x, k = threadIdx.x, nthr = blockDim.x;
+    const size_t base = (size_t)tr * N;
+    double* Uo = U + (size_t)blockIdx.x * T * NU;
+    double* hpo = hp + (size_t)blockIdx.x * 5;
+
+    if (tint[(size_t)tr * 9] != 0) {                     // not timed: stand still
+        if (k < T) {
+#pragma unroll
+            for (int u = 0; u < NU; ++u) Uo[(size_t)k * NU + u] = 0.0;
+        }
+        if (k == 0) {
+            hpo[0] = 1.0; hpo[1] = 0.0;
+#pragma unroll
+            for (int a = 0; a < DIM; ++a) hpo[2 + a] = (double)x[base * DIM + a];
+            if (DIM == 2) hpo[4] = 0.0;
+            clamped[blockIdx.x] = 0;
+        }
+        return;
+    }
+    for (int i = k; i < N; i += nthr) st[i] = tt[base + i];
+    __syncthreads();
+
+    double p[DIM], D[DIM];
+    double n = 0.0;
+    bool mov = false;
+#pragma unroll
+    for (int a = 0; a < DIM; ++a) { p[a] = 0.0; D[a] = 0.0; }
+    if (k < T) {
+        double q[DIM];
+        traj_position<DIM>(x + base * DIM, v + base, st, N, t0 + (double)k * dt, p);
+        traj_position<DIM>(x + base * DIM, v + base, st, N, t0 + (double)(k + 1) * dt, q);
+#pragma unroll
+        for (int a = 0; a < DIM; ++a) D[a] = q[a] - p[a];
+        n = sqrt(D[0] * D[0] + D[1] * D[1]);
+        mov = n > min_move;
+    }
+    if (mov) { sh[0][k] = D[0] / n; sh[1][k] = D[1] / n; }
+    int fst;
+    int last = block_latest_flag(mov, swi, nthr, &fst);  // (its barriers publish sh)
+    if (last < 0) last = fst;
+    sidx[k] = last;
+    __syncthreads();
+    int cl = 0;
+    if (k < T) {
+        const int nxt = k + 1 < T ? sidx[k + 1] : last;  // h_T = h_{T-1}
+        double c = 1.0, s = 0.0, c1 = 1.0, s1 = 0.0;
+        if (last >= 0) { c = sh[0][last]; s = sh[1][last]; }
+        if (nxt >= 0) { c1 = sh[0][nxt]; s1 = sh[1][nxt]; }
+        double* u = Uo + (size_t)k * NU;
+        u[0] = (c * D[0] + s * D[1]) / dt;
+        if (DIM == 3) {
+            u[1] = ((-s) * D[0] + c * D[1]) / dt;
+            u[2] = D[DIM - 1] / dt;
+        }
+        const double num = c * s1 - s * c1, den = 1.0 + (c * c1 + s * s1);
+        double w;
+        if (den <= 0.0) {
+            w = w_limit > 0.0 ? (num >= 0.0 ? w_limit : -w_limit) : 0.0;
+            cl = 1;
+        } else {
+            w = (num / den) / (0.5 * dt);
+            if (w_limit > 0.0 && w > w_limit) { w = w_limit; cl = 1; }
+            else if (w_limit > 0.0 && w < -w_limit) { w = -w_limit; cl = 1; }
+        }
+        u[NU - 1] = w;
+        if (k == 0) {
+            hpo[0] = c; hpo[1] = s;
+#pragma unroll
+            for (int a = 0; a < DIM; ++a) hpo[2 + a] = p[a];
+            if (DIM == 2) hpo[4] = 0.0;
+        }
+    }
+    const int total = block_reduce(cl, OpAdd(), swi, nthr, 0);
+    if (k == 0) clamped[blockIdx.x] = total;
+}
+
 }  // namespace
 
 int traj_check_opts(const TrajOpts& o) {
@@ -297,12 +559,15 @@ int Trajectories::bind(int dev) {
                 hipMemcpy(hs.data(), d_instat, hs.size(), hipMemcpyDeviceToHost) != hipSuccess)
                 rc = GPIS_ERR_HIP;
         }
-        for (void* p : {(void*)d_in, (void*)d_x, (void*)d_instat, (void*)d_fres, (void*)d_ires, (void*)d_arc}) (void)hipFree(p);
+        for (void* p : {(void*)d_in, (void*)d_x, (void*)d_instat, (void*)d_fres, (void*)d_ires, (void*)d_arc, (void*)d_tv, (void*)d_tt,
+                        (void*)d_lim, (void*)d_tsum, (void*)d_tint, (void*)d_cu, (void*)d_chp, (void*)d_cclamp, (void*)d_follow})
+            (void)hipFree(p);
         if (own) (void)hipStreamDestroy(own);
     }
     d_in = d_x = d_fres = d_arc = nullptr; d_instat = nullptr; d_ires = nullptr; own = nullptr;
-    cap_x = cap_m = cap_arc = 0;
-    has_input = valid = false;
+    d_tv = d_tt = d_tsum = nullptr; d_lim = nullptr; d_tint = nullptr; d_cu = d_chp = d_follow = nullptr; d_cclamp = nullptr;
+    cap_x = cap_m = cap_arc = cap_tn = cap_tm = cap_cu = cap_cm = 0;
+    has_input = valid = timed = false;
     m = N = dim = 0;
     device = dev;
     if (dev < 0) return GPIS_OK;
@@ -343,7 +608,7 @@ int Trajectories::from_paths(const Planner& p, int NN) {
     if (NN < kMinN || NN > kMaxN) return GPIS_ERR_ARG;
     if (!p.valid || !p.paths_valid) return GPIS_ERR_STATE;
     if (p.npaths > kMaxTraj) return GPIS_ERR_LIMIT;
-    has_input = valid = false;
+    has_input = valid = timed = false;
     if (int rc = bind(p.device)) return rc;
     const int mm = (int)p.npaths;
     if (int rc = ensure(mm, NN, p.dim)) return rc;
@@ -363,7 +628,7 @@ int Trajectories::from_paths(const Planner& p, int NN) {
 int Trajectories::set(const float* x, int mm, int NN, int dd) {
     if (!x || mm < 1 || NN < kMinN || NN > kMaxN || (dd != 2 && dd != 3)) return GPIS_ERR_ARG;
     if (mm > kMaxTraj) return GPIS_ERR_LIMIT;
-    has_input = valid = false;
+    has_input = valid = timed = false;
     if (int rc = ensure(mm, NN, dd)) return rc;
     const size_t per = (size_t)NN * dd;
     std::vector<unsigned char> st((size_t)mm, 0);
@@ -383,7 +648,7 @@ int Trajectories::optimize(const DistanceField& df, const TrajOpts& o, hipStream
     if (!df.valid || !has_input) return GPIS_ERR_STATE;
     if (df.dim != dim) return GPIS_ERR_ARG;
     const auto t0 = std::chrono::steady_clock::now();
-    valid = false;
+    valid = timed = false;
     if (int rc = bind(df.device)) return rc;
     const DfLattice L = df.lattice();
     const int threads = 64 * ((N + 63) / 64);
@@ -397,6 +662,130 @@ int Trajectories::optimize(const DistanceField& df, const TrajOpts& o, hipStream
     GPIS_HIP(hipStreamSynchronize(s));
     opt_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     valid = true;
+    return GPIS_OK;
+}
+
+// ---- time parametrisation and control sequences ---------------------------------------------------------------
+int timing_check_opts(const TimingOpts& o) {
+    for (float v : {o.v_max, o.v_min, o.a_max, o.d_max, o.a_lat, o.w_max, o.v_start, o.v_end, o.clearance, o.slow_dist})
+        if (!std::isfinite(v)) return GPIS_ERR_ARG;
+    if (!(o.v_max > 0.f) || !(o.v_min > 0.f && o.v_min <= o.v_max) || !(o.a_max > 0.f) || !(o.d_max > 0.f)) return GPIS_ERR_ARG;
+    if (o.a_lat < 0.f || o.w_max < 0.f || o.v_start < 0.f || o.v_end < 0.f || o.slow_dist < 0.f) return GPIS_ERR_ARG;
+    return GPIS_OK;
+}
+
+int timing_check_args(double dt, int T, double t0, double w_limit, double min_move) {
+    if (!std::isfinite(dt) || !std::isfinite(t0) || !std::isfinite(w_limit) || !std::isfinite(min_move)) return GPIS_ERR_ARG;
+    if (!(dt > 0.0) || T < 1 || T > Trajectories::kMaxT || t0 < 0.0 || w_limit < 0.0 || min_move < 0.0) return GPIS_ERR_ARG;
+    return GPIS_OK;
+}
+
+int Trajectories::time(const DistanceField* df, const TimingOpts& o, hipStream_t s) {
+    if (int rc = timing_check_opts(o)) return rc;
+    if (!valid) return GPIS_ERR_STATE;
+    if (df) {
+        if (!df->valid) return GPIS_ERR_STATE;
+        if (df->dim != dim || df->device != device) return GPIS_ERR_ARG;
+    }
+    const auto t0 = std::chrono::steady_clock::now();
+    if (!s) s = df ? df->own : own;
+    timed = false;
+    // (the layout follows the current m and N; the capacities only ever say how much is allocated)
+    const size_t mn = (size_t)m * N;
+    if (mn > cap_tn) {
+        for (void* p : {(void*)d_tv, (void*)d_tt, (void*)d_lim}) (void)hipFree(p);
+        d_tv = d_tt = nullptr; d_lim = nullptr; cap_tn = 0;
+        GPIS_HIP(hipMalloc((void**)&d_tv, sizeof(float) * mn));
+        GPIS_HIP(hipMalloc((void**)&d_tt, sizeof(float) * mn));
+        GPIS_HIP(hipMalloc((void**)&d_lim, mn));
+        cap_tn = mn;
+    }
+    if ((size_t)m > cap_tm) {
+        (void)hipFree(d_tsum); (void)hipFree(d_tint);
+        d_tsum = nullptr; d_tint = nullptr; cap_tm = 0;
+        GPIS_HIP(hipMalloc((void**)&d_tsum, sizeof(float) * 3 * (size_t)m));
+        GPIS_HIP(hipMalloc((void**)&d_tint, sizeof(int) * 9 * (size_t)m));
+        cap_tm = (size_t)m;
+    }
+    DfLattice L{};
+    if (df) L = df->lattice();
+    const float* F = df ? df->d_dist : nullptr;
+    const int threads = 64 * ((N + 63) / 64);
+    if (dim == 2)
+        hipLaunchKernelGGL(traj_time_kernel<2>, dim3((unsigned)m), dim3(threads), 0, s, F, L, df ? 1 : 0, d_x, d_ires, N, o, d_tv, d_tt,
+                           d_lim, d_tsum, d_tint);
+    else
+        hipLaunchKernelGGL(traj_time_kernel<3>, dim3((unsigned)m), dim3(threads), 0, s, F, L, df ? 1 : 0, d_x, d_ires, N, o, d_tv, d_tt,
+                           d_lim, d_tsum, d_tint);
+    GPIS_HIP(hipGetLastError());
+    h_tint.resize(9 * (size_t)m);
+    GPIS_HIP(hipMemcpyAsync(h_tint.data(), d_tint, sizeof(int) * 9 * (size_t)m, hipMemcpyDeviceToHost, s));
+    GPIS_HIP(hipStreamSynchronize(s));
+    time_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    timed = true;
+    return GPIS_OK;
+}
+
+int Trajectories::controls(double dt, int T, double t0, double w_limit, double min_move, double* U, double* heading0, double* p0,
+                           int* clamped) {
+    if (int rc = timing_check_args(dt, T, t0, w_limit, min_move)) return rc;
+    if (!has_timing()) return GPIS_ERR_STATE;
+    const auto c0 = std::chrono::steady_clock::now();
+    const int nu = dim == 3 ? 4 : 2;
+    if (int rc = grow(d_cu, cap_cu, (size_t)m * T * nu)) return rc;
+    if ((size_t)m > cap_cm) {
+        (void)hipFree(d_chp); (void)hipFree(d_cclamp);
+        d_chp = nullptr; d_cclamp = nullptr; cap_cm = 0;
+        GPIS_HIP(hipMalloc((void**)&d_chp, sizeof(double) * 5 * (size_t)m));
+        GPIS_HIP(hipMalloc((void**)&d_cclamp, sizeof(int) * (size_t)m));
+        cap_cm = (size_t)m;
+    }
+    const int threads = 64 * ((T + 63) / 64);
+    if (dim == 2)
+        hipLaunchKernelGGL(traj_controls_kernel<2>, dim3((unsigned)m), dim3(threads), 0, own, d_x, d_tv, d_tt, d_tint, N, T, 0, dt, t0,
+                           w_limit, min_move, d_cu, d_chp, d_cclamp);
+    else
+        hipLaunchKernelGGL(traj_controls_kernel<3>, dim3((unsigned)m), dim3(threads), 0, own, d_x, d_tv, d_tt, d_tint, N, T, 0, dt, t0,
+                           w_limit, min_move, d_cu, d_chp, d_cclamp);
+    GPIS_HIP(hipGetLastError());
+    std::vector<double> hp;
+    if (U) GPIS_HIP(hipMemcpyAsync(U, d_cu, sizeof(double) * (size_t)m * T * nu, hipMemcpyDeviceToHost, own));
+    if (heading0 || p0) {
+        hp.resize(5 * (size_t)m);
+        GPIS_HIP(hipMemcpyAsync(hp.data(), d_chp, sizeof(double) * hp.size(), hipMemcpyDeviceToHost, own));
+    }
+    if (clamped) GPIS_HIP(hipMemcpyAsync(clamped, d_cclamp, sizeof(int) * (size_t)m, hipMemcpyDeviceToHost, own));
+    GPIS_HIP(hipStreamSynchronize(own));
+    for (size_t r = 0; r < (size_t)m && !hp.empty(); ++r) {
+        if (heading0) { heading0[2 * r] = hp[5 * r]; heading0[2 * r + 1] = hp[5 * r + 1]; }
+        if (p0) for (int a = 0; a < dim; ++a) p0[r * dim + a] = hp[5 * r + 2 + a];
+    }
+    controls_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - c0).count();
+    return GPIS_OK;
+}
+
+int Trajectories::follow(Controller& c, int index, double dt, double t0, double w_limit, double min_move, double* heading0,
+                         double* p0) {
+    if (!c.inited || !has_timing()) return GPIS_ERR_STATE;
+    if (int rc = timing_check_args(dt, c.T, t0, w_limit, min_move)) return rc;
+    if (c.dim != dim || c.device != device || index < 0 || index >= m) return GPIS_ERR_ARG;
+    if (h_tint[9 * (size_t)index] != 0) return GPIS_ERR_STATE;
+    if (!d_follow) GPIS_HIP(hipMalloc((void**)&d_follow, sizeof(double) * 8));
+    // (the own stream's work is finished: time() synchronised; the controller's stream orders the write with its steps)
+    const int threads = 64 * ((c.T + 63) / 64);
+    int* d_cl = (int*)(d_follow + 6);
+    if (dim == 2)
+        hipLaunchKernelGGL(traj_controls_kernel<2>, dim3(1), dim3(threads), 0, c.own, d_x, d_tv, d_tt, d_tint, N, c.T, index, dt, t0,
+                           w_limit, min_move, c.d_U[c.cur], d_follow, d_cl);
+    else
+        hipLaunchKernelGGL(traj_controls_kernel<3>, dim3(1), dim3(threads), 0, c.own, d_x, d_tv, d_tt, d_tint, N, c.T, index, dt, t0,
+                           w_limit, min_move, c.d_U[c.cur], d_follow, d_cl);
+    GPIS_HIP(hipGetLastError());
+    double hp[5];
+    GPIS_HIP(hipMemcpyAsync(hp, d_follow, sizeof(hp), hipMemcpyDeviceToHost, c.own));
+    GPIS_HIP(hipStreamSynchronize(c.own));
+    if (heading0) { heading0[0] = hp[0]; heading0[1] = hp[1]; }
+    if (p0) for (int a = 0; a < dim; ++a) p0[a] = hp[2 + a];
     return GPIS_OK;
 }
 

@@ -690,6 +690,77 @@ int   gpis_traj_get(void* traj, float* x, unsigned char* status, int* iterations
  * d_x[m][N][dim]; d_fres[m][4] = length, smooth, obstacle, min_dist; d_ires[m][4] = status, iterations, nonfinite, collides */
 int   gpis_traj_device(void* traj, const float** d_x, const float** d_fres, const int** d_ires);
 
+/* ---- timing: speeds and times on a trajectory handle's last result, control sequences, the controller's seed --
+ * The stage between the trajectories above and the sampling controller below.  (The entries are gpis_timing_*: the trajectory
+ * and controller sections keep their sets of entries.)  tests/timing_ref.py states every bit in numpy.
+ * gpis_timing_time works on the handle's last result (gpis_traj_optimize; iters = 0 is the cheap way to one); every trajectory
+ * of result status 0 or 1 is timed on its own, float32 without FMA, one order per sum:
+ *  - ds_i = |x_{i+1} - x_i| (sqrtf of squares summed left to right), S_0 = 0, S_i = S_{i-1} + ds_{i-1} ascending.
+ *  - Curvature at interior waypoints, a = x_i - x_{i-1}, b = x_{i+1} - x_i, c = x_{i+1} - x_{i-1}: kappa_i = (2.f * |a x b|) /
+ *    ((|a| * |b|) * |c|); a x b = |(a_0 * b_1) - (a_1 * b_0)| in 2-D, the norm of ((a_1 b_2) - (a_2 b_1), (a_2 b_0) - (a_0 b_2),
+ *    (a_0 b_1) - (a_1 b_0)) in 3-D; kappa_i = 0 where the denominator is 0 and at both ends.
+ *  - Slow-down, with a field and slow_dist > 0: d = gpis_dfield_sample's interpolant at x_i; d not finite: no limit (unknown
+ *    space is free); e = d - clearance <= 0: v_min; else v_min + (v_max - v_min) * min(e / slow_dist, 1).
+ *  - L_i, the limit on the squared speed: v_max * v_max (code 0); where kappa_i != 0: a_lat / kappa_i if a_lat > 0 (1),
+ *    (w_max / kappa_i) squared if w_max > 0 (2); the slow-down speed squared (3); each replaces L_i only where strictly
+ *    smaller, in this order.  An interior L_i < v_min * v_min becomes v_min * v_min (4).  Then L_0 takes v_start * v_start and
+ *    L_{N-1} takes v_end * v_end where strictly smaller (5).
+ *  - u_i = min over j of L_j + (2.f * a_max) * (S_i - S_j) for j < i (6), L_i, L_j + (2.f * d_max) * (S_j - S_i) for j > i (7);
+ *    v_i = sqrtf(u_i).  The limiter byte is L_i's code unless a cone is strictly below L_i; 6 unless a braking cone is strictly
+ *    below every acceleration cone.
+ *  - dt_i = 0 where ds_i = 0, else (2.f * ds_i) / (v_i + v_{i+1}); t_0 = 0, t_{i+1} = t_i + dt_i ascending.
+ *  - Timing status 0; 3 where some dt_i is not finite (a positive segment between two zero speeds; the times stay as computed);
+ *    2 for a trajectory without input: NaN v, t, duration, max_speed, max_curvature, limiter bytes and counts 0.
+ *  - duration = t_{N-1}, max_speed = max v_i, max_curvature = max kappa_i, limiter_counts[c] = waypoints of limiter code c.
+ * gpis_timing_controls and gpis_timing_follow are double, left to right, nothing contracted, IEEE / and sqrt, on the float32 x, v,
+ * t cast to double.  Per trajectory of timing status 0 and k = 0 .. T, tau_k = t0 + (double)k * dt:
+ *  - p_k = x_{N-1} if tau_k >= t_{N-1}; else i = the largest index <= N - 2 with t_i <= tau_k, h = t_{i+1} - t_i, e = tau_k - t_i,
+ *    acc = (v_{i+1} - v_i) / h, s = v_i * e + ((0.5 * acc) * e) * e, ds_i = sqrt of the squares of x_{i+1} - x_i summed left to
+ *    right, w = min(max(s / ds_i, 0), 1), p_k = x_i + w * (x_{i+1} - x_i).
+ *  - D_k = p_{k+1} - p_k, n_k = sqrt(Dx * Dx + Dy * Dy); step k moves iff n_k > min_move; h_k = (Dx / n, Dy / n) of the latest
+ *    moving step <= k, of the first moving step where there is none before, (1, 0) without a moving step; h_T = h_{T-1}.
+ *  - With (c, s) = h_k and (c', s') = h_{k+1}: dim 2: U_k = (v, w), v = (c * Dx + s * Dy) / dt; dim 3: U_k = (vx, vy, vz, w) =
+ *    ((c * Dx + s * Dy) / dt, ((-s) * Dx + c * Dy) / dt, Dz / dt).  num = c * s' - s * c', den = 1 + (c * c' + s * s');
+ *    den <= 0: w = +-w_limit by the sign of num (num >= 0: +), 0 with w_limit = 0, counted as clamped; else
+ *    w = (num / den) / (0.5 * dt), with w_limit > 0 limited to +-w_limit (counted).
+ *  - heading0 = h_0, p0 = p_0: the sequence is for a robot at p0 facing heading0.  Timing status 2 or 3: zero controls,
+ *    heading0 (1, 0), p0 = x_0, clamped 0.
+ * gpis_timing_follow computes the sequence of trajectory `index` with the controller's T straight into the controller's nominal
+ * sequence (what gpis_mppi_set_nominal sets, and nothing else of its state), on the controller's stream.
+ * Errors: a NULL handle or opts; a non-finite option; v_max, v_min, a_max or d_max <= 0; v_min > v_max; a negative a_lat, w_max,
+ * v_start, v_end or slow_dist; a field of another dim or device; dt <= 0, T outside [1, 256], t0 < 0, w_limit < 0, min_move < 0
+ * or any of them non-finite; a controller of another dim or device; index outside [0, m) -> GPIS_ERR_ARG.  No result on the
+ * handle (time), no timing (get, controls, follow), a field without a result, a controller that is not initialised, a
+ * trajectory whose timing status is not 0 (follow) -> GPIS_ERR_STATE.  All before anything is written: the previous timing,
+ * result and nominal sequence stay.  A new input or gpis_traj_optimize drops the timing with the result. */
+typedef struct gpis_traj_timing_opts {
+    float v_max;                /* speed limit; > 0 */
+    float v_min;                /* the speed curvature and clearance may slow down to; 0 < v_min <= v_max */
+    float a_max, d_max;         /* acceleration and braking limits along the path; > 0 */
+    float a_lat;                /* lateral acceleration limit; 0: off */
+    float w_max;                /* yaw rate limit; 0: off */
+    float v_start, v_end;       /* speeds at the two ends; >= 0 */
+    float clearance;            /* the distance at which the slow-down reaches v_min */
+    float slow_dist;            /* the slow-down acts where distance - clearance < slow_dist; 0: off */
+} gpis_traj_timing_opts;
+/* v_max 1, v_min 0.05, a_max 0.5, d_max 0.5, a_lat 0.5, w_max 1, v_start 0, v_end 0, clearance step, slow_dist 4 * step.
+ * dim outside {2, 3}, a step that is not finite and positive, NULL opts -> GPIS_ERR_ARG.  Needs no device. */
+int   gpis_timing_default_opts(int dim, float step, gpis_traj_timing_opts* opts);
+/* df NULL: no slow-down; hip_stream NULL: the field's own stream (the handle's without a field) */
+int   gpis_timing_time(void* traj, void* df, const gpis_traj_timing_opts* opts, void* hip_stream);
+/* out[0..n): 1 if a timing is held, ms of host wall time in the last gpis_timing_time, in the last gpis_timing_controls */
+int   gpis_timing_info(void* traj, double* out, int n);
+/* host copies of the last timing: v[m][N], t[m][N], limiter[m][N], and per trajectory status, duration, max_speed,
+ * max_curvature, limiter_counts[m][8]; any may be NULL */
+int   gpis_timing_get(void* traj, float* v, float* t, unsigned char* limiter, unsigned char* status, float* duration,
+                      float* max_speed, float* max_curvature, int* limiter_counts);
+/* U[m][T][2 or 4], heading0[m][2], p0[m][dim], clamped[m]; any may be NULL */
+int   gpis_timing_controls(void* traj, double dt, int T, double t0, double w_limit, double min_move, double* U, double* heading0,
+                           double* p0, int* clamped);
+/* heading0_out[2], p0_out[dim]; either may be NULL */
+int   gpis_timing_follow(void* mppi, void* traj, int index, double dt, double t0, double w_limit, double min_move,
+                         double* heading0_out, double* p0_out);
+
 /* ---- locating: batches of pose hypotheses scored against a distance field on the device -----------------
  * Which of these m poses explains this frame?  The measurement update of Monte-Carlo localisation, the inner loop of
  * correlative scan matching, relocalisation after the tracker lost the pose (status 2): every pose gets the truncated sum of
