@@ -60,6 +60,10 @@ class gpis_mppi_opts(C.Structure):
                 ("w_obs", C.c_double), ("w_col", C.c_double), ("w_off", C.c_double), ("w_goal", C.c_double)]
 
 
+class gpis_obst_opts(C.Structure):
+    _fields_ = [("clearance", C.c_double), ("margin", C.c_double), ("w_obs", C.c_double), ("w_col", C.c_double)]
+
+
 class gpis_plan_opts(C.Structure):
     _fields_ = [("clearance", C.c_float), ("margin", C.c_float), ("gain", C.c_float), ("connectivity", C.c_int),
                 ("max_rounds", C.c_int)]
@@ -326,6 +330,20 @@ def lib():
         L.gpis_mppi_get.argtypes = [vp, dp, dp, C.POINTER(C.c_ulonglong), ip, dp, dp]
         L.gpis_mppi_device.argtypes = [vp, C.POINTER(C.c_void_p), C.c_int]
         L.gpis_mppi_info.argtypes = [vp, dp, C.c_int]
+    if hasattr(L, "gpis_obst_create"):
+        oo = C.POINTER(gpis_obst_opts)
+        L.gpis_obst_default_opts.argtypes = [C.c_int, C.c_float, oo]
+        L.gpis_obst_create.restype = vp
+        L.gpis_obst_create.argtypes = []
+        L.gpis_obst_destroy.argtypes = [vp]
+        L.gpis_obst_set.argtypes = [vp, C.c_int, C.c_int, dp, dp, dp, d]
+        L.gpis_obst_set_opts.argtypes = [vp, oo]
+        L.gpis_obst_get.argtypes = [vp, dp, dp, dp, oo]
+        L.gpis_obst_info.argtypes = [vp, dp, C.c_int]
+        L.gpis_obst_at.argtypes = [vp, d, dp]
+        L.gpis_obst_mppi_step.argtypes = [vp, vp, vp, vp, d, dp, dp, C.POINTER(gpis_mppi_opts), dp, vp]
+        L.gpis_obst_mppi_get.argtypes = [vp, ip, dp, dp]
+        L.gpis_obst_check_timing.argtypes = [vp, vp, d, C.c_int, d, d, d, dp, dp, ip, ip, ip]
     if hasattr(L, "gpis_cover_create"):
         co, ub, ll = C.POINTER(gpis_cover_opts), C.POINTER(C.c_ubyte), C.POINTER(C.c_longlong)
         L.gpis_cover_default_opts.argtypes = [C.c_int, C.c_float, co]
@@ -1249,12 +1267,14 @@ class DistanceField:
             self._trajectories = Trajectories()
         return self._trajectories
 
-    def control(self, controller, pose, goal=None, planner=None, stream=None, **opts):
+    def control(self, controller, pose, goal=None, planner=None, stream=None, obstacles=None, t=0.0, **opts):
         """One step of a sampling Controller through this field (gpis_mppi_step): pose [t, R] as a filter's estimate returns
         it; exactly one of `goal` (a point [dim]) and `planner` (a Planner solved on this field's lattice) gives the terminal
         cost.  opts: the gpis_mppi_opts fields (`lam` for lambda; defaults for this field's step).  Returns (u0, info): the
-        first control of the new nominal sequence and dict(Jmin, best, neff, hits, nominal_cost, nominal_hits, T, Th, S2)."""
-        return controller.step(self, pose, goal=goal, planner=planner, stream=stream, **opts)
+        first control of the new nominal sequence and dict(Jmin, best, neff, hits, nominal_cost, nominal_hits, T, Th, S2).
+        obstacles: an Obstacles whose balls, moved to the absolute time t of `pose` and on from there, are charged in every
+        rollout (gpis_obst_mppi_step); None keeps the plain step."""
+        return controller.step(self, pose, goal=goal, planner=planner, stream=stream, obstacles=obstacles, t=t, **opts)
 
     def explore(self, cover, start, planner=None, out=None, unseen_dist=None, **opts):
         """Where to go next to see more: the frontiers of `cover` (a Coverage on this field's lattice), this field restricted to
@@ -1871,6 +1891,22 @@ class Trajectories:
         return U, h0, p0, cl
 
 
+    def check(self, obstacles, dt, steps, t0=0.0, t_begin=0.0, clearance=None):
+        """The timed trajectories against an Obstacles (gpis_obst_check_timing): sampled at t0 + k dt, k = 0 .. steps, trajectory
+        time 0 at the absolute time t_begin; between samples both bodies move in straight lines and the closest approach is
+        taken in continuous time.  clearance None: the set's own.  Returns dict(min_sep, min_time [m] f64, min_obstacle,
+        first_hit, collides [m] i32)."""
+        m = self.info()["m"]
+        if clearance is None:
+            clearance = obstacles.get()["opts"]["clearance"]
+        r = dict(min_sep=np.zeros(m, np.float64), min_time=np.zeros(m, np.float64), min_obstacle=np.zeros(m, np.int32),
+                 first_hit=np.zeros(m, np.int32), collides=np.zeros(m, np.int32))
+        _check(self.L.gpis_obst_check_timing(self.h, obstacles.h, float(dt), int(steps), float(t0), float(t_begin), float(clearance),
+                                             _p(r["min_sep"], C.c_double), _p(r["min_time"], C.c_double), _p(r["min_obstacle"], C.c_int),
+                                             _p(r["first_hit"], C.c_int), _p(r["collides"], C.c_int)), "gpis_obst_check_timing")
+        return r
+
+
 def timing_opts(dim, step, **opts):
     """gpis_traj_timing_opts of the library's defaults for `dim` and a field of lattice step `step` (gpis_timing_default_opts)
     with the given fields replaced."""
@@ -2208,6 +2244,87 @@ def mppi_opts(dim, step=1.0, **opts):
     return o
 
 
+def obst_opts(dim, step, **opts):
+    """gpis_obst_opts of the library's defaults for `dim` and a field of lattice step `step` (gpis_obst_default_opts) with the
+    given fields replaced."""
+    o = gpis_obst_opts()
+    _check(lib().gpis_obst_default_opts(int(dim), float(step), C.byref(o)), "gpis_obst_default_opts")
+    names = {f[0] for f in gpis_obst_opts._fields_}
+    for k, v in opts.items():
+        if k not in names:
+            raise GpisError("unknown obstacle option %r" % k)
+        setattr(o, k, float(v))
+    return o
+
+
+class Obstacles:
+    """A set of at most 256 moving balls (gpis_obst_*): centres, constant velocities and radii in double with one epoch, and the
+    cost options of their term in a Controller's rollouts.  The set may be changed or closed between any two calls that take it."""
+
+    MAX = 256
+    INFO_KEYS = ("inited", "dim", "n", "epoch", "device")
+
+    def __init__(self, dim, step, **opts):
+        """dim and the lattice step of the field give the default options (obst_opts); opts replace them."""
+        self.L = lib()
+        if not hasattr(self.L, "gpis_obst_create"):
+            raise GpisError("the native library has no moving obstacles (gpis_obst_create)")
+        if self.L.gpis_device_count() < 1:
+            raise GpisError("no HIP device: gpismap_amd has no CPU fallback")
+        self.h = C.c_void_p(self.L.gpis_obst_create())
+        if not self.h:
+            raise GpisError("gpis_obst_create failed")
+        self.dim, self.step = int(dim), float(step)
+        self.set_opts(**opts)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.gpis_obst_destroy(self.h)
+            self.h = None
+
+    __del__ = close
+
+    def set_opts(self, **opts):
+        """Replace the options by the defaults with `opts` over them."""
+        o = obst_opts(self.dim, self.step, **opts)
+        _check(self.L.gpis_obst_set_opts(self.h, C.byref(o)), "gpis_obst_set_opts")
+        return self
+
+    def set(self, centre, velocity, radius, epoch=0.0):
+        """centre, velocity [n, dim], radius [n] (n = 0 empties the set); epoch: the absolute time at which the centres hold."""
+        c = np.ascontiguousarray(centre, dtype=np.float64).reshape(-1, self.dim)
+        v = np.ascontiguousarray(velocity, dtype=np.float64).reshape(-1, self.dim)
+        r = np.ascontiguousarray(radius, dtype=np.float64).ravel()
+        if not (c.shape[0] == v.shape[0] == r.size):
+            raise GpisError("centre, velocity and radius must have one row per ball")
+        _check(self.L.gpis_obst_set(self.h, self.dim, r.size, _p(c, C.c_double), _p(v, C.c_double), _p(r, C.c_double), float(epoch)),
+               "gpis_obst_set")
+        return self
+
+    def info(self):
+        out = np.zeros(len(self.INFO_KEYS), dtype=np.float64)
+        _check(self.L.gpis_obst_info(self.h, _p(out, C.c_double), out.size), "gpis_obst_info")
+        d = dict(zip(self.INFO_KEYS, out.tolist()))
+        for k in ("inited", "dim", "n", "device"):
+            d[k] = int(d[k])
+        return d
+
+    def get(self):
+        """dict(centre [n, dim], velocity [n, dim], radius [n], epoch, opts: dict of the four options)."""
+        i = self.info()
+        n, dim = i["n"], i["dim"] or self.dim
+        c, v, r, o = np.zeros((n, dim), np.float64), np.zeros((n, dim), np.float64), np.zeros(n, np.float64), gpis_obst_opts()
+        _check(self.L.gpis_obst_get(self.h, _p(c, C.c_double), _p(v, C.c_double), _p(r, C.c_double), C.byref(o)), "gpis_obst_get")
+        return dict(centre=c, velocity=v, radius=r, epoch=i["epoch"], opts={f[0]: getattr(o, f[0]) for f in gpis_obst_opts._fields_})
+
+    def at(self, t):
+        """The centres [n, dim] at absolute time t (gpis_obst_at; computed on the host)."""
+        i = self.info()
+        out = np.zeros((i["n"], i["dim"] or self.dim), np.float64)
+        _check(self.L.gpis_obst_at(self.h, float(t), _p(out, C.c_double)), "gpis_obst_at")
+        return out
+
+
 class Controller:
     """Sampled model-predictive control (MPPI) against a DistanceField, resident on the device (gpis_mppi_*): init, then per
     control period step (or DistanceField.control) and shift; a step returns the next command, and only a small block leaves
@@ -2265,8 +2382,8 @@ class Controller:
                                          _p(h0, C.c_double), _p(p0, C.c_double)), "gpis_timing_follow")
         return p0, h0
 
-    def step(self, field, pose, goal=None, planner=None, stream=None, **opts):
-        """gpis_mppi_step: see DistanceField.control."""
+    def step(self, field, pose, goal=None, planner=None, stream=None, obstacles=None, t=0.0, **opts):
+        """gpis_mppi_step, or with `obstacles` (an Obstacles) gpis_obst_mppi_step at absolute time t: see DistanceField.control."""
         if not self.dim:
             raise GpisError("step before init")
         if (goal is None) == (planner is None):
@@ -2283,10 +2400,32 @@ class Controller:
         d.update(opts)
         o = mppi_opts(self.dim, field._step(), **d)
         u0 = np.zeros(4 if self.dim == 3 else 2, dtype=np.float64)
+        if obstacles is not None:
+            _check(self.L.gpis_obst_mppi_step(self.h, field.h, planner.h if planner is not None else None, obstacles.h, float(t),
+                                              _p(pose, C.c_double), _p(g, C.c_double) if g is not None else None, C.byref(o),
+                                              _p(u0, C.c_double), stream), "gpis_obst_mppi_step")
+            return u0, self.stats()
         _check(self.L.gpis_mppi_step(self.h, field.h, planner.h if planner is not None else None, _p(pose, C.c_double),
                                      _p(g, C.c_double) if g is not None else None, C.byref(o), _p(u0, C.c_double), stream),
                "gpis_mppi_step")
         return u0, self.stats()
+
+    def obstacle_stats(self):
+        """dict of the last step's view of the moving balls (gpis_obst_mppi_get): dyn_hit_rollouts, nominal_dyn_hits,
+        nominal_min_sep, n.  After a step without balls: 0, 0, inf, 0."""
+        out = np.zeros(4, dtype=np.float64)
+        _check(self.L.gpis_obst_mppi_get(self.h, None, None, _p(out, C.c_double)), "gpis_obst_mppi_get")
+        return dict(dyn_hit_rollouts=int(out[0]), nominal_dyn_hits=int(out[1]), nominal_min_sep=float(out[2]), n=int(out[3]))
+
+    def get_obstacle(self):
+        """dict(dyn_hits [K] i32: each rollout's steps nearer a ball than the set's clearance; min_sep [K] f64: its least
+        separation) of the last step."""
+        i = self.info()
+        if not i["inited"]:
+            raise GpisError("the controller is not initialised")
+        out = dict(dyn_hits=np.zeros(i["rollouts"], np.int32), min_sep=np.zeros(i["rollouts"], np.float64))
+        _check(self.L.gpis_obst_mppi_get(self.h, _p(out["dyn_hits"], C.c_int), _p(out["min_sep"], C.c_double), None), "gpis_obst_mppi_get")
+        return out
 
     def shift(self):
         """Drop the first row of the nominal sequence (the command that has been applied); the last row stays."""

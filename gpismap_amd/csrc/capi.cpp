@@ -17,6 +17,7 @@
 #include "plan.h"
 #include "traj.h"
 #include "mppi.h"
+#include "obst.h"
 #include "cover.h"
 #include "view.h"
 #include "obsgp.h"
@@ -1811,14 +1812,17 @@ int gpis_mppi_set_nominal(void* mppi, const double* U) {
     DeviceScope ds(c.device);
     return c.set_nominal(U);
 }
-int gpis_mppi_step(void* mppi, void* df, void* plan, const double* pose, const double* goal, const gpis_mppi_opts* opts, double* u0,
-                   void* stream) {
+// gpis_mppi_step and gpis_obst_mppi_step: obst NULL or empty is the plain step, launch for launch
+static int mppi_step_checked(void* mppi, void* df, void* plan, const Obstacles* ob, double t_now, const double* pose, const double* goal,
+                             const gpis_mppi_opts* opts, double* u0, void* stream) {
     if (!mppi || !df || !pose || (plan != nullptr) == (goal != nullptr)) return GPIS_ERR_ARG;
     Controller& c = *(Controller*)mppi;
     if (!c.inited) return GPIS_ERR_STATE;
     const DistanceField& f = *(const DistanceField*)df;
     if (!f.valid) return GPIS_ERR_STATE;
     if (f.dim != c.dim || f.device != c.device) return GPIS_ERR_ARG;
+    if (!std::isfinite(t_now)) return GPIS_ERR_ARG;
+    if (ob && (ob->device != c.device || (ob->inited && ob->dim != c.dim))) return GPIS_ERR_ARG;
     MppiOpts o;
     if (opts) {
         o.dt = opts->dt; o.lambda = opts->lambda; o.gamma = opts->gamma; o.clearance = opts->clearance; o.margin = opts->margin;
@@ -1840,12 +1844,23 @@ int gpis_mppi_step(void* mppi, void* df, void* plan, const double* pose, const d
         if (pl->dim != dim || pl->device != c.device || pl->step != f.step) return GPIS_ERR_ARG;
         for (int a = 0; a < 3; ++a) if (pl->n[a] != f.n[a] || pl->origin[a] != f.origin[a]) return GPIS_ERR_ARG;
     }
+    ObstArgs oa{};
+    const bool seen = ob && ob->n > 0;
+    if (seen) {
+        oa.tab = ob->d_tab; oa.n = ob->n; oa.E0 = t_now - ob->epoch;
+        oa.clearance = ob->opts.clearance; oa.band = ob->opts.clearance + ob->opts.margin; oa.margin = ob->opts.margin;
+        oa.w_obs = ob->opts.w_obs; oa.w_col = ob->opts.w_col;
+    }
     DeviceScope ds(c.device);
     try {
-        const int rc = c.step(f, pl, start, goal, o, c.stream_or_own((hipStream_t)stream));
+        const int rc = c.step(f, pl, start, goal, o, c.stream_or_own((hipStream_t)stream), seen ? &oa : nullptr);
         if (rc == GPIS_OK && u0) for (int u = 0; u < c.nu(); ++u) u0[u] = c.stats.u0[u];
         return rc;
     } catch (...) { return GPIS_ERR_STATE; }
+}
+int gpis_mppi_step(void* mppi, void* df, void* plan, const double* pose, const double* goal, const gpis_mppi_opts* opts, double* u0,
+                   void* stream) {
+    return mppi_step_checked(mppi, df, plan, nullptr, 0.0, pose, goal, opts, u0, stream);
 }
 int gpis_mppi_shift(void* mppi) {
     if (!mppi) return GPIS_ERR_ARG;
@@ -1889,6 +1904,100 @@ int gpis_mppi_info(void* mppi, double* out, int n) {
     const double v[8] = {c.inited ? 1.0 : 0.0, (double)c.dim, (double)c.K, (double)c.T, (double)c.tick, (double)c.steps,
                          c.have_step ? 1.0 : 0.0, c.ms};
     for (int i = 0; i < n && i < 8; ++i) out[i] = v[i];
+    return GPIS_OK;
+}
+
+// ---- moving obstacles -----------------------------------------------------------------------------------------------------
+int gpis_obst_default_opts(int dim, float step, gpis_obst_opts* o) {
+    if (!o || (dim != 2 && dim != 3) || !std::isfinite(step) || !(step > 0.f)) return GPIS_ERR_ARG;
+    ObstOpts d;
+    obst_default_opts(dim, step, &d);
+    o->clearance = d.clearance; o->margin = d.margin; o->w_obs = d.w_obs; o->w_col = d.w_col;
+    return GPIS_OK;
+}
+void* gpis_obst_create(void) {
+    if (gpis_device_count() < 1) { fprintf(stderr, "[gpismap_amd] no HIP device\n"); return nullptr; }
+    Obstacles* b = new (std::nothrow) Obstacles();
+    if (b && !b->ok()) { delete b; return nullptr; }
+    return b;
+}
+void gpis_obst_destroy(void* obst) { delete (Obstacles*)obst; }
+int gpis_obst_set(void* obst, int dim, int n, const double* centre, const double* velocity, const double* radius, double epoch) {
+    if (!obst || (dim != 2 && dim != 3) || n < 0) return GPIS_ERR_ARG;
+    if (n > Obstacles::kMax) return GPIS_ERR_LIMIT;
+    if (n > 0 && (!centre || !velocity || !radius)) return GPIS_ERR_ARG;
+    if (!std::isfinite(epoch)) return GPIS_ERR_ARG;
+    for (int i = 0; i < n * dim; ++i) if (!std::isfinite(centre[i]) || !std::isfinite(velocity[i])) return GPIS_ERR_ARG;
+    for (int i = 0; i < n; ++i) if (!std::isfinite(radius[i]) || radius[i] < 0.0) return GPIS_ERR_ARG;
+    try { return ((Obstacles*)obst)->set(dim, n, centre, velocity, radius, epoch); } catch (...) { return GPIS_ERR_STATE; }
+}
+int gpis_obst_set_opts(void* obst, const gpis_obst_opts* opts) {
+    if (!obst || !opts) return GPIS_ERR_ARG;
+    const ObstOpts o = {opts->clearance, opts->margin, opts->w_obs, opts->w_col};
+    if (int rc = obst_check_opts(o)) return rc;
+    ((Obstacles*)obst)->opts = o;
+    return GPIS_OK;
+}
+int gpis_obst_get(void* obst, double* centre, double* velocity, double* radius, gpis_obst_opts* opts) {
+    if (!obst) return GPIS_ERR_ARG;
+    const Obstacles& b = *(const Obstacles*)obst;
+    for (int i = 0; i < b.n; ++i) {
+        for (int a = 0; a < b.dim; ++a) {
+            if (centre) centre[(size_t)i * b.dim + a] = b.c[i][a];
+            if (velocity) velocity[(size_t)i * b.dim + a] = b.v[i][a];
+        }
+        if (radius) radius[i] = b.r[i];
+    }
+    if (opts) { opts->clearance = b.opts.clearance; opts->margin = b.opts.margin; opts->w_obs = b.opts.w_obs; opts->w_col = b.opts.w_col; }
+    return GPIS_OK;
+}
+int gpis_obst_info(void* obst, double* out, int n) {
+    if (!obst || !out || n < 0) return GPIS_ERR_ARG;
+    const Obstacles& b = *(const Obstacles*)obst;
+    const double v[5] = {b.inited ? 1.0 : 0.0, (double)b.dim, (double)b.n, b.epoch, (double)b.device};
+    for (int i = 0; i < n && i < 5; ++i) out[i] = v[i];
+    return GPIS_OK;
+}
+int gpis_obst_at(void* obst, double t, double* centre_out) {
+    if (!obst || !std::isfinite(t) || (!centre_out && ((const Obstacles*)obst)->n > 0)) return GPIS_ERR_ARG;
+    ((const Obstacles*)obst)->at(t, centre_out);
+    return GPIS_OK;
+}
+int gpis_obst_mppi_step(void* mppi, void* df, void* plan, void* obst, double t_now, const double* pose, const double* goal,
+                        const gpis_mppi_opts* opts, double* u0, void* stream) {
+    return mppi_step_checked(mppi, df, plan, (const Obstacles*)obst, t_now, pose, goal, opts, u0, stream);
+}
+int gpis_obst_check_timing(void* traj, void* obst, double dt, int steps, double t0, double t_begin, double clearance, double* min_sep,
+                           double* min_time, int* min_obstacle, int* first_hit, int* collides) {
+    if (!traj || !obst) return GPIS_ERR_ARG;
+    if (!std::isfinite(dt) || !std::isfinite(t0) || !std::isfinite(t_begin) || !std::isfinite(clearance)) return GPIS_ERR_ARG;
+    if (steps < 1 || steps > 4096 || !(dt > 0.0) || t0 < 0.0 || clearance < 0.0) return GPIS_ERR_ARG;
+    Trajectories& t = *(Trajectories*)traj;
+    const Obstacles& b = *(const Obstacles*)obst;
+    if (!t.has_timing()) return GPIS_ERR_STATE;
+    if (b.device != t.device || (b.inited && b.dim != t.dim)) return GPIS_ERR_ARG;
+    DeviceScope ds(t.device);
+    try { return t.check_obst(b, dt, steps, t0, t_begin, clearance, min_sep, min_time, min_obstacle, first_hit, collides); }
+    catch (...) { return GPIS_ERR_STATE; }
+}
+int gpis_obst_mppi_get(void* mppi, int* dyn_hits, double* min_sep, double* stats) {
+    if (!mppi) return GPIS_ERR_ARG;
+    const Controller& c = *(const Controller*)mppi;
+    if (!c.inited) return GPIS_ERR_STATE;
+    const size_t k = (size_t)c.K;
+    if (c.obst_n > 0) {
+        DeviceScope ds(c.device);
+        if (dyn_hits) GPIS_HIP(hipMemcpyAsync(dyn_hits, c.d_dyn, sizeof(int) * k, hipMemcpyDeviceToHost, c.own));
+        if (min_sep) GPIS_HIP(hipMemcpyAsync(min_sep, c.d_msep, sizeof(double) * k, hipMemcpyDeviceToHost, c.own));
+        GPIS_HIP(hipStreamSynchronize(c.own));
+    } else {
+        for (size_t i = 0; i < k; ++i) { if (dyn_hits) dyn_hits[i] = 0; if (min_sep) min_sep[i] = INFINITY; }
+    }
+    if (stats) {
+        const bool on = c.obst_n > 0;
+        stats[0] = on ? (double)c.ostats.ndyn : 0.0; stats[1] = on ? (double)c.ostats.nominal_dyn_hits : 0.0;
+        stats[2] = on ? c.ostats.nominal_min_sep : (double)INFINITY; stats[3] = (double)c.obst_n;
+    }
     return GPIS_OK;
 }
 

@@ -12,6 +12,7 @@ namespace gpis {
 
 struct DistanceField;
 struct Planner;
+struct ObstArgs;
 
 struct MppiOpts {
     double dt, lambda, gamma;
@@ -28,6 +29,12 @@ struct MppiStats {
     int best, nhit;                  // the lowest index of minimal J; rollouts with a hit count > 0
     int nominal_hits, pad;
     double u0[4];                    // the new Ubar[0]
+};
+
+// what a step that saw moving balls (obst.h) copies back besides
+struct ObstStats {
+    double nominal_min_sep;          // the nominal rollout's least separation
+    int nominal_dyn_hits, ndyn;      // its steps nearer than the set's clearance; rollouts with such a step
 };
 
 struct Controller {
@@ -54,6 +61,13 @@ struct Controller {
     size_t cap_nom = 0;
     MppiStats* d_stats = nullptr;
     MppiStats* h_stats = nullptr;                // page-locked
+    // allocated by the first step that sees a non-empty set of moving balls
+    int* d_dyn = nullptr;                        // [K] steps nearer a ball than the set's clearance
+    double* d_msep = nullptr;                    // [K] the least separation
+    int* d_bdyn = nullptr;                       // [ceil(K / 64)] rollouts of the block with dyn > 0
+    size_t cap_dyn = 0;
+    ObstStats* d_ostats = nullptr;
+    ObstStats* h_ostats = nullptr;               // page-locked
 
     // the state
     bool inited = false, have_step = false;
@@ -63,6 +77,8 @@ struct Controller {
     long long steps = 0;
     MppiStats stats = {};
     double neff = 0.0, ms = 0.0;                 // ms: host wall time of the last step
+    int obst_n = 0;                              // balls the last step saw (0: d_dyn and d_msep hold nothing of it)
+    ObstStats ostats = {};
 
     Controller();
     ~Controller();
@@ -70,8 +86,10 @@ struct Controller {
     int init(int dm, int k, int t, uint64_t sd);                 // on the device current in the caller
     int set_nominal(const double* U);                            // host [T][U]
     // start: (x, y[, z], c, s); goal: [dim] or nullptr; pl: nullptr or a planner holding a cost-to-go on df's lattice.
+    // ob: nullptr, or the moving balls' table and constants (n > 0): the kernels with their term run in place of the plain ones.
     // Arguments are checked by the caller.  Synchronises `s`.
-    int step(const DistanceField& df, const Planner* pl, const double* start, const double* goal, const MppiOpts& o, hipStream_t s);
+    int step(const DistanceField& df, const Planner* pl, const double* start, const double* goal, const MppiOpts& o, hipStream_t s,
+             const ObstArgs* ob = nullptr);
     int shift();
     int nu() const { return dim == 3 ? 4 : 2; }
     hipStream_t stream_or_own(hipStream_t s) const { return s ? s : own; }

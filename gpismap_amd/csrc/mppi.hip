@@ -13,6 +13,7 @@
 #include "dfield.h"
 #include "plan.h"
 #include "mppi.h"
+#include "obst.h"
 #include "block_ops.h"
 #include "philox.h"
 
@@ -48,12 +49,35 @@ __device__ __forceinline__ double mppi_control(uint32_t k, uint32_t col, double 
     return v;
 }
 
+// The least separation of a position from the moving balls (obst.h) at elapsed time e: the minimum over i
+// ascending, from +inf.  Where the index and e are the same in every lane the table's rows come through scalar loads.
+template <int D>
+__device__ __forceinline__ double obst_least_sep(const ObstArgs* ob, const double* pos, double e) {
+    const double* __restrict__ row = ob->tab;
+    double Dm = INFINITY;
+    for (int i = 0; i < ob->n; ++i, row += Obstacles::kRow) {
+        const double q0 = pos[0] - (row[0] + row[3] * e);
+        const double q1 = pos[1] - (row[1] + row[4] * e);
+        double s2 = q0 * q0;
+        s2 = s2 + q1 * q1;
+        if constexpr (D == 3) {
+            const double q2 = pos[2] - (row[2] + row[5] * e);
+            s2 = s2 + q2 * q2;
+        }
+        const double sep = sqrt(s2) - row[6];
+        Dm = sep < Dm ? sep : Dm;
+    }
+    return Dm;
+}
+
 // One rollout: the T steps, the stage and control costs, the terminal term.  Ubar is read through a plain pointer: the top
-// kernel rolls the sequence it has just written.
-template <int D, bool STATES>
+// kernel rolls the sequence it has just written.  OBST = 1 adds the moving balls' term at every new position; OBST = 2 adds it
+// with each step's least separation taken from sep_in[t] (the top kernel has them from a thread per step).
+template <int D, bool STATES, int OBST = 0>
 __device__ __forceinline__ void mppi_roll(uint32_t k, const float* __restrict__ F, const DfLattice& L, const float* __restrict__ cost,
                                           const double* Ubar, const MppiParams& p, double* states, double* __restrict__ Jout,
-                                          int* __restrict__ hout) {
+                                          int* __restrict__ hout, const ObstArgs* ob = nullptr, int* __restrict__ dyn_out = nullptr,
+                                          double* __restrict__ sep_out = nullptr, const double* sep_in = nullptr) {
     constexpr int U = D == 3 ? 4 : 2, NS = D + 2;
     DfLattice Lc = L;
     Lc.dim = D;                                          // (a constant dim keeps the sampler's output in registers)
@@ -61,6 +85,8 @@ __device__ __forceinline__ void mppi_roll(uint32_t k, const float* __restrict__ 
     double c = p.start[D], s = p.start[D + 1];
     double J = 0.0;
     int hits = 0;
+    int dyn = 0;
+    double msep = INFINITY;
     if constexpr (STATES) {
 #pragma unroll
         for (int a = 0; a < D; ++a) states[a] = pos[a];
@@ -111,7 +137,21 @@ __device__ __forceinline__ void mppi_roll(uint32_t k, const float* __restrict__ 
             j = (p.w_obs * r) * r;
         }
         const double g = p.gamma * acc;
-        J = (J + j) + g;
+        if constexpr (OBST) {
+            double Dm;
+            if constexpr (OBST == 2) Dm = sep_in[t];
+            else Dm = obst_least_sep<D>(ob, pos, ob->E0 + ((double)(t + 1) * p.dt));
+            double jd = 0.0;
+            if (Dm < ob->clearance) { jd = ob->w_col; dyn += 1; }
+            else if (Dm < ob->band) {
+                const double r = (ob->band - Dm) / ob->margin;
+                jd = (ob->w_obs * r) * r;
+            }
+            msep = Dm < msep ? Dm : msep;
+            J = ((J + j) + jd) + g;
+        } else {
+            J = (J + j) + g;
+        }
     }
     // terminal term
     if (p.use_plan) {
@@ -135,6 +175,7 @@ __device__ __forceinline__ void mppi_roll(uint32_t k, const float* __restrict__ 
     }
     *Jout = J;
     *hout = hits;
+    if constexpr (OBST) { *dyn_out = dyn; *sep_out = msep; }
 }
 
 template <int D>
@@ -152,6 +193,34 @@ __global__ void __launch_bounds__(kRollBlock) mppi_rollout_kernel(const float* _
     }
     v = block_reduce(v, OpMin(), sh, kRollBlock, (double)INFINITY);
     if (threadIdx.x == 0) bmin[blockIdx.x] = v;
+}
+
+// the same with the moving balls' term: also the rollout's count of steps nearer than the set's clearance, its least separation
+// and the block's number of rollouts with such a step (an integer sum: order-free)
+template <int D>
+__global__ void __launch_bounds__(kRollBlock) mppi_obst_rollout_kernel(const float* __restrict__ F, DfLattice L, const float* __restrict__ cost,
+                                                                       const double* __restrict__ Ubar, MppiParams p, ObstArgs ob,
+                                                                       double* __restrict__ J, int* __restrict__ hits,
+                                                                       double* __restrict__ bmin, int* __restrict__ dyn,
+                                                                       double* __restrict__ msep, int* __restrict__ bdyn) {
+    __shared__ double sh[1];
+    __shared__ int shi[1];
+    const int k = (int)(blockIdx.x * kRollBlock + threadIdx.x);
+    double v = INFINITY;
+    int any = 0;
+    if (k < p.K) {
+        int h, dh;
+        double ms;
+        mppi_roll<D, false, 1>((uint32_t)k, F, L, cost, Ubar, p, nullptr, &v, &h, &ob, &dh, &ms);
+        J[k] = v;
+        hits[k] = h;
+        dyn[k] = dh;
+        msep[k] = ms;
+        any = dh > 0 ? 1 : 0;
+    }
+    v = block_reduce(v, OpMin(), sh, kRollBlock, (double)INFINITY);
+    any = block_reduce(any, OpAdd(), shi, kRollBlock, 0);
+    if (threadIdx.x == 0) { bmin[blockIdx.x] = v; bdyn[blockIdx.x] = any; }
 }
 
 // ---- block reductions (block_ops.h: block_reduce) of order-free operations only: min of doubles without NaN, integer sums and
@@ -221,12 +290,14 @@ __global__ void __launch_bounds__(kBlock) mppi_update_kernel(const double* __res
 }
 
 // One workgroup: the integer totals, the tree over the segment partials (tree_top; P a power of two, in place), the new Ubar
-// into the other half, then thread 0 rolls it (z = 0, the rollout's own code) and writes the stats block.
-template <int D>
-__global__ void __launch_bounds__(kBlock) mppi_top_kernel(const float* __restrict__ F, DfLattice L, const float* __restrict__ cost,
-                                                          const double* __restrict__ Uold, double* Unew, MppiParams p, int nb, int P,
-                                                          const u64* __restrict__ bsum, double* __restrict__ part,
-                                                          double* __restrict__ nom, MppiStats* __restrict__ st) {
+// into the other half, then thread 0 rolls it (z = 0, the rollout's own code) and writes the stats block.  OBST: the nominal
+// rollout charges the moving balls' term, and the block sums the rollout kernel's counts of rollouts that hit a ball (integers).
+template <int D, bool OBST>
+__device__ __forceinline__ void mppi_top(const float* __restrict__ F, const DfLattice L, const float* __restrict__ cost,
+                                         const double* __restrict__ Uold, double* Unew, const MppiParams p, int nb, int P,
+                                         const u64* __restrict__ bsum, double* __restrict__ part, double* __restrict__ nom,
+                                         MppiStats* __restrict__ st, const ObstArgs* ob, int nbr, const int* __restrict__ bdyn,
+                                         ObstStats* __restrict__ ost) {
     constexpr int U = D == 3 ? 4 : 2;
     __shared__ u64 sh[kBlock / kWave];
     __shared__ u64 tot_s;
@@ -259,14 +330,69 @@ __global__ void __launch_bounds__(kBlock) mppi_top_kernel(const float* __restric
     }
     __threadfence();
     __syncthreads();
-    if (threadIdx.x == 0) {
-        double Jn;
-        int hn;
-        mppi_roll<D, true>(0u, F, L, cost, Unew, p, nom, &Jn, &hn);
-        st->nominal_cost = Jn; st->nominal_hits = hn;
-#pragma unroll
-        for (int u = 0; u < 4; ++u) st->u0[u] = u < U ? Unew[u] : 0.0;
+    if constexpr (OBST) {
+        u64 nd = 0;
+        for (int b = threadIdx.x; b < nbr; b += kBlock) nd += (u64)bdyn[b];
+        nd = block_reduce(nd, OpAdd(), sh, kBlock, 0ull);
+        if (threadIdx.x == 0) ost->ndyn = (int)nd;
     }
+    if constexpr (OBST) {
+        // The nominal rollout's states do not depend on its costs: one lane rolls them out (the plain rollout, its cost dropped),
+        // a thread per step then walks the table at that step's position -- T chains of n separations side by side instead of
+        // one of T n -- and the lane rolls again with the steps' least separations at hand.  The same expressions on the same
+        // doubles: the bits are those of the rollout kernel's loop.
+        __shared__ double ssep[Controller::kMaxSteps];
+        constexpr int NS = D + 2;
+        if (threadIdx.x == 0) {
+            double J0;
+            int h0;
+            mppi_roll<D, true>(0u, F, L, cost, Unew, p, nom, &J0, &h0);
+        }
+        __threadfence();
+        __syncthreads();
+        for (int t = threadIdx.x; t < p.T; t += kBlock) {
+            double pos[3] = {0.0, 0.0, 0.0};
+#pragma unroll
+            for (int a = 0; a < D; ++a) pos[a] = nom[(size_t)(t + 1) * NS + a];
+            ssep[t] = obst_least_sep<D>(ob, pos, ob->E0 + ((double)(t + 1) * p.dt));
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            double Jn, sn;
+            int hn, dn;
+            mppi_roll<D, true, 2>(0u, F, L, cost, Unew, p, nom, &Jn, &hn, ob, &dn, &sn, ssep);
+            ost->nominal_dyn_hits = dn; ost->nominal_min_sep = sn;
+            st->nominal_cost = Jn; st->nominal_hits = hn;
+#pragma unroll
+            for (int u = 0; u < 4; ++u) st->u0[u] = u < U ? Unew[u] : 0.0;
+        }
+    } else {
+        if (threadIdx.x == 0) {
+            double Jn;
+            int hn;
+            mppi_roll<D, true>(0u, F, L, cost, Unew, p, nom, &Jn, &hn);
+            st->nominal_cost = Jn; st->nominal_hits = hn;
+#pragma unroll
+            for (int u = 0; u < 4; ++u) st->u0[u] = u < U ? Unew[u] : 0.0;
+        }
+    }
+}
+
+template <int D>
+__global__ void __launch_bounds__(kBlock) mppi_top_kernel(const float* __restrict__ F, DfLattice L, const float* __restrict__ cost,
+                                                          const double* __restrict__ Uold, double* Unew, MppiParams p, int nb, int P,
+                                                          const u64* __restrict__ bsum, double* __restrict__ part,
+                                                          double* __restrict__ nom, MppiStats* __restrict__ st) {
+    mppi_top<D, false>(F, L, cost, Uold, Unew, p, nb, P, bsum, part, nom, st, nullptr, 0, nullptr, nullptr);
+}
+
+template <int D>
+__global__ void __launch_bounds__(kBlock) mppi_obst_top_kernel(const float* __restrict__ F, DfLattice L, const float* __restrict__ cost,
+                                                               const double* __restrict__ Uold, double* Unew, MppiParams p, int nb,
+                                                               int P, const u64* __restrict__ bsum, double* __restrict__ part,
+                                                               double* __restrict__ nom, MppiStats* __restrict__ st, ObstArgs ob,
+                                                               int nbr, const int* __restrict__ bdyn, ObstStats* __restrict__ ost) {
+    mppi_top<D, true>(F, L, cost, Uold, Unew, p, nb, P, bsum, part, nom, st, &ob, nbr, bdyn, ost);
 }
 
 }  // namespace
@@ -309,13 +435,15 @@ int Controller::bind(int dev) {
         DeviceScope ds(device);
         if (own) (void)hipStreamSynchronize(own);
         for (void* p : {(void*)d_U[0], (void*)d_U[1], (void*)d_J, (void*)d_q, (void*)d_hits, (void*)d_bmin, (void*)d_bsum, (void*)d_part,
-                        (void*)d_nom, (void*)d_stats})
+                        (void*)d_nom, (void*)d_stats, (void*)d_dyn, (void*)d_msep, (void*)d_bdyn, (void*)d_ostats})
             (void)hipFree(p);
         if (h_stats) (void)hipHostFree(h_stats);
+        if (h_ostats) (void)hipHostFree(h_ostats);
         if (own) (void)hipStreamDestroy(own);
     }
     d_U[0] = d_U[1] = nullptr; d_J = nullptr; d_q = nullptr; d_hits = nullptr; d_bmin = nullptr; d_bsum = nullptr; d_part = nullptr;
     d_nom = nullptr; d_stats = nullptr; h_stats = nullptr; own = nullptr;
+    d_dyn = nullptr; d_msep = nullptr; d_bdyn = nullptr; d_ostats = nullptr; h_ostats = nullptr; cap_dyn = 0; obst_n = 0;
     cap_u = cap_k = cap_part = cap_nom = 0;
     inited = have_step = false; dim = K = T = 0;
     device = dev;
@@ -377,6 +505,7 @@ int Controller::init(int dm, int k, int t, uint64_t sd) {
     GPIS_HIP(hipStreamSynchronize(own));
     dim = dm; K = k; T = t; cur = 0; tick = 0; seed = sd; steps = 0; neff = 0.0; ms = 0.0;
     stats = MppiStats{};
+    obst_n = 0; ostats = ObstStats{};
     inited = true;
     return GPIS_OK;
 }
@@ -399,8 +528,20 @@ int Controller::shift() {
 }
 
 int Controller::step(const DistanceField& df, const Planner* pl, const double* start, const double* goal, const MppiOpts& o,
-                     hipStream_t s) {
+                     hipStream_t s, const ObstArgs* ob) {
     const auto t0 = std::chrono::steady_clock::now();
+    if (ob) {
+        if (!d_ostats) GPIS_HIP(hipMalloc((void**)&d_ostats, sizeof(ObstStats)));
+        if (!h_ostats) GPIS_HIP(hipHostMalloc((void**)&h_ostats, sizeof(ObstStats)));
+        if ((size_t)K > cap_dyn) {
+            for (void* q : {(void*)d_dyn, (void*)d_msep, (void*)d_bdyn}) (void)hipFree(q);
+            d_dyn = nullptr; d_msep = nullptr; d_bdyn = nullptr; cap_dyn = 0;
+            GPIS_HIP(hipMalloc((void**)&d_dyn, sizeof(int) * (size_t)K));
+            GPIS_HIP(hipMalloc((void**)&d_msep, sizeof(double) * (size_t)K));
+            GPIS_HIP(hipMalloc((void**)&d_bdyn, sizeof(int) * (((size_t)K + kRollBlock - 1) / kRollBlock)));
+            cap_dyn = (size_t)K;
+        }
+    }
     MppiParams p{};
     p.dt = o.dt; p.half_dt = 0.5 * o.dt; p.gamma = o.gamma; p.lambda = o.lambda;
     for (int u = 0; u < 4; ++u) { p.sigma[u] = o.sigma[u]; p.umin[u] = o.umin[u]; p.umax[u] = o.umax[u]; }
@@ -415,7 +556,28 @@ int Controller::step(const DistanceField& df, const Planner* pl, const double* s
     const int nbr = (K + kRollBlock - 1) / kRollBlock, nb = (K + kBlock - 1) / kBlock, P = (int)pow2_at_least(nb);
     const int ncol = T * nu(), nchunk = (ncol + kCols - 1) / kCols, to = cur ^ 1;
     const double* Uc = d_U[cur];
-    if (dim == 3) {
+    if (ob) {
+        const float* F = (const float*)df.d_dist;
+        if (dim == 3) {
+            hipLaunchKernelGGL(mppi_obst_rollout_kernel<3>, dim3(nbr), dim3(kRollBlock), 0, s, F, L, cost, Uc, p, *ob, d_J, d_hits, d_bmin,
+                               d_dyn, d_msep, d_bdyn);
+            hipLaunchKernelGGL(mppi_weigh_kernel, dim3(nb), dim3(kBlock), 0, s, (const double*)d_J, (const int*)d_hits, K, nbr, nb,
+                               (const double*)d_bmin, o.lambda, d_q, d_bsum, d_stats);
+            hipLaunchKernelGGL(mppi_update_kernel<3>, dim3(P, nchunk), dim3(kBlock), 0, s, Uc, (const u64*)d_q, p, P, d_part);
+            hipLaunchKernelGGL(mppi_obst_top_kernel<3>, dim3(1), dim3(kBlock), 0, s, F, L, cost, Uc, d_U[to], p, nb, P, (const u64*)d_bsum,
+                               d_part, d_nom, d_stats, *ob, nbr, (const int*)d_bdyn, d_ostats);
+        } else {
+            hipLaunchKernelGGL(mppi_obst_rollout_kernel<2>, dim3(nbr), dim3(kRollBlock), 0, s, F, L, cost, Uc, p, *ob, d_J, d_hits, d_bmin,
+                               d_dyn, d_msep, d_bdyn);
+            hipLaunchKernelGGL(mppi_weigh_kernel, dim3(nb), dim3(kBlock), 0, s, (const double*)d_J, (const int*)d_hits, K, nbr, nb,
+                               (const double*)d_bmin, o.lambda, d_q, d_bsum, d_stats);
+            hipLaunchKernelGGL(mppi_update_kernel<2>, dim3(P, nchunk), dim3(kBlock), 0, s, Uc, (const u64*)d_q, p, P, d_part);
+            hipLaunchKernelGGL(mppi_obst_top_kernel<2>, dim3(1), dim3(kBlock), 0, s, F, L, cost, Uc, d_U[to], p, nb, P, (const u64*)d_bsum,
+                               d_part, d_nom, d_stats, *ob, nbr, (const int*)d_bdyn, d_ostats);
+        }
+        GPIS_HIP(hipGetLastError());
+        GPIS_HIP(hipMemcpyAsync(h_ostats, d_ostats, sizeof(ObstStats), hipMemcpyDeviceToHost, s));
+    } else if (dim == 3) {
         hipLaunchKernelGGL(mppi_rollout_kernel<3>, dim3(nbr), dim3(kRollBlock), 0, s, (const float*)df.d_dist, L, cost, Uc, p, d_J, d_hits, d_bmin);
         hipLaunchKernelGGL(mppi_weigh_kernel, dim3(nb), dim3(kBlock), 0, s, (const double*)d_J, (const int*)d_hits, K, nbr, nb,
                            (const double*)d_bmin, o.lambda, d_q, d_bsum, d_stats);
@@ -434,6 +596,8 @@ int Controller::step(const DistanceField& df, const Planner* pl, const double* s
     GPIS_HIP(hipMemcpyAsync(h_stats, d_stats, sizeof(MppiStats), hipMemcpyDeviceToHost, s));
     GPIS_HIP(hipStreamSynchronize(s));
     stats = *h_stats;
+    obst_n = ob ? ob->n : 0;
+    if (ob) ostats = *h_ostats;
     neff = (double)stats.Th * (double)stats.Th / (double)stats.S2;
     tick += 1; cur = to; steps += 1; have_step = true;
     ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();

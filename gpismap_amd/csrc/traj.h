@@ -29,6 +29,7 @@ struct TimingOpts {
 };
 
 struct Controller;
+struct Obstacles;
 
 struct Trajectories {
     static constexpr int kMinN = 3, kMaxN = 256;     // waypoints per trajectory (the reduction tree's width)
@@ -64,6 +65,10 @@ struct Trajectories {
     int* d_cclamp = nullptr;                         // [m] clamped steps
     size_t cap_cm = 0;
     double* d_follow = nullptr;                      // [8] heading0, p_0 and the clamped count of the last follow()
+    // the last check against moving balls
+    double* d_chkd = nullptr;                        // [m][2] min_sep, min_time
+    int* d_chki = nullptr;                           // [m][3] min_obstacle, first_hit, collides
+    size_t cap_chk = 0;
 
     int m = 0, N = 0, dim = 0;
     bool has_input = false, valid = false, timed = false;
@@ -86,6 +91,11 @@ struct Trajectories {
     int controls(double dt, int T, double t0, double w_limit, double min_move, double* U, double* heading0, double* p0, int* clamped);
     // the sequence of trajectory `index` with the controller's T into the current half of its nominal sequence
     int follow(Controller& c, int index, double dt, double t0, double w_limit, double min_move, double* heading0, double* p0);
+    // every timed trajectory, sampled at t0 + k dt (k = 0 .. steps) from the absolute time t_begin on, against the balls of
+    // `ob` (on this device): the closest approach in continuous time under straight motion between samples; host outputs [m],
+    // any may be nullptr.  Arguments are checked by the caller; synchronises the own stream
+    int check_obst(const Obstacles& ob, double dt, int steps, double t0, double t_begin, double clearance, double* min_sep,
+                   double* min_time, int* min_obstacle, int* first_hit, int* collides);
 
 private:
     int ensure(int m, int N, int dim);

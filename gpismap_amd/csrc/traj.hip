@@ -17,6 +17,7 @@
 #include "traj.h"
 #include "block_ops.h"
 #include "mppi.h"
+#include "obst.h"
 #include "dfield.h"
 #include "plan.h"
 
@@ -522,6 +523,109 @@ __global__ void __launch_bounds__(kBlock) traj_controls_kernel(const float* __re
     if (k == 0) clamped[blockIdx.x] = total;
 }
 
+// A timed trajectory against a set of moving balls (obst.h; the contract: tests/obst_ref.py).  One workgroup of
+// kBlock threads per trajectory.  The intervals are taken in chunks of kChunk: the timed positions p_k of a chunk (and the one
+// that ends it) go to LDS once, by traj_position; then a thread per interval loops over the table (its index is the same in every
+// lane: scalar loads) and keeps its own least (sep, k, i) -- it meets its intervals and the balls in ascending order, so a
+// strict comparison keeps the smallest (k, i) -- and the first interval with a sep below the clearance.  The block's result:
+// the least sep (a min of doubles that are never NaN where they were taken: order-free), then the least key (k << 8 | i) among
+// the threads that hold it, and the thread that owns that key writes.  Double, nothing contracted.  out_d[tr][2] = min_sep,
+// min_time; out_i[tr][3] = min_obstacle, first_hit, collides.
+constexpr int kChunk = 1024;
+
+template <int DIM>
+__global__ void __launch_bounds__(kBlock) traj_obst_check_kernel(const float* __restrict__ x, const float* __restrict__ v,
+                                                                 const float* __restrict__ tt, const int* __restrict__ tint, int N,
+                                                                 int steps, double dt, double t0, double TB, double clearance,
+                                                                 const double* __restrict__ tab, int n, double* __restrict__ out_d,
+                                                                 int* __restrict__ out_i) {
+    __shared__ float st[kTree];
+    __shared__ double sp[kChunk + 1][DIM];
+    __shared__ double shd[kBlock / 64];
+    __shared__ unsigned long long shk[kBlock / 64];
+    __shared__ int shi[kBlock / 64];
+    const int tr = blockIdx.x, tid = threadIdx.x;
+    const size_t base = (size_t)tr * N;
+    if (tint[(size_t)tr * 9] != 0 || n == 0) {
+        if (tid == 0) {
+            const bool timed = tint[(size_t)tr * 9] == 0;
+            out_d[(size_t)tr * 2] = timed ? (double)INFINITY : (double)NAN; out_d[(size_t)tr * 2 + 1] = (double)NAN;
+            out_i[(size_t)tr * 3] = -1; out_i[(size_t)tr * 3 + 1] = -1; out_i[(size_t)tr * 3 + 2] = 0;
+        }
+        return;
+    }
+    for (int i = tid; i < N; i += kBlock) st[i] = tt[base + i];
+    double best = INFINITY, best_s = 0.0;
+    int best_k = -1, best_i = -1, hit = 0x7fffffff;
+    for (int k0 = 0; k0 < steps; k0 += kChunk) {
+        const int cnt = min(kChunk, steps - k0);
+        __syncthreads();                                 // (st is written; sp of the previous chunk is read)
+        for (int j = tid; j <= cnt; j += kBlock) {
+            double p[DIM];
+            traj_position<DIM>(x + base * DIM, v + base, st, N, t0 + (double)(k0 + j) * dt, p);
+#pragma unroll
+            for (int a = 0; a < DIM; ++a) sp[j][a] = p[a];
+        }
+        __syncthreads();
+        for (int j = tid; j < cnt; j += kBlock) {
+            const int k = k0 + j;
+            const double e0 = TB + (t0 + (double)k * dt), e1 = TB + (t0 + (double)(k + 1) * dt);
+            double p0[DIM], dp[DIM];
+#pragma unroll
+            for (int a = 0; a < DIM; ++a) { p0[a] = sp[j][a]; dp[a] = sp[j + 1][a] - p0[a]; }
+            const double* __restrict__ row = tab;
+            for (int i = 0; i < n; ++i, row += Obstacles::kRow) {
+                double A[DIM], B[DIM], bb = 0.0, ab = 0.0;
+#pragma unroll
+                for (int a = 0; a < DIM; ++a) {
+                    const double o0 = row[a] + row[3 + a] * e0, o1 = row[a] + row[3 + a] * e1;
+                    A[a] = p0[a] - o0;
+                    B[a] = dp[a] - (o1 - o0);
+                    bb = a ? bb + B[a] * B[a] : B[a] * B[a];
+                    ab = a ? ab + A[a] * B[a] : A[a] * B[a];
+                }
+                double s = 0.0;
+                if (bb > 0.0) {
+                    s = (-ab) / bb;
+                    s = s > 0.0 ? s : 0.0;
+                    s = s < 1.0 ? s : 1.0;
+                }
+                double s2 = 0.0;
+#pragma unroll
+                for (int a = 0; a < DIM; ++a) {
+                    const double q = A[a] + s * B[a];
+                    s2 = a ? s2 + q * q : q * q;
+                }
+                const double sep = sqrt(s2) - row[6];
+                if (sep < best) { best = sep; best_s = s; best_k = k; best_i = i; }
+                if (sep < clearance && k < hit) hit = k;
+            }
+        }
+    }
+    const double bmin = block_reduce(best, OpMin(), shd, kBlock, (double)INFINITY);
+    if (tid == 0) shd[0] = bmin;
+    __syncthreads();
+    const double least = shd[0];
+    unsigned long long key = best_k >= 0 && best == least ? ((unsigned long long)best_k << 8) | (unsigned long long)best_i : ~0ull;
+    const unsigned long long kmin = block_reduce(key, OpMin(), shk, kBlock, ~0ull);
+    if (tid == 0) shk[0] = kmin;
+    __syncthreads();
+    const unsigned long long win = shk[0];
+    const int fh = block_reduce(hit, OpMin(), shi, kBlock, 0x7fffffff);
+    if (tid == 0) {
+        out_i[(size_t)tr * 3 + 1] = fh == 0x7fffffff ? -1 : fh;
+        out_i[(size_t)tr * 3 + 2] = fh == 0x7fffffff ? 0 : 1;
+        if (win == ~0ull) {                              // no separation was a number
+            out_d[(size_t)tr * 2] = (double)INFINITY; out_d[(size_t)tr * 2 + 1] = (double)NAN; out_i[(size_t)tr * 3] = -1;
+        }
+    }
+    if (key == win && win != ~0ull) {
+        out_d[(size_t)tr * 2] = best;
+        out_d[(size_t)tr * 2 + 1] = (t0 + (double)best_k * dt) + best_s * dt;
+        out_i[(size_t)tr * 3] = best_i;
+    }
+}
+
 }  // namespace
 
 int traj_check_opts(const TrajOpts& o) {
@@ -560,12 +664,14 @@ int Trajectories::bind(int dev) {
                 rc = GPIS_ERR_HIP;
         }
         for (void* p : {(void*)d_in, (void*)d_x, (void*)d_instat, (void*)d_fres, (void*)d_ires, (void*)d_arc, (void*)d_tv, (void*)d_tt,
-                        (void*)d_lim, (void*)d_tsum, (void*)d_tint, (void*)d_cu, (void*)d_chp, (void*)d_cclamp, (void*)d_follow})
+                        (void*)d_lim, (void*)d_tsum, (void*)d_tint, (void*)d_cu, (void*)d_chp, (void*)d_cclamp, (void*)d_follow,
+                        (void*)d_chkd, (void*)d_chki})
             (void)hipFree(p);
         if (own) (void)hipStreamDestroy(own);
     }
     d_in = d_x = d_fres = d_arc = nullptr; d_instat = nullptr; d_ires = nullptr; own = nullptr;
     d_tv = d_tt = d_tsum = nullptr; d_lim = nullptr; d_tint = nullptr; d_cu = d_chp = d_follow = nullptr; d_cclamp = nullptr;
+    d_chkd = nullptr; d_chki = nullptr; cap_chk = 0;
     cap_x = cap_m = cap_arc = cap_tn = cap_tm = cap_cu = cap_cm = 0;
     has_input = valid = timed = false;
     m = N = dim = 0;
@@ -786,6 +892,39 @@ int Trajectories::follow(Controller& c, int index, double dt, double t0, double 
     GPIS_HIP(hipStreamSynchronize(c.own));
     if (heading0) { heading0[0] = hp[0]; heading0[1] = hp[1]; }
     if (p0) for (int a = 0; a < dim; ++a) p0[a] = hp[2 + a];
+    return GPIS_OK;
+}
+
+int Trajectories::check_obst(const Obstacles& ob, double dt, int steps, double t0, double t_begin, double clearance, double* min_sep,
+                             double* min_time, int* min_obstacle, int* first_hit, int* collides) {
+    if (!has_timing()) return GPIS_ERR_STATE;
+    if ((size_t)m > cap_chk) {
+        (void)hipFree(d_chkd); (void)hipFree(d_chki);
+        d_chkd = nullptr; d_chki = nullptr; cap_chk = 0;
+        GPIS_HIP(hipMalloc((void**)&d_chkd, sizeof(double) * 2 * (size_t)m));
+        GPIS_HIP(hipMalloc((void**)&d_chki, sizeof(int) * 3 * (size_t)m));
+        cap_chk = (size_t)m;
+    }
+    const double TB = t_begin - ob.epoch;
+    if (dim == 2)
+        hipLaunchKernelGGL(traj_obst_check_kernel<2>, dim3((unsigned)m), dim3(kBlock), 0, own, d_x, d_tv, d_tt, d_tint, N, steps, dt, t0, TB,
+                           clearance, (const double*)ob.d_tab, ob.n, d_chkd, d_chki);
+    else
+        hipLaunchKernelGGL(traj_obst_check_kernel<3>, dim3((unsigned)m), dim3(kBlock), 0, own, d_x, d_tv, d_tt, d_tint, N, steps, dt, t0, TB,
+                           clearance, (const double*)ob.d_tab, ob.n, d_chkd, d_chki);
+    GPIS_HIP(hipGetLastError());
+    std::vector<double> hd(2 * (size_t)m);
+    std::vector<int> hi(3 * (size_t)m);
+    GPIS_HIP(hipMemcpyAsync(hd.data(), d_chkd, sizeof(double) * hd.size(), hipMemcpyDeviceToHost, own));
+    GPIS_HIP(hipMemcpyAsync(hi.data(), d_chki, sizeof(int) * hi.size(), hipMemcpyDeviceToHost, own));
+    GPIS_HIP(hipStreamSynchronize(own));
+    for (size_t r = 0; r < (size_t)m; ++r) {
+        if (min_sep) min_sep[r] = hd[2 * r];
+        if (min_time) min_time[r] = hd[2 * r + 1];
+        if (min_obstacle) min_obstacle[r] = hi[3 * r];
+        if (first_hit) first_hit[r] = hi[3 * r + 1];
+        if (collides) collides[r] = hi[3 * r + 2];
+    }
     return GPIS_OK;
 }
 

@@ -968,6 +968,66 @@ int   gpis_mppi_device(void* mppi, void** ptrs, int n);
 /* out[0..n): 1 after init, dim, K, T, tick, steps, 1 after the first step, ms of host wall time of the last step */
 int   gpis_mppi_info(void* mppi, double* out, int n);
 
+/* ---- moving obstacles in the controller's rollouts -----------------------------------------------------------
+ * Every stage above reads the distance field of the static map.  A set of moving balls tells the sampling controller what the
+ * map cannot: n balls, 0 <= n <= 256 (discs in 2-D, spheres in 3-D), each a centre c[dim], a constant velocity v[dim] and a
+ * radius r >= 0 in double, and one epoch: the absolute time at which the centres hold.  Ball i at elapsed time e is at
+ * c_a + v_a * e per axis.  tests/obst_ref.py states every rule below in numpy; all arithmetic is double, written left to right,
+ * nothing contracted, IEEE / and sqrt, and the device's bits are the reference's.
+ * gpis_obst_mppi_step is gpis_mppi_step with one more stage-cost term.  E0 = t_now - epoch on the host.  In rollout k at step t,
+ * after the state update, at the new position p: e = E0 + ((double)(t + 1) * dt); q_a = p_a - (c_a + v_a * e); s2 = q_0 q_0 +
+ * q_1 q_1 [+ q_2 q_2] from the first square; sep_i = sqrt(s2) - r_i; D = the minimum over i ascending, from +inf, by
+ * (sep_i < D ? sep_i : D).  j_dyn = w_col' and dyn_hits += 1 if D < clearance'; (w_obs' r) r with r = ((clearance' + margin')
+ * - D) / margin' if D < clearance' + margin'; else 0 (the primed values are the set's options; margin' = 0 leaves no band).
+ * J = ((J + j) + j_dyn) + g.  The term is charged off the lattice too (j is then w_off); the field's hit count keeps its
+ * meaning.  Per rollout: dyn_hits and min_sep, the minimum over t of D from +inf by the same comparison.  The nominal rollout
+ * after the update charges the same term (nominal_cost includes it) and reports its own dyn_hits and min_sep.  Weights, update,
+ * tick, shift, gpis_timing_follow, gpis_mppi_get and gpis_mppi_device are unchanged.  With obst NULL or an empty set the call
+ * is gpis_mppi_step: the same launches, the same bits in every output, the tick included.
+ * The device table of a set is read only during the calls that take the set; no consumer keeps a pointer into it, so a set may
+ * be changed or destroyed between any two calls.
+ * Errors, each before anything is written (the previous set, the controller's tick and sequence stay): a NULL handle, dim
+ * outside {2, 3}, n < 0, a non-finite centre, velocity, radius, epoch, t or t_now, a negative radius, a non-finite or negative
+ * option; a set of another dim or device than the controller -> GPIS_ERR_ARG; n > 256 -> GPIS_ERR_LIMIT; whatever
+ * gpis_mppi_step refuses stays refused. */
+typedef struct gpis_obst_opts {
+    double clearance, margin;   /* a hit on a ball below clearance (of separation: distance to the centre minus the radius); the band above */
+    double w_obs, w_col;
+} gpis_obst_opts;
+/* clearance step, margin 4 step, w_obs 1, w_col 100.  Needs no device. */
+int   gpis_obst_default_opts(int dim, float step, gpis_obst_opts* opts);
+void* gpis_obst_create(void);                               /* on the current device; NULL without one.  Empty, all options 0 */
+void  gpis_obst_destroy(void* obst);
+/* centre, velocity: double [n][dim]; radius: double [n]; n = 0 empties the set (the pointers are not read) */
+int   gpis_obst_set(void* obst, int dim, int n, const double* centre, const double* velocity, const double* radius, double epoch);
+int   gpis_obst_set_opts(void* obst, const gpis_obst_opts* opts);
+/* host copies (any pointer may be NULL) */
+int   gpis_obst_get(void* obst, double* centre, double* velocity, double* radius, gpis_obst_opts* opts);
+/* out[0..n): 1 after the first set, dim, n, epoch, device */
+int   gpis_obst_info(void* obst, double* out, int n);
+/* centre_out [n][dim]: the centres at absolute time t, on the host: c_a + v_a * (t - epoch) */
+int   gpis_obst_at(void* obst, double t, double* centre_out);
+/* obst: a set or NULL; t_now: the absolute time of `pose`; the rest as gpis_mppi_step */
+int   gpis_obst_mppi_step(void* mppi, void* df, void* plan, void* obst, double t_now, const double* pose, const double* goal,
+                          const gpis_mppi_opts* opts, double* u0, void* hip_stream);
+/* of the last step (any pointer may be NULL): dyn_hits [K], min_sep [K]; stats [4] = rollouts with dyn_hits > 0, the nominal
+ * rollout's dyn_hits and min_sep, n of that step.  After a step without balls: zeros, +inf and n = 0 */
+int   gpis_obst_mppi_get(void* mppi, int* dyn_hits, double* min_sep, double* stats);
+/* Timed trajectories (a handle that holds a timing, gpis_timing_time) against a set.  t_begin: the absolute time at which
+ * trajectory time 0 happens.  For each trajectory of timing status 0 and k = 0 .. steps: tau_k = t0 + (double)k * dt, p_k by
+ * gpis_timing_controls' rule bit for bit (the robot rests at x_{N-1} after the duration), e_k = (t_begin - epoch) + tau_k,
+ * o_{i,k} = c_i + v_i * e_k.  For each interval k = 0 .. steps - 1 and ball i, ascending: a = p_k - o_{i,k}; b = (p_{k+1} - p_k)
+ * - (o_{i,k+1} - o_{i,k}); bb = sum_a b_a b_a and ab = sum_a a_a b_a in axis order from the first product; s = 0 unless bb > 0,
+ * else x = (-ab) / bb, s = (x > 0 ? x : 0), s = (s < 1 ? s : 1); q = a + s * b; sep = sqrt(sum_a q_a q_a) - r_i: the closest
+ * approach in continuous time while both bodies move in straight lines between two samples (the controller's model at that dt).
+ * Per trajectory [m] (any pointer may be NULL): min_sep, the least sep by a strict comparison from +inf, so that ties go to
+ * the smallest (k, i); min_time = tau_k + s * dt; min_obstacle = i; first_hit = the smallest k with some sep < clearance, else
+ * -1; collides.  With n = 0: +inf, NaN, -1, -1, 0; with timing status 2 or 3: NaN, NaN, -1, -1, 0.
+ * steps outside [1, 4096], dt <= 0, t0 < 0, clearance < 0, a non-finite argument, a NULL handle, a set of another dim or device
+ * -> GPIS_ERR_ARG; a handle without a timing -> GPIS_ERR_STATE.  Nothing of the handle's result or timing changes. */
+int   gpis_obst_check_timing(void* traj, void* obst, double dt, int steps, double t0, double t_begin, double clearance,
+                             double* min_sep, double* min_time, int* min_obstacle, int* first_hit, int* collides);
+
 /* ---- coverage: which lattice points of a field a sensor has seen as free space, and its frontiers ----------
  * The field knows surfaces only; unknown space is "outside" in it and therefore free to the planner.  A coverage holder keeps one
  * byte per lattice point of a field: 1 once some integrated depth frame or laser scan has looked through that point.  On it:
