@@ -344,6 +344,16 @@ def lib():
         L.gpis_obst_mppi_step.argtypes = [vp, vp, vp, vp, d, dp, dp, C.POINTER(gpis_mppi_opts), dp, vp]
         L.gpis_obst_mppi_get.argtypes = [vp, ip, dp, dp]
         L.gpis_obst_check_timing.argtypes = [vp, vp, d, C.c_int, d, d, d, dp, dp, ip, ip, ip]
+    if hasattr(L, "gpis_body_create"):
+        L.gpis_body_create.restype = vp
+        L.gpis_body_create.argtypes = []
+        L.gpis_body_destroy.argtypes = [vp]
+        L.gpis_body_set.argtypes = [vp, C.c_int, C.c_int, dp, dp]
+        L.gpis_body_get.argtypes = [vp, dp, dp]
+        L.gpis_body_info.argtypes = [vp, dp, C.c_int]
+        L.gpis_body_clearance.argtypes = [vp, vp, dp, C.c_longlong, d, dp, ip, ip, vp]
+        L.gpis_body_mppi_step.argtypes = [vp, vp, vp, vp, vp, d, dp, dp, C.POINTER(gpis_mppi_opts), dp, vp]
+        L.gpis_body_traj_clearance.argtypes = [vp, vp, vp, d, dp, ip, ip, ip]
     if hasattr(L, "gpis_cover_create"):
         co, ub, ll = C.POINTER(gpis_cover_opts), C.POINTER(C.c_ubyte), C.POINTER(C.c_longlong)
         L.gpis_cover_default_opts.argtypes = [C.c_int, C.c_float, co]
@@ -1267,14 +1277,19 @@ class DistanceField:
             self._trajectories = Trajectories()
         return self._trajectories
 
-    def control(self, controller, pose, goal=None, planner=None, stream=None, obstacles=None, t=0.0, **opts):
+    def control(self, controller, pose, goal=None, planner=None, stream=None, obstacles=None, t=0.0, footprint=None, **opts):
         """One step of a sampling Controller through this field (gpis_mppi_step): pose [t, R] as a filter's estimate returns
         it; exactly one of `goal` (a point [dim]) and `planner` (a Planner solved on this field's lattice) gives the terminal
         cost.  opts: the gpis_mppi_opts fields (`lam` for lambda; defaults for this field's step).  Returns (u0, info): the
         first control of the new nominal sequence and dict(Jmin, best, neff, hits, nominal_cost, nominal_hits, T, Th, S2).
         obstacles: an Obstacles whose balls, moved to the absolute time t of `pose` and on from there, are charged in every
-        rollout (gpis_obst_mppi_step); None keeps the plain step."""
-        return controller.step(self, pose, goal=goal, planner=planner, stream=stream, obstacles=obstacles, t=t, **opts)
+        rollout (gpis_obst_mppi_step); None keeps the plain step.  footprint: a Footprint whose balls, placed at every rollout
+        state, stand in for the point (gpis_body_mppi_step); None or an empty one keeps the point."""
+        return controller.step(self, pose, goal=goal, planner=planner, stream=stream, obstacles=obstacles, t=t, footprint=footprint, **opts)
+
+    def body_clearance(self, footprint, states, clearance=0.0, stream=None):
+        """Footprint.clearance on this field."""
+        return footprint.clearance(self, states, clearance=clearance, stream=stream)
 
     def explore(self, cover, start, planner=None, out=None, unseen_dist=None, **opts):
         """Where to go next to see more: the frontiers of `cover` (a Coverage on this field's lattice), this field restricted to
@@ -1906,6 +1921,16 @@ class Trajectories:
                                              _p(r["first_hit"], C.c_int), _p(r["collides"], C.c_int)), "gpis_obst_check_timing")
         return r
 
+    def body_clearance(self, footprint, field, clearance=0.0):
+        """A Footprint along the waypoints of the last result on a DistanceField (gpis_body_traj_clearance): the heading of a
+        waypoint is its chord's.  Returns dict(D_min [m] f64, waypoint, ball, collides [m] i32)."""
+        m = self.info()["m"]
+        r = dict(D_min=np.zeros(m, np.float64), waypoint=np.zeros(m, np.int32), ball=np.zeros(m, np.int32), collides=np.zeros(m, np.int32))
+        _check(self.L.gpis_body_traj_clearance(self.h, field.h, footprint.h, float(clearance), _p(r["D_min"], C.c_double),
+                                               _p(r["waypoint"], C.c_int), _p(r["ball"], C.c_int), _p(r["collides"], C.c_int)),
+               "gpis_body_traj_clearance")
+        return r
+
 
 def timing_opts(dim, step, **opts):
     """gpis_traj_timing_opts of the library's defaults for `dim` and a field of lattice step `step` (gpis_timing_default_opts)
@@ -2325,6 +2350,98 @@ class Obstacles:
         return out
 
 
+def states_from_poses(poses, dim=None):
+    """States [n, dim + 2] = (p, c, s) of poses [t, R] of 6 (2-D) or 12 (3-D) values each: (c, s) = (R[0], R[1]) divided by its
+    norm, as gpis_mppi_step takes its start."""
+    P = np.asarray(poses, dtype=np.float64)
+    if dim is None:
+        dim = 3 if P.shape[-1] == 12 else 2
+    P = P.reshape(-1, 12 if dim == 3 else 6)
+    out = np.zeros((P.shape[0], dim + 2), np.float64)
+    for i, p in enumerate(P):
+        r0, r1 = float(p[dim]), float(p[dim + 1])
+        n = math.sqrt(r0 * r0 + r1 * r1)
+        out[i, :dim] = p[:dim]
+        out[i, dim], out[i, dim + 1] = r0 / n, r1 / n
+    return out
+
+
+class Footprint:
+    """The robot's footprint (gpis_body_*): at most 16 balls fixed to the robot, offsets in the body frame (x forward, y left, z
+    up) and radii in double.  It may be changed or closed between any two calls that take it."""
+
+    MAX = 16
+    INFO_KEYS = ("inited", "dim", "m", "device")
+
+    def __init__(self, dim):
+        self.L = lib()
+        if not hasattr(self.L, "gpis_body_create"):
+            raise GpisError("the native library has no footprints (gpis_body_create)")
+        if self.L.gpis_device_count() < 1:
+            raise GpisError("no HIP device: gpismap_amd has no CPU fallback")
+        self.h = C.c_void_p(self.L.gpis_body_create())
+        if not self.h:
+            raise GpisError("gpis_body_create failed")
+        self.dim = int(dim)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.gpis_body_destroy(self.h)
+            self.h = None
+
+    __del__ = close
+
+    @staticmethod
+    def box_table(length, width, n):
+        """(offset [n, 2], radius [n]) of n equal discs along the x axis whose union covers a length x width rectangle centred on
+        the reference point: centres at -length / 2 + (j + 1 / 2) length / n, radius hypot(width / 2, length / (2 n)).  Host numpy."""
+        n = int(n)
+        if n < 1 or not (length > 0 and width > 0):
+            raise GpisError("box needs n >= 1 and positive sides")
+        off = np.zeros((n, 2), np.float64)
+        off[:, 0] = -0.5 * float(length) + (np.arange(n, dtype=np.float64) + 0.5) * (float(length) / n)
+        return off, np.full(n, math.hypot(0.5 * float(width), float(length) / (2.0 * n)), np.float64)
+
+    @classmethod
+    def box(cls, length, width, n):
+        """A 2-D Footprint holding box_table(length, width, n)."""
+        off, rad = cls.box_table(length, width, n)
+        return cls(2).set(off, rad)
+
+    def set(self, offset, radius):
+        """offset [m, dim], radius [m] (m = 0 empties the footprint)."""
+        o = np.ascontiguousarray(offset, dtype=np.float64).reshape(-1, self.dim)
+        r = np.ascontiguousarray(radius, dtype=np.float64).ravel()
+        if o.shape[0] != r.size:
+            raise GpisError("offset and radius must have one row per ball")
+        _check(self.L.gpis_body_set(self.h, self.dim, r.size, _p(o, C.c_double), _p(r, C.c_double)), "gpis_body_set")
+        return self
+
+    def info(self):
+        out = np.zeros(len(self.INFO_KEYS), dtype=np.float64)
+        _check(self.L.gpis_body_info(self.h, _p(out, C.c_double), out.size), "gpis_body_info")
+        return {k: int(v) for k, v in zip(self.INFO_KEYS, out.tolist())}
+
+    def get(self):
+        """dict(offset [m, dim], radius [m])."""
+        i = self.info()
+        m, dim = i["m"], i["dim"] or self.dim
+        o, r = np.zeros((m, dim), np.float64), np.zeros(m, np.float64)
+        _check(self.L.gpis_body_get(self.h, _p(o, C.c_double), _p(r, C.c_double)), "gpis_body_get")
+        return dict(offset=o, radius=r)
+
+    def clearance(self, field, states, clearance=0.0, stream=None):
+        """The body rule at states [n, dim + 2] = (p, c, s) with unit headings, on a DistanceField (gpis_body_clearance).  Returns
+        dict(D [n] f64: the least of the balls' sampled distances less their radii, NaN off the lattice; ball [n] i32: which
+        ball; below: states with D < clearance; off: states off the lattice; least: the index of the least D, -1 if none)."""
+        S = np.ascontiguousarray(states, dtype=np.float64).reshape(-1, self.dim + 2)
+        n = S.shape[0]
+        D, b, cnt = np.zeros(n, np.float64), np.zeros(n, np.int32), np.zeros(3, np.int32)
+        _check(self.L.gpis_body_clearance(field.h, self.h, _p(S, C.c_double), n, float(clearance), _p(D, C.c_double), _p(b, C.c_int),
+                                          _p(cnt, C.c_int), stream), "gpis_body_clearance")
+        return dict(D=D, ball=b, below=int(cnt[0]), off=int(cnt[1]), least=int(cnt[2]))
+
+
 class Controller:
     """Sampled model-predictive control (MPPI) against a DistanceField, resident on the device (gpis_mppi_*): init, then per
     control period step (or DistanceField.control) and shift; a step returns the next command, and only a small block leaves
@@ -2382,8 +2499,9 @@ class Controller:
                                          _p(h0, C.c_double), _p(p0, C.c_double)), "gpis_timing_follow")
         return p0, h0
 
-    def step(self, field, pose, goal=None, planner=None, stream=None, obstacles=None, t=0.0, **opts):
-        """gpis_mppi_step, or with `obstacles` (an Obstacles) gpis_obst_mppi_step at absolute time t: see DistanceField.control."""
+    def step(self, field, pose, goal=None, planner=None, stream=None, obstacles=None, t=0.0, footprint=None, **opts):
+        """gpis_mppi_step, or with `obstacles` (an Obstacles) gpis_obst_mppi_step at absolute time t, or with `footprint` (a
+        Footprint) gpis_body_mppi_step: see DistanceField.control."""
         if not self.dim:
             raise GpisError("step before init")
         if (goal is None) == (planner is None):
@@ -2400,6 +2518,12 @@ class Controller:
         d.update(opts)
         o = mppi_opts(self.dim, field._step(), **d)
         u0 = np.zeros(4 if self.dim == 3 else 2, dtype=np.float64)
+        if footprint is not None:
+            _check(self.L.gpis_body_mppi_step(self.h, field.h, planner.h if planner is not None else None, footprint.h,
+                                              obstacles.h if obstacles is not None else None, float(t), _p(pose, C.c_double),
+                                              _p(g, C.c_double) if g is not None else None, C.byref(o), _p(u0, C.c_double), stream),
+                   "gpis_body_mppi_step")
+            return u0, self.stats()
         if obstacles is not None:
             _check(self.L.gpis_obst_mppi_step(self.h, field.h, planner.h if planner is not None else None, obstacles.h, float(t),
                                               _p(pose, C.c_double), _p(g, C.c_double) if g is not None else None, C.byref(o),

@@ -18,6 +18,7 @@
 #include "traj.h"
 #include "mppi.h"
 #include "obst.h"
+#include "body.h"
 #include "cover.h"
 #include "view.h"
 #include "obsgp.h"
@@ -1812,9 +1813,10 @@ int gpis_mppi_set_nominal(void* mppi, const double* U) {
     DeviceScope ds(c.device);
     return c.set_nominal(U);
 }
-// gpis_mppi_step and gpis_obst_mppi_step: obst NULL or empty is the plain step, launch for launch
+// gpis_mppi_step, gpis_obst_mppi_step and gpis_body_mppi_step: obst NULL or empty and body NULL or empty is the plain step, launch
+// for launch
 static int mppi_step_checked(void* mppi, void* df, void* plan, const Obstacles* ob, double t_now, const double* pose, const double* goal,
-                             const gpis_mppi_opts* opts, double* u0, void* stream) {
+                             const gpis_mppi_opts* opts, double* u0, void* stream, const Footprint* body = nullptr) {
     if (!mppi || !df || !pose || (plan != nullptr) == (goal != nullptr)) return GPIS_ERR_ARG;
     Controller& c = *(Controller*)mppi;
     if (!c.inited) return GPIS_ERR_STATE;
@@ -1823,6 +1825,7 @@ static int mppi_step_checked(void* mppi, void* df, void* plan, const Obstacles* 
     if (f.dim != c.dim || f.device != c.device) return GPIS_ERR_ARG;
     if (!std::isfinite(t_now)) return GPIS_ERR_ARG;
     if (ob && (ob->device != c.device || (ob->inited && ob->dim != c.dim))) return GPIS_ERR_ARG;
+    if (body && (body->device != c.device || (body->inited && body->dim != c.dim))) return GPIS_ERR_ARG;
     MppiOpts o;
     if (opts) {
         o.dt = opts->dt; o.lambda = opts->lambda; o.gamma = opts->gamma; o.clearance = opts->clearance; o.margin = opts->margin;
@@ -1851,9 +1854,11 @@ static int mppi_step_checked(void* mppi, void* df, void* plan, const Obstacles* 
         oa.clearance = ob->opts.clearance; oa.band = ob->opts.clearance + ob->opts.margin; oa.margin = ob->opts.margin;
         oa.w_obs = ob->opts.w_obs; oa.w_col = ob->opts.w_col;
     }
+    const bool wide = body && body->m > 0;
+    const BodyArgs ba{wide ? body->d_tab : nullptr, wide ? body->m : 0};
     DeviceScope ds(c.device);
     try {
-        const int rc = c.step(f, pl, start, goal, o, c.stream_or_own((hipStream_t)stream), seen ? &oa : nullptr);
+        const int rc = c.step(f, pl, start, goal, o, c.stream_or_own((hipStream_t)stream), seen ? &oa : nullptr, wide ? &ba : nullptr);
         if (rc == GPIS_OK && u0) for (int u = 0; u < c.nu(); ++u) u0[u] = c.stats.u0[u];
         return rc;
     } catch (...) { return GPIS_ERR_STATE; }
@@ -1999,6 +2004,74 @@ int gpis_obst_mppi_get(void* mppi, int* dyn_hits, double* min_sep, double* stats
         stats[2] = on ? c.ostats.nominal_min_sep : (double)INFINITY; stats[3] = (double)c.obst_n;
     }
     return GPIS_OK;
+}
+
+// ---- the robot's footprint ---------------------------------------------------------------------------------------------------
+void* gpis_body_create(void) {
+    if (gpis_device_count() < 1) { fprintf(stderr, "[gpismap_amd] no HIP device\n"); return nullptr; }
+    Footprint* b = new (std::nothrow) Footprint();
+    if (b && !b->ok()) { delete b; return nullptr; }
+    return b;
+}
+void gpis_body_destroy(void* body) { delete (Footprint*)body; }
+int gpis_body_set(void* body, int dim, int m, const double* offset, const double* radius) {
+    if (!body || (dim != 2 && dim != 3) || m < 0) return GPIS_ERR_ARG;
+    if (m > Footprint::kMax) return GPIS_ERR_LIMIT;
+    if (m > 0 && (!offset || !radius)) return GPIS_ERR_ARG;
+    for (int i = 0; i < m * dim; ++i) if (!std::isfinite(offset[i])) return GPIS_ERR_ARG;
+    for (int i = 0; i < m; ++i) if (!std::isfinite(radius[i]) || radius[i] < 0.0) return GPIS_ERR_ARG;
+    try { return ((Footprint*)body)->set(dim, m, offset, radius); } catch (...) { return GPIS_ERR_STATE; }
+}
+int gpis_body_get(void* body, double* offset, double* radius) {
+    if (!body) return GPIS_ERR_ARG;
+    const Footprint& b = *(const Footprint*)body;
+    for (int j = 0; j < b.m; ++j) {
+        if (offset) for (int a = 0; a < b.dim; ++a) offset[(size_t)j * b.dim + a] = b.b[j][a];
+        if (radius) radius[j] = b.rho[j];
+    }
+    return GPIS_OK;
+}
+int gpis_body_info(void* body, double* out, int n) {
+    if (!body || !out || n < 0) return GPIS_ERR_ARG;
+    const Footprint& b = *(const Footprint*)body;
+    const double v[4] = {b.inited ? 1.0 : 0.0, (double)b.dim, (double)b.m, (double)b.device};
+    for (int i = 0; i < n && i < 4; ++i) out[i] = v[i];
+    return GPIS_OK;
+}
+int gpis_body_clearance(void* df, void* body, const double* states, long long n, double clearance, double* D_out, int* ball_out,
+                        int* counts, void* stream) {
+    if (!df || !body || !states || n < 1 || !std::isfinite(clearance)) return GPIS_ERR_ARG;
+    if (n > Footprint::kMaxStates) return GPIS_ERR_LIMIT;
+    DistanceField& f = *(DistanceField*)df;
+    Footprint& b = *(Footprint*)body;
+    if (!f.valid) return GPIS_ERR_STATE;
+    if (b.m == 0) return GPIS_ERR_STATE;
+    if (b.dim != f.dim || b.device != f.device) return GPIS_ERR_ARG;
+    const int ns = f.dim + 2;
+    for (long long i = 0; i < n; ++i) {
+        const double* S = states + (size_t)i * ns;
+        for (int a = 0; a < ns; ++a) if (!std::isfinite(S[a])) return GPIS_ERR_ARG;
+        const double nn = std::sqrt(S[f.dim] * S[f.dim] + S[f.dim + 1] * S[f.dim + 1]);
+        if (!(nn > 0.0) || !std::isfinite(nn)) return GPIS_ERR_ARG;
+    }
+    DeviceScope ds(f.device);
+    try { return b.clearance(f, states, n, clearance, D_out, ball_out, counts, stream ? (hipStream_t)stream : f.own); }
+    catch (...) { return GPIS_ERR_STATE; }
+}
+int gpis_body_mppi_step(void* mppi, void* df, void* plan, void* body, void* obst, double t_now, const double* pose, const double* goal,
+                        const gpis_mppi_opts* opts, double* u0, void* stream) {
+    return mppi_step_checked(mppi, df, plan, (const Obstacles*)obst, t_now, pose, goal, opts, u0, stream, (const Footprint*)body);
+}
+int gpis_body_traj_clearance(void* traj, void* df, void* body, double clearance, double* D_min, int* waypoint, int* ball, int* collides) {
+    if (!traj || !df || !body || !std::isfinite(clearance)) return GPIS_ERR_ARG;
+    Trajectories& t = *(Trajectories*)traj;
+    const DistanceField& f = *(const DistanceField*)df;
+    const Footprint& b = *(const Footprint*)body;
+    if (!t.valid || !f.valid || b.m == 0) return GPIS_ERR_STATE;
+    if (f.dim != t.dim || f.device != t.device || b.dim != t.dim || b.device != t.device) return GPIS_ERR_ARG;
+    DeviceScope ds(t.device);
+    try { return t.check_body(f, BodyArgs{b.d_tab, b.m}, clearance, D_min, waypoint, ball, collides); }
+    catch (...) { return GPIS_ERR_STATE; }
 }
 
 }  // extern "C"

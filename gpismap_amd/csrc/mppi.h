@@ -13,6 +13,7 @@ namespace gpis {
 struct DistanceField;
 struct Planner;
 struct ObstArgs;
+struct BodyArgs;
 
 struct MppiOpts {
     double dt, lambda, gamma;
@@ -87,9 +88,10 @@ struct Controller {
     int set_nominal(const double* U);                            // host [T][U]
     // start: (x, y[, z], c, s); goal: [dim] or nullptr; pl: nullptr or a planner holding a cost-to-go on df's lattice.
     // ob: nullptr, or the moving balls' table and constants (n > 0): the kernels with their term run in place of the plain ones.
+    // bd: nullptr, or a footprint's table (m > 0; body.h): the kernels with the body rule run in place of those.
     // Arguments are checked by the caller.  Synchronises `s`.
     int step(const DistanceField& df, const Planner* pl, const double* start, const double* goal, const MppiOpts& o, hipStream_t s,
-             const ObstArgs* ob = nullptr);
+             const ObstArgs* ob = nullptr, const BodyArgs* bd = nullptr);
     int shift();
     int nu() const { return dim == 3 ? 4 : 2; }
     hipStream_t stream_or_own(hipStream_t s) const { return s ? s : own; }

@@ -14,6 +14,7 @@
 #include "plan.h"
 #include "mppi.h"
 #include "obst.h"
+#include "body.h"
 #include "block_ops.h"
 #include "philox.h"
 
@@ -70,14 +71,35 @@ __device__ __forceinline__ double obst_least_sep(const ObstArgs* ob, const doubl
     return Dm;
 }
 
+// The least separation of a body (body.h) at position pos with the heading (c, s) from the moving balls at elapsed
+// time e: sep_j = obst_least_sep(w_j, e) - rho_j per body ball j ascending, the minimum from +inf by the same strict comparison.
+template <int D>
+__device__ __forceinline__ double body_least_sep(const ObstArgs* ob, const BodyArgs* bd, const double* pos, double c, double s, double e) {
+    const double* __restrict__ row = bd->tab;
+    double Dm = INFINITY;
+    for (int j = 0; j < bd->m; ++j, row += Footprint::kRow) {
+        double w[3] = {0.0, 0.0, 0.0};
+        body_ball_at<D>(row, pos, c, s, w);
+        const double sep = obst_least_sep<D>(ob, w, e) - row[3];
+        Dm = sep < Dm ? sep : Dm;
+    }
+    return Dm;
+}
+
 // One rollout: the T steps, the stage and control costs, the terminal term.  Ubar is read through a plain pointer: the top
 // kernel rolls the sequence it has just written.  OBST = 1 adds the moving balls' term at every new position; OBST = 2 adds it
-// with each step's least separation taken from sep_in[t] (the top kernel has them from a thread per step).
-template <int D, bool STATES, int OBST = 0>
+// with each step's least separation taken from sep_in[t] (the top kernel has them from a thread per step).  BODY = 1 puts the
+// body rule's D (body.h) at the new position and the new heading in the place of the point's sampled distance, and takes the
+// balls' separation from the body's balls; BODY = 2 takes each step's D from d_in[t] (the top kernel's thread per step).
+// lim: nullptr, or the workgroup's LDS copy of the constants the loop reads -- [3][4] sigma, umin and umax, then clearance, band,
+// margin, w_obs, w_col, w_off and the set's clearance, band, margin, w_obs, w_col: the body rollouts keep them out of the scalar
+// registers, which the two tables' rows need.
+template <int D, bool STATES, int OBST = 0, int BODY = 0>
 __device__ __forceinline__ void mppi_roll(uint32_t k, const float* __restrict__ F, const DfLattice& L, const float* __restrict__ cost,
                                           const double* Ubar, const MppiParams& p, double* states, double* __restrict__ Jout,
                                           int* __restrict__ hout, const ObstArgs* ob = nullptr, int* __restrict__ dyn_out = nullptr,
-                                          double* __restrict__ sep_out = nullptr, const double* sep_in = nullptr) {
+                                          double* __restrict__ sep_out = nullptr, const double* sep_in = nullptr,
+                                          const BodyArgs* bd = nullptr, const double* d_in = nullptr, const double* lim = nullptr) {
     constexpr int U = D == 3 ? 4 : 2, NS = D + 2;
     DfLattice Lc = L;
     Lc.dim = D;                                          // (a constant dim keeps the sampler's output in registers)
@@ -98,8 +120,14 @@ __device__ __forceinline__ void mppi_roll(uint32_t k, const float* __restrict__ 
         for (int u = 0; u < U; ++u) {
             const double ub = Ubar[t * U + u];
             double du;
-            v[u] = mppi_control(k, (uint32_t)(t * U + u), ub, p.sigma[u], p.umin[u], p.umax[u], p, &du);
-            if (p.sigma[u] > 0.0) acc = acc + (ub * du) / (p.sigma[u] * p.sigma[u]);
+            if constexpr (BODY == 1) {
+                const double sg = lim[u];
+                v[u] = mppi_control(k, (uint32_t)(t * U + u), ub, sg, lim[4 + u], lim[8 + u], p, &du);
+                if (sg > 0.0) acc = acc + (ub * du) / (sg * sg);
+            } else {
+                v[u] = mppi_control(k, (uint32_t)(t * U + u), ub, p.sigma[u], p.umin[u], p.umax[u], p, &du);
+                if (p.sigma[u] > 0.0) acc = acc + (ub * du) / (p.sigma[u] * p.sigma[u]);
+            }
         }
         // translation with the heading from before the step
         const double bx = v[0] * p.dt;
@@ -126,26 +154,39 @@ __device__ __forceinline__ void mppi_roll(uint32_t k, const float* __restrict__ 
             S[D] = c; S[D + 1] = s;
         }
         // stage cost
-        float o[1 + D];
-        df_sample_at(F, Lc, (float)pos[0], (float)pos[1], D == 3 ? (float)pos[2] : 0.f, o);
-        const double d = (double)o[0];
+        double d;
+        if constexpr (BODY == 2) d = d_in[t];
+        else if constexpr (BODY == 1) {
+            d = body_clearance_at<D>(F, Lc, bd->tab, bd->m, pos, c, s);
+        } else {
+            float o[1 + D];
+            df_sample_at(F, Lc, (float)pos[0], (float)pos[1], D == 3 ? (float)pos[2] : 0.f, o);
+            d = (double)o[0];
+        }
+        const double clr = BODY == 1 ? lim[12] : p.clearance, band = BODY == 1 ? lim[13] : p.band;
+        const double margin = BODY == 1 ? lim[14] : p.margin, w_obs = BODY == 1 ? lim[15] : p.w_obs;
+        const double w_col = BODY == 1 ? lim[16] : p.w_col, w_off = BODY == 1 ? lim[17] : p.w_off;
         double j = 0.0;
-        if (d != d) j = p.w_off;
-        else if (d < p.clearance) { j = p.w_col; hits += 1; }
-        else if (d < p.band) {
-            const double r = (p.band - d) / p.margin;
-            j = (p.w_obs * r) * r;
+        if (d != d) j = w_off;
+        else if (d < clr) { j = w_col; hits += 1; }
+        else if (d < band) {
+            const double r = (band - d) / margin;
+            j = (w_obs * r) * r;
         }
         const double g = p.gamma * acc;
         if constexpr (OBST) {
             double Dm;
             if constexpr (OBST == 2) Dm = sep_in[t];
+            else if constexpr (BODY) Dm = body_least_sep<D>(ob, bd, pos, c, s, ob->E0 + ((double)(t + 1) * p.dt));
             else Dm = obst_least_sep<D>(ob, pos, ob->E0 + ((double)(t + 1) * p.dt));
+            const double oclr = BODY == 1 ? lim[18] : ob->clearance, oband = BODY == 1 ? lim[19] : ob->band;
+            const double omargin = BODY == 1 ? lim[20] : ob->margin, ow_obs = BODY == 1 ? lim[21] : ob->w_obs;
+            const double ow_col = BODY == 1 ? lim[22] : ob->w_col;
             double jd = 0.0;
-            if (Dm < ob->clearance) { jd = ob->w_col; dyn += 1; }
-            else if (Dm < ob->band) {
-                const double r = (ob->band - Dm) / ob->margin;
-                jd = (ob->w_obs * r) * r;
+            if (Dm < oclr) { jd = ow_col; dyn += 1; }
+            else if (Dm < oband) {
+                const double r = (oband - Dm) / omargin;
+                jd = (ow_obs * r) * r;
             }
             msep = Dm < msep ? Dm : msep;
             J = ((J + j) + jd) + g;
@@ -223,6 +264,51 @@ __global__ void __launch_bounds__(kRollBlock) mppi_obst_rollout_kernel(const flo
     if (threadIdx.x == 0) { bmin[blockIdx.x] = v; bdyn[blockIdx.x] = any; }
 }
 
+// the rollouts of a robot with a footprint (body.h): the body rule at every new state; OBST: with the moving
+// balls' term taken at the body's balls, and the outputs of mppi_obst_rollout_kernel (the pointers are not read without it)
+template <int D, bool OBST>
+__global__ void __launch_bounds__(kRollBlock) mppi_body_rollout_kernel(const float* __restrict__ F, DfLattice L, const float* __restrict__ cost,
+                                                                       const double* __restrict__ Ubar, MppiParams p, BodyArgs bd, ObstArgs ob,
+                                                                       double* __restrict__ J, int* __restrict__ hits,
+                                                                       double* __restrict__ bmin, int* __restrict__ dyn,
+                                                                       double* __restrict__ msep, int* __restrict__ bdyn) {
+    __shared__ double sh[1];
+    __shared__ int shi[1];
+    __shared__ double lim[23];
+    if (threadIdx.x == 0) {
+        lim[12] = p.clearance; lim[13] = p.band; lim[14] = p.margin; lim[15] = p.w_obs; lim[16] = p.w_col; lim[17] = p.w_off;
+        lim[18] = ob.clearance; lim[19] = ob.band; lim[20] = ob.margin; lim[21] = ob.w_obs; lim[22] = ob.w_col;
+        lim[0] = p.sigma[0]; lim[1] = p.sigma[1]; lim[2] = p.sigma[2]; lim[3] = p.sigma[3];
+        lim[4] = p.umin[0]; lim[5] = p.umin[1]; lim[6] = p.umin[2]; lim[7] = p.umin[3];
+        lim[8] = p.umax[0]; lim[9] = p.umax[1]; lim[10] = p.umax[2]; lim[11] = p.umax[3];
+    }
+    __syncthreads();
+    const int k = (int)(blockIdx.x * kRollBlock + threadIdx.x);
+    double v = INFINITY;
+    int any = 0;
+    if (k < p.K) {
+        int h;
+        if constexpr (OBST) {
+            int dh;
+            double ms;
+            mppi_roll<D, false, 1, 1>((uint32_t)k, F, L, cost, Ubar, p, nullptr, &v, &h, &ob, &dh, &ms, nullptr, &bd, nullptr, lim);
+            dyn[k] = dh;
+            msep[k] = ms;
+            any = dh > 0 ? 1 : 0;
+        } else {
+            mppi_roll<D, false, 0, 1>((uint32_t)k, F, L, cost, Ubar, p, nullptr, &v, &h, nullptr, nullptr, nullptr, nullptr, &bd, nullptr, lim);
+        }
+        J[k] = v;
+        hits[k] = h;
+    }
+    v = block_reduce(v, OpMin(), sh, kRollBlock, (double)INFINITY);
+    if (threadIdx.x == 0) bmin[blockIdx.x] = v;
+    if constexpr (OBST) {
+        any = block_reduce(any, OpAdd(), shi, kRollBlock, 0);
+        if (threadIdx.x == 0) bdyn[blockIdx.x] = any;
+    }
+}
+
 // ---- block reductions (block_ops.h: block_reduce) of order-free operations only: min of doubles without NaN, integer sums and
 // minima ------------------------------------------------------------------------------------------------------------------------
 // Jmin from the block minima (every workgroup for itself), then q and the block's integer partials
@@ -292,12 +378,13 @@ __global__ void __launch_bounds__(kBlock) mppi_update_kernel(const double* __res
 // One workgroup: the integer totals, the tree over the segment partials (tree_top; P a power of two, in place), the new Ubar
 // into the other half, then thread 0 rolls it (z = 0, the rollout's own code) and writes the stats block.  OBST: the nominal
 // rollout charges the moving balls' term, and the block sums the rollout kernel's counts of rollouts that hit a ball (integers).
-template <int D, bool OBST>
+// BODY: the nominal rollout applies the body rule (body.h) at every state.
+template <int D, bool OBST, bool BODY = false>
 __device__ __forceinline__ void mppi_top(const float* __restrict__ F, const DfLattice L, const float* __restrict__ cost,
                                          const double* __restrict__ Uold, double* Unew, const MppiParams p, int nb, int P,
                                          const u64* __restrict__ bsum, double* __restrict__ part, double* __restrict__ nom,
                                          MppiStats* __restrict__ st, const ObstArgs* ob, int nbr, const int* __restrict__ bdyn,
-                                         ObstStats* __restrict__ ost) {
+                                         ObstStats* __restrict__ ost, const BodyArgs* bd = nullptr) {
     constexpr int U = D == 3 ? 4 : 2;
     __shared__ u64 sh[kBlock / kWave];
     __shared__ u64 tot_s;
@@ -336,7 +423,45 @@ __device__ __forceinline__ void mppi_top(const float* __restrict__ F, const DfLa
         nd = block_reduce(nd, OpAdd(), sh, kBlock, 0ull);
         if (threadIdx.x == 0) ost->ndyn = (int)nd;
     }
-    if constexpr (OBST) {
+    if constexpr (BODY) {
+        // As below, for a body: one lane rolls the states out, a thread per step applies the body rule at that step's state (m field
+        // samples, and with moving balls m walks of their table), and the lane rolls again with the steps' D (and least separations)
+        // at hand.  The same expressions on the same doubles: the bits are those of the rollout kernel's loop.
+        __shared__ double sd[Controller::kMaxSteps];
+        __shared__ double ssep[OBST ? Controller::kMaxSteps : 1];
+        constexpr int NS = D + 2;
+        if (threadIdx.x == 0) {
+            double J0;
+            int h0;
+            mppi_roll<D, true>(0u, F, L, cost, Unew, p, nom, &J0, &h0);
+        }
+        __threadfence();
+        __syncthreads();
+        DfLattice Lc = L;
+        Lc.dim = D;
+        for (int t = threadIdx.x; t < p.T; t += kBlock) {
+            const double* S = nom + (size_t)(t + 1) * NS;
+            double pos[3] = {0.0, 0.0, 0.0};
+#pragma unroll
+            for (int a = 0; a < D; ++a) pos[a] = S[a];
+            sd[t] = body_clearance_at<D>(F, Lc, bd->tab, bd->m, pos, S[D], S[D + 1]);
+            if constexpr (OBST) ssep[t] = body_least_sep<D>(ob, bd, pos, S[D], S[D + 1], ob->E0 + ((double)(t + 1) * p.dt));
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            double Jn, sn = INFINITY;
+            int hn, dn = 0;
+            if constexpr (OBST) {
+                mppi_roll<D, true, 2, 2>(0u, F, L, cost, Unew, p, nom, &Jn, &hn, ob, &dn, &sn, ssep, bd, sd);
+                ost->nominal_dyn_hits = dn; ost->nominal_min_sep = sn;
+            } else {
+                mppi_roll<D, true, 0, 2>(0u, F, L, cost, Unew, p, nom, &Jn, &hn, nullptr, nullptr, nullptr, nullptr, bd, sd);
+            }
+            st->nominal_cost = Jn; st->nominal_hits = hn;
+#pragma unroll
+            for (int u = 0; u < 4; ++u) st->u0[u] = u < U ? Unew[u] : 0.0;
+        }
+    } else if constexpr (OBST) {
         // The nominal rollout's states do not depend on its costs: one lane rolls them out (the plain rollout, its cost dropped),
         // a thread per step then walks the table at that step's position -- T chains of n separations side by side instead of
         // one of T n -- and the lane rolls again with the steps' least separations at hand.  The same expressions on the same
@@ -393,6 +518,32 @@ __global__ void __launch_bounds__(kBlock) mppi_obst_top_kernel(const float* __re
                                                                double* __restrict__ nom, MppiStats* __restrict__ st, ObstArgs ob,
                                                                int nbr, const int* __restrict__ bdyn, ObstStats* __restrict__ ost) {
     mppi_top<D, true>(F, L, cost, Uold, Unew, p, nb, P, bsum, part, nom, st, &ob, nbr, bdyn, ost);
+}
+
+template <int D, bool OBST>
+__global__ void __launch_bounds__(kBlock) mppi_body_top_kernel(const float* __restrict__ F, DfLattice L, const float* __restrict__ cost,
+                                                               const double* __restrict__ Uold, double* Unew, MppiParams p, int nb,
+                                                               int P, const u64* __restrict__ bsum, double* __restrict__ part,
+                                                               double* __restrict__ nom, MppiStats* __restrict__ st, BodyArgs bd,
+                                                               ObstArgs ob, int nbr, const int* __restrict__ bdyn,
+                                                               ObstStats* __restrict__ ost) {
+    mppi_top<D, OBST, true>(F, L, cost, Uold, Unew, p, nb, P, bsum, part, nom, st, &ob, nbr, bdyn, ost, &bd);
+}
+
+// the four launches of a step with a footprint (OB: and with moving balls), from the controller's current half into the other
+template <int D, bool OB>
+void body_launches(Controller& c, hipStream_t s, const float* F, const DfLattice& L, const float* cost, const MppiParams& p,
+                   const BodyArgs& bd, const ObstArgs& oa, double lambda) {
+    const int K = c.K, nbr = (K + kRollBlock - 1) / kRollBlock, nb = (K + kBlock - 1) / kBlock, P = (int)pow2_at_least(nb);
+    const int nchunk = (c.T * c.nu() + kCols - 1) / kCols;
+    const double* Uc = c.d_U[c.cur];
+    hipLaunchKernelGGL((mppi_body_rollout_kernel<D, OB>), dim3(nbr), dim3(kRollBlock), 0, s, F, L, cost, Uc, p, bd, oa, c.d_J, c.d_hits,
+                       c.d_bmin, c.d_dyn, c.d_msep, c.d_bdyn);
+    hipLaunchKernelGGL(mppi_weigh_kernel, dim3(nb), dim3(kBlock), 0, s, (const double*)c.d_J, (const int*)c.d_hits, K, nbr, nb,
+                       (const double*)c.d_bmin, lambda, c.d_q, c.d_bsum, c.d_stats);
+    hipLaunchKernelGGL(mppi_update_kernel<D>, dim3(P, nchunk), dim3(kBlock), 0, s, Uc, (const u64*)c.d_q, p, P, c.d_part);
+    hipLaunchKernelGGL((mppi_body_top_kernel<D, OB>), dim3(1), dim3(kBlock), 0, s, F, L, cost, Uc, c.d_U[c.cur ^ 1], p, nb, P,
+                       (const u64*)c.d_bsum, c.d_part, c.d_nom, c.d_stats, bd, oa, nbr, (const int*)c.d_bdyn, c.d_ostats);
 }
 
 }  // namespace
@@ -528,7 +679,7 @@ int Controller::shift() {
 }
 
 int Controller::step(const DistanceField& df, const Planner* pl, const double* start, const double* goal, const MppiOpts& o,
-                     hipStream_t s, const ObstArgs* ob) {
+                     hipStream_t s, const ObstArgs* ob, const BodyArgs* bd) {
     const auto t0 = std::chrono::steady_clock::now();
     if (ob) {
         if (!d_ostats) GPIS_HIP(hipMalloc((void**)&d_ostats, sizeof(ObstStats)));
@@ -556,7 +707,21 @@ int Controller::step(const DistanceField& df, const Planner* pl, const double* s
     const int nbr = (K + kRollBlock - 1) / kRollBlock, nb = (K + kBlock - 1) / kBlock, P = (int)pow2_at_least(nb);
     const int ncol = T * nu(), nchunk = (ncol + kCols - 1) / kCols, to = cur ^ 1;
     const double* Uc = d_U[cur];
-    if (ob) {
+    if (bd) {
+        const float* F = (const float*)df.d_dist;
+        const ObstArgs oa = ob ? *ob : ObstArgs{};
+        if (dim == 3) {
+            if (ob) body_launches<3, true>(*this, s, F, L, cost, p, *bd, oa, o.lambda);
+            else body_launches<3, false>(*this, s, F, L, cost, p, *bd, oa, o.lambda);
+        } else {
+            if (ob) body_launches<2, true>(*this, s, F, L, cost, p, *bd, oa, o.lambda);
+            else body_launches<2, false>(*this, s, F, L, cost, p, *bd, oa, o.lambda);
+        }
+        if (ob) {
+            GPIS_HIP(hipGetLastError());
+            GPIS_HIP(hipMemcpyAsync(h_ostats, d_ostats, sizeof(ObstStats), hipMemcpyDeviceToHost, s));
+        }
+    } else if (ob) {
         const float* F = (const float*)df.d_dist;
         if (dim == 3) {
             hipLaunchKernelGGL(mppi_obst_rollout_kernel<3>, dim3(nbr), dim3(kRollBlock), 0, s, F, L, cost, Uc, p, *ob, d_J, d_hits, d_bmin,

@@ -30,6 +30,7 @@ struct TimingOpts {
 
 struct Controller;
 struct Obstacles;
+struct BodyArgs;
 
 struct Trajectories {
     static constexpr int kMinN = 3, kMaxN = 256;     // waypoints per trajectory (the reduction tree's width)
@@ -69,6 +70,10 @@ struct Trajectories {
     double* d_chkd = nullptr;                        // [m][2] min_sep, min_time
     int* d_chki = nullptr;                           // [m][3] min_obstacle, first_hit, collides
     size_t cap_chk = 0;
+    // the last check of a footprint along the result
+    double* d_bodyd = nullptr;                       // [m] D_min
+    int* d_bodyi = nullptr;                          // [m][3] waypoint, ball, collides
+    size_t cap_body = 0;
 
     int m = 0, N = 0, dim = 0;
     bool has_input = false, valid = false, timed = false;
@@ -96,6 +101,10 @@ struct Trajectories {
     // any may be nullptr.  Arguments are checked by the caller; synchronises the own stream
     int check_obst(const Obstacles& ob, double dt, int steps, double t0, double t_begin, double clearance, double* min_sep,
                    double* min_time, int* min_obstacle, int* first_hit, int* collides);
+    // the last result's waypoints with the footprint `bd` (m > 0, on this device) on df's dist, the heading of a waypoint taken
+    // from the horizontal chord: host outputs [m], any may be nullptr.  Arguments are checked by the caller; synchronises the
+    // own stream
+    int check_body(const DistanceField& df, const BodyArgs& bd, double clearance, double* D_min, int* waypoint, int* ball, int* collides);
 
 private:
     int ensure(int m, int N, int dim);

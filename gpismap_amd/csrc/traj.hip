@@ -18,6 +18,7 @@
 #include "block_ops.h"
 #include "mppi.h"
 #include "obst.h"
+#include "body.h"
 #include "dfield.h"
 #include "plan.h"
 
@@ -626,6 +627,84 @@ __global__ void __launch_bounds__(kBlock) traj_obst_check_kernel(const float* __
     }
 }
 
+// A footprint (body.h; the contract: tests/body_ref.py) along a smoothed trajectory.  One workgroup of kBlock
+// threads per trajectory, a thread per waypoint.  The waypoints go to LDS once; a thread finds the chord that gives its waypoint
+// a heading -- the first chord k >= min(i, N - 2) with a horizontal length > 0, else the last one before, else (1, 0); double from
+// the float32 waypoints -- and applies the body rule there.  The block's result: the least D (a min of doubles that are never NaN
+// where they were taken: order-free), then the least waypoint among the threads that hold it, and that thread writes.
+// out_d[tr] = D_min; out_i[tr][3] = waypoint, ball, collides.  A trajectory without a result (status 2): NaN, -1, -1, 0.
+template <int DIM>
+__global__ void __launch_bounds__(kBlock) traj_body_check_kernel(const float* __restrict__ F, DfLattice L, BodyArgs bd,
+                                                                 const float* __restrict__ x, const int* __restrict__ ires, int N,
+                                                                 double clearance, double* __restrict__ out_d, int* __restrict__ out_i) {
+    __shared__ float sx[kTree][2];
+    __shared__ double shd[kBlock / 64];
+    __shared__ int shi[kBlock / 64];
+    const int tr = blockIdx.x, i = threadIdx.x;
+    const float* __restrict__ xt = x + (size_t)tr * N * DIM;
+    if (ires[(size_t)tr * 4] == 2) {
+        if (i == 0) {
+            out_d[tr] = (double)NAN;
+            out_i[(size_t)tr * 3] = -1; out_i[(size_t)tr * 3 + 1] = -1; out_i[(size_t)tr * 3 + 2] = 0;
+        }
+        return;
+    }
+    if (i < N) { sx[i][0] = xt[(size_t)i * DIM]; sx[i][1] = xt[(size_t)i * DIM + 1]; }
+    __syncthreads();
+    DfLattice Lc = L;
+    Lc.dim = DIM;
+    double best = INFINITY;
+    int wp = -1, jm = -1, bad = 0, off = 0;
+    if (i < N) {
+        const int k0 = min(i, N - 2);
+        double c = 1.0, s = 0.0;
+        bool found = false;
+        for (int pass = 0; pass < 2 && !found; ++pass) {
+            // pass 0: k = k0 .. N - 2 ascending; pass 1: k = k0 - 1 .. 0 descending
+            for (int k = pass == 0 ? k0 : k0 - 1; pass == 0 ? k <= N - 2 : k >= 0; k += pass == 0 ? 1 : -1) {
+                const double e0 = (double)sx[k + 1][0] - (double)sx[k][0], e1 = (double)sx[k + 1][1] - (double)sx[k][1];
+                const double n2 = e0 * e0 + e1 * e1;
+                if (n2 > 0.0) {
+                    const double nn = sqrt(n2);
+                    c = e0 / nn; s = e1 / nn;
+                    found = true;
+                    break;
+                }
+            }
+        }
+        double p[3] = {(double)sx[i][0], (double)sx[i][1], DIM == 3 ? (double)xt[(size_t)i * DIM + 2] : 0.0};
+        const double d = body_clearance_at<DIM>(F, Lc, bd.tab, bd.m, p, c, s, &jm);
+        if (d != d) { off = 1; bad = 1; }
+        else {
+            bad = d < clearance ? 1 : 0;
+            if (d < best) { best = d; wp = i; }
+        }
+    }
+    const double bmin = block_reduce(best, OpMin(), shd, kBlock, (double)INFINITY);
+    if (i == 0) shd[0] = bmin;
+    __syncthreads();
+    const double least = shd[0];
+    const int key = wp >= 0 && best == least ? wp : 0x7fffffff;
+    const int kmin = block_reduce(key, OpMin(), shi, kBlock, 0x7fffffff);
+    if (i == 0) shi[0] = kmin;
+    __syncthreads();
+    const int win = shi[0];
+    __syncthreads();
+    const int nbad = block_reduce(bad, OpAdd(), shi, kBlock, 0);
+    const int noff = block_reduce(off, OpAdd(), shi, kBlock, 0);
+    if (i == 0) {
+        out_i[(size_t)tr * 3 + 2] = nbad > 0 ? 1 : 0;
+        if (win == 0x7fffffff) {                         // no waypoint gave a D below +inf
+            out_d[tr] = noff == N ? (double)NAN : (double)INFINITY;
+            out_i[(size_t)tr * 3] = -1; out_i[(size_t)tr * 3 + 1] = -1;
+        }
+    }
+    if (wp >= 0 && wp == win) {
+        out_d[tr] = best;
+        out_i[(size_t)tr * 3] = wp; out_i[(size_t)tr * 3 + 1] = jm;
+    }
+}
+
 }  // namespace
 
 int traj_check_opts(const TrajOpts& o) {
@@ -665,13 +744,14 @@ int Trajectories::bind(int dev) {
         }
         for (void* p : {(void*)d_in, (void*)d_x, (void*)d_instat, (void*)d_fres, (void*)d_ires, (void*)d_arc, (void*)d_tv, (void*)d_tt,
                         (void*)d_lim, (void*)d_tsum, (void*)d_tint, (void*)d_cu, (void*)d_chp, (void*)d_cclamp, (void*)d_follow,
-                        (void*)d_chkd, (void*)d_chki})
+                        (void*)d_chkd, (void*)d_chki, (void*)d_bodyd, (void*)d_bodyi})
             (void)hipFree(p);
         if (own) (void)hipStreamDestroy(own);
     }
     d_in = d_x = d_fres = d_arc = nullptr; d_instat = nullptr; d_ires = nullptr; own = nullptr;
     d_tv = d_tt = d_tsum = nullptr; d_lim = nullptr; d_tint = nullptr; d_cu = d_chp = d_follow = nullptr; d_cclamp = nullptr;
     d_chkd = nullptr; d_chki = nullptr; cap_chk = 0;
+    d_bodyd = nullptr; d_bodyi = nullptr; cap_body = 0;
     cap_x = cap_m = cap_arc = cap_tn = cap_tm = cap_cu = cap_cm = 0;
     has_input = valid = timed = false;
     m = N = dim = 0;
@@ -923,6 +1003,38 @@ int Trajectories::check_obst(const Obstacles& ob, double dt, int steps, double t
         if (min_time) min_time[r] = hd[2 * r + 1];
         if (min_obstacle) min_obstacle[r] = hi[3 * r];
         if (first_hit) first_hit[r] = hi[3 * r + 1];
+        if (collides) collides[r] = hi[3 * r + 2];
+    }
+    return GPIS_OK;
+}
+
+int Trajectories::check_body(const DistanceField& df, const BodyArgs& bd, double clearance, double* D_min, int* waypoint, int* ball,
+                             int* collides) {
+    if (!valid) return GPIS_ERR_STATE;
+    if ((size_t)m > cap_body) {
+        (void)hipFree(d_bodyd); (void)hipFree(d_bodyi);
+        d_bodyd = nullptr; d_bodyi = nullptr; cap_body = 0;
+        GPIS_HIP(hipMalloc((void**)&d_bodyd, sizeof(double) * (size_t)m));
+        GPIS_HIP(hipMalloc((void**)&d_bodyi, sizeof(int) * 3 * (size_t)m));
+        cap_body = (size_t)m;
+    }
+    const DfLattice L = df.lattice();
+    if (dim == 2)
+        hipLaunchKernelGGL(traj_body_check_kernel<2>, dim3((unsigned)m), dim3(kBlock), 0, own, (const float*)df.d_dist, L, bd, (const float*)d_x,
+                           (const int*)d_ires, N, clearance, d_bodyd, d_bodyi);
+    else
+        hipLaunchKernelGGL(traj_body_check_kernel<3>, dim3((unsigned)m), dim3(kBlock), 0, own, (const float*)df.d_dist, L, bd, (const float*)d_x,
+                           (const int*)d_ires, N, clearance, d_bodyd, d_bodyi);
+    GPIS_HIP(hipGetLastError());
+    std::vector<double> hd((size_t)m);
+    std::vector<int> hi(3 * (size_t)m);
+    GPIS_HIP(hipMemcpyAsync(hd.data(), d_bodyd, sizeof(double) * hd.size(), hipMemcpyDeviceToHost, own));
+    GPIS_HIP(hipMemcpyAsync(hi.data(), d_bodyi, sizeof(int) * hi.size(), hipMemcpyDeviceToHost, own));
+    GPIS_HIP(hipStreamSynchronize(own));
+    for (size_t r = 0; r < (size_t)m; ++r) {
+        if (D_min) D_min[r] = hd[r];
+        if (waypoint) waypoint[r] = hi[3 * r];
+        if (ball) ball[r] = hi[3 * r + 1];
         if (collides) collides[r] = hi[3 * r + 2];
     }
     return GPIS_OK;

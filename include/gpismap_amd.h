@@ -1028,6 +1028,63 @@ int   gpis_obst_mppi_get(void* mppi, int* dyn_hits, double* min_sep, double* sta
 int   gpis_obst_check_timing(void* traj, void* obst, double dt, int steps, double t0, double t_begin, double clearance,
                              double* min_sep, double* min_time, int* min_obstacle, int* first_hit, int* collides);
 
+/* ---- the robot's footprint: body balls in pose checks, rollouts and trajectories -----------------------------
+ * Every stage above treats the robot as one point with a scalar clearance.  A footprint is m balls fixed to the robot,
+ * 0 <= m <= 16 (discs in 2-D, spheres in 3-D), each an offset b[dim] in the body frame (x forward, y left, z up) and a radius
+ * rho >= 0 in double.  tests/body_ref.py states every rule below in numpy; all arithmetic is double, written left to right,
+ * nothing contracted, IEEE / and sqrt, and the device's bits are the reference's.
+ * The body rule.  A state is (p, c, s): the position p[dim] and the heading (c, s), a yaw about z in 3-D (the controller's
+ * model).  Ball j sits at w0 = p0 + (c b0 - s b1), w1 = p1 + (s b0 + c b1), w2 = p2 + b2.  Its field sample is
+ * gpis_dfield_sample's, bit for bit, at ((float)w0, (float)w1, (float)w2); d_j = (double)sample - rho_j.  D = the minimum over j
+ * ascending, from +inf, by (d_j < D ? d_j : D); jmin = the first j that attains it.  If any ball's sample is NaN (off the
+ * lattice) the body is off: D = NaN, jmin = -1.  The heading is used as given: callers pass unit headings (the rollouts pass
+ * theirs after their own normalisation).  One ball with offset 0 and radius 0 reproduces the point's bits.
+ * gpis_body_clearance: a batch of states, host double [n][dim + 2] = (p, c, s) in the layout of gpis_mppi_get's
+ * nominal_states, 1 <= n <= 2^24.  Per state D_out and ball_out = jmin; counts[3] = the states with D < clearance, the states
+ * off the lattice, the index of the least D (the lowest index on ties; -1 if every state is off): integer totals and a
+ * lexicographic minimum by (D, index), no floating-point atomics.  A state has the same bits alone, in any batch and at any
+ * batch position.  Any output pointer may be NULL.  hip_stream NULL: the field's own stream.
+ * gpis_body_mppi_step is gpis_obst_mppi_step with the stage cost's sampled distance d replaced by D at the new position and the
+ * new heading (the one after the step's Cayley update: the state nominal_states records): NaN -> w_off; D < clearance -> w_col
+ * and hits += 1; the band is unchanged.  With a non-empty set of moving balls: sep_j = (the least separation of w_j, in double,
+ * from the balls at the step's time) - rho_j per body ball j ascending, Dm = their minimum from +inf by the same strict
+ * comparison; dyn_hits, min_sep and the nominal rollout's values keep their meaning with that Dm.  The terminal term, the
+ * control cost, the weights, the update, the tick, shift and gpis_timing_follow are unchanged; the goal and the cost-to-go stay
+ * at the reference point p.  The nominal rollout after the update uses the same rule.  With body NULL or m = 0 the call is
+ * gpis_obst_mppi_step, with obst NULL or empty as well it is gpis_mppi_step: the same launches, the same bits in every output,
+ * the tick included.  No new per-rollout buffers: the nominal rollout's body clearance is gpis_body_clearance on
+ * nominal_states.
+ * gpis_body_traj_clearance: the waypoints of a handle's last result (gpis_traj_optimize; float32 x[m][N][dim]).  The heading at
+ * waypoint i comes from a horizontal chord, in double from the float32 waypoints: e = x[k+1] - x[k] (the first two components),
+ * n2 = e0 e0 + e1 e1, (c, s) = (e0 / sqrt(n2), e1 / sqrt(n2)), with k the smallest index >= min(i, N - 2) and <= N - 2 with
+ * n2 > 0; if there is none, the largest index < min(i, N - 2) with n2 > 0; if there is none, (c, s) = (1, 0).  Then the body
+ * rule at every waypoint.  Per trajectory [m] (any pointer may be NULL): D_min, the least D by a strict comparison from +inf
+ * (ties: the smallest (i, j)); waypoint and ball, where it occurs; collides = 1 if some D < clearance or some waypoint is off
+ * the lattice.  Every waypoint off: NaN, -1, -1, 1.  A trajectory of status 2 (no result): NaN, -1, -1, 0.  Nothing of the
+ * handle's result or timing changes.
+ * The device table [16][4] = (b0, b1, b2, rho) is written by gpis_body_set and read only during the calls that take the
+ * footprint; no consumer keeps a pointer into it, so a footprint may be changed or destroyed between any two calls.
+ * Errors, each before anything is written: a NULL handle, dim outside {2, 3}, m < 0, a non-finite entry, a negative radius, a
+ * non-finite clearance, a non-finite state or a heading of norm 0, a footprint of another dim or device than its consumer ->
+ * GPIS_ERR_ARG; m > 16, n > 2^24 -> GPIS_ERR_LIMIT; a footprint with m = 0 in gpis_body_clearance and
+ * gpis_body_traj_clearance (there is nothing to check), a field or a handle without a result -> GPIS_ERR_STATE; whatever
+ * gpis_obst_mppi_step refuses stays refused. */
+void* gpis_body_create(void);                               /* on the current device; NULL without one.  Empty */
+void  gpis_body_destroy(void* body);
+/* offset: double [m][dim]; radius: double [m]; m = 0 empties the footprint (the pointers are not read) */
+int   gpis_body_set(void* body, int dim, int m, const double* offset, const double* radius);
+/* host copies (either pointer may be NULL) */
+int   gpis_body_get(void* body, double* offset, double* radius);
+/* out[0..n): 1 after the first set, dim, m, device */
+int   gpis_body_info(void* body, double* out, int n);
+int   gpis_body_clearance(void* df, void* body, const double* states, long long n, double clearance, double* D_out, int* ball_out,
+                          int* counts, void* hip_stream);
+/* body: a footprint or NULL; the rest as gpis_obst_mppi_step */
+int   gpis_body_mppi_step(void* mppi, void* df, void* plan, void* body, void* obst, double t_now, const double* pose,
+                          const double* goal, const gpis_mppi_opts* opts, double* u0, void* hip_stream);
+int   gpis_body_traj_clearance(void* traj, void* df, void* body, double clearance, double* D_min, int* waypoint, int* ball,
+                               int* collides);
+
 /* ---- coverage: which lattice points of a field a sensor has seen as free space, and its frontiers ----------
  * The field knows surfaces only; unknown space is "outside" in it and therefore free to the planner.  A coverage holder keeps one
  * byte per lattice point of a field: 1 once some integrated depth frame or laser scan has looked through that point.  On it:
