@@ -69,6 +69,10 @@ class gpis_plan_opts(C.Structure):
                 ("max_rounds", C.c_int)]
 
 
+class gpis_pplan_opts(C.Structure):
+    _fields_ = [("clearance", C.c_float), ("margin", C.c_float), ("gain", C.c_float), ("turn", C.c_float), ("max_rounds", C.c_int)]
+
+
 class gpis_cover_opts(C.Structure):
     _fields_ = [("back_off", C.c_float), ("max_gap", C.c_float), ("clearance", C.c_float), ("min_size", C.c_int),
                 ("max_rounds", C.c_int)]
@@ -269,6 +273,21 @@ def lib():
         L.gpis_plan_path_counts.argtypes = [vp, ll, ll]
         L.gpis_plan_get_paths.argtypes = [vp, ll, fp, fp, ub]
         L.gpis_plan_set_schedule.argtypes = [vp, C.c_int, C.c_int]
+    if hasattr(L, "gpis_pplan_create"):
+        ll, ub = C.POINTER(C.c_longlong), C.POINTER(C.c_ubyte)
+        L.gpis_pplan_default_opts.argtypes = [C.c_float, C.c_int, C.POINTER(gpis_pplan_opts)]
+        L.gpis_pplan_create.restype = vp
+        L.gpis_pplan_create.argtypes = []
+        L.gpis_pplan_destroy.argtypes = [vp]
+        L.gpis_pplan_solve.argtypes = [vp, vp, vp, dp, C.POINTER(C.c_ushort), C.c_int, fp, C.c_int, C.POINTER(gpis_pplan_opts), vp]
+        L.gpis_pplan_info.argtypes = [vp, dp, C.c_int]
+        L.gpis_pplan_get.argtypes = [vp, fp, ub, fp]
+        L.gpis_pplan_device.argtypes = [vp, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
+        L.gpis_pplan_paths.argtypes = [vp, fp, C.c_int, C.c_int, vp]
+        L.gpis_pplan_path_counts.argtypes = [vp, ll, ll]
+        L.gpis_pplan_get_paths.argtypes = [vp, ll, fp, ip, fp, ub]
+        L.gpis_pplan_project.argtypes = [vp, vp, ub]
+        L.gpis_pplan_set_schedule.argtypes = [vp, C.c_int, C.c_int]
     if hasattr(L, "gpis_traj_create"):
         ub = C.POINTER(C.c_ubyte)
         L.gpis_traj_default_opts.argtypes = [C.c_int, C.c_float, C.POINTER(gpis_traj_opts)]
@@ -1254,6 +1273,17 @@ class DistanceField:
         p = planner if planner is not None else self._own_planner()
         return p.solve(self, goals, **opts)
 
+    def plan_poses(self, footprint, goals, H=16, moves="any", pose_planner=None, **opts):
+        """Cost-to-go and policy over poses (x, y, heading index) of this 2-D field for `footprint` towards `goals` [g, 3] or
+        [g, 2] (gpis_pplan_solve): routes the body fits through, where plan() routes a point.  opts: the gpis_pplan_opts
+        fields (clearance, margin, gain, turn, max_rounds).  Returns the PosePlanner holding the result (default: one kept by
+        this field); its project() gives a Planner for the consumers of plan()."""
+        if pose_planner is None:
+            if getattr(self, "_pose_planner", None) is None:
+                self._pose_planner = PosePlanner()
+            pose_planner = self._pose_planner
+        return pose_planner.solve(self, footprint, goals, H=H, moves=moves, **opts)
+
     def _own_planner(self):
         if getattr(self, "_planner", None) is None:
             self._planner = Planner()
@@ -1533,6 +1563,182 @@ class Planner:
         holding the input (default: a new one), ready for optimize()."""
         t = trajectories if trajectories is not None else Trajectories()
         return t.from_paths(self, N)
+
+
+POSE_HEADINGS = (8, 16, 32, 64)
+# the direction of translation code k as a multiple of 45 degrees anticlockwise from +x
+_POSE_ANGLE8 = {14: 0, 17: 1, 16: 2, 15: 3, 12: 4, 9: 5, 10: 6, 11: 7}
+
+
+def pplan_opts(step, H=16, **opts):
+    """gpis_pplan_opts of the library's defaults for a field of lattice step `step` and H headings (gpis_pplan_default_opts)
+    with the given fields replaced."""
+    o = gpis_pplan_opts()
+    _check(lib().gpis_pplan_default_opts(float(step), int(H), C.byref(o)), "gpis_pplan_default_opts")
+    names = {f[0] for f in gpis_pplan_opts._fields_}
+    for k, v in opts.items():
+        if k not in names:
+            raise GpisError("unknown pose plan option %r" % k)
+        setattr(o, k, v)
+    return o
+
+
+def heading_table(H):
+    """[H, 2] float64 (cos, sin) of 2 pi h / H with exact 0 / +-1 at the quarter turns: the table PosePlanner.solve takes."""
+    H = int(H)
+    if H not in POSE_HEADINGS:
+        raise GpisError("H must be one of 8, 16, 32, 64")
+    t = np.zeros((H, 2), np.float64)
+    q = H // 4
+    exact = {0: (1.0, 0.0), q: (0.0, 1.0), 2 * q: (-1.0, 0.0), 3 * q: (0.0, -1.0)}
+    for h in range(H):
+        t[h] = exact[h] if h in exact else (math.cos(2.0 * math.pi * h / H), math.sin(2.0 * math.pi * h / H))
+    return t
+
+
+def heading_moves(H, mode="any"):
+    """uint16 [H]: bit k - 9 set iff the translation of direction code k is allowed at heading index h.  The direction of code
+    k has the heading index a_k H / 8.  "any": all 8 directions; "forward": those within H / 16 heading steps of h
+    (16 circdist(h, a_k H / 8) <= H); "both": those or their opposites.  Integers only."""
+    H = int(H)
+    if H not in POSE_HEADINGS:
+        raise GpisError("H must be one of 8, 16, 32, 64")
+    if mode not in ("any", "forward", "both"):
+        raise GpisError("mode must be any, forward or both")
+    out = np.zeros(H, np.uint16)
+    for h in range(H):
+        for k, a in _POSE_ANGLE8.items():
+            ok = mode == "any"
+            for aa in ((a,) if mode == "forward" else (a, (a + 4) % 8)):
+                d = abs(h - aa * H // 8) % H
+                ok = ok or 16 * min(d, H - d) <= H
+            if ok:
+                out[h] |= np.uint16(1 << (k - 9))
+    return out
+
+
+def _pose_rows(a):
+    """float32 [n, 3] = (x, y, h) rows of a [n, 3], [n, 2], [3] or [2] array; rows without a heading get h = -1."""
+    a = np.asarray(a, dtype=np.float32)
+    a = a.reshape(1, -1) if a.ndim == 1 else a.reshape(a.shape[0], -1)
+    if a.shape[1] == 2:
+        a = np.concatenate([a, np.full((a.shape[0], 1), -1, np.float32)], axis=1)
+    if a.shape[1] != 3:
+        raise GpisError("poses must have 2 or 3 columns")
+    return np.ascontiguousarray(a, dtype=np.float32)
+
+
+class PosePlanner:
+    """Result holder of the pose planner (gpis_pplan_*): cost-to-go and policy over poses (x, y, heading) of a 2-D field for a
+    Footprint, pose paths, and the projection into a Planner.  A finished plan depends neither on the field nor on the
+    footprint it was solved with."""
+
+    INFO_KEYS = ("valid", "nx", "ny", "H", "step", "goals", "goals_kept", "free", "reachable", "rounds", "tile_launches", "solve_ms",
+                 "max_cost", "setup_ms")
+    INT_KEYS = ("valid", "nx", "ny", "H", "goals", "goals_kept", "free", "reachable", "rounds", "tile_launches")
+
+    def __init__(self):
+        self.L = lib()
+        if not hasattr(self.L, "gpis_pplan_create"):
+            raise GpisError("the native library has no pose planner (gpis_pplan_create)")
+        if self.L.gpis_device_count() < 1:
+            raise GpisError("no HIP device: gpismap_amd has no CPU fallback")
+        self.h = C.c_void_p(self.L.gpis_pplan_create())
+        if not self.h:
+            raise GpisError("gpis_pplan_create failed")
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.gpis_pplan_destroy(self.h)
+            self.h = None
+
+    __del__ = close
+
+    def set_schedule(self, check_every=0, inner_cap=0):
+        """Outer rounds per convergence read-back and relaxation sweeps of a tile per round (0 = defaults 8 / 256; the results
+        do not depend on either)."""
+        _check(self.L.gpis_pplan_set_schedule(self.h, int(check_every), int(inner_cap)), "gpis_pplan_set_schedule")
+
+    def solve(self, field, footprint, goals, H=16, moves="any", headings=None, stream=0, **opts):
+        """gpis_pplan_solve on a 2-D DistanceField holding a result for a Footprint; goals [g, 3] = (x, y, h), h = -1 meaning
+        every free heading (goals [g, 2] are taken as that).  moves: a mode of heading_moves or a uint16 [H] table; headings:
+        a [H, 2] table (default heading_table(H)).  opts: the gpis_pplan_opts fields.  Returns self."""
+        inf = field.info()
+        if inf["dim"] == 0:
+            raise GpisError("distance field holds no result")
+        H = int(H)
+        g = _pose_rows(goals)
+        tab = np.ascontiguousarray(heading_table(H) if headings is None else headings, dtype=np.float64).reshape(-1, 2)
+        mv = np.ascontiguousarray(heading_moves(H, moves) if isinstance(moves, str) else moves, dtype=np.uint16).ravel()
+        if tab.shape[0] != H or mv.size != H:
+            raise GpisError("headings and moves must have H rows")
+        o = pplan_opts(inf["step"], H, **opts)
+        _check(self.L.gpis_pplan_solve(self.h, field.h, footprint.h, _p(tab, C.c_double), _p(mv, C.c_ushort), H, _p(g), g.shape[0],
+                                       C.byref(o), C.c_void_p(stream)), "gpis_pplan_solve")
+        return self
+
+    def info(self):
+        out = np.zeros(len(self.INFO_KEYS), dtype=np.float64)
+        _check(self.L.gpis_pplan_info(self.h, _p(out, C.c_double), out.size), "gpis_pplan_info")
+        d = dict(zip(self.INFO_KEYS, out.tolist()))
+        for k in self.INT_KEYS:
+            d[k] = int(d[k])
+        return d
+
+    def get(self):
+        """(cost f32, policy u8, c f32) host copies of the last result, each of shape (H, ny, nx)."""
+        i = self.info()
+        if not i["valid"]:
+            raise GpisError("pose planner holds no result")
+        shape = (i["H"], i["ny"], i["nx"])
+        n = int(np.prod(shape))
+        cost, pol, c = np.zeros(n, np.float32), np.zeros(n, np.uint8), np.zeros(n, np.float32)
+        _check(self.L.gpis_pplan_get(self.h, _p(cost), _p(pol, C.c_ubyte), _p(c)), "gpis_pplan_get")
+        return cost.reshape(shape), pol.reshape(shape), c.reshape(shape)
+
+    def device_ptrs(self):
+        """(d_cost, d_policy, d_c) device addresses of the last result (0 where there is none)."""
+        a, b, c = C.c_void_p(0), C.c_void_p(0), C.c_void_p(0)
+        _check(self.L.gpis_pplan_device(self.h, C.byref(a), C.byref(b), C.byref(c)), "gpis_pplan_device")
+        return a.value or 0, b.value or 0, c.value or 0
+
+    def paths(self, starts, max_points=None, stream=0):
+        """Pose paths from `starts` [m, 3] = (x, y, h) along the policy (gpis_pplan_paths); h = -1: the free heading of least
+        cost there ([m, 2] starts are taken as that).  Returns (list of [len, 2] float32 points, list of [len] int32 heading
+        indices, start_cost [m], status [m] u8) with gpis_plan_paths' status codes; max_points defaults to the number of
+        states, which no path can exceed."""
+        i = self.info()
+        if not i["valid"]:
+            raise GpisError("pose planner holds no result")
+        x = _pose_rows(starts)
+        if max_points is None:
+            max_points = max(2, min(i["nx"] * i["ny"] * i["H"], 2 ** 31 - 1))
+        _check(self.L.gpis_pplan_paths(self.h, _p(x), x.shape[0], int(max_points), C.c_void_p(stream)), "gpis_pplan_paths")
+        m, tot = C.c_longlong(0), C.c_longlong(0)
+        _check(self.L.gpis_pplan_path_counts(self.h, C.byref(m), C.byref(tot)), "gpis_pplan_path_counts")
+        off = np.zeros(m.value + 1, np.int64)
+        pts = np.zeros((max(tot.value, 1), 2), np.float32)
+        hd = np.zeros(max(tot.value, 1), np.int32)
+        sc = np.zeros(m.value, np.float32)
+        st = np.zeros(m.value, np.uint8)
+        _check(self.L.gpis_pplan_get_paths(self.h, _p(off, C.c_longlong), _p(pts), _p(hd, C.c_int), _p(sc), _p(st, C.c_ubyte)),
+               "gpis_pplan_get_paths")
+        self.last_off = off
+        return ([pts[off[k]:off[k + 1]] for k in range(m.value)], [hd[off[k]:off[k + 1]] for k in range(m.value)], sc, st)
+
+    def project(self, planner=None):
+        """The 2-D summary of the last result in a Planner (gpis_pplan_project; default: a new one): cost2 = the least cost
+        over the headings, a policy that descends it, c2 = the least point cost over the free headings.  Planner.paths,
+        Planner.trajectories and Controller.step(planner=...) take it as any solved Planner.  self.heading2 [ny, nx] u8 is the
+        first heading attaining cost2 (255: none).  The projection is a guide; the pose path is the certificate."""
+        i = self.info()
+        if not i["valid"]:
+            raise GpisError("pose planner holds no result")
+        p = planner if planner is not None else Planner()
+        h2 = np.zeros(i["nx"] * i["ny"], np.uint8)
+        _check(self.L.gpis_pplan_project(self.h, p.h, _p(h2, C.c_ubyte)), "gpis_pplan_project")
+        self.heading2 = h2.reshape(i["ny"], i["nx"])
+        return p
 
 
 def cover_opts(dim, step, **opts):

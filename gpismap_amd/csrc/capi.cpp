@@ -15,6 +15,7 @@
 #include "locate.h"
 #include "pf.h"
 #include "plan.h"
+#include "pplan.h"
 #include "traj.h"
 #include "mppi.h"
 #include "obst.h"
@@ -2072,6 +2073,140 @@ int gpis_body_traj_clearance(void* traj, void* df, void* body, double clearance,
     DeviceScope ds(t.device);
     try { return t.check_body(f, BodyArgs{b.d_tab, b.m}, clearance, D_min, waypoint, ball, collides); }
     catch (...) { return GPIS_ERR_STATE; }
+}
+
+// ---- routes for the robot's footprint: the pose planner ------------------------------------------------------------------------
+int gpis_pplan_default_opts(float step, int H, gpis_pplan_opts* o) {
+    if (!o || !(std::isfinite(step) && step > 0.f) || (H != 8 && H != 16 && H != 32 && H != 64)) return GPIS_ERR_ARG;
+    o->clearance = 0.f; o->margin = 4.f * step; o->gain = 4.f; o->turn = step; o->max_rounds = 0;
+    return GPIS_OK;
+}
+void* gpis_pplan_create(void) {
+    if (gpis_device_count() < 1) { fprintf(stderr, "[gpismap_amd] no HIP device\n"); return nullptr; }
+    PosePlanner* p = new (std::nothrow) PosePlanner();
+    if (p && !p->own) { delete p; return nullptr; }
+    return p;
+}
+void gpis_pplan_destroy(void* pplan) { delete (PosePlanner*)pplan; }
+int gpis_pplan_set_schedule(void* pplan, int check_every, int inner_cap) {
+    if (!pplan || check_every < 0 || inner_cap < 0) return GPIS_ERR_ARG;
+    PosePlanner& p = *(PosePlanner*)pplan;
+    p.check_every = check_every ? std::min(check_every, (int)PosePlanner::kMaxBatch) : 8;
+    p.inner_cap = inner_cap ? inner_cap : 256;
+    return GPIS_OK;
+}
+// a heading index of a goal or a start: an integer in -1 .. H - 1
+static bool pplan_heading_ok(float h, int H) { return std::isfinite(h) && h == std::floor(h) && h >= -1.f && h <= (float)(H - 1); }
+// the argument and state checks come before anything is dropped: such an error leaves the previous result readable
+int gpis_pplan_solve(void* pplan, void* d, void* body, const double* headings, const unsigned short* moves, int H, const float* goals,
+                     int ngoals, const gpis_pplan_opts* opts, void* stream) {
+    if (!pplan || !d || !body || !headings || !moves || !goals || ngoals < 1) return GPIS_ERR_ARG;
+    if (H != 8 && H != 16 && H != 32 && H != 64) return GPIS_ERR_ARG;
+    for (int h = 0; h < H; ++h) {
+        const double c = headings[2 * h], s = headings[2 * h + 1];
+        if (!std::isfinite(c) || !std::isfinite(s) || (c == 0.0 && s == 0.0) || (moves[h] & ~0x1efu)) return GPIS_ERR_ARG;
+    }
+    for (int g = 0; g < ngoals; ++g) if (!pplan_heading_ok(goals[(size_t)g * 3 + 2], H)) return GPIS_ERR_ARG;
+    const DistanceField& df = *(const DistanceField*)d;
+    const Footprint& b = *(const Footprint*)body;
+    if (df.valid && df.dim != 2) return GPIS_ERR_ARG;
+    gpis_pplan_opts dflt;
+    if (!opts) {
+        if (!df.valid) return GPIS_ERR_STATE;
+        (void)gpis_pplan_default_opts(df.step, H, &dflt);
+        opts = &dflt;
+    }
+    PPlanOpts o;
+    o.clearance = opts->clearance; o.margin = opts->margin; o.gain = opts->gain; o.turn = opts->turn; o.max_rounds = opts->max_rounds;
+    if (int rc = pplan_check_opts(o, df.valid ? df.step : 0.f)) return rc;
+    if (!df.valid || b.m == 0 || b.dim != 2) return GPIS_ERR_STATE;
+    if (b.device != df.device) return GPIS_ERR_ARG;
+    if ((long long)df.n[0] * df.n[1] * H > PosePlanner::kMaxStates) return GPIS_ERR_LIMIT;
+    PosePlanner& p = *(PosePlanner*)pplan;
+    DeviceScope ds(df.device);
+    try {
+        if (int rc = p.bind(df.device)) { p.clear_result(); return rc; }
+        const int rc = p.solve(df, b, headings, moves, H, goals, ngoals, o, stream ? (hipStream_t)stream : df.own);
+        if (rc != GPIS_OK) p.clear_result();
+        return rc;
+    } catch (...) { p.clear_result(); return GPIS_ERR_STATE; }
+}
+int gpis_pplan_info(void* pplan, double* out, int n) {
+    if (!pplan || !out || n < 0) return GPIS_ERR_ARG;
+    const PosePlanner& p = *(PosePlanner*)pplan;
+    const bool v = p.valid;
+    const double w[14] = {v ? 1.0 : 0.0, v ? (double)p.n[0] : 0.0, v ? (double)p.n[1] : 0.0, v ? (double)p.H : 0.0, v ? (double)p.step : 0.0,
+                          (double)p.goals_given, (double)p.goals_kept, (double)p.nfree, (double)p.nreach, (double)p.rounds,
+                          (double)p.launches, p.solve_ms, (double)p.max_cost, p.setup_ms};
+    for (int i = 0; i < n && i < 14; ++i) out[i] = w[i];
+    return GPIS_OK;
+}
+int gpis_pplan_get(void* pplan, float* cost, unsigned char* policy, float* c) {
+    if (!pplan) return GPIS_ERR_ARG;
+    PosePlanner& p = *(PosePlanner*)pplan;
+    if (!p.valid) return GPIS_ERR_STATE;
+    DeviceScope ds(p.device);
+    const size_t n = (size_t)p.nstates;
+    if (cost) GPIS_HIP(hipMemcpyAsync(cost, p.d_cost, sizeof(float) * n, hipMemcpyDeviceToHost, p.own));
+    if (policy) GPIS_HIP(hipMemcpyAsync(policy, p.d_policy, n, hipMemcpyDeviceToHost, p.own));
+    if (c) GPIS_HIP(hipMemcpyAsync(c, p.d_c, sizeof(float) * n, hipMemcpyDeviceToHost, p.own));
+    GPIS_HIP(hipStreamSynchronize(p.own));
+    return GPIS_OK;
+}
+int gpis_pplan_device(void* pplan, const float** d_cost, const unsigned char** d_policy, const float** d_c) {
+    if (!pplan) return GPIS_ERR_ARG;
+    const PosePlanner& p = *(PosePlanner*)pplan;
+    if (d_cost) *d_cost = p.valid ? p.d_cost : nullptr;
+    if (d_policy) *d_policy = p.valid ? p.d_policy : nullptr;
+    if (d_c) *d_c = p.valid ? p.d_c : nullptr;
+    return GPIS_OK;
+}
+int gpis_pplan_paths(void* pplan, const float* starts, int m, int max_points, void* stream) {
+    if (!pplan || !starts || m < 1 || max_points < 2) return GPIS_ERR_ARG;
+    PosePlanner& p = *(PosePlanner*)pplan;
+    if (!p.valid) return GPIS_ERR_STATE;
+    if (m > PosePlanner::kMaxStarts) return GPIS_ERR_LIMIT;
+    for (int t = 0; t < m; ++t) if (!pplan_heading_ok(starts[(size_t)t * 3 + 2], p.H)) return GPIS_ERR_ARG;
+    DeviceScope ds(p.device);
+    try {
+        const int rc = p.paths(starts, m, max_points, stream ? (hipStream_t)stream : p.own);
+        if (rc != GPIS_OK) p.paths_valid = false;
+        return rc;
+    } catch (...) { p.paths_valid = false; return GPIS_ERR_STATE; }
+}
+int gpis_pplan_path_counts(void* pplan, long long* npaths, long long* npoints) {
+    if (!pplan) return GPIS_ERR_ARG;
+    const PosePlanner& p = *(PosePlanner*)pplan;
+    if (!p.valid || !p.paths_valid) return GPIS_ERR_STATE;
+    if (npaths) *npaths = p.npaths;
+    if (npoints) *npoints = p.npoints;
+    return GPIS_OK;
+}
+int gpis_pplan_get_paths(void* pplan, long long* off, float* points, int* heading, float* start_cost, unsigned char* status) {
+    if (!pplan) return GPIS_ERR_ARG;
+    PosePlanner& p = *(PosePlanner*)pplan;
+    if (!p.valid || !p.paths_valid) return GPIS_ERR_STATE;
+    DeviceScope ds(p.device);
+    const size_t m = (size_t)p.npaths;
+    if (off) GPIS_HIP(hipMemcpyAsync(off, p.d_off, sizeof(long long) * (m + 1), hipMemcpyDeviceToHost, p.own));
+    if (points && p.npoints > 0) GPIS_HIP(hipMemcpyAsync(points, p.d_points, sizeof(float) * 2 * (size_t)p.npoints, hipMemcpyDeviceToHost, p.own));
+    if (heading && p.npoints > 0) GPIS_HIP(hipMemcpyAsync(heading, p.d_pheading, sizeof(int) * (size_t)p.npoints, hipMemcpyDeviceToHost, p.own));
+    if (start_cost) GPIS_HIP(hipMemcpyAsync(start_cost, p.d_scost, sizeof(float) * m, hipMemcpyDeviceToHost, p.own));
+    if (status) GPIS_HIP(hipMemcpyAsync(status, p.d_status, m, hipMemcpyDeviceToHost, p.own));
+    GPIS_HIP(hipStreamSynchronize(p.own));
+    return GPIS_OK;
+}
+int gpis_pplan_project(void* pplan, void* plan, unsigned char* heading2) {
+    if (!pplan || !plan) return GPIS_ERR_ARG;
+    PosePlanner& p = *(PosePlanner*)pplan;
+    if (!p.valid) return GPIS_ERR_STATE;
+    Planner& q = *(Planner*)plan;
+    DeviceScope ds(p.device);
+    try {
+        const int rc = p.project(q, heading2);
+        if (rc != GPIS_OK) q.clear_result();
+        return rc;
+    } catch (...) { q.clear_result(); return GPIS_ERR_STATE; }
 }
 
 }  // extern "C"

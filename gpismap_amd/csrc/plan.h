@@ -62,6 +62,12 @@ struct Planner {
     int solve(const DistanceField& df, const float* goals, int ngoals, const PlanOpts& o, hipStream_t s);
     // paths from host starts [m][dim]: count, scan, write; synchronises `s`
     int paths(const float* starts, int m, int max_points, hipStream_t s);
+    // A 2-D result computed elsewhere (the pose planner's projection, pplan.hip).  install_begin drops the result held, moves
+    // to `dev`, makes room for nx x ny points and copies the geometry; the caller then fills d_cost, d_c and d_policy on a
+    // stream it synchronises, and install_end records the counters and makes the result valid exactly as solve() does.
+    int install_begin(int dev, int nx, int ny, const float* origin2, float lattice_step);
+    void install_end(long long given, long long kept, long long free_points, long long reachable, long long outer_rounds,
+                     long long tile_launches, double ms, float largest_cost);
 
 private:
     int ensure(long long np, long long tiles);

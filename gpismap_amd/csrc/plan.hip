@@ -17,19 +17,17 @@
 #include <cstring>
 #include "plan.h"
 #include "dfield.h"
+#include "plan_dev.h"
 
 namespace gpis {
 
 namespace {
 
+using namespace plan_dev;
+
 constexpr int kBlock = 256;
 constexpr int kStatKept = 0, kStatLaunch = 1, kStatFree = 2, kStatReach = 3, kStatMax = 4, kStatRaised = 8;
 constexpr int kStatWords = kStatRaised + Planner::kMaxBatch;
-
-struct PlanLat {
-    int dim, nx, ny, nz;
-    float ox, oy, oz, step;
-};
 
 constexpr int off_dx(int k) { return k % 3 - 1; }
 constexpr int off_dy(int k) { return (k / 3) % 3 - 1; }
@@ -58,28 +56,6 @@ __device__ __forceinline__ unsigned open_moves(unsigned nb, int dim, int conn) {
     if (dim == 2) m &= 0x1ffu << 9;
     if (!conn) m &= (1u << 4) | (1u << 10) | (1u << 12) | (1u << 14) | (1u << 16) | (1u << 22);
     return m;
-}
-
-__device__ __forceinline__ float ld_cost(const float* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void st_cost(float* p, float v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-// lattice point of a world point: i = (int)floorf(u + 0.5f), u = (x - origin) / step; false outside the lattice or non-finite
-__device__ __forceinline__ bool snap(const PlanLat& L, const float* x, int* ijk) {
-    const float o[3] = {L.ox, L.oy, L.oz};
-    const int n[3] = {L.nx, L.ny, L.nz};
-    ijk[2] = 0;
-    bool ok = true;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        if (a < L.dim) {
-            const float xa = x[a];
-            const float f = floorf((xa - o[a]) / L.step + 0.5f);
-            const bool in = isfinite(xa) && f >= 0.f && f <= (float)(n[a] - 1);
-            ijk[a] = in ? (int)f : 0;
-            ok = ok && in;
-        }
-    }
-    return ok;
 }
 
 // c[p] = point cost (0: not free), cost[p] = +inf, policy[p] = 255
@@ -325,32 +301,6 @@ __global__ void __launch_bounds__(kBlock) plan_walk_kernel(PlanLat L, const floa
     }
 }
 
-// in place: off[0..m) = exclusive scan of the counts, off[m] = their sum.  One workgroup.
-__global__ void __launch_bounds__(1024) plan_scan_kernel(long long* __restrict__ off, int m) {
-    __shared__ long long s[1024];
-    __shared__ long long carry;
-    const int tid = threadIdx.x;
-    if (tid == 0) carry = 0;
-    __syncthreads();
-    for (int base = 0; base < m; base += 1024) {
-        const int idx = base + tid;
-        const long long v = idx < m ? off[idx] : 0;
-        s[tid] = v;
-        __syncthreads();
-        for (int d = 1; d < 1024; d <<= 1) {
-            const long long t = tid >= d ? s[tid - d] : 0;
-            __syncthreads();
-            s[tid] += t;
-            __syncthreads();
-        }
-        if (idx < m) off[idx] = s[tid] - v + carry;
-        __syncthreads();
-        if (tid == 1023) carry += s[1023];
-        __syncthreads();
-    }
-    if (tid == 0) off[m] = carry;
-}
-
 }  // namespace
 
 int plan_check_opts(const PlanOpts& o) {
@@ -464,6 +414,24 @@ int Planner::solve(const DistanceField& df, const float* goals, int ngoals, cons
     solve_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     valid = true;
     return GPIS_OK;
+}
+
+int Planner::install_begin(int dev, int nx, int ny, const float* origin2, float lattice_step) {
+    if (int rc = bind(dev)) return rc;
+    clear_result();
+    const long long np = (long long)nx * ny;
+    if (int rc = ensure(np, (long long)((nx + kTile2 - 1) / kTile2) * ((ny + kTile2 - 1) / kTile2))) return rc;
+    dim = 2; ngrid = np; step = lattice_step;
+    n[0] = nx; n[1] = ny; n[2] = 1;
+    origin[0] = origin2[0]; origin[1] = origin2[1]; origin[2] = 0.f;
+    return GPIS_OK;
+}
+
+void Planner::install_end(long long given, long long kept, long long free_points, long long reachable, long long outer_rounds,
+                          long long tile_launches, double ms, float largest_cost) {
+    goals_given = given; goals_kept = kept; nfree = free_points; nreach = reachable; rounds = outer_rounds; launches = tile_launches;
+    solve_ms = ms; max_cost = largest_cost;
+    valid = true;
 }
 
 int Planner::paths(const float* starts, int m, int max_points, hipStream_t s) {

@@ -1085,6 +1085,76 @@ int   gpis_body_mppi_step(void* mppi, void* df, void* plan, void* body, void* ob
 int   gpis_body_traj_clearance(void* traj, void* df, void* body, double clearance, double* D_min, int* waypoint, int* ball,
                                int* collides);
 
+/* ---- routes for the robot's footprint: heading layers in the planner ---------------------------------------
+ * gpis_plan_solve plans for a point with one scalar clearance; a long narrow robot has no right scalar.  The pose planner is
+ * the same solver on the lattice nx x ny x H of poses (x, y, heading) of a 2-D field, H in {8, 16, 32, 64}: state s = (i, j, h)
+ * at index (h ny + j) nx + i.  tests/pplan_ref.py states every rule below in numpy; float32 without FMA as in §7h, except the
+ * body rule, which is double as in §7r; the device's bits are the reference's.
+ * Headings: the caller's table, double [H][2] = (c_h, s_h), used as given (finite, not both 0; nothing here calls a
+ * trigonometric function).  Configuration space: D(i, j, h) = the body rule (above) at p = ((double)(ox + (float)i * step),
+ * (double)(oy + (float)j * step)) with the heading (c_h, s_h) -- gpis_body_clearance's D of that state, bit for bit; d =
+ * (float)D; the state is free iff d >= clearance, so a body with a ball off the lattice (D NaN) is not free, and where the
+ * bilinear sampler meets infinite dist values and returns NaN the state is blocked.  c = gpis_plan_solve's point cost on d.
+ * Moves are directed.  Translation (p, h) -> (p + o, h), code k = 9 + (dy + 1) 3 + (dx + 1) (the 2-D direction codes of
+ * gpis_plan_solve): exists iff bit k - 9 of moves[h] is set (uint16 [H], the caller's), the target is in the lattice and p +
+ * every non-empty subset of o's components is free in layer h; weight (len * step) * (0.5f * (c[s] + c[s'])).  Turn (p, h) ->
+ * (p, h +- 1 mod H), codes 27 (+1) and 28 (-1): exists iff both states are free; weight turn * (0.5f * (c[s] + c[s'])).
+ * cost = the greatest solution of cost[s] = min over moves s -> s' of fl(cost[s'] + w) with 0 at the kept goals: a float32
+ * Dijkstra on the reversed graph, the same bits on every run and for every schedule.  Goals: float [g][3] = (x, y, h); x, y snap
+ * as in gpis_plan_solve; h = -1 means every free heading at that point, each counted as a kept goal; a goal that is outside,
+ * non-finite or not free is dropped.  policy[s] = 13 at a goal, else the code minimising fl(cost[s'] + w) (ties: the smaller
+ * cost[s'], then the smaller code), 255 where not free or unreachable.
+ * Pose paths: starts float [m][3] = (x, y, h), h = -1 meaning the free heading of least cost at the snapped point (ties: the
+ * smaller h; none free: status 2, start cost +inf).  Status codes and the count / scan / write packing are gpis_plan_paths';
+ * every state visited is emitted as its world point and its heading index.
+ * gpis_pplan_project fills a plain planner handle with the 2-D summary: cost2[p] = min over h of cost[p, h]; heading2[p] = the
+ * first h attaining it (255 where cost2 is +inf); c2[p] = the least c over the free headings (0: none); policy2[p] = 13 where
+ * cost2 == 0, 255 where it is +inf, else the code 9 .. 17 whose in-lattice neighbour has the least cost2 (ties: the smaller
+ * code) -- a neighbour of smaller cost2 always exists, the first translation of the pose path from (p, heading2[p]) leads to
+ * one.  gpis_plan_info then reports free = the points with a free heading, reachable and max_cost of the projection, and the
+ * pose solve's goals, goals_kept, rounds, tile_launches and solve_ms.  The projected handle is valid exactly as after
+ * gpis_plan_solve (gpis_plan_paths, gpis_traj_from_paths, gpis_body_mppi_step take it unchanged) and outlives the pose
+ * planner.  The projection is a guide -- a cost-to-go and a walkable descent for consumers that track a point; the pose path is
+ * the certificate that the body fits.  Nothing is checked between lattice points or between heading steps: choose H so that
+ * the farthest ball moves at most about one lattice step per heading step.
+ * The pose planner owns its buffers (9 B per state, grow-only, reused), copies the lattice geometry and both tables, and reads
+ * the field and the footprint only during gpis_pplan_solve: a finished plan outlives both.  hip_stream NULL: the field's own
+ * stream (gpis_pplan_paths: the pose planner's); every call returns with its work finished.
+ * Errors: a NULL handle or array, ngoals < 1, m < 1, max_points < 2, a 3-D field, H outside {8, 16, 32, 64}, a non-finite
+ * heading or (0, 0), a move bit other than the 8 translations', a non-finite option, a negative margin or gain, gain > 1e4,
+ * turn outside [step / 64, 1e4 step] (which keeps every weight far above half an ulp of any reachable cost), max_rounds < 0, a
+ * goal or start heading that is not an integer in -1 .. H - 1, a footprint on another device -> GPIS_ERR_ARG; a footprint with
+ * m = 0 or of dimension 3, a field or a handle without a result -> GPIS_ERR_STATE; nx ny H > 2^28, more than 2^24 starts ->
+ * GPIS_ERR_LIMIT: all with the previous result untouched.  max_rounds > 0 exceeded -> GPIS_ERR_LIMIT and no result. */
+typedef struct gpis_pplan_opts {
+    float clearance;            /* free iff (float)D >= clearance */
+    float margin, gain;         /* point cost, as gpis_plan_opts */
+    float turn;                 /* the length of one heading step, in the units of step */
+    int max_rounds;             /* cap on the outer rounds; 0 = none */
+} gpis_pplan_opts;
+/* clearance 0, margin 4 * step, gain 4, turn step, max_rounds 0.  Needs no device. */
+int   gpis_pplan_default_opts(float step, int H, gpis_pplan_opts* opts);
+void* gpis_pplan_create(void);                              /* on the current device; NULL without one */
+void  gpis_pplan_destroy(void* pplan);
+/* headings: double [H][2]; moves: uint16 [H]; goals: host float [ngoals][3].  opts NULL: the defaults for the field's step */
+int   gpis_pplan_solve(void* pplan, void* df, void* body, const double* headings, const unsigned short* moves, int H,
+                       const float* goals, int ngoals, const gpis_pplan_opts* opts, void* hip_stream);
+/* out[0..n): 1 if a result is held, nx, ny, H, the step, goals given, goal states kept, free states, reachable states, outer
+ * rounds, tile launches, ms of host wall time in the solve, the largest finite cost, ms of that time in the set-up kernel (14) */
+int   gpis_pplan_info(void* pplan, double* out, int n);
+/* host copies, nx ny H each; any may be NULL */
+int   gpis_pplan_get(void* pplan, float* cost, unsigned char* policy, float* c);
+/* device pointers of the last result, valid until the next solve or gpis_pplan_destroy (NULL where there is none) */
+int   gpis_pplan_device(void* pplan, const float** d_cost, const unsigned char** d_policy, const float** d_c);
+int   gpis_pplan_paths(void* pplan, const float* starts, int m, int max_points, void* hip_stream);
+int   gpis_pplan_path_counts(void* pplan, long long* npaths, long long* npoints);
+/* off[m + 1], points[off[m]][2], heading[off[m]], start_cost[m] (NaN for status 1), status[m]; any may be NULL */
+int   gpis_pplan_get_paths(void* pplan, long long* off, float* points, int* heading, float* start_cost, unsigned char* status);
+/* plan: a gpis_plan_create handle; heading2: host [nx ny] or NULL */
+int   gpis_pplan_project(void* pplan, void* plan, unsigned char* heading2);
+/* test hook, as gpis_plan_set_schedule */
+int   gpis_pplan_set_schedule(void* pplan, int check_every, int inner_cap);
+
 /* ---- coverage: which lattice points of a field a sensor has seen as free space, and its frontiers ----------
  * The field knows surfaces only; unknown space is "outside" in it and therefore free to the planner.  A coverage holder keeps one
  * byte per lattice point of a field: 1 once some integrated depth frame or laser scan has looked through that point.  On it:
