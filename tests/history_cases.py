@@ -130,6 +130,49 @@ def controller_ref(i):
     return out
 
 
+# ---- Controller with a set of moving balls and a footprint ----------------------------------------------------------------------
+# (dim, K, T, balls, body balls): A; B larger in every capacity; C across P = 1 with one ball and one body ball; a plain step at
+# the largest K, after which the rollout buffers (grown by init under cap_k) are longer than the per-rollout buffers of the balls
+# (d_dyn, d_msep, d_bdyn: grown by step under cap_dyn); then balls under that K, which init has served and step has not; A again
+CONTROLLER_BODY = ((2, 257, 33, 65, 5), (3, 1000, 33, 256, 16), (2, 64, 1, 1, 1), (2, 4097, 2, 0, 0), (2, 4097, 2, 2, 16), (2, 257, 33, 65, 5))
+CONTROLLER_BODY_SEEDS = (5, 6, 7, 8, 9, 5)
+
+
+def controller_body_case(i):
+    """Entry i as a case of tests/body_cases.py (obst None without balls, body None without body balls).  Where the horizon is too
+    short for the shape cases' crossing ball to arrive, ball 0 rests just ahead of the robot instead."""
+    import body_cases as bc
+    import obst_cases as oc
+    import obst_ref
+    dim, K, T, n, m = CONTROLLER_BODY[i]
+    c = dict(mc.shape_case(K, T, dim), seed=CONTROLLER_BODY_SEEDS[i], t_now=oc.T_NOW, expect=())
+    S = oc.balls(dim, n, mc.scene(dim)["step"]) if n else None
+    if S is not None and T <= 2:
+        ahead = mppi_ref.start_state(c["pose"], dim)[:dim] + np.array([0.1, 0.0, 0.0])[:dim]
+        S = obst_ref.make(dim, np.concatenate([ahead[None], S["c"][1:]]), np.concatenate([np.zeros((1, dim)), S["v"][1:]]), S["r"], epoch=S["epoch"],
+                          step=mc.scene(dim)["step"])
+    return dict(c, obst=S, body=bc.footprint(dim, m) if m else None)
+
+
+def controller_body_ref(i):
+    """The two steps of entry i by the reference (its own weights), the clock moved on by dt between them: [step 1, step 2] as
+    body_ref.step returns them."""
+    import body_ref
+    c = controller_body_case(i)
+    sc = mc.scene(c["dim"])
+    cost, goal = mc.terminal_args(c)
+    ctl = body_ref.Controller(c["dim"], c["K"], c["T"], c["seed"])
+    ctl.set_nominal(mc.nominal_of(c))
+    out = []
+    for k in range(2):
+        if k:
+            ctl.shift()
+        ctl.step(sc["dist"], sc["shape"], sc["origin"], sc["step"], c["pose"], c["opts"], cost, goal, obst=c["obst"],
+                 t_now=c["t_now"] + k * c["opts"]["dt"], body=c["body"])
+        out.append(ctl.last)
+    return out
+
+
 # ---- ParticleFilter -----------------------------------------------------------------------------------------------------------
 FILTER = ((2, 257), (2, 4097), (2, 1), (2, 65), (3, 300), (2, 257))      # (dim, particles)
 FILTER_SEEDS = (1, 2, 3, 4, 5, 1)
@@ -319,3 +362,43 @@ def session_pose(name):
         return pose6(0.3, tuple(o + 0.25 * (n - 1) * s))
     c = o + 0.5 * (n - 1) * s
     return pose12(np.eye(3), np.array([c[0] - 2 * s, c[1] + s, o[2] - 0.9]))
+
+
+# what the session's later stages add: a footprint, limits and three balls in the scale of the round's lattice
+SESSION_DT = 0.1
+SESSION_T0 = 1.0
+
+
+def _extent(name):
+    l = FIELDS[name][0]
+    return np.array(l["origin"], F64), (np.array(l["shape"]) - 1) * l["step"], l["step"]
+
+
+def session_body(name):
+    """The robot of a round: a box of five discs (2-D) / three balls turning about z (3-D), a few lattice steps long."""
+    import body_ref
+    o, ext, s = _extent(name)
+    if len(o) == 2:
+        return body_ref.box(6 * s, 2.5 * s, 5)
+    return body_ref.make(3, [(1.2 * s, 0.0, 0.4 * s), (-s, 0.6 * s, -0.4 * s), (0.0, -s, 0.8 * s)], [0.8 * s, s, 0.6 * s])
+
+
+def session_timing(name):
+    """Speed and acceleration limits for a lattice about a metre across."""
+    return dict(v_max=0.3, v_min=0.02, a_max=0.2, d_max=0.2, a_lat=0.2)
+
+
+def session_balls(name):
+    """Three balls: one that crosses just ahead of the round's pose within the controller's horizon, one that rests in a corner,
+    one that drifts along the lattice's far side."""
+    import obst_ref
+    o, ext, s = _extent(name)
+    dim = len(o)
+    p = session_pose(name)[:dim].astype(F64)
+    ahead = p + np.array([4 * s, 0.0, 0.0])[:dim] if dim == 2 else p + np.array([0.0, 0.0, 6 * s])
+    v0 = np.zeros(dim)
+    v0[1] = 2 * s
+    drift = np.zeros(dim)
+    drift[0] = -s
+    c = np.stack([ahead - v0 * (SESSION_T0 + 1.0), o + 0.03 * ext, o + 0.9 * ext])
+    return obst_ref.make(dim, c, np.stack([v0, np.zeros(dim), drift]), [2 * s, s, 1.5 * s], epoch=0.0, step=s)

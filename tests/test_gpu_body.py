@@ -45,14 +45,15 @@ class Checked:
     """A Controller whose every step with a footprint (and a set of balls, if the case has one) is checked against body_ref fed
     with the device's state from before the call."""
 
-    def __init__(self, c, stream=None):
+    def __init__(self, c, stream=None, ctl=None, env_=None):
         import gpismap_amd
         self.c, self.dim, self.K, self.T, self.seed, self.tick = c, c["dim"], c["K"], c["T"], c["seed"], 0
-        self.sc, self.df, self.dist, self.pl, self.cost = env(self.dim)
+        # env_: (lattice dict, field, its dist flat, planner, its cost flat) of another scene in env(dim)'s place
+        self.sc, self.df, self.dist, self.pl, self.cost = env(self.dim) if env_ is None else env_
         self.stream = stream
-        self.ctl = gpismap_amd.Controller()
+        self.ctl = ctl if ctl is not None else gpismap_amd.Controller()
         self.ctl.init(self.dim, self.K, self.T, seed=self.seed)
-        self.ob = device_set(c["obst"]) if c["obst"] is not None else None
+        self.ob = device_set(c["obst"], self.sc["step"]) if c["obst"] is not None else None
         self.fp = device_body(c["body"])
         self.q_off = 0
 

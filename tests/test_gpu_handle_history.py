@@ -7,7 +7,8 @@ except the weights of the filter and the controller, within 1 in 2^32); b. every
 of a fresh handle given only this call, the fields of info() no reference states included; c. the last call equals the first bit
 for bit.  Times and the round counts of the two iterative solvers (the coverage's labelling, the planner) are not compared: they
 depend on the schedule, not on the state.  Then one session: a single set of handles through rounds on different lattices, on a
-caller's stream, against a set made anew each round on the default stream."""
+caller's stream, against a set made anew each round on the default stream (handles against handles; the chain is tied to the
+references in tests/test_gpu_nav_chain.py)."""
 import ctypes as C
 import math
 
@@ -17,9 +18,11 @@ import pytest
 import dfield_ref
 import history_cases as hc
 import mppi_cases as mc
+import test_gpu_body as tbd
 import test_gpu_cover as tcv
 import test_gpu_locate as tlo
 import test_gpu_mppi as tmp
+import test_gpu_obst as tob
 import test_gpu_pf as tpf
 import test_gpu_plan as tpl
 import test_gpu_render_field as trf
@@ -141,6 +144,93 @@ def test_controller_one_handle_through_changing_shapes():
         return tr
 
     _run(len(hc.CONTROLLER), entry, lambda i: _controller_fresh(hc.controller_case(i))[0])
+
+
+# ---- Controller with balls and a footprint --------------------------------------------------------------------------------------
+def _ctl_body_snap(ctl, **more):
+    return dict(more, get=ctl.get(), info=_strip(ctl.info()), obstacle=ctl.get_obstacle(), obstacle_stats=ctl.obstacle_stats())
+
+
+def _set_handles(c, ob, fp):
+    """The case's set and footprint in the long-lived handles (None where the case has none): their own history."""
+    S, B = c["obst"], c["body"]
+    if S is not None:
+        ob[c["dim"]].set(S["c"], S["v"], S["r"], epoch=S["epoch"])
+        ob[c["dim"]].set_opts(**S["opts"])
+        g = ob[c["dim"]].get()
+        tmp._same_bits(g["centre"], S["c"], "centres")
+        tmp._same_bits(g["radius"], S["r"], "radii")
+    if B is not None:
+        fp[c["dim"]].set(B["b"], B["rho"])
+        tmp._same_bits(fp[c["dim"]].get()["offset"], B["b"], "offsets")
+    return (ob[c["dim"]] if S is not None else None), (fp[c["dim"]] if B is not None else None)
+
+
+def _controller_body_calls(c, init, step, shift, ctl_of):
+    tr = []
+    init()
+    ctl = ctl_of()
+    tr.append(_ctl_body_snap(ctl))
+    ctl.set_nominal(mc.nominal_of(c))
+    tr.append(_ctl_body_snap(ctl))
+    for k in range(2):
+        if k:
+            shift()
+            tr.append(_ctl_body_snap(ctl))
+        u0, info = step(c["t_now"] + k * c["opts"]["dt"])
+        tr.append(_ctl_body_snap(ctl, u0=u0, returned=_strip(info)))
+    return tr
+
+
+def _controller_body_checked(c, ctl, ob, fp):
+    box = {}
+
+    def init():
+        if c["body"] is None:                                        # the plain step, by the plain controller's checker
+            assert c["obst"] is None
+            box["ck"] = tmp.Checked(c, ctl=ctl)
+            box["step"] = lambda t: box["ck"].step()[:2]
+        else:
+            ck = box["ck"] = tbd.Checked(c, ctl=ctl)
+            if ck.ob is not None:
+                ck.ob.close()
+            ck.fp.close()
+            ck.ob, ck.fp = _set_handles(c, ob, fp)
+            box["step"] = lambda t: ck.step(t)[:2]
+    return _controller_body_calls(c, init, lambda t: box["step"](t), lambda: box["ck"].shift(), lambda: box["ck"].ctl)
+
+
+def _controller_body_fresh(c):
+    import gpismap_amd
+    sc, df, dist, pl, cost = tmp.env(c["dim"])
+    ctl = gpismap_amd.Controller()
+    ob = tob.device_set(c["obst"]) if c["obst"] is not None else None
+    fp = tbd.device_body(c["body"]) if c["body"] is not None else None
+    plan = c["terminal"] == "plan"
+    step = lambda t: df.control(ctl, c["pose"], goal=None if plan else sc["goal_point"], planner=pl if plan else None, obstacles=ob, t=t,
+                                footprint=fp, **c["opts"])
+    return _controller_body_calls(c, lambda: ctl.init(c["dim"], c["K"], c["T"], seed=c["seed"]), step, ctl.shift, lambda: ctl)
+
+
+def test_controller_with_balls_and_a_footprint_one_handle_through_changing_shapes():
+    """(dim, K, T, balls, body balls) of history_cases.CONTROLLER_BODY on one Controller, one Obstacles and one Footprint per
+    dimension, set again per entry: init, set_nominal, step, shift, step with the clock moved on.  The per-rollout buffers of the
+    balls grow inside step() under their own capacity: entry 3 steps without balls at the largest K, entry 4 with balls at that K.
+    get_obstacle() and obstacle_stats() are part of every comparison with the fresh controller."""
+    import gpismap_amd
+    ctl = gpismap_amd.Controller()
+    ob = {d: gpismap_amd.Obstacles(d, mc.scene(d)["step"]) for d in (2, 3)}
+    fp = {d: gpismap_amd.Footprint(d) for d in (2, 3)}
+    snaps = []
+
+    def entry(i):
+        snaps.append(_controller_body_checked(hc.controller_body_case(i), ctl, ob, fp))
+        return snaps[-1]
+
+    _run(len(hc.CONTROLLER_BODY), entry, lambda i: _controller_body_fresh(hc.controller_body_case(i)))
+    hit = [[t["obstacle_stats"]["dyn_hit_rollouts"] for t in tr if "u0" in t] for tr in snaps]
+    assert all(min(h) > 0 for h, e in zip(hit, hc.CONTROLLER_BODY) if e[3]) and hit[3] == [0, 0], hit
+    assert [tr[-1]["obstacle_stats"]["n"] for tr in snaps] == [e[3] for e in hc.CONTROLLER_BODY]
 
 
 # ---- ParticleFilter -----------------------------------------------------------------------------------------------------------
@@ -378,13 +468,17 @@ def test_distance_field_rebuilt_on_one_handle():
 
 
 # ---- one session --------------------------------------------------------------------------------------------------------------
-SESSION_KEYS = ("df", "rf", "cv", "r", "v", "pl", "tj", "ctl", "pf", "loc", "t")
+SESSION_KEYS = ("df", "rf", "cv", "r", "v", "pl", "tj", "ctl", "pf", "loc", "t", "ob", "fp", "pp", "pj")
 
 
-def _handles():
+def _handles(dim):
+    """The session's handles: the eleven field consumers, a set of moving balls, a footprint and, in 2-D, a pose planner with the
+    Planner its projection goes into."""
     import gpismap_amd as g
+    step = (hc.SMALL2 if dim == 2 else hc.SMALL3)["step"]
     return dict(df=g.DistanceField(), rf=g.DistanceField(), cv=g.Coverage(), r=g.Renderer(), v=g.ViewScorer(), pl=g.Planner(),
-                tj=g.Trajectories(), ctl=g.Controller(), pf=g.ParticleFilter(), loc=g.Locator(), t=g.Tracker())
+                tj=g.Trajectories(), ctl=g.Controller(), pf=g.ParticleFilter(), loc=g.Locator(), t=g.Tracker(),
+                ob=g.Obstacles(dim, step), fp=g.Footprint(dim), pp=g.PosePlanner() if dim == 2 else None, pj=g.Planner() if dim == 2 else None)
 
 
 def _round(h, name, k, stream):
@@ -396,7 +490,7 @@ def _round(h, name, k, stream):
     shape, origin, step = hc.lat(fd)
     dim = len(shape)
     sv = _void(stream)
-    df, rf, cv, r, v, pl, tj, ctl, pf, loc, t = (h[key] for key in SESSION_KEYS)
+    df, rf, cv, r, v, pl, tj, ctl, pf, loc, t, ob, fp, pp, pj = (h[key] for key in SESSION_KEYS)
     out = {}
     pose = hc.session_pose(name)
     off = np.array((0.03, -0.02), F32)
@@ -442,15 +536,37 @@ def _round(h, name, k, stream):
     pl.trajectories(33, trajectories=tj)
     tj.optimize(rf, stream=stream, iters=5)
     out["traj"] = tj.get()
-    # 11: the controller, two steps with a shift
+    # the footprint along the trajectories; in 2-D the pose plan towards the same goals, its paths and its projection
+    B = hc.session_body(name)
+    fp.set(B["b"], B["rho"])
+    out["traj_body"] = tj.body_clearance(fp, rf, clearance=0.0)
+    if dim == 2:
+        any_heading = lambda x: np.concatenate([np.asarray(x, F32), np.full((len(x), 1), -1, F32)], axis=1)
+        pp.solve(rf, fp, any_heading(goals), H=16, stream=stream, clearance=0.0, margin=0.0, turn=2.5 * step)
+        out["pose_plan"] = pp.get()
+        out["pose_plan_info"] = _strip(pp.info())
+        out["pose_paths"] = pp.paths(any_heading(starts), stream=stream)
+        assert pp.project(pj) is pj
+        out["projection"] = dict(plan=pj.get(), heading2=pp.heading2.copy(), info=_strip(pj.info()))
+    # the timing, its controls, and the timed batch against three balls
+    tm = tj.time(rf, stream=stream, **hc.session_timing(name))
+    out["timing"] = tm
+    out["controls"] = tj.controls(hc.SESSION_DT, 33)
+    S = hc.session_balls(name)
+    ob.set(S["c"], S["v"], S["r"], epoch=S["epoch"])
+    out["check"] = tj.check(ob, hc.SESSION_DT, 66, t_begin=hc.SESSION_T0)
+    # 11: the controller, seeded by follow from the first timed trajectory, two steps with a shift, the balls and the footprint in
+    # every rollout, the clock moved on between the steps; the terminal cost is the projection's (2-D) / the plan's (3-D)
     p64 = pose.astype(F64)
     ctl.init(dim, 257, 33, seed=20 + k)
+    timed = np.flatnonzero(tm["status"] == 0)
+    out["follow"] = ctl.follow(tj, int(timed[0]), hc.SESSION_DT) if timed.size else None
     steps = []
     for j in range(2):
         if j:
             ctl.shift()
-        u0, info = df.control(ctl, p64, planner=pl, stream=sv)
-        steps.append(dict(u0=u0, info=_strip(info)))
+        u0, info = df.control(ctl, p64, planner=pj if dim == 2 else pl, stream=sv, obstacles=ob, t=hc.SESSION_T0 + j * hc.SESSION_DT, footprint=fp)
+        steps.append(dict(u0=u0, info=_strip(info), obstacle=ctl.get_obstacle(), obstacle_stats=ctl.obstacle_stats()))
     out["control"] = dict(steps=steps, get=ctl.get(), info=_strip(ctl.info()))
     # 12: the filter, 13: 300 scored poses, 14: one tracking call
     d = np.linspace(-0.06, 0.06, 7)
@@ -482,19 +598,32 @@ def _round(h, name, k, stream):
 @pytest.mark.parametrize("dim", [2, 3])
 def test_one_session_of_long_lived_handles(dim):
     """A single set of handles (field, restricted field, Coverage, Renderer, ViewScorer, Planner, Trajectories, Controller,
-    ParticleFilter, Locator, Tracker) through rounds on different lattices -- 2-D 60 x 40, 150 x 130, 33 x 20; 3-D 24 x 20 x 16,
-    13 x 11 x 9 -- on one caller's stream; per round from_grid, reset, render a frame, integrate it, frontiers, restrict, next_view
-    over 8 yaws, plan, paths, trajectories, two controller steps, a filter step, 300 scored poses and one tracking call.  Every
-    output equals that of a set made anew for the round on the default stream (the tests above tie fresh handles to the references)."""
+    ParticleFilter, Locator, Tracker, Obstacles, Footprint and, in 2-D, a PosePlanner with the Planner of its projection) through
+    rounds on different lattices -- 2-D 60 x 40, 150 x 130, 33 x 20; 3-D 24 x 20 x 16, 13 x 11 x 9 -- on one caller's stream; per
+    round from_grid, reset, render a frame, integrate it, frontiers, restrict, next_view over 8 yaws, plan, paths, trajectories,
+    the footprint along them, the pose plan with its paths and its projection (2-D), the timing, its controls, the timed batch
+    against three balls, follow, two controller steps with the balls and the footprint, a filter step, 300 scored poses and one
+    tracking call.  Every output equals that of a set made anew for the round on the default stream.  This test compares handles
+    with handles: the tests above tie fresh handles to the references on the inputs of history_cases, and
+    tests/test_gpu_nav_chain.py ties a chain like this one to the references on the chain's own data."""
     import torch
     s = torch.cuda.Stream(device=0)
-    h = _handles()
-    seen_something = 0
+    h = _handles(dim)
+    seen_something, later = 0, [0, 0]                         # rounds that followed a timed trajectory / whose balls hit rollouts
     for k, name in enumerate(hc.SESSION2 if dim == 2 else hc.SESSION3):
         got = _round(h, name, k, s.cuda_stream)
-        _same(got, _round(_handles(), name, k, 0), "round %d on %s" % (k, name))
+        _same(got, _round(_handles(dim), name, k, 0), "round %d on %s" % (k, name))
         print("round %d on %s: %d rays hit, %d seen, %d frontier points in %d clusters, plan reaches %d, filter N_eff %.1f, %d inliers tracked"
               % (k, name, int((got["frame"][2] == 0).sum()), int(got["seen"].sum()), got["frontiers"]["npoints"], got["frontiers"]["label"].size,
                  got["plan_info"]["reachable"], got["filter"]["estimate"]["neff"], got["track"]["result"]["inliers"]))
+        st = [x["obstacle_stats"] for x in got["control"]["steps"]]
+        print("   %d trajectories timed, %d collide with the body, %d with a ball; followed: %s; balls hit %s rollouts of 257%s"
+              % (int((got["timing"]["status"] == 0).sum()), int(got["traj_body"]["collides"].sum()), int(got["check"]["collides"].sum()),
+                 got["follow"] is not None, [x["dyn_hit_rollouts"] for x in st],
+                 "; pose plan reaches %d states" % got["pose_plan_info"]["reachable"] if dim == 2 else ""))
+        assert all(x["n"] == 3 for x in st)
         seen_something += int(got["seen"].sum() > 0 and (got["frame"][2] == 0).any() and got["plan_info"]["reachable"] > 0)
+        later[0] += int(got["follow"] is not None and (got["timing"]["status"] == 0).any())
+        later[1] += int(any(x["dyn_hit_rollouts"] > 0 for x in st))
     assert seen_something >= 2
+    assert later[0] >= 1 and later[1] >= 1, later

@@ -56,10 +56,11 @@ class Checked:
     """A Controller (a new one, or `ctl`: one that has served other calls and is initialised again here) whose every call is
     checked against the reference fed with the device's state from before the call."""
 
-    def __init__(self, c, stream=None, ctl=None):
+    def __init__(self, c, stream=None, ctl=None, env_=None):
         import gpismap_amd
         self.c, self.dim, self.K, self.T, self.seed, self.tick = c, c["dim"], c["K"], c["T"], c["seed"], 0
-        self.sc, self.df, self.dist, self.pl, self.cost = env(self.dim)
+        # env_: (lattice dict, field, its dist flat, planner, its cost flat) of another scene in env(dim)'s place
+        self.sc, self.df, self.dist, self.pl, self.cost = env(self.dim) if env_ is None else env_
         self.stream = stream
         self.ctl = ctl if ctl is not None else gpismap_amd.Controller()
         self.ctl.init(self.dim, self.K, self.T, seed=self.seed)

@@ -40,15 +40,16 @@ def device_set(S, step=None):
 class Checked:
     """A Controller whose every step with a set is checked against obst_ref fed with the device's state from before the call."""
 
-    def __init__(self, c, stream=None):
+    def __init__(self, c, stream=None, ctl=None, env_=None):
         import gpismap_amd
         self.c, self.dim, self.K, self.T, self.seed, self.tick = c, c["dim"], c["K"], c["T"], c["seed"], 0
-        self.sc, self.df, self.dist, self.pl, self.cost = env(self.dim)
+        # env_: (lattice dict, field, its dist flat, planner, its cost flat) of another scene in env(dim)'s place
+        self.sc, self.df, self.dist, self.pl, self.cost = env(self.dim) if env_ is None else env_
         self.stream = stream
-        self.ctl = gpismap_amd.Controller()
+        self.ctl = ctl if ctl is not None else gpismap_amd.Controller()
         self.ctl.init(self.dim, self.K, self.T, seed=self.seed)
         assert self.ctl.obstacle_stats() == dict(dyn_hit_rollouts=0, nominal_dyn_hits=0, nominal_min_sep=np.inf, n=0)
-        self.ob = device_set(c["obst"])
+        self.ob = device_set(c["obst"], self.sc["step"])
         self.q_off = 0
 
     def step(self, t_now=None):

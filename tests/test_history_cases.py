@@ -26,6 +26,25 @@ def test_controller_tree_widths_and_columns():
         assert np.count_nonzero(r["J"][:Kc]) == Kc and np.count_nonzero(r["U"][:Tc]) > 0 and r["hits"][:Kc].any()
 
 
+def test_controller_with_balls_and_a_footprint_grows_both_capacities():
+    """The second controller sequence: every entry with balls has rollouts the balls hit, the plain entry reports none, and the
+    per-rollout buffers of the balls have to grow under a K that init has served before (K of entry 4 == K of entry 3 > every K
+    that stepped with balls before it)."""
+    seq = hc.CONTROLLER_BODY
+    assert seq[0] == seq[-1] and hc.CONTROLLER_BODY_SEEDS[0] == hc.CONTROLLER_BODY_SEEDS[-1] and {e[0] for e in seq} == {2, 3}
+    assert seq[3][3:] == (0, 0) and seq[4][1] == seq[3][1] > max(e[1] for e in seq[:3]) and seq[4][3] > 0 and seq[4][4] > 0
+    assert seq[1][1] > seq[0][1] > seq[2][1] and hc.mppi_segments(seq[2][1]) == 1 and seq[1][3] == 256 and seq[1][4] == 16
+    for i, (dim, K, T, n, m) in enumerate(seq[:-1]):
+        c = hc.controller_body_case(i)
+        assert (c["obst"]["n"] if c["obst"] else 0) == n and (c["body"]["m"] if c["body"] else 0) == m
+        for r in hc.controller_body_ref(i):
+            if n:
+                assert 0 < r["ndyn"] <= K and r["dyn_hits"].any() and np.isfinite(r["min_sep"]).all(), (i, r["ndyn"])
+            else:
+                assert r["ndyn"] == 0 and not r["dyn_hits"].any() and np.isposinf(r["min_sep"]).all(), i
+            assert r["J"].size == K and r["U"].shape[0] == T
+
+
 def test_filter_entries_resample_and_keep():
     dims = [d for d, _ in hc.FILTER]
     ms = [m for _, m in hc.FILTER]
