@@ -373,6 +373,11 @@ def lib():
         L.gpis_body_clearance.argtypes = [vp, vp, dp, C.c_longlong, d, dp, ip, ip, vp]
         L.gpis_body_mppi_step.argtypes = [vp, vp, vp, vp, vp, d, dp, dp, C.POINTER(gpis_mppi_opts), dp, vp]
         L.gpis_body_traj_clearance.argtypes = [vp, vp, vp, d, dp, ip, ip, ip]
+    if hasattr(L, "gpis_smooth_body_optimize"):
+        L.gpis_smooth_body_default_opts.argtypes = [C.c_int, C.c_float, C.c_int, C.POINTER(gpis_traj_opts), C.POINTER(C.c_float)]
+        L.gpis_smooth_body_optimize.argtypes = [vp, vp, vp, C.POINTER(gpis_traj_opts), C.c_float, vp]
+        L.gpis_smooth_body_get.argtypes = [vp, dp, ip, ip, ip]
+        L.gpis_smooth_from_pose_paths.argtypes = [vp, vp, C.c_int]
     if hasattr(L, "gpis_cover_create"):
         co, ub, ll = C.POINTER(gpis_cover_opts), C.POINTER(C.c_ubyte), C.POINTER(C.c_longlong)
         L.gpis_cover_default_opts.argtypes = [C.c_int, C.c_float, co]
@@ -1289,18 +1294,21 @@ class DistanceField:
             self._planner = Planner()
         return self._planner
 
-    def smooth(self, x_or_planner, N=64, trajectories=None, stream=0, **opts):
-        """Trajectories through this field (gpis_traj_*): the last paths of a Planner resampled to N waypoints each, or the
-        caller's waypoints [m, N, dim], run through the covariant gradient descent and evaluated.  opts: the gpis_traj_opts
-        fields (clearance, margin, w_smooth, w_obs, rate, max_move, tol, iters, sub; defaults for this field's step);
-        iters=0 is the collision check alone.  Returns the Trajectories holding the result (default: one kept by this field);
-        it stays valid when the field is recomputed."""
+    def smooth(self, x_or_planner, N=64, trajectories=None, stream=0, footprint=None, w_turn=None, **opts):
+        """Trajectories through this field (gpis_traj_*): the last paths of a Planner (or the points of a PosePlanner's)
+        resampled to N waypoints each, or the caller's waypoints [m, N, dim], run through the covariant gradient descent and
+        evaluated.  opts: the gpis_traj_opts fields (clearance, margin, w_smooth, w_obs, rate, max_move, tol, iters, sub;
+        defaults for this field's step); iters=0 is the collision check alone.  footprint, w_turn: Trajectories.optimize's
+        (smoothing for the body, gpis_smooth_body_optimize).  Returns the Trajectories holding the result (default: one kept by
+        this field); it stays valid when the field is recomputed."""
         t = trajectories if trajectories is not None else self._own_trajectories()
         if isinstance(x_or_planner, Planner):
             t.from_paths(x_or_planner, N)
+        elif isinstance(x_or_planner, PosePlanner):
+            t.from_pose_paths(x_or_planner, N)
         else:
             t.set(x_or_planner)
-        return t.optimize(self, stream=stream, **opts)
+        return t.optimize(self, footprint=footprint, w_turn=w_turn, stream=stream, **opts)
 
     def _own_trajectories(self):
         if getattr(self, "_trajectories", None) is None:
@@ -1726,6 +1734,13 @@ class PosePlanner:
         self.last_off = off
         return ([pts[off[k]:off[k + 1]] for k in range(m.value)], [hd[off[k]:off[k + 1]] for k in range(m.value)], sc, st)
 
+    def trajectories(self, N=64, trajectories=None):
+        """The points of the last paths() resampled by arc length to N waypoints each (gpis_smooth_from_pose_paths; the heading
+        indices are not carried over).  Returns the Trajectories holding the input (default: a new one), ready for
+        optimize(field, footprint=...)."""
+        t = trajectories if trajectories is not None else Trajectories()
+        return t.from_pose_paths(self, N)
+
     def project(self, planner=None):
         """The 2-D summary of the last result in a Planner (gpis_pplan_project; default: a new one): cost2 = the least cost
         over the headings, a policy that descends it, c2 = the least point cost over the free headings.  Planner.paths,
@@ -1985,6 +2000,19 @@ def traj_opts(dim, step, **opts):
     return o
 
 
+def traj_body_opts(dim, step, balls, **opts):
+    """(gpis_traj_opts, w_turn) of the library's defaults for smoothing with a footprint of `balls` balls
+    (gpis_smooth_body_default_opts: traj_opts with w_obs = 0.25 step / balls; w_turn = 1) with the given fields replaced."""
+    o, wt = gpis_traj_opts(), C.c_float(0)
+    _check(lib().gpis_smooth_body_default_opts(int(dim), float(step), int(balls), C.byref(o), C.byref(wt)), "gpis_smooth_body_default_opts")
+    names = {f[0] for f in gpis_traj_opts._fields_}
+    for k, v in opts.items():
+        if k not in names:
+            raise GpisError("unknown trajectory option %r" % k)
+        setattr(o, k, v)
+    return o, float(wt.value)
+
+
 class Trajectories:
     """Input and result holder of the trajectory optimiser (gpis_traj_*): a batch of m trajectories of N waypoints on the
     device, buffers reused across calls.  optimize() always starts from the input; a result does not depend on the field or the
@@ -2022,14 +2050,39 @@ class Trajectories:
         _check(self.L.gpis_traj_set(self.h, _p(x), x.shape[0], x.shape[1], x.shape[2]), "gpis_traj_set")
         return self
 
-    def optimize(self, field, stream=0, **opts):
-        """gpis_traj_optimize on a DistanceField holding a result.  Returns self."""
+    def from_pose_paths(self, pose_planner, N=64):
+        """The input from the points of a PosePlanner's last paths() resampled as from_paths does (gpis_smooth_from_pose_paths); a
+        turn in place repeats a point and takes no part of the length.  Returns self."""
+        _check(self.L.gpis_smooth_from_pose_paths(self.h, pose_planner.h, int(N)), "gpis_smooth_from_pose_paths")
+        return self
+
+    def optimize(self, field, footprint=None, w_turn=None, stream=0, **opts):
+        """gpis_traj_optimize on a DistanceField holding a result.  footprint: a Footprint whose balls take the obstacle term in
+        the waypoint's place, the body facing along its chord (gpis_smooth_body_optimize; the defaults are traj_body_opts');
+        w_turn weighs the term that turns the chords (default 1).  Returns self."""
         inf = field.info()
         if inf["dim"] == 0:
             raise GpisError("distance field holds no result")
-        o = traj_opts(inf["dim"], inf["step"], **opts)
-        _check(self.L.gpis_traj_optimize(self.h, field.h, C.byref(o), C.c_void_p(stream)), "gpis_traj_optimize")
+        if footprint is None:
+            if w_turn is not None:
+                raise GpisError("w_turn belongs to a footprint")
+            o = traj_opts(inf["dim"], inf["step"], **opts)
+            _check(self.L.gpis_traj_optimize(self.h, field.h, C.byref(o), C.c_void_p(stream)), "gpis_traj_optimize")
+            return self
+        o, wt = traj_body_opts(inf["dim"], inf["step"], max(footprint.info()["m"], 1), **opts)   # (an empty one: the call refuses it)
+        wt = wt if w_turn is None else float(w_turn)
+        _check(self.L.gpis_smooth_body_optimize(self.h, field.h, footprint.h, C.byref(o), C.c_float(wt), C.c_void_p(stream)),
+               "gpis_smooth_body_optimize")
         return self
+
+    def body_result(self):
+        """The body result of the last optimize() with a footprint (gpis_smooth_body_get): what body_clearance(footprint, field,
+        clearance) returns on the result, kept by the same launch.  dict(D_min [m] f64, waypoint, ball, collides [m] i32)."""
+        m = self.info()["m"]
+        r = dict(D_min=np.zeros(m, np.float64), waypoint=np.zeros(m, np.int32), ball=np.zeros(m, np.int32), collides=np.zeros(m, np.int32))
+        _check(self.L.gpis_smooth_body_get(self.h, _p(r["D_min"], C.c_double), _p(r["waypoint"], C.c_int), _p(r["ball"], C.c_int),
+                                         _p(r["collides"], C.c_int)), "gpis_smooth_body_get")
+        return r
 
     def info(self):
         out = np.zeros(len(self.INFO_KEYS), dtype=np.float64)

@@ -2075,6 +2075,53 @@ int gpis_body_traj_clearance(void* traj, void* df, void* body, double clearance,
     catch (...) { return GPIS_ERR_STATE; }
 }
 
+// ---- smoothing for the robot's footprint ---------------------------------------------------------------------------------------
+int gpis_smooth_body_default_opts(int dim, float step, int balls, gpis_traj_opts* o, float* w_turn) {
+    if (balls < 1 || balls > Footprint::kMax) return GPIS_ERR_ARG;
+    if (int rc = gpis_traj_default_opts(dim, step, o)) return rc;
+    o->w_obs = (0.25f * step) / (float)balls;
+    if (w_turn) *w_turn = 1.f;
+    return GPIS_OK;
+}
+int gpis_smooth_body_optimize(void* traj, void* d, void* body, const gpis_traj_opts* opts, float w_turn, void* stream) {
+    if (!traj || !d || !body) return GPIS_ERR_ARG;
+    if (!std::isfinite(w_turn) || w_turn < 0.f) return GPIS_ERR_ARG;
+    Trajectories& t = *(Trajectories*)traj;
+    const DistanceField& df = *(const DistanceField*)d;
+    const Footprint& b = *(const Footprint*)body;
+    if (b.m == 0) return GPIS_ERR_ARG;
+    gpis_traj_opts dflt;
+    if (!opts) {
+        if (!df.valid) return GPIS_ERR_STATE;
+        (void)gpis_smooth_body_default_opts(df.dim, df.step, b.m, &dflt, nullptr);
+        opts = &dflt;
+    }
+    TrajOpts o;
+    o.clearance = opts->clearance; o.margin = opts->margin; o.w_smooth = opts->w_smooth; o.w_obs = opts->w_obs; o.rate = opts->rate;
+    o.max_move = opts->max_move; o.tol = opts->tol; o.iters = opts->iters; o.sub = opts->sub;
+    if (int rc = traj_check_opts(o)) return rc;
+    if (!df.valid || !t.has_input) return GPIS_ERR_STATE;
+    if (b.dim != df.dim || df.dim != t.dim || b.device != df.device) return GPIS_ERR_ARG;
+    const BodyArgs bd{b.d_tab, b.m};
+    DeviceScope ds(df.device);
+    try { return t.optimize(df, o, stream ? (hipStream_t)stream : df.own, &bd, w_turn); }
+    catch (...) { t.valid = t.body_valid = false; return GPIS_ERR_STATE; }
+}
+int gpis_smooth_body_get(void* traj, double* D_min, int* waypoint, int* ball, int* collides) {
+    if (!traj) return GPIS_ERR_ARG;
+    Trajectories& t = *(Trajectories*)traj;
+    if (!t.valid || !t.body_valid) return GPIS_ERR_STATE;
+    DeviceScope ds(t.device);
+    try { return t.body_result(D_min, waypoint, ball, collides); } catch (...) { return GPIS_ERR_STATE; }
+}
+int gpis_smooth_from_pose_paths(void* traj, void* pplan, int N) {
+    if (!traj || !pplan) return GPIS_ERR_ARG;
+    Trajectories& t = *(Trajectories*)traj;
+    const PosePlanner& p = *(const PosePlanner*)pplan;
+    DeviceScope ds(p.device);
+    try { return t.from_pose_paths(p, N); } catch (...) { t.has_input = t.valid = t.body_valid = false; return GPIS_ERR_STATE; }
+}
+
 // ---- routes for the robot's footprint: the pose planner ------------------------------------------------------------------------
 int gpis_pplan_default_opts(float step, int H, gpis_pplan_opts* o) {
     if (!o || !(std::isfinite(step) && step > 0.f) || (H != 8 && H != 16 && H != 32 && H != 64)) return GPIS_ERR_ARG;

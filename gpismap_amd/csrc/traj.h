@@ -7,6 +7,8 @@
 // On top of a result: speeds and times under speed and acceleration limits, control sequences of the sampling
 // controller's model through the timed positions, and one of them written into a controller's nominal sequence on the device;
 // the bits are those of tests/timing_ref.py.
+// With a footprint the obstacle term acts at the body's balls, the body facing along its chord, and the same
+// launch keeps the body's clearance along the result; the bits are those of tests/traj_body_ref.py.
 #pragma once
 #include <cstdint>
 #include <vector>
@@ -16,6 +18,7 @@ namespace gpis {
 
 struct DistanceField;
 struct Planner;
+struct PosePlanner;
 
 struct TrajOpts {
     float clearance = 0.f, margin = 1.f, w_smooth = 1.f, w_obs = 0.f, rate = 0.f, max_move = 0.f, tol = 0.f;
@@ -74,9 +77,14 @@ struct Trajectories {
     double* d_bodyd = nullptr;                       // [m] D_min
     int* d_bodyi = nullptr;                          // [m][3] waypoint, ball, collides
     size_t cap_body = 0;
+    // the body result of the last optimize() with a footprint
+    double* d_bresd = nullptr;                       // [m] D_min
+    int* d_bresi = nullptr;                          // [m][3] waypoint, ball, collides
+    size_t cap_bres = 0;
 
     int m = 0, N = 0, dim = 0;
     bool has_input = false, valid = false, timed = false;
+    bool body_valid = false;                         // the last result came with a footprint: d_bresd, d_bresi hold its body result
     double opt_ms = 0.0, time_ms = 0.0, controls_ms = 0.0;
 
     Trajectories();
@@ -84,10 +92,17 @@ struct Trajectories {
     int bind(int dev);                               // move to `dev`, the input carried along (the result is dropped)
     // the input from the planner's last paths, N waypoints each; moves to the planner's device; synchronises the own stream
     int from_paths(const Planner& p, int N);
+    // the same from a pose planner's last paths (their points; the heading indices are not carried over): a segment of no
+    // length -- a turn in place -- gives w = 0
+    int from_pose_paths(const PosePlanner& p, int N);
     // the input from host waypoints [m][N][dim]
     int set(const float* x, int m, int N, int dim);
-    // descent and evaluation from the input on df's dist; synchronises `s`
-    int optimize(const DistanceField& df, const TrajOpts& o, hipStream_t s);
+    // descent and evaluation from the input on df's dist; synchronises `s`.  bd: nullptr for the point, else a footprint of this
+    // dim on df's device with m > 0 (checked by the caller): the obstacle term acts at its balls, the turn term has the weight
+    // w_turn, and the body result is kept
+    int optimize(const DistanceField& df, const TrajOpts& o, hipStream_t s, const BodyArgs* bd = nullptr, float w_turn = 0.f);
+    // the body result of the last optimize() with a footprint; host outputs [m], any may be nullptr; synchronises the own stream
+    int body_result(double* D_min, int* waypoint, int* ball, int* collides);
     // speeds, times and limiter codes of the last result; df: nullptr or a field on this device; s: nullptr for the field's
     // (the own) stream; synchronises it
     int time(const DistanceField* df, const TimingOpts& o, hipStream_t s);
@@ -108,6 +123,8 @@ struct Trajectories {
 
 private:
     int ensure(int m, int N, int dim);
+    int from_packed(int dev, long long npaths, long long npoints, int dim, const long long* off, const float* pts,
+                    const unsigned char* pstat, int N, bool zero_w);
 };
 
 // GPIS_ERR_ARG on anything gpis_traj_optimize documents as an argument error of the options

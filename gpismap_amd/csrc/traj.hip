@@ -21,6 +21,7 @@
 #include "body.h"
 #include "dfield.h"
 #include "plan.h"
+#include "pplan.h"
 
 namespace gpis {
 
@@ -56,6 +57,8 @@ __global__ void __launch_bounds__(kBlock) traj_arc_kernel(const long long* __res
 
 // one thread per waypoint: t_i = (float)i * (s_{L-1} / (float)(N - 1)), the last segment k <= L - 2 with s_k <= t_i by bisection,
 // x_i = Q_k + w (Q_{k+1} - Q_k); the two ends are copies.  A path of another status than 0: NaN and input status 2.
+// ZERO_W (pose paths, DESIGN.md §7t: a turn in place repeats a point): w = 0 on a segment of no length.
+template <bool ZERO_W>
 __global__ void __launch_bounds__(kBlock) traj_resample_kernel(const long long* __restrict__ off, const float* __restrict__ pts,
                                                                const unsigned char* __restrict__ pstat,
                                                                const float* __restrict__ arc, int m, int N, int dim,
@@ -84,7 +87,7 @@ __global__ void __launch_bounds__(kBlock) traj_resample_kernel(const long long* 
             const long long mid = (lo + hi + 1) >> 1;
             if (s[mid] <= t) lo = mid; else hi = mid - 1;
         }
-        const float w = (t - s[lo]) / (s[lo + 1] - s[lo]);
+        const float w = ZERO_W && s[lo + 1] == s[lo] ? 0.f : (t - s[lo]) / (s[lo + 1] - s[lo]);
         const float* q0 = q + (size_t)lo * dim;
         for (int a = 0; a < dim; ++a) out[a] = q0[a] + w * (q0[dim + a] - q0[a]);
     }
@@ -112,19 +115,59 @@ __device__ __forceinline__ TrajSample traj_sample(const float* __restrict__ F, c
     return s;
 }
 
+// The heading a waypoint takes from the horizontal chords of its trajectory (the chord rule of DESIGN.md §7r, the one statement
+// of it): waypoint k's first two components are x0[k st], x1[k st].  The first chord k >= min(i, N - 2) with a horizontal length
+// > 0, else the last one before, else (1, 0); double from the float32 waypoints.  own: the chord min(i, N - 2) itself has a
+// length (then nn is that length).
+struct TrajChord {
+    double c, s, nn;
+    bool own;
+};
+
+__device__ __forceinline__ TrajChord traj_chord_heading(const float* x0, const float* x1, int st, int i, int N) {
+    const int k0 = min(i, N - 2);
+    TrajChord h{1.0, 0.0, 1.0, false};
+    bool found = false;
+    for (int pass = 0; pass < 2 && !found; ++pass) {
+        // pass 0: k = k0 .. N - 2 ascending; pass 1: k = k0 - 1 .. 0 descending
+        for (int k = pass == 0 ? k0 : k0 - 1; pass == 0 ? k <= N - 2 : k >= 0; k += pass == 0 ? 1 : -1) {
+            const double e0 = (double)x0[(k + 1) * st] - (double)x0[k * st], e1 = (double)x1[(k + 1) * st] - (double)x1[k * st];
+            const double n2 = e0 * e0 + e1 * e1;
+            if (n2 > 0.0) {
+                const double nn = sqrt(n2);
+                h.c = e0 / nn; h.s = e1 / nn; h.nn = nn;
+                h.own = k == k0;
+                found = true;
+                break;
+            }
+        }
+    }
+    return h;
+}
+
 // One workgroup per trajectory, blockDim.x = 64 ceil(N / 64).  fres[t] = length, smoothness, obstacle cost, min_dist;
 // ires[t] = status, iterations, non-finite samples, collides.
-template <int DIM>
+// BODY (the contract: tests/traj_body_ref.py): the obstacle term acts at the balls of the footprint bd.  Every lane
+// of a waypoint (the ends too) takes its chord's heading from x in LDS, walks the table by a pointer whose index is the same in
+// every lane, and sums the force and the torque over ascending j; the torque over the chord's length along the chord's normal
+// is t_i, kept in LDS, and an interior lane gathers T_{i-1} - T_i after one barrier.  The evaluation walks the table once more:
+// the obstacle cost at the balls and the body rule of every waypoint, reduced as traj_body_check_kernel does.
+// bres_d[t] = D_min; bres_i[t][3] = waypoint, ball, collides.  Without BODY the last four arguments are not read.
+template <int DIM, bool BODY>
 __global__ void __launch_bounds__(kBlock) traj_opt_kernel(const float* __restrict__ F, DfLattice L, const float* __restrict__ xin,
                                                           const unsigned char* __restrict__ instat, int N, TrajOpts o,
                                                           float* __restrict__ xout, float* __restrict__ fres,
-                                                          int* __restrict__ ires) {
+                                                          int* __restrict__ ires, BodyArgs bd, float w_turn,
+                                                          double* __restrict__ bres_d, int* __restrict__ bres_i) {
     __shared__ float sx[DIM][kTree];
     __shared__ float sg[DIM][kTree];
     __shared__ float ssum[3][kTree];
     __shared__ float smin[kTree];
     __shared__ int scnt[kTree];
     __shared__ float swave[kBlock / 64];
+    __shared__ float sT[2][kTree];                       // (BODY only, as the two below)
+    __shared__ double shd[kBlock / 64];
+    __shared__ int shi[kBlock / 64];
     const int tr = blockIdx.x, t = threadIdx.x, n = N - 2, nthr = blockDim.x;
     const size_t base = (size_t)tr * N * DIM;
     const float nan = __int_as_float(0x7fc00000);
@@ -137,6 +180,10 @@ __global__ void __launch_bounds__(kBlock) traj_opt_kernel(const float* __restric
         if (t == 0) {
             for (int k = 0; k < 4; ++k) fres[(size_t)tr * 4 + k] = nan;
             ires[(size_t)tr * 4 + 0] = 2; ires[(size_t)tr * 4 + 1] = 0; ires[(size_t)tr * 4 + 2] = 0; ires[(size_t)tr * 4 + 3] = 0;
+            if constexpr (BODY) {
+                bres_d[tr] = (double)NAN;
+                bres_i[(size_t)tr * 3] = -1; bres_i[(size_t)tr * 3 + 1] = -1; bres_i[(size_t)tr * 3 + 2] = 0;
+            }
         }
         return;
     }
@@ -154,7 +201,62 @@ __global__ void __launch_bounds__(kBlock) traj_opt_kernel(const float* __restric
         float xi[DIM], g[DIM];
 #pragma unroll
         for (int a = 0; a < DIM; ++a) { xi[a] = 0.f; g[a] = 0.f; }
-        if (interior) {
+        if constexpr (BODY) {
+            float f[DIM], t0 = 0.f, t1 = 0.f;
+#pragma unroll
+            for (int a = 0; a < DIM; ++a) f[a] = 0.f;
+            if (t < N) {
+#pragma unroll
+                for (int a = 0; a < DIM; ++a) xi[a] = sx[a][t];
+                const TrajChord h = traj_chord_heading(sx[0], sx[1], 1, t, N);
+                const double p[3] = {(double)xi[0], (double)xi[1], DIM == 3 ? (double)xi[DIM - 1] : 0.0};
+                const double* __restrict__ row = bd.tab;
+                float tau = 0.f;
+                for (int j = 0; j < bd.m; ++j, row += 4) {
+                    double w[3] = {0.0, 0.0, 0.0};
+                    body_ball_at<DIM>(row, p, h.c, h.s, w);
+                    const float pw[3] = {(float)w[0], (float)w[1], (float)w[2]};
+                    const TrajSample s = traj_sample<DIM>(F, L, pw);
+                    const float d = (float)((double)s.d - row[3]);
+                    float q = 0.f;
+                    if (s.fin) {
+                        const float e = d - o.clearance;
+                        if (e >= o.margin) q = 0.f;
+                        else if (e >= 0.f) q = (e - o.margin) / o.margin;
+                        else q = -1.f;
+                    }
+                    const float r0 = (float)((-h.s) * row[0] - h.c * row[1]), r1 = (float)(h.c * row[0] - h.s * row[1]);
+                    float gr[DIM];
+#pragma unroll
+                    for (int a = 0; a < DIM; ++a) {
+                        gr[a] = s.fin ? s.g[a] : 0.f;
+                        const float fj = q * gr[a];
+                        f[a] = j ? f[a] + fj : fj;
+                    }
+                    const float tj = q * (gr[0] * r0 + gr[1] * r1);
+                    tau = j ? tau + tj : tj;
+                }
+                if (h.own) {
+                    const float u = tau / (float)h.nn;
+                    t0 = u * (-(float)h.s);
+                    t1 = u * (float)h.c;
+                }
+            }
+            sT[0][t] = t0; sT[1][t] = t1;
+            __syncthreads();
+            if (interior) {
+#pragma unroll
+                for (int a = 0; a < DIM; ++a) {
+                    const float aa = (xi[a] - sx[a][t - 1]) + (xi[a] - sx[a][t + 1]);
+                    if (a < 2) {
+                        const float Ti = t == N - 2 ? sT[a][t] + sT[a][t + 1] : sT[a][t];
+                        g[a] = o.w_smooth * aa + o.w_obs * (f[a] + w_turn * (sT[a][t - 1] - Ti));
+                    } else {
+                        g[a] = o.w_smooth * aa + o.w_obs * f[a];
+                    }
+                }
+            }
+        } else if (interior) {
 #pragma unroll
             for (int a = 0; a < DIM; ++a) xi[a] = sx[a][t];
             const TrajSample s = traj_sample<DIM>(F, L, xi);
@@ -217,13 +319,45 @@ __global__ void __launch_bounds__(kBlock) traj_opt_kernel(const float* __restric
     for (int k = t; k < kTree; k += nthr) { ssum[0][k] = 0.f; ssum[1][k] = 0.f; ssum[2][k] = 0.f; smin[k] = INFINITY; scnt[k] = 0; }
     float len = 0.f, sm = 0.f, oc = 0.f, md = INFINITY;
     int nf = 0;
+    [[maybe_unused]] double bbest = INFINITY;
+    [[maybe_unused]] int bwp = -1, bjm = -1, bbad = 0, boff = 0;
     if (t < N) {
         float xi[DIM];
 #pragma unroll
         for (int a = 0; a < DIM; ++a) { xi[a] = sx[a][t]; xout[base + (size_t)t * DIM + a] = xi[a]; }
         const TrajSample s = traj_sample<DIM>(F, L, xi);
         if (isfinite(s.d)) md = s.d; else ++nf;
-        if (interior && s.fin) {
+        if constexpr (BODY) {
+            // the body at the result's heading: the obstacle cost at the balls (interior waypoints) and the body rule
+            const TrajChord h = traj_chord_heading(sx[0], sx[1], 1, t, N);
+            const double p[3] = {(double)xi[0], (double)xi[1], DIM == 3 ? (double)xi[DIM - 1] : 0.0};
+            const double* __restrict__ row = bd.tab;
+            double D = INFINITY;
+            int jm = 0;
+            bool off = false;
+            for (int j = 0; j < bd.m; ++j, row += 4) {
+                double w[3] = {0.0, 0.0, 0.0};
+                body_ball_at<DIM>(row, p, h.c, h.s, w);
+                const float pw[3] = {(float)w[0], (float)w[1], (float)w[2]};
+                const TrajSample u = traj_sample<DIM>(F, L, pw);
+                const double d = (double)u.d - row[3];
+                off = off || d != d;
+                if (d < D) { D = d; jm = j; }
+                float cj = 0.f;
+                if (interior && u.fin) {
+                    const float e = (float)d - o.clearance;
+                    if (e >= o.margin) cj = 0.f;
+                    else if (e >= 0.f) { const float v = e - o.margin; cj = (v * v) / (2.f * o.margin); }
+                    else cj = 0.5f * o.margin - e;
+                }
+                oc = j ? oc + cj : cj;
+            }
+            if (off) { boff = 1; bbad = 1; }
+            else {
+                bbad = D < (double)o.clearance ? 1 : 0;
+                if (D < bbest) { bbest = D; bwp = t; bjm = jm; }
+            }
+        } else if (interior && s.fin) {
             const float e = s.d - o.clearance;
             if (e >= o.margin) oc = 0.f;
             else if (e >= 0.f) { const float u = e - o.margin; oc = (u * u) / (2.f * o.margin); }
@@ -265,6 +399,33 @@ __global__ void __launch_bounds__(kBlock) traj_opt_kernel(const float* __restric
         fres[(size_t)tr * 4 + 3] = smin[0];
         ires[(size_t)tr * 4 + 0] = status; ires[(size_t)tr * 4 + 1] = used; ires[(size_t)tr * 4 + 2] = scnt[0];
         ires[(size_t)tr * 4 + 3] = smin[0] < o.clearance ? 1 : 0;
+    }
+    if constexpr (BODY) {
+        // the least D (a min of doubles that are never NaN where they were taken: order-free), then the least waypoint among the
+        // lanes that hold it, and that lane writes
+        const double bmin = block_reduce(bbest, OpMin(), shd, nthr, (double)INFINITY);
+        if (t == 0) shd[0] = bmin;
+        __syncthreads();
+        const double least = shd[0];
+        const int key = bwp >= 0 && bbest == least ? bwp : 0x7fffffff;
+        const int kmin = block_reduce(key, OpMin(), shi, nthr, 0x7fffffff);
+        if (t == 0) shi[0] = kmin;
+        __syncthreads();
+        const int win = shi[0];
+        __syncthreads();
+        const int nbad = block_reduce(bbad, OpAdd(), shi, nthr, 0);
+        const int noff = block_reduce(boff, OpAdd(), shi, nthr, 0);
+        if (t == 0) {
+            bres_i[(size_t)tr * 3 + 2] = nbad > 0 ? 1 : 0;
+            if (win == 0x7fffffff) {                     // no waypoint gave a D below +inf
+                bres_d[tr] = noff == N ? (double)NAN : (double)INFINITY;
+                bres_i[(size_t)tr * 3] = -1; bres_i[(size_t)tr * 3 + 1] = -1;
+            }
+        }
+        if (bwp >= 0 && bwp == win) {
+            bres_d[tr] = bbest;
+            bres_i[(size_t)tr * 3] = bwp; bres_i[(size_t)tr * 3 + 1] = bjm;
+        }
     }
 }
 
@@ -656,24 +817,9 @@ __global__ void __launch_bounds__(kBlock) traj_body_check_kernel(const float* __
     double best = INFINITY;
     int wp = -1, jm = -1, bad = 0, off = 0;
     if (i < N) {
-        const int k0 = min(i, N - 2);
-        double c = 1.0, s = 0.0;
-        bool found = false;
-        for (int pass = 0; pass < 2 && !found; ++pass) {
-            // pass 0: k = k0 .. N - 2 ascending; pass 1: k = k0 - 1 .. 0 descending
-            for (int k = pass == 0 ? k0 : k0 - 1; pass == 0 ? k <= N - 2 : k >= 0; k += pass == 0 ? 1 : -1) {
-                const double e0 = (double)sx[k + 1][0] - (double)sx[k][0], e1 = (double)sx[k + 1][1] - (double)sx[k][1];
-                const double n2 = e0 * e0 + e1 * e1;
-                if (n2 > 0.0) {
-                    const double nn = sqrt(n2);
-                    c = e0 / nn; s = e1 / nn;
-                    found = true;
-                    break;
-                }
-            }
-        }
+        const TrajChord h = traj_chord_heading(&sx[0][0], &sx[0][1], 2, i, N);
         double p[3] = {(double)sx[i][0], (double)sx[i][1], DIM == 3 ? (double)xt[(size_t)i * DIM + 2] : 0.0};
-        const double d = body_clearance_at<DIM>(F, Lc, bd.tab, bd.m, p, c, s, &jm);
+        const double d = body_clearance_at<DIM>(F, Lc, bd.tab, bd.m, p, h.c, h.s, &jm);
         if (d != d) { off = 1; bad = 1; }
         else {
             bad = d < clearance ? 1 : 0;
@@ -744,7 +890,8 @@ int Trajectories::bind(int dev) {
         }
         for (void* p : {(void*)d_in, (void*)d_x, (void*)d_instat, (void*)d_fres, (void*)d_ires, (void*)d_arc, (void*)d_tv, (void*)d_tt,
                         (void*)d_lim, (void*)d_tsum, (void*)d_tint, (void*)d_cu, (void*)d_chp, (void*)d_cclamp, (void*)d_follow,
-                        (void*)d_chkd, (void*)d_chki, (void*)d_bodyd, (void*)d_bodyi})
+                        (void*)d_chkd, (void*)d_chki, (void*)d_bodyd, (void*)d_bodyi, (void*)d_bresd,
+                        (void*)d_bresi})
             (void)hipFree(p);
         if (own) (void)hipStreamDestroy(own);
     }
@@ -752,8 +899,9 @@ int Trajectories::bind(int dev) {
     d_tv = d_tt = d_tsum = nullptr; d_lim = nullptr; d_tint = nullptr; d_cu = d_chp = d_follow = nullptr; d_cclamp = nullptr;
     d_chkd = nullptr; d_chki = nullptr; cap_chk = 0;
     d_bodyd = nullptr; d_bodyi = nullptr; cap_body = 0;
+    d_bresd = nullptr; d_bresi = nullptr; cap_bres = 0;
     cap_x = cap_m = cap_arc = cap_tn = cap_tm = cap_cu = cap_cm = 0;
-    has_input = valid = timed = false;
+    has_input = valid = timed = body_valid = false;
     m = N = dim = 0;
     device = dev;
     if (dev < 0) return GPIS_OK;
@@ -790,31 +938,45 @@ int Trajectories::ensure(int mm, int NN, int dd) {
     return GPIS_OK;
 }
 
+int Trajectories::from_packed(int dev, long long npaths, long long npoints, int dd, const long long* off, const float* pts,
+                              const unsigned char* pstat, int NN, bool zero_w) {
+    has_input = valid = timed = body_valid = false;
+    if (int rc = bind(dev)) return rc;
+    const int mm = (int)npaths;
+    if (int rc = ensure(mm, NN, dd)) return rc;
+    if (int rc = grow(d_arc, cap_arc, (size_t)std::max(1ll, npoints))) return rc;
+    hipLaunchKernelGGL(traj_arc_kernel, dim3(grid_for(mm, kBlock, kGridCapTraj)), dim3(kBlock), 0, own, off, pts, pstat, mm, dd, d_arc);
+    GPIS_HIP(hipGetLastError());
+    const dim3 grid(grid_for((long long)mm * NN, kBlock, kGridCapTraj));
+    if (zero_w)
+        hipLaunchKernelGGL(traj_resample_kernel<true>, grid, dim3(kBlock), 0, own, off, pts, pstat, d_arc, mm, NN, dd, d_in, d_instat);
+    else
+        hipLaunchKernelGGL(traj_resample_kernel<false>, grid, dim3(kBlock), 0, own, off, pts, pstat, d_arc, mm, NN, dd, d_in, d_instat);
+    GPIS_HIP(hipGetLastError());
+    GPIS_HIP(hipStreamSynchronize(own));
+    m = mm; N = NN; dim = dd;
+    has_input = true;
+    return GPIS_OK;
+}
+
 int Trajectories::from_paths(const Planner& p, int NN) {
     if (NN < kMinN || NN > kMaxN) return GPIS_ERR_ARG;
     if (!p.valid || !p.paths_valid) return GPIS_ERR_STATE;
     if (p.npaths > kMaxTraj) return GPIS_ERR_LIMIT;
-    has_input = valid = timed = false;
-    if (int rc = bind(p.device)) return rc;
-    const int mm = (int)p.npaths;
-    if (int rc = ensure(mm, NN, p.dim)) return rc;
-    if (int rc = grow(d_arc, cap_arc, (size_t)std::max(1ll, p.npoints))) return rc;
-    hipLaunchKernelGGL(traj_arc_kernel, dim3(grid_for(mm, kBlock, kGridCapTraj)), dim3(kBlock), 0, own, p.d_off, p.d_points, p.d_status, mm,
-                       p.dim, d_arc);
-    GPIS_HIP(hipGetLastError());
-    hipLaunchKernelGGL(traj_resample_kernel, dim3(grid_for((long long)mm * NN, kBlock, kGridCapTraj)), dim3(kBlock), 0, own, p.d_off,
-                       p.d_points, p.d_status, d_arc, mm, NN, p.dim, d_in, d_instat);
-    GPIS_HIP(hipGetLastError());
-    GPIS_HIP(hipStreamSynchronize(own));
-    m = mm; N = NN; dim = p.dim;
-    has_input = true;
-    return GPIS_OK;
+    return from_packed(p.device, p.npaths, p.npoints, p.dim, p.d_off, p.d_points, p.d_status, NN, false);
+}
+
+int Trajectories::from_pose_paths(const PosePlanner& p, int NN) {
+    if (NN < kMinN || NN > kMaxN) return GPIS_ERR_ARG;
+    if (!p.valid || !p.paths_valid) return GPIS_ERR_STATE;
+    if (p.npaths > kMaxTraj) return GPIS_ERR_LIMIT;
+    return from_packed(p.device, p.npaths, p.npoints, 2, p.d_off, p.d_points, p.d_status, NN, true);
 }
 
 int Trajectories::set(const float* x, int mm, int NN, int dd) {
     if (!x || mm < 1 || NN < kMinN || NN > kMaxN || (dd != 2 && dd != 3)) return GPIS_ERR_ARG;
     if (mm > kMaxTraj) return GPIS_ERR_LIMIT;
-    has_input = valid = timed = false;
+    has_input = valid = timed = body_valid = false;
     if (int rc = ensure(mm, NN, dd)) return rc;
     const size_t per = (size_t)NN * dd;
     std::vector<unsigned char> st((size_t)mm, 0);
@@ -829,25 +991,55 @@ int Trajectories::set(const float* x, int mm, int NN, int dd) {
     return GPIS_OK;
 }
 
-int Trajectories::optimize(const DistanceField& df, const TrajOpts& o, hipStream_t s) {
+int Trajectories::optimize(const DistanceField& df, const TrajOpts& o, hipStream_t s, const BodyArgs* bd, float w_turn) {
     if (int rc = traj_check_opts(o)) return rc;
     if (!df.valid || !has_input) return GPIS_ERR_STATE;
     if (df.dim != dim) return GPIS_ERR_ARG;
     const auto t0 = std::chrono::steady_clock::now();
-    valid = timed = false;
+    valid = timed = body_valid = false;
     if (int rc = bind(df.device)) return rc;
+    if (bd && (size_t)m > cap_bres) {
+        (void)hipFree(d_bresd); (void)hipFree(d_bresi);
+        d_bresd = nullptr; d_bresi = nullptr; cap_bres = 0;
+        GPIS_HIP(hipMalloc((void**)&d_bresd, sizeof(double) * (size_t)m));
+        GPIS_HIP(hipMalloc((void**)&d_bresi, sizeof(int) * 3 * (size_t)m));
+        cap_bres = (size_t)m;
+    }
     const DfLattice L = df.lattice();
     const int threads = 64 * ((N + 63) / 64);
-    if (dim == 2)
-        hipLaunchKernelGGL(traj_opt_kernel<2>, dim3((unsigned)m), dim3(threads), 0, s, df.d_dist, L, d_in, d_instat, N, o, d_x, d_fres,
-                           d_ires);
-    else
-        hipLaunchKernelGGL(traj_opt_kernel<3>, dim3((unsigned)m), dim3(threads), 0, s, df.d_dist, L, d_in, d_instat, N, o, d_x, d_fres,
-                           d_ires);
+    const BodyArgs none{nullptr, 0};
+#define GPIS_TRAJ_OPT(D, B, ARGS, WT, RD, RI)                                                                                        \
+    hipLaunchKernelGGL((traj_opt_kernel<D, B>), dim3((unsigned)m), dim3(threads), 0, s, df.d_dist, L, d_in, d_instat, N, o, d_x, d_fres, \
+                       d_ires, ARGS, WT, RD, RI)
+    if (bd) {
+        if (dim == 2) GPIS_TRAJ_OPT(2, true, *bd, w_turn, d_bresd, d_bresi);
+        else GPIS_TRAJ_OPT(3, true, *bd, w_turn, d_bresd, d_bresi);
+    } else {
+        if (dim == 2) GPIS_TRAJ_OPT(2, false, none, 0.f, (double*)nullptr, (int*)nullptr);
+        else GPIS_TRAJ_OPT(3, false, none, 0.f, (double*)nullptr, (int*)nullptr);
+    }
+#undef GPIS_TRAJ_OPT
     GPIS_HIP(hipGetLastError());
     GPIS_HIP(hipStreamSynchronize(s));
     opt_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     valid = true;
+    body_valid = bd != nullptr;
+    return GPIS_OK;
+}
+
+int Trajectories::body_result(double* D_min, int* waypoint, int* ball, int* collides) {
+    if (!valid || !body_valid) return GPIS_ERR_STATE;
+    std::vector<double> hd((size_t)m);
+    std::vector<int> hi(3 * (size_t)m);
+    GPIS_HIP(hipMemcpyAsync(hd.data(), d_bresd, sizeof(double) * hd.size(), hipMemcpyDeviceToHost, own));
+    GPIS_HIP(hipMemcpyAsync(hi.data(), d_bresi, sizeof(int) * hi.size(), hipMemcpyDeviceToHost, own));
+    GPIS_HIP(hipStreamSynchronize(own));
+    for (size_t r = 0; r < (size_t)m; ++r) {
+        if (D_min) D_min[r] = hd[r];
+        if (waypoint) waypoint[r] = hi[3 * r];
+        if (ball) ball[r] = hi[3 * r + 1];
+        if (collides) collides[r] = hi[3 * r + 2];
+    }
     return GPIS_OK;
 }
 

@@ -1085,6 +1085,46 @@ int   gpis_body_mppi_step(void* mppi, void* df, void* plan, void* body, void* ob
 int   gpis_body_traj_clearance(void* traj, void* df, void* body, double clearance, double* D_min, int* waypoint, int* ball,
                                int* collides);
 
+/* ---- smoothing for the robot's footprint: body balls in the optimiser ----------------------------------------
+ * gpis_smooth_body_optimize is gpis_traj_optimize with the obstacle term applied at the balls of a footprint (m >= 1, dim 2 or 3;
+ * in 3-D the body turns about z only).  tests/traj_body_ref.py states every rule in numpy.  Everything not named here is
+ * gpis_traj_optimize's, bit for bit: the ends fixed, a_i, the metric, R, kappa, the update before the stop test, tol, the status
+ * codes, iters = 0, float32 without FMA.  Per iteration, on the current iterate:
+ *   headings  waypoint i = 0 .. N-1 gets (c, s) by gpis_body_traj_clearance's chord rule, in double; it owns its chord iff chord
+ *             k0 = min(i, N-2) has n2 > 0, nn_i = sqrt(n2) of that chord; the last waypoint shares chord N-2 with waypoint N-2
+ *   balls     j ascending: w_j = the body rule's position (double), sampled at its float32 cast: (smp, grad);
+ *             d_j = (float)((double)smp - rho_j); e_j = d_j - clearance; q_j = gpis_traj_optimize's q(e_j); a sample whose value
+ *             or a gradient component is not finite has q_j = 0 and grad_j = 0
+ *   force     f_i = q_0 grad_0, then f_i + q_j grad_j
+ *   torque    r_j = ((float)((-s) b0 - c b1), (float)(c b0 - s b1)); tau_i = q_0 (grad_0[0] r_0[0] + grad_0[1] r_0[1]), then
+ *             tau_i + q_j (...); the z component of grad_j enters the force only
+ *   chord     t_i = (tau_i / (float)nn_i) * (-(float)s, (float)c) if waypoint i owns its chord, else (0, 0);
+ *             T_k = t_k for k < N-2, T_{N-2} = t_{N-2} + t_{N-1}
+ *   gradient  g_i[a] = w_smooth a_i[a] + w_obs (f_i[a] + w_turn (T_{i-1}[a] - T_i[a])), a < 2, interior i;
+ *             g_i[2] = w_smooth a_i[2] + w_obs f_i[2]
+ * The evaluation in the same launch: length, smooth, min_dist, nonfinite, collides are gpis_traj_optimize's (the point's);
+ * obstacle is the tree sum over the interior waypoints of (c(e_0), then + c(e_j)) with gpis_traj_optimize's point cost c at the
+ * balls of the result; the body result D_min, waypoint, ball, collides is what gpis_body_traj_clearance(traj, df, body,
+ * (double)clearance) returns on the result, bit for bit, and gpis_smooth_body_get reads it without a launch.  With the one-ball
+ * zero footprint (b = 0, rho = 0) x, status, iterations and the four float results have gpis_traj_optimize's bits for any w_turn.
+ * gpis_smooth_body_default_opts: gpis_traj_default_opts with w_obs = 0.25 step / balls (the term is summed over the balls), and
+ * w_turn = 1.  opts NULL: those defaults for the footprint's m; gpis_traj_opts keeps its layout.
+ * A body result is a result: gpis_traj_get, gpis_traj_device, gpis_timing_*, gpis_obst_check_timing and
+ * gpis_body_traj_clearance work on it unchanged; gpis_traj_optimize or a new input drops the body result with the result.
+ * gpis_smooth_from_pose_paths: gpis_traj_from_paths on the points of a pose planner's last gpis_pplan_paths (dim 2; the heading
+ * indices are not carried over: the body faces along its chord).  A turn in place repeats a point, so s_{k+1} == s_k occurs;
+ * there w = 0.  The segment search skips such segments except at the path's end and in a path that only turns.
+ * Errors, each before anything is dropped: a NULL handle, a footprint with m = 0, w_turn negative or not finite, balls outside
+ * 1 .. 16, a footprint of another dim than the field or the input, a footprint on another device than the field, whatever
+ * gpis_traj_optimize / gpis_traj_from_paths refuse as an argument -> GPIS_ERR_ARG; a field without a result, a handle without
+ * input, a pose planner without paths, gpis_smooth_body_get on a handle whose last result came without a footprint
+ * -> GPIS_ERR_STATE. */
+int   gpis_smooth_body_default_opts(int dim, float step, int balls, gpis_traj_opts* opts, float* w_turn);
+int   gpis_smooth_body_optimize(void* traj, void* df, void* body, const gpis_traj_opts* opts, float w_turn, void* hip_stream);
+/* per trajectory [m] (any pointer may be NULL) */
+int   gpis_smooth_body_get(void* traj, double* D_min, int* waypoint, int* ball, int* collides);
+int   gpis_smooth_from_pose_paths(void* traj, void* pplan, int N);
+
 /* ---- routes for the robot's footprint: heading layers in the planner ---------------------------------------
  * gpis_plan_solve plans for a point with one scalar clearance; a long narrow robot has no right scalar.  The pose planner is
  * the same solver on the lattice nx x ny x H of poses (x, y, heading) of a 2-D field, H in {8, 16, 32, 64}: state s = (i, j, h)
