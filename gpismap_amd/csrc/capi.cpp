@@ -794,9 +794,7 @@ void* gpis_plan_create(void) {
 void gpis_plan_destroy(void* plan) { delete (Planner*)plan; }
 int gpis_plan_set_schedule(void* plan, int check_every, int inner_cap) {
     if (!plan || check_every < 0 || inner_cap < 0) return GPIS_ERR_ARG;
-    Planner& p = *(Planner*)plan;
-    p.check_every = check_every ? std::min(check_every, (int)Planner::kMaxBatch) : 8;
-    p.inner_cap = inner_cap ? inner_cap : 256;
+    ((Planner*)plan)->sched.set(check_every, inner_cap);
     return GPIS_OK;
 }
 // the argument and state checks come before anything is dropped: such an error leaves the previous result readable
@@ -827,9 +825,10 @@ int gpis_plan_info(void* plan, double* out, int n) {
     if (!plan || !out || n < 0) return GPIS_ERR_ARG;
     const Planner& p = *(Planner*)plan;
     const bool v = p.valid;
+    const PlanCounters& c = p.cnt;
     const double w[14] = {v ? 1.0 : 0.0, v ? (double)p.dim : 0.0, v ? (double)p.n[0] : 0.0, v ? (double)p.n[1] : 0.0,
-                          v ? (double)p.n[2] : 0.0, v ? (double)p.step : 0.0, (double)p.goals_given, (double)p.goals_kept,
-                          (double)p.nfree, (double)p.nreach, (double)p.rounds, (double)p.launches, p.solve_ms, (double)p.max_cost};
+                          v ? (double)p.n[2] : 0.0, v ? (double)p.step : 0.0, (double)c.goals_given, (double)c.goals_kept,
+                          (double)c.nfree, (double)c.nreach, (double)c.rounds, (double)c.launches, c.solve_ms, (double)c.max_cost};
     for (int i = 0; i < n && i < 14; ++i) out[i] = w[i];
     return GPIS_OK;
 }
@@ -2137,9 +2136,7 @@ void* gpis_pplan_create(void) {
 void gpis_pplan_destroy(void* pplan) { delete (PosePlanner*)pplan; }
 int gpis_pplan_set_schedule(void* pplan, int check_every, int inner_cap) {
     if (!pplan || check_every < 0 || inner_cap < 0) return GPIS_ERR_ARG;
-    PosePlanner& p = *(PosePlanner*)pplan;
-    p.check_every = check_every ? std::min(check_every, (int)PosePlanner::kMaxBatch) : 8;
-    p.inner_cap = inner_cap ? inner_cap : 256;
+    ((PosePlanner*)pplan)->sched.set(check_every, inner_cap);
     return GPIS_OK;
 }
 // a heading index of a goal or a start: an integer in -1 .. H - 1
@@ -2182,9 +2179,10 @@ int gpis_pplan_info(void* pplan, double* out, int n) {
     if (!pplan || !out || n < 0) return GPIS_ERR_ARG;
     const PosePlanner& p = *(PosePlanner*)pplan;
     const bool v = p.valid;
+    const PlanCounters& c = p.cnt;
     const double w[14] = {v ? 1.0 : 0.0, v ? (double)p.n[0] : 0.0, v ? (double)p.n[1] : 0.0, v ? (double)p.H : 0.0, v ? (double)p.step : 0.0,
-                          (double)p.goals_given, (double)p.goals_kept, (double)p.nfree, (double)p.nreach, (double)p.rounds,
-                          (double)p.launches, p.solve_ms, (double)p.max_cost, p.setup_ms};
+                          (double)c.goals_given, (double)c.goals_kept, (double)c.nfree, (double)c.nreach, (double)c.rounds,
+                          (double)c.launches, c.solve_ms, (double)c.max_cost, p.setup_ms};
     for (int i = 0; i < n && i < 14; ++i) out[i] = w[i];
     return GPIS_OK;
 }

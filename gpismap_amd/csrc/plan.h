@@ -16,15 +16,31 @@ struct PlanOpts {
     int connectivity = 1, max_rounds = 0;
 };
 
+// The schedule of a solve (test hook: the results do not depend on it): outer rounds per read-back, inner iterations per launch
+struct PlanSchedule {
+    static constexpr int kMaxBatch = 64;
+    int check_every = 8, inner_cap = 256;
+    void set(int every, int inner) {             // 0: the default
+        check_every = every > 0 ? (every < kMaxBatch ? every : kMaxBatch) : PlanSchedule().check_every;
+        inner_cap = inner > 0 ? inner : PlanSchedule().inner_cap;
+    }
+};
+
+// what a solve leaves besides the arrays; shared by the planner and the pose planner (filled by plan_host.h)
+struct PlanCounters {
+    long long goals_given = 0, goals_kept = 0, nfree = 0, nreach = 0, rounds = 0, launches = 0;
+    double solve_ms = 0.0;
+    float max_cost = 0.f;
+};
+
 struct Planner {
     static constexpr int kMaxStarts = 1 << 24;
     static constexpr float kMaxGain = 1e4f;
-    static constexpr int kMaxBatch = 64;         // outer rounds per read-back (check_every)
     static constexpr int kTile2 = 32, kTile3 = 8;
 
     int device = -1;
     hipStream_t own = nullptr;
-    int check_every = 8, inner_cap = 256;        // schedule (test hook: the results do not depend on it)
+    PlanSchedule sched;
 
     // grow-only device buffers, 10 B per lattice point
     float* d_cost = nullptr;
@@ -32,7 +48,7 @@ struct Planner {
     unsigned char* d_policy = nullptr;
     size_t cap_n = 0;
     int* d_flags = nullptr;   size_t cap_tiles = 0;   // [2][tiles]: active this round / next round
-    unsigned long long* d_stat = nullptr;        // kStatWords counters (kernel side: plan.hip)
+    unsigned long long* d_stat = nullptr;        // kStatWords counters (plan_dev.h)
     float* d_goals = nullptr; size_t cap_goals = 0;
     // paths
     float* d_starts = nullptr; size_t cap_starts = 0;    // [m][dim]
@@ -48,9 +64,7 @@ struct Planner {
     float step = 0.f;
     long long ngrid = 0;
     bool valid = false;
-    long long goals_given = 0, goals_kept = 0, nfree = 0, nreach = 0, rounds = 0, launches = 0;
-    double solve_ms = 0.0;
-    float max_cost = 0.f;
+    PlanCounters cnt;
     bool paths_valid = false;
     long long npaths = 0, npoints = 0;
 
@@ -66,8 +80,7 @@ struct Planner {
     // to `dev`, makes room for nx x ny points and copies the geometry; the caller then fills d_cost, d_c and d_policy on a
     // stream it synchronises, and install_end records the counters and makes the result valid exactly as solve() does.
     int install_begin(int dev, int nx, int ny, const float* origin2, float lattice_step);
-    void install_end(long long given, long long kept, long long free_points, long long reachable, long long outer_rounds,
-                     long long tile_launches, double ms, float largest_cost);
+    void install_end(const PlanCounters& c) { cnt = c; valid = true; }
 
 private:
     int ensure(long long np, long long tiles);

@@ -11,13 +11,10 @@
 // cap).  Values only fall and fl(a + w) is monotone in a, so reading a neighbour's point while its workgroup lowers it is
 // harmless: the old value is merely larger, and the flag raised after the store makes the reader run again in the next launch,
 // which sees the store.  The host ends the solve after a round that raised no flag.  Integer atomics only (flags, counters).
-#include <algorithm>
-#include <chrono>
 #include <cmath>
-#include <cstring>
 #include "plan.h"
 #include "dfield.h"
-#include "plan_dev.h"
+#include "plan_host.h"
 
 namespace gpis {
 
@@ -26,13 +23,7 @@ namespace {
 using namespace plan_dev;
 
 constexpr int kBlock = 256;
-constexpr int kStatKept = 0, kStatLaunch = 1, kStatFree = 2, kStatReach = 3, kStatMax = 4, kStatRaised = 8;
-constexpr int kStatWords = kStatRaised + Planner::kMaxBatch;
 
-constexpr int off_dx(int k) { return k % 3 - 1; }
-constexpr int off_dy(int k) { return (k / 3) % 3 - 1; }
-constexpr int off_dz(int k) { return k / 9 - 1; }
-constexpr int off_nnz(int k) { return (off_dx(k) != 0) + (off_dy(k) != 0) + (off_dz(k) != 0); }
 constexpr int off_index(int dx, int dy, int dz) { return ((dz + 1) * 3 + (dy + 1)) * 3 + (dx + 1); }
 // bits of the points a move along offset k passes: p + every non-empty subset of the offset's non-zero components
 constexpr unsigned off_subsets(int k) {
@@ -63,16 +54,7 @@ __global__ void __launch_bounds__(kBlock) plan_setup_kernel(const float* __restr
                                                             float* __restrict__ c, float* __restrict__ cost,
                                                             unsigned char* __restrict__ policy) {
     for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < n; p += gridDim.x * blockDim.x) {
-        const float d = dist[p];
-        float cc = 0.f;
-        if (d >= clearance) {
-            cc = 1.f;
-            if (margin > 0.f) {
-                const float t = fmaxf(0.f, margin - (d - clearance)) / margin;
-                cc = 1.f + gain * (t * t);
-            }
-        }
-        c[p] = cc;
+        c[p] = point_cost(dist[p], clearance, margin, gain);
         cost[p] = INFINITY;
         policy[p] = 255;
     }
@@ -108,13 +90,7 @@ __global__ void __launch_bounds__(kBlock) plan_tile_kernel(PlanLat L, const floa
     __shared__ int s_act;
     __shared__ unsigned s_nbr;
     const int tid = threadIdx.x, tile = blockIdx.x;
-    if (tid == 0) {
-        s_act = flags_cur[tile];
-        if (s_act) flags_cur[tile] = 0;
-        s_nbr = 0;
-    }
-    __syncthreads();
-    if (!s_act) return;
+    if (!tile_begin(flags_cur, tile, s_act, s_nbr)) return;
     const int ti = tile % tnx, tj = (tile / tnx) % tny, tk = tile / (tnx * tny);
     for (int h = tid; h < NH; h += kBlock) {
         const int gi = ti * T + h % H - 1, gj = tj * T + (h / H) % H - 1, gk = DIM == 3 ? tk * T + h / (H * H) - 1 : 0;
@@ -174,38 +150,17 @@ __global__ void __launch_bounds__(kBlock) plan_tile_kernel(PlanLat L, const floa
         const int li = q % T, lj = (q / T) % T, lk = q / (T * T);
         const int gi = ti * T + li, gj = tj * T + lj, gk = DIM == 3 ? tk * T + lk : 0;
         st_cost(cost + ((gk * L.ny + gj) * L.nx + gi), v);      // (a lowered point is free, hence inside the lattice)
-        const unsigned mx = 2u | (li == 0 ? 1u : 0u) | (li == T - 1 ? 4u : 0u);
-        const unsigned my = 2u | (lj == 0 ? 1u : 0u) | (lj == T - 1 ? 4u : 0u);
-        const unsigned mz = DIM == 2 ? 2u : (2u | (lk == 0 ? 1u : 0u) | (lk == T - 1 ? 4u : 0u));
-        if ((mx | my | mz) != 2u) {
-            unsigned bits = 0;
-#pragma unroll
-            for (int k = 0; k < 27; ++k)
-                if (k != 13 && ((mx >> (k % 3)) & (my >> ((k / 3) % 3)) & (mz >> (k / 9)) & 1u)) bits |= 1u << k;
-            atomicOr(&s_nbr, bits);
-        }
+        note_border(s_nbr, li, lj, lk, T, DIM == 2 ? 0 : T);
     }
-    __syncthreads();
-    if (tid < 27 && tid != 13 && ((s_nbr >> tid) & 1u) && (conn || off_nnz(tid) == 1)) {
-        const int ni = ti + off_dx(tid), nj = tj + off_dy(tid), nk = tk + off_dz(tid);
-        if (ni >= 0 && ni < tnx && nj >= 0 && nj < tny && nk >= 0 && nk < tnz) {
-            flags_next[(nk * tny + nj) * tnx + ni] = 1;
-            atomicAdd(raised, 1ull);
-        }
-    }
-    if (tid == 32) {
-        if (capped) { flags_next[tile] = 1; atomicAdd(raised, 1ull); }
-        atomicAdd(&stat[kStatLaunch], 1ull);
-    }
+    tile_finish(s_nbr, capped, conn != 0, tile, ti, tj, tk, tnx, tny, tnz, flags_next, stat, raised);
 }
 
 // policy[p]: 13 at a goal, the direction of the move minimising fl(cost[q] + w) (ties: the smaller cost[q], then the smaller
 // index) at a free point of finite cost, 255 elsewhere; counts of free and reachable points, the largest finite cost
 __global__ void __launch_bounds__(kBlock) plan_policy_kernel(PlanLat L, const float* __restrict__ c, const float* __restrict__ cost, int conn,
                                                              unsigned char* __restrict__ policy, unsigned long long* __restrict__ stat) {
-    __shared__ unsigned s_free, s_reach, s_max;
-    if (threadIdx.x == 0) { s_free = 0; s_reach = 0; s_max = 0; }
-    __syncthreads();
+    __shared__ unsigned s_cnt[3];
+    counts_begin(s_cnt);
     const int nxy = L.nx * L.ny, n = nxy * L.nz;
     const float ls[3] = {L.step, sqrtf(2.f) * L.step, sqrtf(3.f) * L.step};
     unsigned nf = 0, nr = 0, mx = 0;
@@ -237,7 +192,7 @@ __global__ void __launch_bounds__(kBlock) plan_policy_kernel(PlanLat L, const fl
                             const int q = p + (off_dz(k) * L.ny + off_dy(k)) * L.nx + off_dx(k);
                             const float cq = cost[q];
                             const float v = cq + ls[off_nnz(k) - 1] * (0.5f * (cp + c[q]));
-                            if (v < best || (v == best && cq < bestq)) { best = v; bestq = cq; pol = (unsigned char)k; }
+                            better_move(v, cq, k, best, bestq, pol);
                         }
                     }
                 }
@@ -245,15 +200,7 @@ __global__ void __launch_bounds__(kBlock) plan_policy_kernel(PlanLat L, const fl
         }
         policy[p] = pol;
     }
-    atomicAdd(&s_free, nf);
-    atomicAdd(&s_reach, nr);
-    atomicMax(&s_max, mx);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        atomicAdd(&stat[kStatFree], (unsigned long long)s_free);
-        atomicAdd(&stat[kStatReach], (unsigned long long)s_reach);
-        atomicMax(&stat[kStatMax], (unsigned long long)s_max);
-    }
+    commit_counts(s_cnt, nf, nr, mx, stat + kStatFree);
 }
 
 // One thread per start follows the policy.  WRITE = false: cnt[t] = points of the path, status, start cost.  WRITE = true: the
@@ -374,31 +321,14 @@ int Planner::solve(const DistanceField& df, const float* goals, int ngoals, cons
                        d_stat);
     GPIS_HIP(hipGetLastError());
 
-    const long long cap = o.max_rounds > 0 ? (long long)o.max_rounds : np + 1;
-    const int every = std::max(1, std::min(check_every, (int)kMaxBatch)), inner = std::max(1, inner_cap);
-    unsigned long long raised[kMaxBatch];
-    long long round = 0, done = -1;
-    while (done < 0 && round < cap) {
-        const int nb = (int)std::min((long long)every, cap - round);
-        GPIS_HIP(hipMemsetAsync(d_stat + kStatRaised, 0, sizeof(unsigned long long) * nb, s));
-        for (int b = 0; b < nb; ++b) {
-            int* cur = d_flags + ((round + b) & 1) * tiles;
-            int* nxt = d_flags + ((round + b + 1) & 1) * tiles;
-            if (dm == 2)
-                hipLaunchKernelGGL(plan_tile_kernel<2>, dim3((unsigned)tiles), dim3(kBlock), 0, s, L, d_c, d_cost, tnx, tny, tnz, cur, nxt,
-                                   o.connectivity, inner, d_stat, d_stat + kStatRaised + b);
-            else
-                hipLaunchKernelGGL(plan_tile_kernel<3>, dim3((unsigned)tiles), dim3(kBlock), 0, s, L, d_c, d_cost, tnx, tny, tnz, cur, nxt,
-                                   o.connectivity, inner, d_stat, d_stat + kStatRaised + b);
-            GPIS_HIP(hipGetLastError());
-        }
-        GPIS_HIP(hipMemcpyAsync(raised, d_stat + kStatRaised, sizeof(unsigned long long) * nb, hipMemcpyDeviceToHost, s));
-        GPIS_HIP(hipStreamSynchronize(s));
-        for (int b = 0; b < nb && done < 0; ++b)
-            if (raised[b] == 0) done = round + b + 1;       // (the rounds after it found every flag down)
-        round += nb;
-    }
-    if (done < 0) return GPIS_ERR_LIMIT;
+    const auto tile_kernel = dm == 2 ? plan_tile_kernel<2> : plan_tile_kernel<3>;
+    const long long done = plan_host::run_rounds(
+        s, d_flags, tiles, d_stat + kStatRaised, o.max_rounds > 0 ? (long long)o.max_rounds : np + 1, sched,
+        [&](int* cur, int* nxt, unsigned long long* raised) {
+            hipLaunchKernelGGL(tile_kernel, dim3((unsigned)tiles), dim3(kBlock), 0, s, L, d_c, d_cost, tnx, tny, tnz, cur, nxt,
+                               o.connectivity, sched.inner_cap, d_stat, raised);
+        });
+    if (done < 0) return (int)done;
 
     hipLaunchKernelGGL(plan_policy_kernel, dim3(grid_for(np)), dim3(kBlock), 0, s, L, d_c, d_cost, o.connectivity, d_policy, d_stat);
     GPIS_HIP(hipGetLastError());
@@ -407,11 +337,7 @@ int Planner::solve(const DistanceField& df, const float* goals, int ngoals, cons
     GPIS_HIP(hipStreamSynchronize(s));
     dim = dm; ngrid = np; step = df.step;
     for (int a = 0; a < 3; ++a) { n[a] = a < dm ? df.n[a] : 1; origin[a] = a < dm ? df.origin[a] : 0.f; }
-    goals_given = ngoals; goals_kept = (long long)st[kStatKept]; nfree = (long long)st[kStatFree]; nreach = (long long)st[kStatReach];
-    rounds = done; launches = (long long)st[kStatLaunch];
-    const unsigned mb = (unsigned)st[kStatMax];
-    std::memcpy(&max_cost, &mb, sizeof(float));
-    solve_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    cnt = plan_host::counters(st, kStatFree, ngoals, done, plan_host::ms_since(t0));
     valid = true;
     return GPIS_OK;
 }
@@ -427,43 +353,21 @@ int Planner::install_begin(int dev, int nx, int ny, const float* origin2, float 
     return GPIS_OK;
 }
 
-void Planner::install_end(long long given, long long kept, long long free_points, long long reachable, long long outer_rounds,
-                          long long tile_launches, double ms, float largest_cost) {
-    goals_given = given; goals_kept = kept; nfree = free_points; nreach = reachable; rounds = outer_rounds; launches = tile_launches;
-    solve_ms = ms; max_cost = largest_cost;
-    valid = true;
-}
-
 int Planner::paths(const float* starts, int m, int max_points, hipStream_t s) {
     if (!starts || m < 1 || max_points < 2) return GPIS_ERR_ARG;
     if (!valid) return GPIS_ERR_STATE;
     if (m > kMaxStarts) return GPIS_ERR_LIMIT;
     paths_valid = false;
-    if ((size_t)m > cap_starts) {
-        for (void* p : {(void*)d_starts, (void*)d_off, (void*)d_scost, (void*)d_status}) (void)hipFree(p);
-        d_starts = nullptr; d_off = nullptr; d_scost = nullptr; d_status = nullptr; cap_starts = 0;
-        GPIS_HIP(hipMalloc((void**)&d_starts, sizeof(float) * 3 * (size_t)m));
-        GPIS_HIP(hipMalloc((void**)&d_off, sizeof(long long) * ((size_t)m + 1)));
-        GPIS_HIP(hipMalloc((void**)&d_scost, sizeof(float) * (size_t)m));
-        GPIS_HIP(hipMalloc((void**)&d_status, (size_t)m));
-        cap_starts = (size_t)m;
-    }
     const PlanLat L{dim, n[0], n[1], n[2], origin[0], origin[1], origin[2], step};
-    GPIS_HIP(hipMemcpyAsync(d_starts, starts, sizeof(float) * (size_t)m * dim, hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(plan_walk_kernel<false>, dim3(grid_for(m)), dim3(kBlock), 0, s, L, d_c, d_cost, d_policy, d_starts, m, max_points,
-                       d_off, d_scost, d_status, (float*)nullptr);
-    GPIS_HIP(hipGetLastError());
-    hipLaunchKernelGGL(plan_scan_kernel, dim3(1), dim3(1024), 0, s, d_off, m);
-    GPIS_HIP(hipGetLastError());
-    long long total = 0;
-    GPIS_HIP(hipMemcpyAsync(&total, d_off + m, sizeof(long long), hipMemcpyDeviceToHost, s));
-    GPIS_HIP(hipStreamSynchronize(s));
-    if (int rc = grow(d_points, cap_points, (size_t)std::max(1ll, total) * dim)) return rc;
-    hipLaunchKernelGGL(plan_walk_kernel<true>, dim3(grid_for(m)), dim3(kBlock), 0, s, L, d_c, d_cost, d_policy, d_starts, m, max_points,
-                       d_off, d_scost, d_status, d_points);
-    GPIS_HIP(hipGetLastError());
-    GPIS_HIP(hipStreamSynchronize(s));
-    npaths = m; npoints = total;
+    const auto walk = [&](auto kernel, float* points) {
+        hipLaunchKernelGGL(kernel, dim3(grid_for(m)), dim3(kBlock), 0, s, L, d_c, d_cost, d_policy, d_starts, m, max_points, d_off, d_scost,
+                           d_status, points);
+    };
+    if (int rc = plan_host::run_paths(
+            s, starts, m, dim, d_starts, cap_starts, d_off, d_scost, d_status, npoints, [&] { walk(plan_walk_kernel<false>, nullptr); },
+            [&](size_t total) { return grow(d_points, cap_points, total * dim); }, [&] { walk(plan_walk_kernel<true>, d_points); }))
+        return rc;
+    npaths = m;
     paths_valid = true;
     return GPIS_OK;
 }

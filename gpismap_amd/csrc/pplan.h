@@ -10,11 +10,11 @@
 #include <cstdint>
 #include "dev_common.h"
 #include "body.h"
+#include "plan.h"
 
 namespace gpis {
 
 struct DistanceField;
-struct Planner;
 
 struct PPlanOpts {
     float clearance = 0.f, margin = 0.f, gain = 4.f, turn = 0.f;
@@ -25,14 +25,13 @@ struct PosePlanner {
     static constexpr int kMaxStarts = 1 << 24;
     static constexpr long long kMaxStates = 1ll << 28;
     static constexpr float kMaxGain = 1e4f;
-    static constexpr int kMaxBatch = 64;         // outer rounds per read-back (check_every)
     static constexpr int kTile = 8;              // a tile: 8 x 8 lattice points x all H layers
     static constexpr int kMaxH = 64;
     static constexpr int kTurnUp = 27, kTurnDown = 28;
 
     int device = -1;
     hipStream_t own = nullptr;
-    int check_every = 8, inner_cap = 256;        // schedule (test hook: the results do not depend on it)
+    PlanSchedule sched;
 
     // grow-only device buffers, 9 B per state
     float* d_cost = nullptr;
@@ -63,9 +62,8 @@ struct PosePlanner {
     double head[kMaxH][2];
     unsigned short moves[kMaxH];
     bool valid = false;
-    long long goals_given = 0, goals_kept = 0, nfree = 0, nreach = 0, rounds = 0, launches = 0;
-    double solve_ms = 0.0, setup_ms = 0.0;
-    float max_cost = 0.f;
+    PlanCounters cnt;
+    double setup_ms = 0.0;
     bool paths_valid = false;
     long long npaths = 0, npoints = 0;
 

@@ -10,14 +10,10 @@
 // iterations), stores the states it lowered, and raises the NEXT round's flag of every xy neighbour tile that has a lowered
 // state in its halo (and its own at the cap).  Values only fall and fl(a + w) is monotone in a, so a stale read is merely
 // larger, and the flag raised after the store makes the reader run again.  Integer atomics only (flags, counters).
-#include <algorithm>
-#include <chrono>
 #include <cmath>
-#include <cstring>
 #include "pplan.h"
-#include "plan.h"
 #include "dfield.h"
-#include "plan_dev.h"
+#include "plan_host.h"
 
 namespace gpis {
 
@@ -26,9 +22,6 @@ namespace {
 using namespace plan_dev;
 
 constexpr int kBlock = 256;
-constexpr int kStatKept = 0, kStatLaunch = 1, kStatFree = 2, kStatReach = 3, kStatMax = 4, kStatFree2 = 5, kStatReach2 = 6, kStatMax2 = 7,
-              kStatRaised = 8;
-constexpr int kStatWords = kStatRaised + PosePlanner::kMaxBatch;
 constexpr int kT = PosePlanner::kTile, kW = kT + 2, kLayer = kW * kW;
 constexpr unsigned kBitUp = 1u << 9, kBitDown = 1u << 10;
 
@@ -61,18 +54,6 @@ __device__ __forceinline__ unsigned open_moves(unsigned nb, unsigned allowed, bo
     if (up) m |= kBitUp;
     if (down) m |= kBitDown;
     return m;
-}
-
-__device__ __forceinline__ float point_cost(float d, float clearance, float margin, float gain) {
-    float cc = 0.f;
-    if (d >= clearance) {
-        cc = 1.f;
-        if (margin > 0.f) {
-            const float t = fmaxf(0.f, margin - (d - clearance)) / margin;
-            cc = 1.f + gain * (t * t);
-        }
-    }
-    return cc;
 }
 
 // One thread per state, one heading per blockIdx.y: the heading and the footprint's table come through scalar loads.
@@ -130,13 +111,7 @@ __global__ void __launch_bounds__(kBlock) pplan_tile_kernel(PLat L, const float*
     __shared__ int s_act;
     __shared__ unsigned s_nbr;
     const int tid = threadIdx.x, tile = blockIdx.x;
-    if (tid == 0) {
-        s_act = flags_cur[tile];
-        if (s_act) flags_cur[tile] = 0;
-        s_nbr = 0;
-    }
-    __syncthreads();
-    if (!s_act) return;
+    if (!tile_begin(flags_cur, tile, s_act, s_nbr)) return;
     const int ti = tile % tnx, tj = tile / tnx;
     if (tid < HH) s_mv[tid] = moves[tid];
     for (int e = tid; e < NH; e += kBlock) {
@@ -200,8 +175,6 @@ __global__ void __launch_bounds__(kBlock) pplan_tile_kernel(PLat L, const float*
 
     // store the lowered states; note the xy neighbour tiles whose halo holds one of them
     const int gi = ti * kT + li, gj = tj * kT + lj;
-    const unsigned mx = 2u | (li == 0 ? 1u : 0u) | (li == kT - 1 ? 4u : 0u);
-    const unsigned my = 2u | (lj == 0 ? 1u : 0u) | (lj == kT - 1 ? 4u : 0u);
     bool lowered = false;
 #pragma unroll
     for (int s = 0; s < CPT; ++s) {
@@ -210,25 +183,9 @@ __global__ void __launch_bounds__(kBlock) pplan_tile_kernel(PLat L, const float*
         st_cost(cost + (((l0 + 4 * s) * L.ny + gj) * L.nx + gi), v);      // (a lowered state is free, hence inside the lattice)
         lowered = true;
     }
-    if (lowered && (mx | my) != 2u) {
-        unsigned bits = 0;
-#pragma unroll
-        for (int b = 0; b < 9; ++b)
-            if (b != 4 && ((mx >> (b % 3)) & (my >> (b / 3)) & 1u)) bits |= 1u << b;
-        atomicOr(&s_nbr, bits);
-    }
-    __syncthreads();
-    if (tid < 9 && tid != 4 && ((s_nbr >> tid) & 1u)) {
-        const int ni = ti + b_dx(tid), nj = tj + b_dy(tid);
-        if (ni >= 0 && ni < tnx && nj >= 0 && nj < tny) {
-            flags_next[nj * tnx + ni] = 1;
-            atomicAdd(raised, 1ull);
-        }
-    }
-    if (tid == 32) {
-        if (capped) { flags_next[tile] = 1; atomicAdd(raised, 1ull); }
-        atomicAdd(&stat[kStatLaunch], 1ull);
-    }
+    // (translation b is the planner's offset 9 + b, so the tiles form a one-layer tile lattice: no z bits, tnz = 1)
+    if (lowered) note_border(s_nbr, li, lj, 0, kT, 0);
+    tile_finish(s_nbr, capped, true, tile, ti, tj, 0, tnx, tny, 1, flags_next, stat, raised);
 }
 
 // policy[s]: 13 at a goal, the code of the move minimising fl(cost[s'] + w) (ties: the smaller cost[s'], then the smaller code)
@@ -236,9 +193,8 @@ __global__ void __launch_bounds__(kBlock) pplan_tile_kernel(PLat L, const float*
 __global__ void __launch_bounds__(kBlock) pplan_policy_kernel(PLat L, const float* __restrict__ c, const float* __restrict__ cost,
                                                               const unsigned short* __restrict__ moves, float turn,
                                                               unsigned char* __restrict__ policy, unsigned long long* __restrict__ stat) {
-    __shared__ unsigned s_free, s_reach, s_max;
-    if (threadIdx.x == 0) { s_free = 0; s_reach = 0; s_max = 0; }
-    __syncthreads();
+    __shared__ unsigned s_cnt[3];
+    counts_begin(s_cnt);
     const int nxy = L.nx * L.ny, n = nxy * L.H;
     const float ls[2] = {L.step, sqrtf(2.f) * L.step};
     unsigned nf = 0, nr = 0, mx = 0;
@@ -269,33 +225,25 @@ __global__ void __launch_bounds__(kBlock) pplan_policy_kernel(PLat L, const floa
                             const int q = s + b_dy(b) * L.nx + b_dx(b);
                             const float cq = cost[q];
                             const float v = cq + ls[b_nnz(b) - 1] * (0.5f * (cp + c[q]));
-                            if (v < best || (v == best && cq < bestq)) { best = v; bestq = cq; pol = (unsigned char)(9 + b); }
+                            better_move(v, cq, 9 + b, best, bestq, pol);
                         }
                     }
                     if (open & kBitUp) {
                         const float cq = cost[su];
                         const float v = cq + turn * (0.5f * (cp + c[su]));
-                        if (v < best || (v == best && cq < bestq)) { best = v; bestq = cq; pol = (unsigned char)PosePlanner::kTurnUp; }
+                        better_move(v, cq, PosePlanner::kTurnUp, best, bestq, pol);
                     }
                     if (open & kBitDown) {
                         const float cq = cost[sd];
                         const float v = cq + turn * (0.5f * (cp + c[sd]));
-                        if (v < best || (v == best && cq < bestq)) { best = v; bestq = cq; pol = (unsigned char)PosePlanner::kTurnDown; }
+                        better_move(v, cq, PosePlanner::kTurnDown, best, bestq, pol);
                     }
                 }
             }
         }
         policy[s] = pol;
     }
-    atomicAdd(&s_free, nf);
-    atomicAdd(&s_reach, nr);
-    atomicMax(&s_max, mx);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        atomicAdd(&stat[kStatFree], (unsigned long long)s_free);
-        atomicAdd(&stat[kStatReach], (unsigned long long)s_reach);
-        atomicMax(&stat[kStatMax], (unsigned long long)s_max);
-    }
+    commit_counts(s_cnt, nf, nr, mx, stat + kStatFree);
 }
 
 // One thread per start follows the policy.  WRITE = false: cnt[t] = states of the path, status, start cost.  WRITE = true: the
@@ -386,9 +334,8 @@ __global__ void __launch_bounds__(kBlock) pplan_project_kernel(PLat L, const flo
 // (ties: the smaller code); counts of the points with a free heading and of those of finite cost2, the largest finite cost2
 __global__ void __launch_bounds__(kBlock) pplan_project_policy_kernel(PLat L, const float* __restrict__ cost2, const float* __restrict__ c2,
                                                                       unsigned char* __restrict__ policy2, unsigned long long* __restrict__ stat) {
-    __shared__ unsigned s_free, s_reach, s_max;
-    if (threadIdx.x == 0) { s_free = 0; s_reach = 0; s_max = 0; }
-    __syncthreads();
+    __shared__ unsigned s_cnt[3];
+    counts_begin(s_cnt);
     const int nxy = L.nx * L.ny;
     unsigned nf = 0, nr = 0, mx = 0;
     for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < nxy; p += gridDim.x * blockDim.x) {
@@ -414,21 +361,7 @@ __global__ void __launch_bounds__(kBlock) pplan_project_policy_kernel(PLat L, co
         }
         policy2[p] = pol;
     }
-    atomicAdd(&s_free, nf);
-    atomicAdd(&s_reach, nr);
-    atomicMax(&s_max, mx);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        atomicAdd(&stat[kStatFree2], (unsigned long long)s_free);
-        atomicAdd(&stat[kStatReach2], (unsigned long long)s_reach);
-        atomicMax(&stat[kStatMax2], (unsigned long long)s_max);
-    }
-}
-
-template <int HH>
-void launch_tile(unsigned tiles, hipStream_t s, const PLat& L, const float* c, float* cost, const unsigned short* moves, int tnx, int tny,
-                 int* cur, int* nxt, float turn, int inner, unsigned long long* stat, unsigned long long* raised) {
-    hipLaunchKernelGGL(pplan_tile_kernel<HH>, dim3(tiles), dim3(kBlock), 0, s, L, c, cost, moves, tnx, tny, cur, nxt, turn, inner, stat, raised);
+    commit_counts(s_cnt, nf, nr, mx, stat + kStatFree2);
 }
 
 }  // namespace
@@ -509,37 +442,20 @@ int PosePlanner::solve(const DistanceField& df, const Footprint& body, const dou
                        BodyArgs{body.d_tab, body.m}, (const double*)d_head, o.clearance, o.margin, o.gain, d_c, d_cost, d_policy);
     GPIS_HIP(hipGetLastError());
     GPIS_HIP(hipStreamSynchronize(s));              // (the field and the footprint are not read after this point)
-    setup_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count();
+    setup_ms = plan_host::ms_since(t1);
     hipLaunchKernelGGL(pplan_goal_kernel, dim3(grid_for(ngoals)), dim3(kBlock), 0, s, L, (const float*)d_goals, ngoals, (const float*)d_c, d_cost,
                        tnx, d_flags, d_stat);
     GPIS_HIP(hipGetLastError());
 
-    const long long cap = o.max_rounds > 0 ? (long long)o.max_rounds : ns + 1;
-    const int every = std::max(1, std::min(check_every, (int)kMaxBatch)), inner = std::max(1, inner_cap);
-    unsigned long long raised[kMaxBatch];
-    long long round = 0, done = -1;
-    while (done < 0 && round < cap) {
-        const int nb = (int)std::min((long long)every, cap - round);
-        GPIS_HIP(hipMemsetAsync(d_stat + kStatRaised, 0, sizeof(unsigned long long) * nb, s));
-        for (int b = 0; b < nb; ++b) {
-            int* cur = d_flags + ((round + b) & 1) * tiles;
-            int* nxt = d_flags + ((round + b + 1) & 1) * tiles;
-            unsigned long long* rs = d_stat + kStatRaised + b;
-            switch (nh) {
-                case 8:  launch_tile<8>((unsigned)tiles, s, L, d_c, d_cost, d_moves, tnx, tny, cur, nxt, o.turn, inner, d_stat, rs); break;
-                case 16: launch_tile<16>((unsigned)tiles, s, L, d_c, d_cost, d_moves, tnx, tny, cur, nxt, o.turn, inner, d_stat, rs); break;
-                case 32: launch_tile<32>((unsigned)tiles, s, L, d_c, d_cost, d_moves, tnx, tny, cur, nxt, o.turn, inner, d_stat, rs); break;
-                default: launch_tile<64>((unsigned)tiles, s, L, d_c, d_cost, d_moves, tnx, tny, cur, nxt, o.turn, inner, d_stat, rs); break;
-            }
-            GPIS_HIP(hipGetLastError());
-        }
-        GPIS_HIP(hipMemcpyAsync(raised, d_stat + kStatRaised, sizeof(unsigned long long) * nb, hipMemcpyDeviceToHost, s));
-        GPIS_HIP(hipStreamSynchronize(s));
-        for (int b = 0; b < nb && done < 0; ++b)
-            if (raised[b] == 0) done = round + b + 1;       // (the rounds after it found every flag down)
-        round += nb;
-    }
-    if (done < 0) return GPIS_ERR_LIMIT;
+    const auto tile_kernel = nh == 8 ? pplan_tile_kernel<8> : nh == 16 ? pplan_tile_kernel<16> : nh == 32 ? pplan_tile_kernel<32>
+                                                                                                         : pplan_tile_kernel<64>;
+    const long long done = plan_host::run_rounds(
+        s, d_flags, tiles, d_stat + kStatRaised, o.max_rounds > 0 ? (long long)o.max_rounds : ns + 1, sched,
+        [&](int* cur, int* nxt, unsigned long long* raised) {
+            hipLaunchKernelGGL(tile_kernel, dim3((unsigned)tiles), dim3(kBlock), 0, s, L, (const float*)d_c, d_cost,
+                               (const unsigned short*)d_moves, tnx, tny, cur, nxt, o.turn, sched.inner_cap, d_stat, raised);
+        });
+    if (done < 0) return (int)done;
 
     hipLaunchKernelGGL(pplan_policy_kernel, dim3(grid_for(ns)), dim3(kBlock), 0, s, L, (const float*)d_c, (const float*)d_cost,
                        (const unsigned short*)d_moves, o.turn, d_policy, d_stat);
@@ -549,50 +465,32 @@ int PosePlanner::solve(const DistanceField& df, const Footprint& body, const dou
     GPIS_HIP(hipStreamSynchronize(s));
     H = nh; nstates = ns; step = df.step;
     for (int a = 0; a < 2; ++a) { n[a] = df.n[a]; origin[a] = df.origin[a]; }
-    goals_given = ngoals; goals_kept = (long long)st[kStatKept]; nfree = (long long)st[kStatFree]; nreach = (long long)st[kStatReach];
-    rounds = done; launches = (long long)st[kStatLaunch];
-    const unsigned mb = (unsigned)st[kStatMax];
-    std::memcpy(&max_cost, &mb, sizeof(float));
-    solve_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    cnt = plan_host::counters(st, kStatFree, ngoals, done, plan_host::ms_since(t0));
     valid = true;
     return GPIS_OK;
 }
 
 int PosePlanner::paths(const float* starts, int m, int max_points, hipStream_t s) {
     paths_valid = false;
-    if ((size_t)m > cap_starts) {
-        for (void* p : {(void*)d_starts, (void*)d_off, (void*)d_scost, (void*)d_status}) (void)hipFree(p);
-        d_starts = nullptr; d_off = nullptr; d_scost = nullptr; d_status = nullptr; cap_starts = 0;
-        GPIS_HIP(hipMalloc((void**)&d_starts, sizeof(float) * 3 * (size_t)m));
-        GPIS_HIP(hipMalloc((void**)&d_off, sizeof(long long) * ((size_t)m + 1)));
-        GPIS_HIP(hipMalloc((void**)&d_scost, sizeof(float) * (size_t)m));
-        GPIS_HIP(hipMalloc((void**)&d_status, (size_t)m));
-        cap_starts = (size_t)m;
-    }
     const PLat L{n[0], n[1], H, origin[0], origin[1], step};
-    GPIS_HIP(hipMemcpyAsync(d_starts, starts, sizeof(float) * (size_t)m * 3, hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(pplan_walk_kernel<false>, dim3(grid_for(m)), dim3(kBlock), 0, s, L, (const float*)d_c, (const float*)d_cost,
-                       (const unsigned char*)d_policy, (const float*)d_starts, m, max_points, d_off, d_scost, d_status, (float*)nullptr,
-                       (int*)nullptr);
-    GPIS_HIP(hipGetLastError());
-    hipLaunchKernelGGL(plan_scan_kernel, dim3(1), dim3(1024), 0, s, d_off, m);
-    GPIS_HIP(hipGetLastError());
-    long long total = 0;
-    GPIS_HIP(hipMemcpyAsync(&total, d_off + m, sizeof(long long), hipMemcpyDeviceToHost, s));
-    GPIS_HIP(hipStreamSynchronize(s));
-    const size_t need = (size_t)std::max(1ll, total);
-    if (need > cap_points) {
+    const auto walk = [&](auto kernel, float* points, int* pheading) {
+        hipLaunchKernelGGL(kernel, dim3(grid_for(m)), dim3(kBlock), 0, s, L, (const float*)d_c, (const float*)d_cost,
+                           (const unsigned char*)d_policy, (const float*)d_starts, m, max_points, d_off, d_scost, d_status, points, pheading);
+    };
+    const auto grow_points = [&](size_t need) -> int {          // both buffers at once, under the one capacity
+        if (need <= cap_points) return GPIS_OK;
         (void)hipFree(d_points); (void)hipFree(d_pheading);
         d_points = nullptr; d_pheading = nullptr; cap_points = 0;
         GPIS_HIP(hipMalloc((void**)&d_points, sizeof(float) * 2 * need));
         GPIS_HIP(hipMalloc((void**)&d_pheading, sizeof(int) * need));
         cap_points = need;
-    }
-    hipLaunchKernelGGL(pplan_walk_kernel<true>, dim3(grid_for(m)), dim3(kBlock), 0, s, L, (const float*)d_c, (const float*)d_cost,
-                       (const unsigned char*)d_policy, (const float*)d_starts, m, max_points, d_off, d_scost, d_status, d_points, d_pheading);
-    GPIS_HIP(hipGetLastError());
-    GPIS_HIP(hipStreamSynchronize(s));
-    npaths = m; npoints = total;
+        return GPIS_OK;
+    };
+    if (int rc = plan_host::run_paths(
+            s, starts, m, 3, d_starts, cap_starts, d_off, d_scost, d_status, npoints, [&] { walk(pplan_walk_kernel<false>, nullptr, nullptr); },
+            grow_points, [&] { walk(pplan_walk_kernel<true>, d_points, d_pheading); }))
+        return rc;
+    npaths = m;
     paths_valid = true;
     return GPIS_OK;
 }
@@ -610,14 +508,12 @@ int PosePlanner::project(Planner& plan, unsigned char* heading2) {
     hipLaunchKernelGGL(pplan_project_policy_kernel, dim3(grid_for(nxy)), dim3(kBlock), 0, s, L, (const float*)plan.d_cost, (const float*)plan.d_c,
                        plan.d_policy, d_stat);
     GPIS_HIP(hipGetLastError());
-    unsigned long long st[3];
-    GPIS_HIP(hipMemcpyAsync(st, d_stat + kStatFree2, sizeof(st), hipMemcpyDeviceToHost, s));
+    unsigned long long st[kStatRaised];
+    GPIS_HIP(hipMemcpyAsync(st, d_stat, sizeof(st), hipMemcpyDeviceToHost, s));
     if (heading2) GPIS_HIP(hipMemcpyAsync(heading2, d_heading2, (size_t)nxy, hipMemcpyDeviceToHost, s));
     GPIS_HIP(hipStreamSynchronize(s));
-    float mc;
-    const unsigned mb = (unsigned)st[2];
-    std::memcpy(&mc, &mb, sizeof(float));
-    plan.install_end(goals_given, goals_kept, (long long)st[0], (long long)st[1], rounds, launches, solve_ms, mc);
+    // (the goals kept and the launches are the solve's, still in their words)
+    plan.install_end(plan_host::counters(st, kStatFree2, cnt.goals_given, cnt.rounds, cnt.solve_ms));
     return GPIS_OK;
 }
 

@@ -5,7 +5,8 @@ gain 4, all diagonals).  Per workload it prints one JSON line with
   - field_ms: the field's own build in the same process (median of --repeats),
   - solve_ms: wall time of gpis_plan_solve (median), solve_over_field, outer rounds, tile launches,
     cells_relaxed_per_s = tile launches x points per tile / solve time,
-  - paths_ms: gpis_plan_paths from --paths random free starts, and their total length in points,
+  - paths_ms: gpis_plan_paths from --paths random free starts, and their total length in points
+    (solve_ms_all, paths_ms_all: every repeat, the spread a comparison between two builds needs),
   - host_ms: the host route it replaces -- the same edge list as a scipy.sparse matrix and scipy.sparse.csgraph.dijkstra from
     the goal, timed with and without building the graph (float64 sums: the route, not the bits; skipped without scipy, with
     --no-host, and above --host-limit lattice points).
@@ -144,6 +145,7 @@ def main():
         pm = [paths() for _ in range(args.repeats)]
         r["paths"] = args.paths
         r["paths_ms"] = float(np.median([t for t, _ in pm]))
+        r["paths_ms_all"] = [t for t, _ in pm]
         r["path_points"] = int(pl.last_off[-1])
         r["paths_arrived"] = int((pm[-1][1][2] == 0).sum())
 

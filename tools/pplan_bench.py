@@ -9,7 +9,8 @@ workload and H in --headings, appended to --out.  It measures; no test asserts a
     solve_over_point, outer rounds, tile launches, states_relaxed_per_s = tile launches x 64 H / solve time;
   - setup_samples_per_s = nx ny H m / setup_ms, next to sample_samples_per_s of gpis_dfield_sample on as many device points;
   - project_ms: PosePlanner.project into a kept Planner; paths_ms: --paths pose paths from random free points without a
-    heading, their total length;
+    heading, their total length (solve_ms_all, project_ms_all, paths_ms_all: every repeat, the spread a comparison between two
+    builds needs);
   - host_ms: tests/pplan_ref.py (numpy body rule, heapq Dijkstra on the reversed graph) on the same input, and whether its bits
     equal the device's (skipped with --no-host).
 Kernel statistics come from a run of their own:
@@ -54,9 +55,14 @@ def main():
         r = fn()
         return (time.perf_counter() - t0) * 1e3, r
 
-    def med(fn):
+    repeats = {}                                            # every repeat of the times a comparison between builds looks at
+
+    def med(fn, key=None):
         fn()
-        return float(np.median([timed(fn)[0] for _ in range(args.repeats)]))
+        t = [timed(fn)[0] for _ in range(args.repeats)]
+        if key:
+            repeats[key + "_all"] = t
+        return float(np.median(t))
 
     df = gpismap_amd.DistanceField()
     pl, proj, pp = gpismap_amd.Planner(), gpismap_amd.Planner(), gpismap_amd.PosePlanner()
@@ -105,7 +111,7 @@ def main():
             goal = np.array([[X[p0 % nx], Y[p0 // nx]]], F32)
             point_ms = med(lambda: pl.solve(df, goal, clearance=float(rad[0]), margin=0.0))
             pinf = pl.info()
-            solve_ms = med(lambda: pp.solve(df, fp, goal, H=H, moves=args.moves, **opts))
+            solve_ms = med(lambda: pp.solve(df, fp, goal, H=H, moves=args.moves, **opts), "solve_ms")
             inf = pp.info()
             setups = []
             for _ in range(args.repeats):
@@ -119,11 +125,11 @@ def main():
             torch.cuda.synchronize()
             sample_ms = med(lambda: df.sample(xs.data_ptr(), m=nsamp, d_out=out.data_ptr()))
             del xs, out
-            project_ms = med(lambda: pp.project(proj))
+            project_ms = med(lambda: pp.project(proj), "project_ms")
             rng = np.random.default_rng(0)
             sp = cand[rng.integers(0, cand.size, args.paths)]
             starts = np.stack([X[sp % nx], Y[sp // nx]], axis=1).astype(F32)
-            paths_ms = med(lambda: pp.paths(starts))
+            paths_ms = med(lambda: pp.paths(starts), "paths_ms")
             st = pp.paths(starts)[3]
             r = {"workload": w, "shape": [nx, ny], "H": H, "step": step, "states": nx * ny * H, "body_balls": int(m), "moves": args.moves,
                  "repeats": args.repeats, "point_solve_ms": point_ms, "point_rounds": pinf["rounds"], "point_tile_launches": pinf["tile_launches"],
@@ -133,7 +139,8 @@ def main():
                  "states_relaxed_per_s": inf["tile_launches"] * 64 * H / (solve_ms * 1e-3),
                  "setup_samples": nsamp, "setup_samples_per_s": nsamp / (setup_ms * 1e-3), "sample_ms": sample_ms,
                  "sample_samples_per_s": nsamp / (sample_ms * 1e-3), "project_ms": project_ms, "projected_reachable": proj.info()["reachable"],
-                 "paths": args.paths, "paths_ms": paths_ms, "path_states": int(pp.last_off[-1]), "paths_arrived": int((st == 0).sum())}
+                 "paths": args.paths, "paths_ms": paths_ms, "path_states": int(pp.last_off[-1]), "paths_arrived": int((st == 0).sum()),
+                 **repeats}
             if not args.no_host:
                 import body_ref
                 import pplan_ref
