@@ -78,6 +78,12 @@ class gpis_cover_opts(C.Structure):
                 ("max_rounds", C.c_int)]
 
 
+class gpis_detect_opts(C.Structure):
+    _fields_ = [("min_dist", C.c_double), ("link", C.c_double), ("pad", C.c_double), ("max_radius", C.c_double),
+                ("gate", C.c_double), ("max_speed", C.c_double), ("alpha", C.c_double), ("min_points", C.c_int),
+                ("max_missed", C.c_int), ("stride", C.c_int), ("max_rounds", C.c_int)]
+
+
 class gpis_view_opts(C.Structure):
     _fields_ = [("march", gpis_render_field_opts), ("back_off", C.c_float), ("max_gap", C.c_float), ("miss", C.c_float),
                 ("min_dist", C.c_float)]
@@ -406,6 +412,22 @@ def lib():
         L.gpis_view_get.argtypes = [vp, C.POINTER(C.c_longlong), ip, C.c_int]
         L.gpis_view_get_predicted.argtypes = [vp, C.c_int, fp, C.c_longlong]
         L.gpis_view_info.argtypes = [vp, dp, C.c_int]
+    if hasattr(L, "gpis_detect_create"):
+        do, ub, ll = C.POINTER(gpis_detect_opts), C.POINTER(C.c_ubyte), C.POINTER(C.c_longlong)
+        L.gpis_detect_default_opts.argtypes = [C.c_int, C.c_float, do]
+        L.gpis_detect_create.restype = vp
+        L.gpis_detect_create.argtypes = []
+        L.gpis_detect_destroy.argtypes = [vp]
+        L.gpis_detect_set_schedule.argtypes = [vp, C.c_int, C.c_int]
+        L.gpis_detect_reset_tracks.argtypes = [vp]
+        L.gpis3_detect_depth_field.argtypes = [vp, vp, vp, vp, C.POINTER(gpis_cam), fp, dp, C.c_double, do, vp]
+        L.gpis2_detect_scan_field.argtypes = [vp, vp, vp, vp, fp, fp, C.c_int, fp, dp, C.c_double, do, vp]
+        L.gpis_detect_counts.argtypes = [vp, ll, ll, ll]
+        L.gpis_detect_get_balls.argtypes = [vp, dp, dp, dp, ip, fp, ip, ip, ip, ip]
+        L.gpis_detect_get_components.argtypes = [vp, ip, ip, fp, dp, dp, ip]
+        L.gpis_detect_get_samples.argtypes = [vp, ip, fp, fp, ub]
+        L.gpis_detect_to_obstacles.argtypes = [vp, vp]
+        L.gpis_detect_info.argtypes = [vp, dp, C.c_int]
     _lib = L
     return L
 
@@ -1270,6 +1292,51 @@ class DistanceField:
             self._renderer = Renderer()
         return self._renderer
 
+    def detect_scan(self, thetas, ranges, pose, off2, t, detector=None, cover=None, obstacles=None, stream=None, **opts):
+        """Moving obstacles of a laser scan (gpis2_detect_scan_field without a map): the beams that end in what this field holds
+        as free space, at least min_dist from every surface, grouped along the scan into components and turned into one ball
+        each, with velocities from the detector's tracks.  pose [6] in double ([t(2), R(4)]); t: the absolute time of the scan;
+        cover: a Coverage of this field's lattice (a sample counts only where the mask is set); obstacles: an Obstacles set to
+        receive the balls (Detector.to_obstacles).  opts: the gpis_detect_opts fields.  Returns Detector.result()."""
+        thetas, ranges, off = _scan_frame("detect_scan", thetas, ranges, off2, None)
+        pose = np.ascontiguousarray(pose, dtype=np.float64).ravel()
+        if pose.size != 6:
+            raise GpisError("pose must have 6 elements")
+        d = detector if detector is not None else self._own_detector()
+        o = self._detect_opts(2, opts)
+        _check(self.L.gpis2_detect_scan_field(None, self.h, d.h, cover.h if cover is not None else None, _p(thetas), _p(ranges),
+                                              thetas.size, off, _p(pose, C.c_double), float(t), o, C.c_void_p(stream or 0)),
+               "gpis2_detect_scan_field")
+        if obstacles is not None:
+            d.to_obstacles(obstacles)
+        return d.result()
+
+    def detect_depth(self, depth, pose, cam6, t, detector=None, cover=None, obstacles=None, stream=None, **opts):
+        """detect_scan for a depth frame (gpis3_detect_depth_field without a map): the tracker's strided pixels, components
+        over the 8 neighbours on the strided grid.  pose [12] in double ([t(3), R(9)]); cam6: (fx, fy, cx, cy, width, height)."""
+        depth, cam = _depth_frame("detect_depth", depth, cam6, None, None)
+        pose = np.ascontiguousarray(pose, dtype=np.float64).ravel()
+        if pose.size != 12:
+            raise GpisError("pose must have 12 elements")
+        d = detector if detector is not None else self._own_detector()
+        o = self._detect_opts(3, opts)
+        _check(self.L.gpis3_detect_depth_field(None, self.h, d.h, cover.h if cover is not None else None, cam, _p(depth),
+                                               _p(pose, C.c_double), float(t), o, C.c_void_p(stream or 0)),
+               "gpis3_detect_depth_field")
+        if obstacles is not None:
+            d.to_obstacles(obstacles)
+        return d.result()
+
+    def _detect_opts(self, dim, opts):
+        # (a field without a result has no step: the entry itself refuses it, with GPIS_ERR_STATE)
+        step = self.info()["step"]
+        return C.byref(detect_opts(dim, step, **opts)) if step > 0 else None
+
+    def _own_detector(self):
+        if getattr(self, "_detector", None) is None:
+            self._detector = Detector()
+        return self._detector
+
     def plan(self, goals, planner=None, **opts):
         """Cost-to-go and policy over this field's free space towards `goals` [g, dim] (gpis_plan_solve).  opts: the
         gpis_plan_opts fields (clearance, margin, gain, connectivity, max_rounds; defaults for this field's step).  Unknown
@@ -1918,6 +1985,115 @@ class Coverage:
         _check(self.L.gpis_cover_restrict(self.h, field.h, out.h, u, C.c_void_p(stream or 0)), "gpis_cover_restrict")
         out._device = field.device()
         return out
+
+
+def detect_opts(dim, step, **opts):
+    """gpis_detect_opts of the library's defaults for `dim` and a field of lattice step `step` (gpis_detect_default_opts) with
+    the given fields replaced."""
+    o = gpis_detect_opts()
+    _check(lib().gpis_detect_default_opts(int(dim), float(step), C.byref(o)), "gpis_detect_default_opts")
+    names = {f[0] for f in gpis_detect_opts._fields_}
+    for k, v in opts.items():
+        if k not in names:
+            raise GpisError("unknown detector option %r" % k)
+        setattr(o, k, v)
+    return o
+
+
+class Detector:
+    """Moving obstacles from a frame's residual against a field (gpis_detect_*): holds the device result of the last
+    DistanceField.detect_scan / detect_depth call and the tracks that give the balls their ids, ages and velocities."""
+
+    INFO_KEYS = ("valid", "dim", "grid", "grid_w", "grid_h", "samples", "foreign", "components", "balls", "noise", "too_large",
+                 "dropped", "rounds", "tracks", "tracks_held", "t_prev", "ms", "setup_ms", "flag_ms", "compact_ms", "label_ms",
+                 "table_ms")
+    INT_KEYS = INFO_KEYS[:15]
+
+    def __init__(self):
+        self.L = lib()
+        if not hasattr(self.L, "gpis_detect_create"):
+            raise GpisError("the native library has no detector (gpis_detect_create)")
+        if self.L.gpis_device_count() < 1:
+            raise GpisError("no HIP device: gpismap_amd has no CPU fallback")
+        self.h = C.c_void_p(self.L.gpis_detect_create())
+        if not self.h:
+            raise GpisError("gpis_detect_create failed")
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.gpis_detect_destroy(self.h)
+            self.h = None
+
+    __del__ = close
+
+    def set_schedule(self, check_every=0, profile=False):
+        """Labelling rounds per read-back (1 .. 64; 0 keeps it) and whether every stage is synchronised for its time."""
+        _check(self.L.gpis_detect_set_schedule(self.h, int(check_every), int(bool(profile))), "gpis_detect_set_schedule")
+        return self
+
+    def reset_tracks(self):
+        _check(self.L.gpis_detect_reset_tracks(self.h), "gpis_detect_reset_tracks")
+        return self
+
+    def info(self):
+        out = np.zeros(len(self.INFO_KEYS), dtype=np.float64)
+        _check(self.L.gpis_detect_info(self.h, _p(out, C.c_double), out.size), "gpis_detect_info")
+        d = dict(zip(self.INFO_KEYS, out.tolist()))
+        for k in self.INT_KEYS:
+            d[k] = int(d[k])
+        return d
+
+    def _counts(self):
+        g, c, b = C.c_longlong(0), C.c_longlong(0), C.c_longlong(0)
+        _check(self.L.gpis_detect_counts(self.h, C.byref(g), C.byref(c), C.byref(b)), "gpis_detect_counts")
+        return g.value, c.value, b.value
+
+    def result(self):
+        """The balls of the last call: dict(centre, velocity [b, dim] f64, radius [b] f64, count, label, id, age, missed [b]
+        i32, box [b, 2, dim] f32 (least, greatest), and the counts samples, foreign, components, noise, too_large, dropped,
+        rounds).  Detected balls come in label order; coasting ones (count 0, label -1) follow in id order."""
+        i = self.info()
+        _, _, b = self._counts()
+        dim = i["dim"]
+        c, v, r = np.zeros((b, dim), np.float64), np.zeros((b, dim), np.float64), np.zeros(b, np.float64)
+        cnt, lab, ids, age, mis = (np.zeros(b, np.int32) for _ in range(5))
+        box = np.zeros((b, 6), np.float32)
+        _check(self.L.gpis_detect_get_balls(self.h, _p(c, C.c_double), _p(v, C.c_double), _p(r, C.c_double), _p(cnt, C.c_int), _p(box),
+                                            _p(lab, C.c_int), _p(ids, C.c_int), _p(age, C.c_int), _p(mis, C.c_int)),
+               "gpis_detect_get_balls")
+        out = dict(centre=c, velocity=v, radius=r, count=cnt, label=lab, id=ids, age=age, missed=mis,
+                   box=np.ascontiguousarray(box.reshape(b, 2, 3)[:, :, :dim]))
+        for k in ("samples", "foreign", "components", "noise", "too_large", "dropped", "rounds"):
+            out[k] = i[k]
+        return out
+
+    def components(self):
+        """Every component of the last call in label order: dict(label, count, flag [c] i32 (0 ball, 1 noise, 2 too large, 3
+        dropped for the cap), box [c, 2, dim] f32, centre [c, dim] f64, r2 [c] f64)."""
+        _, nc, _ = self._counts()
+        dim = self.info()["dim"]
+        lab, cnt, flg = np.zeros(nc, np.int32), np.zeros(nc, np.int32), np.zeros(nc, np.int32)
+        box, ctr, r2 = np.zeros((nc, 6), np.float32), np.zeros((nc, 3), np.float64), np.zeros(nc, np.float64)
+        _check(self.L.gpis_detect_get_components(self.h, _p(lab, C.c_int), _p(cnt, C.c_int), _p(box), _p(ctr, C.c_double),
+                                                 _p(r2, C.c_double), _p(flg, C.c_int)), "gpis_detect_get_components")
+        return dict(label=lab, count=cnt, flag=flg, box=np.ascontiguousarray(box.reshape(nc, 2, 3)[:, :, :dim]),
+                    centre=np.ascontiguousarray(ctr[:, :dim]), r2=r2)
+
+    def samples(self):
+        """Per sample of the grid (the beams; 3-D: the W // stride x H // stride strided pixels, column-major): dict(label i32
+        (the component's smallest grid index; -1: not foreign or not valid), d f32 (NaN: not valid, or off the lattice), x
+        [g, dim] f32, foreign u8)."""
+        g, _, _ = self._counts()
+        dim = self.info()["dim"]
+        lab, d, x, f = np.full(g, -1, np.int32), np.full(g, np.nan, np.float32), np.zeros((g, dim), np.float32), np.zeros(g, np.uint8)
+        _check(self.L.gpis_detect_get_samples(self.h, _p(lab, C.c_int), _p(d), _p(x), _p(f, C.c_ubyte)), "gpis_detect_get_samples")
+        return dict(label=lab, d=d, x=x, foreign=f)
+
+    def to_obstacles(self, obstacles):
+        """Hand the current balls to an Obstacles set (gpis_detect_to_obstacles): centres, velocities and radii with epoch =
+        the call's t; the set's cost options stay; no balls empties the set.  Returns the set."""
+        _check(self.L.gpis_detect_to_obstacles(self.h, obstacles.h), "gpis_detect_to_obstacles")
+        return obstacles
 
 
 def view_opts(dim, step, **opts):

@@ -21,6 +21,7 @@
 #include "obst.h"
 #include "body.h"
 #include "cover.h"
+#include "detect.h"
 #include "view.h"
 #include "obsgp.h"
 #include "ongpis.h"
@@ -1553,6 +1554,147 @@ int gpis_cover_info(void* cover, double* out, int n) {
                           v ? (double)c.step : 0.0, (double)c.frames, c.frontiers_valid ? 1.0 : 0.0, (double)c.npoints,
                           (double)c.ncomponents, (double)c.label.size(), (double)c.rounds, c.integrate_ms, c.frontiers_ms};
     for (int i = 0; i < n && i < 14; ++i) out[i] = w[i];
+    return GPIS_OK;
+}
+
+// ---- moving obstacles detected from a frame's residual against a field -----------------------------------------------------
+static void detect_opts_out(const DetectOpts& c, gpis_detect_opts* o) {
+    o->min_dist = c.min_dist; o->link = c.link; o->pad = c.pad; o->max_radius = c.max_radius; o->gate = c.gate;
+    o->max_speed = c.max_speed; o->alpha = c.alpha; o->min_points = c.min_points; o->max_missed = c.max_missed; o->stride = c.stride;
+    o->max_rounds = c.max_rounds;
+}
+int gpis_detect_default_opts(int dim, float step, gpis_detect_opts* o) {
+    DetectOpts c;
+    if (!o) return GPIS_ERR_ARG;
+    if (int rc = detect_default_opts(dim, step, &c)) return rc;
+    detect_opts_out(c, o);
+    return GPIS_OK;
+}
+void* gpis_detect_create(void) {
+    if (gpis_device_count() < 1) { fprintf(stderr, "[gpismap_amd] no HIP device\n"); return nullptr; }
+    Detector* d = new (std::nothrow) Detector();
+    if (d && !d->trk.own) { delete d; return nullptr; }
+    return d;
+}
+void gpis_detect_destroy(void* det) { delete (Detector*)det; }
+int gpis_detect_set_schedule(void* det, int check_every, int profile) {
+    if (!det || check_every < 0) return GPIS_ERR_ARG;
+    Detector& d = *(Detector*)det;
+    if (check_every > 0) d.check_every = std::min(check_every, (int)Detector::kMaxBatch);
+    d.profile = profile != 0;
+    return GPIS_OK;
+}
+int gpis_detect_reset_tracks(void* det) {
+    if (!det) return GPIS_ERR_ARG;
+    ((Detector*)det)->tracks.reset();
+    return GPIS_OK;
+}
+// every refusal comes before the previous result is touched: the options (the caller's, or the defaults for the field's step),
+// the frame, then Detector::check
+static int detect_call(void* d, void* det, void* cover, const SensorFrame& f, const float* in, const double* pose, double t,
+                       const gpis_detect_opts* opts, void* stream) {
+    const DistanceField& df = *(const DistanceField*)d;
+    Detector& dt = *(Detector*)det;
+    DetectOpts o;
+    if (opts) {
+        o.min_dist = opts->min_dist; o.link = opts->link; o.pad = opts->pad; o.max_radius = opts->max_radius; o.gate = opts->gate;
+        o.max_speed = opts->max_speed; o.alpha = opts->alpha; o.min_points = opts->min_points; o.max_missed = opts->max_missed;
+        o.stride = opts->stride; o.max_rounds = opts->max_rounds;
+    } else if (!df.valid) return GPIS_ERR_STATE;
+    else (void)detect_default_opts(df.dim, df.step, &o);
+    if (int rc = dt.check(df, (const Coverage*)cover, f.geo, f.n, pose, o, t)) return rc;
+    DeviceScope ds(df.device);
+    try {
+        if (int rc = dt.bind(df.device)) { dt.clear_result(); return rc; }
+        const int rc = dt.detect(df, (const Coverage*)cover, f.geo, in, f.cs_or_null(), f.n, pose, o, t, stream ? (hipStream_t)stream : df.own);
+        if (rc != GPIS_OK) dt.clear_result();
+        return rc;
+    } catch (...) { dt.clear_result(); return GPIS_ERR_STATE; }
+}
+int gpis3_detect_depth_field(void* m, void* df, void* det, void* cover, const gpis_cam* cam, const float* depth, const double* pose12,
+                             double t, const gpis_detect_opts* opts, void* stream) {
+    if (!df || !det || !depth || !pose12 || (!cam && !m)) return GPIS_ERR_ARG;
+    SensorFrame f;
+    if (int rc = depth_frame(m, cam, &f)) return rc;
+    return detect_call(df, det, cover, f, depth, pose12, t, opts, stream);
+}
+int gpis2_detect_scan_field(void* m, void* df, void* det, void* cover, const float* thetas, const float* ranges, int n, const float* off2,
+                            const double* pose6, double t, const gpis_detect_opts* opts, void* stream) {
+    if (!df || !det || !thetas || !ranges || !pose6 || n < 1 || (!off2 && !m)) return GPIS_ERR_ARG;
+    SensorFrame f;
+    if (int rc = scan_frame(m, thetas, n, off2, &f)) return rc;
+    return detect_call(df, det, cover, f, ranges, pose6, t, opts, stream);
+}
+int gpis_detect_counts(void* det, long long* grid, long long* components, long long* balls) {
+    if (!det) return GPIS_ERR_ARG;
+    const Detector& d = *(const Detector*)det;
+    if (!d.valid) return GPIS_ERR_STATE;
+    if (grid) *grid = d.grid;
+    if (components) *components = d.ncomp;
+    if (balls) *balls = (long long)d.balls.size();
+    return GPIS_OK;
+}
+int gpis_detect_get_balls(void* det, double* centre, double* velocity, double* radius, int* count, float* box, int* label, int* id,
+                          int* age, int* missed) {
+    if (!det) return GPIS_ERR_ARG;
+    const Detector& d = *(const Detector*)det;
+    if (!d.valid) return GPIS_ERR_STATE;
+    for (size_t i = 0; i < d.balls.size(); ++i) {
+        const DetBall& b = d.balls[i];
+        for (int a = 0; a < d.dim; ++a) {
+            if (centre) centre[i * d.dim + a] = b.c[a];
+            if (velocity) velocity[i * d.dim + a] = b.v[a];
+        }
+        if (radius) radius[i] = b.r;
+        if (count) count[i] = b.comp >= 0 ? d.c_count[b.comp] : 0;
+        if (label) label[i] = b.comp >= 0 ? d.c_label[b.comp] : -1;
+        if (box) for (int a = 0; a < 6; ++a) box[i * 6 + a] = b.comp >= 0 ? d.c_box[(size_t)b.comp * 6 + a] : 0.f;
+        if (id) id[i] = b.id;
+        if (age) age[i] = b.age;
+        if (missed) missed[i] = b.missed;
+    }
+    return GPIS_OK;
+}
+int gpis_detect_get_components(void* det, int* label, int* count, float* box, double* centre, double* r2, int* flag) {
+    if (!det) return GPIS_ERR_ARG;
+    const Detector& d = *(const Detector*)det;
+    if (!d.valid) return GPIS_ERR_STATE;
+    const size_t nc = (size_t)d.ncomp;
+    if (label && nc) std::memcpy(label, d.c_label.data(), sizeof(int) * nc);
+    if (count && nc) std::memcpy(count, d.c_count.data(), sizeof(int) * nc);
+    if (box && nc) std::memcpy(box, d.c_box.data(), sizeof(float) * 6 * nc);
+    if (centre && nc) std::memcpy(centre, d.c_centre.data(), sizeof(double) * 3 * nc);
+    if (r2 && nc) std::memcpy(r2, d.c_r2.data(), sizeof(double) * nc);
+    if (flag && nc) std::memcpy(flag, d.c_flag.data(), sizeof(int) * nc);
+    return GPIS_OK;
+}
+int gpis_detect_get_samples(void* det, int* label, float* dist, float* x, unsigned char* foreign) {
+    if (!det) return GPIS_ERR_ARG;
+    Detector& d = *(Detector*)det;
+    if (!d.valid) return GPIS_ERR_STATE;
+    if (d.grid < 1) return GPIS_OK;
+    DeviceScope ds(d.device);
+    const size_t g = (size_t)d.grid;
+    hipStream_t s = d.trk.own;
+    if (label) GPIS_HIP(hipMemcpyAsync(label, d.d_limg, sizeof(int) * g, hipMemcpyDeviceToHost, s));
+    if (dist) GPIS_HIP(hipMemcpyAsync(dist, d.d_d, sizeof(float) * g, hipMemcpyDeviceToHost, s));
+    if (x) GPIS_HIP(hipMemcpyAsync(x, d.d_x, sizeof(float) * g * d.dim, hipMemcpyDeviceToHost, s));
+    if (foreign) GPIS_HIP(hipMemcpyAsync(foreign, d.d_flag, g, hipMemcpyDeviceToHost, s));
+    GPIS_HIP(hipStreamSynchronize(s));
+    return GPIS_OK;
+}
+int gpis_detect_to_obstacles(void* det, void* obst) {
+    if (!det || !obst) return GPIS_ERR_ARG;
+    try { return ((const Detector*)det)->to_obstacles(*(Obstacles*)obst); } catch (...) { return GPIS_ERR_STATE; }
+}
+int gpis_detect_info(void* det, double* out, int n) {
+    if (!det || !out || n < 0) return GPIS_ERR_ARG;
+    const Detector& d = *(const Detector*)det;
+    const double v[22] = {d.valid ? 1.0 : 0.0, (double)d.dim, (double)d.grid, (double)d.gw, (double)d.gh, (double)d.samples, (double)d.foreign,
+                          (double)d.ncomp, (double)d.balls.size(), (double)d.noise, (double)d.large, (double)d.dropped, (double)d.rounds,
+                          (double)d.tracks.balls.size(), d.tracks.held ? 1.0 : 0.0, d.tracks.t_prev, d.ms, d.setup_ms, d.flag_ms,
+                          d.compact_ms, d.label_ms, d.table_ms};
+    for (int i = 0; i < n && i < 22; ++i) out[i] = v[i];
     return GPIS_OK;
 }
 

@@ -1312,6 +1312,81 @@ int   gpis_view_get_predicted(void* view, int pose, float* out, long long n);
  * prediction, of the sector tables (2-D), of the target list, of the gather */
 int   gpis_view_info(void* view, double* out, int n);
 
+/* ---- moving obstacles detected from a frame's residual against a field ------------------------------------------
+ * The stage between "a scan and the field" and the set the controller takes (gpis_obst_*).  tests/detect_ref.py states every rule
+ * below in numpy; the device's arrays have its bits.
+ *
+ * Samples: the tracker's (gpis*_track_*_field: the same validity windows, order, float32 local points and stride), on the sample
+ * grid: the beams of a scan, or the W / stride x H / stride strided pixels of a depth frame in column-major order.  x = the
+ * sample's world point at the pose cast to float32, d = gpis_dfield_sample's distance there.  A sample is foreign iff d is finite
+ * and (double)d >= min_dist and, with a coverage holder, the byte of the lattice point nearest x -- per axis
+ * min((int)floorf((x - origin) / step + 0.5f), n - 1) in float32 -- is set.
+ * Components: two foreign samples that are neighbours on the grid (2-D: beams k - 1 and k + 1, with no wrap from the last beam to
+ * the first; 3-D: the 8 neighbours on the strided grid) are linked iff sum_a e_a e_a <= link * link, e_a = (double)x_a -
+ * (double)y_a, summed left to right.  A component's label is its smallest grid index.
+ * Per component: count; box = the least and greatest float32 coordinate per axis; centre c_a = 0.5 * ((double)lo_a +
+ * (double)hi_a); r2 = the greatest sum_a ((double)x_a - c_a)^2.  Flags: 1 noise (count < min_points), 2 too large (sqrt(r2) >
+ * max_radius), 3 dropped for the cap (of the rest the 256 of the largest counts are kept, ties by the lower label), 0 a ball of
+ * radius sqrt(r2) + pad.
+ * Tracks (host, double): the balls of the previous call at t_prev with velocity, id and age.  Pairs (old i, new j) with
+ * |c_j - (c_i + v_i dt)| <= gate + max_speed * dt are taken greedily in ascending (distance, i, j).  Matched: v_raw = (c_j - c_i)
+ * / dt, v = alpha v_raw + (1 - alpha) v_i (an old ball of age 0: v_raw whole), the id kept, age + 1.  New: v = 0, a fresh id,
+ * age 0.  An unmatched old ball coasts at c_i + v_i dt for up to max_missed calls; coasting balls follow the detected ones in id
+ * order while there is room below 256.
+ *
+ * Errors, all before the previous result is touched: GPIS_ERR_ARG: a NULL handle or array, a non-finite or negative option,
+ * alpha outside (0, 1], stride < 1, min_points < 1, a non-finite pose entry or t, a field of another dim, t <= the previous
+ * call's with tracks held; GPIS_ERR_STATE: a field without a result, a coverage holder that was never reset or lies on another
+ * lattice, getters without a result; GPIS_ERR_LIMIT: more than 2^26 pixels or beams, before anything is read.  max_rounds > 0
+ * exceeded: GPIS_ERR_LIMIT, no result is held, the tracks stay; the same holds for GPIS_ERR_HIP (an allocation, a copy or a
+ * launch failed once the call was under way).  A frame with no valid or no foreign sample is a result with no
+ * balls. */
+typedef struct gpis_detect_opts {
+    double min_dist;            /* metres; default 2 lattice steps */
+    double link;                /* metres; default 3 lattice steps */
+    double pad;                 /* metres; default 1 lattice step */
+    double max_radius;          /* metres; default 1 */
+    double gate;                /* metres; default 4 lattice steps */
+    double max_speed;           /* metres per unit of t; default 2 */
+    double alpha;               /* default 0.5 */
+    int min_points;             /* default 3 */
+    int max_missed;             /* default 2 */
+    int stride;                 /* 3-D: the pixel stride, default 2; ignored in 2-D */
+    int max_rounds;             /* labelling rounds; 0: until converged */
+} gpis_detect_opts;
+/* a length of k lattice steps is stored as (double)(k * step) with the product in float.  Needs no device. */
+int   gpis_detect_default_opts(int dim, float step, gpis_detect_opts* opts);
+void* gpis_detect_create(void);                             /* on the current device; NULL without one */
+void  gpis_detect_destroy(void* det);
+/* check_every: labelling rounds per read-back (1 .. 64; 0 keeps it); profile != 0: synchronise after every stage, so that the
+ * stage times of gpis_detect_info are the stages' own.  Neither changes a result. */
+int   gpis_detect_set_schedule(void* det, int check_every, int profile);
+int   gpis_detect_reset_tracks(void* det);
+/* cover: a coverage holder or NULL; cam NULL: the map's camera; pose12 = [t(3), R(9) column-major] in double; t: the absolute time
+ * of the frame; opts NULL: the defaults for the field's step */
+int   gpis3_detect_depth_field(void* map, void* df, void* det, void* cover, const gpis_cam* cam, const float* depth,
+                               const double* pose12, double t, const gpis_detect_opts* opts, void* hip_stream);
+/* off2 NULL: the map's sensor offset; pose6 = [t(2), R(4)] in double */
+int   gpis2_detect_scan_field(void* map, void* df, void* det, void* cover, const float* thetas, const float* ranges, int n,
+                              const float* off2, const double* pose6, double t, const gpis_detect_opts* opts, void* hip_stream);
+/* the sizes of the last result: samples of the grid, components, balls */
+int   gpis_detect_counts(void* det, long long* grid, long long* components, long long* balls);
+/* the balls: centre, velocity [b][dim], radius, count, box [b][6], label, id, age, missed [b] (a coasting ball: count 0, box 0,
+ * label -1); any may be NULL */
+int   gpis_detect_get_balls(void* det, double* centre, double* velocity, double* radius, int* count, float* box, int* label, int* id,
+                            int* age, int* missed);
+/* every component in label order: label, count, box [c][6], centre [c][3], r2, flag [c]; any may be NULL */
+int   gpis_detect_get_components(void* det, int* label, int* count, float* box, double* centre, double* r2, int* flag);
+/* per sample of the grid: label (-1: not foreign or not valid), d (NaN: not valid, or off the lattice), x [g][dim] (0: not
+ * valid), the foreign byte; any may be NULL */
+int   gpis_detect_get_samples(void* det, int* label, float* dist, float* x, unsigned char* foreign);
+/* gpis_obst_set(dim, balls, centre, velocity, radius, epoch = t) with the current balls; the set's options stay */
+int   gpis_detect_to_obstacles(void* det, void* obst);
+/* out[0..n): 1 if a result is held, dim, grid samples, grid columns, grid rows (3-D), valid samples, foreign samples, components,
+ * balls, noise, too large, dropped, labelling rounds, tracks, 1 if tracks are held, t_prev, ms of host wall time of the call, of
+ * the set-up, the flags, the compaction, the labelling, the table */
+int   gpis_detect_info(void* det, double* out, int n);
+
 #ifdef __cplusplus
 }
 #endif
