@@ -1102,6 +1102,10 @@ int   gpis_body_traj_clearance(void* traj, void* df, void* body, double clearanc
  *             T_k = t_k for k < N-2, T_{N-2} = t_{N-2} + t_{N-1}
  *   gradient  g_i[a] = w_smooth a_i[a] + w_obs (f_i[a] + w_turn (T_{i-1}[a] - T_i[a])), a < 2, interior i;
  *             g_i[2] = w_smooth a_i[2] + w_obs f_i[2]
+ * What is descended: with w_turn = 1, g is the gradient of 1/2 w_smooth sum_k |x_{k+1} - x_k|^2 + w_obs sum_i sum_j c(e_ij) with i
+ * over all N waypoints: the balls of the two end waypoints turn with chords 0 and N-2 and so move x_1 and x_{N-2} through t_0 and
+ * t_{N-1}.  The reported `obstacle` leaves the two ends out, so it is not that cost's second term; w_turn != 1 weighs the turn
+ * term and is the gradient of no cost.
  * The evaluation in the same launch: length, smooth, min_dist, nonfinite, collides are gpis_traj_optimize's (the point's);
  * obstacle is the tree sum over the interior waypoints of (c(e_0), then + c(e_j)) with gpis_traj_optimize's point cost c at the
  * balls of the result; the body result D_min, waypoint, ball, collides is what gpis_body_traj_clearance(traj, df, body,
