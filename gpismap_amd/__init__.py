@@ -64,6 +64,10 @@ class gpis_obst_opts(C.Structure):
     _fields_ = [("clearance", C.c_double), ("margin", C.c_double), ("w_obs", C.c_double), ("w_col", C.c_double)]
 
 
+class gpis_retime_opts(C.Structure):
+    _fields_ = [("slot", C.c_double), ("max_pause", C.c_int), ("clearance", C.c_double), ("press_on", C.c_int)]
+
+
 class gpis_plan_opts(C.Structure):
     _fields_ = [("clearance", C.c_float), ("margin", C.c_float), ("gain", C.c_float), ("connectivity", C.c_int),
                 ("max_rounds", C.c_int)]
@@ -369,6 +373,14 @@ def lib():
         L.gpis_obst_mppi_step.argtypes = [vp, vp, vp, vp, d, dp, dp, C.POINTER(gpis_mppi_opts), dp, vp]
         L.gpis_obst_mppi_get.argtypes = [vp, ip, dp, dp]
         L.gpis_obst_check_timing.argtypes = [vp, vp, d, C.c_int, d, d, d, dp, dp, ip, ip, ip]
+    if hasattr(L, "gpis_retime_solve"):
+        ro = C.POINTER(gpis_retime_opts)
+        L.gpis_retime_default_opts.argtypes = [C.c_int, C.c_float, ro]
+        L.gpis_retime_solve.argtypes = [vp, vp, d, ro, vp]
+        L.gpis_retime_get.argtypes = [vp, ip, ip, ip, ip, ip, ip, ro, dp]
+        L.gpis_retime_controls.argtypes = [vp, C.c_int, C.c_int, d, d, dp, dp, dp, ip]
+        L.gpis_retime_follow.argtypes = [vp, vp, C.c_int, C.c_int, d, d, dp, dp]
+        L.gpis_retime_check.argtypes = [vp, vp, C.c_int, d, dp, dp, ip, ip, ip]
     if hasattr(L, "gpis_body_create"):
         L.gpis_body_create.restype = vp
         L.gpis_body_create.argtypes = []
@@ -2356,6 +2368,66 @@ class Trajectories:
                                              _p(r["first_hit"], C.c_int), _p(r["collides"], C.c_int)), "gpis_obst_check_timing")
         return r
 
+    OWN_LEN = 1280                                       # real slots of the longest schedule (1024 own slots + 255 pauses + 1)
+
+    def retime(self, obstacles, t_begin=0.0, stream=0, **opts):
+        """Re-time the timed trajectories so that they wait for the balls of an Obstacles to pass (gpis_retime_solve): the
+        geometry and the timing stay, a schedule says for every real slot of `slot` seconds, counted from the absolute time
+        t_begin, which own slot of the timed trajectory is played; the schedule that arrives first within max_pause pause slots
+        is kept.  opts: gpis_retime_opts fields (slot, max_pause, clearance, press_on); clearance defaults to the set's own.
+        Returns retimed()."""
+        i = self.info()
+        if not self.timing_info()["timed"]:
+            raise GpisError("trajectories hold no timing")
+        if "clearance" not in opts:
+            opts = dict(opts, clearance=obstacles.get()["opts"]["clearance"])
+        o = retime_opts(i["dim"], 1.0, **opts)
+        _check(self.L.gpis_retime_solve(self.h, obstacles.h, float(t_begin), C.byref(o), C.c_void_p(stream)), "gpis_retime_solve")
+        return self.retimed()
+
+    def retimed(self):
+        """The last schedule (gpis_retime_get): dict(status [m] i32 (0 clear as timed, 1 re-timed with pauses, 2 no timing, 3 no
+        schedule within max_pause, 4 too long for this slot), arrive, pauses, own_slots, first_pause [m] i32, own [m, 1280] i32
+        (the own slot of every real slot), slot, max_pause, clearance, press_on, t_begin, ms)."""
+        m = self.info()["m"]
+        r = {k: np.zeros(m, np.int32) for k in ("status", "arrive", "pauses", "own_slots", "first_pause")}
+        r["own"] = np.zeros((m, self.OWN_LEN), np.int32)
+        o = gpis_retime_opts()
+        inf = np.zeros(2, np.float64)
+        _check(self.L.gpis_retime_get(self.h, _p(r["status"], C.c_int), _p(r["arrive"], C.c_int), _p(r["pauses"], C.c_int),
+                                      _p(r["own_slots"], C.c_int), _p(r["first_pause"], C.c_int), _p(r["own"], C.c_int), C.byref(o),
+                                      _p(inf, C.c_double)), "gpis_retime_get")
+        r.update(slot=o.slot, max_pause=o.max_pause, clearance=o.clearance, press_on=o.press_on, t_begin=float(inf[0]), ms=float(inf[1]))
+        return r
+
+    def retimed_controls(self, T, k0=0, w_limit=0.0, min_move=1e-9):
+        """controls() along the last schedule from real slot k0 on, dt = the schedule's slot (gpis_retime_controls): a paused
+        step has no displacement and keeps the heading of the latest moving step.  (U [m, T, 2 / 4] f64, heading0 [m, 2],
+        p0 [m, dim], clamped [m] i32)."""
+        i = self.info()
+        m, T = i["m"], int(T)
+        nu = 4 if i["dim"] == 3 else 2
+        U = np.zeros((m, max(T, 0), nu), np.float64)
+        h0, p0, cl = np.zeros((m, 2), np.float64), np.zeros((m, i["dim"]), np.float64), np.zeros(m, np.int32)
+        _check(self.L.gpis_retime_controls(self.h, T, int(k0), float(w_limit), float(min_move), _p(U, C.c_double), _p(h0, C.c_double),
+                                           _p(p0, C.c_double), _p(cl, C.c_int)), "gpis_retime_controls")
+        return U, h0, p0, cl
+
+    def retimed_check(self, obstacles, steps, clearance=None):
+        """check() along the last schedule (gpis_retime_check): the robot at the schedule's position of every real slot
+        k = 0 .. steps, the balls of `obstacles` (any set of this dim: a newer detection may be checked against an old schedule)
+        at the real slots from the schedule's t_begin.  clearance None: the set's own.  Returns check()'s dict, min_time in real
+        time from t_begin."""
+        m = self.info()["m"]
+        if clearance is None:
+            clearance = obstacles.get()["opts"]["clearance"]
+        r = dict(min_sep=np.zeros(m, np.float64), min_time=np.zeros(m, np.float64), min_obstacle=np.zeros(m, np.int32),
+                 first_hit=np.zeros(m, np.int32), collides=np.zeros(m, np.int32))
+        _check(self.L.gpis_retime_check(self.h, obstacles.h, int(steps), float(clearance), _p(r["min_sep"], C.c_double),
+                                        _p(r["min_time"], C.c_double), _p(r["min_obstacle"], C.c_int), _p(r["first_hit"], C.c_int),
+                                        _p(r["collides"], C.c_int)), "gpis_retime_check")
+        return r
+
     def body_clearance(self, footprint, field, clearance=0.0):
         """A Footprint along the waypoints of the last result on a DistanceField (gpis_body_traj_clearance): the heading of a
         waypoint is its chord's.  Returns dict(D_min [m] f64, waypoint, ball, collides [m] i32)."""
@@ -2376,6 +2448,19 @@ def timing_opts(dim, step, **opts):
     for k, v in opts.items():
         if k not in names:
             raise GpisError("unknown timing option %r" % k)
+        setattr(o, k, v)
+    return o
+
+
+def retime_opts(dim, step, **opts):
+    """gpis_retime_opts of the library's defaults for `dim` and a field of lattice step `step` (gpis_retime_default_opts) with
+    the given fields replaced."""
+    o = gpis_retime_opts()
+    _check(lib().gpis_retime_default_opts(int(dim), float(step), C.byref(o)), "gpis_retime_default_opts")
+    names = {f[0] for f in gpis_retime_opts._fields_}
+    for k, v in opts.items():
+        if k not in names:
+            raise GpisError("unknown retime option %r" % k)
         setattr(o, k, v)
     return o
 
@@ -2923,13 +3008,23 @@ class Controller:
             raise GpisError("U must be [T, %d]" % (4 if i["dim"] == 3 else 2))
         _check(self.L.gpis_mppi_set_nominal(self.h, _p(U, C.c_double)), "gpis_mppi_set_nominal")
 
-    def follow(self, traj, index, dt, t0=0.0, w_limit=0.0, min_move=1e-9):
+    def follow(self, traj, index, dt=None, t0=0.0, w_limit=0.0, min_move=1e-9, retimed=False, k0=0):
         """Replace the nominal sequence by the control sequence of trajectory `index` of a timed Trajectories from time t0 on, in
-        steps of dt (gpis_timing_follow); the sequence is computed on the device and stays there.  Returns (p0 [dim],
-        heading0 [2]): where the sequence starts and which way it faces."""
+        steps of dt (gpis_timing_follow); the sequence is computed on the device and stays there.  retimed=True: along the
+        trajectory's last schedule from real slot k0 on, in steps of the schedule's slot (gpis_retime_follow; dt and t0 are not
+        given: the controller is meant to run at dt = slot).  Returns (p0 [dim], heading0 [2]): where the sequence starts and
+        which way it faces."""
         if not self.dim:
             raise GpisError("follow before init")
         p0, h0 = np.zeros(self.dim, np.float64), np.zeros(2, np.float64)
+        if retimed:
+            if dt is not None or t0 != 0.0:
+                raise GpisError("a schedule runs in its own slots from k0 on: dt and t0 are not given")
+            _check(self.L.gpis_retime_follow(self.h, traj.h, int(index), int(k0), float(w_limit), float(min_move),
+                                             _p(h0, C.c_double), _p(p0, C.c_double)), "gpis_retime_follow")
+            return p0, h0
+        if dt is None or k0 != 0:
+            raise GpisError("follow needs dt; k0 belongs to a schedule")
         _check(self.L.gpis_timing_follow(self.h, traj.h, int(index), float(dt), float(t0), float(w_limit), float(min_move),
                                          _p(h0, C.c_double), _p(p0, C.c_double)), "gpis_timing_follow")
         return p0, h0

@@ -2127,6 +2127,70 @@ int gpis_obst_check_timing(void* traj, void* obst, double dt, int steps, double 
     try { return t.check_obst(b, dt, steps, t0, t_begin, clearance, min_sep, min_time, min_obstacle, first_hit, collides); }
     catch (...) { return GPIS_ERR_STATE; }
 }
+// ---- re-timing: schedules that wait for moving balls, and what reads them -------------------------------------------------------
+int gpis_retime_default_opts(int dim, float step, gpis_retime_opts* o) {
+    if (!o || (dim != 2 && dim != 3) || !(std::isfinite(step) && step > 0.f)) return GPIS_ERR_ARG;
+    o->slot = 0.1; o->max_pause = 63; o->clearance = (double)step; o->press_on = 0;
+    return GPIS_OK;
+}
+// Everything is checked before the previous schedule is dropped; a failure after that leaves the timing without one.
+int gpis_retime_solve(void* traj, void* obst, double t_begin, const gpis_retime_opts* opts, void* stream) {
+    if (!traj || !obst || !opts || !std::isfinite(t_begin)) return GPIS_ERR_ARG;
+    RetimeOpts o;
+    o.slot = opts->slot; o.max_pause = opts->max_pause; o.clearance = opts->clearance; o.press_on = opts->press_on;
+    if (int rc = retime_check_opts(o)) return rc;
+    Trajectories& t = *(Trajectories*)traj;
+    const Obstacles& b = *(const Obstacles*)obst;
+    if (!t.has_timing()) return GPIS_ERR_STATE;
+    if (b.device != t.device || (b.inited && b.dim != t.dim)) return GPIS_ERR_ARG;
+    DeviceScope ds(t.device);
+    try { return t.retime(b, o, t_begin, (hipStream_t)stream); } catch (...) { t.retimed = false; return GPIS_ERR_STATE; }
+}
+int gpis_retime_get(void* traj, int* status, int* arrive, int* pauses, int* own_slots, int* first_pause, int* own,
+                    gpis_retime_opts* opts, double* info) {
+    if (!traj) return GPIS_ERR_ARG;
+    Trajectories& t = *(Trajectories*)traj;
+    if (!t.has_schedule()) return GPIS_ERR_STATE;
+    DeviceScope ds(t.device);
+    if (own) {
+        GPIS_HIP(hipMemcpyAsync(own, t.d_rown, sizeof(int) * Trajectories::kOwnLen * (size_t)t.m, hipMemcpyDeviceToHost, t.own));
+        GPIS_HIP(hipStreamSynchronize(t.own));
+    }
+    int* outs[5] = {status, arrive, pauses, own_slots, first_pause};
+    for (size_t k = 0; k < (size_t)t.m; ++k)
+        for (int c = 0; c < 5; ++c)
+            if (outs[c]) outs[c][k] = t.h_rres[Trajectories::kSchedRes * k + c];
+    if (opts) { opts->slot = t.ropts.slot; opts->max_pause = t.ropts.max_pause; opts->clearance = t.ropts.clearance; opts->press_on = t.ropts.press_on; }
+    if (info) { info[0] = t.r_begin; info[1] = t.retime_ms; }
+    return GPIS_OK;
+}
+int gpis_retime_controls(void* traj, int T, int k0, double w_limit, double min_move, double* U, double* heading0, double* p0,
+                         int* clamped) {
+    if (!traj || k0 < 0 || k0 > (1 << 20)) return GPIS_ERR_ARG;
+    if (int rc = timing_check_args(1.0, T, 0.0, w_limit, min_move)) return rc;
+    Trajectories& t = *(Trajectories*)traj;
+    DeviceScope ds(t.device);
+    try { return t.retime_controls(T, k0, w_limit, min_move, U, heading0, p0, clamped); } catch (...) { return GPIS_ERR_STATE; }
+}
+int gpis_retime_follow(void* mppi, void* traj, int index, int k0, double w_limit, double min_move, double* heading0, double* p0) {
+    if (!mppi || !traj || k0 < 0 || k0 > (1 << 20)) return GPIS_ERR_ARG;
+    Controller& c = *(Controller*)mppi;
+    Trajectories& t = *(Trajectories*)traj;
+    DeviceScope ds(t.device);
+    try { return t.retime_follow(c, index, k0, w_limit, min_move, heading0, p0); } catch (...) { return GPIS_ERR_STATE; }
+}
+int gpis_retime_check(void* traj, void* obst, int steps, double clearance, double* min_sep, double* min_time, int* min_obstacle,
+                      int* first_hit, int* collides) {
+    if (!traj || !obst) return GPIS_ERR_ARG;
+    if (!std::isfinite(clearance) || steps < 1 || steps > 4096 || clearance < 0.0) return GPIS_ERR_ARG;
+    Trajectories& t = *(Trajectories*)traj;
+    const Obstacles& b = *(const Obstacles*)obst;
+    if (!t.has_schedule()) return GPIS_ERR_STATE;
+    if (b.device != t.device || (b.inited && b.dim != t.dim)) return GPIS_ERR_ARG;
+    DeviceScope ds(t.device);
+    try { return t.retime_check(b, steps, clearance, min_sep, min_time, min_obstacle, first_hit, collides); }
+    catch (...) { return GPIS_ERR_STATE; }
+}
 int gpis_obst_mppi_get(void* mppi, int* dyn_hits, double* min_sep, double* stats) {
     if (!mppi) return GPIS_ERR_ARG;
     const Controller& c = *(const Controller*)mppi;

@@ -9,6 +9,9 @@
 // the bits are those of tests/timing_ref.py.
 // With a footprint the obstacle term acts at the body's balls, the body facing along its chord, and the same
 // launch keeps the body's clearance along the result; the bits are those of tests/traj_body_ref.py.
+// On top of a timing: a schedule that plays the timed trajectory and pauses it until moving balls have passed,
+// and the control sequences, the controller's seed and the check along it; the integers and bits are those of
+// tests/retime_ref.py.
 #pragma once
 #include <cstdint>
 #include <vector>
@@ -29,6 +32,14 @@ struct TrajOpts {
 struct TimingOpts {
     float v_max = 1.f, v_min = 1.f, a_max = 1.f, d_max = 1.f, a_lat = 0.f, w_max = 0.f, v_start = 0.f, v_end = 0.f, clearance = 0.f,
           slow_dist = 0.f;
+};
+
+// the options of a re-timing
+struct RetimeOpts {
+    double slot = 0.1;       // seconds of a slot, > 0
+    int max_pause = 63;      // P: pause slots a schedule may hold, 0 .. 255
+    double clearance = 0.0;  // a cell is free while no ball's separation is below it; >= 0
+    int press_on = 0;        // 0: pauses as early as the optimum allows, 1: as late
 };
 
 struct Controller;
@@ -82,6 +93,20 @@ struct Trajectories {
     int* d_bresi = nullptr;                          // [m][3] waypoint, ball, collides
     size_t cap_bres = 0;
 
+    // the schedule of the last re-timing, dropped wherever the timing is; the layout follows the current m alone
+    static constexpr int kMaxOwnSlots = 1024;        // own slots a trajectory may last (the position table's rows - 1)
+    static constexpr int kMaxPause = 255;            // pause slots (the workgroup's lanes - 1)
+    static constexpr int kOwnLen = kMaxOwnSlots + kMaxPause + 1;   // real slots of the longest schedule
+    static constexpr int kSchedRes = 5;              // status, arrive, pauses, own_slots, first_pause
+    int* d_rres = nullptr;                           // [m][kSchedRes]
+    int* d_rown = nullptr;                           // [m][kOwnLen] the own slot of every real slot
+    size_t cap_rt = 0;
+    std::vector<int> h_rres;                         // d_rres' host copy
+    RetimeOpts ropts;                                // the options and the start of the last re-timing
+    double r_begin = 0.0;
+    bool retimed = false;
+    double retime_ms = 0.0;
+
     int m = 0, N = 0, dim = 0;
     bool has_input = false, valid = false, timed = false;
     bool body_valid = false;                         // the last result came with a footprint: d_bresd, d_bresi hold its body result
@@ -121,6 +146,24 @@ struct Trajectories {
     // own stream
     int check_body(const DistanceField& df, const BodyArgs& bd, double clearance, double* D_min, int* waypoint, int* ball, int* collides);
 
+    // Re-timing (the contract: tests/retime_ref.py).  Own time runs in slots: A = the least a with
+    // (double)a * slot >= t_{N-1}, pos_a the timed position at (double)a * slot.  A schedule plays the timed trajectory and
+    // pauses it: cell (a, p) -- own slot a after p pauses, real slot a + p -- is left by a play step if no ball's separation
+    // from the interval (pos_a, pos_{a+1}) during real slot a + p is below the clearance, by a pause step if none from
+    // (pos_a, pos_a) is; the separation is check_obst's expression.  The schedule that arrives first within max_pause pauses is
+    // kept per trajectory: status (0 clear as timed, 1 with pauses, 2 no timing, 3 none within max_pause, 4 more than
+    // kMaxOwnSlots own slots), arrive, pauses, own_slots, first_pause and own[real slot].  At worst A (P + 1) 2 n separations
+    // per trajectory.  Arguments are checked by the caller; s: nullptr for the own stream; synchronises it
+    int retime(const Obstacles& ob, const RetimeOpts& o, double t_begin, hipStream_t s);
+    bool has_schedule() const { return has_timing() && retimed; }
+    // controls() along the schedule from real slot k0 on, dt = the slot: a paused step has no displacement
+    int retime_controls(int T, int k0, double w_limit, double min_move, double* U, double* heading0, double* p0, int* clamped);
+    // follow() along the schedule of trajectory `index`
+    int retime_follow(Controller& c, int index, int k0, double w_limit, double min_move, double* heading0, double* p0);
+    // check_obst() along the schedule from real slot 0 on, the balls taken at the real slots from the schedule's t_begin
+    int retime_check(const Obstacles& ob, int steps, double clearance, double* min_sep, double* min_time, int* min_obstacle,
+                     int* first_hit, int* collides);
+
 private:
     int ensure(int m, int N, int dim);
     int from_packed(int dev, long long npaths, long long npoints, int dim, const long long* off, const float* pts,
@@ -133,5 +176,7 @@ int traj_check_opts(const TrajOpts& o);
 int timing_check_opts(const TimingOpts& o);
 // GPIS_ERR_ARG unless dt > 0, 1 <= T <= 256, t0 >= 0, w_limit >= 0, min_move >= 0, all finite
 int timing_check_args(double dt, int T, double t0, double w_limit, double min_move);
+// GPIS_ERR_ARG unless slot > 0 and clearance >= 0, both finite, 0 <= max_pause <= 255, press_on 0 or 1
+int retime_check_opts(const RetimeOpts& o);
 
 }  // namespace gpis

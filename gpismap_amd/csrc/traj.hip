@@ -564,8 +564,10 @@ __global__ void __launch_bounds__(kBlock) traj_time_kernel(const float* __restri
 }
 
 // The timed position at tau: the last waypoint from the duration on, else the segment by bisection (the largest i <= N - 2 with
-// t_i <= tau) and the distance along it under constant acceleration.
-template <int DIM>
+// t_i <= tau) and the distance along it under constant acceleration.  USER: 0 for the timing's and the check's kernels, 1 for
+// those that read or make a schedule -- the same statements, instantiated apart: a function of this file has
+// internal linkage, so what the compiler learns from one kernel's arguments would else reach the code of the others.
+template <int DIM, int USER = 0>
 __device__ __forceinline__ void traj_position(const float* __restrict__ x, const float* __restrict__ v, const float* st, int N,
                                               double tau, double* p) {
     if (tau >= (double)st[N - 1]) {
@@ -595,6 +597,20 @@ __device__ __forceinline__ void traj_position(const float* __restrict__ x, const
     for (int a = 0; a < DIM; ++a) p[a] = x0[a] + w * d[a];
 }
 
+// A schedule of gpis_retime_solve as its readers see it: res[tr][kSchedRes] = status, arrive, pauses, own_slots,
+// first_pause; own[tr][kOwnLen] the own slot of every real slot (own_slots from arrive on); k0: the real slot a sequence starts at.
+constexpr int kSchedRes = Trajectories::kSchedRes, kOwnLen = Trajectories::kOwnLen, kMaxOwnSlots = Trajectories::kMaxOwnSlots;
+
+struct TrajSched {
+    const int* res;
+    const int* own;
+    int k0;
+};
+
+__device__ __forceinline__ int sched_own(const TrajSched& sc, int tr, int k) {
+    return k < kOwnLen ? sc.own[(size_t)tr * kOwnLen + k] : sc.res[(size_t)tr * kSchedRes + 3];
+}
+
 // One workgroup per trajectory (first + blockIdx.x), blockDim.x = 64 ceil(T / 64), thread k = step k: its two timed positions,
 // the displacement, the heading of the latest moving step by an integer max-scan, the controls.  U[blockIdx.x][T][nu],
 // hp[blockIdx.x][5] = heading0, p_0, clamped[blockIdx.x].  Double, nothing contracted.
@@ -604,85 +620,21 @@ __global__ void __launch_bounds__(kBlock) traj_controls_kernel(const float* __re
                                                                int T, int first, double dt, double t0, double w_limit,
                                                                double min_move, double* __restrict__ U, double* __restrict__ hp,
                                                                int* __restrict__ clamped) {
-    constexpr int NU = DIM == 3 ? 4 : 2;
-    __shared__ float st[kTree];
-    __shared__ double sh[2][kTree];
-    __shared__ int swi[2 * (kBlock / 64)];
-    __shared__ int sidx[kTree];
-    const int tr = first + blockIdx.x, k = threadIdx.x, nthr = blockDim.x;
-    const size_t base = (size_t)tr * N;
-    double* Uo = U + (size_t)blockIdx.x * T * NU;
-    double* hpo = hp + (size_t)blockIdx.x * 5;
+#define TRAJ_SCHED 0
+#include "traj_controls_body.inc"
+#undef TRAJ_SCHED
+}
 
-    if (tint[(size_t)tr * 9] != 0) {                     // not timed: stand still
-        if (k < T) {
-#pragma unroll
-            for (int u = 0; u < NU; ++u) Uo[(size_t)k * NU + u] = 0.0;
-        }
-        if (k == 0) {
-            hpo[0] = 1.0; hpo[1] = 0.0;
-#pragma unroll
-            for (int a = 0; a < DIM; ++a) hpo[2 + a] = (double)x[base * DIM + a];
-            if (DIM == 2) hpo[4] = 0.0;
-            clamped[blockIdx.x] = 0;
-        }
-        return;
-    }
-    for (int i = k; i < N; i += nthr) st[i] = tt[base + i];
-    __syncthreads();
-
-    double p[DIM], D[DIM];
-    double n = 0.0;
-    bool mov = false;
-#pragma unroll
-    for (int a = 0; a < DIM; ++a) { p[a] = 0.0; D[a] = 0.0; }
-    if (k < T) {
-        double q[DIM];
-        traj_position<DIM>(x + base * DIM, v + base, st, N, t0 + (double)k * dt, p);
-        traj_position<DIM>(x + base * DIM, v + base, st, N, t0 + (double)(k + 1) * dt, q);
-#pragma unroll
-        for (int a = 0; a < DIM; ++a) D[a] = q[a] - p[a];
-        n = sqrt(D[0] * D[0] + D[1] * D[1]);
-        mov = n > min_move;
-    }
-    if (mov) { sh[0][k] = D[0] / n; sh[1][k] = D[1] / n; }
-    int fst;
-    int last = block_latest_flag(mov, swi, nthr, &fst);  // (its barriers publish sh)
-    if (last < 0) last = fst;
-    sidx[k] = last;
-    __syncthreads();
-    int cl = 0;
-    if (k < T) {
-        const int nxt = k + 1 < T ? sidx[k + 1] : last;  // h_T = h_{T-1}
-        double c = 1.0, s = 0.0, c1 = 1.0, s1 = 0.0;
-        if (last >= 0) { c = sh[0][last]; s = sh[1][last]; }
-        if (nxt >= 0) { c1 = sh[0][nxt]; s1 = sh[1][nxt]; }
-        double* u = Uo + (size_t)k * NU;
-        u[0] = (c * D[0] + s * D[1]) / dt;
-        if (DIM == 3) {
-            u[1] = ((-s) * D[0] + c * D[1]) / dt;
-            u[2] = D[DIM - 1] / dt;
-        }
-        const double num = c * s1 - s * c1, den = 1.0 + (c * c1 + s * s1);
-        double w;
-        if (den <= 0.0) {
-            w = w_limit > 0.0 ? (num >= 0.0 ? w_limit : -w_limit) : 0.0;
-            cl = 1;
-        } else {
-            w = (num / den) / (0.5 * dt);
-            if (w_limit > 0.0 && w > w_limit) { w = w_limit; cl = 1; }
-            else if (w_limit > 0.0 && w < -w_limit) { w = -w_limit; cl = 1; }
-        }
-        u[NU - 1] = w;
-        if (k == 0) {
-            hpo[0] = c; hpo[1] = s;
-#pragma unroll
-            for (int a = 0; a < DIM; ++a) hpo[2 + a] = p[a];
-            if (DIM == 2) hpo[4] = 0.0;
-        }
-    }
-    const int total = block_reduce(cl, OpAdd(), swi, nthr, 0);
-    if (k == 0) clamped[blockIdx.x] = total;
+// the same along a schedule (the contract: tests/retime_ref.py): dt is the schedule's slot
+template <int DIM>
+__global__ void __launch_bounds__(kBlock) traj_retime_controls_kernel(const float* __restrict__ x, const float* __restrict__ v,
+                                                                      const float* __restrict__ tt, const int* __restrict__ tint, int N,
+                                                                      int T, int first, double dt, double w_limit, double min_move,
+                                                                      double* __restrict__ U, double* __restrict__ hp,
+                                                                      int* __restrict__ clamped, TrajSched sc) {
+#define TRAJ_SCHED 1
+#include "traj_controls_body.inc"
+#undef TRAJ_SCHED
 }
 
 // A timed trajectory against a set of moving balls (obst.h; the contract: tests/obst_ref.py).  One workgroup of
@@ -701,90 +653,190 @@ __global__ void __launch_bounds__(kBlock) traj_obst_check_kernel(const float* __
                                                                  int steps, double dt, double t0, double TB, double clearance,
                                                                  const double* __restrict__ tab, int n, double* __restrict__ out_d,
                                                                  int* __restrict__ out_i) {
+#define TRAJ_SCHED 0
+#include "traj_check_body.inc"
+#undef TRAJ_SCHED
+}
+
+// the same along a schedule: dt is the schedule's slot, min_time is in real time
+template <int DIM>
+__global__ void __launch_bounds__(kBlock) traj_retime_check_kernel(const float* __restrict__ x, const float* __restrict__ v,
+                                                                   const float* __restrict__ tt, const int* __restrict__ tint, int N,
+                                                                   int steps, double dt, double TB, double clearance,
+                                                                   const double* __restrict__ tab, int n, double* __restrict__ out_d,
+                                                                   int* __restrict__ out_i, TrajSched sc) {
+    constexpr double t0 = 0.0;
+#define TRAJ_SCHED 1
+#include "traj_check_body.inc"
+#undef TRAJ_SCHED
+}
+
+// ---- re-timing: when to move along a timed trajectory so that moving balls pass ----------------------------------
+// The contract: tests/retime_ref.py.  One workgroup of kBlock threads per trajectory; lane = pause count p, rows = own slots a
+// taken in order, the real slot of cell (a, p) is a + p.  pos_a = traj_position((double)a * slot), a = 0 .. A, go to LDS once
+// (<= 1025 x DIM doubles).  A row: the lanes whose cell can still be reached evaluate its pause flag (no ball's separation of
+// (pos_a, 0) at slot a + p below the clearance; the table's index is the same in every lane: scalar loads); the wavefronts'
+// ballots of the seeds (reached from row a - 1 by a free play cell) and of the pause flags meet in LDS, and after one barrier
+// every lane floods the seeds along the open pause links, a wavefront's 64 cells by shifts of one word, the carry into the next
+// wavefront a bit; then only the reached lanes evaluate the play flag that seeds row a + 1.  Reach bits live in registers from
+// row to row; what the walk back needs goes to LDS, one bit per cell (1025 x 256 bits = 32.8 KB): with press_on 0 "reached by a
+// play step", with press_on 1 "reached by a pause step".  The walk back is lane 0's.  Integers and flags: nothing depends on an
+// order.  At worst A (P + 1) 2 n separations per trajectory.
+// res[tr][kSchedRes] = status, arrive, pauses, own_slots, first_pause; own[tr][kOwnLen].
+
+// The separation of one interval from one ball for gpis_retime_solve's cells: the expression of the check's inner loop
+// (traj_check_body.inc), operation for operation (that loop keeps its own text, so that the plain check kernels compile to what they were; the
+// certificate of tests/test_gpu_retime.py holds the two together).  The robot goes from p0 by dp while the ball of `row` goes
+// from its place at the elapsed time e0 to that at e1; *s_out = where in the interval the two are closest.
+template <int DIM>
+__device__ __forceinline__ double traj_ball_sep(const double* p0, const double* dp, double e0, double e1,
+                                                const double* __restrict__ row, double* s_out) {
+    double A[DIM], B[DIM], bb = 0.0, ab = 0.0;
+#pragma unroll
+    for (int a = 0; a < DIM; ++a) {
+        const double o0 = row[a] + row[3 + a] * e0, o1 = row[a] + row[3 + a] * e1;
+        A[a] = p0[a] - o0;
+        B[a] = dp[a] - (o1 - o0);
+        bb = a ? bb + B[a] * B[a] : B[a] * B[a];
+        ab = a ? ab + A[a] * B[a] : A[a] * B[a];
+    }
+    double s = 0.0;
+    if (bb > 0.0) {
+        s = (-ab) / bb;
+        s = s > 0.0 ? s : 0.0;
+        s = s < 1.0 ? s : 1.0;
+    }
+    double s2 = 0.0;
+#pragma unroll
+    for (int a = 0; a < DIM; ++a) {
+        const double q = A[a] + s * B[a];
+        s2 = a ? s2 + q * q : q * q;
+    }
+    *s_out = s;
+    return sqrt(s2) - row[6];
+}
+
+template <int DIM>
+__device__ __forceinline__ bool retime_cell_free(const double* p0, const double* dp, double e0, double e1,
+                                                 const double* __restrict__ tab, int n, double clearance) {
+    bool ok = true;
+    const double* __restrict__ row = tab;
+    for (int i = 0; i < n; ++i, row += Obstacles::kRow) {
+        double s;
+        const double sep = traj_ball_sep<DIM>(p0, dp, e0, e1, row, &s);
+        ok = ok && !(sep < clearance);                   // (a NaN separation is not below the clearance, as in the check)
+    }
+    return ok;
+}
+
+template <int DIM>
+__global__ void __launch_bounds__(kBlock) traj_retime_kernel(const float* __restrict__ x, const float* __restrict__ v,
+                                                             const float* __restrict__ tt, const int* __restrict__ tint, int N,
+                                                             double slot, int P, double clearance, int press_on, double TB,
+                                                             const double* __restrict__ tab, int n, int* __restrict__ res,
+                                                             int* __restrict__ own) {
+    typedef unsigned long long u64;
     __shared__ float st[kTree];
-    __shared__ double sp[kChunk + 1][DIM];
-    __shared__ double shd[kBlock / 64];
-    __shared__ unsigned long long shk[kBlock / 64];
-    __shared__ int shi[kBlock / 64];
-    const int tr = blockIdx.x, tid = threadIdx.x;
+    __shared__ double sp[kMaxOwnSlots + 1][DIM];
+    __shared__ u64 spred[kMaxOwnSlots + 1][kBlock / 64];
+    __shared__ u64 smask[2][2][kBlock / 64];             // [row parity][seeds, pause flags][wavefront]
+    const int tr = blockIdx.x, p = threadIdx.x, lane = p & 63, w = p >> 6;
     const size_t base = (size_t)tr * N;
-    if (tint[(size_t)tr * 9] != 0 || n == 0) {
-        if (tid == 0) {
-            const bool timed = tint[(size_t)tr * 9] == 0;
-            out_d[(size_t)tr * 2] = timed ? (double)INFINITY : (double)NAN; out_d[(size_t)tr * 2 + 1] = (double)NAN;
-            out_i[(size_t)tr * 3] = -1; out_i[(size_t)tr * 3 + 1] = -1; out_i[(size_t)tr * 3 + 2] = 0;
+    int* ro = res + (size_t)tr * kSchedRes;
+    int* oo = own + (size_t)tr * kOwnLen;
+
+    int A = -1, status = 2;
+    if (tint[(size_t)tr * 9] == 0) {                     // (uniform: one trajectory per workgroup)
+        for (int i = p; i < N; i += kBlock) st[i] = tt[base + i];
+        const double dur = (double)tt[base + N - 1];
+        status = 4;
+        if (dur / slot <= (double)(kMaxOwnSlots + 2)) {
+            int a = (int)(dur / slot);
+            while (a > 0 && (double)(a - 1) * slot >= dur) --a;
+            while ((double)a * slot < dur) ++a;
+            if (a <= kMaxOwnSlots) { A = a; status = 0; }
         }
+    }
+    if (status != 0) {                                   // no timing, or too long for this slot
+        for (int k = p; k < kOwnLen; k += kBlock) oo[k] = -1;
+        if (p == 0) { ro[0] = status; ro[1] = -1; ro[2] = -1; ro[3] = -1; ro[4] = -1; }
         return;
     }
-    for (int i = tid; i < N; i += kBlock) st[i] = tt[base + i];
-    double best = INFINITY, best_s = 0.0;
-    int best_k = -1, best_i = -1, hit = 0x7fffffff;
-    for (int k0 = 0; k0 < steps; k0 += kChunk) {
-        const int cnt = min(kChunk, steps - k0);
-        __syncthreads();                                 // (st is written; sp of the previous chunk is read)
-        for (int j = tid; j <= cnt; j += kBlock) {
-            double p[DIM];
-            traj_position<DIM>(x + base * DIM, v + base, st, N, t0 + (double)(k0 + j) * dt, p);
+    if (n == 0) {                                        // nothing to wait for: the identity
+        for (int k = p; k < kOwnLen; k += kBlock) oo[k] = min(k, A);
+        if (p == 0) { ro[0] = 0; ro[1] = A; ro[2] = 0; ro[3] = A; ro[4] = -1; }
+        return;
+    }
+    __syncthreads();                                     // (st is written)
+    for (int j = p; j <= A; j += kBlock) {
+        double q[DIM];
+        traj_position<DIM, 1>(x + base * DIM, v + base, st, N, (double)j * slot, q);
 #pragma unroll
-            for (int a = 0; a < DIM; ++a) sp[j][a] = p[a];
-        }
-        __syncthreads();
-        for (int j = tid; j < cnt; j += kBlock) {
-            const int k = k0 + j;
-            const double e0 = TB + (t0 + (double)k * dt), e1 = TB + (t0 + (double)(k + 1) * dt);
-            double p0[DIM], dp[DIM];
+        for (int a = 0; a < DIM; ++a) sp[j][a] = q[a];
+    }
+    __syncthreads();
+
+    bool seed = p == 0;
+    int lo = 0, pstar = -1;                              // lo: the least reached p of the row before
+    for (int a = 0; a <= A; ++a) {
+        double pa[DIM], dp[DIM];
 #pragma unroll
-            for (int a = 0; a < DIM; ++a) { p0[a] = sp[j][a]; dp[a] = sp[j + 1][a] - p0[a]; }
-            const double* __restrict__ row = tab;
-            for (int i = 0; i < n; ++i, row += Obstacles::kRow) {
-                double A[DIM], B[DIM], bb = 0.0, ab = 0.0;
+        for (int c = 0; c < DIM; ++c) { pa[c] = sp[a][c]; dp[c] = 0.0; }
+        const double e0 = TB + (double)(a + p) * slot, e1 = TB + (double)(a + p + 1) * slot;
+        bool f = false;
+        // (row A needs no pause: a cell reached there by one has a reached cell of a smaller p before it)
+        if (a < A && p < P && p >= lo) f = retime_cell_free<DIM>(pa, dp, e0, e1, tab, n, clearance);
+        const u64 S = __ballot(seed), F = __ballot(f);
+        if (lane == 0) { smask[a & 1][0][w] = S; smask[a & 1][1][w] = F; }
+        __syncthreads();                                 // (the other parity is free: every lane has passed the barrier after its reads)
+        u64 cin = 0, mine = 0, any = 0;
+        int first = -1;
 #pragma unroll
-                for (int a = 0; a < DIM; ++a) {
-                    const double o0 = row[a] + row[3 + a] * e0, o1 = row[a] + row[3 + a] * e1;
-                    A[a] = p0[a] - o0;
-                    B[a] = dp[a] - (o1 - o0);
-                    bb = a ? bb + B[a] * B[a] : B[a] * B[a];
-                    ab = a ? ab + A[a] * B[a] : A[a] * B[a];
-                }
-                double s = 0.0;
-                if (bb > 0.0) {
-                    s = (-ab) / bb;
-                    s = s > 0.0 ? s : 0.0;
-                    s = s < 1.0 ? s : 1.0;
-                }
-                double s2 = 0.0;
+        for (int q = 0; q < kBlock / 64; ++q) {
+            const u64 sq = smask[a & 1][0][q], fq = smask[a & 1][1][q];
+            u64 r = sq | cin, open = fq;
 #pragma unroll
-                for (int a = 0; a < DIM; ++a) {
-                    const double q = A[a] + s * B[a];
-                    s2 = a ? s2 + q * q : q * q;
-                }
-                const double sep = sqrt(s2) - row[6];
-                if (sep < best) { best = sep; best_s = s; best_k = k; best_i = i; }
-                if (sep < clearance && k < hit) hit = k;
+            for (int d = 1; d < 64; d <<= 1) {           // cells reached within 2 d - 1 pauses; open: d links in a row from here
+                r |= (r & open) << d;
+                open &= open >> d;
             }
+            const u64 by_pause = ((r & fq) << 1) | cin;
+            if (q == w) {
+                mine = r;
+                if (lane == 0) spred[a][w] = press_on ? by_pause : sq;
+            }
+            if (first < 0 && r) first = q * 64 + (__ffsll(r) - 1);
+            any |= r;
+            cin = (r & fq) >> 63;
         }
+        if (!any) break;                                 // (uniform) no cell of this row is reached: none of a later one
+        lo = first;
+        if (a == A) { pstar = first; break; }
+#pragma unroll
+        for (int c = 0; c < DIM; ++c) dp[c] = sp[a + 1][c] - pa[c];
+        seed = ((mine >> lane) & 1) ? retime_cell_free<DIM>(pa, dp, e0, e1, tab, n, clearance) : false;
     }
-    const double bmin = block_reduce(best, OpMin(), shd, kBlock, (double)INFINITY);
-    if (tid == 0) shd[0] = bmin;
-    __syncthreads();
-    const double least = shd[0];
-    unsigned long long key = best_k >= 0 && best == least ? ((unsigned long long)best_k << 8) | (unsigned long long)best_i : ~0ull;
-    const unsigned long long kmin = block_reduce(key, OpMin(), shk, kBlock, ~0ull);
-    if (tid == 0) shk[0] = kmin;
-    __syncthreads();
-    const unsigned long long win = shk[0];
-    const int fh = block_reduce(hit, OpMin(), shi, kBlock, 0x7fffffff);
-    if (tid == 0) {
-        out_i[(size_t)tr * 3 + 1] = fh == 0x7fffffff ? -1 : fh;
-        out_i[(size_t)tr * 3 + 2] = fh == 0x7fffffff ? 0 : 1;
-        if (win == ~0ull) {                              // no separation was a number
-            out_d[(size_t)tr * 2] = (double)INFINITY; out_d[(size_t)tr * 2 + 1] = (double)NAN; out_i[(size_t)tr * 3] = -1;
+    if (pstar < 0) {                                     // no schedule within P pauses
+        for (int k = p; k < kOwnLen; k += kBlock) oo[k] = -1;
+        if (p == 0) { ro[0] = 3; ro[1] = -1; ro[2] = -1; ro[3] = A; ro[4] = -1; }
+        return;
+    }
+    const int arrive = A + pstar;
+    for (int k = arrive + 1 + p; k < kOwnLen; k += kBlock) oo[k] = A;
+    __syncthreads();                                     // (spred is written)
+    if (p == 0) {
+        int a = A, pp = pstar, fp = -1;
+        oo[arrive] = A;
+        while (a > 0 || pp > 0) {
+            const bool bit = (spred[a][pp >> 6] >> (pp & 63)) & 1;
+            bool play = press_on ? !bit : bit;
+            if (a == 0) play = false;                    // (what the bits say there anyway; the walk ends whatever they hold)
+            else if (pp == 0) play = true;
+            if (play) --a;
+            else { --pp; fp = a + pp; }
+            oo[a + pp] = a;
         }
-    }
-    if (key == win && win != ~0ull) {
-        out_d[(size_t)tr * 2] = best;
-        out_d[(size_t)tr * 2 + 1] = (t0 + (double)best_k * dt) + best_s * dt;
-        out_i[(size_t)tr * 3] = best_i;
+        ro[0] = pstar > 0 ? 1 : 0; ro[1] = arrive; ro[2] = pstar; ro[3] = A; ro[4] = fp;
     }
 }
 
@@ -891,7 +943,7 @@ int Trajectories::bind(int dev) {
         for (void* p : {(void*)d_in, (void*)d_x, (void*)d_instat, (void*)d_fres, (void*)d_ires, (void*)d_arc, (void*)d_tv, (void*)d_tt,
                         (void*)d_lim, (void*)d_tsum, (void*)d_tint, (void*)d_cu, (void*)d_chp, (void*)d_cclamp, (void*)d_follow,
                         (void*)d_chkd, (void*)d_chki, (void*)d_bodyd, (void*)d_bodyi, (void*)d_bresd,
-                        (void*)d_bresi})
+                        (void*)d_bresi, (void*)d_rres, (void*)d_rown})
             (void)hipFree(p);
         if (own) (void)hipStreamDestroy(own);
     }
@@ -900,8 +952,9 @@ int Trajectories::bind(int dev) {
     d_chkd = nullptr; d_chki = nullptr; cap_chk = 0;
     d_bodyd = nullptr; d_bodyi = nullptr; cap_body = 0;
     d_bresd = nullptr; d_bresi = nullptr; cap_bres = 0;
+    d_rres = nullptr; d_rown = nullptr; cap_rt = 0;
     cap_x = cap_m = cap_arc = cap_tn = cap_tm = cap_cu = cap_cm = 0;
-    has_input = valid = timed = body_valid = false;
+    has_input = valid = timed = body_valid = retimed = false;
     m = N = dim = 0;
     device = dev;
     if (dev < 0) return GPIS_OK;
@@ -940,7 +993,7 @@ int Trajectories::ensure(int mm, int NN, int dd) {
 
 int Trajectories::from_packed(int dev, long long npaths, long long npoints, int dd, const long long* off, const float* pts,
                               const unsigned char* pstat, int NN, bool zero_w) {
-    has_input = valid = timed = body_valid = false;
+    has_input = valid = timed = body_valid = retimed = false;
     if (int rc = bind(dev)) return rc;
     const int mm = (int)npaths;
     if (int rc = ensure(mm, NN, dd)) return rc;
@@ -976,7 +1029,7 @@ int Trajectories::from_pose_paths(const PosePlanner& p, int NN) {
 int Trajectories::set(const float* x, int mm, int NN, int dd) {
     if (!x || mm < 1 || NN < kMinN || NN > kMaxN || (dd != 2 && dd != 3)) return GPIS_ERR_ARG;
     if (mm > kMaxTraj) return GPIS_ERR_LIMIT;
-    has_input = valid = timed = body_valid = false;
+    has_input = valid = timed = body_valid = retimed = false;
     if (int rc = ensure(mm, NN, dd)) return rc;
     const size_t per = (size_t)NN * dd;
     std::vector<unsigned char> st((size_t)mm, 0);
@@ -996,7 +1049,7 @@ int Trajectories::optimize(const DistanceField& df, const TrajOpts& o, hipStream
     if (!df.valid || !has_input) return GPIS_ERR_STATE;
     if (df.dim != dim) return GPIS_ERR_ARG;
     const auto t0 = std::chrono::steady_clock::now();
-    valid = timed = body_valid = false;
+    valid = timed = body_valid = retimed = false;
     if (int rc = bind(df.device)) return rc;
     if (bd && (size_t)m > cap_bres) {
         (void)hipFree(d_bresd); (void)hipFree(d_bresi);
@@ -1067,7 +1120,7 @@ int Trajectories::time(const DistanceField* df, const TimingOpts& o, hipStream_t
     }
     const auto t0 = std::chrono::steady_clock::now();
     if (!s) s = df ? df->own : own;
-    timed = false;
+    timed = retimed = false;
     // (the layout follows the current m and N; the capacities only ever say how much is allocated)
     const size_t mn = (size_t)m * N;
     if (mn > cap_tn) {
@@ -1227,6 +1280,137 @@ int Trajectories::check_body(const DistanceField& df, const BodyArgs& bd, double
         if (D_min) D_min[r] = hd[r];
         if (waypoint) waypoint[r] = hi[3 * r];
         if (ball) ball[r] = hi[3 * r + 1];
+        if (collides) collides[r] = hi[3 * r + 2];
+    }
+    return GPIS_OK;
+}
+
+// ---- re-timing ---------------------------------------------------------------------------------------------------
+int retime_check_opts(const RetimeOpts& o) {
+    if (!std::isfinite(o.slot) || !(o.slot > 0.0) || !std::isfinite(o.clearance) || o.clearance < 0.0) return GPIS_ERR_ARG;
+    if (o.max_pause < 0 || o.max_pause > Trajectories::kMaxPause || (o.press_on != 0 && o.press_on != 1)) return GPIS_ERR_ARG;
+    return GPIS_OK;
+}
+
+int Trajectories::retime(const Obstacles& ob, const RetimeOpts& o, double t_begin, hipStream_t s) {
+    if (!has_timing()) return GPIS_ERR_STATE;
+    const auto c0 = std::chrono::steady_clock::now();
+    if (!s) s = own;
+    retimed = false;
+    if ((size_t)m > cap_rt) {
+        (void)hipFree(d_rres); (void)hipFree(d_rown);
+        d_rres = nullptr; d_rown = nullptr; cap_rt = 0;
+        GPIS_HIP(hipMalloc((void**)&d_rres, sizeof(int) * kSchedRes * (size_t)m));
+        GPIS_HIP(hipMalloc((void**)&d_rown, sizeof(int) * kOwnLen * (size_t)m));
+        cap_rt = (size_t)m;
+    }
+    const double TB = t_begin - ob.epoch;
+    if (dim == 2)
+        hipLaunchKernelGGL(traj_retime_kernel<2>, dim3((unsigned)m), dim3(kBlock), 0, s, d_x, d_tv, d_tt, d_tint, N, o.slot, o.max_pause,
+                           o.clearance, o.press_on, TB, (const double*)ob.d_tab, ob.n, d_rres, d_rown);
+    else
+        hipLaunchKernelGGL(traj_retime_kernel<3>, dim3((unsigned)m), dim3(kBlock), 0, s, d_x, d_tv, d_tt, d_tint, N, o.slot, o.max_pause,
+                           o.clearance, o.press_on, TB, (const double*)ob.d_tab, ob.n, d_rres, d_rown);
+    GPIS_HIP(hipGetLastError());
+    h_rres.resize(kSchedRes * (size_t)m);
+    GPIS_HIP(hipMemcpyAsync(h_rres.data(), d_rres, sizeof(int) * h_rres.size(), hipMemcpyDeviceToHost, s));
+    GPIS_HIP(hipStreamSynchronize(s));
+    ropts = o;
+    r_begin = t_begin;
+    retime_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - c0).count();
+    retimed = true;
+    return GPIS_OK;
+}
+
+int Trajectories::retime_controls(int T, int k0, double w_limit, double min_move, double* U, double* heading0, double* p0, int* clamped) {
+    if (!has_schedule()) return GPIS_ERR_STATE;
+    const int nu = dim == 3 ? 4 : 2;
+    if (int rc = grow(d_cu, cap_cu, (size_t)m * T * nu)) return rc;
+    if ((size_t)m > cap_cm) {
+        (void)hipFree(d_chp); (void)hipFree(d_cclamp);
+        d_chp = nullptr; d_cclamp = nullptr; cap_cm = 0;
+        GPIS_HIP(hipMalloc((void**)&d_chp, sizeof(double) * 5 * (size_t)m));
+        GPIS_HIP(hipMalloc((void**)&d_cclamp, sizeof(int) * (size_t)m));
+        cap_cm = (size_t)m;
+    }
+    const int threads = 64 * ((T + 63) / 64);
+    const TrajSched sc{d_rres, d_rown, k0};
+    if (dim == 2)
+        hipLaunchKernelGGL(traj_retime_controls_kernel<2>, dim3((unsigned)m), dim3(threads), 0, own, d_x, d_tv, d_tt, d_tint, N, T, 0,
+                           ropts.slot, w_limit, min_move, d_cu, d_chp, d_cclamp, sc);
+    else
+        hipLaunchKernelGGL(traj_retime_controls_kernel<3>, dim3((unsigned)m), dim3(threads), 0, own, d_x, d_tv, d_tt, d_tint, N, T, 0,
+                           ropts.slot, w_limit, min_move, d_cu, d_chp, d_cclamp, sc);
+    GPIS_HIP(hipGetLastError());
+    std::vector<double> hp;
+    if (U) GPIS_HIP(hipMemcpyAsync(U, d_cu, sizeof(double) * (size_t)m * T * nu, hipMemcpyDeviceToHost, own));
+    if (heading0 || p0) {
+        hp.resize(5 * (size_t)m);
+        GPIS_HIP(hipMemcpyAsync(hp.data(), d_chp, sizeof(double) * hp.size(), hipMemcpyDeviceToHost, own));
+    }
+    if (clamped) GPIS_HIP(hipMemcpyAsync(clamped, d_cclamp, sizeof(int) * (size_t)m, hipMemcpyDeviceToHost, own));
+    GPIS_HIP(hipStreamSynchronize(own));
+    for (size_t r = 0; r < (size_t)m && !hp.empty(); ++r) {
+        if (heading0) { heading0[2 * r] = hp[5 * r]; heading0[2 * r + 1] = hp[5 * r + 1]; }
+        if (p0) for (int a = 0; a < dim; ++a) p0[r * dim + a] = hp[5 * r + 2 + a];
+    }
+    return GPIS_OK;
+}
+
+int Trajectories::retime_follow(Controller& c, int index, int k0, double w_limit, double min_move, double* heading0, double* p0) {
+    if (!c.inited || !has_schedule()) return GPIS_ERR_STATE;
+    if (int rc = timing_check_args(ropts.slot, c.T, 0.0, w_limit, min_move)) return rc;
+    if (c.dim != dim || c.device != device || index < 0 || index >= m) return GPIS_ERR_ARG;
+    if (h_tint[9 * (size_t)index] != 0 || h_rres[kSchedRes * (size_t)index] >= 2) return GPIS_ERR_STATE;
+    if (!d_follow) GPIS_HIP(hipMalloc((void**)&d_follow, sizeof(double) * 8));
+    // (the own stream's work is finished: retime() synchronised; the controller's stream orders the write with its steps)
+    const int threads = 64 * ((c.T + 63) / 64);
+    int* d_cl = (int*)(d_follow + 6);
+    const TrajSched sc{d_rres, d_rown, k0};
+    if (dim == 2)
+        hipLaunchKernelGGL(traj_retime_controls_kernel<2>, dim3(1), dim3(threads), 0, c.own, d_x, d_tv, d_tt, d_tint, N, c.T, index,
+                           ropts.slot, w_limit, min_move, c.d_U[c.cur], d_follow, d_cl, sc);
+    else
+        hipLaunchKernelGGL(traj_retime_controls_kernel<3>, dim3(1), dim3(threads), 0, c.own, d_x, d_tv, d_tt, d_tint, N, c.T, index,
+                           ropts.slot, w_limit, min_move, c.d_U[c.cur], d_follow, d_cl, sc);
+    GPIS_HIP(hipGetLastError());
+    double hp[5];
+    GPIS_HIP(hipMemcpyAsync(hp, d_follow, sizeof(hp), hipMemcpyDeviceToHost, c.own));
+    GPIS_HIP(hipStreamSynchronize(c.own));
+    if (heading0) { heading0[0] = hp[0]; heading0[1] = hp[1]; }
+    if (p0) for (int a = 0; a < dim; ++a) p0[a] = hp[2 + a];
+    return GPIS_OK;
+}
+
+int Trajectories::retime_check(const Obstacles& ob, int steps, double clearance, double* min_sep, double* min_time, int* min_obstacle,
+                               int* first_hit, int* collides) {
+    if (!has_schedule()) return GPIS_ERR_STATE;
+    if ((size_t)m > cap_chk) {
+        (void)hipFree(d_chkd); (void)hipFree(d_chki);
+        d_chkd = nullptr; d_chki = nullptr; cap_chk = 0;
+        GPIS_HIP(hipMalloc((void**)&d_chkd, sizeof(double) * 2 * (size_t)m));
+        GPIS_HIP(hipMalloc((void**)&d_chki, sizeof(int) * 3 * (size_t)m));
+        cap_chk = (size_t)m;
+    }
+    const double TB = r_begin - ob.epoch;
+    const TrajSched sc{d_rres, d_rown, 0};
+    if (dim == 2)
+        hipLaunchKernelGGL(traj_retime_check_kernel<2>, dim3((unsigned)m), dim3(kBlock), 0, own, d_x, d_tv, d_tt, d_tint, N, steps, ropts.slot,
+                           TB, clearance, (const double*)ob.d_tab, ob.n, d_chkd, d_chki, sc);
+    else
+        hipLaunchKernelGGL(traj_retime_check_kernel<3>, dim3((unsigned)m), dim3(kBlock), 0, own, d_x, d_tv, d_tt, d_tint, N, steps, ropts.slot,
+                           TB, clearance, (const double*)ob.d_tab, ob.n, d_chkd, d_chki, sc);
+    GPIS_HIP(hipGetLastError());
+    std::vector<double> hd(2 * (size_t)m);
+    std::vector<int> hi(3 * (size_t)m);
+    GPIS_HIP(hipMemcpyAsync(hd.data(), d_chkd, sizeof(double) * hd.size(), hipMemcpyDeviceToHost, own));
+    GPIS_HIP(hipMemcpyAsync(hi.data(), d_chki, sizeof(int) * hi.size(), hipMemcpyDeviceToHost, own));
+    GPIS_HIP(hipStreamSynchronize(own));
+    for (size_t r = 0; r < (size_t)m; ++r) {
+        if (min_sep) min_sep[r] = hd[2 * r];
+        if (min_time) min_time[r] = hd[2 * r + 1];
+        if (min_obstacle) min_obstacle[r] = hi[3 * r];
+        if (first_hit) first_hit[r] = hi[3 * r + 1];
         if (collides) collides[r] = hi[3 * r + 2];
     }
     return GPIS_OK;

@@ -1028,6 +1028,72 @@ int   gpis_obst_mppi_get(void* mppi, int* dyn_hits, double* min_sep, double* sta
 int   gpis_obst_check_timing(void* traj, void* obst, double dt, int steps, double t0, double t_begin, double clearance,
                              double* min_sep, double* min_time, int* min_obstacle, int* first_hit, int* collides);
 
+/* ---- re-timing: schedules that wait for moving balls to pass ---------------------------------------------------
+ * gpis_obst_check_timing can say that a timed trajectory collides; gpis_retime_solve makes it hold again by path-velocity
+ * decomposition: the geometry and the timing stay, the search is over when to move.  (The entries are gpis_retime_*: the timing,
+ * obstacle and trajectory sections keep their sets of entries.)  tests/retime_ref.py states every rule in numpy; the schedule
+ * is integers and flags and depends on no order, every separation is gpis_obst_check_timing's expression, operation for
+ * operation in double with nothing contracted, and the device's integers and bits are the reference's.
+ * For a handle that holds a timing, each trajectory of timing status 0, the options slot (seconds), max_pause P, clearance and
+ * press_on, a set of n balls and t_begin (the absolute time at which the schedule starts):
+ *  - Own time runs in slots.  A = the least integer a >= 0 with (double)a * slot >= (double)t_{N-1}; pos_a = the timed
+ *    position p of gpis_timing_controls at tau = (double)a * slot, a = 0 .. A, bit for bit.  A > 1024: status 4.
+ *  - sep(p0, dp, k, i): gpis_obst_check_timing's sep for one interval and ball i with p_k = p0, p_{k+1} - p_k = dp, t0 = 0,
+ *    dt = slot: e_k = TB + (double)k * slot, e_{k+1} = TB + (double)(k + 1) * slot, TB = t_begin - epoch.
+ *  - Cell (a, p): own slot a after p pauses, at real slot k = a + p.  pause_free[a][p] iff no ball has sep(pos_a, 0, a + p, i)
+ *    < clearance; play_free[a][p] iff no ball has sep(pos_a, pos_{a+1} - pos_a, a + p, i) < clearance.  A NaN separation is
+ *    not below the clearance, as in the check.
+ *  - reach[0][0] = 1; reach[a][p] = (a > 0 and reach[a-1][p] and play_free[a-1][p]) or (p > 0 and reach[a][p-1] and
+ *    pause_free[a][p-1]).  p* = the least p <= P with reach[A][p]; none: status 3.
+ *  - The schedule: walk back from (A, p*) to (0, 0).  press_on = 0: the play predecessor wherever it is reached and free, else
+ *    the pause predecessor (pauses fall as early as the optimum allows: the robot holds back); press_on = 1: the pause
+ *    predecessor first (pauses fall as late as allowed).  own[a + p] = a along the walk; own(k) = A for every k > arrive =
+ *    A + p*.  first_pause = the least real slot k with own(k + 1) = own(k), k < arrive; -1 without a pause.
+ *  - Per trajectory: status (0 clear as timed, 1 re-timed with pauses, 2 no timing (timing status 2 or 3), 3 no schedule within
+ *    max_pause, 4 too long for this slot), arrive, pauses = p*, own_slots = A, first_pause, own[1280].  Status 2 and 4: -1 in
+ *    all four and in the table; status 3: own_slots = A, -1 elsewhere.  With n = 0: status 0 and own(k) = min(k, A).
+ *  - Pauses are instantaneous: the model of §7l commands velocities, and a_max / d_max of the timing are not kept across a pause.
+ * Cost: at worst A (P + 1) 2 n separations per trajectory, one workgroup each.
+ * gpis_retime_controls is gpis_timing_controls' second stage with dt = slot and, for step k = 0 .. T - 1, the two positions
+ * pos_own(k0 + k) and pos_own(k0 + k + 1): a paused step has zero displacement and takes the heading of the latest moving step by the
+ * same rule.  A schedule of status >= 2 stands still as an untimed trajectory does.  gpis_retime_follow writes the sequence of
+ * trajectory `index` into the controller's nominal sequence as gpis_timing_follow does; the controller is meant to run at
+ * dt = slot.  gpis_retime_check gives gpis_obst_check_timing's five outputs with p_k = pos_own(k), k = 0 .. steps, the balls
+ * of `obst` at the real slots from the schedule's t_begin and min_time in real time from it; any set of the handle's dim may be
+ * checked against a schedule.  Status >= 2 answers as timing status 2 does.  The certificate: with the solve's set and
+ * clearance and steps <= arrive, a schedule of status 0 or 1 has collides = 0 and min_sep >= clearance -- the same
+ * expressions on the same operands.
+ * Errors: a NULL handle, set or opts; slot <= 0, clearance < 0 or either non-finite; max_pause outside [0, 255]; press_on
+ * outside {0, 1}; a non-finite t_begin; a set of another dim or device; T outside [1, 256]; k0 outside [0, 2^20]; w_limit < 0,
+ * min_move < 0 or non-finite; steps outside [1, 4096]; a controller of another dim or device; index outside [0, m) ->
+ * GPIS_ERR_ARG.  A handle without a timing (solve) or without a schedule (the others), a controller that is not initialised,
+ * a trajectory whose schedule status is >= 2 (follow) -> GPIS_ERR_STATE.  All before anything is written.  A new input,
+ * gpis_traj_optimize or gpis_timing_time drops the schedule with the timing. */
+typedef struct gpis_retime_opts {
+    double slot;                /* seconds of a slot; > 0 */
+    int    max_pause;           /* P: the most pause slots of a schedule; 0 .. 255 */
+    double clearance;           /* a cell is free while no separation is below it; >= 0 */
+    int    press_on;            /* 0: pauses as early as the optimum allows; 1: as late */
+} gpis_retime_opts;
+/* slot 0.1, max_pause 63, clearance step, press_on 0.  dim outside {2, 3}, a step that is not finite and positive, NULL opts
+ * -> GPIS_ERR_ARG.  Needs no device. */
+int   gpis_retime_default_opts(int dim, float step, gpis_retime_opts* opts);
+/* hip_stream NULL: the handle's own stream; returns with the schedule finished */
+int   gpis_retime_solve(void* traj, void* obst, double t_begin, const gpis_retime_opts* opts, void* hip_stream);
+/* host copies of the last schedule (any may be NULL): status, arrive, pauses, own_slots, first_pause [m]; own [m][1280];
+ * the options of the solve; info [2] = t_begin, ms of host wall time in the solve */
+int   gpis_retime_get(void* traj, int* status, int* arrive, int* pauses, int* own_slots, int* first_pause, int* own,
+                      gpis_retime_opts* opts, double* info);
+/* U[m][T][2 or 4], heading0[m][2], p0[m][dim], clamped[m]; any may be NULL */
+int   gpis_retime_controls(void* traj, int T, int k0, double w_limit, double min_move, double* U, double* heading0, double* p0,
+                           int* clamped);
+/* heading0_out[2], p0_out[dim]; either may be NULL */
+int   gpis_retime_follow(void* mppi, void* traj, int index, int k0, double w_limit, double min_move, double* heading0_out,
+                         double* p0_out);
+/* [m] each; any may be NULL */
+int   gpis_retime_check(void* traj, void* obst, int steps, double clearance, double* min_sep, double* min_time,
+                        int* min_obstacle, int* first_hit, int* collides);
+
 /* ---- the robot's footprint: body balls in pose checks, rollouts and trajectories -----------------------------
  * Every stage above treats the robot as one point with a scalar clearance.  A footprint is m balls fixed to the robot,
  * 0 <= m <= 16 (discs in 2-D, spheres in 3-D), each an offset b[dim] in the body frame (x forward, y left, z up) and a radius
