@@ -391,6 +391,12 @@ def lib():
         L.gpis_body_clearance.argtypes = [vp, vp, dp, C.c_longlong, d, dp, ip, ip, vp]
         L.gpis_body_mppi_step.argtypes = [vp, vp, vp, vp, vp, d, dp, dp, C.POINTER(gpis_mppi_opts), dp, vp]
         L.gpis_body_traj_clearance.argtypes = [vp, vp, vp, d, dp, ip, ip, ip]
+    if hasattr(L, "gpis_timed_body_check"):
+        L.gpis_timed_body_check.argtypes = [vp, vp, vp, d, C.c_int, d, d, d, dp, dp, ip, ip, ip, ip]
+        L.gpis_timed_body_retime.argtypes = [vp, vp, vp, d, C.POINTER(gpis_retime_opts), vp]
+        L.gpis_timed_body_info.argtypes = [vp, dp, C.c_int]
+        L.gpis_timed_body_retime_check.argtypes = [vp, vp, vp, C.c_int, d, dp, dp, ip, ip, ip, ip]
+        L.gpis_timed_body_states.argtypes = [vp, d, C.c_int, d, C.c_int, dp]
     if hasattr(L, "gpis_smooth_body_optimize"):
         L.gpis_smooth_body_default_opts.argtypes = [C.c_int, C.c_float, C.c_int, C.POINTER(gpis_traj_opts), C.POINTER(C.c_float)]
         L.gpis_smooth_body_optimize.argtypes = [vp, vp, vp, C.POINTER(gpis_traj_opts), C.c_float, vp]
@@ -2353,37 +2359,66 @@ class Trajectories:
         return U, h0, p0, cl
 
 
-    def check(self, obstacles, dt, steps, t0=0.0, t_begin=0.0, clearance=None):
+    def check(self, obstacles, dt, steps, t0=0.0, t_begin=0.0, clearance=None, footprint=None):
         """The timed trajectories against an Obstacles (gpis_obst_check_timing): sampled at t0 + k dt, k = 0 .. steps, trajectory
         time 0 at the absolute time t_begin; between samples both bodies move in straight lines and the closest approach is
         taken in continuous time.  clearance None: the set's own.  Returns dict(min_sep, min_time [m] f64, min_obstacle,
-        first_hit, collides [m] i32)."""
+        first_hit, collides [m] i32).  footprint: a Footprint in the point's place (gpis_timed_body_check): the body at its timed
+        pose -- the heading of the segment it is on -- and every pair of a body ball and a moving ball; the dict gains min_ball."""
         m = self.info()["m"]
         if clearance is None:
             clearance = obstacles.get()["opts"]["clearance"]
         r = dict(min_sep=np.zeros(m, np.float64), min_time=np.zeros(m, np.float64), min_obstacle=np.zeros(m, np.int32),
                  first_hit=np.zeros(m, np.int32), collides=np.zeros(m, np.int32))
+        if footprint is not None:
+            r["min_ball"] = np.zeros(m, np.int32)
+            _check(self.L.gpis_timed_body_check(self.h, obstacles.h, footprint.h, float(dt), int(steps), float(t0), float(t_begin),
+                                                 float(clearance), _p(r["min_sep"], C.c_double), _p(r["min_time"], C.c_double),
+                                                 _p(r["min_obstacle"], C.c_int), _p(r["min_ball"], C.c_int), _p(r["first_hit"], C.c_int),
+                                                 _p(r["collides"], C.c_int)), "gpis_timed_body_check")
+            return r
         _check(self.L.gpis_obst_check_timing(self.h, obstacles.h, float(dt), int(steps), float(t0), float(t_begin), float(clearance),
                                              _p(r["min_sep"], C.c_double), _p(r["min_time"], C.c_double), _p(r["min_obstacle"], C.c_int),
                                              _p(r["first_hit"], C.c_int), _p(r["collides"], C.c_int)), "gpis_obst_check_timing")
         return r
 
+    def timed_states(self, dt, steps, t0=0.0, retimed=False):
+        """The timed poses (gpis_timed_body_states): [m, steps + 1, dim + 2] f64 states (p, c, s) as Footprint.clearance takes
+        them, at t0 + k dt, or with retimed=True at the own slot of every real slot k of the last schedule (dt and t0 are not
+        read).  The heading is the chord's of the segment the position lies on.  Rows without a timing or a schedule are NaN."""
+        i = self.info()
+        out = np.zeros((i["m"], max(int(steps), 0) + 1, i["dim"] + 2), np.float64)
+        _check(self.L.gpis_timed_body_states(self.h, float(dt), int(steps), float(t0), 1 if retimed else 0, _p(out, C.c_double)),
+               "gpis_timed_body_states")
+        return out
+
     OWN_LEN = 1280                                       # real slots of the longest schedule (1024 own slots + 255 pauses + 1)
 
-    def retime(self, obstacles, t_begin=0.0, stream=0, **opts):
+    def retime(self, obstacles, t_begin=0.0, stream=0, footprint=None, **opts):
         """Re-time the timed trajectories so that they wait for the balls of an Obstacles to pass (gpis_retime_solve): the
         geometry and the timing stay, a schedule says for every real slot of `slot` seconds, counted from the absolute time
         t_begin, which own slot of the timed trajectory is played; the schedule that arrives first within max_pause pause slots
         is kept.  opts: gpis_retime_opts fields (slot, max_pause, clearance, press_on); clearance defaults to the set's own.
-        Returns retimed()."""
+        footprint: a Footprint in the point's place (gpis_timed_body_retime): a pause holds the pose of its own slot, a play step
+        goes from the pose of one own slot to the next.  Returns retimed()."""
         i = self.info()
         if not self.timing_info()["timed"]:
             raise GpisError("trajectories hold no timing")
         if "clearance" not in opts:
             opts = dict(opts, clearance=obstacles.get()["opts"]["clearance"])
         o = retime_opts(i["dim"], 1.0, **opts)
+        if footprint is not None:
+            _check(self.L.gpis_timed_body_retime(self.h, obstacles.h, footprint.h, float(t_begin), C.byref(o), C.c_void_p(stream)),
+                   "gpis_timed_body_retime")
+            return self.retimed()
         _check(self.L.gpis_retime_solve(self.h, obstacles.h, float(t_begin), C.byref(o), C.c_void_p(stream)), "gpis_retime_solve")
         return self.retimed()
+
+    def retimed_body_balls(self):
+        """The number of body balls the last schedule was solved for (gpis_timed_body_info): 0 after a point solve."""
+        out = np.zeros(1, np.float64)
+        _check(self.L.gpis_timed_body_info(self.h, _p(out, C.c_double), 1), "gpis_timed_body_info")
+        return int(out[0])
 
     def retimed(self):
         """The last schedule (gpis_retime_get): dict(status [m] i32 (0 clear as timed, 1 re-timed with pauses, 2 no timing, 3 no
@@ -2413,16 +2448,22 @@ class Trajectories:
                                            _p(p0, C.c_double), _p(cl, C.c_int)), "gpis_retime_controls")
         return U, h0, p0, cl
 
-    def retimed_check(self, obstacles, steps, clearance=None):
+    def retimed_check(self, obstacles, steps, clearance=None, footprint=None):
         """check() along the last schedule (gpis_retime_check): the robot at the schedule's position of every real slot
         k = 0 .. steps, the balls of `obstacles` (any set of this dim: a newer detection may be checked against an old schedule)
         at the real slots from the schedule's t_begin.  clearance None: the set's own.  Returns check()'s dict, min_time in real
-        time from t_begin."""
+        time from t_begin.  footprint: a Footprint in the point's place (gpis_timed_body_retime_check); the dict gains min_ball."""
         m = self.info()["m"]
         if clearance is None:
             clearance = obstacles.get()["opts"]["clearance"]
         r = dict(min_sep=np.zeros(m, np.float64), min_time=np.zeros(m, np.float64), min_obstacle=np.zeros(m, np.int32),
                  first_hit=np.zeros(m, np.int32), collides=np.zeros(m, np.int32))
+        if footprint is not None:
+            r["min_ball"] = np.zeros(m, np.int32)
+            _check(self.L.gpis_timed_body_retime_check(self.h, obstacles.h, footprint.h, int(steps), float(clearance), _p(r["min_sep"], C.c_double),
+                                                 _p(r["min_time"], C.c_double), _p(r["min_obstacle"], C.c_int), _p(r["min_ball"], C.c_int),
+                                                 _p(r["first_hit"], C.c_int), _p(r["collides"], C.c_int)), "gpis_timed_body_retime_check")
+            return r
         _check(self.L.gpis_retime_check(self.h, obstacles.h, int(steps), float(clearance), _p(r["min_sep"], C.c_double),
                                         _p(r["min_time"], C.c_double), _p(r["min_obstacle"], C.c_int), _p(r["first_hit"], C.c_int),
                                         _p(r["collides"], C.c_int)), "gpis_retime_check")

@@ -2280,6 +2280,79 @@ int gpis_body_traj_clearance(void* traj, void* df, void* body, double clearance,
     catch (...) { return GPIS_ERR_STATE; }
 }
 
+// ---- the footprint against moving balls: the timed check, the re-timing and its check ------------------------------------------
+// what every timed entry with a footprint refuses before anything else: no body, an empty one, one of another dim or device
+static int body_time_args(const Trajectories& t, const Footprint* b) {
+    if (!b || b->m == 0) return GPIS_ERR_ARG;
+    if (t.valid && (b->dim != t.dim || b->device != t.device)) return GPIS_ERR_ARG;
+    return GPIS_OK;
+}
+int gpis_timed_body_check(void* traj, void* obst, void* body, double dt, int steps, double t0, double t_begin, double clearance,
+                           double* min_sep, double* min_time, int* min_obstacle, int* min_ball, int* first_hit, int* collides) {
+    if (!traj || !obst || !body) return GPIS_ERR_ARG;
+    if (!std::isfinite(dt) || !std::isfinite(t0) || !std::isfinite(t_begin) || !std::isfinite(clearance)) return GPIS_ERR_ARG;
+    if (steps < 1 || steps > 4096 || !(dt > 0.0) || t0 < 0.0 || clearance < 0.0) return GPIS_ERR_ARG;
+    Trajectories& t = *(Trajectories*)traj;
+    const Obstacles& b = *(const Obstacles*)obst;
+    const Footprint& f = *(const Footprint*)body;
+    if (int rc = body_time_args(t, &f)) return rc;
+    if (!t.has_timing()) return GPIS_ERR_STATE;
+    if (b.device != t.device || (b.inited && b.dim != t.dim)) return GPIS_ERR_ARG;
+    DeviceScope ds(t.device);
+    try {
+        return t.check_body_obst(b, BodyArgs{f.d_tab, f.m}, dt, steps, t0, t_begin, clearance, min_sep, min_time, min_obstacle, min_ball,
+                                 first_hit, collides);
+    } catch (...) { return GPIS_ERR_STATE; }
+}
+// Everything is checked before the previous schedule is dropped; a failure after that leaves the timing without one.
+int gpis_timed_body_retime(void* traj, void* obst, void* body, double t_begin, const gpis_retime_opts* opts, void* stream) {
+    if (!traj || !obst || !body || !opts || !std::isfinite(t_begin)) return GPIS_ERR_ARG;
+    RetimeOpts o;
+    o.slot = opts->slot; o.max_pause = opts->max_pause; o.clearance = opts->clearance; o.press_on = opts->press_on;
+    if (int rc = retime_check_opts(o)) return rc;
+    Trajectories& t = *(Trajectories*)traj;
+    const Obstacles& b = *(const Obstacles*)obst;
+    const Footprint& f = *(const Footprint*)body;
+    if (int rc = body_time_args(t, &f)) return rc;
+    if (!t.has_timing()) return GPIS_ERR_STATE;
+    if (b.device != t.device || (b.inited && b.dim != t.dim)) return GPIS_ERR_ARG;
+    DeviceScope ds(t.device);
+    try { return t.retime_body(b, BodyArgs{f.d_tab, f.m}, o, t_begin, (hipStream_t)stream); }
+    catch (...) { t.retimed = false; return GPIS_ERR_STATE; }
+}
+int gpis_timed_body_info(void* traj, double* out, int n) {
+    if (!traj || !out || n < 0) return GPIS_ERR_ARG;
+    const Trajectories& t = *(const Trajectories*)traj;
+    if (!t.has_schedule()) return GPIS_ERR_STATE;
+    const double v[1] = {(double)t.r_body};
+    for (int i = 0; i < n && i < 1; ++i) out[i] = v[i];
+    return GPIS_OK;
+}
+int gpis_timed_body_retime_check(void* traj, void* obst, void* body, int steps, double clearance, double* min_sep, double* min_time,
+                           int* min_obstacle, int* min_ball, int* first_hit, int* collides) {
+    if (!traj || !obst || !body) return GPIS_ERR_ARG;
+    if (!std::isfinite(clearance) || steps < 1 || steps > 4096 || clearance < 0.0) return GPIS_ERR_ARG;
+    Trajectories& t = *(Trajectories*)traj;
+    const Obstacles& b = *(const Obstacles*)obst;
+    const Footprint& f = *(const Footprint*)body;
+    if (int rc = body_time_args(t, &f)) return rc;
+    if (!t.has_schedule()) return GPIS_ERR_STATE;
+    if (b.device != t.device || (b.inited && b.dim != t.dim)) return GPIS_ERR_ARG;
+    DeviceScope ds(t.device);
+    try {
+        return t.retime_body_check(b, BodyArgs{f.d_tab, f.m}, steps, clearance, min_sep, min_time, min_obstacle, min_ball, first_hit,
+                                   collides);
+    } catch (...) { return GPIS_ERR_STATE; }
+}
+int gpis_timed_body_states(void* traj, double dt, int steps, double t0, int retimed, double* states_out) {
+    if (!traj || !states_out || (retimed != 0 && retimed != 1)) return GPIS_ERR_ARG;
+    if (steps < 1 || steps > 4096) return GPIS_ERR_ARG;
+    if (!retimed && (!std::isfinite(dt) || !std::isfinite(t0) || !(dt > 0.0) || t0 < 0.0)) return GPIS_ERR_ARG;
+    Trajectories& t = *(Trajectories*)traj;
+    DeviceScope ds(t.device);
+    try { return t.timed_states(dt, steps, t0, retimed != 0, states_out); } catch (...) { return GPIS_ERR_STATE; }
+}
+
 // ---- smoothing for the robot's footprint ---------------------------------------------------------------------------------------
 int gpis_smooth_body_default_opts(int dim, float step, int balls, gpis_traj_opts* o, float* w_turn) {
     if (balls < 1 || balls > Footprint::kMax) return GPIS_ERR_ARG;

@@ -12,6 +12,9 @@
 // On top of a timing: a schedule that plays the timed trajectory and pauses it until moving balls have passed,
 // and the control sequences, the controller's seed and the check along it; the integers and bits are those of
 // tests/retime_ref.py.
+// With a footprint against moving balls: the timed check, the re-timing and the check along a schedule take the
+// body at its timed pose -- the timed position and the chord rule's heading of the segment it lies on -- and every pair of a body
+// ball and a moving ball; the integers and bits are those of tests/body_time_ref.py.
 #pragma once
 #include <cstdint>
 #include <vector>
@@ -106,6 +109,12 @@ struct Trajectories {
     double r_begin = 0.0;
     bool retimed = false;
     double retime_ms = 0.0;
+    int r_body = 0;                                  // body balls of the last re-timing (0: the point's)
+    // the last check of a footprint against moving balls, and the last timed poses
+    double* d_btd = nullptr;                         // [m][2] min_sep, min_time
+    int* d_bti = nullptr;                            // [m][4] min_obstacle, first_hit, collides, min_ball
+    size_t cap_bt = 0;
+    double* d_bst = nullptr; size_t cap_bst = 0;     // [m][steps + 1][dim + 2]
 
     int m = 0, N = 0, dim = 0;
     bool has_input = false, valid = false, timed = false;
@@ -164,7 +173,27 @@ struct Trajectories {
     int retime_check(const Obstacles& ob, int steps, double clearance, double* min_sep, double* min_time, int* min_obstacle,
                      int* first_hit, int* collides);
 
+    // The footprint against moving balls (the contract: tests/body_time_ref.py).  The timed pose at tau: the timed
+    // position, and the chord rule's heading (check_body's) of the waypoint whose segment the position lies on (the last waypoint
+    // from the duration on).  A body ball's centre moves in a straight line between two samples; its separation from a moving
+    // ball is check_obst's expression at that centre, less the body ball's radius.  bd: a footprint of this dim on this device
+    // with m > 0 (checked by the caller).
+    // check_obst() over every (interval, moving ball, body ball); min_ball: the body ball of the least separation
+    int check_body_obst(const Obstacles& ob, const BodyArgs& bd, double dt, int steps, double t0, double t_begin, double clearance,
+                        double* min_sep, double* min_time, int* min_obstacle, int* min_ball, int* first_hit, int* collides);
+    // retime() with the cells' flags over every (moving ball, body ball): a pause holds the pose of its own slot, a play step
+    // goes from the pose of own slot a to that of a + 1.  The schedule is kept where retime() keeps it
+    int retime_body(const Obstacles& ob, const BodyArgs& bd, const RetimeOpts& o, double t_begin, hipStream_t s);
+    // retime_check() with the footprint: the pose of own(k) at real slot k
+    int retime_body_check(const Obstacles& ob, const BodyArgs& bd, int steps, double clearance, double* min_sep, double* min_time,
+                          int* min_obstacle, int* min_ball, int* first_hit, int* collides);
+    // the timed poses (p, c, s) [m][steps + 1][dim + 2] at t0 + k dt, or (sched) at own(k) of the schedule with dt its slot; NaN
+    // for a trajectory without a timing or a schedule; a host output; synchronises the own stream
+    int timed_states(double dt, int steps, double t0, bool sched, double* states);
+
 private:
+    int body_time_check(const Obstacles& ob, const BodyArgs& bd, bool sched, double dt, int steps, double t0, double TB, double clearance,
+                        double* min_sep, double* min_time, int* min_obstacle, int* min_ball, int* first_hit, int* collides);
     int ensure(int m, int N, int dim);
     int from_packed(int dev, long long npaths, long long npoints, int dim, const long long* off, const float* pts,
                     const unsigned char* pstat, int N, bool zero_w);

@@ -903,6 +903,390 @@ __global__ void __launch_bounds__(kBlock) traj_body_check_kernel(const float* __
     }
 }
 
+// ---- the footprint against moving balls along a timed trajectory and in its re-timing --------------------------
+// The contract: tests/body_time_ref.py.  The timed pose at tau is (p, c, s): p is traj_position's timed position, i(tau) the
+// segment its bisection ends on (N - 1 from the duration on), (c, s) the chord rule's heading of waypoint i(tau).  The two
+// functions below restate traj_position and traj_chord_heading statement for statement and are called by the kernels of this
+// section alone: a function of this file has internal linkage, and a new caller of the old ones would reach the code of the
+// kernels that call them (§7w).  For the same reason this section writes its minima of two integers as conditionals: the
+// header's min(int, int) is such a shared function too, and new calls of it changed the bisection of the plain check kernels.
+
+// traj_position's statements; returns the segment index
+template <int DIM>
+__device__ __forceinline__ int traj_pose_position(const float* __restrict__ x, const float* __restrict__ v, const float* st, int N,
+                                                  double tau, double* p) {
+    if (tau >= (double)st[N - 1]) {
+#pragma unroll
+        for (int a = 0; a < DIM; ++a) p[a] = (double)x[(size_t)(N - 1) * DIM + a];
+        return N - 1;
+    }
+    int lo = 0, hi = N - 2;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if ((double)st[mid] <= tau) lo = mid; else hi = mid - 1;
+    }
+    const double ti = (double)st[lo], h = (double)st[lo + 1] - ti, e = tau - ti, vi = (double)v[lo];
+    const double acc = ((double)v[lo + 1] - vi) / h;
+    const double s = vi * e + ((0.5 * acc) * e) * e;
+    double d[DIM], x0[DIM], sq = 0.0;
+#pragma unroll
+    for (int a = 0; a < DIM; ++a) {
+        x0[a] = (double)x[(size_t)lo * DIM + a];
+        d[a] = (double)x[(size_t)(lo + 1) * DIM + a] - x0[a];
+        sq = a ? sq + d[a] * d[a] : d[a] * d[a];
+    }
+    double w = s / sqrt(sq);
+    w = w > 0.0 ? w : 0.0;
+    w = w < 1.0 ? w : 1.0;
+#pragma unroll
+    for (int a = 0; a < DIM; ++a) p[a] = x0[a] + w * d[a];
+    return lo;
+}
+
+// traj_chord_heading's rule on the waypoints x[k * DIM + {0, 1}]: (c, s) of waypoint i
+template <int DIM>
+__device__ __forceinline__ void traj_pose_heading(const float* __restrict__ x, int i, int N, double* c, double* s) {
+    const int k0 = i < N - 2 ? i : N - 2;
+    *c = 1.0; *s = 0.0;
+    for (int pass = 0; pass < 2; ++pass) {
+        for (int k = pass == 0 ? k0 : k0 - 1; pass == 0 ? k <= N - 2 : k >= 0; k += pass == 0 ? 1 : -1) {
+            const double e0 = (double)x[(size_t)(k + 1) * DIM] - (double)x[(size_t)k * DIM];
+            const double e1 = (double)x[(size_t)(k + 1) * DIM + 1] - (double)x[(size_t)k * DIM + 1];
+            const double n2 = e0 * e0 + e1 * e1;
+            if (n2 > 0.0) {
+                const double nn = sqrt(n2);
+                *c = e0 / nn; *s = e1 / nn;
+                return;
+            }
+        }
+    }
+}
+
+// the pose q[DIM + 2] = (p, c, s) at tau
+template <int DIM>
+__device__ __forceinline__ void traj_pose_at(const float* __restrict__ x, const float* __restrict__ v, const float* st, int N, double tau,
+                                             double* q) {
+    const int i = traj_pose_position<DIM>(x, v, st, N, tau, q);
+    traj_pose_heading<DIM>(x, i, N, &q[DIM], &q[DIM + 1]);
+}
+
+// where ball `row` of the body sits at the pose q (the body rule's position, §7r: body_ball_at's statements)
+template <int DIM>
+__device__ __forceinline__ void traj_pose_ball(const double* __restrict__ row, const double* q, double* w) {
+    const double b0 = row[0], b1 = row[1], c = q[DIM], s = q[DIM + 1];
+    w[0] = q[0] + (c * b0 - s * b1);
+    w[1] = q[1] + (s * b0 + c * b1);
+    if constexpr (DIM == 3) w[2] = q[2] + row[2];
+}
+
+// the separation of one interval of one body ball's centre (from w0 by dw) from the moving ball of `row`, less the body ball's
+// radius: the expression of the check's inner loop, operation for operation
+template <int DIM>
+__device__ __forceinline__ double traj_body_ball_sep(const double* w0, const double* dw, double e0, double e1,
+                                                     const double* __restrict__ row, double rho, double* s_out) {
+    double A[DIM], B[DIM], bb = 0.0, ab = 0.0;
+#pragma unroll
+    for (int a = 0; a < DIM; ++a) {
+        const double o0 = row[a] + row[3 + a] * e0, o1 = row[a] + row[3 + a] * e1;
+        A[a] = w0[a] - o0;
+        B[a] = dw[a] - (o1 - o0);
+        bb = a ? bb + B[a] * B[a] : B[a] * B[a];
+        ab = a ? ab + A[a] * B[a] : A[a] * B[a];
+    }
+    double s = 0.0;
+    if (bb > 0.0) {
+        s = (-ab) / bb;
+        s = s > 0.0 ? s : 0.0;
+        s = s < 1.0 ? s : 1.0;
+    }
+    double s2 = 0.0;
+#pragma unroll
+    for (int a = 0; a < DIM; ++a) {
+        const double q = A[a] + s * B[a];
+        s2 = a ? s2 + q * q : q * q;
+    }
+    *s_out = s;
+    return (sqrt(s2) - row[6]) - rho;
+}
+
+// The timed poses of every trajectory: out[tr][steps + 1][DIM + 2].  SCHED 0: at t0 + k dt; SCHED 1: at the own slot own(k) of
+// the schedule `sc`, dt its slot.  A trajectory without a timing (SCHED 1: or without a schedule): NaN.
+template <int DIM, int SCHED>
+__global__ void __launch_bounds__(kBlock) traj_body_states_kernel(const float* __restrict__ x, const float* __restrict__ v,
+                                                                  const float* __restrict__ tt, const int* __restrict__ tint, int N,
+                                                                  int steps, double dt, double t0, double* __restrict__ out,
+                                                                  TrajSched sc) {
+    __shared__ float st[kTree];
+    const int tr = blockIdx.x, tid = threadIdx.x;
+    const size_t base = (size_t)tr * N;
+    double* o = out + (size_t)tr * (steps + 1) * (DIM + 2);
+    bool timed = tint[(size_t)tr * 9] == 0;
+    if constexpr (SCHED) timed = timed && sc.res[(size_t)tr * kSchedRes] < 2;
+    if (!timed) {                                        // (uniform: one trajectory per workgroup)
+        for (int j = tid; j < (steps + 1) * (DIM + 2); j += kBlock) o[j] = (double)NAN;
+        return;
+    }
+    for (int i = tid; i < N; i += kBlock) st[i] = tt[base + i];
+    __syncthreads();
+    for (int j = tid; j <= steps; j += kBlock) {
+        double q[DIM + 2];
+        const double tau = SCHED ? (double)sched_own(sc, tr, j) * dt : t0 + (double)j * dt;
+        traj_pose_at<DIM>(x + base * DIM, v + base, st, N, tau, q);
+#pragma unroll
+        for (int a = 0; a < DIM + 2; ++a) o[(size_t)j * (DIM + 2) + a] = q[a];
+    }
+}
+
+// traj_obst_check_kernel / traj_retime_check_kernel (SCHED 1) with the footprint bd.  The chunk's poses go to LDS once; a thread
+// per interval takes the body balls j (the footprint's rows: the same index in every lane, scalar loads) and inside them the
+// moving balls i (the same), and keeps its own least (sep, k, i, j): it meets k ascending, and within an interval a later pair
+// replaces the kept one if its sep is smaller, or equal with a smaller i (its j is the larger one).  The block's result: the
+// least sep, then the least key (k << 12 | i << 4 | j) among the threads that hold it.  out_d[tr][2] = min_sep, min_time;
+// out_i[tr][4] = min_obstacle, first_hit, collides, min_ball.
+template <int DIM, int SCHED>
+__global__ void __launch_bounds__(kBlock) traj_body_time_check_kernel(const float* __restrict__ x, const float* __restrict__ v,
+                                                                      const float* __restrict__ tt, const int* __restrict__ tint, int N,
+                                                                      int steps, double dt, double t0, double TB, double clearance,
+                                                                      const double* __restrict__ tab, int n, BodyArgs bd,
+                                                                      double* __restrict__ out_d, int* __restrict__ out_i, TrajSched sc) {
+    typedef unsigned long long u64;
+    __shared__ float st[kTree];
+    __shared__ double sq[kChunk + 1][DIM + 2];
+    __shared__ double shd[kBlock / 64];
+    __shared__ u64 shk[kBlock / 64];
+    __shared__ int shi[kBlock / 64];
+    const int tr = blockIdx.x, tid = threadIdx.x;
+    const size_t base = (size_t)tr * N;
+    bool timed = tint[(size_t)tr * 9] == 0;
+    if constexpr (SCHED) timed = timed && sc.res[(size_t)tr * kSchedRes] < 2;
+    if (!timed || n == 0) {
+        if (tid == 0) {
+            out_d[(size_t)tr * 2] = timed ? (double)INFINITY : (double)NAN; out_d[(size_t)tr * 2 + 1] = (double)NAN;
+            out_i[(size_t)tr * 4] = -1; out_i[(size_t)tr * 4 + 1] = -1; out_i[(size_t)tr * 4 + 2] = 0; out_i[(size_t)tr * 4 + 3] = -1;
+        }
+        return;
+    }
+    for (int i = tid; i < N; i += kBlock) st[i] = tt[base + i];
+    double best = INFINITY, best_s = 0.0;
+    int best_k = -1, best_i = -1, best_j = -1, hit = 0x7fffffff;
+    for (int k0 = 0; k0 < steps; k0 += kChunk) {
+        const int cnt = steps - k0 < kChunk ? steps - k0 : kChunk;
+        __syncthreads();                                 // (st is written; sq of the previous chunk is read)
+        for (int j = tid; j <= cnt; j += kBlock) {
+            double q[DIM + 2];
+            const double tau = SCHED ? (double)sched_own(sc, tr, k0 + j) * dt : t0 + (double)(k0 + j) * dt;
+            traj_pose_at<DIM>(x + base * DIM, v + base, st, N, tau, q);
+#pragma unroll
+            for (int a = 0; a < DIM + 2; ++a) sq[j][a] = q[a];
+        }
+        __syncthreads();
+        for (int jj = tid; jj < cnt; jj += kBlock) {
+            const int k = k0 + jj;
+            const double e0 = TB + (t0 + (double)k * dt), e1 = TB + (t0 + (double)(k + 1) * dt);
+            double q0[DIM + 2], q1[DIM + 2];
+#pragma unroll
+            for (int a = 0; a < DIM + 2; ++a) { q0[a] = sq[jj][a]; q1[a] = sq[jj + 1][a]; }
+            const double* __restrict__ brow = bd.tab;
+            for (int j = 0; j < bd.m; ++j, brow += 4) {
+                double w0[DIM], w1[DIM], dw[DIM];
+                traj_pose_ball<DIM>(brow, q0, w0);
+                traj_pose_ball<DIM>(brow, q1, w1);
+#pragma unroll
+                for (int a = 0; a < DIM; ++a) dw[a] = w1[a] - w0[a];
+                const double rho = brow[3];
+                const double* __restrict__ row = tab;
+                for (int i = 0; i < n; ++i, row += Obstacles::kRow) {
+                    double s;
+                    const double sep = traj_body_ball_sep<DIM>(w0, dw, e0, e1, row, rho, &s);
+                    if (sep < best || (sep == best && k == best_k && i < best_i)) { best = sep; best_s = s; best_k = k; best_i = i; best_j = j; }
+                    if (sep < clearance && k < hit) hit = k;
+                }
+            }
+        }
+    }
+    const double bmin = block_reduce(best, OpMin(), shd, kBlock, (double)INFINITY);
+    if (tid == 0) shd[0] = bmin;
+    __syncthreads();
+    const double least = shd[0];
+    const u64 key = best_k >= 0 && best == least ? ((u64)best_k << 12) | ((u64)best_i << 4) | (u64)best_j : ~0ull;
+    const u64 kmin = block_reduce(key, OpMin(), shk, kBlock, ~0ull);
+    if (tid == 0) shk[0] = kmin;
+    __syncthreads();
+    const u64 win = shk[0];
+    const int fh = block_reduce(hit, OpMin(), shi, kBlock, 0x7fffffff);
+    if (tid == 0) {
+        out_i[(size_t)tr * 4 + 1] = fh == 0x7fffffff ? -1 : fh;
+        out_i[(size_t)tr * 4 + 2] = fh == 0x7fffffff ? 0 : 1;
+        if (win == ~0ull) {                              // no separation was a number
+            out_d[(size_t)tr * 2] = (double)INFINITY; out_d[(size_t)tr * 2 + 1] = (double)NAN;
+            out_i[(size_t)tr * 4] = -1; out_i[(size_t)tr * 4 + 3] = -1;
+        }
+    }
+    if (key == win && win != ~0ull) {
+        out_d[(size_t)tr * 2] = best;
+        out_d[(size_t)tr * 2 + 1] = (t0 + (double)best_k * dt) + best_s * dt;
+        out_i[(size_t)tr * 4] = best_i; out_i[(size_t)tr * 4 + 3] = best_j;
+    }
+}
+
+// a cell of the body's re-timing: no (body ball, moving ball) pair's separation is below the clearance while the body goes from
+// the pose q0 to q1 (a pause: q1 = q0 and every ball's displacement is 0) during the real slot [e0, e1]
+template <int DIM, bool PAUSE>
+__device__ __forceinline__ bool retime_body_cell_free(const double* q0, const double* q1, double e0, double e1,
+                                                      const double* __restrict__ tab, int n, BodyArgs bd, double clearance) {
+    bool ok = true;
+    const double* __restrict__ brow = bd.tab;
+    for (int j = 0; j < bd.m; ++j, brow += 4) {
+        double w0[DIM], dw[DIM];
+        traj_pose_ball<DIM>(brow, q0, w0);
+        if constexpr (PAUSE) {
+#pragma unroll
+            for (int a = 0; a < DIM; ++a) dw[a] = 0.0;
+        } else {
+            double w1[DIM];
+            traj_pose_ball<DIM>(brow, q1, w1);
+#pragma unroll
+            for (int a = 0; a < DIM; ++a) dw[a] = w1[a] - w0[a];
+        }
+        const double rho = brow[3];
+        const double* __restrict__ row = tab;
+        for (int i = 0; i < n; ++i, row += Obstacles::kRow) {
+            double s;
+            const double sep = traj_body_ball_sep<DIM>(w0, dw, e0, e1, row, rho, &s);
+            ok = ok && !(sep < clearance);               // (a NaN separation is not below the clearance, as in the check)
+        }
+    }
+    return ok;
+}
+
+// traj_retime_kernel with the footprint bd: the same rows, ballots, flood and walk; a cell's flags range over the pairs (body
+// ball, moving ball).  The table in LDS is the timed position and the segment index of every own slot (a byte: N <= 256) and the
+// chord rule's heading of every waypoint, which is the pose of every own slot -- the body holds its segment's heading -- in
+// (1025 DIM + 512) doubles and 1025 bytes: one chord search per waypoint, and the kernel's LDS stays below 64 KB with the walk's bits
+// as the point kernel's does.
+template <int DIM>
+__global__ void __launch_bounds__(kBlock) traj_body_retime_kernel(const float* __restrict__ x, const float* __restrict__ v,
+                                                                  const float* __restrict__ tt, const int* __restrict__ tint, int N,
+                                                                  double slot, int P, double clearance, int press_on, double TB,
+                                                                  const double* __restrict__ tab, int n, BodyArgs bd,
+                                                                  int* __restrict__ res, int* __restrict__ own) {
+    typedef unsigned long long u64;
+    __shared__ float st[kTree];
+    __shared__ double sp[kMaxOwnSlots + 1][DIM];
+    __shared__ double shead[kTree][2];
+    __shared__ unsigned char sseg[kMaxOwnSlots + 4];
+    __shared__ u64 spred[kMaxOwnSlots + 1][kBlock / 64];
+    __shared__ u64 smask[2][2][kBlock / 64];             // [row parity][seeds, pause flags][wavefront]
+    const int tr = blockIdx.x, p = threadIdx.x, lane = p & 63, w = p >> 6;
+    const size_t base = (size_t)tr * N;
+    int* ro = res + (size_t)tr * kSchedRes;
+    int* oo = own + (size_t)tr * kOwnLen;
+
+    int A = -1, status = 2;
+    if (tint[(size_t)tr * 9] == 0) {                     // (uniform: one trajectory per workgroup)
+        for (int i = p; i < N; i += kBlock) st[i] = tt[base + i];
+        const double dur = (double)tt[base + N - 1];
+        status = 4;
+        if (dur / slot <= (double)(kMaxOwnSlots + 2)) {
+            int a = (int)(dur / slot);
+            while (a > 0 && (double)(a - 1) * slot >= dur) --a;
+            while ((double)a * slot < dur) ++a;
+            if (a <= kMaxOwnSlots) { A = a; status = 0; }
+        }
+    }
+    if (status != 0) {                                   // no timing, or too long for this slot
+        for (int k = p; k < kOwnLen; k += kBlock) oo[k] = -1;
+        if (p == 0) { ro[0] = status; ro[1] = -1; ro[2] = -1; ro[3] = -1; ro[4] = -1; }
+        return;
+    }
+    if (n == 0) {                                        // nothing to wait for: the identity
+        for (int k = p; k < kOwnLen; k += kBlock) oo[k] = k < A ? k : A;
+        if (p == 0) { ro[0] = 0; ro[1] = A; ro[2] = 0; ro[3] = A; ro[4] = -1; }
+        return;
+    }
+    __syncthreads();                                     // (st is written)
+    for (int j = p; j <= A; j += kBlock) {
+        double q[DIM];
+        const int i = traj_pose_position<DIM>(x + base * DIM, v + base, st, N, (double)j * slot, q);
+#pragma unroll
+        for (int a = 0; a < DIM; ++a) sp[j][a] = q[a];
+        sseg[j] = (unsigned char)i;
+    }
+    for (int i = p; i < N; i += kBlock) {
+        double c, s;
+        traj_pose_heading<DIM>(x + base * DIM, i, N, &c, &s);
+        shead[i][0] = c; shead[i][1] = s;
+    }
+    __syncthreads();
+
+    bool seed = p == 0;
+    int lo = 0, pstar = -1;                              // lo: the least reached p of the row before
+    for (int a = 0; a <= A; ++a) {
+        double qa[DIM + 2], qb[DIM + 2];
+        const int ia = sseg[a];
+#pragma unroll
+        for (int c = 0; c < DIM; ++c) qa[c] = sp[a][c];
+        qa[DIM] = shead[ia][0]; qa[DIM + 1] = shead[ia][1];
+        const double e0 = TB + (double)(a + p) * slot, e1 = TB + (double)(a + p + 1) * slot;
+        bool f = false;
+        // (row A needs no pause: a cell reached there by one has a reached cell of a smaller p before it)
+        if (a < A && p < P && p >= lo) f = retime_body_cell_free<DIM, true>(qa, qa, e0, e1, tab, n, bd, clearance);
+        const u64 S = __ballot(seed), F = __ballot(f);
+        if (lane == 0) { smask[a & 1][0][w] = S; smask[a & 1][1][w] = F; }
+        __syncthreads();                                 // (the other parity is free: every lane has passed the barrier after its reads)
+        u64 cin = 0, mine = 0, any = 0;
+        int first = -1;
+#pragma unroll
+        for (int q = 0; q < kBlock / 64; ++q) {
+            const u64 sq = smask[a & 1][0][q], fq = smask[a & 1][1][q];
+            u64 r = sq | cin, open = fq;
+#pragma unroll
+            for (int d = 1; d < 64; d <<= 1) {           // cells reached within 2 d - 1 pauses; open: d links in a row from here
+                r |= (r & open) << d;
+                open &= open >> d;
+            }
+            const u64 by_pause = ((r & fq) << 1) | cin;
+            if (q == w) {
+                mine = r;
+                if (lane == 0) spred[a][w] = press_on ? by_pause : sq;
+            }
+            if (first < 0 && r) first = q * 64 + (__ffsll(r) - 1);
+            any |= r;
+            cin = (r & fq) >> 63;
+        }
+        if (!any) break;                                 // (uniform) no cell of this row is reached: none of a later one
+        lo = first;
+        if (a == A) { pstar = first; break; }
+        const int ib = sseg[a + 1];
+#pragma unroll
+        for (int c = 0; c < DIM; ++c) qb[c] = sp[a + 1][c];
+        qb[DIM] = shead[ib][0]; qb[DIM + 1] = shead[ib][1];
+        seed = ((mine >> lane) & 1) ? retime_body_cell_free<DIM, false>(qa, qb, e0, e1, tab, n, bd, clearance) : false;
+    }
+    if (pstar < 0) {                                     // no schedule within P pauses
+        for (int k = p; k < kOwnLen; k += kBlock) oo[k] = -1;
+        if (p == 0) { ro[0] = 3; ro[1] = -1; ro[2] = -1; ro[3] = A; ro[4] = -1; }
+        return;
+    }
+    const int arrive = A + pstar;
+    for (int k = arrive + 1 + p; k < kOwnLen; k += kBlock) oo[k] = A;
+    __syncthreads();                                     // (spred is written)
+    if (p == 0) {
+        int a = A, pp = pstar, fp = -1;
+        oo[arrive] = A;
+        while (a > 0 || pp > 0) {
+            const bool bit = (spred[a][pp >> 6] >> (pp & 63)) & 1;
+            bool play = press_on ? !bit : bit;
+            if (a == 0) play = false;                    // (what the bits say there anyway; the walk ends whatever they hold)
+            else if (pp == 0) play = true;
+            if (play) --a;
+            else { --pp; fp = a + pp; }
+            oo[a + pp] = a;
+        }
+        ro[0] = pstar > 0 ? 1 : 0; ro[1] = arrive; ro[2] = pstar; ro[3] = A; ro[4] = fp;
+    }
+}
+
 }  // namespace
 
 int traj_check_opts(const TrajOpts& o) {
@@ -943,7 +1327,7 @@ int Trajectories::bind(int dev) {
         for (void* p : {(void*)d_in, (void*)d_x, (void*)d_instat, (void*)d_fres, (void*)d_ires, (void*)d_arc, (void*)d_tv, (void*)d_tt,
                         (void*)d_lim, (void*)d_tsum, (void*)d_tint, (void*)d_cu, (void*)d_chp, (void*)d_cclamp, (void*)d_follow,
                         (void*)d_chkd, (void*)d_chki, (void*)d_bodyd, (void*)d_bodyi, (void*)d_bresd,
-                        (void*)d_bresi, (void*)d_rres, (void*)d_rown})
+                        (void*)d_bresi, (void*)d_rres, (void*)d_rown, (void*)d_btd, (void*)d_bti, (void*)d_bst})
             (void)hipFree(p);
         if (own) (void)hipStreamDestroy(own);
     }
@@ -953,6 +1337,7 @@ int Trajectories::bind(int dev) {
     d_bodyd = nullptr; d_bodyi = nullptr; cap_body = 0;
     d_bresd = nullptr; d_bresi = nullptr; cap_bres = 0;
     d_rres = nullptr; d_rown = nullptr; cap_rt = 0;
+    d_btd = nullptr; d_bti = nullptr; cap_bt = 0; d_bst = nullptr; cap_bst = 0;
     cap_x = cap_m = cap_arc = cap_tn = cap_tm = cap_cu = cap_cm = 0;
     has_input = valid = timed = body_valid = retimed = false;
     m = N = dim = 0;
@@ -1317,6 +1702,7 @@ int Trajectories::retime(const Obstacles& ob, const RetimeOpts& o, double t_begi
     GPIS_HIP(hipStreamSynchronize(s));
     ropts = o;
     r_begin = t_begin;
+    r_body = 0;
     retime_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - c0).count();
     retimed = true;
     return GPIS_OK;
@@ -1413,6 +1799,105 @@ int Trajectories::retime_check(const Obstacles& ob, int steps, double clearance,
         if (first_hit) first_hit[r] = hi[3 * r + 1];
         if (collides) collides[r] = hi[3 * r + 2];
     }
+    return GPIS_OK;
+}
+
+// ---- the footprint against moving balls ---------------------------------------------------------------------------
+int Trajectories::body_time_check(const Obstacles& ob, const BodyArgs& bd, bool sched, double dt, int steps, double t0, double TB,
+                                  double clearance, double* min_sep, double* min_time, int* min_obstacle, int* min_ball, int* first_hit,
+                                  int* collides) {
+    if ((size_t)m > cap_bt) {
+        (void)hipFree(d_btd); (void)hipFree(d_bti);
+        d_btd = nullptr; d_bti = nullptr; cap_bt = 0;
+        GPIS_HIP(hipMalloc((void**)&d_btd, sizeof(double) * 2 * (size_t)m));
+        GPIS_HIP(hipMalloc((void**)&d_bti, sizeof(int) * 4 * (size_t)m));
+        cap_bt = (size_t)m;
+    }
+    const TrajSched sc{d_rres, d_rown, 0};
+#define GPIS_BODY_CHECK(D, S)                                                                                                          \
+    hipLaunchKernelGGL((traj_body_time_check_kernel<D, S>), dim3((unsigned)m), dim3(kBlock), 0, own, d_x, d_tv, d_tt, d_tint, N, steps, dt, \
+                       t0, TB, clearance, (const double*)ob.d_tab, ob.n, bd, d_btd, d_bti, sc)
+    if (dim == 2) { if (sched) GPIS_BODY_CHECK(2, 1); else GPIS_BODY_CHECK(2, 0); }
+    else { if (sched) GPIS_BODY_CHECK(3, 1); else GPIS_BODY_CHECK(3, 0); }
+#undef GPIS_BODY_CHECK
+    GPIS_HIP(hipGetLastError());
+    std::vector<double> hd(2 * (size_t)m);
+    std::vector<int> hi(4 * (size_t)m);
+    GPIS_HIP(hipMemcpyAsync(hd.data(), d_btd, sizeof(double) * hd.size(), hipMemcpyDeviceToHost, own));
+    GPIS_HIP(hipMemcpyAsync(hi.data(), d_bti, sizeof(int) * hi.size(), hipMemcpyDeviceToHost, own));
+    GPIS_HIP(hipStreamSynchronize(own));
+    for (size_t r = 0; r < (size_t)m; ++r) {
+        if (min_sep) min_sep[r] = hd[2 * r];
+        if (min_time) min_time[r] = hd[2 * r + 1];
+        if (min_obstacle) min_obstacle[r] = hi[4 * r];
+        if (first_hit) first_hit[r] = hi[4 * r + 1];
+        if (collides) collides[r] = hi[4 * r + 2];
+        if (min_ball) min_ball[r] = hi[4 * r + 3];
+    }
+    return GPIS_OK;
+}
+
+int Trajectories::check_body_obst(const Obstacles& ob, const BodyArgs& bd, double dt, int steps, double t0, double t_begin,
+                                  double clearance, double* min_sep, double* min_time, int* min_obstacle, int* min_ball, int* first_hit,
+                                  int* collides) {
+    if (!has_timing()) return GPIS_ERR_STATE;
+    return body_time_check(ob, bd, false, dt, steps, t0, t_begin - ob.epoch, clearance, min_sep, min_time, min_obstacle, min_ball,
+                           first_hit, collides);
+}
+
+int Trajectories::retime_body_check(const Obstacles& ob, const BodyArgs& bd, int steps, double clearance, double* min_sep,
+                                    double* min_time, int* min_obstacle, int* min_ball, int* first_hit, int* collides) {
+    if (!has_schedule()) return GPIS_ERR_STATE;
+    return body_time_check(ob, bd, true, ropts.slot, steps, 0.0, r_begin - ob.epoch, clearance, min_sep, min_time, min_obstacle,
+                           min_ball, first_hit, collides);
+}
+
+int Trajectories::retime_body(const Obstacles& ob, const BodyArgs& bd, const RetimeOpts& o, double t_begin, hipStream_t s) {
+    if (!has_timing()) return GPIS_ERR_STATE;
+    const auto c0 = std::chrono::steady_clock::now();
+    if (!s) s = own;
+    retimed = false;
+    if ((size_t)m > cap_rt) {
+        (void)hipFree(d_rres); (void)hipFree(d_rown);
+        d_rres = nullptr; d_rown = nullptr; cap_rt = 0;
+        GPIS_HIP(hipMalloc((void**)&d_rres, sizeof(int) * kSchedRes * (size_t)m));
+        GPIS_HIP(hipMalloc((void**)&d_rown, sizeof(int) * kOwnLen * (size_t)m));
+        cap_rt = (size_t)m;
+    }
+    const double TB = t_begin - ob.epoch;
+    if (dim == 2)
+        hipLaunchKernelGGL(traj_body_retime_kernel<2>, dim3((unsigned)m), dim3(kBlock), 0, s, d_x, d_tv, d_tt, d_tint, N, o.slot,
+                           o.max_pause, o.clearance, o.press_on, TB, (const double*)ob.d_tab, ob.n, bd, d_rres, d_rown);
+    else
+        hipLaunchKernelGGL(traj_body_retime_kernel<3>, dim3((unsigned)m), dim3(kBlock), 0, s, d_x, d_tv, d_tt, d_tint, N, o.slot,
+                           o.max_pause, o.clearance, o.press_on, TB, (const double*)ob.d_tab, ob.n, bd, d_rres, d_rown);
+    GPIS_HIP(hipGetLastError());
+    h_rres.resize(kSchedRes * (size_t)m);
+    GPIS_HIP(hipMemcpyAsync(h_rres.data(), d_rres, sizeof(int) * h_rres.size(), hipMemcpyDeviceToHost, s));
+    GPIS_HIP(hipStreamSynchronize(s));
+    ropts = o;
+    r_begin = t_begin;
+    r_body = bd.m;
+    retime_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - c0).count();
+    retimed = true;
+    return GPIS_OK;
+}
+
+int Trajectories::timed_states(double dt, int steps, double t0, bool sched, double* states) {
+    if (sched ? !has_schedule() : !has_timing()) return GPIS_ERR_STATE;
+    const size_t cnt = (size_t)m * (steps + 1) * (dim + 2);
+    if (int rc = grow(d_bst, cap_bst, cnt)) return rc;
+    const TrajSched sc{d_rres, d_rown, 0};
+    if (sched) dt = ropts.slot;
+#define GPIS_BODY_STATES(D, S)                                                                                                         \
+    hipLaunchKernelGGL((traj_body_states_kernel<D, S>), dim3((unsigned)m), dim3(kBlock), 0, own, d_x, d_tv, d_tt, d_tint, N, steps, dt, t0, \
+                       d_bst, sc)
+    if (dim == 2) { if (sched) GPIS_BODY_STATES(2, 1); else GPIS_BODY_STATES(2, 0); }
+    else { if (sched) GPIS_BODY_STATES(3, 1); else GPIS_BODY_STATES(3, 0); }
+#undef GPIS_BODY_STATES
+    GPIS_HIP(hipGetLastError());
+    if (states) GPIS_HIP(hipMemcpyAsync(states, d_bst, sizeof(double) * cnt, hipMemcpyDeviceToHost, own));
+    GPIS_HIP(hipStreamSynchronize(own));
     return GPIS_OK;
 }
 

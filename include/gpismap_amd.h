@@ -1195,6 +1195,48 @@ int   gpis_smooth_body_optimize(void* traj, void* df, void* body, const gpis_tra
 int   gpis_smooth_body_get(void* traj, double* D_min, int* waypoint, int* ball, int* collides);
 int   gpis_smooth_from_pose_paths(void* traj, void* pplan, int N);
 
+/* ---- the footprint in the moving-obstacle check and in re-timing ---------------------------------------------
+ * gpis_obst_check_timing and gpis_retime_* certify a timed trajectory for a point.  The entries below do it for a footprint
+ * (m >= 1).  tests/body_time_ref.py states every rule in numpy.  All arithmetic is double, left to right, nothing contracted,
+ * with IEEE / and sqrt.
+ *  - The timed pose.  For a trajectory of timing status 0 and tau >= 0: p(tau) is gpis_timing_controls' timed position, bit for
+ *    bit; i(tau) is the segment index that position's bisection ends on (the largest i <= N-2 with t_i <= tau), and N-1 for
+ *    tau >= t[N-1]; the heading (c, s)(tau) is gpis_body_traj_clearance's chord rule at waypoint i(tau), in double on the float32
+ *    waypoints: the chord is horizontal, searched forward from min(i, N-2), then backward, and with no usable chord the heading
+ *    is (1, 0).  The body holds its segment's heading; it turns at knots.
+ *  - Ball positions.  w_j(tau) = the body rule's position of ball j at (p, c, s)(tau): w0 = p0 + (c b0 - s b1),
+ *    w1 = p1 + (s b0 + c b1), w2 = p2 + b2, in double with no float32 cast.  No field is sampled.
+ *  - The separation of one interval.  For the poses at tau_k and tau_{k+1}, body ball j and moving ball i it is
+ *    gpis_obst_check_timing's expression with p_k := w_j(tau_k) and p_{k+1} - p_k := w_j(tau_{k+1}) - w_j(tau_k), then
+ *    sep = (sqrt(s2) - r_i) - rho_j.  Between two samples a body ball's centre moves on the chord of its arc (an approximation
+ *    where the heading turns inside the interval).  With the one-ball zero footprint every output below has the
+ *    point call's bits.
+ * gpis_timed_body_check is gpis_obst_check_timing with that separation over k, i, j ascending: min_sep is the least sep by a
+ * strict comparison from +inf (ties: the smallest (k, i, j)), min_time and min_obstacle as before, min_ball = j, first_hit = the
+ * least k with some sep < clearance; a NaN sep is not below the clearance.  n = 0 and untimed rows answer as the point call does,
+ * with min_ball = -1.
+ * gpis_timed_body_retime is gpis_retime_solve's dynamic programme with pause_free[a][p] iff no (i, j) has sep < clearance with
+ * the pose of own slot a held (every ball's displacement 0) and play_free[a][p] iff none has going from the pose of own slot a to
+ * that of a + 1, both at real slot a + p.  A, the status codes, p*, the walk with press_on, the own table and n = 0 are
+ * gpis_retime_solve's, and the schedule is stored where gpis_retime_solve stores it: gpis_retime_get, gpis_retime_controls and
+ * gpis_retime_follow read it unchanged.  gpis_timed_body_info: out[0] = the number of body balls of the last solve (0 after
+ * gpis_retime_solve).
+ * gpis_timed_body_retime_check is gpis_retime_check with the pose of own(k) at real slot k and the footprint given to it.  The
+ * certificate: with the solve's set, footprint and clearance and steps <= arrive, a schedule of status 0 or 1 has collides = 0
+ * and min_sep >= clearance.
+ * gpis_timed_body_states: the timed poses (p, c, s) as states_out[m][steps + 1][dim + 2] (gpis_body_clearance's layout) at
+ * t0 + k dt, or with retimed = 1 at own(k) of the last schedule with dt = its slot (dt and t0 are not read); rows without a
+ * timing or a schedule are NaN.  1 <= steps <= 4096.
+ * Errors, each before anything is written or dropped: whatever the point forms refuse; a NULL footprint, one with m = 0, one of
+ * another dim or on another device than the trajectories -> GPIS_ERR_ARG. */
+int   gpis_timed_body_check(void* traj, void* obst, void* body, double dt, int steps, double t0, double t_begin, double clearance,
+                             double* min_sep, double* min_time, int* min_obstacle, int* min_ball, int* first_hit, int* collides);
+int   gpis_timed_body_retime(void* traj, void* obst, void* body, double t_begin, const gpis_retime_opts* opts, void* hip_stream);
+int   gpis_timed_body_info(void* traj, double* out, int n);
+int   gpis_timed_body_retime_check(void* traj, void* obst, void* body, int steps, double clearance, double* min_sep, double* min_time,
+                             int* min_obstacle, int* min_ball, int* first_hit, int* collides);
+int   gpis_timed_body_states(void* traj, double dt, int steps, double t0, int retimed, double* states_out);
+
 /* ---- routes for the robot's footprint: heading layers in the planner ---------------------------------------
  * gpis_plan_solve plans for a point with one scalar clearance; a long narrow robot has no right scalar.  The pose planner is
  * the same solver on the lattice nx x ny x H of poses (x, y, heading) of a 2-D field, H in {8, 16, 32, 64}: state s = (i, j, h)
