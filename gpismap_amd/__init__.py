@@ -73,6 +73,12 @@ class gpis_plan_opts(C.Structure):
                 ("max_rounds", C.c_int)]
 
 
+class gpis_tplan_opts(C.Structure):
+    _fields_ = [("clearance", C.c_float), ("margin", C.c_float), ("gain", C.c_float), ("connectivity", C.c_int),
+                ("slot", C.c_double), ("horizon", C.c_int), ("dyn_clearance", C.c_double), ("wait", C.c_float),
+                ("keep_cost", C.c_int)]
+
+
 class gpis_pplan_opts(C.Structure):
     _fields_ = [("clearance", C.c_float), ("margin", C.c_float), ("gain", C.c_float), ("turn", C.c_float), ("max_rounds", C.c_int)]
 
@@ -381,6 +387,23 @@ def lib():
         L.gpis_retime_controls.argtypes = [vp, C.c_int, C.c_int, d, d, dp, dp, dp, ip]
         L.gpis_retime_follow.argtypes = [vp, vp, C.c_int, C.c_int, d, d, dp, dp]
         L.gpis_retime_check.argtypes = [vp, vp, C.c_int, d, dp, dp, ip, ip, ip]
+    if hasattr(L, "gpis_tplan_create"):
+        to, ub, ll = C.POINTER(gpis_tplan_opts), C.POINTER(C.c_ubyte), C.POINTER(C.c_longlong)
+        L.gpis_tplan_default_opts.argtypes = [C.c_float, to]
+        L.gpis_tplan_check_opts.argtypes = [to, C.c_int, C.c_int]
+        L.gpis_tplan_create.restype = vp
+        L.gpis_tplan_create.argtypes = []
+        L.gpis_tplan_destroy.argtypes = [vp]
+        L.gpis_tplan_solve.argtypes = [vp, vp, vp, fp, C.c_int, d, to, vp]
+        L.gpis_tplan_info.argtypes = [vp, dp, C.c_int]
+        L.gpis_tplan_get.argtypes = [vp, fp, ub, fp, fp]
+        L.gpis_tplan_device.argtypes = [vp, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
+        L.gpis_tplan_paths.argtypes = [vp, fp, C.c_int, vp]
+        L.gpis_tplan_path_counts.argtypes = [vp, ll, ll]
+        L.gpis_tplan_get_paths.argtypes = [vp, ll, fp, ip, fp, ub]
+        L.gpis_tplan_check.argtypes = [vp, vp, d, dp, dp, ip, ip, ip]
+        L.gpis_tplan_controls.argtypes = [vp, C.c_int, C.c_int, d, d, dp, dp, dp, ip]
+        L.gpis_tplan_set_schedule.argtypes = [vp, C.c_int, C.c_int]
     if hasattr(L, "gpis_body_create"):
         L.gpis_body_create.restype = vp
         L.gpis_body_create.argtypes = []
@@ -1363,6 +1386,17 @@ class DistanceField:
         p = planner if planner is not None else self._own_planner()
         return p.solve(self, goals, **opts)
 
+    def plan_timed(self, goals, obstacles=None, t_begin=0.0, time_planner=None, **opts):
+        """A plan through space and time over this 2-D field's free space towards `goals` [g, 2] around the moving balls of
+        `obstacles` (an Obstacles, or None) from absolute time t_begin on (gpis_tplan_solve).  opts: the gpis_tplan_opts fields
+        (clearance, margin, gain, connectivity, slot, horizon, dyn_clearance, wait, keep_cost).  Returns the TimePlanner holding
+        the result (default: one kept by this field); it stays valid when the field or the set changes."""
+        if time_planner is None:
+            if getattr(self, "_time_planner", None) is None:
+                self._time_planner = TimePlanner()
+            time_planner = self._time_planner
+        return time_planner.solve(self, goals, obstacles, t_begin, **opts)
+
     def plan_poses(self, footprint, goals, H=16, moves="any", pose_planner=None, **opts):
         """Cost-to-go and policy over poses (x, y, heading index) of this 2-D field for `footprint` towards `goals` [g, 3] or
         [g, 2] (gpis_pplan_solve): routes the body fits through, where plan() routes a point.  opts: the gpis_pplan_opts
@@ -1656,6 +1690,153 @@ class Planner:
         holding the input (default: a new one), ready for optimize()."""
         t = trajectories if trajectories is not None else Trajectories()
         return t.from_paths(self, N)
+
+
+def tplan_opts(step, **opts):
+    """gpis_tplan_opts of the library's defaults for a field of lattice step `step` (gpis_tplan_default_opts; needs no device)
+    with the given fields replaced."""
+    o = gpis_tplan_opts()
+    _check(lib().gpis_tplan_default_opts(float(step), C.byref(o)), "gpis_tplan_default_opts")
+    names = {f[0] for f in gpis_tplan_opts._fields_}
+    for k, v in opts.items():
+        if k not in names:
+            raise GpisError("unknown time-plan option %r" % k)
+        setattr(o, k, v)
+    return o
+
+
+class TimePlanner:
+    """Result holder of the planner through space and time (gpis_tplan_*): a policy byte per (lattice point, slot), the cost of
+    slot 0, paths, their check against moving balls and their control sequences, on the device; buffers reused across calls.
+    A finished plan depends neither on the field nor on the set it was solved with."""
+
+    INFO_KEYS = ("valid", "nx", "ny", "horizon", "slot", "balls", "goals", "goals_kept", "free", "finite0", "layer_launches",
+                 "skipped", "solve_ms", "max_cost0", "t_begin", "keep_cost")
+    INT_KEYS = ("valid", "nx", "ny", "horizon", "balls", "goals", "goals_kept", "free", "finite0", "layer_launches", "skipped",
+                "keep_cost")
+
+    def __init__(self):
+        self.L = lib()
+        if not hasattr(self.L, "gpis_tplan_create"):
+            raise GpisError("the native library has no time planner (gpis_tplan_create)")
+        if self.L.gpis_device_count() < 1:
+            raise GpisError("no HIP device: gpismap_amd has no CPU fallback")
+        self.h = C.c_void_p(self.L.gpis_tplan_create())
+        if not self.h:
+            raise GpisError("gpis_tplan_create failed")
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.gpis_tplan_destroy(self.h)
+            self.h = None
+
+    __del__ = close
+
+    def set_schedule(self, layers_per_launch=0, cull=1):
+        """Layers a launch advances (0 = the default: 4 without balls, 1 with them; at most 16) and the broad phase over the balls (0 / 1); the results do not
+        depend on either."""
+        _check(self.L.gpis_tplan_set_schedule(self.h, int(layers_per_launch), int(cull)), "gpis_tplan_set_schedule")
+        return self
+
+    def solve(self, field, goals, obstacles=None, t_begin=0.0, stream=0, **opts):
+        """gpis_tplan_solve on a 2-D DistanceField holding a result; goals [g, 2]; obstacles: an Obstacles or None.  Returns
+        self."""
+        inf = field.info()
+        if inf["dim"] == 0:
+            raise GpisError("distance field holds no result")
+        g = np.ascontiguousarray(goals, dtype=np.float32).reshape(-1, 2)
+        o = tplan_opts(inf["step"], **opts)
+        _check(self.L.gpis_tplan_solve(self.h, field.h, obstacles.h if obstacles is not None else None, _p(g), g.shape[0],
+                                       float(t_begin), C.byref(o), C.c_void_p(stream)), "gpis_tplan_solve")
+        self.dyn_clearance = float(o.dyn_clearance)
+        return self
+
+    def info(self):
+        out = np.zeros(len(self.INFO_KEYS), dtype=np.float64)
+        _check(self.L.gpis_tplan_info(self.h, _p(out, C.c_double), out.size), "gpis_tplan_info")
+        d = dict(zip(self.INFO_KEYS, out.tolist()))
+        for k in self.INT_KEYS:
+            d[k] = int(d[k])
+        return d
+
+    def get(self, cost_all=False):
+        """dict(cost0 f32 [ny, nx], policy u8 [S + 1, ny, nx], c f32 [ny, nx]) host copies of the last result, with cost_all
+        f32 [S + 1, ny, nx] on request (the solve must have kept it)."""
+        i = self.info()
+        if not i["valid"]:
+            raise GpisError("time planner holds no result")
+        ny, nx, S = i["ny"], i["nx"], i["horizon"]
+        cost0, c = np.zeros((ny, nx), np.float32), np.zeros((ny, nx), np.float32)
+        pol = np.zeros((S + 1, ny, nx), np.uint8)
+        call = np.zeros((S + 1, ny, nx), np.float32) if cost_all else None
+        _check(self.L.gpis_tplan_get(self.h, _p(cost0), _p(pol, C.c_ubyte), _p(call) if cost_all else None, _p(c)), "gpis_tplan_get")
+        out = dict(cost0=cost0, policy=pol, c=c)
+        if cost_all:
+            out["cost_all"] = call
+        return out
+
+    def device_ptrs(self):
+        """(d_cost0, d_policy) device addresses of the last result (0 where there is none)."""
+        a, b = C.c_void_p(0), C.c_void_p(0)
+        _check(self.L.gpis_tplan_device(self.h, C.byref(a), C.byref(b)), "gpis_tplan_device")
+        return a.value or 0, b.value or 0
+
+    def paths(self, starts, stream=0):
+        """Routes from `starts` [m, 2] at slot 0 along the policy (gpis_tplan_paths).  Returns dict(paths: list of [arrive + 1,
+        2] float32 arrays, one point per slot; off i64 [m + 1]; points f32 [total, 2]; arrive i32 [m]; start_cost f32 [m];
+        status u8 [m]: 0 arrived, 1 outside / non-finite, 2 not free, 3 no arrival within the horizon)."""
+        x = np.ascontiguousarray(starts, dtype=np.float32).reshape(-1, 2)
+        _check(self.L.gpis_tplan_paths(self.h, _p(x), x.shape[0], C.c_void_p(stream)), "gpis_tplan_paths")
+        m, tot = C.c_longlong(0), C.c_longlong(0)
+        _check(self.L.gpis_tplan_path_counts(self.h, C.byref(m), C.byref(tot)), "gpis_tplan_path_counts")
+        off = np.zeros(m.value + 1, np.int64)
+        pts = np.zeros((max(tot.value, 1), 2), np.float32)
+        arrive = np.zeros(m.value, np.int32)
+        sc = np.zeros(m.value, np.float32)
+        st = np.zeros(m.value, np.uint8)
+        _check(self.L.gpis_tplan_get_paths(self.h, _p(off, C.c_longlong), _p(pts), _p(arrive, C.c_int), _p(sc), _p(st, C.c_ubyte)),
+               "gpis_tplan_get_paths")
+        pts = pts[:tot.value]
+        return dict(paths=[pts[off[k]:off[k + 1]] for k in range(m.value)], off=off, points=pts, arrive=arrive, start_cost=sc, status=st)
+
+    def _npaths(self):
+        m = C.c_longlong(0)
+        _check(self.L.gpis_tplan_path_counts(self.h, C.byref(m), None), "gpis_tplan_path_counts")
+        return m.value
+
+    def check(self, obstacles, clearance=None):
+        """The last paths against the balls of `obstacles` (any 2-D set: the solve's, or a newer detection) at the solve's
+        t_begin and slot (gpis_tplan_check): dict(min_sep, min_time f64 [m], min_obstacle, first_hit, collides i32 [m]).
+        clearance None: the last solve's dyn_clearance."""
+        m = self._npaths()
+        if clearance is None:
+            clearance = self.dyn_clearance
+        ms, mt = np.zeros(m, np.float64), np.zeros(m, np.float64)
+        mo, fh, co = np.zeros(m, np.int32), np.zeros(m, np.int32), np.zeros(m, np.int32)
+        _check(self.L.gpis_tplan_check(self.h, obstacles.h, float(clearance), _p(ms, C.c_double), _p(mt, C.c_double), _p(mo, C.c_int),
+                                       _p(fh, C.c_int), _p(co, C.c_int)), "gpis_tplan_check")
+        return dict(min_sep=ms, min_time=mt, min_obstacle=mo, first_hit=fh, collides=co)
+
+    def controls(self, T, k0=0, w_limit=0.0, min_move=1e-9):
+        """Control sequences of T steps of the plan's slot along the last paths from slot k0 on (gpis_tplan_controls): dict(U
+        f64 [m, T, 2], heading0 [m, 2], p0 [m, 2], clamped i32 [m]); a start without a path stands still."""
+        m, T = self._npaths(), int(T)
+        U = np.zeros((m, max(T, 1), 2), np.float64)
+        h0, p0, cl = np.zeros((m, 2), np.float64), np.zeros((m, 2), np.float64), np.zeros(m, np.int32)
+        _check(self.L.gpis_tplan_controls(self.h, T, int(k0), float(w_limit), float(min_move), _p(U, C.c_double), _p(h0, C.c_double),
+                                          _p(p0, C.c_double), _p(cl, C.c_int)), "gpis_tplan_controls")
+        return dict(U=U, heading0=h0, p0=p0, clamped=cl)
+
+    def follow(self, controller, index, k0=0, w_limit=0.0, min_move=1e-9):
+        """Replace `controller`'s nominal sequence by the control sequence of path `index` from slot k0 on, over the controller's
+        horizon (controls + gpis_mppi_set_nominal; the controller is meant to run at dt = the plan's slot).  Returns (p0 [2],
+        heading0 [2])."""
+        i = controller.info()
+        if not i["inited"] or i["dim"] != 2:
+            raise GpisError("follow needs a 2-D controller after init")
+        r = self.controls(i["horizon"], k0, w_limit, min_move)
+        controller.set_nominal(r["U"][int(index)])
+        return r["p0"][int(index)].copy(), r["heading0"][int(index)].copy()
 
 
 POSE_HEADINGS = (8, 16, 32, 64)

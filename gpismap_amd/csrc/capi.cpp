@@ -16,6 +16,7 @@
 #include "pf.h"
 #include "plan.h"
 #include "pplan.h"
+#include "tplan.h"
 #include "traj.h"
 #include "mppi.h"
 #include "obst.h"
@@ -2531,6 +2532,163 @@ int gpis_pplan_project(void* pplan, void* plan, unsigned char* heading2) {
         if (rc != GPIS_OK) q.clear_result();
         return rc;
     } catch (...) { q.clear_result(); return GPIS_ERR_STATE; }
+}
+
+// ---- planning through space and time around moving balls -----------------------------------------------------------------------
+int gpis_tplan_default_opts(float step, gpis_tplan_opts* o) {
+    if (!o || !(std::isfinite(step) && step > 0.f)) return GPIS_ERR_ARG;
+    o->clearance = 0.f; o->margin = 4.f * step; o->gain = 4.f; o->connectivity = 1;
+    o->slot = 0.1; o->horizon = 256; o->dyn_clearance = (double)step; o->wait = 0.5f; o->keep_cost = 0;
+    return GPIS_OK;
+}
+static TimePlanOpts tplan_opts_of(const gpis_tplan_opts* opts) {
+    TimePlanOpts o;
+    o.clearance = opts->clearance; o.margin = opts->margin; o.gain = opts->gain; o.connectivity = opts->connectivity;
+    o.slot = opts->slot; o.horizon = opts->horizon; o.dyn_clearance = opts->dyn_clearance; o.wait = opts->wait;
+    o.keep_cost = opts->keep_cost;
+    return o;
+}
+static int tplan_check_size(long long points, const TimePlanOpts& o) {
+    return points * (long long)(o.horizon + 1) > (o.keep_cost ? TimePlanner::kMaxStatesKept : TimePlanner::kMaxStates) ? GPIS_ERR_LIMIT
+                                                                                                                      : GPIS_OK;
+}
+int gpis_tplan_check_opts(const gpis_tplan_opts* opts, int nx, int ny) {
+    if (!opts || nx < 0 || ny < 0) return GPIS_ERR_ARG;
+    const TimePlanOpts o = tplan_opts_of(opts);
+    if (int rc = tplan_check_opts(o)) return rc;
+    return tplan_check_size((long long)nx * ny, o);
+}
+void* gpis_tplan_create(void) {
+    if (gpis_device_count() < 1) { fprintf(stderr, "[gpismap_amd] no HIP device\n"); return nullptr; }
+    TimePlanner* p = new (std::nothrow) TimePlanner();
+    if (p && !p->own) { delete p; return nullptr; }
+    return p;
+}
+void gpis_tplan_destroy(void* tplan) { delete (TimePlanner*)tplan; }
+int gpis_tplan_set_schedule(void* tplan, int layers_per_launch, int cull) {
+    if (!tplan || layers_per_launch < 0 || layers_per_launch > TimePlanner::kMaxLayers || (cull != 0 && cull != 1)) return GPIS_ERR_ARG;
+    TimePlanner& p = *(TimePlanner*)tplan;
+    p.layers_per_launch = layers_per_launch;
+    p.cull = cull;
+    return GPIS_OK;
+}
+// every check comes before anything is written: such an error leaves the previous result readable
+int gpis_tplan_solve(void* tplan, void* d, void* obst, const float* goals, int ngoals, double t_begin, const gpis_tplan_opts* opts,
+                     void* stream) {
+    if (!tplan || !d || !goals || ngoals < 1 || !std::isfinite(t_begin)) return GPIS_ERR_ARG;
+    const DistanceField& df = *(const DistanceField*)d;
+    gpis_tplan_opts dflt;
+    if (!opts) {
+        if (!df.valid) return GPIS_ERR_STATE;
+        (void)gpis_tplan_default_opts(df.step, &dflt);
+        opts = &dflt;
+    }
+    const TimePlanOpts o = tplan_opts_of(opts);
+    if (int rc = tplan_check_opts(o)) return rc;
+    if (!df.valid) return GPIS_ERR_STATE;
+    if (df.dim != 2) return GPIS_ERR_ARG;
+    const Obstacles* ob = (const Obstacles*)obst;
+    if (ob && (ob->device != df.device || (ob->inited && ob->n > 0 && ob->dim != 2))) return GPIS_ERR_ARG;
+    if (int rc = tplan_check_size(df.ngrid, o)) return rc;
+    TimePlanner& p = *(TimePlanner*)tplan;
+    DeviceScope ds(df.device);
+    try {
+        if (int rc = p.bind(df.device)) { p.clear_result(); return rc; }
+        const int rc = p.solve(df, ob, goals, ngoals, t_begin, o, stream ? (hipStream_t)stream : df.own);
+        if (rc != GPIS_OK) p.clear_result();
+        return rc;
+    } catch (...) { p.clear_result(); return GPIS_ERR_STATE; }
+}
+int gpis_tplan_info(void* tplan, double* out, int n) {
+    if (!tplan || !out || n < 0) return GPIS_ERR_ARG;
+    const TimePlanner& p = *(TimePlanner*)tplan;
+    const bool v = p.valid;
+    const double w[16] = {v ? 1.0 : 0.0, v ? (double)p.nx : 0.0, v ? (double)p.ny : 0.0, v ? (double)p.S : 0.0, v ? p.opts.slot : 0.0,
+                          (double)p.n, (double)p.goals_given, (double)p.goals_kept, (double)p.nfree, (double)p.nfinite,
+                          (double)p.launches, (double)p.skipped, p.solve_ms, (double)p.max_cost0, p.t_begin, p.kept ? 1.0 : 0.0};
+    for (int i = 0; i < n && i < 16; ++i) out[i] = w[i];
+    return GPIS_OK;
+}
+int gpis_tplan_get(void* tplan, float* cost0, unsigned char* policy, float* cost_all, float* c) {
+    if (!tplan) return GPIS_ERR_ARG;
+    TimePlanner& p = *(TimePlanner*)tplan;
+    if (!p.valid || (cost_all && !p.kept)) return GPIS_ERR_STATE;
+    DeviceScope ds(p.device);
+    const size_t n = (size_t)p.np, ns = n * (size_t)(p.S + 1);
+    if (cost0) GPIS_HIP(hipMemcpyAsync(cost0, p.d_cost0, sizeof(float) * n, hipMemcpyDeviceToHost, p.own));
+    if (policy) GPIS_HIP(hipMemcpyAsync(policy, p.d_policy, ns, hipMemcpyDeviceToHost, p.own));
+    if (cost_all) GPIS_HIP(hipMemcpyAsync(cost_all, p.d_all, sizeof(float) * ns, hipMemcpyDeviceToHost, p.own));
+    if (c) GPIS_HIP(hipMemcpyAsync(c, p.d_c, sizeof(float) * n, hipMemcpyDeviceToHost, p.own));
+    GPIS_HIP(hipStreamSynchronize(p.own));
+    return GPIS_OK;
+}
+int gpis_tplan_device(void* tplan, const float** d_cost0, const unsigned char** d_policy) {
+    if (!tplan) return GPIS_ERR_ARG;
+    const TimePlanner& p = *(TimePlanner*)tplan;
+    if (d_cost0) *d_cost0 = p.valid ? p.d_cost0 : nullptr;
+    if (d_policy) *d_policy = p.valid ? p.d_policy : nullptr;
+    return GPIS_OK;
+}
+int gpis_tplan_paths(void* tplan, const float* starts, int m, void* stream) {
+    if (!tplan || !starts || m < 1) return GPIS_ERR_ARG;
+    TimePlanner& p = *(TimePlanner*)tplan;
+    if (!p.valid) return GPIS_ERR_STATE;
+    if (m > TimePlanner::kMaxStarts) return GPIS_ERR_LIMIT;
+    DeviceScope ds(p.device);
+    try {
+        const int rc = p.paths(starts, m, stream ? (hipStream_t)stream : p.own);
+        if (rc != GPIS_OK) p.paths_valid = false;
+        return rc;
+    } catch (...) { p.paths_valid = false; return GPIS_ERR_STATE; }
+}
+int gpis_tplan_path_counts(void* tplan, long long* npaths, long long* npoints) {
+    if (!tplan) return GPIS_ERR_ARG;
+    const TimePlanner& p = *(TimePlanner*)tplan;
+    if (!p.valid || !p.paths_valid) return GPIS_ERR_STATE;
+    if (npaths) *npaths = p.npaths;
+    if (npoints) *npoints = p.npoints;
+    return GPIS_OK;
+}
+int gpis_tplan_get_paths(void* tplan, long long* off, float* points, int* arrive, float* start_cost, unsigned char* status) {
+    if (!tplan) return GPIS_ERR_ARG;
+    TimePlanner& p = *(TimePlanner*)tplan;
+    if (!p.valid || !p.paths_valid) return GPIS_ERR_STATE;
+    DeviceScope ds(p.device);
+    const size_t m = (size_t)p.npaths;
+    std::vector<long long> ho(m + 1);
+    std::vector<unsigned char> hs(m);
+    GPIS_HIP(hipMemcpyAsync(ho.data(), p.d_off, sizeof(long long) * (m + 1), hipMemcpyDeviceToHost, p.own));
+    GPIS_HIP(hipMemcpyAsync(hs.data(), p.d_status, m, hipMemcpyDeviceToHost, p.own));
+    if (points && p.npoints > 0)
+        GPIS_HIP(hipMemcpyAsync(points, p.d_points, sizeof(float) * (size_t)p.npoints * 2, hipMemcpyDeviceToHost, p.own));
+    if (start_cost) GPIS_HIP(hipMemcpyAsync(start_cost, p.d_scost, sizeof(float) * m, hipMemcpyDeviceToHost, p.own));
+    GPIS_HIP(hipStreamSynchronize(p.own));
+    for (size_t k = 0; k < m; ++k) {
+        if (off) off[k] = ho[k];
+        if (status) status[k] = hs[k];
+        if (arrive) arrive[k] = hs[k] == 0 ? (int)(ho[k + 1] - ho[k]) - 1 : -1;
+    }
+    if (off) off[m] = ho[m];
+    return GPIS_OK;
+}
+int gpis_tplan_check(void* tplan, void* obst, double clearance, double* min_sep, double* min_time, int* min_obstacle, int* first_hit,
+                     int* collides) {
+    if (!tplan || !obst || !std::isfinite(clearance) || clearance < 0.0) return GPIS_ERR_ARG;
+    TimePlanner& p = *(TimePlanner*)tplan;
+    const Obstacles& b = *(const Obstacles*)obst;
+    if (!p.valid || !p.paths_valid) return GPIS_ERR_STATE;
+    if (b.device != p.device || (b.inited && b.n > 0 && b.dim != 2)) return GPIS_ERR_ARG;
+    DeviceScope ds(p.device);
+    try { return p.check(b, clearance, min_sep, min_time, min_obstacle, first_hit, collides); } catch (...) { return GPIS_ERR_STATE; }
+}
+int gpis_tplan_controls(void* tplan, int T, int k0, double w_limit, double min_move, double* U, double* heading0, double* p0,
+                        int* clamped) {
+    if (!tplan || k0 < 0 || k0 > (1 << 20) || T < 1 || T > TimePlanner::kMaxT) return GPIS_ERR_ARG;
+    if (!std::isfinite(w_limit) || !std::isfinite(min_move) || w_limit < 0.0 || min_move < 0.0) return GPIS_ERR_ARG;
+    TimePlanner& p = *(TimePlanner*)tplan;
+    if (!p.valid || !p.paths_valid) return GPIS_ERR_STATE;
+    DeviceScope ds(p.device);
+    try { return p.controls(T, k0, w_limit, min_move, U, heading0, p0, clamped); } catch (...) { return GPIS_ERR_STATE; }
 }
 
 }  // extern "C"

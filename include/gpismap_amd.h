@@ -1499,6 +1499,75 @@ int   gpis_detect_to_obstacles(void* det, void* obst);
  * the set-up, the flags, the compaction, the labelling, the table */
 int   gpis_detect_info(void* det, double* out, int n);
 
+/* ---- planning through space and time around moving balls (the contract: tests/tplan_ref.py) ----------------
+ * gpis_plan_solve plans through the static field and gpis_retime_solve can only wait on a fixed geometry; gpis_tplan_solve
+ * plans on the time-expanded lattice (lattice point x real slot) of a 2-D field, so a route may wait or go another way.
+ * Static part: gpis_plan_solve's, bit for bit (point cost c, free iff c > 0, the translations with codes 9 .. 17 without 13,
+ * connectivity, no corner cutting, w = (len * step) * (0.5f * (c[p] + c[q])), goals snapped and dropped alike).  Waiting is the
+ * move p -> p with code 27, offered after the translations, of weight (wait * step) * c[p] in float32.  Real slots s = 0 .. S
+ * (S = horizon), each `slot` seconds long; TB = t_begin - epoch in double; world point P(p) = (double)(origin + (float)i * step).
+ * A move p -> q during slot s is clear iff no ball i has sep(P(p), P(q) - P(p), s, i) < dyn_clearance, sep being
+ * gpis_obst_check_timing's interval expression with t0 = 0, dt = slot (so e0 = TB + (double)s * slot, e1 = TB + (double)(s + 1) *
+ * slot), in double, nothing contracted; a NaN separation is not below the clearance.
+ * h[S][p] = 0 at the kept goals, +inf elsewhere; for s = S - 1 .. 0: h[s][p] = 0 at goals, +inf where p is not free, else the
+ * minimum of fl(h[s+1][q] + w) over the moves that exist, are clear during slot s and have h[s+1][q] finite.  policy[s][p] = 13 at
+ * goals, else the minimising code (ties: the smaller h[s+1][q], then the order offered), 255 without a candidate.  Goals are
+ * absorbing.  Layer s depends on layer s + 1 alone: no iteration, and the bits do not depend on the schedule.
+ * Storage (grow-only): one policy byte per state, c, the cost of slot 0, two cost layers, and every layer's cost with keep_cost.
+ * The handle copies the lattice geometry and the ball table during the solve: a result outlives its field and its set.
+ * Errors: NULL handle, field or goals, ngoals < 1, an option outside its range, a non-finite t_begin, a field that is not 2-D,
+ * a set of another device or of 3-D balls -> GPIS_ERR_ARG; a field without a result, or readers without a solve / paths ->
+ * GPIS_ERR_STATE; nx * ny * (S + 1) > 2^30 (2^28 with keep_cost), more than 2^24 starts -> GPIS_ERR_LIMIT: all with the previous
+ * result untouched. */
+typedef struct gpis_tplan_opts {
+    float clearance, margin, gain;  /* the point cost, as gpis_plan_opts */
+    int connectivity;               /* 0: axis moves, 1: diagonals too */
+    double slot;                    /* seconds per slot, > 0 */
+    int horizon;                    /* S, 1 .. 1024 */
+    double dyn_clearance;           /* >= 0: the separation every move keeps from every ball */
+    float wait;                     /* 0 .. 1e4: a wait weighs (wait * step) * c[p] */
+    int keep_cost;                  /* 1: every layer's cost is kept for gpis_tplan_get */
+} gpis_tplan_opts;
+/* the planner's clearance 0, margin 4 * step, gain 4, connectivity 1; slot 0.1, horizon 256, dyn_clearance step, wait 0.5,
+ * keep_cost 0.  Needs no device. */
+int   gpis_tplan_default_opts(float step, gpis_tplan_opts* opts);
+/* what gpis_tplan_solve would say to these options on a lattice of nx x ny points (0, 0: the options alone): GPIS_OK,
+ * GPIS_ERR_ARG or GPIS_ERR_LIMIT.  Needs no device. */
+int   gpis_tplan_check_opts(const gpis_tplan_opts* opts, int nx, int ny);
+void* gpis_tplan_create(void);                             /* on the current device; NULL without one */
+void  gpis_tplan_destroy(void* tplan);
+/* obst NULL or an empty set: no balls.  goals: host [ngoals][2].  opts NULL: the defaults for the field's step */
+int   gpis_tplan_solve(void* tplan, void* df, void* obst, const float* goals, int ngoals, double t_begin, const gpis_tplan_opts* opts,
+                       void* hip_stream);
+/* out[0..n): 1 if a result is held, nx, ny, S, slot, balls, goals given, goals kept, free points, points with a finite cost at
+ * slot 0, layer launches, (tile, layer batch, ball) triples the broad phase skipped, ms of host wall time in the solve, the
+ * largest finite cost at slot 0, t_begin, 1 if every layer's cost is kept (16 values) */
+int   gpis_tplan_info(void* tplan, double* out, int n);
+/* host copies: cost0 [nx ny], policy [(S + 1) nx ny], cost_all [(S + 1) nx ny] (GPIS_ERR_STATE without keep_cost), c [nx ny];
+ * any may be NULL */
+int   gpis_tplan_get(void* tplan, float* cost0, unsigned char* policy, float* cost_all, float* c);
+/* device pointers of the last result, valid until the next solve or gpis_tplan_destroy (NULL where there is none) */
+int   gpis_tplan_device(void* tplan, const float** d_cost0, const unsigned char** d_policy);
+/* Paths from the host starts [m][2], each at slot 0 and snapped like a goal.  Status 1: outside the lattice or non-finite; 2: not
+ * free; 3: h[0] = +inf, no arrival within S slots (these give no points); 0: the policy is followed from slot 0 until code 13
+ * and one float32 world point is emitted per slot (a wait repeats its point): arrive + 1 points, packed at offsets from a scan. */
+int   gpis_tplan_paths(void* tplan, const float* starts, int m, void* hip_stream);
+int   gpis_tplan_path_counts(void* tplan, long long* npaths, long long* npoints);
+/* off[m + 1], points[off[m]][2], arrive[m] (-1 unless status 0), start_cost[m] (NaN for status 1), status[m]; any may be NULL */
+int   gpis_tplan_get_paths(void* tplan, long long* off, float* points, int* arrive, float* start_cost, unsigned char* status);
+/* The last paths against any 2-D set at the solve's t_begin and slot: gpis_retime_check's five outputs [m] over the intervals
+ * s = 0 .. arrive - 1 of each status-0 path (ties: the smallest (s, i)); a path of another status answers NaN, NaN, -1, -1, 0;
+ * n = 0 or arrive = 0 answers +inf, NaN, -1, -1, 0.  With the solve's set and dyn_clearance every status-0 path has collides 0
+ * and min_sep >= dyn_clearance: the expressions and the operands are the same. */
+int   gpis_tplan_check(void* tplan, void* obst, double clearance, double* min_sep, double* min_time, int* min_obstacle,
+                       int* first_hit, int* collides);
+/* gpis_retime_controls' stage with dt = slot on the positions P(point at slot min(k0 + k, arrive)), k = 0 .. T (T <= 256):
+ * U [m][T][2], heading0 [m][2], p0 [m][2], clamped [m].  A path of status != 0 stands still, p0 the start as given. */
+int   gpis_tplan_controls(void* tplan, int T, int k0, double w_limit, double min_move, double* U, double* heading0, double* p0,
+                          int* clamped);
+/* test hook (the results do not depend on it): layers per launch (0 = the default: 4 without balls, 1 with them; at most 16) and the broad phase (0 / 1) */
+int   gpis_tplan_set_schedule(void* tplan, int layers_per_launch, int cull);
+
 #ifdef __cplusplus
 }
 #endif
