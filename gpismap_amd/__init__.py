@@ -79,6 +79,11 @@ class gpis_tplan_opts(C.Structure):
                 ("keep_cost", C.c_int)]
 
 
+class gpis_tpplan_opts(C.Structure):
+    _fields_ = [("clearance", C.c_float), ("margin", C.c_float), ("gain", C.c_float), ("turn", C.c_float), ("slot", C.c_double),
+                ("horizon", C.c_int), ("dyn_clearance", C.c_double), ("wait", C.c_float), ("keep_cost", C.c_int)]
+
+
 class gpis_pplan_opts(C.Structure):
     _fields_ = [("clearance", C.c_float), ("margin", C.c_float), ("gain", C.c_float), ("turn", C.c_float), ("max_rounds", C.c_int)]
 
@@ -404,6 +409,22 @@ def lib():
         L.gpis_tplan_check.argtypes = [vp, vp, d, dp, dp, ip, ip, ip]
         L.gpis_tplan_controls.argtypes = [vp, C.c_int, C.c_int, d, d, dp, dp, dp, ip]
         L.gpis_tplan_set_schedule.argtypes = [vp, C.c_int, C.c_int]
+    if hasattr(L, "gpis_tpplan_create"):
+        to, ub, ll, us = C.POINTER(gpis_tpplan_opts), C.POINTER(C.c_ubyte), C.POINTER(C.c_longlong), C.POINTER(C.c_ushort)
+        L.gpis_tpplan_default_opts.argtypes = [C.c_float, C.c_int, to]
+        L.gpis_tpplan_check_opts.argtypes = [to, C.c_int, C.c_int, C.c_int]
+        L.gpis_tpplan_create.restype = vp
+        L.gpis_tpplan_create.argtypes = []
+        L.gpis_tpplan_destroy.argtypes = [vp]
+        L.gpis_tpplan_solve.argtypes = [vp, vp, vp, vp, dp, us, C.c_int, fp, C.c_int, d, to, vp]
+        L.gpis_tpplan_info.argtypes = [vp, dp, C.c_int]
+        L.gpis_tpplan_get.argtypes = [vp, fp, ub, fp, fp]
+        L.gpis_tpplan_paths.argtypes = [vp, fp, C.c_int, vp]
+        L.gpis_tpplan_path_counts.argtypes = [vp, ll, ll]
+        L.gpis_tpplan_get_paths.argtypes = [vp, ll, fp, ip, ip, fp, ub]
+        L.gpis_tpplan_check.argtypes = [vp, vp, vp, d, dp, dp, ip, ip, ip, ip]
+        L.gpis_tpplan_controls.argtypes = [vp, C.c_int, C.c_int, d, d, dp, dp, dp, ip]
+        L.gpis_tpplan_set_schedule.argtypes = [vp, C.c_int]
     if hasattr(L, "gpis_body_create"):
         L.gpis_body_create.restype = vp
         L.gpis_body_create.argtypes = []
@@ -1397,6 +1418,19 @@ class DistanceField:
             time_planner = self._time_planner
         return time_planner.solve(self, goals, obstacles, t_begin, **opts)
 
+    def plan_poses_timed(self, goals, footprint, obstacles=None, H=16, moves="any", t_begin=0.0, time_pose_planner=None, **opts):
+        """A plan through space and time over poses (x, y, heading index) of this 2-D field for `footprint` towards `goals`
+        [g, 3] or [g, 2] around the moving balls of `obstacles` (an Obstacles, or None) from absolute time t_begin on
+        (gpis_tpplan_solve): every body ball keeps dyn_clearance from every moving ball during every move.  H, moves: as
+        plan_poses (heading_table, heading_moves).  opts: the gpis_tpplan_opts fields (clearance, margin, gain, turn, slot,
+        horizon, dyn_clearance, wait, keep_cost).  Returns the TimePosePlanner holding the result (default: one kept by this
+        field); it stays valid when the field, the set or the footprint changes."""
+        if time_pose_planner is None:
+            if getattr(self, "_time_pose_planner", None) is None:
+                self._time_pose_planner = TimePosePlanner()
+            time_pose_planner = self._time_pose_planner
+        return time_pose_planner.solve(self, goals, footprint, obstacles, H=H, moves=moves, t_begin=t_begin, **opts)
+
     def plan_poses(self, footprint, goals, H=16, moves="any", pose_planner=None, **opts):
         """Cost-to-go and policy over poses (x, y, heading index) of this 2-D field for `footprint` towards `goals` [g, 3] or
         [g, 2] (gpis_pplan_solve): routes the body fits through, where plan() routes a point.  opts: the gpis_pplan_opts
@@ -2020,6 +2054,159 @@ class PosePlanner:
         _check(self.L.gpis_pplan_project(self.h, p.h, _p(h2, C.c_ubyte)), "gpis_pplan_project")
         self.heading2 = h2.reshape(i["ny"], i["nx"])
         return p
+
+
+def tpplan_opts(step, H=16, **opts):
+    """gpis_tpplan_opts of the library's defaults for a field of lattice step `step` and H headings (gpis_tpplan_default_opts;
+    needs no device) with the given fields replaced."""
+    o = gpis_tpplan_opts()
+    _check(lib().gpis_tpplan_default_opts(float(step), int(H), C.byref(o)), "gpis_tpplan_default_opts")
+    names = {f[0] for f in gpis_tpplan_opts._fields_}
+    for k, v in opts.items():
+        if k not in names:
+            raise GpisError("unknown time-pose-plan option %r" % k)
+        setattr(o, k, v)
+    return o
+
+
+class TimePosePlanner:
+    """Result holder of the time-pose planner (gpis_tpplan_*): a policy byte per (lattice point, heading index, slot), the cost
+    of slot 0, pose paths, their check against moving balls with a footprint, and their control sequences, on the device;
+    buffers reused across calls.  A finished plan depends on neither the field, the set nor the footprint it was solved with."""
+
+    INFO_KEYS = ("valid", "nx", "ny", "H", "horizon", "slot", "balls", "body_balls", "goals", "goals_kept", "free", "finite0",
+                 "max_cost0", "t_begin", "keep_cost", "launches", "skipped", "solve_ms")
+    INT_KEYS = ("valid", "nx", "ny", "H", "horizon", "balls", "body_balls", "goals", "goals_kept", "free", "finite0", "keep_cost",
+                "launches", "skipped")
+
+    def __init__(self):
+        self.L = lib()
+        if not hasattr(self.L, "gpis_tpplan_create"):
+            raise GpisError("the native library has no time-pose planner (gpis_tpplan_create)")
+        if self.L.gpis_device_count() < 1:
+            raise GpisError("no HIP device: gpismap_amd has no CPU fallback")
+        self.h = C.c_void_p(self.L.gpis_tpplan_create())
+        if not self.h:
+            raise GpisError("gpis_tpplan_create failed")
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.gpis_tpplan_destroy(self.h)
+            self.h = None
+
+    __del__ = close
+
+    def set_schedule(self, cull=1):
+        """The broad phase over the balls (0 / 1); the results do not depend on it."""
+        _check(self.L.gpis_tpplan_set_schedule(self.h, int(cull)), "gpis_tpplan_set_schedule")
+        return self
+
+    def solve(self, field, goals, footprint, obstacles=None, H=16, moves="any", t_begin=0.0, headings=None, stream=0, **opts):
+        """gpis_tpplan_solve on a 2-D DistanceField holding a result for a Footprint; goals [g, 3] = (x, y, h), h = -1 meaning
+        every free heading (goals [g, 2] are taken as that); obstacles: an Obstacles or None.  moves: a mode of heading_moves
+        or a uint16 [H] table; headings: a [H, 2] table (default heading_table(H)).  Returns self."""
+        inf = field.info()
+        if inf["dim"] == 0:
+            raise GpisError("distance field holds no result")
+        H = int(H)
+        g = _pose_rows(goals)
+        tab = np.ascontiguousarray(heading_table(H) if headings is None else headings, dtype=np.float64).reshape(-1, 2)
+        mv = np.ascontiguousarray(heading_moves(H, moves) if isinstance(moves, str) else moves, dtype=np.uint16).ravel()
+        if tab.shape[0] != H or mv.size != H:
+            raise GpisError("headings and moves must have H rows")
+        o = tpplan_opts(inf["step"], H, **opts)
+        _check(self.L.gpis_tpplan_solve(self.h, field.h, obstacles.h if obstacles is not None else None, footprint.h,
+                                        _p(tab, C.c_double), _p(mv, C.c_ushort), H, _p(g), g.shape[0], float(t_begin), C.byref(o),
+                                        C.c_void_p(stream)), "gpis_tpplan_solve")
+        self.dyn_clearance = float(o.dyn_clearance)
+        return self
+
+    def info(self):
+        out = np.zeros(len(self.INFO_KEYS), dtype=np.float64)
+        _check(self.L.gpis_tpplan_info(self.h, _p(out, C.c_double), out.size), "gpis_tpplan_info")
+        d = dict(zip(self.INFO_KEYS, out.tolist()))
+        for k in self.INT_KEYS:
+            d[k] = int(d[k])
+        return d
+
+    def get(self, cost_all=False):
+        """dict(cost0 f32 [H, ny, nx], policy u8 [S + 1, H, ny, nx], c f32 [H, ny, nx]) host copies of the last result, with
+        cost_all f32 [S + 1, H, ny, nx] on request (the solve must have kept it)."""
+        i = self.info()
+        if not i["valid"]:
+            raise GpisError("time-pose planner holds no result")
+        shape, S = (i["H"], i["ny"], i["nx"]), i["horizon"]
+        cost0, c = np.zeros(shape, np.float32), np.zeros(shape, np.float32)
+        pol = np.zeros((S + 1,) + shape, np.uint8)
+        call = np.zeros((S + 1,) + shape, np.float32) if cost_all else None
+        _check(self.L.gpis_tpplan_get(self.h, _p(cost0), _p(pol, C.c_ubyte), _p(call) if cost_all else None, _p(c)), "gpis_tpplan_get")
+        out = dict(cost0=cost0, policy=pol, c=c)
+        if cost_all:
+            out["cost_all"] = call
+        return out
+
+    def paths(self, starts, stream=0):
+        """Pose routes from `starts` [m, 3] = (x, y, h) at slot 0 along the policy (gpis_tpplan_paths); h = -1: the free heading
+        of least cost there ([m, 2] starts are taken as that).  Returns dict(paths: list of [arrive + 1, 2] float32 points, one
+        per slot; headings: list of [arrive + 1] int32 heading indices; off i64 [m + 1]; points f32 [total, 2]; heading i32
+        [total]; arrive i32 [m]; start_cost f32 [m]; status u8 [m]: 0 arrived, 1 outside / non-finite, 2 not free, 3 no arrival
+        within the horizon)."""
+        x = _pose_rows(starts)
+        _check(self.L.gpis_tpplan_paths(self.h, _p(x), x.shape[0], C.c_void_p(stream)), "gpis_tpplan_paths")
+        m, tot = C.c_longlong(0), C.c_longlong(0)
+        _check(self.L.gpis_tpplan_path_counts(self.h, C.byref(m), C.byref(tot)), "gpis_tpplan_path_counts")
+        off = np.zeros(m.value + 1, np.int64)
+        pts = np.zeros((max(tot.value, 1), 2), np.float32)
+        hd = np.zeros(max(tot.value, 1), np.int32)
+        arrive = np.zeros(m.value, np.int32)
+        sc = np.zeros(m.value, np.float32)
+        st = np.zeros(m.value, np.uint8)
+        _check(self.L.gpis_tpplan_get_paths(self.h, _p(off, C.c_longlong), _p(pts), _p(hd, C.c_int), _p(arrive, C.c_int), _p(sc),
+                                            _p(st, C.c_ubyte)), "gpis_tpplan_get_paths")
+        pts, hd = pts[:tot.value], hd[:tot.value]
+        return dict(paths=[pts[off[k]:off[k + 1]] for k in range(m.value)], headings=[hd[off[k]:off[k + 1]] for k in range(m.value)],
+                    off=off, points=pts, heading=hd, arrive=arrive, start_cost=sc, status=st)
+
+    def _npaths(self):
+        m = C.c_longlong(0)
+        _check(self.L.gpis_tpplan_path_counts(self.h, C.byref(m), None), "gpis_tpplan_path_counts")
+        return m.value
+
+    def check(self, obstacles, footprint=None, clearance=None):
+        """The last paths against the balls of `obstacles` (any 2-D set) with `footprint` (any 2-D Footprint; None: the solve's)
+        at the solve's t_begin, slot and heading table (gpis_tpplan_check): dict(min_sep, min_time f64 [m], min_obstacle,
+        min_ball, first_hit, collides i32 [m]).  clearance None: the last solve's dyn_clearance."""
+        m = self._npaths()
+        if clearance is None:
+            clearance = self.dyn_clearance
+        ms, mt = np.zeros(m, np.float64), np.zeros(m, np.float64)
+        mo, mb, fh, co = np.zeros(m, np.int32), np.zeros(m, np.int32), np.zeros(m, np.int32), np.zeros(m, np.int32)
+        _check(self.L.gpis_tpplan_check(self.h, obstacles.h, footprint.h if footprint is not None else None, float(clearance),
+                                        _p(ms, C.c_double), _p(mt, C.c_double), _p(mo, C.c_int), _p(mb, C.c_int), _p(fh, C.c_int),
+                                        _p(co, C.c_int)), "gpis_tpplan_check")
+        return dict(min_sep=ms, min_time=mt, min_obstacle=mo, min_ball=mb, first_hit=fh, collides=co)
+
+    def controls(self, T, k0=0, w_limit=0.0, min_move=1e-9):
+        """Control sequences of T steps of the plan's slot along the points of the last paths from slot k0 on
+        (gpis_tpplan_controls): dict(U f64 [m, T, 2], heading0 [m, 2], p0 [m, 2], clamped i32 [m]); a start without a path
+        stands still.  The heading indices are not tracked: the pose path is the certificate, the controls are a guide."""
+        m, T = self._npaths(), int(T)
+        U = np.zeros((m, max(T, 1), 2), np.float64)
+        h0, p0, cl = np.zeros((m, 2), np.float64), np.zeros((m, 2), np.float64), np.zeros(m, np.int32)
+        _check(self.L.gpis_tpplan_controls(self.h, T, int(k0), float(w_limit), float(min_move), _p(U, C.c_double), _p(h0, C.c_double),
+                                           _p(p0, C.c_double), _p(cl, C.c_int)), "gpis_tpplan_controls")
+        return dict(U=U, heading0=h0, p0=p0, clamped=cl)
+
+    def follow(self, controller, index, k0=0, w_limit=0.0, min_move=1e-9):
+        """Replace `controller`'s nominal sequence by the control sequence of path `index` from slot k0 on, over the controller's
+        horizon (controls + gpis_mppi_set_nominal; the controller is meant to run at dt = the plan's slot).  Returns (p0 [2],
+        heading0 [2])."""
+        i = controller.info()
+        if not i["inited"] or i["dim"] != 2:
+            raise GpisError("follow needs a 2-D controller after init")
+        r = self.controls(i["horizon"], k0, w_limit, min_move)
+        controller.set_nominal(r["U"][int(index)])
+        return r["p0"][int(index)].copy(), r["heading0"][int(index)].copy()
 
 
 def cover_opts(dim, step, **opts):

@@ -17,6 +17,7 @@
 #include "plan.h"
 #include "pplan.h"
 #include "tplan.h"
+#include "tpplan.h"
 #include "traj.h"
 #include "mppi.h"
 #include "obst.h"
@@ -2686,6 +2687,172 @@ int gpis_tplan_controls(void* tplan, int T, int k0, double w_limit, double min_m
     if (!tplan || k0 < 0 || k0 > (1 << 20) || T < 1 || T > TimePlanner::kMaxT) return GPIS_ERR_ARG;
     if (!std::isfinite(w_limit) || !std::isfinite(min_move) || w_limit < 0.0 || min_move < 0.0) return GPIS_ERR_ARG;
     TimePlanner& p = *(TimePlanner*)tplan;
+    if (!p.valid || !p.paths_valid) return GPIS_ERR_STATE;
+    DeviceScope ds(p.device);
+    try { return p.controls(T, k0, w_limit, min_move, U, heading0, p0, clamped); } catch (...) { return GPIS_ERR_STATE; }
+}
+
+// ---- planning through space and time for the robot's footprint ------------------------------------------------------------------
+static bool tpplan_h_ok(int H) { return H == 8 || H == 16 || H == 32 || H == 64; }
+int gpis_tpplan_default_opts(float step, int H, gpis_tpplan_opts* o) {
+    if (!o || !(std::isfinite(step) && step > 0.f) || !tpplan_h_ok(H)) return GPIS_ERR_ARG;
+    o->clearance = 0.f; o->margin = 4.f * step; o->gain = 4.f; o->turn = step;
+    o->slot = 0.1; o->horizon = 256; o->dyn_clearance = (double)step; o->wait = 0.5f; o->keep_cost = 0;
+    return GPIS_OK;
+}
+static TimePosePlanOpts tpplan_opts_of(const gpis_tpplan_opts* opts) {
+    TimePosePlanOpts o;
+    o.clearance = opts->clearance; o.margin = opts->margin; o.gain = opts->gain; o.turn = opts->turn;
+    o.slot = opts->slot; o.horizon = opts->horizon; o.dyn_clearance = opts->dyn_clearance; o.wait = opts->wait;
+    o.keep_cost = opts->keep_cost;
+    return o;
+}
+static int tpplan_check_size(long long points, int H, const TimePosePlanOpts& o) {
+    return points * H * (long long)(o.horizon + 1) > (o.keep_cost ? TimePosePlanner::kMaxStatesKept : TimePosePlanner::kMaxStates)
+               ? GPIS_ERR_LIMIT
+               : GPIS_OK;
+}
+int gpis_tpplan_check_opts(const gpis_tpplan_opts* opts, int H, int nx, int ny) {
+    if (!opts || !tpplan_h_ok(H) || nx < 0 || ny < 0) return GPIS_ERR_ARG;
+    const TimePosePlanOpts o = tpplan_opts_of(opts);
+    if (int rc = tpplan_check_opts(o, 0.f)) return rc;
+    return tpplan_check_size((long long)nx * ny, H, o);
+}
+void* gpis_tpplan_create(void) {
+    if (gpis_device_count() < 1) { fprintf(stderr, "[gpismap_amd] no HIP device\n"); return nullptr; }
+    TimePosePlanner* p = new (std::nothrow) TimePosePlanner();
+    if (p && !p->own) { delete p; return nullptr; }
+    return p;
+}
+void gpis_tpplan_destroy(void* tpp) { delete (TimePosePlanner*)tpp; }
+int gpis_tpplan_set_schedule(void* tpp, int cull) {
+    if (!tpp || (cull != 0 && cull != 1)) return GPIS_ERR_ARG;
+    ((TimePosePlanner*)tpp)->cull = cull;
+    return GPIS_OK;
+}
+// every check comes before anything is written: such an error leaves the previous result readable
+int gpis_tpplan_solve(void* tpp, void* d, void* obst, void* body, const double* headings, const unsigned short* moves, int H,
+                      const float* goals, int ngoals, double t_begin, const gpis_tpplan_opts* opts, void* stream) {
+    if (!tpp || !d || !body || !headings || !moves || !goals || ngoals < 1 || !std::isfinite(t_begin)) return GPIS_ERR_ARG;
+    if (!tpplan_h_ok(H)) return GPIS_ERR_ARG;
+    for (int h = 0; h < H; ++h) {
+        const double c = headings[2 * h], s = headings[2 * h + 1];
+        if (!std::isfinite(c) || !std::isfinite(s) || (c == 0.0 && s == 0.0) || (moves[h] & ~0x1efu)) return GPIS_ERR_ARG;
+    }
+    for (int g = 0; g < ngoals; ++g) if (!pplan_heading_ok(goals[(size_t)g * 3 + 2], H)) return GPIS_ERR_ARG;
+    const DistanceField& df = *(const DistanceField*)d;
+    const Footprint& b = *(const Footprint*)body;
+    if (df.valid && df.dim != 2) return GPIS_ERR_ARG;
+    gpis_tpplan_opts dflt;
+    if (!opts) {
+        if (!df.valid) return GPIS_ERR_STATE;
+        (void)gpis_tpplan_default_opts(df.step, H, &dflt);
+        opts = &dflt;
+    }
+    const TimePosePlanOpts o = tpplan_opts_of(opts);
+    if (int rc = tpplan_check_opts(o, df.valid ? df.step : 0.f)) return rc;
+    if (!df.valid || b.m == 0 || b.dim != 2) return GPIS_ERR_STATE;
+    if (b.device != df.device) return GPIS_ERR_ARG;
+    const Obstacles* ob = (const Obstacles*)obst;
+    if (ob && (ob->device != df.device || (ob->inited && ob->n > 0 && ob->dim != 2))) return GPIS_ERR_ARG;
+    if (int rc = tpplan_check_size(df.ngrid, H, o)) return rc;
+    TimePosePlanner& p = *(TimePosePlanner*)tpp;
+    DeviceScope ds(df.device);
+    try {
+        if (int rc = p.bind(df.device)) { p.clear_result(); return rc; }
+        const int rc = p.solve(df, ob, b, headings, moves, H, goals, ngoals, t_begin, o, stream ? (hipStream_t)stream : df.own);
+        if (rc != GPIS_OK) p.clear_result();
+        return rc;
+    } catch (...) { p.clear_result(); return GPIS_ERR_STATE; }
+}
+int gpis_tpplan_info(void* tpp, double* out, int n) {
+    if (!tpp || !out || n < 0) return GPIS_ERR_ARG;
+    const TimePosePlanner& p = *(TimePosePlanner*)tpp;
+    const bool v = p.valid;
+    const double w[18] = {v ? 1.0 : 0.0, v ? (double)p.nx : 0.0, v ? (double)p.ny : 0.0, v ? (double)p.H : 0.0, v ? (double)p.S : 0.0,
+                          v ? p.opts.slot : 0.0, (double)p.n, (double)p.mb, (double)p.goals_given, (double)p.goals_kept, (double)p.nfree,
+                          (double)p.nfinite, (double)p.max_cost0, p.t_begin, p.kept ? 1.0 : 0.0, (double)p.launches, (double)p.skipped,
+                          p.solve_ms};
+    for (int i = 0; i < n && i < 18; ++i) out[i] = w[i];
+    return GPIS_OK;
+}
+int gpis_tpplan_get(void* tpp, float* cost0, unsigned char* policy, float* cost_all, float* c) {
+    if (!tpp) return GPIS_ERR_ARG;
+    TimePosePlanner& p = *(TimePosePlanner*)tpp;
+    if (!p.valid || (cost_all && !p.kept)) return GPIS_ERR_STATE;
+    DeviceScope ds(p.device);
+    const size_t n = (size_t)p.ns, ns = n * (size_t)(p.S + 1);
+    if (cost0) GPIS_HIP(hipMemcpyAsync(cost0, p.d_cost0, sizeof(float) * n, hipMemcpyDeviceToHost, p.own));
+    if (policy) GPIS_HIP(hipMemcpyAsync(policy, p.d_policy, ns, hipMemcpyDeviceToHost, p.own));
+    if (cost_all) GPIS_HIP(hipMemcpyAsync(cost_all, p.d_all, sizeof(float) * ns, hipMemcpyDeviceToHost, p.own));
+    if (c) GPIS_HIP(hipMemcpyAsync(c, p.d_c, sizeof(float) * n, hipMemcpyDeviceToHost, p.own));
+    GPIS_HIP(hipStreamSynchronize(p.own));
+    return GPIS_OK;
+}
+int gpis_tpplan_paths(void* tpp, const float* starts, int m, void* stream) {
+    if (!tpp || !starts || m < 1) return GPIS_ERR_ARG;
+    TimePosePlanner& p = *(TimePosePlanner*)tpp;
+    if (!p.valid) return GPIS_ERR_STATE;
+    if (m > TimePosePlanner::kMaxStarts) return GPIS_ERR_LIMIT;
+    for (int t = 0; t < m; ++t) if (!pplan_heading_ok(starts[(size_t)t * 3 + 2], p.H)) return GPIS_ERR_ARG;
+    DeviceScope ds(p.device);
+    try {
+        const int rc = p.paths(starts, m, stream ? (hipStream_t)stream : p.own);
+        if (rc != GPIS_OK) p.paths_valid = false;
+        return rc;
+    } catch (...) { p.paths_valid = false; return GPIS_ERR_STATE; }
+}
+int gpis_tpplan_path_counts(void* tpp, long long* npaths, long long* npoints) {
+    if (!tpp) return GPIS_ERR_ARG;
+    const TimePosePlanner& p = *(TimePosePlanner*)tpp;
+    if (!p.valid || !p.paths_valid) return GPIS_ERR_STATE;
+    if (npaths) *npaths = p.npaths;
+    if (npoints) *npoints = p.npoints;
+    return GPIS_OK;
+}
+int gpis_tpplan_get_paths(void* tpp, long long* off, float* points, int* heading, int* arrive, float* start_cost, unsigned char* status) {
+    if (!tpp) return GPIS_ERR_ARG;
+    TimePosePlanner& p = *(TimePosePlanner*)tpp;
+    if (!p.valid || !p.paths_valid) return GPIS_ERR_STATE;
+    DeviceScope ds(p.device);
+    const size_t m = (size_t)p.npaths;
+    std::vector<long long> ho(m + 1);
+    std::vector<unsigned char> hs(m);
+    GPIS_HIP(hipMemcpyAsync(ho.data(), p.d_off, sizeof(long long) * (m + 1), hipMemcpyDeviceToHost, p.own));
+    GPIS_HIP(hipMemcpyAsync(hs.data(), p.d_status, m, hipMemcpyDeviceToHost, p.own));
+    if (points && p.npoints > 0)
+        GPIS_HIP(hipMemcpyAsync(points, p.d_points, sizeof(float) * (size_t)p.npoints * 2, hipMemcpyDeviceToHost, p.own));
+    if (heading && p.npoints > 0)
+        GPIS_HIP(hipMemcpyAsync(heading, p.d_pheading, sizeof(int) * (size_t)p.npoints, hipMemcpyDeviceToHost, p.own));
+    if (start_cost) GPIS_HIP(hipMemcpyAsync(start_cost, p.d_scost, sizeof(float) * m, hipMemcpyDeviceToHost, p.own));
+    GPIS_HIP(hipStreamSynchronize(p.own));
+    for (size_t k = 0; k < m; ++k) {
+        if (off) off[k] = ho[k];
+        if (status) status[k] = hs[k];
+        if (arrive) arrive[k] = hs[k] == 0 ? (int)(ho[k + 1] - ho[k]) - 1 : -1;
+    }
+    if (off) off[m] = ho[m];
+    return GPIS_OK;
+}
+int gpis_tpplan_check(void* tpp, void* obst, void* body, double clearance, double* min_sep, double* min_time, int* min_obstacle,
+                      int* min_ball, int* first_hit, int* collides) {
+    if (!tpp || !obst || !std::isfinite(clearance) || clearance < 0.0) return GPIS_ERR_ARG;
+    TimePosePlanner& p = *(TimePosePlanner*)tpp;
+    const Obstacles& b = *(const Obstacles*)obst;
+    const Footprint* f = (const Footprint*)body;
+    if (!p.valid || !p.paths_valid) return GPIS_ERR_STATE;
+    if (b.device != p.device || (b.inited && b.n > 0 && b.dim != 2)) return GPIS_ERR_ARG;
+    if (f && (f->m == 0 || f->dim != 2)) return GPIS_ERR_STATE;
+    if (f && f->device != p.device) return GPIS_ERR_ARG;
+    DeviceScope ds(p.device);
+    try {
+        return p.check(b, f, clearance, min_sep, min_time, min_obstacle, min_ball, first_hit, collides);
+    } catch (...) { return GPIS_ERR_STATE; }
+}
+int gpis_tpplan_controls(void* tpp, int T, int k0, double w_limit, double min_move, double* U, double* heading0, double* p0, int* clamped) {
+    if (!tpp || k0 < 0 || k0 > (1 << 20) || T < 1 || T > TimePosePlanner::kMaxT) return GPIS_ERR_ARG;
+    if (!std::isfinite(w_limit) || !std::isfinite(min_move) || w_limit < 0.0 || min_move < 0.0) return GPIS_ERR_ARG;
+    TimePosePlanner& p = *(TimePosePlanner*)tpp;
     if (!p.valid || !p.paths_valid) return GPIS_ERR_STATE;
     DeviceScope ds(p.device);
     try { return p.controls(T, k0, w_limit, min_move, U, heading0, p0, clamped); } catch (...) { return GPIS_ERR_STATE; }

@@ -1568,6 +1568,80 @@ int   gpis_tplan_controls(void* tplan, int T, int k0, double w_limit, double min
 /* test hook (the results do not depend on it): layers per launch (0 = the default: 4 without balls, 1 with them; at most 16) and the broad phase (0 / 1) */
 int   gpis_tplan_set_schedule(void* tplan, int layers_per_launch, int cull);
 
+/* ---- planning through space and time for the robot's footprint (the contract: tests/tpplan_ref.py) ----------
+ * gpis_tplan_solve plans for a point with one dyn_clearance; gpis_tpplan_solve runs its layer recursion on gpis_pplan_solve's
+ * lattice of poses: states (lattice point, heading index h of the caller's table headings[H][2], real slot s = 0 .. S).
+ * Static part: gpis_pplan_solve's, bit for bit (the body rule's D at (P(p), (c_h, s_h)), the point cost c on (float)D, free iff
+ * c > 0, the directed translations with codes 9 .. 17 without 13 gated by moves[h] and the subset rule per heading layer, the
+ * turns 27 (h + 1) and 28 (h - 1) mod H, their weights; goals [g][3] with h = -1 for every free heading, snapped and dropped
+ * alike).  Waiting is the move (p, h) -> (p, h) with code 29 and weight (wait * step) * c in float32.  The moves are offered as
+ * translations by rising code, 27, 28, 29; every move takes one slot.
+ * A move (p, h) -> (q, h') during slot s is clear iff no pair (moving ball i, body ball j) has sep < dyn_clearance: body ball j
+ * starts at W0 = P(p) + (c_h b0 - s_h b1, s_h b0 + c_h b1), ends at W1 = the same at (P(q), h'), and sep is
+ * gpis_timed_body_check's interval expression with dW = W1 - W0, e0 = TB + (double)s * slot, e1 = TB + (double)(s + 1) * slot,
+ * sep = (sqrt(s2) - r_i) - rho_j, in double, nothing contracted; a NaN is not below the clearance.  Between the two ends a
+ * ball's centre moves on the chord of its arc.
+ * h[S] = 0 at the kept goals, +inf elsewhere; for s = S - 1 .. 0: 0 at goals, +inf where the state is not free, else the minimum
+ * of fl(h[s+1][s'] + w) over the moves that exist statically, are clear during slot s and have a finite target.  policy = 13 at
+ * goals, else the minimising code (ties: the smaller h[s+1][s'], then the order offered), 255 without a candidate.
+ * Storage (grow-only): one policy byte per state, c, the cost of slot 0, two cost layers, and every layer's cost with keep_cost.
+ * The handle copies the lattice geometry, the ball table, the footprint and both caller tables during the solve: a result
+ * outlives its field, its set and its footprint.
+ * Errors: what gpis_pplan_solve and gpis_tplan_solve answer to the same faults (a 3-D field, a set of another device or of 3-D
+ * balls, a footprint of another device, a bad table, heading or option -> GPIS_ERR_ARG; a field without a result, an empty or
+ * 3-D footprint, readers without a solve / paths -> GPIS_ERR_STATE); nx * ny * H * (S + 1) > 2^30 (2^28 with keep_cost), more
+ * than 2^24 starts -> GPIS_ERR_LIMIT: all with the previous result untouched. */
+typedef struct gpis_tpplan_opts {
+    float clearance, margin, gain, turn;   /* as gpis_pplan_opts */
+    double slot;                    /* seconds per slot, > 0 */
+    int horizon;                    /* S, 1 .. 1024 */
+    double dyn_clearance;           /* >= 0: the separation every body ball keeps from every moving ball */
+    float wait;                     /* 0 .. 1e4: a wait weighs (wait * step) * c */
+    int keep_cost;                  /* 1: every layer's cost is kept for gpis_tpplan_get */
+} gpis_tpplan_opts;
+/* the pose planner's clearance 0, margin 4 * step, gain 4, turn step; slot 0.1, horizon 256, dyn_clearance step, wait 0.5,
+ * keep_cost 0.  Needs no device. */
+int   gpis_tpplan_default_opts(float step, int H, gpis_tpplan_opts* opts);
+/* what gpis_tpplan_solve would say to these options with H headings on a lattice of nx x ny points (0, 0: the options alone;
+ * turn is only asked to be positive, its range depends on the field's step): GPIS_OK, GPIS_ERR_ARG or GPIS_ERR_LIMIT.  Needs no
+ * device. */
+int   gpis_tpplan_check_opts(const gpis_tpplan_opts* opts, int H, int nx, int ny);
+void* gpis_tpplan_create(void);                            /* on the current device; NULL without one */
+void  gpis_tpplan_destroy(void* tpp);
+/* obst NULL or an empty set: no balls.  body: a 2-D footprint.  headings [H][2], moves [H], goals [ngoals][3]: host, as
+ * gpis_pplan_solve's.  opts NULL: the defaults for the field's step */
+int   gpis_tpplan_solve(void* tpp, void* df, void* obst, void* body, const double* headings, const unsigned short* moves, int H,
+                        const float* goals, int ngoals, double t_begin, const gpis_tpplan_opts* opts, void* hip_stream);
+/* out[0..n): 1 if a result is held, nx, ny, H, S, slot, balls, body balls, goals given, goals kept, free states, states with a
+ * finite cost at slot 0, the largest such cost, t_begin, 1 if every layer's cost is kept, layer launches, (tile, layer, ball)
+ * triples the broad phase skipped, ms of host wall time in the solve (18 values) */
+int   gpis_tpplan_info(void* tpp, double* out, int n);
+/* host copies: cost0 [H ny nx], policy [(S + 1) H ny nx], cost_all [(S + 1) H ny nx] (GPIS_ERR_STATE without keep_cost),
+ * c [H ny nx]; any may be NULL */
+int   gpis_tpplan_get(void* tpp, float* cost0, unsigned char* policy, float* cost_all, float* c);
+/* Pose paths from the host starts [m][3] = (x, y, h), each at slot 0 and snapped like a goal; h = -1: the free heading of least
+ * slot-0 cost there (ties: the smaller h).  Status 1: outside the lattice or non-finite; 2: no free heading, or the given one
+ * not free; 3: cost +inf (these give no entries); 0: the policy is followed from slot 0 until code 13, one float32 world point
+ * and one int32 heading index per slot: arrive + 1 entries, packed at offsets from a scan. */
+int   gpis_tpplan_paths(void* tpp, const float* starts, int m, void* hip_stream);
+int   gpis_tpplan_path_counts(void* tpp, long long* npaths, long long* npoints);
+/* off[m + 1], points[off[m]][2], heading[off[m]], arrive[m] (-1 unless status 0), start_cost[m], status[m]; any may be NULL */
+int   gpis_tpplan_get_paths(void* tpp, long long* off, float* points, int* heading, int* arrive, float* start_cost,
+                            unsigned char* status);
+/* The last paths against any 2-D set with any 2-D footprint (body NULL: the solve's) at the solve's t_begin, slot and heading
+ * table: gpis_timed_body_check's six outputs [m] over the intervals s = 0 .. arrive - 1 of each status-0 path (ties: the
+ * smallest (s, i, j)); min_time = (double)s * slot + sigma * slot.  A path of another status answers NaN, NaN, -1, -1, -1, 0;
+ * n = 0 or arrive = 0 answers +inf, NaN, -1, -1, -1, 0.  clearance: >= 0, as gpis_tplan_check's (the solve's dyn_clearance is
+ * the caller's to pass).  With the solve's set, footprint and dyn_clearance every status-0 path has collides 0 and min_sep >=
+ * dyn_clearance: the expressions and the operands are the solve's own. */
+int   gpis_tpplan_check(void* tpp, void* obst, void* body, double clearance, double* min_sep, double* min_time, int* min_obstacle,
+                        int* min_ball, int* first_hit, int* collides);
+/* gpis_tplan_controls on the paths' points (a turn repeats its point, as a wait does; the heading indices are not tracked) */
+int   gpis_tpplan_controls(void* tpp, int T, int k0, double w_limit, double min_move, double* U, double* heading0, double* p0,
+                           int* clamped);
+/* test hook (the results do not depend on it): the broad phase over the balls (0 / 1) */
+int   gpis_tpplan_set_schedule(void* tpp, int cull);
+
 #ifdef __cplusplus
 }
 #endif
