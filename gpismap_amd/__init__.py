@@ -180,6 +180,10 @@ def lib():
     L.gpis2_get_nodes.argtypes = [vp, fp, C.c_int]
     L.gpis2_stats.argtypes = [vp, dp, C.c_int]
     L.gpis2_pass_jobs.argtypes = [vp, C.POINTER(C.c_longlong)]
+    if hasattr(L, "gpis3_set_pass2_mode"):
+        for name in ("gpis3", "gpis2", "gpis_mapquery"):
+            getattr(L, name + "_set_pass2_mode").argtypes = [vp, C.c_int]
+            getattr(L, name + "_pass_detail").argtypes = [vp, dp]
     if hasattr(L, "gpis2_sync"):
         L.gpis2_sync.argtypes = [vp]
         L.gpis2_set_pipeline.argtypes = [vp, C.c_int]
@@ -722,6 +726,19 @@ class GPisMap3:
         _check(self.L.gpis3_pass_jobs(self.h, a), "gpis3_pass_jobs")
         return dict(zip(self.PASS_KEYS, list(a)))
 
+    DETAIL_KEYS = ("predicted_full", "value_only", "repair", "unread", "predictions", "hits", "pick_ms", "mode")
+
+    def set_pass2_mode(self, mode):
+        """How test() evaluates candidates 2 and 3 of a three-candidate fallback: 0 value columns first, 1 the predicted candidate
+        in full (default), 2 / 3 always candidate 2 / 3, 4 the predictor inverted.  Same results in every mode (gpis3_set_pass2_mode)."""
+        _check(self.L.gpis3_set_pass2_mode(self.h, int(mode)), "gpis3_set_pass2_mode")
+
+    def pass_detail(self):
+        """How the prediction of the last test() went (gpis3_pass_detail)."""
+        a = (C.c_double * 8)()
+        _check(self.L.gpis3_pass_detail(self.h, a), "gpis3_pass_detail")
+        return dict(zip(self.DETAIL_KEYS, list(a)))
+
     def save(self, path):
         """Map checkpoint: spatial index, surface points and the packed prediction records of the trained models (gpis3_save)."""
         _check(self.L.gpis3_save(self.h, os.fsencode(path)), "gpis3_save")
@@ -927,6 +944,15 @@ class GPisMap:
         a = (C.c_longlong * 4)()
         _check(self.L.gpis2_pass_jobs(self.h, a), "gpis2_pass_jobs")
         return dict(zip(GPisMap3.PASS_KEYS, list(a)))
+
+    def set_pass2_mode(self, mode):
+        """As GPisMap3.set_pass2_mode (gpis2_set_pass2_mode)."""
+        _check(self.L.gpis2_set_pass2_mode(self.h, int(mode)), "gpis2_set_pass2_mode")
+
+    def pass_detail(self):
+        a = (C.c_double * 8)()
+        _check(self.L.gpis2_pass_detail(self.h, a), "gpis2_pass_detail")
+        return dict(zip(GPisMap3.DETAIL_KEYS, list(a)))
 
     def sync(self):
         """Join the training the last update() left in flight (pipelined mode); raises when it failed."""
@@ -3862,3 +3888,11 @@ class MapQueryProbe:
         a = (C.c_longlong * 4)()
         _check(self.L.gpis_mapquery_pass_jobs(self.h, a), "gpis_mapquery_pass_jobs")
         return [int(v) for v in a]
+
+    def set_pass2_mode(self, mode):
+        _check(self.L.gpis_mapquery_set_pass2_mode(self.h, int(mode)), "gpis_mapquery_set_pass2_mode")
+
+    def pass_detail(self):
+        a = (C.c_double * 8)()
+        _check(self.L.gpis_mapquery_pass_detail(self.h, a), "gpis_mapquery_pass_detail")
+        return dict(zip(GPisMap3.DETAIL_KEYS, list(a)))

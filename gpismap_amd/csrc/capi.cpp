@@ -36,6 +36,10 @@ void gpis3_impl_profile(GPisMap3* m, int on);
 void gpis2_impl_stats(GPisMap* m, double* out, int n);
 void gpis3_impl_pass_jobs(GPisMap3* m, long long* out);
 void gpis2_impl_pass_jobs(GPisMap* m, long long* out);
+void gpis3_impl_pass_detail(GPisMap3* m, double* out);
+void gpis2_impl_pass_detail(GPisMap* m, double* out);
+int gpis3_impl_set_pass2_mode(GPisMap3* m, int mode);
+int gpis2_impl_set_pass2_mode(GPisMap* m, int mode);
 int gpis3_impl_fail(GPisMap3* m);
 int gpis2_impl_fail(GPisMap* m);
 int gpis3_impl_update_fail(GPisMap3* m);
@@ -211,6 +215,8 @@ int gpis3_load(void* m, const char* path) {
 }
 int gpis3_stats(void* m, double* out, int n) { if (!m || !out) return GPIS_ERR_ARG; gpis3_impl_stats((GPisMap3*)m, out, n); return GPIS_OK; }
 int gpis3_pass_jobs(void* m, long long* out4) { if (!m || !out4) return GPIS_ERR_ARG; gpis3_impl_pass_jobs((GPisMap3*)m, out4); return GPIS_OK; }
+int gpis3_pass_detail(void* m, double* out8) { if (!m || !out8) return GPIS_ERR_ARG; gpis3_impl_pass_detail((GPisMap3*)m, out8); return GPIS_OK; }
+int gpis3_set_pass2_mode(void* m, int mode) { if (!m || mode < 0 || mode > 4) return GPIS_ERR_ARG; return gpis3_impl_set_pass2_mode((GPisMap3*)m, mode); }
 int gpis3_sync(void* m) { if (!m) return GPIS_ERR_ARG; try { return gpis3_impl_sync((GPisMap3*)m); } catch (...) { return GPIS_ERR_STATE; } }
 int gpis3_set_pipeline(void* m, int on) { if (!m) return GPIS_ERR_ARG; try { gpis3_impl_set_pipeline((GPisMap3*)m, on); return GPIS_OK; } catch (...) { return GPIS_ERR_STATE; } }
 int gpis3_set_host_gather(void* m, int on) { if (!m) return GPIS_ERR_ARG; gpis3_impl_set_host_gather((GPisMap3*)m, on); return GPIS_OK; }
@@ -256,6 +262,8 @@ int gpis2_get_nodes(void* m, float* out, int cap) {
 }
 int gpis2_stats(void* m, double* out, int n) { if (!m || !out) return GPIS_ERR_ARG; gpis2_impl_stats((GPisMap*)m, out, n); return GPIS_OK; }
 int gpis2_pass_jobs(void* m, long long* out4) { if (!m || !out4) return GPIS_ERR_ARG; gpis2_impl_pass_jobs((GPisMap*)m, out4); return GPIS_OK; }
+int gpis2_pass_detail(void* m, double* out8) { if (!m || !out8) return GPIS_ERR_ARG; gpis2_impl_pass_detail((GPisMap*)m, out8); return GPIS_OK; }
+int gpis2_set_pass2_mode(void* m, int mode) { if (!m || mode < 0 || mode > 4) return GPIS_ERR_ARG; return gpis2_impl_set_pass2_mode((GPisMap*)m, mode); }
 
 // ---- ObsGP --------------------------------------------------------------------
 struct ObsHandle { int device = -1; ObsGPDevice g; hipStream_t s = nullptr; hipStream_t sb = nullptr; int nb = -1; };   // sb: the second staging set's stream, nb: queries of its batch not collected yet, -1 none (gpis_obsgp_query_route)
@@ -595,6 +603,16 @@ int gpis_mapquery_candidates(void* h, int* ncand, int* cand3) {
 int gpis_mapquery_pass_jobs(void* h, long long* out4) {
     if (!h || !out4) return GPIS_ERR_ARG;
     for (int k = 0; k < 4; ++k) out4[k] = ((MqHandle*)h)->mq.last_pass_jobs[k];
+    return GPIS_OK;
+}
+int gpis_mapquery_pass_detail(void* h, double* out8) {
+    if (!h || !out8) return GPIS_ERR_ARG;
+    ((MqHandle*)h)->mq.pass_detail(out8);
+    return GPIS_OK;
+}
+int gpis_mapquery_set_pass2_mode(void* h, int mode) {
+    if (!h || mode < 0 || mode > 4) return GPIS_ERR_ARG;
+    ((MqHandle*)h)->mq.pass2_mode = mode;
     return GPIS_OK;
 }
 

@@ -652,6 +652,8 @@ void gpis2_impl_pass_jobs(GPisMap* g, long long* out) {
     GPisMap::Impl& m = *g->impl();
     for (int i = 0; i < 4; ++i) out[i] = m.mq.last_pass_jobs[i];
 }
+void gpis2_impl_pass_detail(GPisMap* g, double* out) { g->impl()->mq.pass_detail(out); }
+int gpis2_impl_set_pass2_mode(GPisMap* g, int mode) { g->impl()->mq.pass2_mode = mode; return GPIS_OK; }
 
 // What gpis2_extract_contour, gpis2_distance_field, gpis2_render_scan and gpis2_track_scan share: testDevice's checks and join,
 // the consumer moved to the map's device, its call on the caller's stream or the map's, and the report of a failed device path.

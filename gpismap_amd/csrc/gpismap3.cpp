@@ -2128,6 +2128,13 @@ void gpis3_impl_pass_jobs(GPisMap3* g, long long* out) {
     GPisMap3::Impl& m = *g->impl();
     for (int i = 0; i < 4; ++i) out[i] = m.mq.last_pass_jobs[i];
 }
+void gpis3_impl_pass_detail(GPisMap3* g, double* out) { g->impl()->mq.pass_detail(out); }
+int gpis3_impl_set_pass2_mode(GPisMap3* g, int mode) {
+    GPisMap3::Impl& m = *g->impl();
+    for (GPisMap3* q : m.peers) gpis3_impl_set_pass2_mode(q, mode);
+    m.mq.pass2_mode = mode;
+    return GPIS_OK;
+}
 // join the training the last update() left in flight; returns the update status (0: fine)
 int gpis3_impl_sync(GPisMap3* g) {
     GPisMap3::Impl& m = *g->impl();

@@ -62,8 +62,25 @@ public:
     void last_candidates(const int** ncand, const int** cand, int* cap) const { *ncand = d_ncand_; *cand = d_cand_; *cap = cap_n_; }
     // statistics of the last run
     long long last_evals = 0, last_flops = 0, last_touched = 0;
-    // K4 jobs of the last run per pass: 1, 2 full (two-candidate queries), 2a (value column), 2b (gradient columns)
+    // (last_flops counts the columns computed: with a prediction that includes the gradient columns of a mispredicted record,
+    // which nobody reads)
+    // Evaluations of the last run by kind, in every pass2_mode: pass 1; two-candidate queries' candidate 2 in full; value columns of
+    // candidates 2 and 3 of three-candidate queries behind the gate; the records among those that the blend reads in full --
+    // whichever pass and layout computed them
     long long last_pass_jobs[4] = {0, 0, 0, 0};
+    // How pass 2 of three-candidate queries went: jobs of pass 2F with a predicted candidate, of pass 2V, of pass 2G; records pass
+    // 2F computed in full that the blend did not read; predictions made (both candidates have a model), predictions read
+    long long last_pass_detail[6] = {0, 0, 0, 0, 0, 0};
+    float last_pick_ms = 0.f;   // time in pick_kernel (profile on)
+    // the six counts, last_pick_ms and pass2_mode (the *_pass_detail entries of the C API)
+    void pass_detail(double* out8) const {
+        for (int k = 0; k < 6; ++k) out8[k] = (double)last_pass_detail[k];
+        out8[6] = (double)last_pick_ms; out8[7] = (double)pass2_mode;
+    }
+    // 0 = value columns of both, then the gradient columns the blend reads (no prediction); 1 = the predicted candidate in full
+    // (default); 2 / 3 = always candidate 2 / 3 in full; 4 = the prediction inverted.  Same results in every mode.  GPIS_PASS2 in
+    // the environment sets the initial value.  May change between runs.
+    int pass2_mode = 1;
     int last_launches = 0;      // K4 launches of the last run
     float last_eval_ms = 0.f;   // time inside the K4 launches (hipEvents on the stream)
     int chunk = 1 << 22;
@@ -85,6 +102,9 @@ private:
     float4* d_xq_ = nullptr;
     int* d_cand_ = nullptr;     // [3][cap]
     int* d_ncand_ = nullptr;    // [cap]
+    int* d_pick_ = nullptr;     // [cap] pass 2F's candidate of a three-candidate query behind the gate: 1 or 2, else 0
+    int h_stat_[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // the job kernels' counters of the chunk (d_tot_ + 20), as of the last binning round
+    hipEvent_t evp0_ = nullptr, evp1_ = nullptr;
     int* d_jm_ = nullptr;       // [2*cap] job -> model (-1 inactive)
     int* d_jq_ = nullptr;       // [2*cap] sorted query index
     int* d_jo_ = nullptr;       // [2*cap] sorted output record
@@ -95,7 +115,7 @@ private:
     int* d_tbase_ = nullptr;    // [models]
     int* d_tile_ = nullptr;     // [3][tile_cap]
     int tile_cap_ = 0;
-    int* d_tot_ = nullptr;      // [16] totals
+    int* d_tot_ = nullptr;      // [32] totals of a binning round [0..17], counters of the chunk [20..27]
     int* d_tie_ = nullptr;      // [1] queries with an exact distance tie among their nearest candidates (list: d_jq_, free at that time)
     std::vector<int> h_maxN_, h_maxLd_;   // per class: largest N and ld (LDS sizing of K4)
     hipEvent_t ev0_ = nullptr, ev1_ = nullptr;

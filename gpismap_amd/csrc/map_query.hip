@@ -9,10 +9,15 @@
 //            scatter) and tile list construction -- all on the device.
 //   passes : 1 = every query against its nearest candidate, all columns (mean, gradient, four
 //            variances).  A query whose value variance exceeds thre falls back to its next two:
-//            with two candidates, candidate 2 in full (it is always read); with three, 2a =
-//            the value column only of candidates 2 and 3, then `decide` runs the blend's sort
-//            on the three value variances and 2b = the gradient columns of the candidates
-//            among 2 and 3 the blend reads.  The other gradient columns are never computed.
+//            with two candidates, candidate 2 in full (it is always read).  With three, the blend
+//            reads in full almost always exactly one of candidates 2 and 3: `pick` predicts which
+//            from the query's distances to the models' points, 2F = that candidate in full (in one
+//            round with the two-candidate jobs), 2V = the value column only of the other, then
+//            `decide` runs the blend's sort on the three value variances and 2G = the gradient
+//            columns of the records the blend reads that 2F did not compute (the mispredictions
+//            and the queries that read both).  A column has the same bits in every layout, so the
+//            prediction moves time only.  pass2_mode 0 is the split without a prediction: 2a = the
+//            value column of both, 2b = the gradient columns of the records the blend reads.
 //   blend  : GPisMap3.cpp:816-898 / GPisMap.cpp:685-757 (nearest, fallback to the next two
 //            when var > thre, pick or variance-weighted blend).
 #include <algorithm>
@@ -171,33 +176,163 @@ __global__ void jobs_pass2_kernel(const int* __restrict__ cand, const int* __res
     jm[2 * q + 1] = (more && nc >= 3) ? cand[(size_t)2 * cap + q] : -1;
 }
 
+// counters of a chunk (d_tot_ + kStatOff, read back with the totals of every binning round): per block in LDS first
+enum { ST_TWO = 0, ST_PFULL, ST_VALUE, ST_REPAIR, ST_UNREAD, ST_PRED, ST_HIT, ST_READ, ST_N };
+constexpr int kStatOff = 20;
+__device__ __forceinline__ void stat_add(int* sh, int slot, int k) {       // (every lane of the block calls this)
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) k += __shfl_xor(k, o);
+    if (k && (threadIdx.x & 63) == 0) atomicAdd(&sh[slot], k);
+}
+__device__ __forceinline__ void stat_flush(const int* sh, int* __restrict__ stat) {
+    __syncthreads();
+    if (threadIdx.x < ST_N && sh[threadIdx.x]) atomicAdd(&stat[threadIdx.x], sh[threadIdx.x]);
+}
+
+// pick: which of candidates 2 and 3 of a three-candidate query behind the gate runs in full (pass 2F): 1 = candidate 2, 2 =
+// candidate 3, 0 = no such query.  The blend will read the one with the smaller value variance, which is the one whose
+// training points crowd the query: score = sum over the model's points of exp(-kPickSharp |x - p|^2 / scale^2), the larger
+// wins, a tie goes to candidate 2 (NOTEBOOK: 0.97 of the picks are read, better than the mean of the 32 nearest distances at a
+// fraction of its cost -- no selection, no square root).  With one model among the two, that one.  mode 2 / 3: always
+// candidate 2 / 3; 4: the prediction inverted (the repair path under load).  Nothing read later depends on the pick.
+// One lane per query: neighbouring queries share their candidates, so a wavefront's loads of a point mostly hit one address
+// (one wavefront per query was 10 ms on the 256^3 pass, bound by the chain query -> candidates -> model -> points that every
+// wavefront walked on its own).
+constexpr float kPickSharp = 4.0f;
+__device__ __forceinline__ float pick_score(const ClusterModel* __restrict__ M, float4 x) {
+    const float4* __restrict__ p = reinterpret_cast<const float4*>(M->x4);
+    const int N = M->N;
+    const float sc = M->scale;
+    const float c = -kPickSharp * 1.44269504f / (sc * sc);
+    float acc = 0.f;
+#pragma unroll 4
+    for (int i = 0; i < N; ++i) {
+        const float4 a = p[i];
+        const float dx = a.x - x.x, dy = a.y - x.y, dz = a.z - x.z;
+        acc += exp2f(c * (dx * dx + dy * dy + dz * dz));
+    }
+    return acc;
+}
+__global__ __launch_bounds__(256) void pick_kernel(const ClusterModel* __restrict__ models, const float4* __restrict__ xq,
+                                                   const int* __restrict__ cand, const int* __restrict__ ncand, int n, int cap,
+                                                   const float* __restrict__ out, float var_thre, float prior_var, int mode,
+                                                   int* __restrict__ pick) {
+    const int q = blockIdx.x * 256 + threadIdx.x;
+    if (q >= n) return;
+    int p = 0;
+    if (ncand[q] == 3) {
+        const float v0 = (cand[q] >= 0) ? out[(size_t)q * 8 + 4] : prior_var;
+        if (v0 > var_thre) {
+            const int m1 = cand[(size_t)cap + q], m2 = cand[(size_t)2 * cap + q];
+            if (m1 >= 0 && m2 >= 0) {
+                if (mode == 2) p = 1;
+                else if (mode == 3) p = 2;
+                else {
+                    const float4 x = xq[q];
+                    const float s1 = pick_score(models + m1, x), s2 = pick_score(models + m2, x);
+                    p = (s2 > s1) ? 2 : 1;
+                    if (mode == 4) p = 3 - p;
+                }
+            } else if (m1 >= 0) p = 1;
+            else if (m2 >= 0) p = 2;
+        }
+    }
+    pick[q] = p;
+}
+
+// pass-2F jobs (all columns): job 2q+s -> candidate s+1: candidate 2 of a two-candidate query behind the gate and the picked
+// candidate of a three-candidate one.  One layout, one record addressing (cap + 2q + s): one binning round for both kinds.
+__global__ __launch_bounds__(256) void jobs_pass2f_kernel(const int* __restrict__ cand, const int* __restrict__ ncand, int n, int cap,
+                                                          const float* __restrict__ out, float var_thre, float prior_var,
+                                                          const int* __restrict__ pick, int* __restrict__ jm, int* __restrict__ stat) {
+    __shared__ int sh[ST_N];
+    if (threadIdx.x < ST_N) sh[threadIdx.x] = 0;
+    __syncthreads();
+    const int q = blockIdx.x * 256 + threadIdx.x;
+    int a = -1, b = -1, two = 0, pf = 0;
+    if (q < n) {
+        const int nc = ncand[q];
+        if (nc == 2) {
+            const float v0 = (cand[q] >= 0) ? out[(size_t)q * 8 + 4] : prior_var;
+            if (v0 > var_thre) { a = cand[(size_t)cap + q]; two = a >= 0; }
+        } else if (nc == 3) {
+            const int p = pick[q];
+            if (p == 1) a = cand[(size_t)cap + q];
+            if (p == 2) b = cand[(size_t)2 * cap + q];
+            pf = p != 0;
+        }
+        jm[2 * q] = a; jm[2 * q + 1] = b;
+    }
+    stat_add(sh, ST_TWO, two); stat_add(sh, ST_PFULL, pf);
+    stat_flush(sh, stat);
+}
+
+// pass-2V jobs (value column): the candidate among 2 and 3 that pass 2F did not take, where it has a model
+__global__ __launch_bounds__(256) void jobs_pass2v_kernel(const int* __restrict__ cand, int n, int cap, const int* __restrict__ pick,
+                                                          int* __restrict__ jm, int* __restrict__ stat) {
+    __shared__ int sh[ST_N];
+    if (threadIdx.x < ST_N) sh[threadIdx.x] = 0;
+    __syncthreads();
+    const int q = blockIdx.x * 256 + threadIdx.x;
+    int a = -1, b = -1;
+    if (q < n) {
+        const int p = pick[q];
+        if (p == 2) a = cand[(size_t)cap + q];
+        if (p == 1) b = cand[(size_t)2 * cap + q];
+        jm[2 * q] = a; jm[2 * q + 1] = b;
+    }
+    stat_add(sh, ST_VALUE, (a >= 0) + (b >= 0));
+    stat_flush(sh, stat);
+}
+
 // pass-2b jobs (decide): for a three-candidate query in pass 2, blend_kernel's stable sort of the three value variances picks
 // the record(s) it reads in full: the best alone when its variance is below thre, else the best two.  Job 2q+s (s = 0,1) ->
 // candidate s+1 when it is one of them and has a model (one without contributes the prior and got no pass-2a job).
-__global__ void jobs_decide_kernel(const int* __restrict__ cand, const int* __restrict__ ncand, int n, int cap,
-                                   const float* __restrict__ out, float var_thre, float prior_var, int* __restrict__ jm) {
-    int q = blockIdx.x * 256 + threadIdx.x;
-    if (q >= n) return;
-    jm[2 * q] = -1; jm[2 * q + 1] = -1;
-    const int nc = ncand[q];
-    if (nc != 3) return;
-    const float v0 = (cand[q] >= 0) ? out[(size_t)q * 8 + 4] : prior_var;
-    if (!(v0 > var_thre)) return;
-    const int m1 = cand[(size_t)cap + q], m2 = cand[(size_t)2 * cap + q];
-    const float v1 = (m1 >= 0) ? out[((size_t)cap + 2 * (size_t)q) * 8 + 4] : prior_var;
-    const float v2 = (m2 >= 0) ? out[((size_t)cap + 2 * (size_t)q + 1) * 8 + 4] : prior_var;
-    // blend_kernel's stable insertion sort of the indices {0, 1, 2} by value variance, comparison for comparison (written out:
-    // an indexed array here lives in scratch memory)
-    auto var = [&](int i) { return i == 0 ? v0 : (i == 1 ? v1 : v2); };
-    int b0 = 0, b1 = 1;
-    if (v1 < v0) { b0 = 1; b1 = 0; }
-    if (v2 < var(b1)) {
-        b1 = 2;
-        if (v2 < var(b0)) { b1 = b0; b0 = 2; }
+// pick (nullptr: pass2_mode 0): the candidate pass 2F computed in full needs no job; the counters tell the prediction's outcome.
+__global__ __launch_bounds__(256) void jobs_decide_kernel(const int* __restrict__ cand, const int* __restrict__ ncand, int n, int cap,
+                                                          const float* __restrict__ out, float var_thre, float prior_var,
+                                                          const int* __restrict__ pick, int* __restrict__ jm, int* __restrict__ stat) {
+    __shared__ int sh[ST_N];
+    if (threadIdx.x < ST_N) sh[threadIdx.x] = 0;
+    __syncthreads();
+    const int q = blockIdx.x * 256 + threadIdx.x;
+    bool r1 = false, r2 = false, both = false;      // candidate 2 / 3 is read in full; both have a model
+    int p = 0;
+    if (q < n) {
+        int j1 = -1, j2 = -1;
+        float v0 = 0.f;
+        const bool three = ncand[q] == 3;
+        if (three) v0 = (cand[q] >= 0) ? out[(size_t)q * 8 + 4] : prior_var;
+        if (three && v0 > var_thre) {
+            const int m1 = cand[(size_t)cap + q], m2 = cand[(size_t)2 * cap + q];
+            const float v1 = (m1 >= 0) ? out[((size_t)cap + 2 * (size_t)q) * 8 + 4] : prior_var;
+            const float v2 = (m2 >= 0) ? out[((size_t)cap + 2 * (size_t)q + 1) * 8 + 4] : prior_var;
+            // blend_kernel's stable insertion sort of the indices {0, 1, 2} by value variance, comparison for comparison (written
+            // out: an indexed array here lives in scratch memory)
+            auto var = [&](int i) { return i == 0 ? v0 : (i == 1 ? v1 : v2); };
+            int b0 = 0, b1 = 1;
+            if (v1 < v0) { b0 = 1; b1 = 0; }
+            if (v2 < var(b1)) {
+                b1 = 2;
+                if (v2 < var(b0)) { b1 = b0; b0 = 2; }
+            }
+            if (var(b0) < var_thre) b1 = -1;          // the best alone
+            r1 = m1 >= 0 && (b0 == 1 || b1 == 1);
+            r2 = m2 >= 0 && (b0 == 2 || b1 == 2);
+            both = m1 >= 0 && m2 >= 0;
+            p = pick ? pick[q] : 0;
+            if (r1 && p != 1) j1 = m1;
+            if (r2 && p != 2) j2 = m2;
+        }
+        jm[2 * q] = j1; jm[2 * q + 1] = j2;
     }
-    if (var(b0) < var_thre) b1 = -1;          // the best alone
-    if (m1 >= 0 && (b0 == 1 || b1 == 1)) jm[2 * q] = m1;
-    if (m2 >= 0 && (b0 == 2 || b1 == 2)) jm[2 * q + 1] = m2;
+    if (!pick) return;                                // (uniform)
+    stat_add(sh, ST_READ, (int)r1 + (int)r2);
+    stat_add(sh, ST_REPAIR, (int)(r1 && p != 1) + (int)(r2 && p != 2));
+    stat_add(sh, ST_UNREAD, (int)((p == 1 && !r1) || (p == 2 && !r2)));
+    stat_add(sh, ST_PRED, (int)both);
+    stat_add(sh, ST_HIT, (int)(both && ((p == 1 && r1) || (p == 2 && r2))));
+    stat_flush(sh, stat);
 }
 
 // ------------------------------------------------------------------ binning ----
@@ -421,12 +556,15 @@ __global__ void prior_only_kernel(int n, int nc2, int vidx, float prior_var, flo
 MapQuery::MapQuery(int dim, float search_half, float var_thre, float prior_var)
     : dim_(dim), search_half_(search_half), var_thre_(var_thre), prior_var_(prior_var), h_maxN_(ONGPIS_NCLASS, 0), h_maxLd_(ONGPIS_NCLASS, 0) {
     std::memset(&tv_, 0, sizeof(tv_));
+    if (const char* e = getenv("GPIS_PASS2")) { const int m = atoi(e); if (m >= 0 && m <= 4) pass2_mode = m; }
 }
 
 MapQuery::~MapQuery() {
     (void)hipFree(d_tab_); (void)hipFree(d_grid_); (void)hipFree(d_xq_); (void)hipFree(d_cand_); (void)hipFree(d_ncand_); (void)hipFree(d_tie_);
     (void)hipFree(d_jm_); (void)hipFree(d_jq_); (void)hipFree(d_jo_); (void)hipFree(d_out_); (void)hipFree(d_cnt_);
-    (void)hipFree(d_base_); (void)hipFree(d_cursor_); (void)hipFree(d_tbase_); (void)hipFree(d_tile_); (void)hipFree(d_tot_);
+    (void)hipFree(d_base_); (void)hipFree(d_cursor_); (void)hipFree(d_tbase_); (void)hipFree(d_tile_); (void)hipFree(d_tot_); (void)hipFree(d_pick_);
+    if (evp0_) (void)hipEventDestroy(evp0_);
+    if (evp1_) (void)hipEventDestroy(evp1_);
     if (ev0_) (void)hipEventDestroy(ev0_);
     if (ev1_) (void)hipEventDestroy(ev1_);
     for (int i = 0; i < kSide; ++i) { if (side_[i]) (void)hipStreamDestroy(side_[i]); if (evjoin_[i]) (void)hipEventDestroy(evjoin_[i]); }
@@ -504,13 +642,14 @@ int MapQuery::set_clusters(const std::vector<ClusterEntry>& cl, const std::vecto
 int MapQuery::ensure_scratch(int n, int nmodels) {
     if (n > cap_n_) {
         (void)hipFree(d_xq_); (void)hipFree(d_cand_); (void)hipFree(d_ncand_); (void)hipFree(d_jm_); (void)hipFree(d_jq_);
-        (void)hipFree(d_jo_); (void)hipFree(d_out_); (void)hipFree(d_tile_);
-        d_xq_ = nullptr; d_cand_ = d_ncand_ = d_jm_ = d_jq_ = d_jo_ = d_tile_ = nullptr; d_out_ = nullptr; cap_n_ = 0;
+        (void)hipFree(d_jo_); (void)hipFree(d_out_); (void)hipFree(d_tile_); (void)hipFree(d_pick_);
+        d_xq_ = nullptr; d_cand_ = d_ncand_ = d_jm_ = d_jq_ = d_jo_ = d_tile_ = d_pick_ = nullptr; d_out_ = nullptr; cap_n_ = 0;
         tile_cap_ = 0;   // d_tile_ is gone: the size check below must reallocate it even when need_tiles did not grow
         size_t c = (size_t)n;
         GPIS_HIP(hipMalloc(&d_xq_, sizeof(float4) * c));
         GPIS_HIP(hipMalloc(&d_cand_, sizeof(int) * 3 * c));
         GPIS_HIP(hipMalloc(&d_ncand_, sizeof(int) * c));
+        GPIS_HIP(hipMalloc(&d_pick_, sizeof(int) * c));
         if (!d_tie_) GPIS_HIP(hipMalloc(&d_tie_, sizeof(int) * 4));
         GPIS_HIP(hipMalloc(&d_jm_, sizeof(int) * 2 * c));
         GPIS_HIP(hipMalloc(&d_jq_, sizeof(int) * 2 * c));
@@ -562,12 +701,13 @@ int MapQuery::eval_pass(OnGPISStore& store, int njobs, int shift, int rec_base, 
     int* t_cnt = d_tile_ + 2 * (size_t)tile_cap_;
     hipLaunchKernelGGL(tiles_kernel, dim3(nmodels), dim3(64), 0, s, store.d_models(), nmodels, d_cnt_, d_base_, d_tbase_,
                        d_tot_, t_model, t_off, t_cnt, tq);
-    int tot[20];
-    GPIS_HIP(hipMemcpyAsync(tot, d_tot_, sizeof(int) * 20, hipMemcpyDeviceToHost, s));
+    int tot[kStatOff + ST_N];
+    GPIS_HIP(hipMemcpyAsync(tot, d_tot_, sizeof(int) * (kStatOff + ST_N), hipMemcpyDeviceToHost, s));
     GPIS_HIP(hipStreamSynchronize(s));
-    // (an evaluation in the reference's sense is a (query, candidate) pair: pass 2b completes evaluations pass 2a counted)
+    std::memcpy(h_stat_, tot + kStatOff, sizeof(int) * ST_N);   // (the job kernels' counters so far in this chunk)
+    // (an evaluation in the reference's sense is a (query, candidate) pair: the gradient pass completes evaluations already counted)
     if (layout != ONGPIS_LAYOUT_GRAD) last_evals += tot[15];
-    last_pass_jobs[pass] += tot[15];
+    if (pass >= 0) last_pass_jobs[pass] += tot[15];   // (pass < 0: run_chunk fills the slots from the counters)
     { unsigned long long f; std::memcpy(&f, tot + 16, sizeof(f)); last_flops += (long long)f; }
     for (int c = 0; c < ONGPIS_NCLASS; ++c) if (tot[c] > 0) ++last_launches;
     if (profile) {
@@ -650,6 +790,42 @@ int MapQuery::run_chunk(OnGPISStore& store, const float* d_x, int n, float* d_re
         hipLaunchKernelGGL(jobs_pass1_kernel, dim3(nblk), dim3(256), 0, s, d_cand_, d_ncand_, n, d_jm_);
         rc = eval_pass(store, n, 0, 0, nmodels, s, ONGPIS_LAYOUT_FULL, 0);
         if (rc) return rc;
+    }
+    if (nmodels > 0 && pass2_mode != 0) {
+        GPIS_HIP(hipMemsetAsync(d_tot_ + kStatOff, 0, sizeof(int) * ST_N, s));
+        if (profile) {
+            if (!evp0_) { GPIS_HIP(hipEventCreate(&evp0_)); GPIS_HIP(hipEventCreate(&evp1_)); }
+            GPIS_HIP(hipEventRecord(evp0_, s));
+        }
+        hipLaunchKernelGGL(pick_kernel, dim3(nblk), dim3(256), 0, s, store.d_models(), d_xq_, d_cand_, d_ncand_, n, cap_n_,
+                           d_out_, var_thre_, prior_var_, pass2_mode, d_pick_);
+        if (profile) GPIS_HIP(hipEventRecord(evp1_, s));
+        // pass 2F: candidate 2 of the two-candidate queries and the picked candidate of the three-candidate ones, in full
+        hipLaunchKernelGGL(jobs_pass2f_kernel, dim3(nblk), dim3(256), 0, s, d_cand_, d_ncand_, n, cap_n_, d_out_, var_thre_,
+                           prior_var_, d_pick_, d_jm_, d_tot_ + kStatOff);
+        rc = eval_pass(store, 2 * n, 1, cap_n_, nmodels, s, ONGPIS_LAYOUT_FULL, -1);
+        if (rc) return rc;
+        if (profile) {
+            float ms = 0.f;
+            GPIS_HIP(hipEventElapsedTime(&ms, evp0_, evp1_));
+            last_pick_ms += ms;
+        }
+        // pass 2V: the value column of the candidate not picked
+        hipLaunchKernelGGL(jobs_pass2v_kernel, dim3(nblk), dim3(256), 0, s, d_cand_, n, cap_n_, d_pick_, d_jm_, d_tot_ + kStatOff);
+        rc = eval_pass(store, 2 * n, 1, cap_n_, nmodels, s, ONGPIS_LAYOUT_VALUE, -1);
+        if (rc) return rc;
+        // pass 2G: the gradient columns of the records the blend reads in full that pass 2F did not compute
+        hipLaunchKernelGGL(jobs_decide_kernel, dim3(nblk), dim3(256), 0, s, d_cand_, d_ncand_, n, cap_n_, d_out_, var_thre_,
+                           prior_var_, d_pick_, d_jm_, d_tot_ + kStatOff);
+        rc = eval_pass(store, 2 * n, 1, cap_n_, nmodels, s, ONGPIS_LAYOUT_GRAD, -1);
+        if (rc) return rc;
+        // the documented slots, whichever pass did the work: value columns of candidates 2 and 3, records read in full
+        last_pass_jobs[1] += h_stat_[ST_TWO];
+        last_pass_jobs[2] += h_stat_[ST_PFULL] + h_stat_[ST_VALUE];
+        last_pass_jobs[3] += h_stat_[ST_READ];
+        last_pass_detail[0] += h_stat_[ST_PFULL]; last_pass_detail[1] += h_stat_[ST_VALUE]; last_pass_detail[2] += h_stat_[ST_REPAIR];
+        last_pass_detail[3] += h_stat_[ST_UNREAD]; last_pass_detail[4] += h_stat_[ST_PRED]; last_pass_detail[5] += h_stat_[ST_HIT];
+    } else if (nmodels > 0) {
         // pass 2, two-candidate queries: candidate 2 in full
         hipLaunchKernelGGL(jobs_pass2_kernel, dim3(nblk), dim3(256), 0, s, d_cand_, d_ncand_, n, cap_n_, d_out_, var_thre_,
                            prior_var_, 2, d_jm_);
@@ -662,7 +838,7 @@ int MapQuery::run_chunk(OnGPISStore& store, const float* d_x, int n, float* d_re
         if (rc) return rc;
         // pass 2b: the gradient columns of the records the blend reads in full
         hipLaunchKernelGGL(jobs_decide_kernel, dim3(nblk), dim3(256), 0, s, d_cand_, d_ncand_, n, cap_n_, d_out_, var_thre_,
-                           prior_var_, d_jm_);
+                           prior_var_, (const int*)nullptr, d_jm_, d_tot_ + kStatOff);
         rc = eval_pass(store, 2 * n, 1, cap_n_, nmodels, s, ONGPIS_LAYOUT_GRAD, 3);
         if (rc) return rc;
     }
@@ -675,8 +851,9 @@ int MapQuery::run_chunk(OnGPISStore& store, const float* d_x, int n, float* d_re
 }
 
 int MapQuery::run(OnGPISStore& store, const float* d_x, int n, float* d_res, hipStream_t s) {
-    last_evals = 0; last_eval_ms = 0.f; last_flops = 0; last_launches = 0;
+    last_evals = 0; last_eval_ms = 0.f; last_flops = 0; last_launches = 0; last_pick_ms = 0.f;
     for (long long& j : last_pass_jobs) j = 0;
+    for (long long& j : last_pass_detail) j = 0;
     if (n <= 0) return GPIS_OK;
     int rc = prepare(store, s);
     if (rc) return rc;
@@ -708,8 +885,9 @@ bool MapQuery::cluster_box(float* lo, float* hi) const {
 }
 
 int MapQuery::run_prepared(OnGPISStore& store, const float* d_x, int n, float* d_res, hipStream_t s) {
-    last_evals = 0; last_eval_ms = 0.f; last_flops = 0; last_launches = 0;
+    last_evals = 0; last_eval_ms = 0.f; last_flops = 0; last_launches = 0; last_pick_ms = 0.f;
     for (long long& j : last_pass_jobs) j = 0;
+    for (long long& j : last_pass_detail) j = 0;
     if (n <= 0) return GPIS_OK;
     int rc = GPIS_OK;
     const int nc = 2 * (1 + dim_);
@@ -725,6 +903,7 @@ int MapQuery::run_prepared(OnGPISStore& store, const float* d_x, int n, float* d
         if (rc) return rc;
     }
     GPIS_HIP(hipStreamSynchronize(s));
+    if (pass2_mode == 0) { last_pass_detail[1] = last_pass_jobs[2]; last_pass_detail[2] = last_pass_jobs[3]; }   // (no prediction made)
     if (const int ew = store.take_eval_err()) {
         // (a ring wait of K4 expired: a protocol error.  The affected queries carry NaN; the call fails instead of handing them out.)
         fprintf(stderr, "[gpismap_amd] prediction kernels reported error word 0x%x (a ring wait expired): the affected results are NaN\n", ew);

@@ -123,10 +123,25 @@ int   gpis3_get_nodes(void* map, float* out9, int cap);         /* pos3 grad3 va
  * CUs the training streams leave free, host replays of the last update() over all devices of the map (1: the host logic ran
  * once, on the lead device, however many devices train), factor records received in the last model exchange (inverses deferred) */
 int   gpis3_stats(void* map, double* out, int n);
-/* K4 jobs of the last test() per evaluation pass: [0] pass 1 (nearest candidate, all columns), [1] pass 2 of two-candidate
- * queries (candidate 2, all columns), [2] pass 2a (value column of candidates 2 and 3), [3] pass 2b (gradient columns of the
- * candidates the blend reads) */
+/* K4 evaluations of the last test() by kind: [0] pass 1 (nearest candidate, all columns), [1] candidate 2 of two-candidate
+ * queries (all columns), [2] value columns of candidates 2 and 3 of three-candidate queries, [3] the records among those that
+ * the blend reads in full (their gradient columns are needed) -- the same numbers in every pass-2 mode, whichever pass and
+ * layout did the work.  The flops of gpis3_stats count the columns computed: in the predicting modes they include the
+ * gradient columns of a candidate that was evaluated in full and then not read. */
 int   gpis3_pass_jobs(void* map, long long* out4);
+/* How test() evaluates candidates 2 and 3 of a three-candidate query whose first variance is above the threshold.  The blend
+ * reads in full almost always exactly one of them.  0: the value column of both, then the gradient columns of the records the
+ * blend reads.  1 (default): a predictor picks one from the query's distances to the models' points; that one is evaluated in
+ * full together with the two-candidate jobs, the other gets its value column, and gradient columns are computed afterwards
+ * only where the prediction missed or both are read.  2 / 3: always candidate 2 / 3 in full.  4: the predictor inverted (for
+ * tests of the repair path).  The results are the same bits in every mode; only the time differs.  The environment variable
+ * GPIS_PASS2 sets the initial mode of a new map.  Takes effect at the next test().  GPIS_ERR_ARG outside 0..4. */
+int   gpis3_set_pass2_mode(void* map, int mode);
+/* out[0..7] of the last test(): evaluations in full of a predicted candidate, value-column-only evaluations, gradient-column
+ * evaluations afterwards, predicted candidates evaluated in full that the blend did not read, predictions made (both candidates
+ * have a model), predictions the blend read, ms in the predictor kernel (profiling on), the mode.  out[0] + out[1] = [2] and
+ * out[2] + out[0] - out[3] = [3] of gpis3_pass_jobs. */
+int   gpis3_pass_detail(void* map, double* out8);
 /* Map checkpoint (optional; the reference keeps its map only in the mex singleton): gpis3_save writes the spatial
  * index, the surface points with their data and every trained model as its packed prediction record (about 2 K^2 bytes per
  * cluster: the file of a 500-cluster map is ~1.2 GB) (GPisMap3::saveMap); gpis3_load replaces the map's state with a file's.
@@ -181,6 +196,8 @@ int   gpis2_set_pipeline(void* map, int on);
 int   gpis2_get_nodes(void* map, float* out7, int cap);         /* pos2 grad2 val sigx sigg, tree order */
 int   gpis2_stats(void* map, double* out, int n);               /* same slots as gpis3_stats */
 int   gpis2_pass_jobs(void* map, long long* out4);              /* same slots as gpis3_pass_jobs */
+int   gpis2_set_pass2_mode(void* map, int mode);                /* as gpis3_set_pass2_mode */
+int   gpis2_pass_detail(void* map, double* out8);               /* same slots as gpis3_pass_detail */
 
 /* ---- kernel level: observation GP (K1, K2) -------------------------------- */
 void* gpis_obsgp_create(void);
@@ -293,6 +310,9 @@ int   gpis_mapquery_run(void* mq, const float* x, int n, float* res_inout);
 int   gpis_mapquery_candidates(void* mq, int* ncand, int* cand3);
 /* K4 jobs of the last run per pass: 1, 2 (two-candidate queries, all columns), 2a (value column), 2b (gradient columns) */
 int   gpis_mapquery_pass_jobs(void* mq, long long* out4);
+/* as gpis3_set_pass2_mode / gpis3_pass_detail */
+int   gpis_mapquery_set_pass2_mode(void* mq, int mode);
+int   gpis_mapquery_pass_detail(void* mq, double* out8);
 
 /* ---- surface extraction: the map's zero-level surface on the device (DESIGN.md "Surface extraction") ------------------
  * The map's test() on a lattice of nx x ny (x nz) points (index p = (k ny + j) nx + i, x fastest; coordinates
