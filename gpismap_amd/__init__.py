@@ -1765,7 +1765,105 @@ def tplan_opts(step, **opts):
     return o
 
 
-class TimePlanner:
+class _LayeredPlanner:
+    """What TimePlanner and TimePosePlanner share: the handle behind gpis_<_PREFIX>_*, info(), the host copies of a result and of
+    its paths, the control sequences and follow().  _WHAT names the planner in error messages."""
+
+    _PREFIX = _WHAT = None
+
+    def __init__(self):
+        self.L = lib()
+        if not hasattr(self.L, "gpis_%s_create" % self._PREFIX):
+            raise GpisError("the native library has no %s (gpis_%s_create)" % (self._WHAT, self._PREFIX))
+        if self.L.gpis_device_count() < 1:
+            raise GpisError("no HIP device: gpismap_amd has no CPU fallback")
+        self.h = C.c_void_p(self._fn("create")())
+        if not self.h:
+            raise GpisError("gpis_%s_create failed" % self._PREFIX)
+
+    def _fn(self, name):
+        return getattr(self.L, "gpis_%s_%s" % (self._PREFIX, name))
+
+    def _call(self, name, *args):
+        _check(self._fn(name)(self.h, *args), "gpis_%s_%s" % (self._PREFIX, name))
+
+    def close(self):
+        if getattr(self, "h", None):
+            self._fn("destroy")(self.h)
+            self.h = None
+
+    __del__ = close
+
+    def info(self):
+        out = np.zeros(len(self.INFO_KEYS), dtype=np.float64)
+        self._call("info", _p(out, C.c_double), out.size)
+        d = dict(zip(self.INFO_KEYS, out.tolist()))
+        for k in self.INT_KEYS:
+            d[k] = int(d[k])
+        return d
+
+    def _get(self, dims, cost_all):
+        """get() for a layer of the shape given by the info keys `dims`"""
+        i = self.info()
+        if not i["valid"]:
+            raise GpisError("%s holds no result" % self._WHAT)
+        shape, S = tuple(i[k] for k in dims), i["horizon"]
+        cost0, c = np.zeros(shape, np.float32), np.zeros(shape, np.float32)
+        pol = np.zeros((S + 1,) + shape, np.uint8)
+        call = np.zeros((S + 1,) + shape, np.float32) if cost_all else None
+        self._call("get", _p(cost0), _p(pol, C.c_ubyte), _p(call) if cost_all else None, _p(c))
+        out = dict(cost0=cost0, policy=pol, c=c)
+        if cost_all:
+            out["cost_all"] = call
+        return out
+
+    def _paths(self, x, stream, heading):
+        """paths() from the start rows x; heading: whether the handle's paths carry a heading index per point"""
+        self._call("paths", _p(x), x.shape[0], C.c_void_p(stream))
+        m, tot = C.c_longlong(0), C.c_longlong(0)
+        self._call("path_counts", C.byref(m), C.byref(tot))
+        off = np.zeros(m.value + 1, np.int64)
+        pts = np.zeros((max(tot.value, 1), 2), np.float32)
+        hd = np.zeros(max(tot.value, 1), np.int32)
+        arrive = np.zeros(m.value, np.int32)
+        sc = np.zeros(m.value, np.float32)
+        st = np.zeros(m.value, np.uint8)
+        self._call("get_paths", _p(off, C.c_longlong), _p(pts), *([_p(hd, C.c_int)] if heading else []), _p(arrive, C.c_int), _p(sc),
+                   _p(st, C.c_ubyte))
+        pts, hd = pts[:tot.value], hd[:tot.value]
+        out = dict(paths=[pts[off[k]:off[k + 1]] for k in range(m.value)], off=off, points=pts, arrive=arrive, start_cost=sc, status=st)
+        if heading:
+            out.update(headings=[hd[off[k]:off[k + 1]] for k in range(m.value)], heading=hd)
+        return out
+
+    def _npaths(self):
+        m = C.c_longlong(0)
+        self._call("path_counts", C.byref(m), None)
+        return m.value
+
+    def controls(self, T, k0=0, w_limit=0.0, min_move=1e-9):
+        """Control sequences of T steps of the plan's slot along the last paths from slot k0 on (gpis_tplan_controls): dict(U
+        f64 [m, T, 2], heading0 [m, 2], p0 [m, 2], clamped i32 [m]); a start without a path stands still."""
+        m, T = self._npaths(), int(T)
+        U = np.zeros((m, max(T, 1), 2), np.float64)
+        h0, p0, cl = np.zeros((m, 2), np.float64), np.zeros((m, 2), np.float64), np.zeros(m, np.int32)
+        self._call("controls", T, int(k0), float(w_limit), float(min_move), _p(U, C.c_double), _p(h0, C.c_double), _p(p0, C.c_double),
+                   _p(cl, C.c_int))
+        return dict(U=U, heading0=h0, p0=p0, clamped=cl)
+
+    def follow(self, controller, index, k0=0, w_limit=0.0, min_move=1e-9):
+        """Replace `controller`'s nominal sequence by the control sequence of path `index` from slot k0 on, over the controller's
+        horizon (controls + gpis_mppi_set_nominal; the controller is meant to run at dt = the plan's slot).  Returns (p0 [2],
+        heading0 [2])."""
+        i = controller.info()
+        if not i["inited"] or i["dim"] != 2:
+            raise GpisError("follow needs a 2-D controller after init")
+        r = self.controls(i["horizon"], k0, w_limit, min_move)
+        controller.set_nominal(r["U"][int(index)])
+        return r["p0"][int(index)].copy(), r["heading0"][int(index)].copy()
+
+
+class TimePlanner(_LayeredPlanner):
     """Result holder of the planner through space and time (gpis_tplan_*): a policy byte per (lattice point, slot), the cost of
     slot 0, paths, their check against moving balls and their control sequences, on the device; buffers reused across calls.
     A finished plan depends neither on the field nor on the set it was solved with."""
@@ -1775,22 +1873,7 @@ class TimePlanner:
     INT_KEYS = ("valid", "nx", "ny", "horizon", "balls", "goals", "goals_kept", "free", "finite0", "layer_launches", "skipped",
                 "keep_cost")
 
-    def __init__(self):
-        self.L = lib()
-        if not hasattr(self.L, "gpis_tplan_create"):
-            raise GpisError("the native library has no time planner (gpis_tplan_create)")
-        if self.L.gpis_device_count() < 1:
-            raise GpisError("no HIP device: gpismap_amd has no CPU fallback")
-        self.h = C.c_void_p(self.L.gpis_tplan_create())
-        if not self.h:
-            raise GpisError("gpis_tplan_create failed")
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.gpis_tplan_destroy(self.h)
-            self.h = None
-
-    __del__ = close
+    _PREFIX, _WHAT = "tplan", "time planner"
 
     def set_schedule(self, layers_per_launch=0, cull=1):
         """Layers a launch advances (0 = the default: 4 without balls, 1 with them; at most 16) and the broad phase over the balls (0 / 1); the results do not
@@ -1811,29 +1894,10 @@ class TimePlanner:
         self.dyn_clearance = float(o.dyn_clearance)
         return self
 
-    def info(self):
-        out = np.zeros(len(self.INFO_KEYS), dtype=np.float64)
-        _check(self.L.gpis_tplan_info(self.h, _p(out, C.c_double), out.size), "gpis_tplan_info")
-        d = dict(zip(self.INFO_KEYS, out.tolist()))
-        for k in self.INT_KEYS:
-            d[k] = int(d[k])
-        return d
-
     def get(self, cost_all=False):
         """dict(cost0 f32 [ny, nx], policy u8 [S + 1, ny, nx], c f32 [ny, nx]) host copies of the last result, with cost_all
         f32 [S + 1, ny, nx] on request (the solve must have kept it)."""
-        i = self.info()
-        if not i["valid"]:
-            raise GpisError("time planner holds no result")
-        ny, nx, S = i["ny"], i["nx"], i["horizon"]
-        cost0, c = np.zeros((ny, nx), np.float32), np.zeros((ny, nx), np.float32)
-        pol = np.zeros((S + 1, ny, nx), np.uint8)
-        call = np.zeros((S + 1, ny, nx), np.float32) if cost_all else None
-        _check(self.L.gpis_tplan_get(self.h, _p(cost0), _p(pol, C.c_ubyte), _p(call) if cost_all else None, _p(c)), "gpis_tplan_get")
-        out = dict(cost0=cost0, policy=pol, c=c)
-        if cost_all:
-            out["cost_all"] = call
-        return out
+        return self._get(("ny", "nx"), cost_all)
 
     def device_ptrs(self):
         """(d_cost0, d_policy) device addresses of the last result (0 where there is none)."""
@@ -1845,24 +1909,7 @@ class TimePlanner:
         """Routes from `starts` [m, 2] at slot 0 along the policy (gpis_tplan_paths).  Returns dict(paths: list of [arrive + 1,
         2] float32 arrays, one point per slot; off i64 [m + 1]; points f32 [total, 2]; arrive i32 [m]; start_cost f32 [m];
         status u8 [m]: 0 arrived, 1 outside / non-finite, 2 not free, 3 no arrival within the horizon)."""
-        x = np.ascontiguousarray(starts, dtype=np.float32).reshape(-1, 2)
-        _check(self.L.gpis_tplan_paths(self.h, _p(x), x.shape[0], C.c_void_p(stream)), "gpis_tplan_paths")
-        m, tot = C.c_longlong(0), C.c_longlong(0)
-        _check(self.L.gpis_tplan_path_counts(self.h, C.byref(m), C.byref(tot)), "gpis_tplan_path_counts")
-        off = np.zeros(m.value + 1, np.int64)
-        pts = np.zeros((max(tot.value, 1), 2), np.float32)
-        arrive = np.zeros(m.value, np.int32)
-        sc = np.zeros(m.value, np.float32)
-        st = np.zeros(m.value, np.uint8)
-        _check(self.L.gpis_tplan_get_paths(self.h, _p(off, C.c_longlong), _p(pts), _p(arrive, C.c_int), _p(sc), _p(st, C.c_ubyte)),
-               "gpis_tplan_get_paths")
-        pts = pts[:tot.value]
-        return dict(paths=[pts[off[k]:off[k + 1]] for k in range(m.value)], off=off, points=pts, arrive=arrive, start_cost=sc, status=st)
-
-    def _npaths(self):
-        m = C.c_longlong(0)
-        _check(self.L.gpis_tplan_path_counts(self.h, C.byref(m), None), "gpis_tplan_path_counts")
-        return m.value
+        return self._paths(np.ascontiguousarray(starts, dtype=np.float32).reshape(-1, 2), stream, False)
 
     def check(self, obstacles, clearance=None):
         """The last paths against the balls of `obstacles` (any 2-D set: the solve's, or a newer detection) at the solve's
@@ -1876,27 +1923,6 @@ class TimePlanner:
         _check(self.L.gpis_tplan_check(self.h, obstacles.h, float(clearance), _p(ms, C.c_double), _p(mt, C.c_double), _p(mo, C.c_int),
                                        _p(fh, C.c_int), _p(co, C.c_int)), "gpis_tplan_check")
         return dict(min_sep=ms, min_time=mt, min_obstacle=mo, first_hit=fh, collides=co)
-
-    def controls(self, T, k0=0, w_limit=0.0, min_move=1e-9):
-        """Control sequences of T steps of the plan's slot along the last paths from slot k0 on (gpis_tplan_controls): dict(U
-        f64 [m, T, 2], heading0 [m, 2], p0 [m, 2], clamped i32 [m]); a start without a path stands still."""
-        m, T = self._npaths(), int(T)
-        U = np.zeros((m, max(T, 1), 2), np.float64)
-        h0, p0, cl = np.zeros((m, 2), np.float64), np.zeros((m, 2), np.float64), np.zeros(m, np.int32)
-        _check(self.L.gpis_tplan_controls(self.h, T, int(k0), float(w_limit), float(min_move), _p(U, C.c_double), _p(h0, C.c_double),
-                                          _p(p0, C.c_double), _p(cl, C.c_int)), "gpis_tplan_controls")
-        return dict(U=U, heading0=h0, p0=p0, clamped=cl)
-
-    def follow(self, controller, index, k0=0, w_limit=0.0, min_move=1e-9):
-        """Replace `controller`'s nominal sequence by the control sequence of path `index` from slot k0 on, over the controller's
-        horizon (controls + gpis_mppi_set_nominal; the controller is meant to run at dt = the plan's slot).  Returns (p0 [2],
-        heading0 [2])."""
-        i = controller.info()
-        if not i["inited"] or i["dim"] != 2:
-            raise GpisError("follow needs a 2-D controller after init")
-        r = self.controls(i["horizon"], k0, w_limit, min_move)
-        controller.set_nominal(r["U"][int(index)])
-        return r["p0"][int(index)].copy(), r["heading0"][int(index)].copy()
 
 
 POSE_HEADINGS = (8, 16, 32, 64)
@@ -2095,7 +2121,7 @@ def tpplan_opts(step, H=16, **opts):
     return o
 
 
-class TimePosePlanner:
+class TimePosePlanner(_LayeredPlanner):
     """Result holder of the time-pose planner (gpis_tpplan_*): a policy byte per (lattice point, heading index, slot), the cost
     of slot 0, pose paths, their check against moving balls with a footprint, and their control sequences, on the device;
     buffers reused across calls.  A finished plan depends on neither the field, the set nor the footprint it was solved with."""
@@ -2105,22 +2131,7 @@ class TimePosePlanner:
     INT_KEYS = ("valid", "nx", "ny", "H", "horizon", "balls", "body_balls", "goals", "goals_kept", "free", "finite0", "keep_cost",
                 "launches", "skipped")
 
-    def __init__(self):
-        self.L = lib()
-        if not hasattr(self.L, "gpis_tpplan_create"):
-            raise GpisError("the native library has no time-pose planner (gpis_tpplan_create)")
-        if self.L.gpis_device_count() < 1:
-            raise GpisError("no HIP device: gpismap_amd has no CPU fallback")
-        self.h = C.c_void_p(self.L.gpis_tpplan_create())
-        if not self.h:
-            raise GpisError("gpis_tpplan_create failed")
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.gpis_tpplan_destroy(self.h)
-            self.h = None
-
-    __del__ = close
+    _PREFIX, _WHAT = "tpplan", "time-pose planner"
 
     def set_schedule(self, cull=1):
         """The broad phase over the balls (0 / 1); the results do not depend on it."""
@@ -2147,29 +2158,10 @@ class TimePosePlanner:
         self.dyn_clearance = float(o.dyn_clearance)
         return self
 
-    def info(self):
-        out = np.zeros(len(self.INFO_KEYS), dtype=np.float64)
-        _check(self.L.gpis_tpplan_info(self.h, _p(out, C.c_double), out.size), "gpis_tpplan_info")
-        d = dict(zip(self.INFO_KEYS, out.tolist()))
-        for k in self.INT_KEYS:
-            d[k] = int(d[k])
-        return d
-
     def get(self, cost_all=False):
         """dict(cost0 f32 [H, ny, nx], policy u8 [S + 1, H, ny, nx], c f32 [H, ny, nx]) host copies of the last result, with
         cost_all f32 [S + 1, H, ny, nx] on request (the solve must have kept it)."""
-        i = self.info()
-        if not i["valid"]:
-            raise GpisError("time-pose planner holds no result")
-        shape, S = (i["H"], i["ny"], i["nx"]), i["horizon"]
-        cost0, c = np.zeros(shape, np.float32), np.zeros(shape, np.float32)
-        pol = np.zeros((S + 1,) + shape, np.uint8)
-        call = np.zeros((S + 1,) + shape, np.float32) if cost_all else None
-        _check(self.L.gpis_tpplan_get(self.h, _p(cost0), _p(pol, C.c_ubyte), _p(call) if cost_all else None, _p(c)), "gpis_tpplan_get")
-        out = dict(cost0=cost0, policy=pol, c=c)
-        if cost_all:
-            out["cost_all"] = call
-        return out
+        return self._get(("H", "ny", "nx"), cost_all)
 
     def paths(self, starts, stream=0):
         """Pose routes from `starts` [m, 3] = (x, y, h) at slot 0 along the policy (gpis_tpplan_paths); h = -1: the free heading
@@ -2177,26 +2169,7 @@ class TimePosePlanner:
         per slot; headings: list of [arrive + 1] int32 heading indices; off i64 [m + 1]; points f32 [total, 2]; heading i32
         [total]; arrive i32 [m]; start_cost f32 [m]; status u8 [m]: 0 arrived, 1 outside / non-finite, 2 not free, 3 no arrival
         within the horizon)."""
-        x = _pose_rows(starts)
-        _check(self.L.gpis_tpplan_paths(self.h, _p(x), x.shape[0], C.c_void_p(stream)), "gpis_tpplan_paths")
-        m, tot = C.c_longlong(0), C.c_longlong(0)
-        _check(self.L.gpis_tpplan_path_counts(self.h, C.byref(m), C.byref(tot)), "gpis_tpplan_path_counts")
-        off = np.zeros(m.value + 1, np.int64)
-        pts = np.zeros((max(tot.value, 1), 2), np.float32)
-        hd = np.zeros(max(tot.value, 1), np.int32)
-        arrive = np.zeros(m.value, np.int32)
-        sc = np.zeros(m.value, np.float32)
-        st = np.zeros(m.value, np.uint8)
-        _check(self.L.gpis_tpplan_get_paths(self.h, _p(off, C.c_longlong), _p(pts), _p(hd, C.c_int), _p(arrive, C.c_int), _p(sc),
-                                            _p(st, C.c_ubyte)), "gpis_tpplan_get_paths")
-        pts, hd = pts[:tot.value], hd[:tot.value]
-        return dict(paths=[pts[off[k]:off[k + 1]] for k in range(m.value)], headings=[hd[off[k]:off[k + 1]] for k in range(m.value)],
-                    off=off, points=pts, heading=hd, arrive=arrive, start_cost=sc, status=st)
-
-    def _npaths(self):
-        m = C.c_longlong(0)
-        _check(self.L.gpis_tpplan_path_counts(self.h, C.byref(m), None), "gpis_tpplan_path_counts")
-        return m.value
+        return self._paths(_pose_rows(starts), stream, True)
 
     def check(self, obstacles, footprint=None, clearance=None):
         """The last paths against the balls of `obstacles` (any 2-D set) with `footprint` (any 2-D Footprint; None: the solve's)
@@ -2216,23 +2189,7 @@ class TimePosePlanner:
         """Control sequences of T steps of the plan's slot along the points of the last paths from slot k0 on
         (gpis_tpplan_controls): dict(U f64 [m, T, 2], heading0 [m, 2], p0 [m, 2], clamped i32 [m]); a start without a path
         stands still.  The heading indices are not tracked: the pose path is the certificate, the controls are a guide."""
-        m, T = self._npaths(), int(T)
-        U = np.zeros((m, max(T, 1), 2), np.float64)
-        h0, p0, cl = np.zeros((m, 2), np.float64), np.zeros((m, 2), np.float64), np.zeros(m, np.int32)
-        _check(self.L.gpis_tpplan_controls(self.h, T, int(k0), float(w_limit), float(min_move), _p(U, C.c_double), _p(h0, C.c_double),
-                                           _p(p0, C.c_double), _p(cl, C.c_int)), "gpis_tpplan_controls")
-        return dict(U=U, heading0=h0, p0=p0, clamped=cl)
-
-    def follow(self, controller, index, k0=0, w_limit=0.0, min_move=1e-9):
-        """Replace `controller`'s nominal sequence by the control sequence of path `index` from slot k0 on, over the controller's
-        horizon (controls + gpis_mppi_set_nominal; the controller is meant to run at dt = the plan's slot).  Returns (p0 [2],
-        heading0 [2])."""
-        i = controller.info()
-        if not i["inited"] or i["dim"] != 2:
-            raise GpisError("follow needs a 2-D controller after init")
-        r = self.controls(i["horizon"], k0, w_limit, min_move)
-        controller.set_nominal(r["U"][int(index)])
-        return r["p0"][int(index)].copy(), r["heading0"][int(index)].copy()
+        return super().controls(T, k0, w_limit, min_move)
 
 
 def cover_opts(dim, step, **opts):

@@ -2553,6 +2553,113 @@ int gpis_pplan_project(void* pplan, void* plan, unsigned char* heading2) {
     } catch (...) { q.clear_result(); return GPIS_ERR_STATE; }
 }
 
+// ---- planning through space and time: what gpis_tplan_* and gpis_tpplan_* share, over the handle type -------------------------------
+}  // extern "C"
+
+namespace {
+
+template <class P>
+int tp_check_size(long long states, int horizon, int keep_cost) {
+    return states * (long long)(horizon + 1) > (keep_cost ? P::kMaxStatesKept : P::kMaxStates) ? GPIS_ERR_LIMIT : GPIS_OK;
+}
+template <class P>
+void* tp_create() {
+    if (gpis_device_count() < 1) { fprintf(stderr, "[gpismap_amd] no HIP device\n"); return nullptr; }
+    P* p = new (std::nothrow) P();
+    if (p && !p->own) { delete p; return nullptr; }
+    return p;
+}
+// bind to the field's device and solve; whatever fails, the handle holds no result afterwards
+template <class P, class Solve>
+int tp_solve(P& p, int device, Solve solve) {
+    DeviceScope ds(device);
+    try {
+        if (int rc = p.bind(device)) { p.clear_result(); return rc; }
+        const int rc = solve();
+        if (rc != GPIS_OK) p.clear_result();
+        return rc;
+    } catch (...) { p.clear_result(); return GPIS_ERR_STATE; }
+}
+template <class P>
+int tp_get(void* h, float* cost0, unsigned char* policy, float* cost_all, float* c) {
+    if (!h) return GPIS_ERR_ARG;
+    P& p = *(P*)h;
+    if (!p.valid || (cost_all && !p.kept)) return GPIS_ERR_STATE;
+    DeviceScope ds(p.device);
+    const size_t n = (size_t)p.ns, ns = n * (size_t)(p.S + 1);
+    if (cost0) GPIS_HIP(hipMemcpyAsync(cost0, p.d_cost0, sizeof(float) * n, hipMemcpyDeviceToHost, p.own));
+    if (policy) GPIS_HIP(hipMemcpyAsync(policy, p.d_policy, ns, hipMemcpyDeviceToHost, p.own));
+    if (cost_all) GPIS_HIP(hipMemcpyAsync(cost_all, p.d_all, sizeof(float) * ns, hipMemcpyDeviceToHost, p.own));
+    if (c) GPIS_HIP(hipMemcpyAsync(c, p.d_c, sizeof(float) * n, hipMemcpyDeviceToHost, p.own));
+    GPIS_HIP(hipStreamSynchronize(p.own));
+    return GPIS_OK;
+}
+// the checks of a paths call that do not look at the starts' values
+template <class P>
+int tp_paths_args(void* h, const float* starts, int m) {
+    if (!h || !starts || m < 1) return GPIS_ERR_ARG;
+    if (!((P*)h)->valid) return GPIS_ERR_STATE;
+    return m > P::kMaxStarts ? GPIS_ERR_LIMIT : GPIS_OK;
+}
+template <class P>
+int tp_paths(P& p, const float* starts, int m, void* stream) {
+    DeviceScope ds(p.device);
+    try {
+        const int rc = p.paths(starts, m, stream ? (hipStream_t)stream : p.own);
+        if (rc != GPIS_OK) p.paths_valid = false;
+        return rc;
+    } catch (...) { p.paths_valid = false; return GPIS_ERR_STATE; }
+}
+template <class P>
+int tp_path_counts(void* h, long long* npaths, long long* npoints) {
+    if (!h) return GPIS_ERR_ARG;
+    const P& p = *(P*)h;
+    if (!p.valid || !p.paths_valid) return GPIS_ERR_STATE;
+    if (npaths) *npaths = p.npaths;
+    if (npoints) *npoints = p.npoints;
+    return GPIS_OK;
+}
+// d_heading: the handle's device buffer of a heading index per point, where it has one (heading: host [npoints] or null)
+template <class P>
+int tp_get_paths(void* h, long long* off, float* points, int* heading, const int* d_heading, int* arrive, float* start_cost,
+                 unsigned char* status) {
+    if (!h) return GPIS_ERR_ARG;
+    P& p = *(P*)h;
+    if (!p.valid || !p.paths_valid) return GPIS_ERR_STATE;
+    DeviceScope ds(p.device);
+    const size_t m = (size_t)p.npaths;
+    std::vector<long long> ho(m + 1);
+    std::vector<unsigned char> hs(m);
+    GPIS_HIP(hipMemcpyAsync(ho.data(), p.d_off, sizeof(long long) * (m + 1), hipMemcpyDeviceToHost, p.own));
+    GPIS_HIP(hipMemcpyAsync(hs.data(), p.d_status, m, hipMemcpyDeviceToHost, p.own));
+    if (points && p.npoints > 0)
+        GPIS_HIP(hipMemcpyAsync(points, p.d_points, sizeof(float) * (size_t)p.npoints * 2, hipMemcpyDeviceToHost, p.own));
+    if (heading && d_heading && p.npoints > 0)
+        GPIS_HIP(hipMemcpyAsync(heading, d_heading, sizeof(int) * (size_t)p.npoints, hipMemcpyDeviceToHost, p.own));
+    if (start_cost) GPIS_HIP(hipMemcpyAsync(start_cost, p.d_scost, sizeof(float) * m, hipMemcpyDeviceToHost, p.own));
+    GPIS_HIP(hipStreamSynchronize(p.own));
+    for (size_t k = 0; k < m; ++k) {
+        if (off) off[k] = ho[k];
+        if (status) status[k] = hs[k];
+        if (arrive) arrive[k] = hs[k] == 0 ? (int)(ho[k + 1] - ho[k]) - 1 : -1;
+    }
+    if (off) off[m] = ho[m];
+    return GPIS_OK;
+}
+template <class P>
+int tp_controls(void* h, int T, int k0, double w_limit, double min_move, double* U, double* heading0, double* p0, int* clamped) {
+    if (!h || k0 < 0 || k0 > (1 << 20) || T < 1 || T > P::kMaxT) return GPIS_ERR_ARG;
+    if (!std::isfinite(w_limit) || !std::isfinite(min_move) || w_limit < 0.0 || min_move < 0.0) return GPIS_ERR_ARG;
+    P& p = *(P*)h;
+    if (!p.valid || !p.paths_valid) return GPIS_ERR_STATE;
+    DeviceScope ds(p.device);
+    try { return p.controls(T, k0, w_limit, min_move, U, heading0, p0, clamped); } catch (...) { return GPIS_ERR_STATE; }
+}
+
+}  // namespace
+
+extern "C" {
+
 // ---- planning through space and time around moving balls -----------------------------------------------------------------------
 int gpis_tplan_default_opts(float step, gpis_tplan_opts* o) {
     if (!o || !(std::isfinite(step) && step > 0.f)) return GPIS_ERR_ARG;
@@ -2567,22 +2674,13 @@ static TimePlanOpts tplan_opts_of(const gpis_tplan_opts* opts) {
     o.keep_cost = opts->keep_cost;
     return o;
 }
-static int tplan_check_size(long long points, const TimePlanOpts& o) {
-    return points * (long long)(o.horizon + 1) > (o.keep_cost ? TimePlanner::kMaxStatesKept : TimePlanner::kMaxStates) ? GPIS_ERR_LIMIT
-                                                                                                                      : GPIS_OK;
-}
 int gpis_tplan_check_opts(const gpis_tplan_opts* opts, int nx, int ny) {
     if (!opts || nx < 0 || ny < 0) return GPIS_ERR_ARG;
     const TimePlanOpts o = tplan_opts_of(opts);
     if (int rc = tplan_check_opts(o)) return rc;
-    return tplan_check_size((long long)nx * ny, o);
+    return tp_check_size<TimePlanner>((long long)nx * ny, o.horizon, o.keep_cost);
 }
-void* gpis_tplan_create(void) {
-    if (gpis_device_count() < 1) { fprintf(stderr, "[gpismap_amd] no HIP device\n"); return nullptr; }
-    TimePlanner* p = new (std::nothrow) TimePlanner();
-    if (p && !p->own) { delete p; return nullptr; }
-    return p;
-}
+void* gpis_tplan_create(void) { return tp_create<TimePlanner>(); }
 void gpis_tplan_destroy(void* tplan) { delete (TimePlanner*)tplan; }
 int gpis_tplan_set_schedule(void* tplan, int layers_per_launch, int cull) {
     if (!tplan || layers_per_launch < 0 || layers_per_launch > TimePlanner::kMaxLayers || (cull != 0 && cull != 1)) return GPIS_ERR_ARG;
@@ -2608,15 +2706,9 @@ int gpis_tplan_solve(void* tplan, void* d, void* obst, const float* goals, int n
     if (df.dim != 2) return GPIS_ERR_ARG;
     const Obstacles* ob = (const Obstacles*)obst;
     if (ob && (ob->device != df.device || (ob->inited && ob->n > 0 && ob->dim != 2))) return GPIS_ERR_ARG;
-    if (int rc = tplan_check_size(df.ngrid, o)) return rc;
+    if (int rc = tp_check_size<TimePlanner>(df.ngrid, o.horizon, o.keep_cost)) return rc;
     TimePlanner& p = *(TimePlanner*)tplan;
-    DeviceScope ds(df.device);
-    try {
-        if (int rc = p.bind(df.device)) { p.clear_result(); return rc; }
-        const int rc = p.solve(df, ob, goals, ngoals, t_begin, o, stream ? (hipStream_t)stream : df.own);
-        if (rc != GPIS_OK) p.clear_result();
-        return rc;
-    } catch (...) { p.clear_result(); return GPIS_ERR_STATE; }
+    return tp_solve(p, df.device, [&] { return p.solve(df, ob, goals, ngoals, t_begin, o, stream ? (hipStream_t)stream : df.own); });
 }
 int gpis_tplan_info(void* tplan, double* out, int n) {
     if (!tplan || !out || n < 0) return GPIS_ERR_ARG;
@@ -2629,17 +2721,7 @@ int gpis_tplan_info(void* tplan, double* out, int n) {
     return GPIS_OK;
 }
 int gpis_tplan_get(void* tplan, float* cost0, unsigned char* policy, float* cost_all, float* c) {
-    if (!tplan) return GPIS_ERR_ARG;
-    TimePlanner& p = *(TimePlanner*)tplan;
-    if (!p.valid || (cost_all && !p.kept)) return GPIS_ERR_STATE;
-    DeviceScope ds(p.device);
-    const size_t n = (size_t)p.np, ns = n * (size_t)(p.S + 1);
-    if (cost0) GPIS_HIP(hipMemcpyAsync(cost0, p.d_cost0, sizeof(float) * n, hipMemcpyDeviceToHost, p.own));
-    if (policy) GPIS_HIP(hipMemcpyAsync(policy, p.d_policy, ns, hipMemcpyDeviceToHost, p.own));
-    if (cost_all) GPIS_HIP(hipMemcpyAsync(cost_all, p.d_all, sizeof(float) * ns, hipMemcpyDeviceToHost, p.own));
-    if (c) GPIS_HIP(hipMemcpyAsync(c, p.d_c, sizeof(float) * n, hipMemcpyDeviceToHost, p.own));
-    GPIS_HIP(hipStreamSynchronize(p.own));
-    return GPIS_OK;
+    return tp_get<TimePlanner>(tplan, cost0, policy, cost_all, c);
 }
 int gpis_tplan_device(void* tplan, const float** d_cost0, const unsigned char** d_policy) {
     if (!tplan) return GPIS_ERR_ARG;
@@ -2649,46 +2731,12 @@ int gpis_tplan_device(void* tplan, const float** d_cost0, const unsigned char** 
     return GPIS_OK;
 }
 int gpis_tplan_paths(void* tplan, const float* starts, int m, void* stream) {
-    if (!tplan || !starts || m < 1) return GPIS_ERR_ARG;
-    TimePlanner& p = *(TimePlanner*)tplan;
-    if (!p.valid) return GPIS_ERR_STATE;
-    if (m > TimePlanner::kMaxStarts) return GPIS_ERR_LIMIT;
-    DeviceScope ds(p.device);
-    try {
-        const int rc = p.paths(starts, m, stream ? (hipStream_t)stream : p.own);
-        if (rc != GPIS_OK) p.paths_valid = false;
-        return rc;
-    } catch (...) { p.paths_valid = false; return GPIS_ERR_STATE; }
+    if (int rc = tp_paths_args<TimePlanner>(tplan, starts, m)) return rc;
+    return tp_paths(*(TimePlanner*)tplan, starts, m, stream);
 }
-int gpis_tplan_path_counts(void* tplan, long long* npaths, long long* npoints) {
-    if (!tplan) return GPIS_ERR_ARG;
-    const TimePlanner& p = *(TimePlanner*)tplan;
-    if (!p.valid || !p.paths_valid) return GPIS_ERR_STATE;
-    if (npaths) *npaths = p.npaths;
-    if (npoints) *npoints = p.npoints;
-    return GPIS_OK;
-}
+int gpis_tplan_path_counts(void* tplan, long long* npaths, long long* npoints) { return tp_path_counts<TimePlanner>(tplan, npaths, npoints); }
 int gpis_tplan_get_paths(void* tplan, long long* off, float* points, int* arrive, float* start_cost, unsigned char* status) {
-    if (!tplan) return GPIS_ERR_ARG;
-    TimePlanner& p = *(TimePlanner*)tplan;
-    if (!p.valid || !p.paths_valid) return GPIS_ERR_STATE;
-    DeviceScope ds(p.device);
-    const size_t m = (size_t)p.npaths;
-    std::vector<long long> ho(m + 1);
-    std::vector<unsigned char> hs(m);
-    GPIS_HIP(hipMemcpyAsync(ho.data(), p.d_off, sizeof(long long) * (m + 1), hipMemcpyDeviceToHost, p.own));
-    GPIS_HIP(hipMemcpyAsync(hs.data(), p.d_status, m, hipMemcpyDeviceToHost, p.own));
-    if (points && p.npoints > 0)
-        GPIS_HIP(hipMemcpyAsync(points, p.d_points, sizeof(float) * (size_t)p.npoints * 2, hipMemcpyDeviceToHost, p.own));
-    if (start_cost) GPIS_HIP(hipMemcpyAsync(start_cost, p.d_scost, sizeof(float) * m, hipMemcpyDeviceToHost, p.own));
-    GPIS_HIP(hipStreamSynchronize(p.own));
-    for (size_t k = 0; k < m; ++k) {
-        if (off) off[k] = ho[k];
-        if (status) status[k] = hs[k];
-        if (arrive) arrive[k] = hs[k] == 0 ? (int)(ho[k + 1] - ho[k]) - 1 : -1;
-    }
-    if (off) off[m] = ho[m];
-    return GPIS_OK;
+    return tp_get_paths<TimePlanner>(tplan, off, points, nullptr, nullptr, arrive, start_cost, status);
 }
 int gpis_tplan_check(void* tplan, void* obst, double clearance, double* min_sep, double* min_time, int* min_obstacle, int* first_hit,
                      int* collides) {
@@ -2702,12 +2750,7 @@ int gpis_tplan_check(void* tplan, void* obst, double clearance, double* min_sep,
 }
 int gpis_tplan_controls(void* tplan, int T, int k0, double w_limit, double min_move, double* U, double* heading0, double* p0,
                         int* clamped) {
-    if (!tplan || k0 < 0 || k0 > (1 << 20) || T < 1 || T > TimePlanner::kMaxT) return GPIS_ERR_ARG;
-    if (!std::isfinite(w_limit) || !std::isfinite(min_move) || w_limit < 0.0 || min_move < 0.0) return GPIS_ERR_ARG;
-    TimePlanner& p = *(TimePlanner*)tplan;
-    if (!p.valid || !p.paths_valid) return GPIS_ERR_STATE;
-    DeviceScope ds(p.device);
-    try { return p.controls(T, k0, w_limit, min_move, U, heading0, p0, clamped); } catch (...) { return GPIS_ERR_STATE; }
+    return tp_controls<TimePlanner>(tplan, T, k0, w_limit, min_move, U, heading0, p0, clamped);
 }
 
 // ---- planning through space and time for the robot's footprint ------------------------------------------------------------------
@@ -2725,23 +2768,13 @@ static TimePosePlanOpts tpplan_opts_of(const gpis_tpplan_opts* opts) {
     o.keep_cost = opts->keep_cost;
     return o;
 }
-static int tpplan_check_size(long long points, int H, const TimePosePlanOpts& o) {
-    return points * H * (long long)(o.horizon + 1) > (o.keep_cost ? TimePosePlanner::kMaxStatesKept : TimePosePlanner::kMaxStates)
-               ? GPIS_ERR_LIMIT
-               : GPIS_OK;
-}
 int gpis_tpplan_check_opts(const gpis_tpplan_opts* opts, int H, int nx, int ny) {
     if (!opts || !tpplan_h_ok(H) || nx < 0 || ny < 0) return GPIS_ERR_ARG;
     const TimePosePlanOpts o = tpplan_opts_of(opts);
     if (int rc = tpplan_check_opts(o, 0.f)) return rc;
-    return tpplan_check_size((long long)nx * ny, H, o);
+    return tp_check_size<TimePosePlanner>((long long)nx * ny * H, o.horizon, o.keep_cost);
 }
-void* gpis_tpplan_create(void) {
-    if (gpis_device_count() < 1) { fprintf(stderr, "[gpismap_amd] no HIP device\n"); return nullptr; }
-    TimePosePlanner* p = new (std::nothrow) TimePosePlanner();
-    if (p && !p->own) { delete p; return nullptr; }
-    return p;
-}
+void* gpis_tpplan_create(void) { return tp_create<TimePosePlanner>(); }
 void gpis_tpplan_destroy(void* tpp) { delete (TimePosePlanner*)tpp; }
 int gpis_tpplan_set_schedule(void* tpp, int cull) {
     if (!tpp || (cull != 0 && cull != 1)) return GPIS_ERR_ARG;
@@ -2773,15 +2806,11 @@ int gpis_tpplan_solve(void* tpp, void* d, void* obst, void* body, const double* 
     if (b.device != df.device) return GPIS_ERR_ARG;
     const Obstacles* ob = (const Obstacles*)obst;
     if (ob && (ob->device != df.device || (ob->inited && ob->n > 0 && ob->dim != 2))) return GPIS_ERR_ARG;
-    if (int rc = tpplan_check_size(df.ngrid, H, o)) return rc;
+    if (int rc = tp_check_size<TimePosePlanner>(df.ngrid * H, o.horizon, o.keep_cost)) return rc;
     TimePosePlanner& p = *(TimePosePlanner*)tpp;
-    DeviceScope ds(df.device);
-    try {
-        if (int rc = p.bind(df.device)) { p.clear_result(); return rc; }
-        const int rc = p.solve(df, ob, b, headings, moves, H, goals, ngoals, t_begin, o, stream ? (hipStream_t)stream : df.own);
-        if (rc != GPIS_OK) p.clear_result();
-        return rc;
-    } catch (...) { p.clear_result(); return GPIS_ERR_STATE; }
+    return tp_solve(p, df.device, [&] {
+        return p.solve(df, ob, b, headings, moves, H, goals, ngoals, t_begin, o, stream ? (hipStream_t)stream : df.own);
+    });
 }
 int gpis_tpplan_info(void* tpp, double* out, int n) {
     if (!tpp || !out || n < 0) return GPIS_ERR_ARG;
@@ -2795,62 +2824,17 @@ int gpis_tpplan_info(void* tpp, double* out, int n) {
     return GPIS_OK;
 }
 int gpis_tpplan_get(void* tpp, float* cost0, unsigned char* policy, float* cost_all, float* c) {
-    if (!tpp) return GPIS_ERR_ARG;
-    TimePosePlanner& p = *(TimePosePlanner*)tpp;
-    if (!p.valid || (cost_all && !p.kept)) return GPIS_ERR_STATE;
-    DeviceScope ds(p.device);
-    const size_t n = (size_t)p.ns, ns = n * (size_t)(p.S + 1);
-    if (cost0) GPIS_HIP(hipMemcpyAsync(cost0, p.d_cost0, sizeof(float) * n, hipMemcpyDeviceToHost, p.own));
-    if (policy) GPIS_HIP(hipMemcpyAsync(policy, p.d_policy, ns, hipMemcpyDeviceToHost, p.own));
-    if (cost_all) GPIS_HIP(hipMemcpyAsync(cost_all, p.d_all, sizeof(float) * ns, hipMemcpyDeviceToHost, p.own));
-    if (c) GPIS_HIP(hipMemcpyAsync(c, p.d_c, sizeof(float) * n, hipMemcpyDeviceToHost, p.own));
-    GPIS_HIP(hipStreamSynchronize(p.own));
-    return GPIS_OK;
+    return tp_get<TimePosePlanner>(tpp, cost0, policy, cost_all, c);
 }
 int gpis_tpplan_paths(void* tpp, const float* starts, int m, void* stream) {
-    if (!tpp || !starts || m < 1) return GPIS_ERR_ARG;
+    if (int rc = tp_paths_args<TimePosePlanner>(tpp, starts, m)) return rc;
     TimePosePlanner& p = *(TimePosePlanner*)tpp;
-    if (!p.valid) return GPIS_ERR_STATE;
-    if (m > TimePosePlanner::kMaxStarts) return GPIS_ERR_LIMIT;
     for (int t = 0; t < m; ++t) if (!pplan_heading_ok(starts[(size_t)t * 3 + 2], p.H)) return GPIS_ERR_ARG;
-    DeviceScope ds(p.device);
-    try {
-        const int rc = p.paths(starts, m, stream ? (hipStream_t)stream : p.own);
-        if (rc != GPIS_OK) p.paths_valid = false;
-        return rc;
-    } catch (...) { p.paths_valid = false; return GPIS_ERR_STATE; }
+    return tp_paths(p, starts, m, stream);
 }
-int gpis_tpplan_path_counts(void* tpp, long long* npaths, long long* npoints) {
-    if (!tpp) return GPIS_ERR_ARG;
-    const TimePosePlanner& p = *(TimePosePlanner*)tpp;
-    if (!p.valid || !p.paths_valid) return GPIS_ERR_STATE;
-    if (npaths) *npaths = p.npaths;
-    if (npoints) *npoints = p.npoints;
-    return GPIS_OK;
-}
+int gpis_tpplan_path_counts(void* tpp, long long* npaths, long long* npoints) { return tp_path_counts<TimePosePlanner>(tpp, npaths, npoints); }
 int gpis_tpplan_get_paths(void* tpp, long long* off, float* points, int* heading, int* arrive, float* start_cost, unsigned char* status) {
-    if (!tpp) return GPIS_ERR_ARG;
-    TimePosePlanner& p = *(TimePosePlanner*)tpp;
-    if (!p.valid || !p.paths_valid) return GPIS_ERR_STATE;
-    DeviceScope ds(p.device);
-    const size_t m = (size_t)p.npaths;
-    std::vector<long long> ho(m + 1);
-    std::vector<unsigned char> hs(m);
-    GPIS_HIP(hipMemcpyAsync(ho.data(), p.d_off, sizeof(long long) * (m + 1), hipMemcpyDeviceToHost, p.own));
-    GPIS_HIP(hipMemcpyAsync(hs.data(), p.d_status, m, hipMemcpyDeviceToHost, p.own));
-    if (points && p.npoints > 0)
-        GPIS_HIP(hipMemcpyAsync(points, p.d_points, sizeof(float) * (size_t)p.npoints * 2, hipMemcpyDeviceToHost, p.own));
-    if (heading && p.npoints > 0)
-        GPIS_HIP(hipMemcpyAsync(heading, p.d_pheading, sizeof(int) * (size_t)p.npoints, hipMemcpyDeviceToHost, p.own));
-    if (start_cost) GPIS_HIP(hipMemcpyAsync(start_cost, p.d_scost, sizeof(float) * m, hipMemcpyDeviceToHost, p.own));
-    GPIS_HIP(hipStreamSynchronize(p.own));
-    for (size_t k = 0; k < m; ++k) {
-        if (off) off[k] = ho[k];
-        if (status) status[k] = hs[k];
-        if (arrive) arrive[k] = hs[k] == 0 ? (int)(ho[k + 1] - ho[k]) - 1 : -1;
-    }
-    if (off) off[m] = ho[m];
-    return GPIS_OK;
+    return tp_get_paths<TimePosePlanner>(tpp, off, points, heading, tpp ? ((TimePosePlanner*)tpp)->d_pheading : nullptr, arrive, start_cost, status);
 }
 int gpis_tpplan_check(void* tpp, void* obst, void* body, double clearance, double* min_sep, double* min_time, int* min_obstacle,
                       int* min_ball, int* first_hit, int* collides) {
@@ -2868,12 +2852,7 @@ int gpis_tpplan_check(void* tpp, void* obst, void* body, double clearance, doubl
     } catch (...) { return GPIS_ERR_STATE; }
 }
 int gpis_tpplan_controls(void* tpp, int T, int k0, double w_limit, double min_move, double* U, double* heading0, double* p0, int* clamped) {
-    if (!tpp || k0 < 0 || k0 > (1 << 20) || T < 1 || T > TimePosePlanner::kMaxT) return GPIS_ERR_ARG;
-    if (!std::isfinite(w_limit) || !std::isfinite(min_move) || w_limit < 0.0 || min_move < 0.0) return GPIS_ERR_ARG;
-    TimePosePlanner& p = *(TimePosePlanner*)tpp;
-    if (!p.valid || !p.paths_valid) return GPIS_ERR_STATE;
-    DeviceScope ds(p.device);
-    try { return p.controls(T, k0, w_limit, min_move, U, heading0, p0, clamped); } catch (...) { return GPIS_ERR_STATE; }
+    return tp_controls<TimePosePlanner>(tpp, T, k0, w_limit, min_move, U, heading0, p0, clamped);
 }
 
 }  // extern "C"

@@ -4,11 +4,11 @@
 // translations, the two turns and their weights.  The clock, the wait and the separation of a body ball from a moving ball over
 // one interval are the timed body check's (traj.h, §7x).  The graph is acyclic: layer s depends on layer s + 1 alone, so the bits
 // are unique by construction.  The handle copies the lattice geometry, the ball table, the footprint and both caller tables during
-// solve(): a result outlives its field, its set and its footprint.
+// solve(): a result outlives its field, its set and its footprint.  What the handle shares with the time planner's is TimePlanCore
+// (tplan_host.h), the kernels' shared rules are tplan_dev.h.
 #pragma once
-#include "dev_common.h"
 #include "body.h"
-#include "obst.h"
+#include "tplan_host.h"
 
 namespace gpis {
 
@@ -23,62 +23,28 @@ struct TimePosePlanOpts {
     int keep_cost = 0;
 };
 
-struct TimePosePlanner {
+struct TimePosePlanner : TimePlanCore {
     static constexpr int kMaxHorizon = 1024, kTile = 8, kMaxH = 64, kMaxT = 256;
     static constexpr int kTurnUp = 27, kTurnDown = 28, kWait = 29;
     static constexpr int kMaxStarts = 1 << 24;
     static constexpr long long kMaxStates = 1ll << 30, kMaxStatesKept = 1ll << 28;
     static constexpr float kMaxWait = 1e4f;
 
-    int device = -1;
-    hipStream_t own = nullptr;
-    int cull = 1;                            // the broad phase (test hook: the results do not depend on it)
-
-    // grow-only device buffers
-    unsigned char* d_policy = nullptr; size_t cap_policy = 0;     // [S + 1][ns]
-    float* d_c = nullptr;                                          // [ns] point cost; 0 = not free
-    float* d_cost0 = nullptr;                                      // [ns] the cost of slot 0
-    float* d_lay = nullptr;      size_t cap_n = 0;                 // [2][ns] two cost layers in turn
-    float* d_all = nullptr;      size_t cap_all = 0;               // [S + 1][ns] with keep_cost
-    double* d_tab = nullptr;                                       // [Obstacles::kMax][kRow]: the solve's copy of the set
+    // grow-only device buffers on top of the shared ones (bind() frees them)
     double* d_body = nullptr;                                      // [Footprint::kMax][kRow]: the solve's copy of the footprint
     double* d_head = nullptr;                                      // [kMaxH][2]
     double* d_rot = nullptr;                                       // [kMaxH][Footprint::kMax][2]: the rotated offsets
     unsigned short* d_moves = nullptr;                             // [kMaxH]
-    unsigned long long* d_stat = nullptr;
-    float* d_goals = nullptr;    size_t cap_goals = 0;
-    // paths
-    float* d_starts = nullptr;   size_t cap_starts = 0;            // [m][3]
-    long long* d_off = nullptr;                                    // [m + 1]
-    float* d_scost = nullptr;
-    unsigned char* d_status = nullptr;
-    float* d_points = nullptr;                                     // [total][2]
-    int* d_pheading = nullptr;                                     // [total]
-    size_t cap_points = 0;
-    // check and controls
-    double* d_cd = nullptr;      size_t cap_cd = 0;                // [m][2]
-    int* d_ci = nullptr;         size_t cap_ci = 0;                // [m][4]
-    double* d_u = nullptr;       size_t cap_u = 0;                 // [m][T][2]
-    double* d_hp = nullptr;      size_t cap_hp = 0;                // [m][4]: heading0, p0
-    int* d_cl = nullptr;         size_t cap_cl = 0;                // [m]
+    int* d_pheading = nullptr;                                     // [total], under cap_points with d_points
 
-    // the last result
-    bool valid = false, kept = false, paths_valid = false;
-    int nx = 0, ny = 0, H = 0, S = 0, n = 0, mb = 0;
-    float origin[2] = {0.f, 0.f};
-    float step = 0.f;
-    long long ns = 0;                        // nx ny H
+    // the last result: ns = nx ny H
+    int H = 0, mb = 0;
     TimePosePlanOpts opts;
-    double t_begin = 0.0;
-    long long goals_given = 0, goals_kept = 0, nfree = 0, nfinite = 0, launches = 0, skipped = 0;
-    double solve_ms = 0.0;
-    float max_cost0 = 0.f;
-    long long npaths = 0, npoints = 0;
 
-    TimePosePlanner();
-    ~TimePosePlanner();
-    void clear_result() { valid = kept = paths_valid = false; npaths = npoints = 0; }
-    int bind(int dev);
+    ~TimePosePlanner() { (void)bind(-1); }
+    int bind(int dev) {
+        return TimePlanCore::bind(dev, {(void**)&d_body, (void**)&d_head, (void**)&d_rot, (void**)&d_moves, (void**)&d_pheading});
+    }
     // Arguments are checked by the caller.  ob: nullptr or a set of this device (2-D where it holds balls); body: a 2-D
     // footprint of this device with m > 0; goals: host [ngoals][3]; synchronises `s`
     int solve(const DistanceField& df, const Obstacles* ob, const Footprint& body, const double* headings, const unsigned short* move_bits,

@@ -22,19 +22,17 @@
 #include "tpplan.h"
 #include "dfield.h"
 #include "plan_host.h"
-#include "block_ops.h"
+#include "tplan_dev.h"
 
 namespace gpis {
 
 namespace {
 
-using namespace plan_dev;
+using namespace tplan_dev;
 
-constexpr int kBlock = 256;
 constexpr int kT = TimePosePlanner::kTile, kW = kT + 2, kLayer = kW * kW;
 constexpr int kMB = Footprint::kMax;
 constexpr unsigned kBitWait = 1u << 4, kBitUp = 1u << 9, kBitDown = 1u << 10;
-enum { kPStatKept = 0, kPStatSkipped, kPStatFree, kPStatFinite, kPStatMax, kPStatWords };
 
 struct TPLat {
     int nx, ny, H;
@@ -65,9 +63,7 @@ constexpr unsigned b_need(int b) {
     return m;
 }
 
-__device__ __forceinline__ double world(float o, int i, float step) { return (double)(o + (float)i * step); }
-
-// The pose planner's set-up (pplan.hip), restated: one thread per state, one heading per blockIdx.y.  c = the point cost of
+// The pose planner's set-up (pplan.hip) for the top layer: one thread per state, one heading per blockIdx.y.  c = the point cost of
 // (float)D (0: not free; a NaN D is not free), the top layer's cost +inf and policy 255
 __global__ void __launch_bounds__(kBlock) tpplan_setup_kernel(const float* __restrict__ F, DfLattice L, BodyArgs bd, const double* __restrict__ head,
                                                               float clearance, float margin, float gain, float* __restrict__ c,
@@ -104,7 +100,7 @@ __global__ void __launch_bounds__(kBlock) tpplan_goal_kernel(TPLat L, const floa
             pol_top[s] = 13;
             ++kept;
         }
-        if (kept) atomicAdd(&stat[kPStatKept], (unsigned long long)kept);
+        if (kept) atomicAdd(&stat[TimePlanCore::kStatKept], (unsigned long long)kept);
     }
 }
 
@@ -133,30 +129,11 @@ __global__ void __launch_bounds__(kBlock) tpplan_layer_kernel(TPLat G, int tnx, 
         s_c[e] = in ? c[s] : 0.f;
         s_h[e] = in ? hin[s] : INFINITY;
     }
-    {   // the broad phase: thread i decides for ball i
-        bool keep = tid < B.n;
-        if (keep && B.cull) {
-            const double* row = B.tab + (size_t)tid * Obstacles::kRow;
-            const double ax = row[0] + row[3] * B.e0, bx = row[0] + row[3] * B.e1;
-            const double ay = row[1] + row[4] * B.e0, by = row[1] + row[4] * B.e1;
-            if (isfinite(ax) && isfinite(bx) && isfinite(ay) && isfinite(by)) {
-                const double rx0 = world(G.ox, ti * kT - 1, G.step), rx1 = world(G.ox, ti * kT + kT, G.step);
-                const double ry0 = world(G.oy, tj * kT - 1, G.step), ry1 = world(G.oy, tj * kT + kT, G.step);
-                const double gx = fmax(0.0, fmax(rx0 - fmax(ax, bx), fmin(ax, bx) - rx1));
-                const double gy = fmax(0.0, fmax(ry0 - fmax(ay, by), fmin(ay, by) - ry1));
-                // (the proof needs > beta + r + clr; two lattice steps more are the margin)
-                if (sqrt(gx * gx + gy * gy) > B.reach + row[6]) keep = false;
-            }
-        }
-        const unsigned long long b = __ballot(keep);
-        if ((tid & 63) == 0) { s_keep[tid >> 5] = (unsigned)b; s_keep[(tid >> 5) + 1] = (unsigned)(b >> 32); }
-    }
-    __syncthreads();
-    if (tid == 0 && B.cull && B.n > 0) {
-        int k = 0;
-        for (int w = 0; w < Obstacles::kMax / 32; ++w) k += __popc(s_keep[w]);
-        if (B.n - k > 0) atomicAdd(&stat[kPStatSkipped], (unsigned long long)(B.n - k));
-    }
+    // the broad phase over this layer and the tile with its halo (the proof needs > beta + r + clr; two lattice steps more are
+    // the margin); its barrier publishes s_mv, s_c and s_h
+    broad_phase(B.tab, B.n, B.cull, B.e0, B.e1, world(G.ox, ti * kT - 1, G.step), world(G.ox, ti * kT + kT, G.step),
+                world(G.oy, tj * kT - 1, G.step), world(G.oy, tj * kT + kT, G.step),
+                [reach = B.reach](const double* row) { return reach + row[6]; }, s_keep, stat);
 
     // thread tid: the point (li, lj) of the tile in the layers l0, l0 + 4, ...; l0 is the wavefront's index
     const int li = tid & (kT - 1), lj = (tid >> 3) & (kT - 1), l0 = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -221,16 +198,8 @@ __global__ void __launch_bounds__(kBlock) tpplan_layer_kernel(TPLat G, int tnx, 
                                         else if (m == 9) { W1x = Px[1] + ru[2 * j]; W1y = Py[1] + ru[2 * j + 1]; }
                                         else { W1x = Px[1] + rd[2 * j]; W1y = Py[1] + rd[2 * j + 1]; }
                                         const double Bx = (W1x - W0x) - dox, By = (W1y - W0y) - doy;
-                                        const double bb = Bx * Bx + By * By, ab = Ax * Bx + Ay * By;
-                                        double t = 0.0;
-                                        if (bb > 0.0) {
-                                            t = (-ab) / bb;
-                                            t = t > 0.0 ? t : 0.0;
-                                            t = t < 1.0 ? t : 1.0;
-                                        }
-                                        const double qx = Ax + t * Bx, qy = Ay + t * By;
-                                        const double s2 = qx * qx + qy * qy;
-                                        const double sep = (sqrt(s2) - rad) - rho;
+                                        double t;
+                                        const double sep = (closest_approach(Ax, Ay, Bx, By, t) - rad) - rho;
                                         if (sep < B.clr) blocked |= 1u << m;   // (a NaN separation is not below the clearance)
                                     }
                                 }
@@ -261,23 +230,6 @@ __global__ void __launch_bounds__(kBlock) tpplan_layer_kernel(TPLat G, int tnx, 
             hout[p] = hv;
         }
     }
-}
-
-// cost0 = the last layer; counts of free states and of states with a finite cost at slot 0, the largest such cost
-__global__ void __launch_bounds__(kBlock) tpplan_finish_kernel(const float* __restrict__ c, const float* __restrict__ lay, long long ns,
-                                                               float* __restrict__ cost0, unsigned long long* __restrict__ stat) {
-    __shared__ unsigned s_cnt[3];
-    counts_begin(s_cnt);
-    unsigned nf = 0, nr = 0, mx = 0;
-    for (long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x; p < ns; p += (long long)gridDim.x * blockDim.x) {
-        const float v = lay[p];
-        cost0[p] = v;
-        if (c[p] > 0.f) {
-            ++nf;
-            if (v < INFINITY) { ++nr; mx = max(mx, __float_as_uint(v)); }
-        }
-    }
-    commit_counts(s_cnt, nf, nr, mx, stat + kPStatFree);
 }
 
 // One thread per start follows the policy from slot 0.  WRITE = false: off[t] = entries of the path (arrive + 1; 0 without a
@@ -346,26 +298,17 @@ __global__ void __launch_bounds__(kBlock) tpplan_walk_kernel(TPLat L, int S, con
 // own poses, one per slot.  One workgroup per path; a thread per interval takes the moving balls i and inside them the body
 // balls j (both tables through scalar loads) and keeps its own least (sep, s, i, j) by a strict comparison in ascending order;
 // the block takes the least sep, then the least key (s << 12 | i << 4 | j) among the threads that hold it.
-// out_d[tr][2] = min_sep, min_time; out_i[tr][4] = min_obstacle, first_hit, collides, min_ball.
+// out_d[tr][2] = min_sep, min_time; out_i[tr][4] = min_obstacle, first_hit, collides, min_ball (check_begin() / check_finish()).
 __global__ void __launch_bounds__(kBlock) tpplan_check_kernel(const long long* __restrict__ off, const unsigned char* __restrict__ status,
                                                               const float* __restrict__ pts, const int* __restrict__ hd,
                                                               const double* __restrict__ head, double dt, double TB, double clearance,
                                                               const double* __restrict__ tab, int n, BodyArgs bd,
                                                               double* __restrict__ out_d, int* __restrict__ out_i) {
     typedef unsigned long long u64;
-    __shared__ double shd[kBlock / 64];
-    __shared__ u64 shk[kBlock / 64];
-    __shared__ int shi[kBlock / 64];
     const int tr = blockIdx.x, tid = threadIdx.x;
-    const long long o = off[tr];
-    const int A = (int)(off[tr + 1] - o) - 1;
-    if (status[tr] != 0 || n == 0 || A <= 0) {
-        if (tid == 0) {
-            out_d[(size_t)tr * 2] = status[tr] == 0 ? (double)INFINITY : (double)NAN; out_d[(size_t)tr * 2 + 1] = (double)NAN;
-            out_i[(size_t)tr * 4] = -1; out_i[(size_t)tr * 4 + 1] = -1; out_i[(size_t)tr * 4 + 2] = 0; out_i[(size_t)tr * 4 + 3] = -1;
-        }
-        return;
-    }
+    long long o;
+    int A;
+    if (!check_begin(off, status, n, o, A, out_d, out_i)) return;
     double best = INFINITY, best_s = 0.0;
     int best_k = -1, best_i = -1, best_j = -1, hit = 0x7fffffff;
     for (int k = tid; k < A; k += kBlock) {
@@ -386,113 +329,19 @@ __global__ void __launch_bounds__(kBlock) tpplan_check_kernel(const long long* _
                 const double W1x = p1x + (c1 * b0 - s1 * b1), W1y = p1y + (s1 * b0 + c1 * b1);
                 const double Ax = W0x - o0x, Ay = W0y - o0y;
                 const double Bx = (W1x - W0x) - dox, By = (W1y - W0y) - doy;
-                const double bb = Bx * Bx + By * By, ab = Ax * Bx + Ay * By;
-                double t = 0.0;
-                if (bb > 0.0) {
-                    t = (-ab) / bb;
-                    t = t > 0.0 ? t : 0.0;
-                    t = t < 1.0 ? t : 1.0;
-                }
-                const double qx = Ax + t * Bx, qy = Ay + t * By;
-                const double s2 = qx * qx + qy * qy;
-                const double sep = (sqrt(s2) - rad) - brow[3];
+                double t;
+                const double sep = (closest_approach(Ax, Ay, Bx, By, t) - rad) - brow[3];
                 if (sep < best) { best = sep; best_s = t; best_k = k; best_i = i; best_j = j; }
                 if (sep < clearance && k < hit) hit = k;
             }
         }
     }
-    const double bmin = block_reduce(best, OpMin(), shd, kBlock, (double)INFINITY);
-    if (tid == 0) shd[0] = bmin;
-    __syncthreads();
-    const double least = shd[0];
-    const u64 key = best_k >= 0 && best == least ? ((u64)best_k << 12) | ((u64)best_i << 4) | (u64)best_j : ~0ull;
-    const u64 kmin = block_reduce(key, OpMin(), shk, kBlock, ~0ull);
-    if (tid == 0) shk[0] = kmin;
-    __syncthreads();
-    const u64 win = shk[0];
-    const int fh = block_reduce(hit, OpMin(), shi, kBlock, 0x7fffffff);
-    if (tid == 0) {
-        out_i[(size_t)tr * 4 + 1] = fh == 0x7fffffff ? -1 : fh;
-        out_i[(size_t)tr * 4 + 2] = fh == 0x7fffffff ? 0 : 1;
-        if (win == ~0ull) {                              // no separation was a number
-            out_d[(size_t)tr * 2] = (double)INFINITY; out_d[(size_t)tr * 2 + 1] = (double)NAN;
-            out_i[(size_t)tr * 4] = -1; out_i[(size_t)tr * 4 + 3] = -1;
-        }
-    }
-    if (key == win && win != ~0ull) {
+    const u64 key = best_k >= 0 ? ((u64)best_k << 12) | ((u64)best_i << 4) | (u64)best_j : ~0ull;
+    if (check_finish(best, key, hit, out_d, out_i)) {
         out_d[(size_t)tr * 2] = best;
         out_d[(size_t)tr * 2 + 1] = (double)best_k * dt + best_s * dt;
         out_i[(size_t)tr * 4] = best_i; out_i[(size_t)tr * 4 + 3] = best_j;
     }
-}
-
-// Control sequences along the paths: the time planner's stage (tplan.hip, §7y) restated for starts of three floats.  The position
-// of step k is the point of slot min(k0 + k, arrive): a turn repeats its point, as a wait does.  One workgroup per path,
-// blockDim.x = 64 ceil(T / 64), thread k = step k.  U[tr][T][2], hp[tr][4] = heading0, p_0, clamped[tr].  Double, nothing
-// contracted.
-__global__ void __launch_bounds__(kBlock) tpplan_controls_kernel(const long long* __restrict__ off, const unsigned char* __restrict__ status,
-                                                                 const float* __restrict__ pts, const float* __restrict__ starts, int T,
-                                                                 int k0, double dt, double w_limit, double min_move,
-                                                                 double* __restrict__ U, double* __restrict__ hp, int* __restrict__ clamped) {
-    __shared__ double sh[2][kBlock];
-    __shared__ int swi[2 * (kBlock / 64)];
-    __shared__ int sidx[kBlock];
-    const int tr = blockIdx.x, k = threadIdx.x, nthr = blockDim.x;
-    double* Uo = U + (size_t)tr * T * 2;
-    double* hpo = hp + (size_t)tr * 4;
-    if (status[tr] != 0) {                               // no path: stand still at the start as given
-        if (k < T) { Uo[(size_t)k * 2] = 0.0; Uo[(size_t)k * 2 + 1] = 0.0; }
-        if (k == 0) {
-            hpo[0] = 1.0; hpo[1] = 0.0;
-            hpo[2] = (double)starts[(size_t)tr * 3]; hpo[3] = (double)starts[(size_t)tr * 3 + 1];
-            clamped[tr] = 0;
-        }
-        return;
-    }
-    const long long o = off[tr];
-    const int A = (int)(off[tr + 1] - o) - 1;
-    double p[2] = {0.0, 0.0}, D[2] = {0.0, 0.0};
-    double n = 0.0;
-    bool mov = false;
-    if (k < T) {
-        const int ia = min(k0 + k, A), ib = min(k0 + k + 1, A);
-#pragma unroll
-        for (int a = 0; a < 2; ++a) {
-            p[a] = (double)pts[(size_t)(o + ia) * 2 + a];
-            D[a] = (double)pts[(size_t)(o + ib) * 2 + a] - p[a];
-        }
-        n = sqrt(D[0] * D[0] + D[1] * D[1]);
-        mov = n > min_move;
-    }
-    if (mov) { sh[0][k] = D[0] / n; sh[1][k] = D[1] / n; }
-    int fst;
-    int last = block_latest_flag(mov, swi, nthr, &fst);  // (its barriers publish sh)
-    if (last < 0) last = fst;
-    sidx[k] = last;
-    __syncthreads();
-    int cl = 0;
-    if (k < T) {
-        const int nxt = k + 1 < T ? sidx[k + 1] : last;  // h_T = h_{T-1}
-        double c = 1.0, s = 0.0, c1 = 1.0, s1 = 0.0;
-        if (last >= 0) { c = sh[0][last]; s = sh[1][last]; }
-        if (nxt >= 0) { c1 = sh[0][nxt]; s1 = sh[1][nxt]; }
-        double* u = Uo + (size_t)k * 2;
-        u[0] = (c * D[0] + s * D[1]) / dt;
-        const double num = c * s1 - s * c1, den = 1.0 + (c * c1 + s * s1);
-        double w;
-        if (den <= 0.0) {
-            w = w_limit > 0.0 ? (num >= 0.0 ? w_limit : -w_limit) : 0.0;
-            cl = 1;
-        } else {
-            w = (num / den) / (0.5 * dt);
-            if (w_limit > 0.0 && w > w_limit) { w = w_limit; cl = 1; }
-            else if (w_limit > 0.0 && w < -w_limit) { w = -w_limit; cl = 1; }
-        }
-        u[1] = w;
-        if (k == 0) { hpo[0] = c; hpo[1] = s; hpo[2] = p[0]; hpo[3] = p[1]; }
-    }
-    const int total = block_reduce(cl, OpAdd(), swi, nthr, 0);
-    if (k == 0) clamped[tr] = total;
 }
 
 }  // namespace
@@ -509,36 +358,6 @@ int tpplan_check_opts(const TimePosePlanOpts& o, float step) {
     return GPIS_OK;
 }
 
-TimePosePlanner::TimePosePlanner() {
-    (void)hipGetDevice(&device);
-    if (hipStreamCreateWithFlags(&own, hipStreamNonBlocking) != hipSuccess) own = nullptr;
-}
-
-TimePosePlanner::~TimePosePlanner() { (void)bind(-1); }
-
-int TimePosePlanner::bind(int dev) {
-    if (dev == device && dev >= 0) return GPIS_OK;
-    {
-        DeviceScope ds(device);
-        if (own) (void)hipStreamSynchronize(own);
-        for (void* p : {(void*)d_policy, (void*)d_c, (void*)d_cost0, (void*)d_lay, (void*)d_all, (void*)d_tab, (void*)d_body, (void*)d_head,
-                        (void*)d_rot, (void*)d_moves, (void*)d_stat, (void*)d_goals, (void*)d_starts, (void*)d_off, (void*)d_scost,
-                        (void*)d_status, (void*)d_points, (void*)d_pheading, (void*)d_cd, (void*)d_ci, (void*)d_u, (void*)d_hp, (void*)d_cl})
-            (void)hipFree(p);
-        if (own) (void)hipStreamDestroy(own);
-    }
-    d_policy = nullptr; d_c = d_cost0 = d_lay = d_all = nullptr; d_tab = d_body = d_head = d_rot = nullptr; d_moves = nullptr;
-    d_stat = nullptr; d_goals = d_starts = nullptr; d_off = nullptr; d_scost = nullptr; d_status = nullptr; d_points = nullptr;
-    d_pheading = nullptr; d_cd = nullptr; d_ci = nullptr; d_u = d_hp = nullptr; d_cl = nullptr; own = nullptr;
-    cap_policy = cap_n = cap_all = cap_goals = cap_starts = cap_points = cap_cd = cap_ci = cap_u = cap_hp = cap_cl = 0;
-    clear_result();
-    device = dev;
-    if (dev < 0) return GPIS_OK;
-    DeviceScope ds(dev);
-    GPIS_HIP(hipStreamCreateWithFlags(&own, hipStreamNonBlocking));
-    return GPIS_OK;
-}
-
 int TimePosePlanner::solve(const DistanceField& df, const Obstacles* ob, const Footprint& body, const double* headings,
                            const unsigned short* move_bits, int nh, const float* goals, int ngoals, double tb, const TimePosePlanOpts& o,
                            hipStream_t s) {
@@ -547,25 +366,11 @@ int TimePosePlanner::solve(const DistanceField& df, const Obstacles* ob, const F
     const int Sn = o.horizon, nb = ob ? ob->n : 0, nbody = body.m;
     const int gx = df.n[0], gy = df.n[1], tnx = (gx + kTile - 1) / kTile, tny = (gy + kTile - 1) / kTile;
     const long long nxy = (long long)gx * gy, states = nxy * nh;
-    if (!d_stat) GPIS_HIP(hipMalloc((void**)&d_stat, sizeof(unsigned long long) * kPStatWords));
-    if (!d_tab) GPIS_HIP(hipMalloc((void**)&d_tab, sizeof(double) * Obstacles::kMax * Obstacles::kRow));
+    if (int rc = reserve(states, Sn, o.keep_cost, ngoals, 3)) return rc;
     if (!d_body) GPIS_HIP(hipMalloc((void**)&d_body, sizeof(double) * kMB * Footprint::kRow));
     if (!d_head) GPIS_HIP(hipMalloc((void**)&d_head, sizeof(double) * 2 * kMaxH));
     if (!d_rot) GPIS_HIP(hipMalloc((void**)&d_rot, sizeof(double) * 2 * kMaxH * kMB));
     if (!d_moves) GPIS_HIP(hipMalloc((void**)&d_moves, sizeof(unsigned short) * kMaxH));
-    if ((size_t)states > cap_n) {
-        for (void* p : {(void*)d_c, (void*)d_cost0, (void*)d_lay}) (void)hipFree(p);
-        d_c = d_cost0 = d_lay = nullptr; cap_n = 0;
-        GPIS_HIP(hipMalloc((void**)&d_c, sizeof(float) * states));
-        GPIS_HIP(hipMalloc((void**)&d_cost0, sizeof(float) * states));
-        GPIS_HIP(hipMalloc((void**)&d_lay, sizeof(float) * 2 * states));
-        cap_n = (size_t)states;
-    }
-    if (int rc = grow(d_policy, cap_policy, (size_t)states * (Sn + 1))) return rc;
-    if (o.keep_cost)
-        if (int rc = grow(d_all, cap_all, (size_t)states * (Sn + 1))) return rc;
-    if (int rc = grow(d_goals, cap_goals, (size_t)ngoals * 3)) return rc;
-
     // the footprint's rows and its rotated offsets per (heading, ball): the body rule's own operations, in double; beta = the
     // farthest any body ball reaches from the reference point: the largest |rot[h][j]| + rho_j
     std::vector<double> hbody((size_t)kMB * Footprint::kRow, 0.0), hrot((size_t)2 * kMaxH * kMB, 0.0);
@@ -594,7 +399,7 @@ int TimePosePlanner::solve(const DistanceField& df, const Obstacles* ob, const F
     GPIS_HIP(hipMemcpyAsync(d_body, hbody.data(), sizeof(double) * hbody.size(), hipMemcpyHostToDevice, s));
     GPIS_HIP(hipMemcpyAsync(d_rot, hrot.data(), sizeof(double) * hrot.size(), hipMemcpyHostToDevice, s));
     if (nb) GPIS_HIP(hipMemcpyAsync(d_tab, ob->d_tab, sizeof(double) * (size_t)nb * Obstacles::kRow, hipMemcpyDeviceToDevice, s));
-    GPIS_HIP(hipMemsetAsync(d_stat, 0, sizeof(unsigned long long) * kPStatWords, s));
+    GPIS_HIP(hipMemsetAsync(d_stat, 0, sizeof(unsigned long long) * kStatWords, s));
     float* top = d_lay;
     unsigned char* pol_top = d_policy + (size_t)Sn * states;
     hipLaunchKernelGGL(tpplan_setup_kernel, dim3((unsigned)((nxy + kBlock - 1) / kBlock), (unsigned)nh), dim3(kBlock), 0, s, (const float*)df.d_dist,
@@ -619,18 +424,13 @@ int TimePosePlanner::solve(const DistanceField& df, const Obstacles* ob, const F
         GPIS_HIP(hipGetLastError());
         cur ^= 1;
     }
-    hipLaunchKernelGGL(tpplan_finish_kernel, dim3(grid_for(states)), dim3(kBlock), 0, s, (const float*)d_c,
+    hipLaunchKernelGGL(tplan_finish_kernel, dim3(grid_for(states)), dim3(kBlock), 0, s, (const float*)d_c,
                        (const float*)(d_lay + (size_t)cur * states), states, d_cost0, d_stat);
     GPIS_HIP(hipGetLastError());
-    unsigned long long st[kPStatWords];
-    GPIS_HIP(hipMemcpyAsync(st, d_stat, sizeof(st), hipMemcpyDeviceToHost, s));
-    GPIS_HIP(hipStreamSynchronize(s));
+    if (int rc = read_stats(s)) return rc;
     nx = gx; ny = gy; H = nh; S = Sn; n = nb; mb = nbody; ns = states; step = df.step; origin[0] = df.origin[0]; origin[1] = df.origin[1];
     opts = o; t_begin = tb;
-    goals_given = ngoals; goals_kept = (long long)st[kPStatKept]; skipped = (long long)st[kPStatSkipped];
-    nfree = (long long)st[kPStatFree]; nfinite = (long long)st[kPStatFinite]; launches = Sn;
-    const unsigned mbits = (unsigned)st[kPStatMax];
-    std::memcpy(&max_cost0, &mbits, sizeof(float));
+    goals_given = ngoals; launches = Sn;
     solve_ms = plan_host::ms_since(t0);
     kept = o.keep_cost != 0;
     valid = true;
@@ -664,49 +464,18 @@ int TimePosePlanner::paths(const float* starts, int m, hipStream_t s) {
 
 int TimePosePlanner::check(const Obstacles& ob, const Footprint* body, double clearance, double* min_sep, double* min_time, int* min_obstacle,
                            int* min_ball, int* first_hit, int* collides) {
-    const size_t m = (size_t)npaths;
-    if (int rc = grow(d_cd, cap_cd, m * 2)) return rc;
-    if (int rc = grow(d_ci, cap_ci, m * 4)) return rc;
     const BodyArgs bd = body ? BodyArgs{body->d_tab, body->m} : BodyArgs{d_body, mb};
-    hipLaunchKernelGGL(tpplan_check_kernel, dim3((unsigned)m), dim3(kBlock), 0, own, (const long long*)d_off, (const unsigned char*)d_status,
-                       (const float*)d_points, (const int*)d_pheading, (const double*)d_head, opts.slot, t_begin - ob.epoch, clearance,
-                       (const double*)ob.d_tab, ob.n, bd, d_cd, d_ci);
-    GPIS_HIP(hipGetLastError());
-    std::vector<double> hd(m * 2);
-    std::vector<int> hi(m * 4);
-    GPIS_HIP(hipMemcpyAsync(hd.data(), d_cd, sizeof(double) * m * 2, hipMemcpyDeviceToHost, own));
-    GPIS_HIP(hipMemcpyAsync(hi.data(), d_ci, sizeof(int) * m * 4, hipMemcpyDeviceToHost, own));
-    GPIS_HIP(hipStreamSynchronize(own));
-    for (size_t k = 0; k < m; ++k) {
-        if (min_sep) min_sep[k] = hd[2 * k];
-        if (min_time) min_time[k] = hd[2 * k + 1];
-        if (min_obstacle) min_obstacle[k] = hi[4 * k];
-        if (first_hit) first_hit[k] = hi[4 * k + 1];
-        if (collides) collides[k] = hi[4 * k + 2];
-        if (min_ball) min_ball[k] = hi[4 * k + 3];
-    }
-    return GPIS_OK;
+    return run_check(
+        [&] {
+            hipLaunchKernelGGL(tpplan_check_kernel, dim3((unsigned)npaths), dim3(kBlock), 0, own, (const long long*)d_off,
+                               (const unsigned char*)d_status, (const float*)d_points, (const int*)d_pheading, (const double*)d_head,
+                               opts.slot, t_begin - ob.epoch, clearance, (const double*)ob.d_tab, ob.n, bd, d_cd, d_ci);
+        },
+        min_sep, min_time, min_obstacle, min_ball, first_hit, collides);
 }
 
 int TimePosePlanner::controls(int T, int k0, double w_limit, double min_move, double* U, double* heading0, double* p0, int* clamped) {
-    const size_t m = (size_t)npaths;
-    if (int rc = grow(d_u, cap_u, m * T * 2)) return rc;
-    if (int rc = grow(d_hp, cap_hp, m * 4)) return rc;
-    if (int rc = grow(d_cl, cap_cl, m)) return rc;
-    const int threads = 64 * ((T + 63) / 64);
-    hipLaunchKernelGGL(tpplan_controls_kernel, dim3((unsigned)m), dim3(threads), 0, own, (const long long*)d_off, (const unsigned char*)d_status,
-                       (const float*)d_points, (const float*)d_starts, T, k0, opts.slot, w_limit, min_move, d_u, d_hp, d_cl);
-    GPIS_HIP(hipGetLastError());
-    std::vector<double> hp(m * 4);
-    if (U) GPIS_HIP(hipMemcpyAsync(U, d_u, sizeof(double) * m * T * 2, hipMemcpyDeviceToHost, own));
-    if (clamped) GPIS_HIP(hipMemcpyAsync(clamped, d_cl, sizeof(int) * m, hipMemcpyDeviceToHost, own));
-    GPIS_HIP(hipMemcpyAsync(hp.data(), d_hp, sizeof(double) * m * 4, hipMemcpyDeviceToHost, own));
-    GPIS_HIP(hipStreamSynchronize(own));
-    for (size_t k = 0; k < m; ++k) {
-        if (heading0) { heading0[2 * k] = hp[4 * k]; heading0[2 * k + 1] = hp[4 * k + 1]; }
-        if (p0) { p0[2 * k] = hp[4 * k + 2]; p0[2 * k + 1] = hp[4 * k + 3]; }
-    }
-    return GPIS_OK;
+    return run_controls(tplan_controls_kernel, 3, opts.slot, T, k0, w_limit, min_move, U, heading0, p0, clamped);
 }
 
 }  // namespace gpis

@@ -5,7 +5,8 @@ field's box with speeds up to 0.25 m/s scaled by the step, radius two lattice st
 --horizons and n in --balls it prints one JSON line with
   - solve_ms: TimePlanner.solve through Python with the default schedule (median of --repeats), solve_L1_ms: one layer per
     launch, solve_nocull_ms: the broad phase off; the triples the broad phase skipped and the share of points served at slot 0,
-  - paths_ms (1000 starts, host copies included), check_ms, controls_ms (T = --steps),
+  - paths_ms (1000 starts, host copies included), check_ms, controls_ms (T = --steps); solve_ms_all .. controls_ms_all: every
+    repeat, the spread a comparison between two builds needs,
   - plan_ms: Planner.solve on the same field in the same process; retime_ms: Trajectories.retime of the static routes (N = 64,
     smoothed and timed with the defaults) against the same balls: what the new stage is set against, with the statuses of both,
   - host_solve_ms: tests/tplan_ref.py on --host-layers layers, scaled to S (the host route; skipped with --no-host), and whether
@@ -55,6 +56,7 @@ def main():
             t0 = time.perf_counter()
             fn()
             t.append((time.perf_counter() - t0) * 1e3)
+        med.all = t
         return float(np.median(t))
 
     df = gpismap_amd.DistanceField()
@@ -117,14 +119,18 @@ def main():
                 r["solve_nocull_ms"] = med(lambda: tp.solve(df, goal, ob, **kw))
                 tp.set_schedule(0, 1)
                 r["solve_ms"] = med(lambda: tp.solve(df, goal, ob, **kw))
+                r["solve_ms_all"] = med.all
                 i = tp.info()
                 r.update(solve_inner_ms=i["solve_ms"], layer_launches=i["layer_launches"], skipped=i["skipped"],
                          served=i["finite0"] / max(i["free"], 1), solve_over_plan=r["solve_ms"] / plan_ms,
                          solve_over_retime=r["solve_ms"] / retime_ms)
                 r["paths_ms"] = med(lambda: tp.paths(starts))
+                r["paths_ms_all"] = med.all
                 pa = tp.paths(starts)
                 r["check_ms"] = med(lambda: tp.check(ob))
+                r["check_ms_all"] = med.all
                 r["controls_ms"] = med(lambda: tp.controls(T))
+                r["controls_ms_all"] = med.all
                 ck = tp.check(ob)
                 r.update(status=np.bincount(pa["status"], minlength=5).tolist(), arrive_max=int(pa["arrive"].max()),
                          collides=int(ck["collides"].sum()))

@@ -6,7 +6,8 @@ field and the same box in lattice units (10 x 4 steps) on the slice, whose step 
 in --balls it prints one JSON line with
   - solve_ms: TimePosePlanner.solve through Python with the broad phase on (median of --repeats), solve_nocull_ms: one call with
     it off; the triples the broad phase skipped and the share of free states served at slot 0,
-  - paths_ms (1000 starts, host copies included), check_ms, controls_ms (T = --steps), statuses and the longest arrival,
+  - paths_ms (1000 starts, host copies included), check_ms, controls_ms (T = --steps), statuses and the longest arrival;
+    solve_ms_all .. controls_ms_all: every repeat, the spread a comparison between two builds needs,
   - tplan_ms: TimePlanner.solve and pplan_ms: PosePlanner.solve on the same field, set and footprint in the same process: the
     yardsticks (tplan_ms x H x body balls is the naive product),
   - host_solve_ms: tests/tpplan_ref.py on --host-layers layers, scaled to S, with goals on a grid of three lattice steps so that
@@ -61,6 +62,7 @@ def main():
             t0 = time.perf_counter()
             fn()
             t.append((time.perf_counter() - t0) * 1e3)
+        med.all = t
         return float(np.median(t))
 
     def once(fn):
@@ -123,14 +125,18 @@ def main():
                 r["tplan_ms"] = med(lambda: tpl.solve(df, goal, ob, slot=SLOT, horizon=S))
                 tp.set_schedule(1)
                 r["solve_ms"] = med(lambda: tp.solve(df, goal, fp, ob, H=H, **kw))
+                r["solve_ms_all"] = med.all
                 i = tp.info()
                 r.update(solve_inner_ms=i["solve_ms"], launches=i["launches"], skipped=i["skipped"], free=i["free"],
                          served=i["finite0"] / max(i["free"], 1), naive_ms=r["tplan_ms"] * H * BOX[2],
                          solve_over_naive=r["solve_ms"] / (r["tplan_ms"] * H * BOX[2]), solve_over_pplan=r["solve_ms"] / pplan_ms)
                 r["paths_ms"] = med(lambda: tp.paths(starts))
+                r["paths_ms_all"] = med.all
                 pa = tp.paths(starts)
                 r["check_ms"] = med(lambda: tp.check(ob))
+                r["check_ms_all"] = med.all
                 r["controls_ms"] = med(lambda: tp.controls(T))
+                r["controls_ms_all"] = med.all
                 ck = tp.check(ob)
                 r.update(status=np.bincount(pa["status"], minlength=5).tolist(), arrive_max=int(pa["arrive"].max()),
                          collides=int(ck["collides"].sum()))
