@@ -184,6 +184,10 @@ def lib():
         for name in ("gpis3", "gpis2", "gpis_mapquery"):
             getattr(L, name + "_set_pass2_mode").argtypes = [vp, C.c_int]
             getattr(L, name + "_pass_detail").argtypes = [vp, dp]
+    if hasattr(L, "gpis3_set_k4_schedule"):
+        L.gpis3_set_k4_schedule.argtypes = [vp, C.c_int]
+        L.gpis_mapquery_set_k4_schedule.argtypes = [vp, C.c_int]
+        L.gpis_mapquery_last_counts.argtypes = [vp, C.POINTER(C.c_longlong)]
     if hasattr(L, "gpis2_sync"):
         L.gpis2_sync.argtypes = [vp]
         L.gpis2_set_pipeline.argtypes = [vp, C.c_int]
@@ -732,6 +736,11 @@ class GPisMap3:
         """How test() evaluates candidates 2 and 3 of a three-candidate fallback: 0 value columns first, 1 the predicted candidate
         in full (default), 2 / 3 always candidate 2 / 3, 4 the predictor inverted.  Same results in every mode (gpis3_set_pass2_mode)."""
         _check(self.L.gpis3_set_pass2_mode(self.h, int(mode)), "gpis3_set_pass2_mode")
+
+    def set_k4_schedule(self, mode):
+        """How test() cuts a call into chunks: 0 chunks of 2^22 queries, 1 (default) the whole call in one chunk where the device
+        has the memory.  Same results (gpis3_set_k4_schedule)."""
+        _check(self.L.gpis3_set_k4_schedule(self.h, int(mode)), "gpis3_set_k4_schedule")
 
     def pass_detail(self):
         """How the prediction of the last test() went (gpis3_pass_detail)."""
@@ -3848,6 +3857,15 @@ class MapQueryProbe:
 
     def set_pass2_mode(self, mode):
         _check(self.L.gpis_mapquery_set_pass2_mode(self.h, int(mode)), "gpis_mapquery_set_pass2_mode")
+
+    def set_k4_schedule(self, mode):
+        _check(self.L.gpis_mapquery_set_k4_schedule(self.h, int(mode)), "gpis_mapquery_set_k4_schedule")
+
+    def last_counts(self):
+        """Of the last run: last_test_evals, last_test_k4_launches, the queries per chunk, the K4 schedule in force."""
+        a = (C.c_longlong * 4)()
+        _check(self.L.gpis_mapquery_last_counts(self.h, a), "gpis_mapquery_last_counts")
+        return dict(zip(("last_test_evals", "last_test_k4_launches", "chunk", "k4_schedule"), (int(v) for v in a)))
 
     def pass_detail(self):
         a = (C.c_double * 8)()

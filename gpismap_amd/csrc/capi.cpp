@@ -39,6 +39,7 @@ void gpis2_impl_pass_jobs(GPisMap* m, long long* out);
 void gpis3_impl_pass_detail(GPisMap3* m, double* out);
 void gpis2_impl_pass_detail(GPisMap* m, double* out);
 int gpis3_impl_set_pass2_mode(GPisMap3* m, int mode);
+int gpis3_impl_set_k4_schedule(GPisMap3* m, int mode);
 int gpis2_impl_set_pass2_mode(GPisMap* m, int mode);
 int gpis3_impl_fail(GPisMap3* m);
 int gpis2_impl_fail(GPisMap* m);
@@ -216,6 +217,7 @@ int gpis3_load(void* m, const char* path) {
 int gpis3_stats(void* m, double* out, int n) { if (!m || !out) return GPIS_ERR_ARG; gpis3_impl_stats((GPisMap3*)m, out, n); return GPIS_OK; }
 int gpis3_pass_jobs(void* m, long long* out4) { if (!m || !out4) return GPIS_ERR_ARG; gpis3_impl_pass_jobs((GPisMap3*)m, out4); return GPIS_OK; }
 int gpis3_pass_detail(void* m, double* out8) { if (!m || !out8) return GPIS_ERR_ARG; gpis3_impl_pass_detail((GPisMap3*)m, out8); return GPIS_OK; }
+int gpis3_set_k4_schedule(void* m, int mode) { if (!m || mode < 0 || mode > 1) return GPIS_ERR_ARG; return gpis3_impl_set_k4_schedule((GPisMap3*)m, mode); }
 int gpis3_set_pass2_mode(void* m, int mode) { if (!m || mode < 0 || mode > 4) return GPIS_ERR_ARG; return gpis3_impl_set_pass2_mode((GPisMap3*)m, mode); }
 int gpis3_sync(void* m) { if (!m) return GPIS_ERR_ARG; try { return gpis3_impl_sync((GPisMap3*)m); } catch (...) { return GPIS_ERR_STATE; } }
 int gpis3_set_pipeline(void* m, int on) { if (!m) return GPIS_ERR_ARG; try { gpis3_impl_set_pipeline((GPisMap3*)m, on); return GPIS_OK; } catch (...) { return GPIS_ERR_STATE; } }
@@ -557,7 +559,7 @@ int gpis_mapquery_set_table(void* h, int ncl, const float* c, const float* lo, c
 }
 int gpis_mapquery_set_chunk(void* h, int n) {
     if (!h || n < 0) return GPIS_ERR_ARG;
-    ((MqHandle*)h)->mq.chunk = n ? n : (1 << 22);
+    ((MqHandle*)h)->mq.chunk = n;   // (0: automatic)
     return GPIS_OK;
 }
 int gpis_mapquery_run(void* h, const float* x, int n, float* res_inout) {
@@ -581,7 +583,7 @@ int gpis_mapquery_run(void* h, const float* x, int n, float* res_inout) {
     if (rc && rc != GPIS_ERR_STATE) return rc;
     if (n > 0) GPIS_HIP(hipMemcpyAsync(res_inout, q->d_res, sizeof(float) * nr, hipMemcpyDeviceToHost, s));
     GPIS_HIP(hipStreamSynchronize(s));
-    if (rc == GPIS_OK && n > 0 && n <= q->mq.chunk && q->mq.num_clusters() > 0) q->last_n = n;
+    if (rc == GPIS_OK && n > 0 && n <= q->mq.last_chunk_len && q->mq.num_clusters() > 0) q->last_n = n;
     return rc;
 }
 int gpis_mapquery_candidates(void* h, int* ncand, int* cand3) {
@@ -608,6 +610,17 @@ int gpis_mapquery_pass_jobs(void* h, long long* out4) {
 int gpis_mapquery_pass_detail(void* h, double* out8) {
     if (!h || !out8) return GPIS_ERR_ARG;
     ((MqHandle*)h)->mq.pass_detail(out8);
+    return GPIS_OK;
+}
+int gpis_mapquery_set_k4_schedule(void* h, int mode) {
+    if (!h || mode < 0 || mode > 1) return GPIS_ERR_ARG;
+    ((MqHandle*)h)->mq.k4_schedule = mode;
+    return GPIS_OK;
+}
+int gpis_mapquery_last_counts(void* h, long long* out4) {
+    if (!h || !out4) return GPIS_ERR_ARG;
+    const MapQuery& mq = ((MqHandle*)h)->mq;
+    out4[0] = mq.last_evals; out4[1] = mq.last_launches; out4[2] = mq.last_chunk_len; out4[3] = mq.k4_schedule;
     return GPIS_OK;
 }
 int gpis_mapquery_set_pass2_mode(void* h, int mode) {

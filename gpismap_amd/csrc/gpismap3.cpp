@@ -2135,6 +2135,12 @@ int gpis3_impl_set_pass2_mode(GPisMap3* g, int mode) {
     m.mq.pass2_mode = mode;
     return GPIS_OK;
 }
+int gpis3_impl_set_k4_schedule(GPisMap3* g, int mode) {
+    GPisMap3::Impl& m = *g->impl();
+    for (GPisMap3* q : m.peers) gpis3_impl_set_k4_schedule(q, mode);
+    m.mq.k4_schedule = mode;
+    return GPIS_OK;
+}
 // join the training the last update() left in flight; returns the update status (0: fine)
 int gpis3_impl_sync(GPisMap3* g) {
     GPisMap3::Impl& m = *g->impl();

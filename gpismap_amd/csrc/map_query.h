@@ -83,10 +83,20 @@ public:
     int pass2_mode = 1;
     int last_launches = 0;      // K4 launches of the last run
     float last_eval_ms = 0.f;   // time inside the K4 launches (hipEvents on the stream)
-    int chunk = 1 << 22;
+    // queries per pass of the chunk loop; 0 = automatic (chunk_for: the whole call where the device has the memory, 2^22 under
+    // k4_schedule 0).  The results do not depend on it.
+    int chunk = 0;
+    int last_chunk_len = 0;     // the chunk length of the last run
+    // How an automatic chunk is chosen: 0 = 2^22 queries whatever the call; 1 (default) = the chunk follows the call and the
+    // device's free memory, so that a pass is one K4 launch per size class over the whole call where that fits.  Same results in
+    // both.  GPIS_K4_SCHEDULE in the environment sets the initial value.  May change between runs.
+    int k4_schedule = 1;
     bool profile = false;
+    static constexpr int kMinChunk = 1 << 22, kMaxChunk = 1 << 28;
+    static size_t scratch_bytes(int n);
 
 private:
+    int chunk_for(int n);
     int ensure_scratch(int n, int nmodels);
     int run_chunk(OnGPISStore& store, const float* d_x, int n, float* d_res, hipStream_t s);
     int eval_pass(OnGPISStore& store, int njobs, int shift, int rec_base, int nmodels, hipStream_t s, int layout, int pass);

@@ -557,6 +557,7 @@ MapQuery::MapQuery(int dim, float search_half, float var_thre, float prior_var)
     : dim_(dim), search_half_(search_half), var_thre_(var_thre), prior_var_(prior_var), h_maxN_(ONGPIS_NCLASS, 0), h_maxLd_(ONGPIS_NCLASS, 0) {
     std::memset(&tv_, 0, sizeof(tv_));
     if (const char* e = getenv("GPIS_PASS2")) { const int m = atoi(e); if (m >= 0 && m <= 4) pass2_mode = m; }
+    if (const char* e = getenv("GPIS_K4_SCHEDULE")) { const int m = atoi(e); if (m == 0 || m == 1) k4_schedule = m; }
 }
 
 MapQuery::~MapQuery() {
@@ -637,6 +638,32 @@ int MapQuery::set_clusters(const std::vector<ClusterEntry>& cl, const std::vecto
     tv_.gx = g[0]; tv_.gy = g[1]; tv_.gz = g[2];
     tv_.ox = org[0]; tv_.oy = org[1]; tv_.oz = org[2]; tv_.pitch = pitch;
     return GPIS_OK;
+}
+
+// bytes of the per-query scratch ensure_scratch allocates for a chunk of n queries (the per-model arrays are small beside it)
+size_t MapQuery::scratch_bytes(int n) {
+    const size_t c = (size_t)std::max(n, 0);
+    const size_t per_query = sizeof(float4) + sizeof(int) * (3 + 1 + 1 + 3 * 2) + sizeof(float) * 8 * 3;   // xq, cand, ncand, pick, jm / jq / jo, out
+    return c * per_query + sizeof(int) * 3 * (2 * (c / ONGPIS_TILE_Q + 1));
+}
+
+// Queries per chunk of a call of n.  A set chunk holds.  Otherwise (chunk 0): 2^22 under k4_schedule 0; under schedule 1 the whole
+// call, halved until the scratch of a chunk fits in one eighth of the device memory that is free (counting the scratch this object
+// holds already, which a larger chunk replaces), and never less than 2^22.  Every chunk pays the lookup, four job kernels, four
+// binning rounds and four count read-backs with the device idle during each, and ends every K4 launch of its passes on a
+// draining device: fewer chunks, less of both.
+// Every index that grows with the chunk -- records cap + 2q + s up to 3 chunk, jobs up to 2 chunk, tiles up to chunk / 4 + models,
+// binning blocks of BIN_CHUNK jobs -- stays below 2^31 up to kMaxChunk = 2^28; the byte and float offsets made from them (records x
+// 8 floats) are size_t throughout.
+int MapQuery::chunk_for(int n) {
+    if (chunk > 0) return std::min(chunk, kMaxChunk);
+    if (k4_schedule == 0 || n <= kMinChunk) return kMinChunk;
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); return kMinChunk; }
+    const size_t room = (free_b + scratch_bytes(cap_n_)) / 8;
+    long long c = std::min<long long>(n, kMaxChunk);
+    while (c > kMinChunk && c > cap_n_ && scratch_bytes((int)c) > room) c = (c + 1) / 2;
+    return (int)std::max<long long>(c, kMinChunk);
 }
 
 int MapQuery::ensure_scratch(int n, int nmodels) {
@@ -897,8 +924,10 @@ int MapQuery::run_prepared(OnGPISStore& store, const float* d_x, int n, float* d
         GPIS_HIP(hipStreamSynchronize(s));
         return GPIS_OK;
     }
-    for (int off = 0; off < n; off += chunk) {
-        int len = std::min(chunk, n - off);
+    const int len_max = chunk_for(n);
+    last_chunk_len = len_max;
+    for (long long off = 0; off < n; off += len_max) {
+        int len = (int)std::min<long long>(len_max, n - off);
         rc = run_chunk(store, d_x + (size_t)dim_ * off, len, d_res + (size_t)nc * off, s);
         if (rc) return rc;
     }

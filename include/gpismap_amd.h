@@ -137,6 +137,12 @@ int   gpis3_pass_jobs(void* map, long long* out4);
  * tests of the repair path).  The results are the same bits in every mode; only the time differs.  The environment variable
  * GPIS_PASS2 sets the initial mode of a new map.  Takes effect at the next test().  GPIS_ERR_ARG outside 0..4. */
 int   gpis3_set_pass2_mode(void* map, int mode);
+/* How test() cuts a call into chunks, each of which runs every pass (one prediction launch per cluster size class and pass).
+ * 0: chunks of 2^22 queries.  1 (default): the whole call in one chunk where the device has the memory, as
+ * gpis_mapquery_set_chunk(mq, 0) describes: the per-chunk work and the drained device at the end of every launch are paid once.
+ * The results are the same bits in both; only the time differs.  The environment variable GPIS_K4_SCHEDULE sets the initial mode
+ * of a new map.  Takes effect at the next test().  GPIS_ERR_ARG outside 0..1. */
+int   gpis3_set_k4_schedule(void* map, int mode);
 /* out[0..7] of the last test(): evaluations in full of a predicted candidate, value-column-only evaluations, gradient-column
  * evaluations afterwards, predicted candidates evaluated in full that the blend did not read, predictions made (both candidates
  * have a model), predictions the blend read, ms in the predictor kernel (profiling on), the mode.  out[0] + out[1] = [2] and
@@ -300,7 +306,9 @@ void  gpis_mapquery_destroy(void* mq);
 int   gpis_mapquery_set_table(void* mq, int ncl, const float* c, const float* lo, const float* hi, const int* model,
                               const int* parent, int nanc, const float* anc_lo, const float* anc_hi, const int* anc_parent,
                               double pitch);
-/* queries per pass of the chunk loop (the results do not depend on it); 0 = 2^22, negative -> GPIS_ERR_ARG */
+/* queries per pass of the chunk loop (the results do not depend on it); negative -> GPIS_ERR_ARG.  0 (the default) = automatic:
+ * the whole call in one chunk when its scratch (about 156 bytes per query) fits in one eighth of the free device memory, halved
+ * until it does, never below 2^22 and never above 2^28; 2^22 under K4 schedule 0. */
 int   gpis_mapquery_set_chunk(void* mq, int n);
 /* x [n][dim], res [n][2(1+dim)] host arrays; res is uploaded first (as gpis3_test does): only the entries the reference
  * writes change.  n = 0 is a no-op. */
@@ -310,7 +318,10 @@ int   gpis_mapquery_run(void* mq, const float* x, int n, float* res_inout);
 int   gpis_mapquery_candidates(void* mq, int* ncand, int* cand3);
 /* K4 jobs of the last run per pass: 1, 2 (two-candidate queries, all columns), 2a (value column), 2b (gradient columns) */
 int   gpis_mapquery_pass_jobs(void* mq, long long* out4);
-/* as gpis3_set_pass2_mode / gpis3_pass_detail */
+/* as gpis3_set_pass2_mode / gpis3_pass_detail / gpis3_set_k4_schedule */
+int   gpis_mapquery_set_k4_schedule(void* mq, int mode);
+/* of the last run: evaluations, K4 launches, queries per chunk, the K4 schedule in force */
+int   gpis_mapquery_last_counts(void* mq, long long* out4);
 int   gpis_mapquery_set_pass2_mode(void* mq, int mode);
 int   gpis_mapquery_pass_detail(void* mq, double* out8);
 
