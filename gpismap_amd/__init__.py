@@ -232,6 +232,8 @@ def lib():
         L.gpis_mapquery_set_table.argtypes = [vp, C.c_int, fp, fp, fp, ip, ip, C.c_int, fp, fp, ip, C.c_double]
         L.gpis_mapquery_set_chunk.argtypes = [vp, C.c_int]
         L.gpis_mapquery_run.argtypes = [vp, fp, C.c_int, fp]
+        if hasattr(L, "gpis_mapquery_run_device"):
+            L.gpis_mapquery_run_device.argtypes = [vp, vp, C.c_int, vp, vp]
         L.gpis_mapquery_candidates.argtypes = [vp, ip, ip]
         L.gpis_mapquery_pass_jobs.argtypes = [vp, C.POINTER(C.c_longlong)]
     if hasattr(L, "gpis_mesh_create"):
@@ -3841,6 +3843,13 @@ class MapQueryProbe:
         _check(self.L.gpis_mapquery_run(self.h, _p(x), x.shape[0], _p(res)), "gpis_mapquery_run")
         self._n = x.shape[0]
         return res
+
+    def run_device(self, d_x_ptr, n, d_res_ptr, stream=0):
+        """run() on the caller's device buffers (raw pointers: x [n, dim], res [n, 2(1+dim)] float32, res input and output), on
+        `stream` (0: the store's).  Whatever wrote the buffers must have finished; synchronous on return."""
+        _check(self.L.gpis_mapquery_run_device(self.h, C.c_void_p(d_x_ptr), int(n), C.c_void_p(d_res_ptr), C.c_void_p(stream)),
+               "gpis_mapquery_run_device")
+        self._n = int(n)
 
     def candidates(self):
         """(ncand [n], cand [3, n]) of the last run (one chunk, non-empty table)."""

@@ -586,6 +586,19 @@ int gpis_mapquery_run(void* h, const float* x, int n, float* res_inout) {
     if (rc == GPIS_OK && n > 0 && n <= q->mq.last_chunk_len && q->mq.num_clusters() > 0) q->last_n = n;
     return rc;
 }
+int gpis_mapquery_run_device(void* h, const float* d_x, int n, float* d_res_inout, void* hip_stream) {
+    if (!h || n < 0 || (n > 0 && (!d_x || !d_res_inout))) return GPIS_ERR_ARG;
+    MqHandle* q = (MqHandle*)h;
+    DeviceScope dev_scope_(q->on->device);
+    q->last_n = -1;
+    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : q->on->s;
+    int rc;
+    try { rc = q->mq.run(q->on->st, d_x, n, d_res_inout, s); } catch (...) { return GPIS_ERR_STATE; }
+    if (rc && rc != GPIS_ERR_STATE) return rc;
+    GPIS_HIP(hipStreamSynchronize(s));
+    if (rc == GPIS_OK && n > 0 && n <= q->mq.last_chunk_len && q->mq.num_clusters() > 0) q->last_n = n;
+    return rc;
+}
 int gpis_mapquery_candidates(void* h, int* ncand, int* cand3) {
     if (!h || !ncand || !cand3) return GPIS_ERR_ARG;
     MqHandle* q = (MqHandle*)h;

@@ -313,6 +313,10 @@ int   gpis_mapquery_set_chunk(void* mq, int n);
 /* x [n][dim], res [n][2(1+dim)] host arrays; res is uploaded first (as gpis3_test does): only the entries the reference
  * writes change.  n = 0 is a no-op. */
 int   gpis_mapquery_run(void* mq, const float* x, int n, float* res_inout);
+/* The same run on the caller's device buffers (on the probe's device), as gpis3_test_device: d_x [n][dim], d_res_inout
+ * [n][2(1+dim)], on hip_stream (NULL: the store's stream).  Work queued on another stream that writes the buffers must have
+ * finished.  Synchronous on return; the same refusals as gpis_mapquery_run. */
+int   gpis_mapquery_run_device(void* mq, const float* d_x, int n, float* d_res_inout, void* hip_stream);
 /* the lookup's result of the last run: ncand [n], cand [3][n] (model slot or -1).  Only after a run of one chunk over a
  * non-empty table, GPIS_ERR_STATE otherwise. */
 int   gpis_mapquery_candidates(void* mq, int* ncand, int* cand3);

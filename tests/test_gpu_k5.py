@@ -478,6 +478,7 @@ def test_error_paths():
     assert L.gpis_mapquery_set_table(None, 0, None, None, None, None, None, 0, None, None, None, 0.05) == ARG
     assert L.gpis_mapquery_run(None, None, 0, None) == ARG and L.gpis_mapquery_set_chunk(None, 0) == ARG
     assert L.gpis_mapquery_candidates(None, None, None) == ARG and L.gpis_mapquery_pass_jobs(None, None) == ARG
+    assert L.gpis_mapquery_run_device(None, None, 0, None, None) == ARG
     st = new_store(3)
     tab = Cs.box_table(3, (2, 2, 2))
     give_models(st, tab, np.random.default_rng(1), big=False)
@@ -493,6 +494,9 @@ def test_error_paths():
     assert L.gpis_mapquery_set_table(*args(tab["model"], tab["parent"], np.arange(nanc))) == ARG             # an ancestor its own parent
     assert L.gpis_mapquery_set_table(*args(np.full(8, 99), tab["parent"], tab["anc_parent"])) == ARG          # not a slot of the store
     assert L.gpis_mapquery_set_chunk(probe.h, -1) == ARG
+    for entry, tail in ((L.gpis_mapquery_run, ()), (L.gpis_mapquery_run_device, (None,))):     # the same refusals in both forms
+        assert entry(probe.h, None, -1, None, *tail) == ARG and entry(probe.h, None, 4, None, *tail) == ARG
+        assert entry(probe.h, None, 0, None, *tail) == 0                                     # n = 0: nothing to do
     assert L.gpis_mapquery_candidates(probe.h, i32(np.zeros(8)), i32(np.zeros(24))) == STATE                  # nothing run yet
     assert L.gpis_mapquery_set_table(*args(tab["model"], tab["parent"], tab["anc_parent"])) == 0
     x = tab["c"][:, :3].copy()
