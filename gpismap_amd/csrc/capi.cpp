@@ -1572,7 +1572,7 @@ int gpis_cover_get_frontiers(void* cover, int* label, int* count, long long* sum
     if ((points || point_label) && c.npoints > 0) {
         DeviceScope ds(c.device);
         const size_t m = (size_t)c.npoints;
-        if (points) GPIS_HIP(hipMemcpyAsync(points, c.d_list, sizeof(int) * m, hipMemcpyDeviceToHost, c.own));
+        if (points) GPIS_HIP(hipMemcpyAsync(points, c.comp.d_list, sizeof(int) * m, hipMemcpyDeviceToHost, c.own));
         if (point_label) GPIS_HIP(hipMemcpyAsync(point_label, c.d_plabel, sizeof(int) * m, hipMemcpyDeviceToHost, c.own));
         GPIS_HIP(hipStreamSynchronize(c.own));
     }
@@ -1626,7 +1626,7 @@ void gpis_detect_destroy(void* det) { delete (Detector*)det; }
 int gpis_detect_set_schedule(void* det, int check_every, int profile) {
     if (!det || check_every < 0) return GPIS_ERR_ARG;
     Detector& d = *(Detector*)det;
-    if (check_every > 0) d.check_every = std::min(check_every, (int)Detector::kMaxBatch);
+    if (check_every > 0) d.comp.check_every = std::min(check_every, kCompMaxBatch);
     d.profile = profile != 0;
     return GPIS_OK;
 }

@@ -7,7 +7,9 @@
 #include <cstdint>
 #include <vector>
 #include "dev_common.h"
+#include "components.h"
 #include "cover_host.h"
+#include "dfield_sample.h"
 #include "frame.h"
 
 namespace gpis {
@@ -15,33 +17,20 @@ namespace gpis {
 struct DistanceField;
 
 struct Coverage {
-    static constexpr int kBlock = 256;           // threads of every kernel, and the width of both scans
-    static constexpr int kItems = 8;             // compaction: points per thread, kChunk = kBlock * kItems per workgroup
-    static constexpr int kChunk = kBlock * kItems;
-    static constexpr int kMaxBatch = 64;         // labelling rounds per read-back (check_every)
-    static constexpr int kTabWords = 8;          // 64-bit words per component: count, sums (3), d2 bits, rep, label, unused
+    static constexpr int kBlock = 256;           // threads of every kernel
 
     int device = -1;
     hipStream_t own = nullptr;
-    int check_every = 4;                         // schedule (the results do not depend on it)
 
     // grow-only device buffers
     unsigned char* d_seen = nullptr;  size_t cap_n = 0;         // 1 B per lattice point
     int* d_rank = nullptr;            size_t cap_rank = 0;      // frontiers: the rank grid, 4 B per lattice point
-    int* d_bcount = nullptr;          size_t cap_blocks = 0;    // per-chunk counts, then their exclusive scan and the total
-    int* d_list = nullptr;                                      // per frontier point: lattice index, ...
-    int* d_label = nullptr;                                     // ... label as a rank, ...
-    int* d_plabel = nullptr;                                    // ... label as a lattice index, ...
-    int* d_cidx = nullptr;                                      // ... component index of a root (-1 elsewhere), ...
-    int* d_roots = nullptr;           size_t cap_m = 0;         // ... and the roots' ranks, ascending
-    unsigned long long* d_tab = nullptr;
-    int* d_box = nullptr;             size_t cap_c = 0;
+    // the frontier points (comp.d_list: lattice indices), their components, and the table (components.h), per component the words
+    // count, sums (3), d2 bits, rep, label, unused and the integer box
+    Components<int> comp;
+    int* d_plabel = nullptr;          size_t cap_plabel = 0;    // per frontier point: its label as a lattice index
     double* d_sector = nullptr;       size_t cap_beams = 0;     // q [m], then lim_eff [m]
     float* d_depth = nullptr;         size_t cap_pix = 0;
-    int* d_word = nullptr;                                      // [0]: a labelling round changed something
-    // page-locked staging of what comes back
-    int* h_word = nullptr;
-    unsigned long long* h_tab = nullptr;  size_t cap_htab = 0;  // kTabWords words, then 6 ints of box, per component
 
     // the lattice (after reset) and the last frontiers
     int dim = 0;
@@ -59,6 +48,7 @@ struct Coverage {
     ~Coverage();
     void clear_frontiers() { frontiers_valid = false; npoints = ncomponents = rounds = 0; label.clear(); count.clear(); box.clear(); rep.clear(); sums.clear(); }
     int bind(int dev);
+    DfLattice lattice() const { return DfLattice{dim, n[0], n[1], n[2], origin[0], origin[1], origin[2], step}; }
     bool same_lattice(const DistanceField& df) const;
     int reset(const DistanceField& df);                          // the field's lattice, seen = 0; moves to the field's device
     int set(const unsigned char* seen);                          // host [ngrid]; non-zero = seen

@@ -6,15 +6,13 @@
 // Integration: one thread per lattice point (grid stride) reads its own byte, leaves a seen point alone, else projects the point
 // into the frame (3-D: the nearest pixel's depth; 2-D: a binary search of the sector table) and writes its own byte.
 // Frontiers: count, scan, write over chunks of 2048 points (the lattice indices come out ascending) with the rank grid as a
-// by-product; labels by min-label propagation over the list -- thread r alone writes label[r], values only fall, so the fixed point
-// does not depend on the schedule --; the roots compacted by the same three kernels; the table by integer atomics.
-#include <chrono>
+// by-product; labels, roots and the table's buffers by components.h, the neighbours being the 8 / 26 of the lattice; the table by
+// integer atomics.
 #include <climits>
 #include <cmath>
 #include <cstring>
 #include "cover.h"
 #include "block_ops.h"
-#include "compact.h"
 #include "dfield.h"
 
 namespace gpis {
@@ -22,19 +20,12 @@ namespace gpis {
 namespace {
 
 constexpr int kBlock = Coverage::kBlock;
-constexpr int kItems = Coverage::kItems;
-constexpr int kChunk = Coverage::kChunk;
-constexpr int kTabWords = Coverage::kTabWords;
-static_assert(kBlock == kCompactBlock && kChunk == kCompactChunk, "compact.h's chunks are the coverage's");
+constexpr int kTabWords = kCompTabWords;
 
-struct CovLat {
-    int dim, nx, ny, nz;
-    float ox, oy, oz, step;
-};
 struct CovPose { float v[12]; };
 
 // ---- integration ----------------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(kBlock) cover_depth_kernel(CovLat L, int n, CovPose P, double fx, double fy, double cx, double cy, int W, int H,
+__global__ void __launch_bounds__(kBlock) cover_depth_kernel(DfLattice L, int n, CovPose P, double fx, double fy, double cx, double cy, int W, int H,
                                                              const float* __restrict__ depth, double back_off,
                                                              unsigned char* __restrict__ seen) {
     const int nxy = L.nx * L.ny;
@@ -42,7 +33,7 @@ __global__ void __launch_bounds__(kBlock) cover_depth_kernel(CovLat L, int n, Co
     for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < n; p += gridDim.x * blockDim.x) {
         if (seen[p]) continue;
         const int i = p % L.nx, j = (p / L.nx) % L.ny, k = p / nxy;
-        const float x0 = L.ox + (float)i * L.step, x1 = L.oy + (float)j * L.step, x2 = L.oz + (float)k * L.step;
+        const float x0 = L.ox + (float)i * L.st, x1 = L.oy + (float)j * L.st, x2 = L.oz + (float)k * L.st;
         const double d0 = (double)x0 - t0, d1 = (double)x1 - t1, d2 = (double)x2 - t2;
         const double lx = (double)P.v[3] * d0 + (double)P.v[4] * d1 + (double)P.v[5] * d2;
         const double ly = (double)P.v[6] * d0 + (double)P.v[7] * d1 + (double)P.v[8] * d2;
@@ -55,13 +46,13 @@ __global__ void __launch_bounds__(kBlock) cover_depth_kernel(CovLat L, int n, Co
     }
 }
 
-__global__ void __launch_bounds__(kBlock) cover_scan_kernel(CovLat L, int n, CovPose P, double off0, double off1, const double* __restrict__ q,
+__global__ void __launch_bounds__(kBlock) cover_scan_kernel(DfLattice L, int n, CovPose P, double off0, double off1, const double* __restrict__ q,
                                                             const double* __restrict__ lim, int m, unsigned char* __restrict__ seen) {
     const double t0 = (double)P.v[0], t1 = (double)P.v[1];
     for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < n; p += gridDim.x * blockDim.x) {
         if (seen[p]) continue;
         const int i = p % L.nx, j = p / L.nx;
-        const float x0 = L.ox + (float)i * L.step, x1 = L.oy + (float)j * L.step;
+        const float x0 = L.ox + (float)i * L.st, x1 = L.oy + (float)j * L.st;
         const double d0 = (double)x0 - t0, d1 = (double)x1 - t1;
         const double lx = ((double)P.v[2] * d0 + (double)P.v[3] * d1) - off0;
         const double ly = ((double)P.v[4] * d0 + (double)P.v[5] * d1) - off1;
@@ -82,7 +73,7 @@ __global__ void __launch_bounds__(kBlock) cover_binarise_kernel(unsigned char* _
 // ---- compaction (compact.h): the predicates ---------------------------------------------------------------------------------
 // a frontier point: seen and traversable, with an unseen and traversable axis neighbour inside the lattice
 struct FrontierPred {
-    CovLat L;
+    DfLattice L;
     const unsigned char* seen;
     const float* dist;
     float clearance;
@@ -100,30 +91,17 @@ struct FrontierPred {
         return f;
     }
 };
-// a root of the converged labels
-struct RootPred {
-    const int* label;
-    __device__ bool operator()(int r) const { return label[r] == r; }
-};
 
-// ---- labels ---------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ int ld_label(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void st_label(int* p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-__global__ void __launch_bounds__(kBlock) cover_iota_kernel(int* __restrict__ label, int m) {
-    for (int r = blockIdx.x * blockDim.x + threadIdx.x; r < m; r += gridDim.x * blockDim.x) label[r] = r;
-}
-
-// One round: label[r] = the smallest label among r and its 8 / 26 neighbours, followed down its chain of labels (a label is the
-// rank of a member of the same component and never exceeds the own rank, so the chain falls and ends).
-__global__ void __launch_bounds__(kBlock) cover_label_kernel(CovLat L, const int* __restrict__ list, const int* __restrict__ rank, int m, int* label,
-                                                             int* changed) {
-    const int nxy = L.nx * L.ny;
-    for (int r = blockIdx.x * blockDim.x + threadIdx.x; r < m; r += gridDim.x * blockDim.x) {
+// ---- labels (components.h): the links ---------------------------------------------------------------------------------------
+// the 8 / 26 neighbours of frontier point r, through the rank grid
+struct LatticeLinks {
+    DfLattice L;
+    const int* __restrict__ list;
+    const int* __restrict__ rank;
+    __device__ int operator()(int r, int best, const int* label) const {
+        const int nxy = L.nx * L.ny;
         const int p = list[r];
         const int i = p % L.nx, j = (p / L.nx) % L.ny, k = p / nxy;
-        const int old = ld_label(label + r);
-        int best = old;
         for (int dz = -1; dz <= 1; ++dz) {
             if (k + dz < 0 || k + dz >= L.nz) continue;
             for (int dy = -1; dy <= 1; ++dy) {
@@ -135,14 +113,9 @@ __global__ void __launch_bounds__(kBlock) cover_label_kernel(CovLat L, const int
                 }
             }
         }
-        for (;;) {
-            const int t = ld_label(label + best);
-            if (t >= best) break;
-            best = t;
-        }
-        if (best < old) { st_label(label + r, best); *changed = 1; }
+        return best;
     }
-}
+};
 
 // ---- the table ------------------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(kBlock) cover_tab_init_kernel(unsigned long long* __restrict__ tab, int* __restrict__ box, int nc) {
@@ -158,7 +131,7 @@ __global__ void __launch_bounds__(kBlock) cover_tab_init_kernel(unsigned long lo
 // count, integer sums and box of each component; the points' labels as lattice indices.  The list ascends and components are
 // compact, so the 64 points of a wavefront mostly share one component: such a wavefront reduces its integers through lane
 // shuffles and sends one atomic per word instead of 64 to the same address (integers: the order changes nothing).
-__global__ void __launch_bounds__(kBlock) cover_tab_sum_kernel(CovLat L, const int* __restrict__ list, const int* __restrict__ label,
+__global__ void __launch_bounds__(kBlock) cover_tab_sum_kernel(DfLattice L, const int* __restrict__ list, const int* __restrict__ label,
                                                                const int* __restrict__ cidx, int m, unsigned long long* tab, int* box,
                                                                int* __restrict__ plabel) {
     const int nxy = L.nx * L.ny;
@@ -208,7 +181,7 @@ __global__ void __launch_bounds__(kBlock) cover_tab_sum_kernel(CovLat L, const i
 }
 
 // the squared distance of point r to its component's centroid, in double: (i - si / n)^2 + (j - sj / n)^2 (+ (k - sk / n)^2)
-__device__ __forceinline__ double cover_d2(const CovLat& L, int p, const unsigned long long* t) {
+__device__ __forceinline__ double cover_d2(const DfLattice& L, int p, const unsigned long long* t) {
     const int nxy = L.nx * L.ny;
     const double cnt = (double)t[0];
     const double di = (double)(p % L.nx) - (double)t[1] / cnt, dj = (double)((p / L.nx) % L.ny) - (double)t[2] / cnt;
@@ -223,7 +196,7 @@ __device__ __forceinline__ double cover_d2(const CovLat& L, int p, const unsigne
 // STAGE 0: t[4] = the smallest distance's bits (non-negative doubles order as their bits), one atomic per wavefront where its
 // points share a component; STAGE 1: t[5] = the smallest rank among the points at that distance
 template <int STAGE>
-__global__ void __launch_bounds__(kBlock) cover_tab_rep_kernel(CovLat L, const int* __restrict__ list, const int* __restrict__ label,
+__global__ void __launch_bounds__(kBlock) cover_tab_rep_kernel(DfLattice L, const int* __restrict__ list, const int* __restrict__ label,
                                                                const int* __restrict__ cidx, int m, unsigned long long* tab) {
     for (int r0 = blockIdx.x * blockDim.x; r0 < m; r0 += gridDim.x * blockDim.x) {
         const int r = r0 + threadIdx.x;
@@ -266,14 +239,6 @@ __global__ void __launch_bounds__(kBlock) cover_restrict_kernel(const unsigned c
     }
 }
 
-inline CovLat lat_of(const Coverage& c) {
-    return CovLat{c.dim, c.n[0], c.n[1], c.n[2], c.origin[0], c.origin[1], c.origin[2], c.step};
-}
-
-double ms_since(std::chrono::steady_clock::time_point t0) {
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-}
-
 }  // namespace
 
 Coverage::Coverage() {
@@ -288,16 +253,12 @@ int Coverage::bind(int dev) {
     {
         DeviceScope ds(device);
         if (own) (void)hipStreamSynchronize(own);
-        for (void* p : {(void*)d_seen, (void*)d_rank, (void*)d_bcount, (void*)d_list, (void*)d_label, (void*)d_plabel, (void*)d_cidx,
-                        (void*)d_roots, (void*)d_tab, (void*)d_box, (void*)d_sector, (void*)d_depth, (void*)d_word})
-            (void)hipFree(p);
-        if (h_word) (void)hipHostFree(h_word);
-        if (h_tab) (void)hipHostFree(h_tab);
+        for (void* p : {(void*)d_seen, (void*)d_rank, (void*)d_plabel, (void*)d_sector, (void*)d_depth}) (void)hipFree(p);
+        comp.release();
         if (own) (void)hipStreamDestroy(own);
     }
-    d_seen = nullptr; d_rank = d_bcount = d_list = d_label = d_plabel = d_cidx = d_roots = d_box = d_word = nullptr; d_tab = nullptr;
-    d_sector = nullptr; d_depth = nullptr; h_word = nullptr; h_tab = nullptr; own = nullptr;
-    cap_n = cap_rank = cap_blocks = cap_m = cap_c = cap_beams = cap_pix = cap_htab = 0;
+    d_seen = nullptr; d_rank = d_plabel = nullptr; d_sector = nullptr; d_depth = nullptr; own = nullptr;
+    cap_n = cap_rank = cap_plabel = cap_beams = cap_pix = 0;
     clear_frontiers();
     has_lattice = false; dim = 0; ngrid = 0; frames = 0;
     device = dev;
@@ -319,8 +280,6 @@ int Coverage::reset(const DistanceField& df) {
     if (int rc = bind(df.device)) return rc;
     clear_frontiers();
     has_lattice = false;
-    if (!d_word) GPIS_HIP(hipMalloc((void**)&d_word, sizeof(int) * 4));
-    if (!h_word) GPIS_HIP(hipHostMalloc((void**)&h_word, sizeof(int) * 4));
     if (int rc = grow(d_seen, cap_n, (size_t)df.ngrid)) return rc;
     GPIS_HIP(hipMemsetAsync(d_seen, 0, (size_t)df.ngrid, own));
     GPIS_HIP(hipStreamSynchronize(own));
@@ -353,7 +312,7 @@ int Coverage::integrate(const SensorFrame& f, const float* in, const float* pose
     if (f.geo.dim != dim) return GPIS_ERR_ARG;
     const auto t0 = std::chrono::steady_clock::now();
     clear_frontiers();
-    const CovLat L = lat_of(*this);
+    const DfLattice L = lattice();
     CovPose P;
     for (int k = 0; k < 12; ++k) P.v[k] = k < (dim == 3 ? 12 : 6) ? pose[k] : 0.f;
     if (dim == 3) {
@@ -388,67 +347,27 @@ int Coverage::frontiers(const DistanceField& df, const CoverOpts& o, hipStream_t
     if (int rc = cover_check_opts(o)) return rc;
     const auto t0 = std::chrono::steady_clock::now();
     clear_frontiers();
-    const CovLat L = lat_of(*this);
-    const int np = (int)ngrid, nb = (np + kChunk - 1) / kChunk;
+    const DfLattice L = lattice();
+    const int np = (int)ngrid;
     if (int rc = grow(d_rank, cap_rank, (size_t)np)) return rc;
-    if (int rc = grow(d_bcount, cap_blocks, (size_t)nb + 1)) return rc;
-
-    // the per-point buffers grow together, once the count is known (the lists are at least one element long)
+    if (int rc = comp.reserve(np)) return rc;
     auto grow_lists = [&](int m) -> int {
-        const size_t need = (size_t)std::max(1, m);
-        if (need <= cap_m) return GPIS_OK;
-        for (void* p : {(void*)d_list, (void*)d_label, (void*)d_plabel, (void*)d_cidx, (void*)d_roots}) (void)hipFree(p);
-        d_list = d_label = d_plabel = d_cidx = d_roots = nullptr; cap_m = 0;
-        for (int** p : {&d_list, &d_label, &d_plabel, &d_cidx, &d_roots}) GPIS_HIP(hipMalloc((void**)p, sizeof(int) * need));
-        cap_m = need;
-        return GPIS_OK;
+        if (int rc = comp.grow_lists(m)) return rc;
+        return grow(d_plabel, cap_plabel, (size_t)std::max(1, m));
     };
     int m = 0;
-    if (int rc = compact_run(FrontierPred{L, d_seen, df.d_dist, o.clearance}, np, d_bcount, h_word, &m, d_list, d_rank, s, grow_lists))
-        return rc;
+    const FrontierPred pred{L, d_seen, df.d_dist, o.clearance};
+    if (int rc = compact_run(pred, np, comp.d_bcount, comp.h_word, &m, comp.d_list, d_rank, s, grow_lists)) return rc;
 
     long long done = 0;
     int nc = 0;
     if (m > 0) {
-        hipLaunchKernelGGL(cover_iota_kernel, dim3(grid_for(m)), dim3(kBlock), 0, s, d_label, m);
-        GPIS_HIP(hipGetLastError());
-        const long long cap = o.max_rounds > 0 ? (long long)o.max_rounds : (long long)m + 1;
-        const int every = std::max(1, std::min(check_every, (int)kMaxBatch));
-        long long round = 0;
-        bool conv = false;
-        while (!conv && round < cap) {
-            const int nbatch = (int)std::min((long long)every, cap - round);
-            for (int b = 0; b < nbatch; ++b) {
-                if (b == nbatch - 1) GPIS_HIP(hipMemsetAsync(d_word, 0, sizeof(int), s));   // (the batch's last round decides)
-                hipLaunchKernelGGL(cover_label_kernel, dim3(grid_for(m)), dim3(kBlock), 0, s, L, d_list, d_rank, m, d_label, d_word);
-                GPIS_HIP(hipGetLastError());
-            }
-            GPIS_HIP(hipMemcpyAsync(h_word, d_word, sizeof(int), hipMemcpyDeviceToHost, s));
-            GPIS_HIP(hipStreamSynchronize(s));
-            round += nbatch;
-            conv = h_word[0] == 0;
-        }
-        if (!conv) return GPIS_ERR_LIMIT;
-        done = round;
-
-        // the roots, ascending: component c = the c-th smallest label
-        const int nbm = (m + kChunk - 1) / kChunk;
-        if (int rc = grow(d_bcount, cap_blocks, (size_t)std::max(nb, nbm) + 1)) return rc;
-        auto no_grow = [&](int) -> int { return GPIS_OK; };       // (at most m roots: d_roots holds them)
-        if (int rc = compact_run(RootPred{d_label}, m, d_bcount, h_word, &nc, d_roots, d_cidx, s, no_grow)) return rc;
-        if ((size_t)nc > cap_c) {
-            (void)hipFree(d_tab); (void)hipFree(d_box); d_tab = nullptr; d_box = nullptr; cap_c = 0;
-            GPIS_HIP(hipMalloc((void**)&d_tab, sizeof(unsigned long long) * kTabWords * (size_t)nc));
-            GPIS_HIP(hipMalloc((void**)&d_box, sizeof(int) * 6 * (size_t)nc));
-            cap_c = (size_t)nc;
-        }
-        const size_t hneed = (size_t)nc * (kTabWords + 3);
-        if (hneed > cap_htab) {
-            if (h_tab) (void)hipHostFree(h_tab);
-            h_tab = nullptr; cap_htab = 0;
-            GPIS_HIP(hipHostMalloc((void**)&h_tab, sizeof(unsigned long long) * hneed));
-            cap_htab = hneed;
-        }
+        done = comp.label(LatticeLinks{L, comp.d_list, d_rank}, m, o.max_rounds, s);
+        if (done < 0) return (int)done;
+        if (int rc = comp.roots(m, &nc, s)) return rc;
+        if (int rc = comp.grow_table(nc)) return rc;
+        int *const d_list = comp.d_list, *const d_label = comp.d_label, *const d_cidx = comp.d_cidx, *const d_box = comp.d_box;
+        unsigned long long* const d_tab = comp.d_tab;
         hipLaunchKernelGGL(cover_tab_init_kernel, dim3(grid_for(nc)), dim3(kBlock), 0, s, d_tab, d_box, nc);
         GPIS_HIP(hipGetLastError());
         hipLaunchKernelGGL(cover_tab_sum_kernel, dim3(grid_for(m)), dim3(kBlock), 0, s, L, d_list, d_label, d_cidx, m, d_tab, d_box, d_plabel);
@@ -457,14 +376,12 @@ int Coverage::frontiers(const DistanceField& df, const CoverOpts& o, hipStream_t
         GPIS_HIP(hipGetLastError());
         hipLaunchKernelGGL(cover_tab_rep_kernel<1>, dim3(grid_for(m)), dim3(kBlock), 0, s, L, d_list, d_label, d_cidx, m, d_tab);
         GPIS_HIP(hipGetLastError());
-        hipLaunchKernelGGL(cover_tab_final_kernel, dim3(grid_for(nc)), dim3(kBlock), 0, s, d_list, d_roots, nc, d_tab);
+        hipLaunchKernelGGL(cover_tab_final_kernel, dim3(grid_for(nc)), dim3(kBlock), 0, s, d_list, comp.d_roots, nc, d_tab);
         GPIS_HIP(hipGetLastError());
-        int* h_box = (int*)(h_tab + (size_t)nc * kTabWords);
-        GPIS_HIP(hipMemcpyAsync(h_tab, d_tab, sizeof(unsigned long long) * kTabWords * (size_t)nc, hipMemcpyDeviceToHost, s));
-        GPIS_HIP(hipMemcpyAsync(h_box, d_box, sizeof(int) * 6 * (size_t)nc, hipMemcpyDeviceToHost, s));
-        GPIS_HIP(hipStreamSynchronize(s));
+        const int* h_box;
+        if (int rc = comp.fetch_table(nc, &h_box, s)) return rc;
         for (int c = 0; c < nc; ++c) {
-            const unsigned long long* t = h_tab + (size_t)c * kTabWords;
+            const unsigned long long* t = comp.h_tab + (size_t)c * kTabWords;
             if ((long long)t[0] < (long long)o.min_size) continue;
             label.push_back((int)t[6]); count.push_back((int)t[0]); rep.push_back((int)t[5]);
             for (int a = 0; a < 3; ++a) sums.push_back((long long)t[1 + a]);

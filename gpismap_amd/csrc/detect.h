@@ -9,6 +9,7 @@
 #include <cstdint>
 #include <vector>
 #include "dev_common.h"
+#include "components.h"
 #include "detect_host.h"
 #include "frame.h"
 #include "track.h"
@@ -21,12 +22,9 @@ struct Obstacles;
 
 struct Detector {
     static constexpr int kBlock = 256;
-    static constexpr int kMaxBatch = 64;         // labelling rounds per read-back (check_every)
-    static constexpr int kTabWords = 8;          // 64-bit words per component: count, centre bits (3), r2 bits, label, unused (2)
 
     int device = -1;
     Tracker trk;                                 // the frame's set-up (its stream is the detector's own)
-    int check_every = 4;                         // schedule (the results do not depend on it)
     bool profile = false;                        // synchronise at every stage's end, so that the stage times are the stages'
 
     // grow-only device buffers over the sample grid (beams; 3-D: W / stride x H / stride, column-major) ...
@@ -35,17 +33,10 @@ struct Detector {
     unsigned char* d_flag = nullptr;             // 1: foreign
     int* d_rank = nullptr;                       // position in the list, -1 elsewhere
     int* d_limg = nullptr;        size_t cap_g = 0;   // the label image: the component's smallest grid index, -1 elsewhere
-    int* d_bcount = nullptr;      size_t cap_blocks = 0;
-    // ... and over the foreign samples
-    int* d_list = nullptr;                       // grid index, ascending
-    int* d_label = nullptr;                      // label as a rank
-    int* d_cidx = nullptr;                       // component index of a root (-1 elsewhere)
-    int* d_roots = nullptr;       size_t cap_m = 0;
-    unsigned long long* d_tab = nullptr;
-    unsigned* d_box = nullptr;    size_t cap_c = 0;   // per component: the keys of the least (3) and greatest (3) coordinates
-    int* d_word = nullptr;
-    int* h_word = nullptr;
-    unsigned long long* h_tab = nullptr;  size_t cap_htab = 0;
+    // ... and over the foreign samples (comp.d_list: grid indices), their components and the table (components.h), per component
+    // the words count, centre bits (3), r2 bits, label, unused (2) and the keys of the least and greatest coordinates; the
+    // schedule is comp.check_every
+    Components<unsigned> comp;
 
     // the last result
     bool valid = false;

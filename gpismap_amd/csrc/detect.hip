@@ -6,19 +6,17 @@
 // coverage mask, the byte of the lattice point nearest x -- per axis min((int)floorf((x - o) / step + 0.5f), n - 1), in float --
 // is set.  Neighbours: beams q - 1, q + 1 (no wrap from the last beam to the first); in 3-D the 8 neighbours on the strided grid.
 // Two neighbouring foreign samples are linked iff e_0 e_0 + e_1 e_1 (+ e_2 e_2) <= link * link with e_a = (double)x_a -
-// (double)y_a, summed left to right.  Labels: min-label propagation over the list with pointer jumping -- thread r alone writes
-// label[r], values only fall, so the fixed point does not depend on the schedule.  The table: a count (integer sum), per axis the
-// least and greatest coordinate (integer min / max of an order-preserving key of the float), the centre 0.5 * ((double)lo +
-// (double)hi), r2 = the greatest sum_a ((double)x_a - c_a)^2 (integer max on the bits of the non-negative double).  No
-// floating-point atomics.  Every double expression is written in the order tests/detect_ref.py evaluates it; the build does not
-// contract, so the bits agree.
+// (double)y_a, summed left to right.  Labels, roots and the table's buffers: components.h.  The table: a count (integer sum), per
+// axis the least and greatest coordinate (integer min / max of an order-preserving key of the float), the centre 0.5 *
+// ((double)lo + (double)hi), r2 = the greatest sum_a ((double)x_a - c_a)^2 (integer max on the bits of the non-negative double).
+// No floating-point atomics.  Every double expression is written in the order tests/detect_ref.py evaluates it; the build does
+// not contract, so the bits agree.
 #include <chrono>
 #include <climits>
 #include <cmath>
 #include <cstring>
 #include "detect.h"
 #include "block_ops.h"
-#include "compact.h"
 #include "cover.h"
 #include "dfield.h"
 #include "obst.h"
@@ -31,8 +29,7 @@ static_assert(kDetectMaxBalls == Obstacles::kMax, "detect_host.h's cap is the se
 namespace {
 
 constexpr int kBlock = Detector::kBlock;
-constexpr int kTabWords = Detector::kTabWords;
-static_assert(kBlock == kCompactBlock, "compact.h's block is the detector's");
+constexpr int kTabWords = kCompTabWords;
 
 struct DetPose { float R[9], t[3]; };
 struct DetGrid { int g, gh, gw; };             // samples, rows and columns of the grid (2-D: gh = gw = 0)
@@ -72,19 +69,8 @@ struct ForeignPred {
     const unsigned char* flag;
     __device__ bool operator()(int q) const { return flag[q] != 0; }
 };
-struct RootPred {
-    const int* label;
-    __device__ bool operator()(int r) const { return label[r] == r; }
-};
 
-// ---- labels -------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ int ld_label(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void st_label(int* p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-__global__ void __launch_bounds__(kBlock) detect_iota_kernel(int* __restrict__ label, int m) {
-    for (int r = blockIdx.x * blockDim.x + threadIdx.x; r < m; r += gridDim.x * blockDim.x) label[r] = r;
-}
-
+// ---- labels (components.h): the links -------------------------------------------------------------------------------------------
 template <int D>
 __device__ __forceinline__ bool det_linked(const float* __restrict__ x, int q, int p, double link2) {
     double s = 0.0;
@@ -96,14 +82,16 @@ __device__ __forceinline__ bool det_linked(const float* __restrict__ x, int q, i
     return s <= link2;
 }
 
-// One round: label[r] = the smallest label among r and its linked neighbours, followed down its chain of labels.
+// the grid neighbours of foreign sample r (2-D: beams q - 1, q + 1; 3-D: the 8 of the strided grid) whose world points lie within link
 template <int D>
-__global__ void __launch_bounds__(kBlock) detect_label_kernel(DetGrid G, const int* __restrict__ list, const int* __restrict__ rank,
-                                                              const float* __restrict__ x, double link2, int m, int* label, int* changed) {
-    for (int r = blockIdx.x * blockDim.x + threadIdx.x; r < m; r += gridDim.x * blockDim.x) {
+struct GridLinks {
+    DetGrid G;
+    const int* __restrict__ list;
+    const int* __restrict__ rank;
+    const float* __restrict__ x;
+    double link2;
+    __device__ int operator()(int r, int best, const int* label) const {
         const int q = list[r];
-        const int old = ld_label(label + r);
-        int best = old;
         if (D == 2) {
             for (int dq = -1; dq <= 1; dq += 2) {
                 const int p = q + dq;
@@ -123,14 +111,9 @@ __global__ void __launch_bounds__(kBlock) detect_label_kernel(DetGrid G, const i
                 }
             }
         }
-        for (;;) {
-            const int t = ld_label(label + best);
-            if (t >= best) break;
-            best = t;
-        }
-        if (best < old) { st_label(label + r, best); *changed = 1; }
+        return best;
     }
-}
+};
 
 // ---- the table ----------------------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(kBlock) detect_tab_init_kernel(unsigned long long* __restrict__ tab, unsigned* __restrict__ box, int nc) {
@@ -238,10 +221,6 @@ __global__ void __launch_bounds__(kBlock) detect_tab_r2_kernel(const int* __rest
     }
 }
 
-double ms_since(std::chrono::steady_clock::time_point t0) {
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-}
-
 }  // namespace
 
 Detector::Detector() { (void)hipGetDevice(&device); }
@@ -253,15 +232,11 @@ int Detector::bind(int dev) {
     {
         DeviceScope ds(device);
         if (trk.own) (void)hipStreamSynchronize(trk.own);
-        for (void* p : {(void*)d_x, (void*)d_d, (void*)d_flag, (void*)d_rank, (void*)d_limg, (void*)d_bcount, (void*)d_list, (void*)d_label,
-                        (void*)d_cidx, (void*)d_roots, (void*)d_tab, (void*)d_box, (void*)d_word})
-            (void)hipFree(p);
-        if (h_word) (void)hipHostFree(h_word);
-        if (h_tab) (void)hipHostFree(h_tab);
+        for (void* p : {(void*)d_x, (void*)d_d, (void*)d_flag, (void*)d_rank, (void*)d_limg}) (void)hipFree(p);
+        comp.release();
     }
-    d_x = d_d = nullptr; d_flag = nullptr; d_rank = d_limg = d_bcount = d_list = d_label = d_cidx = d_roots = d_word = nullptr;
-    d_tab = nullptr; d_box = nullptr; h_word = nullptr; h_tab = nullptr;
-    cap_g = cap_blocks = cap_m = cap_c = cap_htab = 0;
+    d_x = d_d = nullptr; d_flag = nullptr; d_rank = d_limg = nullptr;
+    cap_g = 0;
     clear_result();
     tracks.reset();
     device = dev;
@@ -303,8 +278,6 @@ int Detector::detect(const DistanceField& df, const Coverage* cover, const Track
     const long long G = dm == 3 ? (long long)gww * ghh : n;
     lap(&setup_ms);
 
-    if (!d_word) GPIS_HIP(hipMalloc((void**)&d_word, sizeof(int) * 4));
-    if (!h_word) GPIS_HIP(hipHostMalloc((void**)&h_word, sizeof(int) * 4));
     const size_t ng = (size_t)std::max(1ll, G);
     if (ng > cap_g) {
         for (void* p : {(void*)d_x, (void*)d_d, (void*)d_flag, (void*)d_rank, (void*)d_limg}) (void)hipFree(p);
@@ -316,8 +289,7 @@ int Detector::detect(const DistanceField& df, const Coverage* cover, const Track
         GPIS_HIP(hipMalloc((void**)&d_limg, sizeof(int) * ng));
         cap_g = ng;
     }
-    const int nb = (int)((G + kCompactChunk - 1) / kCompactChunk);
-    if (int rc = grow(d_bcount, cap_blocks, (size_t)nb + 1)) return rc;
+    if (int rc = comp.reserve(G)) return rc;
 
     GPIS_HIP(hipMemsetAsync(d_x, 0, sizeof(float) * (size_t)dm * ng, s));
     GPIS_HIP(hipMemsetD32Async((hipDeviceptr_t)d_d, 0x7fc00000, ng, s));
@@ -338,17 +310,9 @@ int Detector::detect(const DistanceField& df, const Coverage* cover, const Track
     }
     lap(&flag_ms);
 
-    auto grow_lists = [&](int mm) -> int {
-        const size_t need = (size_t)std::max(1, mm);
-        if (need <= cap_m) return GPIS_OK;
-        for (void* p : {(void*)d_list, (void*)d_label, (void*)d_cidx, (void*)d_roots}) (void)hipFree(p);
-        d_list = d_label = d_cidx = d_roots = nullptr; cap_m = 0;
-        for (int** p : {&d_list, &d_label, &d_cidx, &d_roots}) GPIS_HIP(hipMalloc((void**)p, sizeof(int) * need));
-        cap_m = need;
-        return GPIS_OK;
-    };
+    auto grow_lists = [&](int mm) -> int { return comp.grow_lists(mm); };
     int mf = 0;
-    if (int rc = compact_run(ForeignPred{d_flag}, (int)G, d_bcount, h_word, &mf, d_list, d_rank, s, grow_lists)) return rc;
+    if (int rc = compact_run(ForeignPred{d_flag}, (int)G, comp.d_bcount, comp.h_word, &mf, comp.d_list, d_rank, s, grow_lists)) return rc;
     lap(&compact_ms);
 
     const DetGrid GG{(int)G, ghh, gww};
@@ -356,49 +320,16 @@ int Detector::detect(const DistanceField& df, const Coverage* cover, const Track
     long long done = 0;
     int nc = 0;
     if (mf > 0) {
-        hipLaunchKernelGGL(detect_iota_kernel, dim3(grid_for(mf)), dim3(kBlock), 0, s, d_label, mf);
-        GPIS_HIP(hipGetLastError());
-        const long long cap = o.max_rounds > 0 ? (long long)o.max_rounds : (long long)mf + 1;
-        const int every = std::max(1, std::min(check_every, (int)kMaxBatch));
-        long long round = 0;
-        bool conv = false;
-        while (!conv && round < cap) {
-            const int nbatch = (int)std::min((long long)every, cap - round);
-            for (int b = 0; b < nbatch; ++b) {
-                if (b == nbatch - 1) GPIS_HIP(hipMemsetAsync(d_word, 0, sizeof(int), s));   // (the batch's last round decides)
-                if (dm == 3)
-                    hipLaunchKernelGGL(detect_label_kernel<3>, dim3(grid_for(mf)), dim3(kBlock), 0, s, GG, d_list, d_rank, d_x, link2, mf,
-                                       d_label, d_word);
-                else
-                    hipLaunchKernelGGL(detect_label_kernel<2>, dim3(grid_for(mf)), dim3(kBlock), 0, s, GG, d_list, d_rank, d_x, link2, mf,
-                                       d_label, d_word);
-                GPIS_HIP(hipGetLastError());
-            }
-            GPIS_HIP(hipMemcpyAsync(h_word, d_word, sizeof(int), hipMemcpyDeviceToHost, s));
-            GPIS_HIP(hipStreamSynchronize(s));
-            round += nbatch;
-            conv = h_word[0] == 0;
-        }
-        if (!conv) return GPIS_ERR_LIMIT;
-        done = round;
+        int *const d_list = comp.d_list, *const d_label = comp.d_label, *const d_cidx = comp.d_cidx, *const d_roots = comp.d_roots;
+        done = dm == 3 ? comp.label(GridLinks<3>{GG, d_list, d_rank, d_x, link2}, mf, o.max_rounds, s)
+                       : comp.label(GridLinks<2>{GG, d_list, d_rank, d_x, link2}, mf, o.max_rounds, s);
+        if (done < 0) return (int)done;
         lap(&label_ms);
 
-        // the roots, ascending: component c = the c-th smallest label
-        auto no_grow = [&](int) -> int { return GPIS_OK; };       // (at most mf roots: d_roots holds them)
-        if (int rc = compact_run(RootPred{d_label}, mf, d_bcount, h_word, &nc, d_roots, d_cidx, s, no_grow)) return rc;
-        if ((size_t)nc > cap_c) {
-            (void)hipFree(d_tab); (void)hipFree(d_box); d_tab = nullptr; d_box = nullptr; cap_c = 0;
-            GPIS_HIP(hipMalloc((void**)&d_tab, sizeof(unsigned long long) * kTabWords * (size_t)nc));
-            GPIS_HIP(hipMalloc((void**)&d_box, sizeof(unsigned) * 6 * (size_t)nc));
-            cap_c = (size_t)nc;
-        }
-        const size_t hneed = (size_t)nc * (kTabWords + 3);
-        if (hneed > cap_htab) {
-            if (h_tab) (void)hipHostFree(h_tab);
-            h_tab = nullptr; cap_htab = 0;
-            GPIS_HIP(hipHostMalloc((void**)&h_tab, sizeof(unsigned long long) * hneed));
-            cap_htab = hneed;
-        }
+        if (int rc = comp.roots(mf, &nc, s)) return rc;
+        if (int rc = comp.grow_table(nc)) return rc;
+        unsigned long long* const d_tab = comp.d_tab;
+        unsigned* const d_box = comp.d_box;
         hipLaunchKernelGGL(detect_tab_init_kernel, dim3(grid_for(nc)), dim3(kBlock), 0, s, d_tab, d_box, nc);
         GPIS_HIP(hipGetLastError());
         if (dm == 3) {
@@ -411,13 +342,11 @@ int Detector::detect(const DistanceField& df, const Coverage* cover, const Track
             hipLaunchKernelGGL(detect_tab_r2_kernel<2>, dim3(grid_for(mf)), dim3(kBlock), 0, s, d_list, d_label, d_cidx, d_x, mf, d_tab);
         }
         GPIS_HIP(hipGetLastError());
-        unsigned* h_box = (unsigned*)(h_tab + (size_t)nc * kTabWords);
-        GPIS_HIP(hipMemcpyAsync(h_tab, d_tab, sizeof(unsigned long long) * kTabWords * (size_t)nc, hipMemcpyDeviceToHost, s));
-        GPIS_HIP(hipMemcpyAsync(h_box, d_box, sizeof(unsigned) * 6 * (size_t)nc, hipMemcpyDeviceToHost, s));
-        GPIS_HIP(hipStreamSynchronize(s));
+        const unsigned* h_box;
+        if (int rc = comp.fetch_table(nc, &h_box, s)) return rc;
         c_label.resize(nc); c_count.resize(nc); c_box.assign((size_t)nc * 6, 0.f); c_centre.assign((size_t)nc * 3, 0.0); c_r2.resize(nc);
         for (int c = 0; c < nc; ++c) {
-            const unsigned long long* tt = h_tab + (size_t)c * kTabWords;
+            const unsigned long long* tt = comp.h_tab + (size_t)c * kTabWords;
             c_count[c] = (int)tt[0]; c_label[c] = (int)tt[5];
             std::memcpy(&c_r2[c], &tt[4], sizeof(double));
             for (int a = 0; a < dm; ++a) {

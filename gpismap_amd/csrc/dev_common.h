@@ -15,6 +15,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <algorithm>
+#include <chrono>
 #include <cstdint>
 #include <cstdio>
 
@@ -79,6 +80,11 @@ constexpr int kGridCap = 2048;
 // blocks of a grid-stride launch over n elements: at least one, at most cap
 inline int grid_for(long long n, int block = 256, long long cap = kGridCap) {
     return (int)std::max(1ll, std::min(cap, (n + block - 1) / block));
+}
+
+// host wall time since t0, in milliseconds
+inline double ms_since(std::chrono::steady_clock::time_point t0) {
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 }
 
 inline long long pow2_at_least(long long n) {

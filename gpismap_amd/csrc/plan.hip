@@ -337,7 +337,7 @@ int Planner::solve(const DistanceField& df, const float* goals, int ngoals, cons
     GPIS_HIP(hipStreamSynchronize(s));
     dim = dm; ngrid = np; step = df.step;
     for (int a = 0; a < 3; ++a) { n[a] = a < dm ? df.n[a] : 1; origin[a] = a < dm ? df.origin[a] : 0.f; }
-    cnt = plan_host::counters(st, kStatFree, ngoals, done, plan_host::ms_since(t0));
+    cnt = plan_host::counters(st, kStatFree, ngoals, done, ms_since(t0));
     valid = true;
     return GPIS_OK;
 }

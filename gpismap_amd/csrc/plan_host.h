@@ -45,10 +45,6 @@ inline PlanCounters counters(const unsigned long long* st, int free_word, long l
     return c;
 }
 
-inline double ms_since(std::chrono::steady_clock::time_point t0) {
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-}
-
 // paths(): the m starts (host, `width` floats each) go to the device, count_walk() leaves the path lengths in d_off, the scan
 // turns them into offsets, grow_points(total) makes room (int: GPIS_OK or an error), write_walk() stores the points.  The start
 // buffers grow exactly to the need and never shrink.  Synchronises `s`.

@@ -442,7 +442,7 @@ int PosePlanner::solve(const DistanceField& df, const Footprint& body, const dou
                        BodyArgs{body.d_tab, body.m}, (const double*)d_head, o.clearance, o.margin, o.gain, d_c, d_cost, d_policy);
     GPIS_HIP(hipGetLastError());
     GPIS_HIP(hipStreamSynchronize(s));              // (the field and the footprint are not read after this point)
-    setup_ms = plan_host::ms_since(t1);
+    setup_ms = ms_since(t1);
     hipLaunchKernelGGL(pplan_goal_kernel, dim3(grid_for(ngoals)), dim3(kBlock), 0, s, L, (const float*)d_goals, ngoals, (const float*)d_c, d_cost,
                        tnx, d_flags, d_stat);
     GPIS_HIP(hipGetLastError());
@@ -465,7 +465,7 @@ int PosePlanner::solve(const DistanceField& df, const Footprint& body, const dou
     GPIS_HIP(hipStreamSynchronize(s));
     H = nh; nstates = ns; step = df.step;
     for (int a = 0; a < 2; ++a) { n[a] = df.n[a]; origin[a] = df.origin[a]; }
-    cnt = plan_host::counters(st, kStatFree, ngoals, done, plan_host::ms_since(t0));
+    cnt = plan_host::counters(st, kStatFree, ngoals, done, ms_since(t0));
     valid = true;
     return GPIS_OK;
 }

@@ -311,7 +311,7 @@ int TimePlanner::solve(const DistanceField& df, const Obstacles* ob, const float
     nx = gx; ny = gy; S = H; n = nb; ns = pts; step = df.step; origin[0] = df.origin[0]; origin[1] = df.origin[1];
     opts = o; t_begin = tb;
     goals_given = ngoals; launches = nl;
-    solve_ms = plan_host::ms_since(t0);
+    solve_ms = ms_since(t0);
     kept = o.keep_cost != 0;
     valid = true;
     return GPIS_OK;

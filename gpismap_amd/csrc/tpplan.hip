@@ -431,7 +431,7 @@ int TimePosePlanner::solve(const DistanceField& df, const Obstacles* ob, const F
     nx = gx; ny = gy; H = nh; S = Sn; n = nb; mb = nbody; ns = states; step = df.step; origin[0] = df.origin[0]; origin[1] = df.origin[1];
     opts = o; t_begin = tb;
     goals_given = ngoals; launches = Sn;
-    solve_ms = plan_host::ms_since(t0);
+    solve_ms = ms_since(t0);
     kept = o.keep_cost != 0;
     valid = true;
     return GPIS_OK;

@@ -11,7 +11,6 @@
 // popcount into a per-wavefront LDS word and ends the tile with one integer atomic per pose.  Integer sums: the schedule does
 // not reach the bits.  An exact early reject skips the divisions: l.z >= the pose's largest valid d' less back_off (3-D), l.l >=
 // the pose's largest lim^2 (2-D); rounding is monotone, so no point the rule accepts is rejected.
-#include <chrono>
 #include <cmath>
 #include <cstring>
 #include "view.h"
@@ -30,11 +29,6 @@ constexpr int kPoints = ViewScorer::kPoints;
 constexpr int kPoseTile = ViewScorer::kPoseTile;
 constexpr int kWaves = kBlock / kWave;
 static_assert(kPoseTile <= kBlock, "one thread per pose of a tile stages its cut and sends its count");
-
-struct ViewLat {
-    int dim, nx, ny, nz;
-    float ox, oy, oz, step;
-};
 
 // ---- prediction -------------------------------------------------------------------------------------------------------------
 // wavefront w of the grid: pose w / wpp, and of that pose's rays tile w % wpp (3-D: the 8 x 8 pixel tile (t / tiles_r, t %
@@ -150,7 +144,7 @@ struct TargetPred {
 
 // ---- the gather ---------------------------------------------------------------------------------------------------------------
 // the kPoints targets of this thread as doubles of their float32 lattice points; ok: the slot lies inside the list
-__device__ __forceinline__ void view_decode(const ViewLat& L, const int* __restrict__ list, int T, double (*x)[3], bool* ok) {
+__device__ __forceinline__ void view_decode(const DfLattice& L, const int* __restrict__ list, int T, double (*x)[3], bool* ok) {
     const int nxy = L.nx * L.ny;
     const int base = blockIdx.x * (kBlock * kPoints);
 #pragma unroll
@@ -159,9 +153,9 @@ __device__ __forceinline__ void view_decode(const ViewLat& L, const int* __restr
         ok[a] = r < T;
         const int p = ok[a] ? list[r] : 0;
         const int i = p % L.nx, j = (p / L.nx) % L.ny, k = p / nxy;
-        x[a][0] = (double)(L.ox + (float)i * L.step);
-        x[a][1] = (double)(L.oy + (float)j * L.step);
-        x[a][2] = (double)(L.oz + (float)k * L.step);
+        x[a][0] = (double)(L.ox + (float)i * L.st);
+        x[a][1] = (double)(L.oy + (float)j * L.st);
+        x[a][2] = (double)(L.oz + (float)k * L.st);
     }
 }
 
@@ -175,7 +169,7 @@ __device__ __forceinline__ void view_flush(const int (*cnt)[kPoseTile], int k0, 
     }
 }
 
-__global__ void __launch_bounds__(kBlock) view_gather_depth_kernel(ViewLat L, const int* __restrict__ list, int T,
+__global__ void __launch_bounds__(kBlock) view_gather_depth_kernel(DfLattice L, const int* __restrict__ list, int T,
                                                                    const float* __restrict__ pose, int m, double fx, double fy, double cx,
                                                                    double cy, int W, int H, const float* __restrict__ pred,
                                                                    const unsigned* __restrict__ dmax, double back_off,
@@ -226,7 +220,7 @@ __global__ void __launch_bounds__(kBlock) view_gather_depth_kernel(ViewLat L, co
     }
 }
 
-__global__ void __launch_bounds__(kBlock) view_gather_scan_kernel(ViewLat L, const int* __restrict__ list, int T,
+__global__ void __launch_bounds__(kBlock) view_gather_scan_kernel(DfLattice L, const int* __restrict__ list, int T,
                                                                   const float* __restrict__ pose, int m, double off0, double off1, int n,
                                                                   const double* __restrict__ q, const double* __restrict__ lim,
                                                                   const int* __restrict__ nvalid, const double* __restrict__ lim2,
@@ -274,10 +268,6 @@ __global__ void __launch_bounds__(kBlock) view_gather_scan_kernel(ViewLat L, con
         __syncthreads();
         view_flush(cnt, k0, nk, gain);
     }
-}
-
-double ms_since(std::chrono::steady_clock::time_point t0) {
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 }
 
 }  // namespace
@@ -420,16 +410,15 @@ int ViewScorer::score(const DistanceField& df, const Coverage& cv, const SensorF
     // 4. the gather (no target: nothing is launched, the gains stay zero)
     t0 = std::chrono::steady_clock::now();
     if (T > 0) {
-        const ViewLat L{cv.dim, cv.n[0], cv.n[1], cv.n[2], cv.origin[0], cv.origin[1], cv.origin[2], cv.step};
         // blocks (x, y): chunk x of the targets against the pose tiles y, y + ny, ...; a short list spreads its tiles over more
         // workgroups (a pose still lies in one tile, so it still gets one atomic per workgroup that meets it)
         const int nbx = (T + kBlock * kPoints - 1) / (kBlock * kPoints), tiles = (m + kPoseTile - 1) / kPoseTile;
         const dim3 nb(nbx, std::max(1, std::min(tiles, kGridCap / nbx)));
         if (dm == 3)
-            hipLaunchKernelGGL(view_gather_depth_kernel, nb, dim3(kBlock), 0, s, L, d_list, T, d_pose, m, (double)f.geo.fx, (double)f.geo.fy,
+            hipLaunchKernelGGL(view_gather_depth_kernel, nb, dim3(kBlock), 0, s, DL, d_list, T, d_pose, m, (double)f.geo.fx, (double)f.geo.fy,
                                (double)f.geo.cx, (double)f.geo.cy, f.geo.width, f.geo.height, d_pred, d_dmax, (double)vo.back_off, d_gain);
         else
-            hipLaunchKernelGGL(view_gather_scan_kernel, nb, dim3(kBlock), 0, s, L, d_list, T, d_pose, m, (double)f.geo.off[0],
+            hipLaunchKernelGGL(view_gather_scan_kernel, nb, dim3(kBlock), 0, s, DL, d_list, T, d_pose, m, (double)f.geo.off[0],
                                (double)f.geo.off[1], (int)n, d_sector, d_sector + M * n, d_nvalid, d_lim2, d_gain);
         GPIS_HIP(hipGetLastError());
     }
